@@ -37,7 +37,7 @@ def _check_config5(c5, n, world):
 
 
 def test_bench_line_contract_and_small_config5():
-    line = _run(["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-other-configs", "--pipeline-files", "300",
+    line = _run(["--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-other-configs", "--pipeline-files", "300",
                  "--config5-images", "700", "--config5-classes", "120"])
     pl = line["pipeline"]
     assert "error" not in pl and pl["h2d_inclusive"]["value"] > 0 and pl["file_inclusive"]["value"] > 0
@@ -65,7 +65,7 @@ def test_bench_line_contract_and_small_config5():
 
 
 def test_bench_two_self_launched_ranks_share_the_gpu_over_gloo():
-    line = _run(["--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1", "--no-op-events",
+    line = _run(["--full", "--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1", "--no-op-events",
                  "--config5-images", "701", "--config5-classes", "120"])
     assert line["n_gpus"] == 2 and line["config"]["global_batch"] == 512
     assert len(line["per_rank_faces_per_s"]) == 2 and line["allgather_ms"] > 0
@@ -83,7 +83,7 @@ def test_bench_eight_ranks_lfw_shards_with_pad_rows_equal_the_single_rank_extrac
     shard 1142 rows + 4 pad rows) -- with the ranks sharing this box's one GPU over gloo: every call site of the 8-GPU job
     (torchrun env, shard ranges, the ONE all-gather, identification on every rank) and the gathered matrix row for row against
     rank 0's single-rank extraction of all 9164 photos."""
-    line = _run(["--gpus", "8", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--no-op-events", "--no-sustained"], timeout=1500)
+    line = _run(["--full", "--gpus", "8", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--no-op-events", "--no-sustained"], timeout=1500)
     assert line["n_gpus"] == 8 and len(line["per_rank_faces_per_s"]) == 8
     c5 = line["config5"]
     _check_config5(c5, 9164, 8)
@@ -96,7 +96,7 @@ def test_side_configs_carry_a_per_kernel_view():
     """other_configs[ResNet-50 bf16] and other_configs[age / gender] carry `kernels` (one row per kernel instantiation,
     named by the launchers' own routing) and the dominant kernel as a roofline object of the headline's shape; the strict-fp32 ResNet
     carries `traffic` once a profile of it is committed."""
-    line = _run(["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-pipeline", "--no-latency", "--no-config5", "--no-sustained", "--no-op-events"])
+    line = _run(["--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-pipeline", "--no-latency", "--no-config5", "--no-sustained", "--no-op-events"])
     oc = {o["config"].split(":")[0]: o for o in line["other_configs"]}
     for key, fam in (("BASELINE configs[2]", "conv"), ("BASELINE configs[3]", "pwconv_ps_kernel")):
         o = oc[key]
@@ -115,3 +115,41 @@ def test_side_configs_carry_a_per_kernel_view():
     assert any(k["kernel"] == "heads_kernel" for k in oc["BASELINE configs[3]"]["kernels"])
     f32 = next(o for o in line["other_configs"] if o["config"].startswith("BASELINE configs[2] in the fp32-grade mode"))
     assert "traffic" in f32["roofline"] and "traffic_source" in f32["roofline"]
+
+
+def test_plain_run_is_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """Without --full the line is the headline alone (side objects null), the run spends little time outside its steps, and
+    --dump-outputs writes what the last timed step returned: rank 0's [256, 1024] float32 embeddings of the seeded batch that
+    step read.  With 1 warm-up + 3 timed steps over the four batches fed round-robin (step i reads batch i & 3), the last step
+    is the only one that read batch 0."""
+    import time
+    import numpy as np
+    import torch
+    t0 = time.perf_counter()
+    line = _run(["--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)], timeout=300)
+    wall = time.perf_counter() - t0
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line
+    assert line["value"] == pytest.approx(256 * 1e3 / line["ms_per_step"], rel=1e-3)
+    for k in ("roofline", "roofline_depthwise", "kernels", "cpu_baseline", "sustained", "config5", "other_configs", "latency_batch1",
+              "pipeline", "allgather_ms", "ms_per_step_instrumented"):
+        assert line[k] is None, k
+    assert wall - 4 * line["ms_per_step"] * 1e-3 < 30.0, wall
+    assert sorted(os.listdir(tmp_path)) == ["features.npy"]
+    f = np.load(tmp_path / "features.npy")
+    assert f.shape == (256, 1024) and f.dtype == np.float32 and np.isfinite(f).all() and np.abs(f).max() > 0
+
+    # the same engine and the same seeded batches in this process: the dump is batch 0's forward, bit for bit
+    from hse_facerec_tf_amd.tf_inference import AGE_GENDER_PB, TensorFlowInference
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    tfi = TensorFlowInference(AGE_GENDER_PB, input_tensor="input_1:0", output_tensor="global_pooling/Mean:0",
+                              convert2BGR=True, imageNetUtilsMean=True, input_size=(192, 192), max_batch=256, device=0)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(123)
+    xs = [(torch.rand((256, 192, 192, 3), device=dev, generator=gen) * 256.0 - 128.0).contiguous() for _ in range(2)]
+    want = [tfi.engine.forward(x)["features"].cpu().numpy() for x in xs]
+    tfi.close_session()
+    assert np.array_equal(f, want[0])
+    assert not np.array_equal(f, want[1])          # the warm-up's batch gives other embeddings: the comparison can tell them apart

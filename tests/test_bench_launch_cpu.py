@@ -55,6 +55,17 @@ def test_bench_without_gpu_fails_loudly_not_silently():
     assert r.returncode != 0 and "no CPU fallback" in (r.stderr + r.stdout)
 
 
+def test_side_legs_run_only_with_full():
+    import bench
+    legs = ("op_events", "cpu_baseline", "config5", "other_configs", "pipeline", "latency", "sustained", "allgather")
+    plain = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert plain.steps == 7 and plain.warmup == 2 and not plain.full and plain.dump_outputs is None
+    assert all(getattr(plain, "no_" + leg) for leg in legs)
+    full = bench.parse_args(["--full", "--no-config5", "--dump-outputs", "out"])
+    assert full.no_config5 and full.dump_outputs == "out"
+    assert not any(getattr(full, "no_" + leg) for leg in legs if leg != "config5")
+
+
 def test_lfw_like_labels_have_lfw_totals():
     from hse_facerec_tf_amd import gallery
     sizes = gallery.lfw_like_class_sizes()

@@ -100,7 +100,7 @@ def _run_bench(extra, launcher):
 def test_bench_force_group_runs_every_collective_on_rccl(launcher):
     """`bench.py --gpus 1 --force-group`: process group on nccl, barrier-bracketed timed region, the per-rank all-gather of
     timings, the embeddings all-gather, and config 5 through extract_sharded -- the N > 1 code path with N = 1."""
-    line = _run_bench(["--gpus", "1", "--force-group", "--steps", "3", "--warmup", "1", "--no-op-events", "--no-cpu-baseline",
+    line = _run_bench(["--full", "--gpus", "1", "--force-group", "--steps", "3", "--warmup", "1", "--no-op-events", "--no-cpu-baseline",
                        "--no-other-configs", "--no-pipeline", "--no-latency", "--config5-images", "700", "--config5-classes", "120"], launcher)
     assert line["n_gpus"] == 1 and line["config"]["backend"].startswith("RCCL") and line["config"]["process_group"] is True
     assert line["allgather_ms"] is not None and line["allgather_ms"] > 0

@@ -1,5 +1,5 @@
 #!/bin/bash
-# LDS bank-conflict share per kernel (rocprofv3 PMC pass): tools/lds_conflicts.sh python3 /root/repo/bench.py --steps 5 --warmup 2 --no-cpu-baseline
+# LDS bank-conflict share per kernel (rocprofv3 PMC pass): tools/lds_conflicts.sh python3 "$PWD/bench.py" --full --steps 5 --warmup 2 --no-cpu-baseline
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/pmc_lds
 timeout 300 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS --kernel-trace --output-format csv -d /tmp/pmc_lds -- "$@" > /dev/null 2>&1

@@ -3,8 +3,8 @@
 # -> gpurun_out/prof_<tag>{,_resnet,_agegender,_f32}/ (tools/gpu_pmc.sh: kernel-trace stats + one PMC group per pass), the per-LAYER
 # tables of the four configs and the default bench line of the same box.  Then, here:  bash tools/profile_round.sh r05 collect
 # (bench.py marks its traffic figures stale unless profiles/<tag>_traffic.json carries the hash of the sources it runs on: for a bench line
-# with fresh traffic run  `profile_round.sh <tag>; profile_round.sh <tag> collect; python bench.py > gpurun_out/prof_<tag>/bench_line.json`
-# in ONE gpurun call -- gpurun_out/ does not travel to the box -- and collect again here.)
+# with fresh traffic run  `profile_round.sh <tag>; profile_round.sh <tag> collect` and then `python bench.py --full` into the tag's output
+# folder as bench_line.json, all on the same box in one session -- the output folder does not travel to the box -- and collect again here.)
 set -u
 TAG=${1:-r05}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
@@ -24,7 +24,7 @@ if [ "${2:-}" = "collect" ]; then
   exit 0
 fi
 cd "$R"
-HEAD="--steps 20 --warmup 5 --no-config5 --no-other-configs --no-pipeline --no-latency --no-cpu-baseline --no-sustained"
+HEAD="--full --steps 20 --warmup 5 --no-config5 --no-other-configs --no-pipeline --no-latency --no-cpu-baseline --no-sustained"
 bash tools/gpu_pmc.sh gpurun_out/prof_${TAG} python3 $R/bench.py $HEAD
 bash tools/gpu_pmc.sh gpurun_out/prof_${TAG}_resnet python3 $R/tools/bench_configs.py resnet50
 bash tools/gpu_pmc.sh gpurun_out/prof_${TAG}_agegender python3 $R/tools/bench_configs.py agegender
