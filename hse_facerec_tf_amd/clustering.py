@@ -1,0 +1,342 @@
+"""Face clustering (the album tool and the clustering study of age_gender_identity/) with single linkage on the GPU.
+
+The reference groups faces with ``hac.linkage(squareform(D), 'single')`` + ``fcluster(z, t, 'distance')`` on a dense host matrix
+(facial_clustering.py:214-285, process_photos.py:45-77, facial_clustering_test.py:362-414).  Single linkage is the minimum spanning
+tree of the distance graph, which libhsefr builds by Boruvka rounds without an N x N matrix (ops.single_linkage_edges,
+csrc/linkage.hip).  Here the tree becomes scipy's linkage matrix Z, flat cuts of Z cost O(n) each (a threshold sweep pays for one
+tree), and the reference's same-photo split (complete linkage on small per-cluster matrices) runs on the host in NumPy.
+No CPU fallback: the functions that compute distances raise without the library or a GPU.
+"""
+from __future__ import annotations
+
+import hashlib
+from typing import List, Optional, Sequence
+
+import numpy as np
+
+SAME_PHOTO_PENALTY = 100.0      # facial_clustering.py:254 (inf_dist)
+
+
+# ---- linkage matrices ----------------------------------------------------------------------------------------------
+def linkage_from_edges(edge_a, edge_b, edge_h, n: int) -> np.ndarray:
+    """scipy-format Z [n-1, 4] float64 from the n - 1 edges of a minimum spanning tree: the edges sorted by (height, lower endpoint,
+    higher endpoint), then merged by union-find.  Row k = [id_a, id_b, height, size] with id_a < id_b; the cluster made by row k is
+    n + k."""
+    a = np.asarray(edge_a, dtype=np.int64)
+    b = np.asarray(edge_b, dtype=np.int64)
+    h = np.asarray(edge_h, dtype=np.float64)
+    if not (len(a) == len(b) == len(h) == n - 1):
+        raise ValueError("a spanning tree of %d points has %d edges, got %d" % (n, n - 1, len(a)))
+    lo, hi = np.minimum(a, b), np.maximum(a, b)
+    if n > 1 and (lo.min() < 0 or hi.max() >= n):
+        raise RuntimeError("single linkage: edge endpoints out of range (the tree is incomplete)")
+    order = np.lexsort((hi, lo, h))
+    parent = list(range(2 * n - 1))
+    size = [1] * n + [0] * (n - 1)
+    Z = np.empty((n - 1, 4), dtype=np.float64)
+
+    def find(v):
+        r = v
+        while parent[r] != r:
+            r = parent[r]
+        while parent[v] != r:
+            parent[v], v = r, parent[v]
+        return r
+    for k, e in enumerate(order.tolist()):
+        ra, rb = find(int(lo[e])), find(int(hi[e]))
+        if ra == rb:
+            raise RuntimeError("single linkage: the edges close a cycle (not a spanning tree)")
+        if ra > rb:
+            ra, rb = rb, ra
+        parent[ra] = parent[rb] = n + k
+        size[n + k] = size[ra] + size[rb]
+        Z[k] = (ra, rb, h[e], size[n + k])
+    return Z
+
+
+def _device_tensor(a, dtype, device=None):
+    from . import _lib
+    torch = _lib.require_gpu()
+    if isinstance(a, torch.Tensor):
+        return a.to(device=_lib.cuda_device(device) if not a.is_cuda else a.device, dtype=dtype).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32 if dtype == torch.float32 else np.float64)) \
+        .to(_lib.cuda_device(device)).contiguous()
+
+
+def _age_arrays(born_years, photo_years, n):
+    if born_years is None and photo_years is None:
+        return None, None
+    if born_years is None or photo_years is None:
+        raise ValueError("born_years and photo_years come together")
+    by = np.asarray(born_years, dtype=np.float64).reshape(-1)
+    yr = np.asarray(photo_years, dtype=np.float64).reshape(-1)
+    if len(by) != n or len(yr) != n:
+        raise ValueError("%d faces, %d born years, %d photo years" % (n, len(by), len(yr)))
+    if not (np.isfinite(by).all() and np.isfinite(yr).all()):
+        raise ValueError("born_years / photo_years must be finite")
+    if not (yr - by > 0).all():
+        raise ValueError("every face needs photo_year - born_year > 0 (the age term divides by the sum of two ages)")
+    return by, yr
+
+
+def linkage_single(features, born_years=None, photo_years=None, device=None) -> np.ndarray:
+    """hac.linkage(squareform(D), 'single') for D = the feature distance of perform_clustering (process_photos.py:45-56):
+    |x_i - x_j| (+ the age term with born / photo years), from the features [n, d] on the GPU, with no N x N matrix anywhere."""
+    from . import _lib, ops
+    torch = _lib.require_gpu()
+    x = _device_tensor(features, torch.float32, device)
+    if x.dim() != 2 or x.shape[0] < 1:
+        raise ValueError("features must be [n, d] with n >= 1")
+    n = x.shape[0]
+    by, yr = _age_arrays(born_years, photo_years, n)
+    born = year = None
+    if by is not None:
+        born = torch.from_numpy(by.astype(np.float32)).to(x.device)
+        year = torch.from_numpy(yr.astype(np.float32)).to(x.device)
+    ea, eb, eh = ops.single_linkage_edges(x=x, born=born, year=year)
+    return linkage_from_edges(ea.cpu().numpy(), eb.cpu().numpy(), eh.cpu().numpy(), n)
+
+
+def linkage_single_dense(dist_matrix, device=None) -> np.ndarray:
+    """hac.linkage(squareform(dist_matrix, checks=False), 'single') with the spanning tree built on the GPU from the fp64 matrix's
+    upper triangle: the heights are scipy's, bit for bit."""
+    from . import _lib, ops
+    torch = _lib.require_gpu()
+    D = dist_matrix if isinstance(dist_matrix, torch.Tensor) else np.asarray(dist_matrix, dtype=np.float64)
+    if D.ndim != 2 or D.shape[0] != D.shape[1] or D.shape[0] < 1:
+        raise ValueError("dist_matrix must be a non-empty square matrix, got shape %r" % (tuple(D.shape),))
+    if isinstance(D, np.ndarray) and not np.isfinite(D).all():
+        raise ValueError("dist_matrix holds non-finite values")
+    if isinstance(D, torch.Tensor) and not bool(torch.isfinite(D).all()):
+        raise ValueError("dist_matrix holds non-finite values")
+    n = D.shape[0]
+    ea, eb, eh = ops.single_linkage_edges(dense=_device_tensor(D, torch.float64, device))
+    return linkage_from_edges(ea.cpu().numpy(), eb.cpu().numpy(), eh.cpu().numpy(), n)
+
+
+# ---- flat cuts ------------------------------------------------------------------------------------------------------
+_CUT_CACHE = {}
+
+
+def _cut_order(Z: np.ndarray):
+    """Leaves in dendrogram order, and for each of the n - 1 gaps between neighbours in that order the largest height inside the
+    smallest cluster that holds both (scipy's max-dist monocrit).  Every flat cluster of every cut is a run of that order."""
+    Z = np.ascontiguousarray(Z, dtype=np.float64)
+    key = hashlib.blake2b(Z.tobytes(), digest_size=16).digest()
+    hit = _CUT_CACHE.get(key)
+    if hit is not None:
+        return hit
+    n = Z.shape[0] + 1
+    head = list(range(n)) + [0] * (n - 1)
+    tail = list(range(n)) + [0] * (n - 1)
+    maxh = [-np.inf] * n + [0.0] * (n - 1)
+    nxt = [-1] * n
+    gap_h = [0.0] * n
+    ids = Z[:, :2].astype(np.int64).tolist()
+    hs = Z[:, 2].tolist()
+    for k in range(n - 1):
+        a, b = ids[k]
+        c = n + k
+        m = max(hs[k], maxh[a], maxh[b])
+        maxh[c] = m
+        nxt[tail[a]] = head[b]
+        gap_h[tail[a]] = m
+        head[c], tail[c] = head[a], tail[b]
+    order = np.empty(n, dtype=np.int64)
+    v = head[2 * n - 2] if n > 1 else 0
+    for p in range(n):
+        order[p] = v
+        v = nxt[v]
+    gaps = np.asarray(gap_h, dtype=np.float64)[order[:-1]]
+    if len(_CUT_CACHE) >= 8:
+        _CUT_CACHE.clear()
+    _CUT_CACHE[key] = (order, gaps)
+    return order, gaps
+
+
+def fcluster_distance(Z, t):
+    """fcluster(Z, t, 'distance'): flat clusters whose members are joined at heights <= t, labelled 1..k (the partition is scipy's,
+    label numbers are in dendrogram order).  ``t`` may be a sequence: one row of labels per threshold.  Z's leaf order is computed once
+    and cached, so a sweep costs O(n) vectorised work per threshold."""
+    Z = np.asarray(Z, dtype=np.float64)
+    order, gaps = _cut_order(Z)
+    n = len(order)
+    ts = np.atleast_1d(np.asarray(t, dtype=np.float64))
+    out = np.empty((len(ts), n), dtype=np.int32)
+    for r, tv in enumerate(ts):
+        run = np.empty(n, dtype=np.int32)
+        run[0] = 1
+        run[1:] = 1 + np.cumsum(gaps > tv)
+        out[r, order] = run
+    return out[0] if np.ndim(t) == 0 else out
+
+
+def _groups(labels: np.ndarray) -> List[np.ndarray]:
+    """Members of each label, ascending, the groups ordered by their smallest member."""
+    labels = np.asarray(labels)
+    order = np.argsort(labels, kind="stable")
+    cuts = np.flatnonzero(np.diff(labels[order])) + 1
+    groups = np.split(order, cuts)
+    groups.sort(key=lambda g: int(g[0]))
+    return groups
+
+
+# ---- the same-photo split: complete linkage on the host --------------------------------------------------------------
+def complete_linkage_labels(D: np.ndarray, t: float) -> np.ndarray:
+    """fcluster(linkage(squareform(D), 'complete'), t, 'distance') for a small symmetric matrix, as labels 0..k-1 by first
+    occurrence: the nearest-neighbour chain with scipy's tie rules (the previous chain element wins a tie; otherwise the lowest index),
+    Lance-Williams complete update max(d(x,k), d(y,k)), merged cluster kept in the larger slot.  O(k^2)."""
+    D = np.array(D, dtype=np.float64)
+    k = D.shape[0]
+    if k == 1:
+        return np.zeros(1, dtype=np.int64)
+    np.fill_diagonal(D, np.inf)
+    parent = list(range(k))
+    chain: List[int] = []
+    alive = np.ones(k, dtype=bool)
+    merges = []
+    for _ in range(k - 1):
+        if not chain:
+            chain.append(int(np.flatnonzero(alive)[0]))
+        while True:
+            x = chain[-1]
+            if len(chain) > 1:
+                y, cur = chain[-2], D[x, chain[-2]]
+            else:
+                y, cur = -1, np.inf
+            j = int(np.argmin(D[x]))
+            if D[x, j] < cur:
+                y = j
+            if len(chain) > 1 and y == chain[-2]:
+                break
+            chain.append(y)
+        x, y = chain.pop(), chain.pop()
+        if x > y:
+            x, y = y, x
+        merges.append((x, y, D[x, y]))
+        row = np.maximum(D[x], D[y])
+        D[y, :] = row
+        D[:, y] = row
+        D[y, y] = np.inf
+        D[x, :] = np.inf
+        D[:, x] = np.inf
+        alive[x] = False
+
+    def find(v):
+        while parent[v] != v:
+            parent[v] = parent[parent[v]]
+            v = parent[v]
+        return v
+    for x, y, h in merges:          # complete linkage has no inversions: a merge at h <= t has all its sub-merges <= t as well
+        if h <= t:
+            parent[find(x)] = find(y)
+    roots = np.array([find(v) for v in range(k)])
+    _, first = np.unique(roots, return_index=True)
+    relabel = {int(roots[f]): i for i, f in enumerate(sorted(first))}
+    return np.array([relabel[int(r)] for r in roots], dtype=np.int64)
+
+
+def _split_same_photo(D_sub: np.ndarray, photo: np.ndarray) -> List[np.ndarray]:
+    """facial_clustering.py:250-261 inside one cluster: +100 for two faces of one photo, complete linkage, cut at 50."""
+    P = np.triu(np.asarray(D_sub, dtype=np.float64), 1)
+    P = P + P.T
+    same = photo[:, None] == photo[None, :]
+    np.fill_diagonal(same, False)
+    P += SAME_PHOTO_PENALTY * same
+    lab = complete_linkage_labels(P, SAME_PHOTO_PENALTY / 2)
+    return [np.flatnonzero(lab == v) for v in range(int(lab.max()) + 1)]
+
+
+def _finish(clusters: List[np.ndarray], min_size: int = 1) -> List[List[int]]:
+    out = [sorted(int(i) for i in c) for c in clusters if len(c) >= min_size]
+    out.sort(key=lambda c: (-len(c), c[0]))
+    return out
+
+
+def get_facial_clusters(dist_matrix, distanceThreshold=1, all_indices=None, no_images_in_cluster=1, device=None) -> List[List[int]]:
+    """The single-linkage branch of facial_clustering.get_facial_clusters (:243-261) with the linkage on the GPU (dense fp64 path):
+    clusters of faces joined at distances <= distanceThreshold; with ``all_indices`` (the photo of every face) each cluster is split so
+    that no two faces of one photo stay together (complete linkage on the cluster's penalised distances, cut at 50, as the reference).
+    ``no_images_in_cluster`` is accepted and ignored, as that branch does.  Returns lists of face indices, longest first; clusters of
+    equal length are ordered by their smallest index (the reference leaves that order to scipy's label numbering).  One face gives
+    [[0]] (the reference's linkage raises on it).  Non-finite distances raise ValueError."""
+    D = np.asarray(dist_matrix, dtype=np.float64)
+    if D.ndim != 2 or D.shape[0] != D.shape[1] or D.shape[0] < 1:
+        raise ValueError("dist_matrix must be a non-empty square matrix, got shape %r" % (D.shape,))
+    if not np.isfinite(D).all():
+        raise ValueError("dist_matrix holds non-finite values")
+    n = D.shape[0]
+    if n == 1:
+        return [[0]]
+    groups = _groups(fcluster_distance(linkage_single_dense(D, device), distanceThreshold))
+    if all_indices is None:
+        return _finish(groups)
+    photo = np.asarray(all_indices).reshape(-1)
+    if len(photo) != n:
+        raise ValueError("%d faces, %d photo indices" % (n, len(photo)))
+    clusters = []
+    for g in groups:
+        if len(g) > 1:
+            clusters.extend(g[part] for part in _split_same_photo(D[np.ix_(g, g)], photo[g]))
+        else:
+            clusters.append(g)
+    return _finish(clusters)
+
+
+def cluster_faces(features, distance_threshold: float, born_years=None, photo_years=None, all_indices=None,
+                  min_cluster_size: int = 1, device=None) -> List[List[int]]:
+    """perform_clustering (process_photos.py:45-77) without the date rule, from the features: single linkage on the GPU with no N x N
+    matrix (the age term when born / photo years are given), the same-photo split on each cluster's own distances (its rows through
+    ops.pairwise_distances plus the host age term, clipped at 0, as feature_distance_matrix builds them), and clusters shorter than
+    ``min_cluster_size`` dropped.  Same order as get_facial_clusters."""
+    from . import _lib, ops
+    torch = _lib.require_gpu()
+    x = _device_tensor(features, torch.float32, device)
+    if x.dim() != 2 or x.shape[0] < 1:
+        raise ValueError("features must be [n, d] with n >= 1")
+    n = x.shape[0]
+    by, yr = _age_arrays(born_years, photo_years, n)
+    if n == 1:
+        return _finish([np.zeros(1, dtype=np.int64)], min_cluster_size)
+    Z = linkage_single(x, by, yr)
+    groups = _groups(fcluster_distance(Z, distance_threshold))
+    if all_indices is None:
+        return _finish(groups, min_cluster_size)
+    photo = np.asarray(all_indices).reshape(-1)
+    if len(photo) != n:
+        raise ValueError("%d faces, %d photo indices" % (n, len(photo)))
+    xp = x if x.shape[1] % 8 == 0 else torch.nn.functional.pad(x, (0, 8 - x.shape[1] % 8)).contiguous()
+    clusters = []
+    for g in groups:
+        if len(g) < 2:
+            clusters.append(g)
+            continue
+        rows = xp[torch.from_numpy(g).to(x.device)].contiguous()
+        D = ops.pairwise_distances(rows).cpu().numpy().astype(np.float64)
+        if by is not None:
+            b, y = by[g], yr[g]
+            max_year = np.maximum(y[:, None], y[None, :])
+            ai, aj = max_year - b[:, None], max_year - b[None, :]
+            D = D + 0.1 * (ai - aj) ** 2 / (ai + aj)
+        D = np.clip(D, 0, None)
+        clusters.extend(g[part] for part in _split_same_photo(D, photo[g]))
+    return _finish(clusters, min_cluster_size)
+
+
+# ---- scoring --------------------------------------------------------------------------------------------------------
+def bcubed(y_true: Sequence, y_pred: Sequence):
+    """Extended B-cubed of the clustering study (facial_clustering_test.py:321-359, one label per item) -> (precision, recall, f).
+    In the study's naming, precision averages over items the share of their TRUE class that shares their predicted cluster, recall
+    the share of their predicted cluster that shares their true class; f is their harmonic mean.  From the contingency table."""
+    y_true, y_pred = np.asarray(y_true).reshape(-1), np.asarray(y_pred).reshape(-1)
+    if len(y_true) != len(y_pred) or len(y_true) == 0:
+        raise ValueError("bcubed: %d true labels, %d predicted" % (len(y_true), len(y_pred)))
+    _, t = np.unique(y_true, return_inverse=True)
+    _, p = np.unique(y_pred, return_inverse=True)
+    t, p = t.reshape(-1), p.reshape(-1)
+    cells = t.astype(np.int64) * (int(p.max()) + 1) + p
+    _, cell, both = np.unique(cells, return_inverse=True, return_counts=True)
+    both = both[cell.reshape(-1)].astype(np.float64)
+    prec = float(np.mean(both / np.bincount(t)[t]))
+    rec = float(np.mean(both / np.bincount(p)[p]))
+    return prec, rec, 2.0 * prec * rec / (prec + rec)

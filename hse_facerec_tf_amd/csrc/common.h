@@ -271,6 +271,8 @@ int launch_cv_resize(const unsigned char* in, float* out, int n, int H, int W, i
 int launch_area_level(const unsigned char* src, float* dst, int sh, int sw, int dh, int dw, hipStream_t s);
 int launch_area_crops(const unsigned char* src, const int* boxes, float* dst, int sh, int sw, int n, int size, hipStream_t s);
 int launch_pairwise_dist(const float* x, const float* y, int n, int m, int d, float* out, hipStream_t s);
+int launch_single_linkage(const float* x, int n, int d, const float* born, const float* year, const double* dense, int* edge_a, int* edge_b,
+                          double* edge_h, hipStream_t s);
 
 bool dwpw_fused_supported(int c, int cout, int stride, int act_dw, int act_pw);
 int launch_dwpw_fused(const float* x, const float* wd, const float* dscale, const float* dshift, const float* wp_t,

@@ -1374,5 +1374,16 @@ int hsefr_pairwise_dist(const float* x, const float* y, int n, int m, int d, flo
     return launch_pairwise_dist(x, y, n, m, d, out, (hipStream_t)stream);
 }
 
+int hsefr_single_linkage(const float* x, int n, int d, const float* born, const float* year, const double* dense, int* edge_a, int* edge_b,
+                         double* edge_h, hsefr_stream_t stream) {
+    HSEFR_REQUIRE(n >= 1, HSEFR_ERR_INVALID, "single_linkage: n=%d", n);
+    HSEFR_REQUIRE((x != nullptr) != (dense != nullptr), HSEFR_ERR_INVALID, "single_linkage: pass exactly one of x and dense");
+    HSEFR_REQUIRE(edge_a && edge_b && edge_h, HSEFR_ERR_INVALID, "single_linkage: null pointer (edge outputs)");
+    HSEFR_REQUIRE(!born == !year, HSEFR_ERR_INVALID, "single_linkage: born and year come together");
+    HSEFR_REQUIRE(!(dense && born), HSEFR_ERR_INVALID, "single_linkage: the age term belongs to the features path");
+    HSEFR_REQUIRE(dense || (d > 0 && d % 8 == 0), HSEFR_ERR_INVALID, "single_linkage: d=%d must be a positive multiple of 8", d);
+    return launch_single_linkage(x, n, d, born, year, dense, edge_a, edge_b, edge_h, (hipStream_t)stream);
+}
+
 }  // extern "C"
 #pragma GCC visibility pop

@@ -530,6 +530,49 @@ def pairwise_distances(x, y=None):
     return out
 
 
+@_device_guarded
+def single_linkage_edges(x=None, dense=None, born=None, year=None):
+    """The minimum spanning tree behind single linkage (hsefr_single_linkage) -> (edge_a int32, edge_b int32, edge_h float64), n - 1 CUDA
+    tensors each, edge_a < edge_b, round by round.  Exactly one source: x [n,d] float32 features (zero columns pad d to a multiple of 8,
+    which changes no distance) with optional born / year float32 [n] (the age term of process_photos.py:46-51), or dense [n,n] float64
+    distances read as their upper triangle.  Asynchronous on the current stream."""
+    torch = _lib.require_gpu()
+    if (x is None) == (dense is None):
+        raise ValueError("single_linkage_edges: pass exactly one of x and dense")
+    if (born is None) != (year is None):
+        raise ValueError("single_linkage_edges: born and year come together")
+    d = 0
+    if x is not None:
+        _f32c(x, "x")
+        if x.dim() != 2:
+            raise ValueError("x must be [n, d]")
+        n, d = x.shape
+        if d % 8:
+            x = torch.nn.functional.pad(x, (0, 8 - d % 8)).contiguous()
+            d = x.shape[1]
+        for v, name in ((born, "born"), (year, "year")):
+            if v is not None and _f32c(v, name).numel() != n:
+                raise ValueError("%s has %d elements for %d rows" % (name, v.numel(), n))
+    else:
+        if born is not None:
+            raise ValueError("single_linkage_edges: the age term belongs to the features path")
+        if not (dense.is_cuda and dense.dtype == torch.float64 and dense.is_contiguous() and dense.dim() == 2
+                and dense.shape[0] == dense.shape[1]):
+            raise ValueError("dense must be a contiguous square float64 CUDA tensor")
+        n = dense.shape[0]
+    if n < 1:
+        raise ValueError("single_linkage_edges: no points")
+    dev = (x if x is not None else dense).device
+    m = max(n - 1, 1)
+    ea = torch.full((m,), -1, dtype=torch.int32, device=dev)
+    eb = torch.full((m,), -1, dtype=torch.int32, device=dev)
+    eh = torch.empty((m,), dtype=torch.float64, device=dev)
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    _lib.check(_lib.lib().hsefr_single_linkage(ptr(x), n, d, ptr(born), ptr(year), ptr(dense), ea.data_ptr(), eb.data_ptr(),
+                                               eh.data_ptr(), _lib.current_stream_ptr()), "hsefr_single_linkage")
+    return ea[:n - 1], eb[:n - 1], eh[:n - 1]
+
+
 # ---- bf16 ResNet-50 kernels -------------------------------------------------------------------------
 def _bf16c(t, name):
     torch = _lib.require_gpu()

@@ -593,6 +593,20 @@ int hsefr_maxpool_f32(const float* x, float* y, int n, int h, int w, int c, int 
  * ~1e-7*(|x|^2+|y|^2) on the SQUARED distance, i.e. distances below ~1e-2 (near-duplicates) carry up to 6e-4. */
 int hsefr_pairwise_dist(const float* x, const float* y, int n, int m, int d, float* out, hsefr_stream_t stream);
 
+/* Single-linkage clustering without an N x N matrix (hac.linkage(squareform(D), 'single') of get_facial_clusters,
+ * facial_clustering.py:243-245, on the dist_matrix of process_photos.py:45-60): the minimum spanning tree of the distance graph by
+ * Boruvka rounds (csrc/linkage.hip).  Exactly one source:
+ *   x [n,d] fp32, d multiple of 8, with optional born [n] and year [n] fp32 (both or neither):
+ *     w(i,j) = max(|x_i - x_j| + 0.1 (born_j - born_i)^2 / (2 max(year_i, year_j) - born_i - born_j), 0), the Euclidean term as
+ *     |x_i|^2 + |x_j|^2 - 2 x_i.x_j on the fp32 MFMA and computed bitwise symmetrically; the caller keeps year - born > 0;
+ *   dense [n,n] fp64, read as its upper triangle D[min(i,j), max(i,j)] (squareform(D, checks=False)).
+ * Outputs (device): the n - 1 tree edges edge_a < edge_b with their height edge_h (the fp32 distance widened to double, or the fp64
+ * input value), round by round in discovery order (unordered within a round).  Ties are broken by (height, lower endpoint, higher
+ * endpoint), so the tree is one well-defined MST; sorting the edges by that key gives scipy's single-linkage merge sequence.  O(n)
+ * stream-ordered workspace, no host synchronisation.  Arguments are checked before any device call (HSEFR_ERR_INVALID). */
+int hsefr_single_linkage(const float* x, int n, int d, const float* born, const float* year, const double* dense, int* edge_a,
+                         int* edge_b, double* edge_h, hsefr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

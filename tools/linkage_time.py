@@ -1,0 +1,115 @@
+#!/usr/bin/env python3
+"""GPU time of single-linkage clustering from features (hsefr_single_linkage, csrc/linkage.hip: Boruvka rounds, no N x N matrix) for
+n in {2048, 9164, 32768} x d in {1024, 2048}, with the rounds the tree actually needed and the time per round, next to the host path it
+replaces (identification.feature_distance_matrix + scipy's single linkage on the dense matrix, up to n = 9164).
+usage: python tools/linkage_time.py [--out FILE]"""
+import argparse
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+
+from hse_facerec_tf_amd import identification, ops
+
+SIZES = [2048, 9164, 32768]
+DIMS = [1024, 2048]
+HOST_MAX_N = 9164
+
+
+def unit_rows(n, d, seed):
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    c = torch.randn((max(2, n // 6), d), device="cuda", generator=g)
+    x = c[torch.randint(0, c.shape[0], (n,), device="cuda", generator=g)] + 0.8 * torch.randn((n, d), device="cuda", generator=g)
+    return (x / x.norm(dim=1, keepdim=True)).contiguous()
+
+
+def rounds_used(n, a, b, h):
+    """Boruvka on the tree itself under the same total order (height, lower, higher): the lightest edge leaving a component of the
+    full graph is a tree edge, so this replays the device's rounds."""
+    lo, hi = np.minimum(a, b), np.maximum(a, b)
+    rank = np.empty(n - 1, dtype=np.int64)
+    rank[np.lexsort((hi, lo, h))] = np.arange(n - 1)
+    label = np.arange(n)
+    rounds = 0
+    while len(np.unique(label)) > 1:
+        rounds += 1
+        la, lb = label[lo], label[hi]
+        out = la != lb
+        best = np.full(n, n, dtype=np.int64)          # per component root: rank of its lightest outgoing edge
+        np.minimum.at(best, la[out], rank[out])
+        np.minimum.at(best, lb[out], rank[out])
+        chosen = np.flatnonzero(best < n)
+        e = np.argsort(rank)[best[chosen]]
+        # union the chosen edges (a forest plus mutual picks), then relabel
+        uf = np.arange(n)
+
+        def find(v):
+            while uf[v] != v:
+                uf[v] = uf[uf[v]]
+                v = uf[v]
+            return v
+        for x, y in zip(label[lo[e]], label[hi[e]]):
+            rx, ry = find(x), find(y)
+            if rx != ry:
+                uf[max(rx, ry)] = min(rx, ry)
+        parent = np.array([find(v) for v in range(n)])
+        label = parent[label]
+    return rounds
+
+
+def gpu_ms(x, reps):
+    ops.single_linkage_edges(x=x)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        out = ops.single_linkage_edges(x=x)
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps, out
+
+
+def host_s(xh):
+    from scipy.cluster import hierarchy as hac
+    from scipy.spatial.distance import squareform
+    t0 = time.perf_counter()
+    D = identification.feature_distance_matrix(xh)
+    t1 = time.perf_counter()
+    hac.linkage(squareform(D, checks=False), "single")
+    t2 = time.perf_counter()
+    return t1 - t0, t2 - t1
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    lines = ["# single-linkage clustering from unit-norm features, fp32 (tools/linkage_time.py); %s" % torch.cuda.get_device_name(0),
+             "# GPU: hsefr_single_linkage, CUDA-event time per call (mean of reps after one warm-up); rounds launched = ceil(log2 n)",
+             "# host: identification.feature_distance_matrix (GPU distances + copy to a host float64 matrix) + scipy linkage 'single'",
+             "%7s %5s %11s %9s %9s %13s %12s %12s %10s" % ("n", "d", "gpu_ms", "launched", "used", "ms_per_round", "host_D_s",
+                                                        "host_link_s", "speedup")]
+    for n in SIZES:
+        for d in DIMS:
+            x = unit_rows(n, d, n + d)
+            ms, (a, b, h) = gpu_ms(x, 3 if n <= 9164 else 2)
+            used = rounds_used(n, a.cpu().numpy(), b.cpu().numpy(), h.cpu().numpy())
+            launched = int(np.ceil(np.log2(n)))
+            hd = hl = float("nan")
+            if n <= HOST_MAX_N:
+                hd, hl = host_s(x.cpu().numpy())
+            sp = (hd + hl) * 1e3 / ms if n <= HOST_MAX_N else float("nan")
+            lines.append("%7d %5d %11.2f %9d %9d %13.2f %12.3f %12.3f %10.1f" % (n, d, ms, launched, used, ms / used, hd, hl, sp))
+            print(lines[-1], flush=True)
+    text = "\n".join(lines) + "\n"
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text)
+    print(text)
+
+
+if __name__ == "__main__":
+    main()
