@@ -1,10 +1,13 @@
-"""Face clustering (the album tool and the clustering study of age_gender_identity/) with single linkage on the GPU.
+"""Face clustering (the album tool and the clustering study of age_gender_identity/) with single, average, complete or weighted linkage
+on the GPU.
 
 The reference groups faces with ``hac.linkage(squareform(D), 'single')`` + ``fcluster(z, t, 'distance')`` on a dense host matrix
 (facial_clustering.py:214-285, process_photos.py:45-77, facial_clustering_test.py:362-414).  Single linkage is the minimum spanning
 tree of the distance graph, which libhsefr builds by Boruvka rounds without an N x N matrix (ops.single_linkage_edges,
 csrc/linkage.hip).  Here the tree becomes scipy's linkage matrix Z, flat cuts of Z cost O(n) each (a threshold sweep pays for one
 tree), and the reference's same-photo split (complete linkage on small per-cluster matrices) runs on the host in NumPy.
+The study's other methods (facial_clustering_test.py:513-514: 'average', 'complete', 'weighted') need the whole matrix: libhsefr
+merges reciprocal nearest neighbours round by round on an fp64 n x n device matrix (ops.hier_linkage_merges, csrc/hier_linkage.hip).
 No CPU fallback: the functions that compute distances raise without the library or a GPU.
 """
 from __future__ import annotations
@@ -15,6 +18,14 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 SAME_PHOTO_PENALTY = 100.0      # facial_clustering.py:254 (inf_dist)
+# scipy's reducible methods with a per-round Lance-Williams update; 'centroid' and 'median' are not reducible (their trees can have
+# inversions), and 'ward''s update of two clusters merged in the same round does not factor into two-way steps
+LINKAGE_METHODS = ("single", "average", "complete", "weighted")
+
+
+def _check_method(method):
+    if method not in LINKAGE_METHODS:
+        raise ValueError("linkage method %r is not supported; the supported methods are %s" % (method, ", ".join(LINKAGE_METHODS)))
 
 
 # ---- linkage matrices ----------------------------------------------------------------------------------------------
@@ -28,9 +39,27 @@ def linkage_from_edges(edge_a, edge_b, edge_h, n: int) -> np.ndarray:
     if not (len(a) == len(b) == len(h) == n - 1):
         raise ValueError("a spanning tree of %d points has %d edges, got %d" % (n, n - 1, len(a)))
     lo, hi = np.minimum(a, b), np.maximum(a, b)
+    return _join(lo, hi, h, np.lexsort((hi, lo, h)), n, "single linkage")
+
+
+def linkage_from_merges(merge_a, merge_b, merge_h, merge_round, n: int) -> np.ndarray:
+    """scipy-format Z from the n - 1 merge records of ops.hier_linkage_merges: record k joined the clusters of points merge_a[k] and
+    merge_b[k] at merge_h[k] in round merge_round[k].  Records are taken in (height, round, surviving point) order -- a merge in an
+    earlier round precedes one of a later round at the same height, so a child never follows its parent -- and joined by union-find
+    as in linkage_from_edges."""
+    a = np.asarray(merge_a, dtype=np.int64)
+    b = np.asarray(merge_b, dtype=np.int64)
+    h = np.asarray(merge_h, dtype=np.float64)
+    r = np.asarray(merge_round, dtype=np.int64)
+    if not (len(a) == len(b) == len(h) == len(r) == n - 1):
+        raise ValueError("a hierarchy of %d points has %d merges, got %d" % (n, n - 1, len(a)))
+    lo, hi = np.minimum(a, b), np.maximum(a, b)
+    return _join(lo, hi, h, np.lexsort((lo, r, h)), n, "linkage")
+
+
+def _join(lo, hi, h, order, n, what) -> np.ndarray:
     if n > 1 and (lo.min() < 0 or hi.max() >= n):
-        raise RuntimeError("single linkage: edge endpoints out of range (the tree is incomplete)")
-    order = np.lexsort((hi, lo, h))
+        raise RuntimeError("%s: edge endpoints out of range (the tree is incomplete)" % what)
     parent = list(range(2 * n - 1))
     size = [1] * n + [0] * (n - 1)
     Z = np.empty((n - 1, 4), dtype=np.float64)
@@ -45,7 +74,7 @@ def linkage_from_edges(edge_a, edge_b, edge_h, n: int) -> np.ndarray:
     for k, e in enumerate(order.tolist()):
         ra, rb = find(int(lo[e])), find(int(hi[e]))
         if ra == rb:
-            raise RuntimeError("single linkage: the edges close a cycle (not a spanning tree)")
+            raise RuntimeError("%s: the edges close a cycle (not a spanning tree)" % what)
         if ra > rb:
             ra, rb = rb, ra
         parent[ra] = parent[rb] = n + k
@@ -88,11 +117,7 @@ def linkage_single(features, born_years=None, photo_years=None, device=None) -> 
     if x.dim() != 2 or x.shape[0] < 1:
         raise ValueError("features must be [n, d] with n >= 1")
     n = x.shape[0]
-    by, yr = _age_arrays(born_years, photo_years, n)
-    born = year = None
-    if by is not None:
-        born = torch.from_numpy(by.astype(np.float32)).to(x.device)
-        year = torch.from_numpy(yr.astype(np.float32)).to(x.device)
+    born, year = _age_tensors(*_age_arrays(born_years, photo_years, n), x.device)
     ea, eb, eh = ops.single_linkage_edges(x=x, born=born, year=year)
     return linkage_from_edges(ea.cpu().numpy(), eb.cpu().numpy(), eh.cpu().numpy(), n)
 
@@ -112,6 +137,55 @@ def linkage_single_dense(dist_matrix, device=None) -> np.ndarray:
     n = D.shape[0]
     ea, eb, eh = ops.single_linkage_edges(dense=_device_tensor(D, torch.float64, device))
     return linkage_from_edges(ea.cpu().numpy(), eb.cpu().numpy(), eh.cpu().numpy(), n)
+
+
+def _age_tensors(by, yr, dev):
+    import torch
+    if by is None:
+        return None, None
+    return torch.from_numpy(by.astype(np.float32)).to(dev), torch.from_numpy(yr.astype(np.float32)).to(dev)
+
+
+def linkage(features, method, born_years=None, photo_years=None, device=None) -> np.ndarray:
+    """hac.linkage(squareform(D), method) for D = the feature distance of perform_clustering (process_photos.py:45-56) from the
+    features [n, d] on the GPU.  'single' is linkage_single (no N x N matrix); 'average', 'complete' and 'weighted' build D as an fp64
+    device matrix (fp32 distances widened, 8 n^2 bytes) and merge reciprocal nearest neighbours there.  Non-finite features raise
+    ValueError; so does any other method."""
+    from . import _lib, ops
+    _check_method(method)
+    torch = _lib.require_gpu()
+    x = _device_tensor(features, torch.float32, device)
+    if x.dim() != 2 or x.shape[0] < 1:
+        raise ValueError("features must be [n, d] with n >= 1")
+    if not bool(torch.isfinite(x).all()):
+        raise ValueError("features hold non-finite values")
+    if method == "single":
+        return linkage_single(x, born_years, photo_years)
+    n = x.shape[0]
+    born, year = _age_tensors(*_age_arrays(born_years, photo_years, n), x.device)
+    ma, mb, mh, mr = ops.hier_linkage_merges(x=x, born=born, year=year, method=method)
+    return linkage_from_merges(ma.cpu().numpy(), mb.cpu().numpy(), mh.cpu().numpy(), mr.cpu().numpy(), n)
+
+
+def linkage_dense(dist_matrix, method, device=None) -> np.ndarray:
+    """hac.linkage(squareform(dist_matrix, checks=False), method), the matrix read as its upper triangle: 'single' is
+    linkage_single_dense, 'average' / 'complete' / 'weighted' run on an fp64 device copy with scipy's Lance-Williams updates (complete
+    linkage's heights are scipy's bit for bit; the two means agree to rounding)."""
+    from . import _lib, ops
+    _check_method(method)
+    if method == "single":
+        return linkage_single_dense(dist_matrix, device)
+    torch = _lib.require_gpu()
+    D = dist_matrix if isinstance(dist_matrix, torch.Tensor) else np.asarray(dist_matrix, dtype=np.float64)
+    if D.ndim != 2 or D.shape[0] != D.shape[1] or D.shape[0] < 1:
+        raise ValueError("dist_matrix must be a non-empty square matrix, got shape %r" % (tuple(D.shape),))
+    if isinstance(D, np.ndarray) and not np.isfinite(D).all():
+        raise ValueError("dist_matrix holds non-finite values")
+    if isinstance(D, torch.Tensor) and not bool(torch.isfinite(D).all()):
+        raise ValueError("dist_matrix holds non-finite values")
+    n = D.shape[0]
+    ma, mb, mh, mr = ops.hier_linkage_merges(dense=_device_tensor(D, torch.float64, device), method=method)
+    return linkage_from_merges(ma.cpu().numpy(), mb.cpu().numpy(), mh.cpu().numpy(), mr.cpu().numpy(), n)
 
 
 # ---- flat cuts ------------------------------------------------------------------------------------------------------
@@ -253,13 +327,16 @@ def _finish(clusters: List[np.ndarray], min_size: int = 1) -> List[List[int]]:
     return out
 
 
-def get_facial_clusters(dist_matrix, distanceThreshold=1, all_indices=None, no_images_in_cluster=1, device=None) -> List[List[int]]:
-    """The single-linkage branch of facial_clustering.get_facial_clusters (:243-261) with the linkage on the GPU (dense fp64 path):
+def get_facial_clusters(dist_matrix, distanceThreshold=1, all_indices=None, no_images_in_cluster=1, device=None,
+                        method="single") -> List[List[int]]:
+    """The scipy branch of facial_clustering.get_facial_clusters (:243-261) with the linkage on the GPU (dense fp64 path) -- single
+    linkage by default, or ``method`` 'average' / 'complete' / 'weighted' (the module global clusteringMethod the study sets):
     clusters of faces joined at distances <= distanceThreshold; with ``all_indices`` (the photo of every face) each cluster is split so
     that no two faces of one photo stay together (complete linkage on the cluster's penalised distances, cut at 50, as the reference).
     ``no_images_in_cluster`` is accepted and ignored, as that branch does.  Returns lists of face indices, longest first; clusters of
     equal length are ordered by their smallest index (the reference leaves that order to scipy's label numbering).  One face gives
     [[0]] (the reference's linkage raises on it).  Non-finite distances raise ValueError."""
+    _check_method(method)
     D = np.asarray(dist_matrix, dtype=np.float64)
     if D.ndim != 2 or D.shape[0] != D.shape[1] or D.shape[0] < 1:
         raise ValueError("dist_matrix must be a non-empty square matrix, got shape %r" % (D.shape,))
@@ -268,7 +345,7 @@ def get_facial_clusters(dist_matrix, distanceThreshold=1, all_indices=None, no_i
     n = D.shape[0]
     if n == 1:
         return [[0]]
-    groups = _groups(fcluster_distance(linkage_single_dense(D, device), distanceThreshold))
+    groups = _groups(fcluster_distance(linkage_dense(D, method, device), distanceThreshold))
     if all_indices is None:
         return _finish(groups)
     photo = np.asarray(all_indices).reshape(-1)
@@ -284,12 +361,14 @@ def get_facial_clusters(dist_matrix, distanceThreshold=1, all_indices=None, no_i
 
 
 def cluster_faces(features, distance_threshold: float, born_years=None, photo_years=None, all_indices=None,
-                  min_cluster_size: int = 1, device=None) -> List[List[int]]:
+                  min_cluster_size: int = 1, device=None, method: str = "single") -> List[List[int]]:
     """perform_clustering (process_photos.py:45-77) without the date rule, from the features: single linkage on the GPU with no N x N
-    matrix (the age term when born / photo years are given), the same-photo split on each cluster's own distances (its rows through
+    matrix (or ``method`` 'average' / 'complete' / 'weighted' on an fp64 device matrix; see linkage), the age term when born / photo
+    years are given, the same-photo split on each cluster's own distances (its rows through
     ops.pairwise_distances plus the host age term, clipped at 0, as feature_distance_matrix builds them), and clusters shorter than
     ``min_cluster_size`` dropped.  Same order as get_facial_clusters."""
     from . import _lib, ops
+    _check_method(method)
     torch = _lib.require_gpu()
     x = _device_tensor(features, torch.float32, device)
     if x.dim() != 2 or x.shape[0] < 1:
@@ -298,7 +377,7 @@ def cluster_faces(features, distance_threshold: float, born_years=None, photo_ye
     by, yr = _age_arrays(born_years, photo_years, n)
     if n == 1:
         return _finish([np.zeros(1, dtype=np.int64)], min_cluster_size)
-    Z = linkage_single(x, by, yr)
+    Z = linkage_single(x, by, yr) if method == "single" else linkage(x, method, by, yr)
     groups = _groups(fcluster_distance(Z, distance_threshold))
     if all_indices is None:
         return _finish(groups, min_cluster_size)

@@ -1385,5 +1385,18 @@ int hsefr_single_linkage(const float* x, int n, int d, const float* born, const 
     return launch_single_linkage(x, n, d, born, year, dense, edge_a, edge_b, edge_h, (hipStream_t)stream);
 }
 
+int hsefr_hier_linkage(const float* x, int n, int d, const float* born, const float* year, const double* dense, int method, int* merge_a,
+                       int* merge_b, double* merge_h, int* merge_round, hsefr_stream_t stream) {
+    HSEFR_REQUIRE(n >= 1, HSEFR_ERR_INVALID, "hier_linkage: n=%d", n);
+    HSEFR_REQUIRE(method == HSEFR_LINK_AVERAGE || method == HSEFR_LINK_COMPLETE || method == HSEFR_LINK_WEIGHTED, HSEFR_ERR_INVALID,
+                  "hier_linkage: method=%d (HSEFR_LINK_AVERAGE, _COMPLETE or _WEIGHTED)", method);
+    HSEFR_REQUIRE((x != nullptr) != (dense != nullptr), HSEFR_ERR_INVALID, "hier_linkage: pass exactly one of x and dense");
+    HSEFR_REQUIRE(merge_a && merge_b && merge_h && merge_round, HSEFR_ERR_INVALID, "hier_linkage: null pointer (merge outputs)");
+    HSEFR_REQUIRE(!born == !year, HSEFR_ERR_INVALID, "hier_linkage: born and year come together");
+    HSEFR_REQUIRE(!(dense && born), HSEFR_ERR_INVALID, "hier_linkage: the age term belongs to the features path");
+    HSEFR_REQUIRE(dense || (d > 0 && d % 8 == 0), HSEFR_ERR_INVALID, "hier_linkage: d=%d must be a positive multiple of 8", d);
+    return launch_hier_linkage(x, n, d, born, year, dense, method, merge_a, merge_b, merge_h, merge_round, (hipStream_t)stream);
+}
+
 }  // extern "C"
 #pragma GCC visibility pop

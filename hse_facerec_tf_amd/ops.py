@@ -573,6 +573,57 @@ def single_linkage_edges(x=None, dense=None, born=None, year=None):
     return ea[:n - 1], eb[:n - 1], eh[:n - 1]
 
 
+LINK_METHODS = {"average": 0, "complete": 1, "weighted": 2}     # HSEFR_LINK_AVERAGE / _COMPLETE / _WEIGHTED
+
+
+@_device_guarded
+def hier_linkage_merges(x=None, dense=None, born=None, year=None, method="average"):
+    """Average, complete or weighted linkage (hsefr_hier_linkage) -> (merge_a int32, merge_b int32, merge_h float64, merge_round int32),
+    n - 1 CUDA tensors each: merge_a < merge_b are the points whose clusters merged at height merge_h in round merge_round (the cluster
+    lives on in merge_a's slot).  The sources are single_linkage_edges': x [n,d] float32 features (zero columns pad d to a multiple of 8)
+    with optional born / year float32 [n], or dense [n,n] float64 distances read as their upper triangle.  Needs 8 n^2 bytes of device
+    workspace; returns with the current stream synchronised (the host checks the cluster count once per batch of rounds)."""
+    torch = _lib.require_gpu()
+    if method not in LINK_METHODS:
+        raise ValueError("hier_linkage_merges: method %r is not one of %s" % (method, ", ".join(sorted(LINK_METHODS))))
+    if (x is None) == (dense is None):
+        raise ValueError("hier_linkage_merges: pass exactly one of x and dense")
+    if (born is None) != (year is None):
+        raise ValueError("hier_linkage_merges: born and year come together")
+    d = 0
+    if x is not None:
+        _f32c(x, "x")
+        if x.dim() != 2:
+            raise ValueError("x must be [n, d]")
+        n, d = x.shape
+        if d % 8:
+            x = torch.nn.functional.pad(x, (0, 8 - d % 8)).contiguous()
+            d = x.shape[1]
+        for v, name in ((born, "born"), (year, "year")):
+            if v is not None and _f32c(v, name).numel() != n:
+                raise ValueError("%s has %d elements for %d rows" % (name, v.numel(), n))
+    else:
+        if born is not None:
+            raise ValueError("hier_linkage_merges: the age term belongs to the features path")
+        if not (dense.is_cuda and dense.dtype == torch.float64 and dense.is_contiguous() and dense.dim() == 2
+                and dense.shape[0] == dense.shape[1]):
+            raise ValueError("dense must be a contiguous square float64 CUDA tensor")
+        n = dense.shape[0]
+    if n < 1:
+        raise ValueError("hier_linkage_merges: no points")
+    dev = (x if x is not None else dense).device
+    m = max(n - 1, 1)
+    ma = torch.full((m,), -1, dtype=torch.int32, device=dev)
+    mb = torch.full((m,), -1, dtype=torch.int32, device=dev)
+    mh = torch.empty((m,), dtype=torch.float64, device=dev)
+    mr = torch.full((m,), -1, dtype=torch.int32, device=dev)
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    _lib.check(_lib.lib().hsefr_hier_linkage(ptr(x), n, d, ptr(born), ptr(year), ptr(dense), LINK_METHODS[method], ma.data_ptr(),
+                                             mb.data_ptr(), mh.data_ptr(), mr.data_ptr(), _lib.current_stream_ptr()),
+               "hsefr_hier_linkage")
+    return ma[:n - 1], mb[:n - 1], mh[:n - 1], mr[:n - 1]
+
+
 # ---- bf16 ResNet-50 kernels -------------------------------------------------------------------------
 def _bf16c(t, name):
     torch = _lib.require_gpu()

@@ -607,6 +607,20 @@ int hsefr_pairwise_dist(const float* x, const float* y, int n, int m, int d, flo
 int hsefr_single_linkage(const float* x, int n, int d, const float* born, const float* year, const double* dense, int* edge_a,
                          int* edge_b, double* edge_h, hsefr_stream_t stream);
 
+/* Average, complete and weighted linkage (hac.linkage(squareform(D), method) of get_facial_clusters, facial_clustering.py:241-245, for
+ * the methods of the clustering study, facial_clustering_test.py:513-514) by parallel reciprocal-nearest-neighbour rounds on an fp64
+ * n x n working matrix (csrc/hier_linkage.hip).  The sources are hsefr_single_linkage's: x [n,d] fp32 (d multiple of 8) with optional
+ * born / year, or dense [n,n] fp64 read as its upper triangle and never written.  method: HSEFR_LINK_AVERAGE (UPGMA, size-weighted
+ * mean), HSEFR_LINK_COMPLETE (max) or HSEFR_LINK_WEIGHTED (WPGMA, plain mean), with scipy's Lance-Williams updates.
+ * Outputs (device, n - 1 each): merge_a < merge_b, the slots (points) whose clusters merged -- merge_a's slot carries the union on --
+ * merge_h the height, merge_round the round; unordered within a round.  Sorting by (height, round, merge_a) and joining by union-find
+ * gives scipy's Z.  Workspace 8 n^2 + O(n) bytes, stream-ordered, refused (HSEFR_ERR_NOMEM) before any launch; the host reads a device
+ * count once per batch of rounds, so the call returns with the stream synchronised.  Arguments are checked before any device call
+ * (HSEFR_ERR_INVALID). */
+enum { HSEFR_LINK_AVERAGE = 0, HSEFR_LINK_COMPLETE = 1, HSEFR_LINK_WEIGHTED = 2 };
+int hsefr_hier_linkage(const float* x, int n, int d, const float* born, const float* year, const double* dense, int method, int* merge_a,
+                       int* merge_b, double* merge_h, int* merge_round, hsefr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,9 @@
 """GPU time of single-linkage clustering from features (hsefr_single_linkage, csrc/linkage.hip: Boruvka rounds, no N x N matrix) for
 n in {2048, 9164, 32768} x d in {1024, 2048}, with the rounds the tree actually needed and the time per round, next to the host path it
 replaces (identification.feature_distance_matrix + scipy's single linkage on the dense matrix, up to n = 9164).
-usage: python tools/linkage_time.py [--out FILE]"""
+With --method average / complete / weighted: hsefr_hier_linkage (csrc/hier_linkage.hip: the fp64 n x n matrix, then reciprocal
+nearest-neighbour rounds) for n in {2048, 9164}, against the host matrix + scipy's linkage of the same method.
+usage: python tools/linkage_time.py [--method M] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -72,21 +74,60 @@ def gpu_ms(x, reps):
     return e0.elapsed_time(e1) / reps, out
 
 
-def host_s(xh):
+def host_s(xh, method="single"):
     from scipy.cluster import hierarchy as hac
     from scipy.spatial.distance import squareform
     t0 = time.perf_counter()
     D = identification.feature_distance_matrix(xh)
     t1 = time.perf_counter()
-    hac.linkage(squareform(D, checks=False), "single")
+    hac.linkage(squareform(D, checks=False), method)
     t2 = time.perf_counter()
     return t1 - t0, t2 - t1
+
+
+def hier_ms(x, method, reps):
+    ops.hier_linkage_merges(x=x, method=method)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        out = ops.hier_linkage_merges(x=x, method=method)
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps, out
+
+
+def main_hier(method, out):
+    lines = ["# %s-linkage clustering from unit-norm features, fp32 distances in an fp64 matrix (tools/linkage_time.py --method %s); %s"
+             % (method, method, torch.cuda.get_device_name(0)),
+             "# GPU: hsefr_hier_linkage, CUDA-event time per call (mean of reps after one warm-up): matrix build + reciprocal-NN rounds",
+             "# rounds = rounds the tree needed (launched in batches of 32); ms_per_round = gpu_ms / rounds, the matrix build included",
+             "# host: identification.feature_distance_matrix (GPU distances + copy to a host float64 matrix) + scipy linkage '%s'" % method,
+             "%7s %5s %11s %9s %13s %12s %12s %10s" % ("n", "d", "gpu_ms", "rounds", "ms_per_round", "host_D_s", "host_link_s",
+                                                      "speedup")]
+    for n in (2048, 9164):
+        for d in DIMS:
+            x = unit_rows(n, d, n + d)
+            ms, (a, b, h, r) = hier_ms(x, method, 3)
+            rounds = int(r.max().item()) + 1
+            hd, hl = host_s(x.cpu().numpy(), method)
+            lines.append("%7d %5d %11.2f %9d %13.3f %12.3f %12.3f %10.1f" % (n, d, ms, rounds, ms / rounds, hd, hl,
+                                                                            (hd + hl) * 1e3 / ms))
+            print(lines[-1], flush=True)
+    text = "\n".join(lines) + "\n"
+    if out:
+        with open(out, "w") as f:
+            f.write(text)
+    print(text)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
+    ap.add_argument("--method", default="single", choices=["single", "average", "complete", "weighted"])
     args = ap.parse_args()
+    if args.method != "single":
+        return main_hier(args.method, args.out)
     lines = ["# single-linkage clustering from unit-norm features, fp32 (tools/linkage_time.py); %s" % torch.cuda.get_device_name(0),
              "# GPU: hsefr_single_linkage, CUDA-event time per call (mean of reps after one warm-up); rounds launched = ceil(log2 n)",
              "# host: identification.feature_distance_matrix (GPU distances + copy to a host float64 matrix) + scipy linkage 'single'",
