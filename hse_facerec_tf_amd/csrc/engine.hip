@@ -67,16 +67,50 @@ struct hsefr_engine {
     long long graph_launches = 0;
 };
 
+static const void* blob_ptr(const hsefr_engine* e, uint64_t off) {
+    return off == HSEFR_NO_OFFSET ? nullptr : (const void*)(e->d_blob + off);
+}
+
+// ---- the packed parts of a plan op (include/hsefr.h), decoded here only; the decoders check nothing, validate_plan does ----
+static int field(int32_t word, int shift, int bits) { return (int)(((uint32_t)word >> shift) & ((1u << bits) - 1)); }
+struct Geometry { int c2, stride2, h2, w2; };      // the aux word of a projected shortcut or a strided residual
+static Geometry geometry(int32_t aux) {
+    return {field(aux, HSEFR_AUX_C2_SHIFT, HSEFR_AUX_C2_BITS), field(aux, HSEFR_AUX_STRIDE2_SHIFT, HSEFR_AUX_STRIDE2_BITS),
+            field(aux, HSEFR_AUX_H2_SHIFT, HSEFR_AUX_H2_BITS), field(aux, HSEFR_AUX_W2_SHIFT, HSEFR_AUX_W2_BITS)};
+}
+struct PsDwAux { int a_log2, out_log2; };         // PWCONV_PS_DW
+static PsDwAux ps_dw_aux(int32_t aux) { return {field(aux, 0, HSEFR_AUX_LOG2_BITS), aux >> HSEFR_AUX_OUT_LOG2_SHIFT}; }
+struct StemAux { int a_log2, in_log2, u8; };      // STEM3_F16S
+static StemAux stem_aux(int32_t aux) {
+    return {field(aux, 0, HSEFR_AUX_LOG2_BITS), field(aux, HSEFR_AUX_IN_LOG2_SHIFT, HSEFR_AUX_LOG2_BITS) - HSEFR_AUX_IN_LOG2_BIAS,
+            field(aux, HSEFR_AUX_U8_BIT, 1)};
+}
+struct PoolPads { int t, l; };                     // STEM7X7_POOL_BF16
+static PoolPads pool_pads(int32_t aux) { return {field(aux, 0, 1), field(aux, HSEFR_AUX_POOL_PAD_L_SHIFT, 1)}; }
+struct StemKw { int k, pad_t2, pad_l2; };         // the kw field of STEM2_F16S / STEM3_F16S
+static StemKw stem_kw(int32_t kw) {
+    return {field(kw, 0, HSEFR_STEM_KW_PAD_T2_BIT), field(kw, HSEFR_STEM_KW_PAD_T2_BIT, 1), field(kw, HSEFR_STEM_KW_PAD_L2_BIT, 1)};
+}
+// a stem's constant pack (w_off; the STEM3 segments exist in a STEM3_F16S pack only) and its shift2 block (descale, pshift)
+struct StemPack {
+    const float *conv, *conv_shift, *dw1, *dw1_scale, *dw1_shift, *dw2, *dw2_scale, *dw2_shift, *conv_split, *conv_descale, *conv4, *conv4_u8,
+        *u8_shift, *u8_descale, *descale, *pshift;
+};
+static StemPack stem_pack(const hsefr_engine* e, const hsefr_plan_op& o) {
+    const float *pk = (const float*)blob_ptr(e, o.w_off), *s2 = (const float*)blob_ptr(e, o.shift2_off);
+    return {pk + HSEFR_STEM_PACK_CONV, pk + HSEFR_STEM_PACK_CONV_SHIFT, pk + HSEFR_STEM_PACK_DW1, pk + HSEFR_STEM_PACK_DW1_SCALE,
+            pk + HSEFR_STEM_PACK_DW1_SHIFT, pk + HSEFR_STEM_PACK_DW2, pk + HSEFR_STEM_PACK_DW2_SCALE, pk + HSEFR_STEM_PACK_DW2_SHIFT,
+            pk + HSEFR_STEM_PACK_CONV_SPLIT, pk + HSEFR_STEM_PACK_CONV_DESCALE, pk + HSEFR_STEM_PACK_CONV4, pk + HSEFR_STEM_PACK_CONV4_U8,
+            pk + HSEFR_STEM_PACK_U8_SHIFT, pk + HSEFR_STEM_PACK_U8_DESCALE, s2 + HSEFR_STEM_SHIFT2_DESCALE, s2 + HSEFR_STEM_SHIFT2_SHIFT};
+}
+
 // stem4_fused.hip hard-codes TensorFlow's SAME geometry for inputs whose edges are multiples of 4 (conv1 and the stride-2
 // depthwise pad at the bottom / right only, H1 = h / 2, OH2 = h / 4) and its uint8 mean-folded shifts assume it too: an op with
 // any other padding (VALID, a hand-made plan) keeps stem3_fused.hip, which honours pad_t / pad_l / pad3 / oh / ow.
 static bool stem4_route(const hsefr_plan_op& o) {
-    return stem4_fused_supported(o.cin, 32, o.cout, o.stride, 1, 2, o.kh, o.kw & 15, o.h, o.w) && o.pad_t == 0 && o.pad_l == 0 &&
-           ((o.kw >> 4) & 3) == 0 && o.oh == o.h / 4 && o.ow == o.w / 4;
-}
-
-static const void* blob_ptr(const hsefr_engine* e, uint64_t off) {
-    return off == HSEFR_NO_OFFSET ? nullptr : (const void*)(e->d_blob + off);
+    const StemKw kw = stem_kw(o.kw);
+    return stem4_fused_supported(o.cin, 32, o.cout, o.stride, 1, 2, o.kh, kw.k, o.h, o.w) && o.pad_t == 0 && o.pad_l == 0 && kw.pad_t2 == 0 &&
+           kw.pad_l2 == 0 && o.oh == o.h / 4 && o.ow == o.w / 4;
 }
 
 // Buffer table of ONE forward: the engine's activation buffers, with the buffers of the requested outputs replaced by
@@ -140,6 +174,7 @@ static int validate_plan(const hsefr_plan_header& h, const hsefr_plan_buffer* bu
             return false;
         };
         const uint64_t co = o.cout, ci = o.cin, kk = (uint64_t)o.kh * o.kw;
+        const Geometry g = geometry(o.aux);       // (CONV_BF16 / CONV_F32 only)
         switch (o.kind) {
             case HSEFR_OP_GAP: case HSEFR_OP_SOFTMAX: case HSEFR_OP_MAXPOOL_BF16: case HSEFR_OP_GAP_BF16: case HSEFR_OP_MAXPOOL_F32:
                 break;
@@ -148,13 +183,12 @@ static int validate_plan(const hsefr_plan_header& h, const hsefr_plan_buffer* bu
                 if (o.scale_off != HSEFR_NO_OFFSET && !need(o.scale_off, co * 4, "scale")) return HSEFR_ERR_INVALID;
                 if (o.shift_off != HSEFR_NO_OFFSET && !need(o.shift_off, co * 4, "shift")) return HSEFR_ERR_INVALID;
                 HSEFR_REQUIRE(o.cout % 4 == 0, HSEFR_ERR_UNSUPPORTED, "plan op %u: fp32 convolution with cout=%d (must be a multiple of 4)", i, o.cout);
-                if (o.reserved != 0) {      // strided residual, as HSEFR_OP_CONV_BF16's (round 6): only the fp32-MFMA kernel reads one
-                    const int k2 = o.reserved & 0xFFF, st2 = (o.reserved >> 12) & 3, h2 = (o.reserved >> 14) & 0x1FF, w2 = (o.reserved >> 23) & 0x1FF;
-                    HSEFR_REQUIRE(k2 == 0 && o.kh == 1 && o.kw == 1 && o.stride == 1 && o.pad_t == 0 && o.pad_l == 0 && o.res_buf >= 0 && st2 >= 1 &&
-                                      o.oh == o.h && o.ow == o.w && o.oh * o.ow > 1 && o.ow > 1 && (o.oh - 1) * st2 < h2 && (o.ow - 1) * st2 < w2 &&
-                                      conv_f32_mfma_supported(o.cin, o.cout),
-                                  HSEFR_ERR_INVALID, "plan op %u: bad strided residual (stride %d, %dx%d)", i, st2, h2, w2);
-                    HSEFR_REQUIRE((uint64_t)h2 * w2 * co * 4 <= bufs[o.res_buf].elems_per_image * bufs[o.res_buf].elem_bytes, HSEFR_ERR_INVALID,
+                if (o.aux != 0) {      // strided residual, as HSEFR_OP_CONV_BF16's (round 6): only the fp32-MFMA kernel reads one
+                    HSEFR_REQUIRE(g.c2 == 0 && o.kh == 1 && o.kw == 1 && o.stride == 1 && o.pad_t == 0 && o.pad_l == 0 && o.res_buf >= 0 && g.stride2 >= 1 &&
+                                      o.oh == o.h && o.ow == o.w && o.oh * o.ow > 1 && o.ow > 1 && (o.oh - 1) * g.stride2 < g.h2 &&
+                                      (o.ow - 1) * g.stride2 < g.w2 && conv_f32_mfma_supported(o.cin, o.cout),
+                                  HSEFR_ERR_INVALID, "plan op %u: bad strided residual (stride %d, %dx%d)", i, g.stride2, g.h2, g.w2);
+                    HSEFR_REQUIRE((uint64_t)g.h2 * g.w2 * co * 4 <= bufs[o.res_buf].elems_per_image * bufs[o.res_buf].elem_bytes, HSEFR_ERR_INVALID,
                                   "plan op %u: strided residual exceeds buffer %d", i, o.res_buf);
                 }
                 break;
@@ -164,7 +198,7 @@ static int validate_plan(const hsefr_plan_header& h, const hsefr_plan_buffer* bu
             case HSEFR_OP_DWCONV3X3:
                 if (!need(o.w_off, 9 * ci * 4, "kernel") || !need(o.scale_off, ci * 4, "scale") || !need(o.shift_off, ci * 4, "shift"))
                     return HSEFR_ERR_INVALID;
-                HSEFR_REQUIRE(o.reserved == 0 || (o.reserved > 0 && o.reserved <= 12 && o.act == HSEFR_ACT_RELU6 && o.cin % 32 == 0),
+                HSEFR_REQUIRE(o.aux == 0 || (o.aux > 0 && o.aux <= 12 && o.act == HSEFR_ACT_RELU6 && o.cin % 32 == 0),
                               HSEFR_ERR_INVALID, "plan op %u: split-row depthwise output needs ReLU6, c %% 32 == 0 and a_log2 in [1, 12]", i);
                 break;
             case HSEFR_OP_PWCONV_F32:
@@ -178,28 +212,25 @@ static int validate_plan(const hsefr_plan_header& h, const hsefr_plan_buffer* bu
                 if (!need(o.w_off, kk * ci * co * 2, "kernel") || !need(o.scale_off, co * 4, "scale") || !need(o.shift_off, co * 4, "shift"))
                     return HSEFR_ERR_INVALID;
                 if (o.w2_off != HSEFR_NO_OFFSET) {
-                    // projected shortcut (round 5): res_buf is the BLOCK INPUT [h2, w2, k2], w2 its 1x1 kernel [cout][k2], shift2 =
-                    // [scale2 | shift2]; reserved = k2 | stride << 12 | h2 << 14 | w2 << 23
-                    const int k2 = o.reserved & 0xFFF, st2 = (o.reserved >> 12) & 3, h2 = (o.reserved >> 14) & 0x1FF, w2 = (o.reserved >> 23) & 0x1FF;
-                    HSEFR_REQUIRE(o.kh == 1 && o.kw == 1 && o.stride == 1 && o.res_buf >= 0 && k2 > 0 && k2 % 64 == 0 && st2 >= 1 &&
-                                      (o.oh - 1) * st2 < h2 && (o.ow - 1) * st2 < w2,
-                                  HSEFR_ERR_INVALID, "plan op %u: bad projected shortcut (k2 %d, stride %d, %dx%d)", i, k2, st2, h2, w2);
-                    if (!need(o.w2_off, (uint64_t)k2 * co * 2, "projection kernel") || !need(o.shift2_off, 2 * co * 4, "projection scale / shift"))
+                    // projected shortcut (round 5): res_buf is the BLOCK INPUT [h2, w2, c2], w2 its 1x1 kernel [cout][c2], shift2 = [scale2 | shift2]
+                    HSEFR_REQUIRE(o.kh == 1 && o.kw == 1 && o.stride == 1 && o.res_buf >= 0 && g.c2 > 0 && g.c2 % 64 == 0 && g.stride2 >= 1 &&
+                                      (o.oh - 1) * g.stride2 < g.h2 && (o.ow - 1) * g.stride2 < g.w2,
+                                  HSEFR_ERR_INVALID, "plan op %u: bad projected shortcut (k2 %d, stride %d, %dx%d)", i, g.c2, g.stride2, g.h2, g.w2);
+                    if (!need(o.w2_off, (uint64_t)g.c2 * co * 2, "projection kernel") || !need(o.shift2_off, 2 * co * 4, "projection scale / shift"))
                         return HSEFR_ERR_INVALID;
-                    HSEFR_REQUIRE((uint64_t)h2 * w2 * k2 * 2 <= bufs[o.res_buf].elems_per_image * bufs[o.res_buf].elem_bytes, HSEFR_ERR_INVALID,
+                    HSEFR_REQUIRE((uint64_t)g.h2 * g.w2 * g.c2 * 2 <= bufs[o.res_buf].elems_per_image * bufs[o.res_buf].elem_bytes, HSEFR_ERR_INVALID,
                                   "plan op %u: projected shortcut input exceeds buffer %d", i, o.res_buf);
-                } else if (o.reserved != 0) {
-                    // strided residual (round 6): res_buf is a LARGER map [h2, w2, cout] read at every stride-th pixel; reserved = stride << 12 | h2 << 14 | w2 << 23
-                    const int k2 = o.reserved & 0xFFF, st2 = (o.reserved >> 12) & 3, h2 = (o.reserved >> 14) & 0x1FF, w2 = (o.reserved >> 23) & 0x1FF;
-                    HSEFR_REQUIRE(k2 == 0 && o.kh == 1 && o.kw == 1 && o.stride == 1 && o.pad_t == 0 && o.pad_l == 0 && o.res_buf >= 0 && st2 >= 1 &&
-                                      o.oh == o.h && o.ow == o.w && o.oh * o.ow > 1 && o.ow > 1 && (o.oh - 1) * st2 < h2 && (o.ow - 1) * st2 < w2,
-                                  HSEFR_ERR_INVALID, "plan op %u: bad strided residual (stride %d, %dx%d)", i, st2, h2, w2);
-                    HSEFR_REQUIRE((uint64_t)h2 * w2 * co * 2 <= bufs[o.res_buf].elems_per_image * bufs[o.res_buf].elem_bytes, HSEFR_ERR_INVALID,
+                } else if (o.aux != 0) {
+                    // strided residual (round 6): res_buf is a LARGER map [h2, w2, cout] read at every stride-th pixel
+                    HSEFR_REQUIRE(g.c2 == 0 && o.kh == 1 && o.kw == 1 && o.stride == 1 && o.pad_t == 0 && o.pad_l == 0 && o.res_buf >= 0 && g.stride2 >= 1 &&
+                                      o.oh == o.h && o.ow == o.w && o.oh * o.ow > 1 && o.ow > 1 && (o.oh - 1) * g.stride2 < g.h2 && (o.ow - 1) * g.stride2 < g.w2,
+                                  HSEFR_ERR_INVALID, "plan op %u: bad strided residual (stride %d, %dx%d)", i, g.stride2, g.h2, g.w2);
+                    HSEFR_REQUIRE((uint64_t)g.h2 * g.w2 * co * 2 <= bufs[o.res_buf].elems_per_image * bufs[o.res_buf].elem_bytes, HSEFR_ERR_INVALID,
                                   "plan op %u: strided residual exceeds buffer %d", i, o.res_buf);
                 }
                 break;
             case HSEFR_OP_STEM7X7_POOL_BF16:
-                HSEFR_REQUIRE(o.act == HSEFR_ACT_RELU && (o.reserved & ~0x11) == 0 && o.cin == 3 && o.cout == 64, HSEFR_ERR_INVALID,
+                HSEFR_REQUIRE(o.act == HSEFR_ACT_RELU && (o.aux & ~(1 | 1 << HSEFR_AUX_POOL_PAD_L_SHIFT)) == 0 && o.cin == 3 && o.cout == 64, HSEFR_ERR_INVALID,
                               "plan op %u: fused stem + pool needs ReLU, 3 -> 64 channels and pool pads in {0, 1}", i);
                 [[fallthrough]];
             case HSEFR_OP_STEM7X7_BF16:
@@ -211,7 +242,7 @@ static int validate_plan(const hsefr_plan_header& h, const hsefr_plan_buffer* bu
                               "plan op %u: fused pointwise + global pool on a %dx%d map not covered (33 .. 288 pixels)", i, o.h, o.w);
                 if (!need(o.w_off, ci * co * 4, "split rows") || !need(o.scale_off, co * 4, "descale") || !need(o.shift_off, co * 4, "shift"))
                     return HSEFR_ERR_INVALID;
-                HSEFR_REQUIRE(o.reserved > 0 && o.reserved <= 24, HSEFR_ERR_INVALID, "plan op %u: a_log2 out of range (reserved %d)", i, o.reserved);
+                HSEFR_REQUIRE(o.aux > 0 && o.aux <= 24, HSEFR_ERR_INVALID, "plan op %u: a_log2 out of range (reserved %d)", i, o.aux);
                 break;
             case HSEFR_OP_PWCONV_PS_DW:
                 HSEFR_REQUIRE(pwconv_ps_dw_supported(0, o.cin, o.cout, o.w, o.h * o.w, o.stride) && o.oh * o.stride == o.h && o.ow * o.stride == o.w &&
@@ -220,8 +251,11 @@ static int validate_plan(const hsefr_plan_header& h, const hsefr_plan_buffer* bu
                 if (!need(o.w_off, ci * co * 4, "split rows") || !need(o.scale_off, co * 4, "descale") || !need(o.shift_off, co * 4, "shift") ||
                     !need(o.w2_off, 11 * co * 4, "depthwise constants"))
                     return HSEFR_ERR_INVALID;
-                HSEFR_REQUIRE((o.reserved & 255) > 0 && (o.reserved & 255) <= 24 && (o.reserved >> 8) >= 1 && (o.reserved >> 8) <= 12,
-                              HSEFR_ERR_INVALID, "plan op %u: a_log2 / out_log2 out of range (reserved %d)", i, o.reserved);
+                {
+                    const PsDwAux a = ps_dw_aux(o.aux);
+                    HSEFR_REQUIRE(a.a_log2 > 0 && a.a_log2 <= 24 && a.out_log2 >= 1 && a.out_log2 <= 12,
+                                  HSEFR_ERR_INVALID, "plan op %u: a_log2 / out_log2 out of range (reserved %d)", i, o.aux);
+                }
                 break;
             case HSEFR_OP_PWCONV_PS:
                 HSEFR_REQUIRE(pwconv_ps_supported(0, o.cin, o.cout), HSEFR_ERR_UNSUPPORTED,
@@ -231,21 +265,23 @@ static int validate_plan(const hsefr_plan_header& h, const hsefr_plan_buffer* bu
                 if (!need(o.w_off, ci * co * 4, "split rows") || !need(o.scale_off, co * 4, "descale") || !need(o.shift_off, co * 4, "shift"))
                     return HSEFR_ERR_INVALID;
                 HSEFR_REQUIRE(o.w_off != HSEFR_NO_OFFSET && o.scale_off != HSEFR_NO_OFFSET && o.shift_off != HSEFR_NO_OFFSET &&
-                                  o.reserved > 0 && o.reserved <= 24,
+                                  o.aux > 0 && o.aux <= 24,
                               HSEFR_ERR_INVALID, "plan op %u: split-f16 pointwise needs split rows, descale, shift and a_log2 in (0, 24]", i);
                 break;
-            case HSEFR_OP_STEM3_F16S:
-                HSEFR_REQUIRE(stem3_fused_supported(o.cin, 32, o.cout, o.stride, 1, 2, o.kh, o.kw & 15) && (o.reserved & 255) > 0 &&
-                                  (o.reserved & 255) <= 12 && ((o.reserved >> 8) & 255) >= 64 - 8 && ((o.reserved >> 8) & 255) <= 64 + 14 &&
+            case HSEFR_OP_STEM3_F16S: {
+                const StemAux a = stem_aux(o.aux);
+                HSEFR_REQUIRE(stem3_fused_supported(o.cin, 32, o.cout, o.stride, 1, 2, o.kh, stem_kw(o.kw).k) && a.a_log2 > 0 && a.a_log2 <= 12 &&
+                                  a.in_log2 >= -8 && a.in_log2 <= 14 &&
                                   o.w_off != HSEFR_NO_OFFSET && o.w2_off != HSEFR_NO_OFFSET && o.shift2_off != HSEFR_NO_OFFSET &&
-                                  o.w_off + 7264 * 4 <= h.blob_bytes && o.w2_off + 64 * 128 <= h.blob_bytes &&
+                                  o.w_off + HSEFR_STEM_PACK_STEM3_END * 4 <= h.blob_bytes && o.w2_off + 64 * 128 <= h.blob_bytes &&
                                   o.shift2_off + 128 * 4 <= h.blob_bytes && o.in_buf == HSEFR_BUF_INPUT,
                               HSEFR_ERR_UNSUPPORTED, "plan op %u: bounded fused stem cin=%d cout=%d stride=%d not covered", i, o.cin, o.cout, o.stride);
                 break;
+            }
             case HSEFR_OP_STEM2_F16S:
-                HSEFR_REQUIRE(stem2_fused_supported(o.cin, 32, o.cout, o.stride, 1, 2, o.kh, o.kw & 15) && o.reserved > 0 && o.reserved <= 12 &&
+                HSEFR_REQUIRE(stem2_fused_supported(o.cin, 32, o.cout, o.stride, 1, 2, o.kh, stem_kw(o.kw).k) && o.aux > 0 && o.aux <= 12 &&
                                   o.w_off != HSEFR_NO_OFFSET && o.w2_off != HSEFR_NO_OFFSET && o.shift2_off != HSEFR_NO_OFFSET &&
-                                  o.w_off + 1952 * 4 <= h.blob_bytes && o.in_buf == HSEFR_BUF_INPUT,
+                                  o.w_off + HSEFR_STEM_PACK_STEM2_END * 4 <= h.blob_bytes && o.in_buf == HSEFR_BUF_INPUT,
                               HSEFR_ERR_UNSUPPORTED, "plan op %u: fused stem+dw2 cin=%d cout=%d stride=%d not covered", i, o.cin, o.cout, o.stride);
                 break;
             case HSEFR_OP_STEM_F16S:
@@ -253,9 +289,9 @@ static int validate_plan(const hsefr_plan_header& h, const hsefr_plan_buffer* bu
                 set_error("plan op %u: HSEFR_OP_STEM_F16S (round 1's fused stem) runs on development builds of the library only", i);
                 return HSEFR_ERR_UNSUPPORTED;
 #else
-                HSEFR_REQUIRE(stem_fused_supported(o.cin, 32, o.cout, o.stride, 1, o.kh, o.kw) && o.reserved > 0 && o.reserved <= 12 &&
+                HSEFR_REQUIRE(stem_fused_supported(o.cin, 32, o.cout, o.stride, 1, o.kh, o.kw) && o.aux > 0 && o.aux <= 12 &&
                                   o.w_off != HSEFR_NO_OFFSET && o.w2_off != HSEFR_NO_OFFSET && o.shift2_off != HSEFR_NO_OFFSET &&
-                                  o.w_off + 1248 * 4 <= h.blob_bytes && o.in_buf == HSEFR_BUF_INPUT,
+                                  o.w_off + HSEFR_STEM_PACK_DW2 * 4 <= h.blob_bytes && o.in_buf == HSEFR_BUF_INPUT,
                               HSEFR_ERR_UNSUPPORTED, "plan op %u: fused stem cin=%d cout=%d stride=%d not covered", i, o.cin, o.cout, o.stride);
                 break;
 #endif
@@ -263,11 +299,11 @@ static int validate_plan(const hsefr_plan_header& h, const hsefr_plan_buffer* bu
                 if (!need(o.w_off, 9 * ci * 4, "depthwise kernel") || !need(o.scale_off, ci * 4, "scale") || !need(o.shift_off, ci * 4, "shift") ||
                     !need(o.w2_off, ci * co * 4, "split rows") || !need(o.shift2_off, 2 * co * 4, "descale | shift"))
                     return HSEFR_ERR_INVALID;
-                HSEFR_REQUIRE(dwpw_f16s_supported(o.cin, o.cout, o.stride) && o.reserved > 0 && o.reserved <= 12 &&
+                HSEFR_REQUIRE(dwpw_f16s_supported(o.cin, o.cout, o.stride) && o.aux > 0 && o.aux <= 12 &&
                                   o.w_off != HSEFR_NO_OFFSET && o.scale_off != HSEFR_NO_OFFSET && o.shift_off != HSEFR_NO_OFFSET &&
                                   o.w2_off != HSEFR_NO_OFFSET && o.shift2_off != HSEFR_NO_OFFSET,
                               HSEFR_ERR_UNSUPPORTED, "plan op %u: split-f16 fused block cin=%d cout=%d stride=%d a_log2=%d not covered",
-                              i, o.cin, o.cout, o.stride, o.reserved);
+                              i, o.cin, o.cout, o.stride, o.aux);
                 break;
             case HSEFR_OP_DWPW_F32:
                 if (!need(o.w_off, 9 * ci * 4, "depthwise kernel") || !need(o.scale_off, ci * 4, "scale") || !need(o.shift_off, ci * 4, "shift") ||
@@ -290,14 +326,15 @@ static int validate_plan(const hsefr_plan_header& h, const hsefr_plan_buffer* bu
             HSEFR_REQUIRE(i + 1 < h.n_ops, HSEFR_ERR_INVALID, "plan op %u: PAIR_NEXT on the last op", i);
             const hsefr_plan_op& b = ops[i + 1];
             const bool proj = o.w2_off != HSEFR_NO_OFFSET;
-            const int c2 = proj ? (o.reserved & 0xFFF) : 0, st2 = (o.reserved >> 12) & 3, h2 = (o.reserved >> 14) & 0x1FF, w2 = (o.reserved >> 23) & 0x1FF;
+            const Geometry g = geometry(o.aux);
+            const int c2 = proj ? g.c2 : 0;
             const bool sub2 = (o.flags & HSEFR_OPF_OUT_SUB2) != 0;      // the first output is stored at even rows / columns only; the second op reads all of it
             HSEFR_REQUIRE(o.kind == HSEFR_OP_CONV_BF16 && b.kind == HSEFR_OP_CONV_BF16 && o.kh == 1 && o.kw == 1 && o.stride == 1 && o.pad_t == 0 &&
                               o.pad_l == 0 && (sub2 ? (o.oh == (o.h + 1) / 2 && o.ow == (o.w + 1) / 2 && o.h > 1 && o.w > 1) : (o.oh == o.h && o.ow == o.w)) &&
                               b.kh == 1 && b.kw == 1 && b.stride == 1 && b.pad_t == 0 && b.pad_l == 0 &&
                               b.h == o.h && b.w == o.w && b.oh == b.h && b.ow == b.w && b.cin == o.cout && b.in_buf == o.out_buf &&
                               b.res_buf == HSEFR_BUF_NONE && b.w2_off == HSEFR_NO_OFFSET && b.flags == 0 && o.res_buf >= 0 &&
-                              (!proj || (st2 == 1 && h2 == o.h && w2 == o.w)),
+                              (!proj || (g.stride2 == 1 && g.h2 == o.h && g.w2 == o.w)),
                           HSEFR_ERR_INVALID, "plan op %u: PAIR_NEXT needs two 1x1 stride-1 bf16 convolutions at the same pixels, the first with a residual "
                           "or a same-pixel projected shortcut, the second reading the first", i);
             HSEFR_REQUIRE(b.out_buf != o.in_buf && b.out_buf != o.res_buf && b.out_buf != o.out_buf, HSEFR_ERR_INVALID,
@@ -661,8 +698,10 @@ static int run_ops(hsefr_engine* e, const std::vector<void*>& tab, const void* d
         size_t covered = 0;       // ops behind this one that its launch computes as well (hsefr_op_flags)
         set_sweep_reverse(g_sweep_alternate ? (int)(launches++ & 1) : 0);   // consecutive LAUNCHES sweep in opposite directions (common.h)
         const bool sub2 = (o.flags & HSEFR_OPF_OUT_SUB2) != 0;
+        const Geometry g = geometry(o.aux);                                     // (CONV_BF16 / CONV_F32 only)
+        const int c2 = o.w2_off != HSEFR_NO_OFFSET ? g.c2 : 0;                  // a projected shortcut's input channels
         const bool pair_ok = (o.flags & HSEFR_OPF_PAIR_NEXT) && needed[i + 1] &&
-                             conv1x1_pair_bf16_supported((long long)n * o.h * o.w, o.cin, o.cout, e->ops[i + 1].cout, o.w2_off != HSEFR_NO_OFFSET ? (o.reserved & 0xFFF) : 0);
+                             conv1x1_pair_bf16_supported((long long)n * o.h * o.w, o.cin, o.cout, e->ops[i + 1].cout, c2);
         HSEFR_REQUIRE(!sub2 || pair_ok, HSEFR_ERR_UNSUPPORTED, "forward: op %zu stores its output at every second pixel (OUT_SUB2) and cannot run without the pair launch", i);
         if (pair_ok) {
             // increase (+ residual | + projected shortcut) -> the next block's reduce in one launch (csrc/conv1x1_pair_bf16.hip; the pattern
@@ -674,7 +713,7 @@ static int run_ops(hsefr_engine* e, const std::vector<void*>& tab, const void* d
                                           proj ? nullptr : tab[o.res_buf], proj ? tab[o.res_buf] : nullptr, proj ? blob_ptr(e, o.w2_off) : nullptr,
                                           proj ? ssp : nullptr, proj ? ssp + o.cout : nullptr, out, blob_ptr(e, b.w_off),
                                           (const float*)blob_ptr(e, b.scale_off), (const float*)blob_ptr(e, b.shift_off), tab[b.out_buf],
-                                          (long long)n * o.h * o.w, o.cin, o.cout, b.cout, proj ? (o.reserved & 0xFFF) : 0, o.act, b.act, s, sub2 ? 2 : 1, o.h, o.w);
+                                          (long long)n * o.h * o.w, o.cin, o.cout, b.cout, c2, o.act, b.act, s, sub2 ? 2 : 1, o.h, o.w);
             covered = 1;
         } else if ((o.flags & HSEFR_OPF_HEADS) && !g_heads_off && needed[i + 1] && needed[i + 2] && needed[i + 3]) {
             // the age / gender heads in one launch (csrc/pool_dense.hip): hidden, logits, probabilities and the gender sigmoid are all written
@@ -692,10 +731,10 @@ static int run_ops(hsefr_engine* e, const std::vector<void*>& tab, const void* d
                                     o.stride, o.pad_t, o.pad_l, o.oh, o.ow, o.cout, o.act, s);
                 break;
             case HSEFR_OP_DWCONV3X3:
-                if (o.reserved > 0)
+                if (o.aux > 0)
                     rc = launch_dwconv3x3_split((const float*)in, (const float*)blob_ptr(e, o.w_off),
                                                 (const float*)blob_ptr(e, o.scale_off), (const float*)blob_ptr(e, o.shift_off),
-                                                out, n, o.h, o.w, o.cin, o.stride, o.pad_t, o.pad_l, o.oh, o.ow, o.act, o.reserved, s);
+                                                out, n, o.h, o.w, o.cin, o.stride, o.pad_t, o.pad_l, o.oh, o.ow, o.act, o.aux, s);
                 else
                     rc = launch_dwconv3x3((const float*)in, (const float*)blob_ptr(e, o.w_off),
                                           (const float*)blob_ptr(e, o.scale_off), (const float*)blob_ptr(e, o.shift_off),
@@ -708,7 +747,7 @@ static int run_ops(hsefr_engine* e, const std::vector<void*>& tab, const void* d
             case HSEFR_OP_PWCONV_PS_DW:
                 rc = launch_pwconv_ps_dw(in, blob_ptr(e, o.w_off), (const float*)blob_ptr(e, o.scale_off), (const float*)blob_ptr(e, o.shift_off),
                                          (const float*)blob_ptr(e, o.w2_off), out, (long long)n * o.h * o.w, o.cin, o.cout, o.act, o.w,
-                                         o.h * o.w, o.stride, o.reserved >> 8, s);
+                                         o.h * o.w, o.stride, ps_dw_aux(o.aux).out_log2, s);
                 break;
             case HSEFR_OP_PWCONV_PS:
                 rc = launch_pwconv_ps(in, blob_ptr(e, o.w_off), (const float*)blob_ptr(e, o.scale_off),
@@ -723,7 +762,7 @@ static int run_ops(hsefr_engine* e, const std::vector<void*>& tab, const void* d
             case HSEFR_OP_PWCONV_F16S:
                 rc = launch_pwconv_f16s((const float*)in, blob_ptr(e, o.w_off), (const float*)blob_ptr(e, o.scale_off),
                                         (const float*)blob_ptr(e, o.shift_off), (float*)out, (long long)n * o.h * o.w,
-                                        o.cin, o.cout, o.reserved, o.act, s);
+                                        o.cin, o.cout, o.aux, o.act, s);
                 break;
             case HSEFR_OP_GAP:
                 rc = launch_gap((const float*)in, (float*)out, n, o.h * o.w, o.cin, s);
@@ -740,14 +779,12 @@ static int run_ops(hsefr_engine* e, const std::vector<void*>& tab, const void* d
                     const float* ss2 = (const float*)blob_ptr(e, o.shift2_off);
                     rc = launch_conv1x1_proj_bf16(in, blob_ptr(e, o.w_off), (const float*)blob_ptr(e, o.scale_off),
                                                   (const float*)blob_ptr(e, o.shift_off), tab[o.res_buf], blob_ptr(e, o.w2_off), ss2, ss2 + o.cout,
-                                                  out, n, o.oh, o.ow, o.cin, o.cout, o.reserved & 0xFFF, (o.reserved >> 12) & 3,
-                                                  (o.reserved >> 14) & 0x1FF, (o.reserved >> 23) & 0x1FF, o.act, s);
+                                                  out, n, o.oh, o.ow, o.cin, o.cout, g.c2, g.stride2, g.h2, g.w2, o.act, s);
                     break;
                 }
-                if (o.res_buf >= 0 && o.reserved != 0) {      // the residual is a stride view of a larger map (csrc/conv1x1_bf16.hip, rs_stride)
+                if (o.res_buf >= 0 && o.aux != 0) {      // the residual is a stride view of a larger map (csrc/conv1x1_bf16.hip, rs_stride)
                     rc = launch_conv1x1_sres_bf16(in, blob_ptr(e, o.w_off), (const float*)blob_ptr(e, o.scale_off), (const float*)blob_ptr(e, o.shift_off),
-                                                  tab[o.res_buf], out, n, o.oh, o.ow, o.cin, o.cout, (o.reserved >> 12) & 3, (o.reserved >> 14) & 0x1FF,
-                                                  (o.reserved >> 23) & 0x1FF, o.act, s);
+                                                  tab[o.res_buf], out, n, o.oh, o.ow, o.cin, o.cout, g.stride2, g.h2, g.w2, o.act, s);
                     break;
                 }
                 rc = launch_conv_bf16(in, blob_ptr(e, o.w_off), (const float*)blob_ptr(e, o.scale_off),
@@ -760,7 +797,7 @@ static int run_ops(hsefr_engine* e, const std::vector<void*>& tab, const void* d
                     rc = launch_conv_f32_mfma((const float*)in, (const float*)blob_ptr(e, o.w_off), (const float*)blob_ptr(e, o.scale_off),
                                               (const float*)blob_ptr(e, o.shift_off), o.res_buf >= 0 ? (const float*)tab[o.res_buf] : nullptr,
                                               (float*)out, n, o.h, o.w, o.cin, o.oh, o.ow, o.cout, o.kh, o.kw, o.stride, o.pad_t, o.pad_l, o.act, s,
-                                              o.res_buf >= 0 ? (o.reserved >> 12) & 3 : 0, (o.reserved >> 14) & 0x1FF, (o.reserved >> 23) & 0x1FF);
+                                              o.res_buf >= 0 ? g.stride2 : 0, g.h2, g.w2);
                     break;
                 }
                 rc = launch_conv2d_f32((const float*)in, (const float*)blob_ptr(e, o.w_off), (const float*)blob_ptr(e, o.scale_off),
@@ -776,8 +813,8 @@ static int run_ops(hsefr_engine* e, const std::vector<void*>& tab, const void* d
                 break;
             case HSEFR_OP_STEM7X7_POOL_BF16:
                 rc = launch_stem7x7_pool_bf16((const float*)in, blob_ptr(e, o.w_off), (const float*)blob_ptr(e, o.scale_off),
-                                              (const float*)blob_ptr(e, o.shift_off), out, n, o.h, o.w, o.oh, o.ow, o.reserved & 15,
-                                              (o.reserved >> 4) & 15, s, i < e->d_derived.size() ? e->d_derived[i] : nullptr);
+                                              (const float*)blob_ptr(e, o.shift_off), out, n, o.h, o.w, o.oh, o.ow, pool_pads(o.aux).t,
+                                              pool_pads(o.aux).l, s, i < e->d_derived.size() ? e->d_derived[i] : nullptr);
                 break;
             case HSEFR_OP_MAXPOOL_BF16:
                 rc = launch_maxpool3x3s2_bf16(in, out, n, o.h, o.w, o.cin, o.oh, o.ow, o.pad_t, o.pad_l, s);
@@ -792,46 +829,41 @@ static int run_ops(hsefr_engine* e, const std::vector<void*>& tab, const void* d
                                        o.pad_t, o.pad_l, o.oh, o.ow, o.cout, HSEFR_ACT_RELU6, o.act, s);
                 break;
             case HSEFR_OP_STEM3_F16S: {
-                const float* pk = (const float*)blob_ptr(e, o.w_off);
-                const float* ds2 = (const float*)blob_ptr(e, o.shift2_off);
+                const StemPack p = stem_pack(e, o);
+                const StemAux a = stem_aux(o.aux);
+                const StemKw kw = stem_kw(o.kw);
                 const int h1 = (o.h + 1) / 2, w1 = (o.w + 1) / 2;
-                // pack: [0, 1952) the fp32 constants of stem2, [1952, 3008) conv1 split rows + descale for stem3_fused.hip,
-                // [3008, 5056) conv1 in the two-step K layout of stem4_fused.hip, [5056, 7104) the same channel-reversed for uint8
-                // RGB input, [7104, 7232) its four mean-folded shift vectors, [7232, 7264) its descale
                 if (input_u8) {
-                    rc = (g_stem5 ? launch_stem5_stream : launch_stem4_fused)(in, 1, pk + 5056, pk + 7232, pk + 7104, pk + 896, pk + 1184, pk + 1216,
-                                                                            blob_ptr(e, o.w2_off), ds2, ds2 + 64, pk + 1248, pk + 1824, pk + 1888,
-                                                                            (float*)out, nullptr, n, o.h, o.w, 0, o.reserved & 255, o.act, s);
+                    rc = (g_stem5 ? launch_stem5_stream : launch_stem4_fused)(in, 1, p.conv4_u8, p.u8_descale, p.u8_shift, p.dw1, p.dw1_scale, p.dw1_shift,
+                                                                            blob_ptr(e, o.w2_off), p.descale, p.pshift, p.dw2, p.dw2_scale, p.dw2_shift,
+                                                                            (float*)out, nullptr, n, o.h, o.w, 0, a.a_log2, o.act, s);
                     break;
                 }
                 if (g_stem4 && stem4_route(o)) {
-                    rc = (g_stem5 ? launch_stem5_stream : launch_stem4_fused)(in, 0, pk + 3008, pk + 1952 + 1024, pk + 864, pk + 896, pk + 1184, pk + 1216,
-                                                                            blob_ptr(e, o.w2_off), ds2, ds2 + 64, pk + 1248, pk + 1824, pk + 1888,
-                                                                            (float*)out, e->d_overflow, n, o.h, o.w, ((o.reserved >> 8) & 255) - 64,
-                                                                            o.reserved & 255, o.act, s);
+                    rc = (g_stem5 ? launch_stem5_stream : launch_stem4_fused)(in, 0, p.conv4, p.conv_descale, p.conv_shift, p.dw1, p.dw1_scale, p.dw1_shift,
+                                                                            blob_ptr(e, o.w2_off), p.descale, p.pshift, p.dw2, p.dw2_scale, p.dw2_shift,
+                                                                            (float*)out, e->d_overflow, n, o.h, o.w, a.in_log2, a.a_log2, o.act, s);
                     break;
                 }
-                rc = launch_stem3_fused((const float*)in, pk + 1952, pk + 1952 + 1024, pk + 864, pk + 896, pk + 1184, pk + 1216,
-                                        blob_ptr(e, o.w2_off), ds2, ds2 + 64, pk + 1248, pk + 1824, pk + 1888, (float*)out, e->d_overflow, n,
-                                        o.h, o.w, o.pad_t, o.pad_l, h1, w1, (o.kw >> 4) & 1, (o.kw >> 5) & 1, o.oh, o.ow,
-                                        ((o.reserved >> 8) & 255) - 64, o.reserved & 255, o.act, s);
+                rc = launch_stem3_fused((const float*)in, p.conv_split, p.conv_descale, p.conv_shift, p.dw1, p.dw1_scale, p.dw1_shift,
+                                        blob_ptr(e, o.w2_off), p.descale, p.pshift, p.dw2, p.dw2_scale, p.dw2_shift, (float*)out, e->d_overflow, n,
+                                        o.h, o.w, o.pad_t, o.pad_l, h1, w1, kw.pad_t2, kw.pad_l2, o.oh, o.ow, a.in_log2, a.a_log2, o.act, s);
                 break;
             }
             case HSEFR_OP_STEM2_F16S: {
-                const float* pk = (const float*)blob_ptr(e, o.w_off);
-                const float* ds2 = (const float*)blob_ptr(e, o.shift2_off);
+                const StemPack p = stem_pack(e, o);
+                const StemKw kw = stem_kw(o.kw);
                 const int h1 = (o.h + 1) / 2, w1 = (o.w + 1) / 2;
-                rc = launch_stem2_fused((const float*)in, pk, pk + 864, pk + 896, pk + 1184, pk + 1216, blob_ptr(e, o.w2_off), ds2,
-                                        ds2 + 64, pk + 1248, pk + 1824, pk + 1888, (float*)out, n, o.h, o.w, o.pad_t, o.pad_l, h1, w1,
-                                        (o.kw >> 4) & 1, (o.kw >> 5) & 1, o.oh, o.ow, o.reserved, o.act, s);
+                rc = launch_stem2_fused((const float*)in, p.conv, p.conv_shift, p.dw1, p.dw1_scale, p.dw1_shift, blob_ptr(e, o.w2_off), p.descale,
+                                        p.pshift, p.dw2, p.dw2_scale, p.dw2_shift, (float*)out, n, o.h, o.w, o.pad_t, o.pad_l, h1, w1,
+                                        kw.pad_t2, kw.pad_l2, o.oh, o.ow, o.aux, o.act, s);
                 break;
             }
 #ifdef HSEFR_DEV
             case HSEFR_OP_STEM_F16S: {
-                const float* pk = (const float*)blob_ptr(e, o.w_off);
-                const float* ds2 = (const float*)blob_ptr(e, o.shift2_off);
-                rc = launch_stem_fused((const float*)in, pk, pk + 864, pk + 896, pk + 1184, pk + 1216, blob_ptr(e, o.w2_off), ds2,
-                                       ds2 + o.cout, (float*)out, n, o.h, o.w, o.pad_t, o.pad_l, o.oh, o.ow, o.reserved, o.act, s);
+                const StemPack p = stem_pack(e, o);
+                rc = launch_stem_fused((const float*)in, p.conv, p.conv_shift, p.dw1, p.dw1_scale, p.dw1_shift, blob_ptr(e, o.w2_off), p.descale,
+                                       p.pshift, (float*)out, n, o.h, o.w, o.pad_t, o.pad_l, o.oh, o.ow, o.aux, o.act, s);
                 break;
             }
 #endif
@@ -840,7 +872,7 @@ static int run_ops(hsefr_engine* e, const std::vector<void*>& tab, const void* d
                 rc = launch_dwpw_f16s((const float*)in, (const float*)blob_ptr(e, o.w_off), (const float*)blob_ptr(e, o.scale_off),
                                       (const float*)blob_ptr(e, o.shift_off), blob_ptr(e, o.w2_off), ds2, ds2 + o.cout,
                                       (float*)out, n, o.h, o.w, o.cin, o.stride, o.pad_t, o.pad_l, o.oh, o.ow, o.cout,
-                                      o.reserved, o.act, s);
+                                      o.aux, o.act, s);
                 break;
             }
             default:
@@ -867,7 +899,7 @@ int hsefr_engine_forward(hsefr_engine* e, const void* d_input, int n, void* d_fe
 int hsefr_engine_accepts_u8(const hsefr_engine* e) {
     if (!e || e->ops.empty()) return 0;
     const hsefr_plan_op& o = e->ops[0];
-    return o.kind == HSEFR_OP_STEM3_F16S && o.in_buf == HSEFR_BUF_INPUT && ((o.reserved >> 16) & 1) && stem4_route(o);
+    return o.kind == HSEFR_OP_STEM3_F16S && o.in_buf == HSEFR_BUF_INPUT && stem_aux(o.aux).u8 && stem4_route(o);
 }
 
 int hsefr_engine_forward_u8(hsefr_engine* e, const void* d_input_u8, int n, void* d_features, void* d_age_probs,

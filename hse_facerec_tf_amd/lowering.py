@@ -49,6 +49,19 @@ _HEADER = struct.Struct("<QIIIIII3i3IQ")          # hsefr_plan_header
 _BUFFER = struct.Struct("<QII")                   # hsefr_plan_buffer
 _OP = struct.Struct("<II3i3i3i3i2iii5Q")         # hsefr_plan_op (112 bytes; `flags` sits where the struct's padding was until round 6)
 OPF_PAIR_NEXT, OPF_HEADS, OPF_OUT_SUB2 = 1, 2, 4  # hsefr_op_flags
+# hsefr_plan_op.aux: the geometry word (shift, width of each field), PWCONV_PS_DW's out_log2, STEM3_F16S's in_log2 and uint8 bit,
+# STEM7X7_POOL_BF16's pool pads
+AUX_C2_SHIFT, AUX_C2_BITS, AUX_STRIDE2_SHIFT, AUX_STRIDE2_BITS = 0, 12, 12, 2
+AUX_H2_SHIFT, AUX_H2_BITS, AUX_W2_SHIFT, AUX_W2_BITS = 14, 9, 23, 9
+AUX_LOG2_BITS, AUX_OUT_LOG2_SHIFT, AUX_IN_LOG2_SHIFT, AUX_IN_LOG2_BIAS, AUX_U8_BIT = 8, 8, 8, 64, 16
+AUX_POOL_PAD_L_SHIFT = 4
+STEM_KW_PAD_T2_BIT, STEM_KW_PAD_L2_BIT = 4, 5    # hsefr_plan_op.kw of STEM2_F16S / STEM3_F16S
+# float offsets of the stem constant pack, and of the stems' shift2 block
+STEM_PACK_CONV, STEM_PACK_CONV_SHIFT, STEM_PACK_DW1, STEM_PACK_DW1_SCALE, STEM_PACK_DW1_SHIFT = 0, 864, 896, 1184, 1216
+STEM_PACK_DW2, STEM_PACK_DW2_SCALE, STEM_PACK_DW2_SHIFT, STEM_PACK_STEM2_END = 1248, 1824, 1888, 1952
+STEM_PACK_CONV_SPLIT, STEM_PACK_CONV_DESCALE, STEM_PACK_CONV4, STEM_PACK_CONV4_U8 = 1952, 2976, 3008, 5056
+STEM_PACK_U8_SHIFT, STEM_PACK_U8_DESCALE, STEM_PACK_STEM3_END = 7104, 7232, 7264
+STEM_SHIFT2_DESCALE, STEM_SHIFT2_SHIFT = 0, 64
 
 
 # Kernel families (csrc/*.hip) a plan may route to in the PRODUCT library, as Plan.describe() names them.  Development builds add
@@ -216,6 +229,51 @@ class Layer:
         return int(np.prod(self.out_shape)) * (2 if self.kind in _BF16_OUT else 4)
 
 
+def geometry_word(c2: int, stride2: int, h2: int, w2: int) -> int:
+    """The aux word of a projected shortcut (c2 > 0) or of a strided residual (c2 = 0), as the signed int32 the plan stores."""
+    assert 0 <= c2 < 1 << AUX_C2_BITS and 1 <= stride2 < 1 << AUX_STRIDE2_BITS and 0 < h2 < 1 << AUX_H2_BITS and 0 < w2 < 1 << AUX_W2_BITS
+    aux = c2 << AUX_C2_SHIFT | stride2 << AUX_STRIDE2_SHIFT | h2 << AUX_H2_SHIFT | w2 << AUX_W2_SHIFT
+    return aux - (1 << 32) if aux >= 1 << 31 else aux       # w2 >= 256 reaches bit 31 of the signed wire field (ADVICE r5)
+
+
+def stem_pack(L: Layer) -> np.ndarray:
+    """The fp32 constant pack of a fused stem layer (STEM_F16S, STEM2_F16S, STEM3_F16S), every segment at its offset in hsefr.h."""
+    segs = [(STEM_PACK_CONV, L.w0), (STEM_PACK_CONV_SHIFT, L.shift0), (STEM_PACK_DW1, L.w), (STEM_PACK_DW1_SCALE, L.scale),
+            (STEM_PACK_DW1_SHIFT, L.shift)]
+    end = STEM_PACK_DW2
+    if L.kind != OP_STEM_F16S:
+        segs += [(STEM_PACK_DW2, L.w3), (STEM_PACK_DW2_SCALE, L.scale3), (STEM_PACK_DW2_SHIFT, L.shift3)]
+        end = STEM_PACK_STEM2_END
+    if L.kind == OP_STEM3_F16S:
+        # conv1 as a [32 x 27 -> 32] contraction over k = dy*9 + dx*3 + ci, split like a pointwise kernel
+        cw_t = np.zeros((32, 32), np.float32)
+        cw_t[:, :27] = L.w0.reshape(27, 32).T
+        cimg, cds = split_pointwise_weights(cw_t, L.in_log2)
+        # ... and in the two-step K layout of csrc/stem4_fused.hip (inputs whose edges are multiples of 4), for fp32
+        # input and -- channel-reversed, with the mean folded into four shift vectors -- for uint8 RGB input
+        img4, ds4 = stem4_conv_image(L.w0, L.in_log2)
+        assert np.array_equal(ds4, cds)
+        if L.u8_mean_bgr is not None:
+            img8, ds8 = stem4_conv_image(L.w0, 0, reverse_channels=True)
+            sh8 = stem4_u8_shifts(L.w0, L.shift0, L.u8_mean_bgr)
+        else:
+            img8, ds8, sh8 = np.zeros_like(img4), np.zeros(32, np.float32), np.zeros((4, 32), np.float32)
+
+        def rows(img):      # split rows: f16 pairs filling whole floats
+            return np.ascontiguousarray(img).reshape(-1).view(np.float32)
+
+        segs += [(STEM_PACK_CONV_SPLIT, rows(cimg)), (STEM_PACK_CONV_DESCALE, cds), (STEM_PACK_CONV4, rows(img4)),
+                 (STEM_PACK_CONV4_U8, rows(img8)), (STEM_PACK_U8_SHIFT, sh8), (STEM_PACK_U8_DESCALE, ds8)]
+        end = STEM_PACK_STEM3_END
+    parts, at = [], 0
+    for off, a in segs:
+        assert at == off, "stem pack: a segment starts at float %d, not at %d" % (at, off)
+        parts.append(np.asarray(a).reshape(-1).astype(np.float32))
+        at += parts[-1].size
+    assert at == end, "stem pack: %d floats, not %d" % (at, end)
+    return np.concatenate(parts)
+
+
 @dataclass
 class Plan:
     layers: List[Layer]
@@ -258,49 +316,26 @@ class Plan:
             if L.proj is not None:              # the packed bf16 projection kernel as it is; geometry in the aux word (hsefr.h)
                 assert L.kind == OP_CONV_BF16 and L.res >= 0 and L.w2.dtype == np.uint16
                 c2, s2, h2, wd2 = L.proj
-                assert 0 < c2 < 4096 and 1 <= s2 <= 3 and 0 < h2 < 512 and 0 < wd2 < 512 and tuple(L.w2.shape) == (L.out_shape[2], c2)
+                assert c2 > 0 and tuple(L.w2.shape) == (L.out_shape[2], c2)
                 w2 = L.w2
-                aux = c2 | (s2 << 12) | (h2 << 14) | (wd2 << 23)
-                if aux >= 1 << 31:              # w2 >= 256 reaches bit 31 of the signed wire field; the C side masks after >> 23
-                    aux -= 1 << 32
+                aux = geometry_word(c2, s2, h2, wd2)
             if L.res_geom is not None:          # the residual is a stride view of a larger map (hsefr.h: hsefr_conv1x1_sres_bf16)
                 assert L.kind in (OP_CONV_BF16, OP_CONV_F32) and L.res >= 0 and L.proj is None and L.kh == 1 and L.kw == 1 and L.stride == 1
                 s2, h2, wd2 = L.res_geom
-                assert 1 <= s2 <= 3 and 0 < h2 < 512 and 0 < wd2 < 512 and tuple(self.layers[L.res].out_shape) == (h2, wd2, L.out_shape[2])
-                aux = (s2 << 12) | (h2 << 14) | (wd2 << 23)
-                if aux >= 1 << 31:
-                    aux -= 1 << 32
-            if L.kind in (OP_STEM2_F16S, OP_STEM3_F16S):
-                w = np.concatenate([L.w0.reshape(-1), L.shift0.reshape(-1), L.w.reshape(-1), L.scale.reshape(-1), L.shift.reshape(-1),
-                                    L.w3.reshape(-1), L.scale3.reshape(-1), L.shift3.reshape(-1)]).astype(np.float32)
-                assert w.size == 1952
-                if L.kind == OP_STEM3_F16S:
-                    # conv1 as a [32 x 27 -> 32] contraction over k = dy*9 + dx*3 + ci, split like a pointwise kernel
-                    cw_t = np.zeros((32, 32), np.float32)
-                    cw_t[:, :27] = L.w0.reshape(27, 32).T
-                    cimg, cds = split_pointwise_weights(cw_t, L.in_log2)
-                    w = np.concatenate([w, np.ascontiguousarray(cimg).reshape(-1).view(np.float32), cds.astype(np.float32)])
-                    assert w.size == 3008
-                    # ... and in the two-step K layout of csrc/stem4_fused.hip (inputs whose edges are multiples of 4), for fp32
-                    # input and -- channel-reversed, with the mean folded into four shift vectors -- for uint8 RGB input
-                    img4, ds4 = stem4_conv_image(L.w0, L.in_log2)
-                    assert np.array_equal(ds4, cds)
-                    u8_ok = L.u8_mean_bgr is not None
-                    if u8_ok:
-                        img8, ds8 = stem4_conv_image(L.w0, 0, reverse_channels=True)
-                        sh8 = stem4_u8_shifts(L.w0, L.shift0, L.u8_mean_bgr)
-                    else:
-                        img8, ds8, sh8 = np.zeros_like(img4), np.zeros(32, np.float32), np.zeros((4, 32), np.float32)
-                    w = np.concatenate([w, img4.reshape(-1).view(np.float32), img8.reshape(-1).view(np.float32),
-                                        sh8.reshape(-1).astype(np.float32), ds8.astype(np.float32)])
-                    assert w.size == 7264
-                scale = None
+                assert tuple(self.layers[L.res].out_shape) == (h2, wd2, L.out_shape[2])
+                aux = geometry_word(0, s2, h2, wd2)
+            if L.kind in (OP_STEM_F16S, OP_STEM2_F16S, OP_STEM3_F16S):
+                w, scale = stem_pack(L), None
                 w2, descale = split_pointwise_weights(w2, L.a_log2)
+                assert descale.size == STEM_SHIFT2_SHIFT - STEM_SHIFT2_DESCALE
                 shift2 = np.concatenate([descale, L.shift2.astype(np.float32)])
-                aux = L.a_log2 if L.kind == OP_STEM2_F16S else (L.a_log2 | ((L.in_log2 + 64) << 8) | ((1 << 16) if L.u8_mean_bgr is not None else 0))
-                kw_field = 3 + 16 * L.pad3[0] + 32 * L.pad3[1]
+                aux = L.a_log2
+                if L.kind == OP_STEM3_F16S:
+                    aux |= (L.in_log2 + AUX_IN_LOG2_BIAS) << AUX_IN_LOG2_SHIFT | int(L.u8_mean_bgr is not None) << AUX_U8_BIT
+                if L.kind != OP_STEM_F16S:
+                    kw_field = 3 | L.pad3[0] << STEM_KW_PAD_T2_BIT | L.pad3[1] << STEM_KW_PAD_L2_BIT
             if L.kind == OP_STEM7X7_POOL_BF16:
-                aux = L.pad3[0] | (L.pad3[1] << 4)
+                aux = L.pad3[0] | L.pad3[1] << AUX_POOL_PAD_L_SHIFT
             if L.kind == OP_PWGAP_PS:
                 w = np.ascontiguousarray(w.reshape(w.shape[-2], w.shape[-1]).T)
                 w, scale = split_pointwise_weights(w, L.a_log2)
@@ -311,18 +346,9 @@ class Plan:
                 c = L.out_shape[2]
                 amp = np.float32(2.0 ** L.out_split)
                 w2 = np.concatenate([L.w3.reshape(9, c), (L.scale3 * amp).reshape(1, c), (L.shift3 * amp).reshape(1, c)]).astype(np.float32)
-                aux = L.a_log2 | (L.out_split << 8)
+                aux = L.a_log2 | L.out_split << AUX_OUT_LOG2_SHIFT
                 kw_field = 3
             if L.kind == OP_DWPW_F16S:
-                w2, descale = split_pointwise_weights(w2, L.a_log2)
-                shift2 = np.concatenate([descale, L.shift2.astype(np.float32)])
-                aux = L.a_log2
-            if L.kind == OP_STEM_F16S:
-                # one fp32 pack [conv HWIO 864 | conv shift 32 | dw 3x3x32 288 | dw scale 32 | dw shift 32], split pointwise rows
-                w = np.concatenate([L.w0.reshape(-1), L.shift0.reshape(-1), L.w.reshape(-1), L.scale.reshape(-1),
-                                    L.shift.reshape(-1)]).astype(np.float32)
-                assert w.size == 1248
-                scale = None
                 w2, descale = split_pointwise_weights(w2, L.a_log2)
                 shift2 = np.concatenate([descale, L.shift2.astype(np.float32)])
                 aux = L.a_log2

@@ -84,8 +84,8 @@ typedef enum hsefr_op_kind {
     HSEFR_OP_SOFTMAX = 6,      /* row softmax                                                             */
     HSEFR_OP_CONV_BF16 = 7,    /* KxK conv (1x1/3x3, stride 1|2) as bf16-MFMA implicit GEMM, fp32 acc,
                                   + shift (+ residual) + act; bf16 activations.  w2_off set: + projected shortcut
-                                  (hsefr_conv1x1_proj_bf16); residual, no w2_off, reserved != 0: the residual is a stride view
-                                  of a larger map (hsefr_conv1x1_sres_bf16: reserved = stride << 12 | h2 << 14 | w2 << 23)  */
+                                  (hsefr_conv1x1_proj_bf16); residual, no w2_off, aux != 0: the residual is a stride view
+                                  of a larger map (hsefr_conv1x1_sres_bf16).  aux = the geometry word (HSEFR_AUX_C2_SHIFT) */
     HSEFR_OP_MAXPOOL_BF16 = 8, /* 3x3/2 max-pool, bf16                                                    */
     HSEFR_OP_GAP_BF16 = 9,     /* mean over H,W of bf16 activations -> fp32                               */
     HSEFR_OP_STEM7X7_BF16 = 10,/* 7x7/2 pad-3 conv over the fp32 3-channel image -> 64 ch bf16 (+scale+shift+ReLU) */
@@ -93,50 +93,47 @@ typedef enum hsefr_op_kind {
                                   cout 64|128: the depthwise result never leaves the CU                            */
     HSEFR_OP_PWCONV_F16S = 12, /* 1x1 conv + shift + act, fp32 in/out, products on the f16 MFMA from a two-term split of
                                   both operands (fp32-grade, csrc/pwconv_f16s.hip); input bounded: |x| * 2^a_log2 < 32768.
-                                  w_off = split rows, scale_off = descale, shift_off = shift, `reserved` = a_log2   */
+                                  w_off = split rows, scale_off = descale, shift_off = shift, aux = a_log2        */
     HSEFR_OP_DWPW_F16S = 13,   /* fused depthwise 3x3 (+scale+shift+ReLU6) -> pointwise 1x1 (+shift+act) for any cin % 32,
                                   cout % 64, pointwise products as in PWCONV_F16S (csrc/dwpw_f16s.hip).  w_off/scale_off/
                                   shift_off = depthwise; w2_off = split rows; shift2_off = [2][cout]: descale, then shift;
-                                  `reserved` = a_log2 (the depthwise result is in [0,6]: 12)                         */
+                                  aux = a_log2 (the depthwise result is in [0,6]: 12)                                */
     HSEFR_OP_STEM_F16S = 14,   /* DEVELOPMENT BUILDS ONLY since round 6 (the product library answers HSEFR_ERR_UNSUPPORTED; no default lowering emits it).
                                   The whole MobileNet stem (csrc/stem_fused.hip): conv 3x3/2 3->32 + shift + ReLU6 ->
                                   depthwise 3x3/1 + scale + shift + ReLU6 -> pointwise 32->64 + shift + act.  h,w,cin = the
-                                  image, oh,ow,cout = the block output, pad_t/pad_l = the conv's; w_off = fp32 pack
-                                  [conv HWIO 864 | conv shift 32 | dw 3x3x32 288 | dw scale 32 | dw shift 32];
-                                  w2_off = split rows [64][64 f16]; shift2_off = [2][64] descale, shift; reserved = a_log2 */
+                                  image, oh,ow,cout = the block output, pad_t/pad_l = the conv's; w_off = the stem pack
+                                  up to HSEFR_STEM_PACK_DW2 (conv1 and the depthwise, HSEFR_STEM_PACK_CONV);
+                                  w2_off = split rows [64][64 f16]; shift2_off = HSEFR_STEM_SHIFT2_DESCALE; aux = a_log2 */
     HSEFR_OP_CONV_F32 = 18,    /* general KxK conv, stride, zero padding, fp32 NHWC in/out, exact fp32 FMA; epilogue as CONV_BF16
                                   (per-channel scale + shift, optional residual buffer, act): the fp32-grade mode of
                                   ResNet-style graphs (csrc/smallnet.hip).  w_off = TF HWIO kernel fp32, cout % 4 == 0  */
     HSEFR_OP_MAXPOOL_F32 = 19, /* k x k / stride max-pool with windows clipped to the image, fp32 (kh = kw = k)          */
     HSEFR_OP_STEM7X7_POOL_BF16 = 20, /* STEM7X7_BF16 (act must be ReLU) + the 3x3 / 2 max-pool behind it in one kernel
                                   (csrc/stem7s_stream.hip; csrc/stem7x7_pool.hip beyond 32-bit offsets): fp32 image in, POOLED bf16 map out (oh, ow = pooled size);
-                                  reserved = pool_pad_t | pool_pad_l << 4, each 0 or 1; blob operands as STEM7X7_BF16    */
+                                  aux = pool pads (HSEFR_AUX_POOL_PAD_L_SHIFT); blob operands as STEM7X7_BF16            */
     HSEFR_OP_PWCONV_PS_DW = 21, /* PWCONV_PS + the NEXT block's depthwise 3x3 (stride 1, SAME) + scale + shift + ReLU6 in the GEMM's epilogue,
                                   output = that depthwise layer's split rows (csrc/pwconv_ps.hip): h * w <= 288; stride = the depthwise's
                                   (1, or 2 on 12 x 12 / 14 x 14 maps with pad 0), oh / ow = its output size.
                                   w2_off = [11][cout] fp32: taps 0..8, scale * 2^out_log2, shift * 2^out_log2;
-                                  reserved = a_log2 | out_log2 << 8                                                         */
+                                  aux = a_log2 and out_log2 (HSEFR_AUX_OUT_LOG2_SHIFT)                                      */
     HSEFR_OP_PWCONV_PS_GAP = 22, /* PWCONV_PS + the global average pool behind it in the GEMM's epilogue: output [1,1,cout] fp32 per image
-                                  (33 <= h * w <= 288); blob operands as PWCONV_PS, reserved = a_log2            */
+                                  (33 <= h * w <= 288); blob operands as PWCONV_PS, aux = a_log2                 */
     HSEFR_OP_STEM3_F16S = 17,  /* STEM2_F16S for an input with a DECLARED BOUND |x| < 2^(15 - in_log2) (csrc/stem3_fused.hip): conv1's
                                   products are formed on the f16 MFMA from two-term splits like the pointwise layers'.
-                                  w_off = the STEM2 fp32 pack (1952 floats) | conv1 split rows [32][64 f16] (1024 floats) |
-                                  conv1 descale [32] | the conv kernel in the two-step K layout of csrc/stem4_fused.hip (2048 floats)
-                                  | the same channel-reversed for uint8 RGB input (2048) | its four mean-folded shift vectors
-                                  [4][32] | its descale [32] = 7264 floats; `reserved` = a_log2 | (in_log2 + 64) << 8 |
-                                  (uint8 constants valid ? 1 << 16 : 0); the rest as STEM2_F16S.  Inputs whose edges are
-                                  multiples of 4 run stem4_fused.hip, the others stem3_fused.hip.
+                                  w_off = the whole stem pack, up to HSEFR_STEM_PACK_STEM3_END (HSEFR_STEM_PACK_CONV);
+                                  aux = a_log2, in_log2 and the uint8 bit (HSEFR_AUX_IN_LOG2_SHIFT); the rest as STEM2_F16S.
+                                  Inputs whose edges are multiples of 4 run stem5_stream.hip, the others stem3_fused.hip.
                                   An input value outside the bound raises the engine's overflow flag (see
                                   hsefr_engine_input_overflow) -- the results of that forward are then meaningless.   */
     HSEFR_OP_PWCONV_PS = 16,   /* PWCONV_F16S whose INPUT buffer holds pre-split activations ("split rows", written by a
-                                  DWCONV3X3 op with `reserved` = a_log2 > 0): both GEMM operands go to LDS by DMA
+                                  DWCONV3X3 op with aux = a_log2 > 0): both GEMM operands go to LDS by DMA
                                   (csrc/pwconv_ps.hip); operands as PWCONV_F16S; k % 32 == 0, cout % 128 == 0            */
     HSEFR_OP_STEM2_F16S = 15   /* the stem plus the depthwise of block 2 (csrc/stem2_fused.hip): ... -> pointwise 32->64 +
                                   shift + ReLU6 -> depthwise 3x3/2 + scale + shift + act.  h,w,cin = the image, oh,ow,cout =
-                                  the stride-2 depthwise output (64 ch); pad_t/pad_l = conv1's; kh (sic) low byte = 3,
-                                  w_off = fp32 pack [conv HWIO 864 | conv shift 32 | dw1 288 | dw1 scale 32 | dw1 shift 32 |
-                                  dw2 3x3x64 576 | dw2 scale 64 | dw2 shift 64]; w2_off / shift2_off / reserved as STEM_F16S;
-                                  res_buf unused; stride = 2; `kw` = 3 + 16*pad_t2 + 32*pad_l2 (depthwise-2 padding)   */
+                                  the stride-2 depthwise output (64 ch); pad_t/pad_l = conv1's;
+                                  w_off = the stem pack up to HSEFR_STEM_PACK_STEM2_END (HSEFR_STEM_PACK_CONV);
+                                  w2_off / shift2_off / aux as STEM_F16S; res_buf unused; stride = 2;
+                                  kw = 3 and the depthwise-2 padding (HSEFR_STEM_KW_PAD_T2_BIT)                        */
 } hsefr_op_kind;
 
 typedef enum hsefr_output_slot {
@@ -180,6 +177,56 @@ typedef enum hsefr_op_flags {
                                 cannot run it as one launch fails                                                                      */
 } hsefr_op_flags;
 
+/* hsefr_plan_op.aux, the per-kind aux word.  PWCONV_F16S, PWCONV_PS, PWCONV_PS_GAP, DWPW_F16S, STEM_F16S, STEM2_F16S: a_log2 alone (the
+ * activation pre-scale exponent).  DWCONV3X3: 0 = fp32 output, a_log2 > 0 = output stored as split rows scaled by 2^a_log2 (act must be
+ * ReLU6, c % 32 == 0).  The kinds below pack fields into it, a field being (aux >> SHIFT) & ((1 << BITS) - 1).  0 for every other kind. */
+enum {
+    /* CONV_BF16 with w2_off set (projected shortcut), CONV_BF16 / CONV_F32 with a residual, no w2_off and aux != 0 (strided residual):
+     * the GEOMETRY WORD of res_buf, a map [h2, w2, c2] read at every stride2-th pixel.  A projected shortcut's res_buf is the block input,
+     * w2_off its 1x1 projection kernel [cout][c2] bf16 and shift2_off [scale2 | shift2]; a strided residual's res_buf is a larger map with
+     * cout channels (c2 = 0).  A w2 >= 256 reaches bit 31: the int32 field is then negative. */
+    HSEFR_AUX_C2_SHIFT = 0, HSEFR_AUX_C2_BITS = 12,
+    HSEFR_AUX_STRIDE2_SHIFT = 12, HSEFR_AUX_STRIDE2_BITS = 2,
+    HSEFR_AUX_H2_SHIFT = 14, HSEFR_AUX_H2_BITS = 9,
+    HSEFR_AUX_W2_SHIFT = 23, HSEFR_AUX_W2_BITS = 9,
+    HSEFR_AUX_LOG2_BITS = 8,          /* PWCONV_PS_DW, STEM3_F16S: a_log2 in the low bits                                              */
+    HSEFR_AUX_OUT_LOG2_SHIFT = 8,     /* PWCONV_PS_DW: out_log2, the rest of the word                                                   */
+    HSEFR_AUX_IN_LOG2_SHIFT = 8,      /* STEM3_F16S: in_log2 + HSEFR_AUX_IN_LOG2_BIAS, HSEFR_AUX_LOG2_BITS wide                         */
+    HSEFR_AUX_IN_LOG2_BIAS = 64,
+    HSEFR_AUX_U8_BIT = 16,            /* STEM3_F16S: set = the pack's uint8-input constants are valid (lowered with a BGR mean)         */
+    HSEFR_AUX_POOL_PAD_L_SHIFT = 4    /* STEM7X7_POOL_BF16: pool_pad_t | pool_pad_l << HSEFR_AUX_POOL_PAD_L_SHIFT, each 0 or 1           */
+};
+
+/* hsefr_plan_op.kw of STEM2_F16S / STEM3_F16S: the kernel size (3) in the bits below HSEFR_STEM_KW_PAD_T2_BIT, then one bit each for the
+ * top and the left padding of the stride-2 depthwise. */
+enum { HSEFR_STEM_KW_PAD_T2_BIT = 4, HSEFR_STEM_KW_PAD_L2_BIT = 5 };
+
+/* The stem constant pack at w_off of the fused stems: fp32 segments at these FLOAT offsets.  STEM_F16S's pack ends at
+ * HSEFR_STEM_PACK_DW2, STEM2_F16S's at HSEFR_STEM_PACK_STEM2_END, STEM3_F16S's at HSEFR_STEM_PACK_STEM3_END.  Split rows
+ * (hsefr_pwconv1x1_f16split) are f16 pairs that fill whole floats. */
+enum {
+    HSEFR_STEM_PACK_CONV = 0,             /* conv1 3x3/2 3 -> 32, TF HWIO [3][3][3][32]                                                 */
+    HSEFR_STEM_PACK_CONV_SHIFT = 864,     /* its shift [32]                                                                             */
+    HSEFR_STEM_PACK_DW1 = 896,            /* depthwise 3x3/1 [3][3][32]                                                                 */
+    HSEFR_STEM_PACK_DW1_SCALE = 1184,     /* its scale [32]                                                                             */
+    HSEFR_STEM_PACK_DW1_SHIFT = 1216,     /* its shift [32]                                                                             */
+    HSEFR_STEM_PACK_DW2 = 1248,           /* depthwise 3x3/2 [3][3][64] (behind the pointwise 32 -> 64 at w2_off)                       */
+    HSEFR_STEM_PACK_DW2_SCALE = 1824,     /* its scale [64]                                                                             */
+    HSEFR_STEM_PACK_DW2_SHIFT = 1888,     /* its shift [64]                                                                             */
+    HSEFR_STEM_PACK_STEM2_END = 1952,
+    HSEFR_STEM_PACK_CONV_SPLIT = 1952,    /* conv1 as a [32 x 27 -> 32] contraction (k = dy*9 + dx*3 + ci): split rows [32][64 f16],
+                                             the bound |x| * 2^in_log2 < 32768 in place of a_log2 (csrc/stem3_fused.hip)                */
+    HSEFR_STEM_PACK_CONV_DESCALE = 2976,  /* its descale [32], also the descale of HSEFR_STEM_PACK_CONV4                                */
+    HSEFR_STEM_PACK_CONV4 = 3008,         /* conv1 in the two-step K layout [2][32][64 f16] (hsefr_stem4_fused, hsefr_stem5_stream)     */
+    HSEFR_STEM_PACK_CONV4_U8 = 5056,      /* the same channel-reversed with in_log2 = 0, for uint8 RGB input (zeros when u8 = 0)        */
+    HSEFR_STEM_PACK_U8_SHIFT = 7104,      /* its four mean-folded shift vectors [4][32]                                                 */
+    HSEFR_STEM_PACK_U8_DESCALE = 7232,    /* its descale [32]                                                                           */
+    HSEFR_STEM_PACK_STEM3_END = 7264
+};
+
+/* shift2_off of the fused stems: [2][64] floats, the pointwise 32 -> 64 layer's descale, then its shift. */
+enum { HSEFR_STEM_SHIFT2_DESCALE = 0, HSEFR_STEM_SHIFT2_SHIFT = 64 };
+
 typedef struct hsefr_plan_op {
     uint32_t kind; /* hsefr_op_kind */
     uint32_t act;  /* hsefr_act     */
@@ -188,11 +235,7 @@ typedef struct hsefr_plan_op {
     int32_t oh, ow, cout; /* output                                                    */
     int32_t kh, kw, stride;
     int32_t pad_t, pad_l; /* TF SAME: pad_total//2 on top/left (0 for even input, k=3, s=2) */
-    int32_t reserved;   /* CONV_BF16 with w2_off set (round 5, projected shortcut): c2 | stride2 << 12 | h2 << 14 | w2 << 23 -- res_buf is then
-                           the BLOCK INPUT [h2, w2, c2], w2_off its 1x1 projection kernel [cout][c2] bf16, shift2_off [scale2 | shift2];
-                           PWCONV_F16S / PWCONV_PS / fused kinds: a_log2 (activation pre-scale exponent);
-                           DWCONV3X3: 0 = fp32 output, a_log2 > 0 = output stored as split rows scaled by 2^a_log2
-                           (act must be ReLU6, c % 32 == 0); 0 otherwise */
+    int32_t aux;        /* the per-kind aux word: the HSEFR_AUX_* constants above */
     int32_t flags;      /* hsefr_op_flags (round 6; the four bytes were padding before: plans written by older lowerings read as 0) */
     uint64_t w_off;     /* weights; layout depends on kind (see the per-kernel entry points) */
     uint64_t scale_off; /* per-channel scale (DWCONV), descale (PWCONV_F16S)                 */
@@ -431,7 +474,7 @@ int hsefr_conv_bf16(const void* x, const void* wgt_t, const float* scale, const 
  * -- the rounding points of the two-launch form (hsefr_conv_bf16 for the projection, then hsefr_conv_bf16 with res): the projection's
  * [n, oh, ow, cout] tensor is never written.  x [n,oh,ow,c], wgt_t [cout][c], x2 [n,h2,w2,c2] (the block's input), wgt2_t [cout][c2],
  * y [n,oh,ow,cout], all bf16; c, c2, cout multiples of 64.  What the engine runs for an HSEFR_OP_CONV_BF16 whose w2_off is set
- * (res_buf = the block input, shift2 = [scale2 | shift2], reserved = c2 | stride2 << 12 | h2 << 14 | w2 << 23). */
+ * (res_buf = the block input, shift2 = [scale2 | shift2], aux = the geometry word: HSEFR_AUX_C2_SHIFT). */
 int hsefr_conv1x1_proj_bf16(const void* x, const void* wgt_t, const float* scale, const float* shift, const void* x2, const void* wgt2_t,
                             const float* scale2, const float* shift2, void* y, int n, int oh, int ow, int c, int cout, int c2, int stride2,
                             int h2, int w2, int act, hsefr_stream_t stream);
@@ -441,7 +484,7 @@ int hsefr_conv1x1_proj_bf16(const void* x, const void* wgt_t, const float* scale
  * x [n,oh,ow,c], wgt_t [cout][c], res [n,h2,w2,cout], y [n,oh,ow,cout], all bf16; c, cout multiples of 64; (oh - 1) * res_stride < h2.  The last
  * bottleneck of a ResNet stage feeds only stride-2 1x1 layers: its 3x3 and increase layers run at the pixels those layers read
  * (lowering.subsample_stage_tails; results identical at those pixels), and the block's shortcut is still the full-size map of the block
- * before it.  What the engine runs for an HSEFR_OP_CONV_BF16 with a residual, no w2_off and reserved = res_stride << 12 | h2 << 14 | w2 << 23. */
+ * before it.  What the engine runs for an HSEFR_OP_CONV_BF16 with a residual, no w2_off and aux = the geometry word with c2 = 0, stride2 = res_stride. */
 int hsefr_conv1x1_sres_bf16(const void* x, const void* wgt_t, const float* scale, const float* shift, const void* res, void* y, int n, int oh,
                             int ow, int c, int cout, int res_stride, int h2, int w2, int act, hsefr_stream_t stream);
 

@@ -1,6 +1,7 @@
 """CPU suite, part 2: the product's TF-free reader + lowering, executed on CPU by tests/plan_ref.py
 (oracle ops over the SERIALISED plan) and compared with the oracle's unfused graph interpreter."""
 import os
+import re
 import struct
 
 import numpy as np
@@ -194,13 +195,23 @@ def test_plan_struct_layout_matches_header():
     assert "HSEFR_PLAN_MAGIC 0x314c505246455348ull" in hdr
     assert lowering._HEADER.size == 64 and lowering._BUFFER.size == 16 and lowering._OP.size == 112
     assert struct.pack("<Q", lowering.PLAN_MAGIC) == b"HSEFRPL1"
+    # the packed parts of an op: the aux word, the stems' kw field, the stem constant pack and the stems' shift2 block -- every one the
+    # header defines is mirrored, with its value
+    mirrored = ("AUX_C2_SHIFT", "AUX_C2_BITS", "AUX_STRIDE2_SHIFT", "AUX_STRIDE2_BITS", "AUX_H2_SHIFT", "AUX_H2_BITS", "AUX_W2_SHIFT",
+                "AUX_W2_BITS", "AUX_LOG2_BITS", "AUX_OUT_LOG2_SHIFT", "AUX_IN_LOG2_SHIFT", "AUX_IN_LOG2_BIAS", "AUX_U8_BIT",
+                "AUX_POOL_PAD_L_SHIFT", "STEM_KW_PAD_T2_BIT", "STEM_KW_PAD_L2_BIT", "STEM_PACK_CONV", "STEM_PACK_CONV_SHIFT", "STEM_PACK_DW1",
+                "STEM_PACK_DW1_SCALE", "STEM_PACK_DW1_SHIFT", "STEM_PACK_DW2", "STEM_PACK_DW2_SCALE", "STEM_PACK_DW2_SHIFT",
+                "STEM_PACK_STEM2_END", "STEM_PACK_CONV_SPLIT", "STEM_PACK_CONV_DESCALE", "STEM_PACK_CONV4", "STEM_PACK_CONV4_U8",
+                "STEM_PACK_U8_SHIFT", "STEM_PACK_U8_DESCALE", "STEM_PACK_STEM3_END", "STEM_SHIFT2_DESCALE", "STEM_SHIFT2_SHIFT")
+    assert sorted(re.findall(r"HSEFR_((?:AUX|STEM_KW|STEM_PACK|STEM_SHIFT2)_\w+) = \d+", hdr)) == sorted(mirrored)
+    layouts = tuple(("HSEFR_" + n, getattr(lowering, n)) for n in mirrored)
     for name, val in (("HSEFR_OP_CONV_C3", lowering.OP_CONV_C3), ("HSEFR_OP_DWCONV3X3", lowering.OP_DWCONV3X3),
                       ("HSEFR_OP_PWCONV_F32", lowering.OP_PWCONV_F32), ("HSEFR_OP_GAP", lowering.OP_GAP),
                       ("HSEFR_OP_DENSE", lowering.OP_DENSE), ("HSEFR_OP_SOFTMAX", lowering.OP_SOFTMAX),
                       ("HSEFR_OP_DWPW_F32", lowering.OP_DWPW_F32), ("HSEFR_OP_PWCONV_F16S", lowering.OP_PWCONV_F16S),
                       ("HSEFR_OP_DWPW_F16S", lowering.OP_DWPW_F16S), ("HSEFR_OP_STEM_F16S", lowering.OP_STEM_F16S),
                       ("HSEFR_OP_STEM2_F16S", lowering.OP_STEM2_F16S),
-                      ("HSEFR_ACT_RELU6", lowering.ACT_RELU6), ("HSEFR_ACT_SIGMOID", lowering.ACT_SIGMOID)):
+                      ("HSEFR_ACT_RELU6", lowering.ACT_RELU6), ("HSEFR_ACT_SIGMOID", lowering.ACT_SIGMOID)) + layouts:
         assert "%s = %d" % (name, val) in hdr
 
 
