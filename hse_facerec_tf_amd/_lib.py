@@ -84,6 +84,7 @@ SIGNATURES = {
     "hsefr_pairwise_dist": (c_int, [_fp, _fp, c_int, c_int, c_int, _fp, c_void_p]),
     "hsefr_single_linkage": (c_int, [_fp, c_int, c_int, _fp, _fp, _fp, _fp, _fp, _fp, c_void_p]),
     "hsefr_hier_linkage": (c_int, [_fp, c_int, c_int, _fp, _fp, _fp, c_int, _fp, _fp, _fp, _fp, c_void_p]),
+    "hsefr_dbscan": (c_int, [_fp, c_int, c_int, _fp, _fp, _fp, ctypes.c_double, c_int, _fp, _fp, c_void_p]),
     "hsefr_nn1": (c_int, [_fp, _fp, c_int, c_int, c_int, _fp, _fp, c_void_p]),
     "hsefr_nn1_fallbacks": (c_longlong, []),
 }

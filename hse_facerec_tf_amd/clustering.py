@@ -8,11 +8,15 @@ csrc/linkage.hip).  Here the tree becomes scipy's linkage matrix Z, flat cuts of
 tree), and the reference's same-photo split (complete linkage on small per-cluster matrices) runs on the host in NumPy.
 The study's other methods (facial_clustering_test.py:513-514: 'average', 'complete', 'weighted') need the whole matrix: libhsefr
 merges reciprocal nearest neighbours round by round on an fp64 n x n device matrix (ops.hier_linkage_merges, csrc/hier_linkage.hip).
+The reference's third branch, scikit-learn's DBSCAN on the precomputed matrix (facial_clustering.py:260-265), runs on the device with
+scikit-learn's labels from either source, without an N x N matrix from features (ops.dbscan_labels, csrc/dbscan.hip).
 No CPU fallback: the functions that compute distances raise without the library or a GPU.
 """
 from __future__ import annotations
 
 import hashlib
+import math
+import numbers
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -21,11 +25,13 @@ SAME_PHOTO_PENALTY = 100.0      # facial_clustering.py:254 (inf_dist)
 # scipy's reducible methods with a per-round Lance-Williams update; 'centroid' and 'median' are not reducible (their trees can have
 # inversions), and 'ward''s update of two clusters merged in the same round does not factor into two-way steps
 LINKAGE_METHODS = ("single", "average", "complete", "weighted")
+# get_facial_clusters and cluster_faces also take the reference's DBSCAN branch
+CLUSTER_METHODS = LINKAGE_METHODS + ("dbscan",)
 
 
-def _check_method(method):
-    if method not in LINKAGE_METHODS:
-        raise ValueError("linkage method %r is not supported; the supported methods are %s" % (method, ", ".join(LINKAGE_METHODS)))
+def _check_method(method, supported=LINKAGE_METHODS):
+    if method not in supported:
+        raise ValueError("linkage method %r is not supported; the supported methods are %s" % (method, ", ".join(supported)))
 
 
 # ---- linkage matrices ----------------------------------------------------------------------------------------------
@@ -188,6 +194,65 @@ def linkage_dense(dist_matrix, method, device=None) -> np.ndarray:
     return linkage_from_merges(ma.cpu().numpy(), mb.cpu().numpy(), mh.cpu().numpy(), mr.cpu().numpy(), n)
 
 
+# ---- DBSCAN ---------------------------------------------------------------------------------------------------------
+def _check_dbscan_args(eps, min_samples):
+    if isinstance(eps, bool) or not isinstance(eps, numbers.Real) or not math.isfinite(eps) or not eps > 0:
+        raise ValueError("dbscan: eps must be a finite real > 0, got %r" % (eps,))
+    if isinstance(min_samples, bool) or not isinstance(min_samples, numbers.Integral) or min_samples < 1:
+        raise ValueError("dbscan: min_samples must be an int >= 1, got %r" % (min_samples,))
+
+
+def _dbscan_result(labels, core):
+    labels = labels.cpu().numpy().astype(np.int64)
+    return np.flatnonzero(core.cpu().numpy()).astype(np.int64), labels
+
+
+def dbscan(features, eps=0.5, min_samples=5, born_years=None, photo_years=None, device=None):
+    """sklearn.cluster.dbscan(D, eps, min_samples=min_samples, metric="precomputed") for D = the feature distance of
+    perform_clustering (process_photos.py:45-56) from the features [n, d] on the GPU, with no N x N matrix anywhere ->
+    (core_sample_indices, labels) int64, scikit-learn's.  Distances are the fp32 ones of linkage_single, compared as (double)w <= eps.
+    Bad eps, min_samples, features or age arrays raise ValueError before any device work (for host inputs)."""
+    from . import _lib, ops
+    _check_dbscan_args(eps, min_samples)
+    if not hasattr(features, "is_cuda"):
+        features = np.asarray(features, dtype=np.float32)
+    if features.ndim != 2 or features.shape[0] < 1:
+        raise ValueError("features must be [n, d] with n >= 1")
+    if isinstance(features, np.ndarray) and not np.isfinite(features).all():
+        raise ValueError("features hold non-finite values")
+    born_years, photo_years = _age_arrays(born_years, photo_years, features.shape[0])
+    torch = _lib.require_gpu()
+    x = _device_tensor(features, torch.float32, device)
+    if not bool(torch.isfinite(x).all()):
+        raise ValueError("features hold non-finite values")
+    born, year = _age_tensors(born_years, photo_years, x.device)
+    return _dbscan_result(*ops.dbscan_labels(x=x, born=born, year=year, eps=eps, min_samples=min_samples))
+
+
+def dbscan_dense(dist_matrix, eps=0.5, min_samples=5, device=None):
+    """sklearn.cluster.dbscan(dist_matrix, eps, min_samples=min_samples, metric="precomputed") on the GPU -> (core_sample_indices,
+    labels) int64.  The matrix is read as its upper triangle D[min(i,j), max(i,j)] (scikit-learn reads whole rows: the results agree
+    on every symmetric matrix).  A non-square, empty, non-finite or negative matrix raises ValueError, as do bad eps / min_samples."""
+    from . import _lib, ops
+    _check_dbscan_args(eps, min_samples)
+    D = dist_matrix if hasattr(dist_matrix, "is_cuda") else np.asarray(dist_matrix, dtype=np.float64)
+    if D.ndim != 2 or D.shape[0] != D.shape[1] or D.shape[0] < 1:
+        raise ValueError("dist_matrix must be a non-empty square matrix, got shape %r" % (tuple(D.shape),))
+    if not bool(np.isfinite(D).all() if isinstance(D, np.ndarray) else D.isfinite().all()):
+        raise ValueError("dist_matrix holds non-finite values")
+    if bool((D < 0).any()):
+        raise ValueError("dist_matrix holds negative values (scikit-learn rejects them in a precomputed matrix)")
+    torch = _lib.require_gpu()
+    return _dbscan_result(*ops.dbscan_labels(dense=_device_tensor(D, torch.float64, device), eps=eps, min_samples=min_samples))
+
+
+def _clusters(labels) -> List[np.ndarray]:
+    """Members of each non-negative label (noise dropped)."""
+    labels = np.asarray(labels)
+    keep = np.flatnonzero(labels >= 0)
+    return [keep[g] for g in _groups(labels[keep])] if len(keep) else []
+
+
 # ---- flat cuts ------------------------------------------------------------------------------------------------------
 _CUT_CACHE = {}
 
@@ -335,8 +400,12 @@ def get_facial_clusters(dist_matrix, distanceThreshold=1, all_indices=None, no_i
     that no two faces of one photo stay together (complete linkage on the cluster's penalised distances, cut at 50, as the reference).
     ``no_images_in_cluster`` is accepted and ignored, as that branch does.  Returns lists of face indices, longest first; clusters of
     equal length are ordered by their smallest index (the reference leaves that order to scipy's label numbering).  One face gives
-    [[0]] (the reference's linkage raises on it).  Non-finite distances raise ValueError."""
-    _check_method(method)
+    [[0]] (the reference's linkage raises on it).  Non-finite distances raise ValueError.
+    ``method`` 'dbscan' is the DBSCAN branch (:260-265): dbscan_dense with eps = distanceThreshold and min_samples =
+    no_images_in_cluster, noise dropped, ``all_indices`` accepted and ignored, the same order; one face gives scikit-learn's answer."""
+    _check_method(method, CLUSTER_METHODS)
+    if method == "dbscan":
+        return _finish(_clusters(dbscan_dense(dist_matrix, distanceThreshold, no_images_in_cluster, device)[1]))
     D = np.asarray(dist_matrix, dtype=np.float64)
     if D.ndim != 2 or D.shape[0] != D.shape[1] or D.shape[0] < 1:
         raise ValueError("dist_matrix must be a non-empty square matrix, got shape %r" % (D.shape,))
@@ -366,9 +435,14 @@ def cluster_faces(features, distance_threshold: float, born_years=None, photo_ye
     matrix (or ``method`` 'average' / 'complete' / 'weighted' on an fp64 device matrix; see linkage), the age term when born / photo
     years are given, the same-photo split on each cluster's own distances (its rows through
     ops.pairwise_distances plus the host age term, clipped at 0, as feature_distance_matrix builds them), and clusters shorter than
-    ``min_cluster_size`` dropped.  Same order as get_facial_clusters."""
+    ``min_cluster_size`` dropped.  Same order as get_facial_clusters.  ``method`` 'dbscan' is perform_clustering's DBSCAN branch:
+    dbscan with eps = distance_threshold and min_samples = min_cluster_size, noise dropped, then the clusters shorter than
+    min_cluster_size (a border point claimed by an earlier cluster can leave one short); ``all_indices`` is ignored."""
     from . import _lib, ops
-    _check_method(method)
+    _check_method(method, CLUSTER_METHODS)
+    if method == "dbscan":
+        _, labels = dbscan(features, distance_threshold, min_cluster_size, born_years, photo_years, device)
+        return _finish(_clusters(labels), min_cluster_size)
     torch = _lib.require_gpu()
     x = _device_tensor(features, torch.float32, device)
     if x.dim() != 2 or x.shape[0] < 1:

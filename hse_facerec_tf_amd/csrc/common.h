@@ -273,6 +273,8 @@ int launch_area_crops(const unsigned char* src, const int* boxes, float* dst, in
 int launch_pairwise_dist(const float* x, const float* y, int n, int m, int d, float* out, hipStream_t s);
 int launch_single_linkage(const float* x, int n, int d, const float* born, const float* year, const double* dense, int* edge_a, int* edge_b,
                           double* edge_h, hipStream_t s);
+int launch_dbscan(const float* x, int n, int d, const float* born, const float* year, const double* dense, double eps, int min_samples,
+                  int* labels, unsigned char* core, hipStream_t s);
 int launch_hier_linkage(const float* x, int n, int d, const float* born, const float* year, const double* dense, int method, int* merge_a,
                         int* merge_b, double* merge_h, int* merge_round, hipStream_t s);
 

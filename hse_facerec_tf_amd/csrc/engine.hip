@@ -6,6 +6,7 @@
 // ONE stream over pre-allocated NHWC activation buffers.  No allocation, no synchronisation and
 // no host<->device copy happens inside hsefr_engine_forward, so a forward can be captured into
 // a hipGraph by the caller.
+#include <math.h>
 #include <string.h>
 
 #include <cxxabi.h>
@@ -1428,6 +1429,19 @@ int hsefr_hier_linkage(const float* x, int n, int d, const float* born, const fl
     HSEFR_REQUIRE(!(dense && born), HSEFR_ERR_INVALID, "hier_linkage: the age term belongs to the features path");
     HSEFR_REQUIRE(dense || (d > 0 && d % 8 == 0), HSEFR_ERR_INVALID, "hier_linkage: d=%d must be a positive multiple of 8", d);
     return launch_hier_linkage(x, n, d, born, year, dense, method, merge_a, merge_b, merge_h, merge_round, (hipStream_t)stream);
+}
+
+int hsefr_dbscan(const float* x, int n, int d, const float* born, const float* year, const double* dense, double eps, int min_samples,
+                 int* labels, unsigned char* core, hsefr_stream_t stream) {
+    HSEFR_REQUIRE(n >= 1, HSEFR_ERR_INVALID, "dbscan: n=%d", n);
+    HSEFR_REQUIRE((x != nullptr) != (dense != nullptr), HSEFR_ERR_INVALID, "dbscan: pass exactly one of x and dense");
+    HSEFR_REQUIRE(labels, HSEFR_ERR_INVALID, "dbscan: null pointer (labels)");
+    HSEFR_REQUIRE(!born == !year, HSEFR_ERR_INVALID, "dbscan: born and year come together");
+    HSEFR_REQUIRE(!(dense && born), HSEFR_ERR_INVALID, "dbscan: the age term belongs to the features path");
+    HSEFR_REQUIRE(dense || (d > 0 && d % 8 == 0), HSEFR_ERR_INVALID, "dbscan: d=%d must be a positive multiple of 8", d);
+    HSEFR_REQUIRE(isfinite(eps) && eps > 0, HSEFR_ERR_INVALID, "dbscan: eps=%g must be finite and > 0", eps);
+    HSEFR_REQUIRE(min_samples >= 1, HSEFR_ERR_INVALID, "dbscan: min_samples=%d must be >= 1", min_samples);
+    return launch_dbscan(x, n, d, born, year, dense, eps, min_samples, labels, core, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1,12 +1,8 @@
 // Single-linkage clustering on device without an N x N matrix: the minimum spanning tree of the distance graph by Boruvka rounds.
 //
 // Replaces hac.linkage(squareform(D), 'single') of get_facial_clusters (facial_clustering.py:243-245) and the O(N^2) host distance
-// matrix of perform_clustering (process_photos.py:45-60).  Two distance sources share every kernel but the first of a round:
-//   features  w(i,j) = max(sqrt(max(|x_i|^2 + |x_j|^2 - 2 x_i.x_j, 0)) + 0.1 (born_j - born_i)^2 / (2 max(year_i, year_j) - born_i - born_j), 0)
-//             (the age term only with born / year), the contraction on the fp32 MFMA as in nn1_kernel -- every w(i,j) is computed by the
-//             same commutative expression from the same row norms and the same FMA chain whichever side of a tile i falls on, so the graph
-//             is bitwise symmetric;
-//   dense     a caller's fp64 D [n,n], read as its upper triangle D[min(i,j), max(i,j)] (what squareform(D, checks=False) reads).
+// matrix of perform_clustering (process_photos.py:45-60).  The two distance sources (features on the fp32 MFMA, or a caller's fp64
+// matrix read as its upper triangle) are linkage_scan.h's; they share every kernel but the first of a round.
 // Edges are ordered strictly by (w, lower endpoint, higher endpoint); under that total order the lightest edge leaving every component
 // is unique and the chosen edges close no cycle but mutual picks.  A round:
 //   1. row_min_*      for every row i: the least (w, j) with j outside i's component (for a fixed row the total order is (w, j)); one
@@ -15,17 +11,18 @@
 //   3. hook           every root hooks under the root across its edge and appends the edge; of a mutual pair only the higher root does;
 //   4. jump x J       pointer jumping on par[] until every vertex points at its root (J covers the depth bound of the round);
 //   5. relabel        label = par.
-// ceil(log2 n) rounds are launched with no host synchronisation (each round at least halves the components); the device component count
-// turns rounds after completion into early exits.  Workspace: O(n), stream-ordered (hipMallocAsync), as hsefr_nn1's.
-#include "common.h"
+// ceil(log2 n) rounds are launched with no host synchronisation (each round at least halves the components that still have a candidate
+// edge); the device component count, and a flag raised by a round that hooked nothing, turn rounds after completion into early exits.
+// dbscan.hip runs the same rounds with a candidate filter (both ends core, w <= eps): its core clusters are the components.
+// Workspace: O(n), stream-ordered (hipMallocAsync), as hsefr_nn1's.
+#include "linkage_scan.h"
 
 namespace hsefr {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned long long u64;
+using link::better;
+using link::u64;
 
 constexpr u64 NO_KEY = ~0ull;
 
@@ -40,18 +37,18 @@ __device__ __forceinline__ double key_value(u64 k) {
     return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
 }
 
-template <typename T>
-__device__ __forceinline__ bool better(T v, int i, T bv, int bi) { return v < bv || (v == bv && i < bi); }
+// cnt[0] components, cnt[1] hooks so far, cnt[2] hooks at the end of the previous round, cnt[3] "a round hooked nothing"
+__device__ __forceinline__ bool rounds_done(const int* cnt) { return cnt[0] <= 1 || cnt[3] != 0; }
 
 __global__ __launch_bounds__(256) void sl_init_kernel(int* __restrict__ label, int* __restrict__ cnt, int n) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < n) label[i] = i;
-    if (i == 0) { cnt[0] = n; cnt[1] = 0; }
+    if (i == 0) { cnt[0] = n; cnt[1] = 0; cnt[2] = 0; cnt[3] = 0; }
 }
 
 __global__ __launch_bounds__(256) void sl_reset_kernel(const int* __restrict__ label, int* __restrict__ par, u64* __restrict__ cmin_w,
                                                        u64* __restrict__ cmin_e, const int* __restrict__ cnt, int n) {
-    if (cnt[0] <= 1) return;
+    if (rounds_done(cnt)) return;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     par[i] = label[i];
@@ -59,70 +56,47 @@ __global__ __launch_bounds__(256) void sl_reset_kernel(const int* __restrict__ l
     cmin_e[i] = NO_KEY;
 }
 
-// Features: one workgroup = 32 rows x all n columns, its 4 waves take column tiles of 32 round-robin (nn1_kernel's layout).  Row norms come
-// from the fragments that feed the MFMAs: lane (li, half) sums the same elements in the same order for a row on either operand, and the
-// halves meet in a commutative add, so |x_i|^2 is one value whichever side i is on.
+// FILTER: an edge is a candidate only if both ends are core and w <= eps; a workgroup whose rows are all non-core has none
+template <bool FILTER>
 __global__ __launch_bounds__(256) void sl_row_min_feat_kernel(const float* __restrict__ x, int n, int d, const float* __restrict__ born,
                                                               const float* __restrict__ year, const int* __restrict__ label,
-                                                              const int* __restrict__ cnt, u64* __restrict__ row_key,
-                                                              int* __restrict__ row_j) {
-    if (cnt[0] <= 1) return;
+                                                              const int* __restrict__ cnt, const unsigned char* __restrict__ core,
+                                                              float eps, u64* __restrict__ row_key, int* __restrict__ row_j) {
+    if (rounds_done(cnt)) return;
     __shared__ float s_val[4][32];
     __shared__ int s_idx[4][32];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int li = lane & 31, lh = lane >> 5;
     const int q0 = blockIdx.x * 32;
-    const float* qp = x + (size_t)min(q0 + li, n - 1) * d + 4 * lh;
-    const bool age = born != nullptr;
+    if (FILTER && !__syncthreads_or(threadIdx.x < 32 && q0 + (int)threadIdx.x < n && core[q0 + threadIdx.x])) {
+        if (threadIdx.x < 32 && q0 + (int)threadIdx.x < n) { row_key[q0 + threadIdx.x] = NO_KEY; row_j[q0 + threadIdx.x] = -1; }
+        return;
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int li = lane & 31;
+    link::FeatScan fs(x, n, d, born, year);
 
-    float best_v[16], born_r[16], year_r[16];
+    float best_v[16];
     int best_i[16], lab_r[16];
+    bool core_r[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int row = min(q0 + (r & 3) + 8 * (r >> 2) + 4 * lh, n - 1);
-        lab_r[r] = label[row];
-        born_r[r] = age ? born[row] : 0.f;
-        year_r[r] = age ? year[row] : 0.f;
+        lab_r[r] = label[fs.row(r)];
+        core_r[r] = FILTER ? core[fs.row(r)] != 0 : true;
         best_v[r] = INFINITY;
         best_i[r] = 0x7fffffff;
     }
 
-    float qq = 0.f;  // |x_row|^2 (lane rr holds row q0 + rr), from the wave's first tile
-    bool qq_done = false;
     const int tiles = (n + 31) / 32;
     for (int gt = wave; gt < tiles; gt += 4) {
         const int gcol = gt * 32 + li;
         const int grow = min(gcol, n - 1);
-        const float* gp = x + (size_t)grow * d + 4 * lh;
         const int glab = label[grow];
-        const float gb = age ? born[grow] : 0.f, gy = age ? year[grow] : 0.f;
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        float gg = 0.f, qs = 0.f;
-        for (int k = 0; k < d; k += 8) {
-            const f32x4 a = *(const f32x4*)(qp + k);
-            const f32x4 b = *(const f32x4*)(gp + k);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j], b[j], acc, 0, 0, 0);
-                gg = fmaf(b[j], b[j], gg);
-                qs = fmaf(a[j], a[j], qs);
-            }
-        }
-        gg += __shfl_xor(gg, 32);
-        if (!qq_done) { qq = qs + __shfl_xor(qs, 32); qq_done = true; }
+        const bool gcore = FILTER ? core[grow] != 0 : true;
+        float v[16];
+        fs.tile(grow, v);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int rr = (r & 3) + 8 * (r >> 2) + 4 * lh;
-            const float s = __shfl(qq, rr) + gg;
-            float v = sqrtf(fmaxf(fmaf(-2.f, acc[r], s), 0.f));
-            if (age) {
-                const float t = gb - born_r[r];
-                const float den = 2.f * fmaxf(year_r[r], gy) - (born_r[r] + gb);
-                v = fmaxf(v + 0.1f * (t * t) / den, 0.f);
-            }
-            if (gcol < n && glab != lab_r[r] && better(v, gcol, best_v[r], best_i[r])) { best_v[r] = v; best_i[r] = gcol; }
+            const bool cand = !FILTER || (gcore && core_r[r] && v[r] <= eps);
+            if (gcol < n && glab != lab_r[r] && cand && better(v[r], gcol, best_v[r], best_i[r])) { best_v[r] = v[r]; best_i[r] = gcol; }
         }
     }
 #pragma unroll
@@ -137,9 +111,8 @@ __global__ __launch_bounds__(256) void sl_row_min_feat_kernel(const float* __res
     if (li == 0) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int rr = (r & 3) + 8 * (r >> 2) + 4 * lh;
-            s_val[wave][rr] = best_v[r];
-            s_idx[wave][rr] = best_i[r];
+            s_val[wave][fs.rr(r)] = best_v[r];
+            s_idx[wave][fs.rr(r)] = best_i[r];
         }
     }
     __syncthreads();
@@ -155,37 +128,35 @@ __global__ __launch_bounds__(256) void sl_row_min_feat_kernel(const float* __res
     }
 }
 
-// Dense fp64: one workgroup = 64 rows x all n columns, walked in 64 x 64 tiles of the UPPER triangle staged through LDS with coalesced
-// row reads -- tile (R, C) with C > R is read as it is, C < R from its mirror D[C, R] and transposed, C == R by (min, max).  Thread t
-// holds row t / 4 and the columns t % 4 + 4 m of each tile.  Bandwidth-bound: every upper element is read twice per round.
+template <bool FILTER>
 __global__ __launch_bounds__(256) void sl_row_min_dense_kernel(const double* __restrict__ D, int n, const int* __restrict__ label,
-                                                               const int* __restrict__ cnt, u64* __restrict__ row_key,
-                                                               int* __restrict__ row_j) {
-    if (cnt[0] <= 1) return;
+                                                               const int* __restrict__ cnt, const unsigned char* __restrict__ core,
+                                                               double eps, u64* __restrict__ row_key, int* __restrict__ row_j) {
+    if (rounds_done(cnt)) return;
     __shared__ double s_t[64][65];
     __shared__ int s_lab[64];
     const int t = threadIdx.x, ri = t >> 2, sub = t & 3;
     const int r0 = blockIdx.x * 64, row = r0 + ri;
+    if (FILTER && !__syncthreads_or(t < 64 && r0 + t < n && core[r0 + t])) {
+        if (sub == 0 && row < n) { row_key[row] = NO_KEY; row_j[row] = -1; }
+        return;
+    }
     const int my_lab = row < n ? label[row] : -1;
+    const bool my_core = FILTER ? row < n && core[row] != 0 : true;
     double bv = INFINITY;
     int bi = 0x7fffffff;
     for (int c0 = 0; c0 < n; c0 += 64) {
-        const int sr0 = c0 < r0 ? c0 : r0, sc0 = c0 < r0 ? r0 : c0;
         __syncthreads();                                     // the previous tile has been read
-#pragma unroll 4
-        for (int k = 0; k < 16; ++k) {
-            const int a = (t >> 6) + 4 * k, b = t & 63;
-            const int gr = sr0 + a, gc = sc0 + b;
-            s_t[a][b] = (gr < n && gc < n) ? D[(size_t)gr * n + gc] : 0.0;
-        }
-        if (t < 64) s_lab[t] = c0 + t < n ? label[c0 + t] : -1;
+        link::dense_stage(D, n, r0, c0, s_t);
+        // a non-core column takes no label a core row can hold
+        if (t < 64) s_lab[t] = c0 + t < n && (!FILTER || core[c0 + t]) ? label[c0 + t] : -1;
         __syncthreads();
 #pragma unroll 4
         for (int m = 0; m < 16; ++m) {
             const int cj = sub + 4 * m, col = c0 + cj;
-            const bool up = c0 > r0 || (c0 == r0 && ri < cj);
-            const double v = up ? s_t[ri][cj] : s_t[cj][ri];
-            if (col < n && s_lab[cj] != my_lab && better(v, col, bv, bi)) { bv = v; bi = col; }
+            const double v = link::dense_at(s_t, r0, c0, ri, cj);
+            const bool cand = !FILTER || (my_core && s_lab[cj] >= 0 && v <= eps);
+            if (col < n && s_lab[cj] != my_lab && cand && better(v, col, bv, bi)) { bv = v; bi = col; }
         }
     }
 #pragma unroll
@@ -203,7 +174,7 @@ __global__ __launch_bounds__(256) void sl_row_min_dense_kernel(const double* __r
 
 __global__ __launch_bounds__(256) void sl_comp_min1_kernel(const int* __restrict__ label, const u64* __restrict__ row_key,
                                                            u64* __restrict__ cmin_w, const int* __restrict__ cnt, int n) {
-    if (cnt[0] <= 1) return;
+    if (rounds_done(cnt)) return;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const u64 k = row_key[i];
@@ -213,7 +184,7 @@ __global__ __launch_bounds__(256) void sl_comp_min1_kernel(const int* __restrict
 __global__ __launch_bounds__(256) void sl_comp_min2_kernel(const int* __restrict__ label, const u64* __restrict__ row_key,
                                                            const int* __restrict__ row_j, const u64* __restrict__ cmin_w,
                                                            u64* __restrict__ cmin_e, const int* __restrict__ cnt, int n) {
-    if (cnt[0] <= 1) return;
+    if (rounds_done(cnt)) return;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const u64 k = row_key[i];
@@ -226,11 +197,11 @@ __global__ __launch_bounds__(256) void sl_comp_min2_kernel(const int* __restrict
 
 // Roots read label[] only and write par[] only, so no hook sees another's write.  cnt[0] may drop while this kernel runs; a root that reads
 // it at <= 1 finds every hook of the round already counted, so it has none to make.  Edge slots and the component count take one atomic
-// per wavefront (ballot + prefix count), not one per root.
+// per wavefront (ballot + prefix count), not one per root.  edge_a == nullptr: the edges are not recorded.
 __global__ __launch_bounds__(256) void sl_hook_kernel(const int* __restrict__ label, int* __restrict__ par, const u64* __restrict__ cmin_w,
                                                       const u64* __restrict__ cmin_e, int* __restrict__ cnt, int* __restrict__ edge_a,
                                                       int* __restrict__ edge_b, double* __restrict__ edge_h, int n) {
-    if (*(volatile const int*)cnt <= 1) return;
+    if (*(volatile const int*)cnt <= 1 || cnt[3] != 0) return;
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 256 + threadIdx.x;
     bool hook = false;
@@ -256,7 +227,7 @@ __global__ __launch_bounds__(256) void sl_hook_kernel(const int* __restrict__ la
     if (!hook) return;
     par[r] = tgt;
     const int slot = base + __popcll(m & ((1ull << lane) - 1));
-    if (slot < n - 1) {
+    if (edge_a && slot < n - 1) {
         edge_a[slot] = lo;
         edge_b[slot] = hi;
         edge_h[slot] = key_value(cmin_w[r]);
@@ -271,9 +242,15 @@ __global__ __launch_bounds__(256) void sl_jump_kernel(int* par, int n) {
     if (pp != p) par[i] = pp;
 }
 
-__global__ __launch_bounds__(256) void sl_relabel_kernel(int* __restrict__ label, const int* __restrict__ par, int n) {
+// ends the round: a round that hooked nothing leaves nothing for the next ones (with a filter, components can stop while several remain)
+__global__ __launch_bounds__(256) void sl_relabel_kernel(int* __restrict__ label, const int* __restrict__ par, int* __restrict__ cnt, int n) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < n) label[i] = par[i];
+    if (i == 0) {
+        const int hooks = cnt[1];
+        if (hooks == cnt[2]) cnt[3] = 1;
+        else cnt[2] = hooks;
+    }
 }
 
 int ceil_log2(long long v) {
@@ -284,17 +261,11 @@ int ceil_log2(long long v) {
 
 }  // namespace
 
-int launch_single_linkage(const float* x, int n, int d, const float* born, const float* year, const double* dense, int* edge_a, int* edge_b,
-                          double* edge_h, hipStream_t s) {
-    if (n == 1) return HSEFR_OK;
-    // u64 arrays first: row_key, cmin_w, cmin_e; then int arrays: label, par, row_j, cnt[2]
-    const size_t bytes = (size_t)n * 3 * 8 + (size_t)n * 3 * 4 + 16;
-    char* ws = nullptr;
-    if (hipMallocAsync((void**)&ws, bytes, s) != hipSuccess || !ws) {
-        (void)hipGetLastError();
-        set_error("single_linkage: no stream-ordered workspace (%zu bytes) for n=%d", bytes, n);
-        return HSEFR_ERR_NOMEM;
-    }
+// u64 arrays first: row_key, cmin_w, cmin_e; then int arrays: label, par, row_j, cnt[4]
+size_t boruvka_bytes(int n) { return (size_t)n * 3 * 8 + (size_t)n * 3 * 4 + 16; }
+
+int* boruvka_rounds(const float* x, int n, int d, const float* born, const float* year, const double* dense, const unsigned char* core,
+                    float eps_f, double eps, char* ws, int* edge_a, int* edge_b, double* edge_h, hipStream_t s) {
     u64* row_key = (u64*)ws;
     u64* cmin_w = row_key + n;
     u64* cmin_e = cmin_w + n;
@@ -307,20 +278,40 @@ int launch_single_linkage(const float* x, int n, int d, const float* born, const
     const int rounds = ceil_log2(n);
     for (int k = 0; k < rounds; ++k) {
         HSEFR_LAUNCH(sl_reset_kernel, g1, blk, 0, s, label, par, cmin_w, cmin_e, cnt, n);
-        if (dense)
-            HSEFR_LAUNCH(sl_row_min_dense_kernel, dim3((n + 63) / 64), blk, 0, s, dense, n, label, cnt, row_key, row_j);
+        if (dense && core)
+            HSEFR_LAUNCH(sl_row_min_dense_kernel<true>, dim3((n + 63) / 64), blk, 0, s, dense, n, label, cnt, core, eps, row_key, row_j);
+        else if (dense)
+            HSEFR_LAUNCH(sl_row_min_dense_kernel<false>, dim3((n + 63) / 64), blk, 0, s, dense, n, label, cnt, core, eps, row_key, row_j);
+        else if (core)
+            HSEFR_LAUNCH(sl_row_min_feat_kernel<true>, dim3((n + 31) / 32), blk, 0, s, x, n, d, born, year, label, cnt, core, eps_f, row_key,
+                         row_j);
         else
-            HSEFR_LAUNCH(sl_row_min_feat_kernel, dim3((n + 31) / 32), blk, 0, s, x, n, d, born, year, label, cnt, row_key, row_j);
+            HSEFR_LAUNCH(sl_row_min_feat_kernel<false>, dim3((n + 31) / 32), blk, 0, s, x, n, d, born, year, label, cnt, core, eps_f, row_key,
+                         row_j);
         HSEFR_LAUNCH(sl_comp_min1_kernel, g1, blk, 0, s, label, row_key, cmin_w, cnt, n);
         HSEFR_LAUNCH(sl_comp_min2_kernel, g1, blk, 0, s, label, row_key, row_j, cmin_w, cmin_e, cnt, n);
         HSEFR_LAUNCH(sl_hook_kernel, g1, blk, 0, s, label, par, cmin_w, cmin_e, cnt, edge_a, edge_b, edge_h, n);
-        // round k starts with at most ceil(n / 2^k) components: a hook tree over them is at most that deep, and a vertex sits one step below
-        // its old root
+        // round k starts with at most ceil(n / 2^k) components that can still hook: a hook tree over them is at most that deep, and a
+        // vertex sits one step below its old root
         const long long comps = ((long long)n + (1ll << k) - 1) >> k;
         const int jumps = ceil_log2(comps + 1);
         for (int j = 0; j < jumps; ++j) HSEFR_LAUNCH(sl_jump_kernel, g1, blk, 0, s, par, n);
-        HSEFR_LAUNCH(sl_relabel_kernel, g1, blk, 0, s, label, par, n);
+        HSEFR_LAUNCH(sl_relabel_kernel, g1, blk, 0, s, label, par, cnt, n);
     }
+    return label;
+}
+
+int launch_single_linkage(const float* x, int n, int d, const float* born, const float* year, const double* dense, int* edge_a, int* edge_b,
+                          double* edge_h, hipStream_t s) {
+    if (n == 1) return HSEFR_OK;
+    const size_t bytes = boruvka_bytes(n);
+    char* ws = nullptr;
+    if (hipMallocAsync((void**)&ws, bytes, s) != hipSuccess || !ws) {
+        (void)hipGetLastError();
+        set_error("single_linkage: no stream-ordered workspace (%zu bytes) for n=%d", bytes, n);
+        return HSEFR_ERR_NOMEM;
+    }
+    boruvka_rounds(x, n, d, born, year, dense, nullptr, 0.f, 0.0, ws, edge_a, edge_b, edge_h, s);
     const int rc = launch_status("single_linkage");
     (void)hipFreeAsync(ws, s);
     return rc;

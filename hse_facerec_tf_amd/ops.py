@@ -624,6 +624,48 @@ def hier_linkage_merges(x=None, dense=None, born=None, year=None, method="averag
     return ma[:n - 1], mb[:n - 1], mh[:n - 1], mr[:n - 1]
 
 
+@_device_guarded
+def dbscan_labels(x=None, dense=None, born=None, year=None, eps=0.5, min_samples=5):
+    """DBSCAN with scikit-learn's labels (hsefr_dbscan) -> (labels int32 [n], core uint8 [n]) CUDA tensors: clusters 0, 1, ... in
+    order of their smallest core index, -1 for noise.  The sources are single_linkage_edges': x [n,d] float32 features (zero columns
+    pad d to a multiple of 8) with optional born / year float32 [n], or dense [n,n] float64 distances read as their upper triangle.
+    O(n) device workspace, no N x N matrix on the features path.  Asynchronous on the current stream."""
+    torch = _lib.require_gpu()
+    if (x is None) == (dense is None):
+        raise ValueError("dbscan_labels: pass exactly one of x and dense")
+    if (born is None) != (year is None):
+        raise ValueError("dbscan_labels: born and year come together")
+    d = 0
+    if x is not None:
+        _f32c(x, "x")
+        if x.dim() != 2:
+            raise ValueError("x must be [n, d]")
+        n, d = x.shape
+        if d % 8:
+            x = torch.nn.functional.pad(x, (0, 8 - d % 8)).contiguous()
+            d = x.shape[1]
+        for v, name in ((born, "born"), (year, "year")):
+            if v is not None and _f32c(v, name).numel() != n:
+                raise ValueError("%s has %d elements for %d rows" % (name, v.numel(), n))
+    else:
+        if born is not None:
+            raise ValueError("dbscan_labels: the age term belongs to the features path")
+        if not (dense.is_cuda and dense.dtype == torch.float64 and dense.is_contiguous() and dense.dim() == 2
+                and dense.shape[0] == dense.shape[1]):
+            raise ValueError("dense must be a contiguous square float64 CUDA tensor")
+        n = dense.shape[0]
+    if n < 1:
+        raise ValueError("dbscan_labels: no points")
+    dev = (x if x is not None else dense).device
+    labels = torch.empty((n,), dtype=torch.int32, device=dev)
+    core = torch.empty((n,), dtype=torch.uint8, device=dev)
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    # min_samples above n + 1 makes no point core, as n + 1 does (the C argument is an int)
+    _lib.check(_lib.lib().hsefr_dbscan(ptr(x), n, d, ptr(born), ptr(year), ptr(dense), float(eps), int(min(min_samples, n + 1)),
+                                       labels.data_ptr(), core.data_ptr(), _lib.current_stream_ptr()), "hsefr_dbscan")
+    return labels, core
+
+
 # ---- bf16 ResNet-50 kernels -------------------------------------------------------------------------
 def _bf16c(t, name):
     torch = _lib.require_gpu()

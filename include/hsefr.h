@@ -664,6 +664,20 @@ enum { HSEFR_LINK_AVERAGE = 0, HSEFR_LINK_COMPLETE = 1, HSEFR_LINK_WEIGHTED = 2 
 int hsefr_hier_linkage(const float* x, int n, int d, const float* born, const float* year, const double* dense, int method, int* merge_a,
                        int* merge_b, double* merge_h, int* merge_round, hsefr_stream_t stream);
 
+/* DBSCAN with scikit-learn's labels (DBSCAN(eps, min_samples, metric="precomputed").fit(D).labels_ of get_facial_clusters,
+ * facial_clustering.py:260-265) on the sources of hsefr_single_linkage: x [n,d] fp32 (d multiple of 8) with optional born / year and
+ * the same w, bit for bit, never forming an n x n matrix; or dense [n,n] fp64 read as its upper triangle D[min(i,j), max(i,j)] -- the
+ * one difference from scikit-learn, which reads whole rows of an asymmetric matrix.  The rule, for eps > 0 and min_samples >= 1:
+ *   N(i) = {j : w(i,j) <= eps} + {i} (a point counts itself whatever its self-distance); i is core when |N(i)| >= min_samples;
+ *   core clusters are the connected components of the core points joined by core-core edges with w <= eps, numbered 0, 1, 2, ... in
+ *   increasing order of their smallest core index (the seed); a non-core point with a core neighbour takes the cluster of the smallest
+ *   seed among its core neighbours, every other point is noise (-1).
+ * Features compare (double)w <= eps.  Outputs (device): labels [n] int32 and, unless core is null, core [n] (1 for a core point, else 0).
+ * The core clusters come from hsefr_single_linkage's Boruvka rounds with a candidate filter.  O(n) stream-ordered workspace, refused
+ * (HSEFR_ERR_NOMEM) before any launch; no host synchronisation.  Arguments are checked before any device call (HSEFR_ERR_INVALID). */
+int hsefr_dbscan(const float* x, int n, int d, const float* born, const float* year, const double* dense, double eps, int min_samples,
+                 int* labels, unsigned char* core, hsefr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,10 @@ n in {2048, 9164, 32768} x d in {1024, 2048}, with the rounds the tree actually 
 replaces (identification.feature_distance_matrix + scipy's single linkage on the dense matrix, up to n = 9164).
 With --method average / complete / weighted: hsefr_hier_linkage (csrc/hier_linkage.hip: the fp64 n x n matrix, then reciprocal
 nearest-neighbour rounds) for n in {2048, 9164}, against the host matrix + scipy's linkage of the same method.
-usage: python tools/linkage_time.py [--method M] [--out FILE]"""
+With --method dbscan: hsefr_dbscan (csrc/dbscan.hip: degree scan, filtered Boruvka rounds, border scan; no N x N matrix) for the same
+n x d as single linkage at --eps / --min-samples, with the rounds used, clusters and noise, against the host matrix + scikit-learn's
+DBSCAN on it (up to n = 9164).
+usage: python tools/linkage_time.py [--method M] [--eps E] [--min-samples K] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -29,21 +32,22 @@ def unit_rows(n, d, seed):
 
 
 def rounds_used(n, a, b, h):
-    """Boruvka on the tree itself under the same total order (height, lower, higher): the lightest edge leaving a component of the
-    full graph is a tree edge, so this replays the device's rounds."""
+    """Boruvka on the tree (or forest) itself under the same total order (height, lower, higher): the lightest edge leaving a component
+    of the full graph is a tree edge, so this replays the device's rounds."""
     lo, hi = np.minimum(a, b), np.maximum(a, b)
-    rank = np.empty(n - 1, dtype=np.int64)
-    rank[np.lexsort((hi, lo, h))] = np.arange(n - 1)
+    m = len(lo)
+    rank = np.empty(m, dtype=np.int64)
+    rank[np.lexsort((hi, lo, h))] = np.arange(m)
     label = np.arange(n)
     rounds = 0
-    while len(np.unique(label)) > 1:
+    while (label[lo] != label[hi]).any():
         rounds += 1
         la, lb = label[lo], label[hi]
         out = la != lb
-        best = np.full(n, n, dtype=np.int64)          # per component root: rank of its lightest outgoing edge
+        best = np.full(n, m, dtype=np.int64)          # per component root: rank of its lightest outgoing edge
         np.minimum.at(best, la[out], rank[out])
         np.minimum.at(best, lb[out], rank[out])
-        chosen = np.flatnonzero(best < n)
+        chosen = np.flatnonzero(best < m)
         e = np.argsort(rank)[best[chosen]]
         # union the chosen edges (a forest plus mutual picks), then relabel
         uf = np.arange(n)
@@ -121,11 +125,74 @@ def main_hier(method, out):
     print(text)
 
 
+def dbscan_ms(x, eps, min_samples, reps):
+    ops.dbscan_labels(x=x, eps=eps, min_samples=min_samples)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        out = ops.dbscan_labels(x=x, eps=eps, min_samples=min_samples)
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps, out
+
+
+def dbscan_rounds(x, core, eps):
+    """The filtered rounds are Boruvka on the core points' spanning forest of edges w <= eps: the core points' minimum spanning tree
+    (single linkage on them, the same w and the same order under their increasing renumbering) cut at eps."""
+    idx = torch.nonzero(core, as_tuple=True)[0]
+    if len(idx) < 2:
+        return 0
+    a, b, h = (t.cpu().numpy() for t in ops.single_linkage_edges(x=x[idx].contiguous()))
+    keep = h <= eps
+    return rounds_used(len(idx), a[keep], b[keep], h[keep])
+
+
+def main_dbscan(eps, min_samples, out):
+    from sklearn.cluster import DBSCAN
+    lines = ["# DBSCAN from unit-norm features, fp32 (tools/linkage_time.py --method dbscan --eps %g --min-samples %d); %s"
+             % (eps, min_samples, torch.cuda.get_device_name(0)),
+             "# GPU: hsefr_dbscan, CUDA-event time per call (mean of reps after one warm-up): degree scan, Boruvka rounds filtered to",
+             "# core-core edges w <= eps (ceil(log2 n) launched; the round after the last that hooks ends the rest), border scan",
+             "# used = rounds that hooked; row scans = degree + min(used + 1, launched) rounds + border; ms_per_scan = gpu_ms / row scans",
+             "# host: identification.feature_distance_matrix (GPU distances + copy to a host float64 matrix) + sklearn DBSCAN (precomputed)",
+             "%7s %5s %11s %9s %6s %9s %7s %12s %12s %12s %10s" % ("n", "d", "gpu_ms", "launched", "used", "clusters", "noise",
+                                                               "ms_per_scan", "host_D_s", "host_db_s", "speedup")]
+    for n in SIZES:
+        for d in DIMS:
+            x = unit_rows(n, d, n + d)
+            ms, (labels, core) = dbscan_ms(x, eps, min_samples, 3 if n <= 9164 else 2)
+            used = dbscan_rounds(x, core, eps)
+            launched = int(np.ceil(np.log2(n)))
+            lab = labels.cpu().numpy()
+            hd = hb = float("nan")
+            if n <= HOST_MAX_N:
+                t0 = time.perf_counter()
+                D = identification.feature_distance_matrix(x.cpu().numpy())
+                t1 = time.perf_counter()
+                DBSCAN(eps=eps, min_samples=min_samples, metric="precomputed").fit(D)
+                hd, hb = t1 - t0, time.perf_counter() - t1
+            sp = (hd + hb) * 1e3 / ms if n <= HOST_MAX_N else float("nan")
+            scans = min(used + 1, launched) + 2
+            lines.append("%7d %5d %11.2f %9d %6d %9d %7d %12.2f %12.3f %12.3f %10.1f" % (n, d, ms, launched, used, lab.max() + 1,
+                                                                                   (lab < 0).sum(), ms / scans, hd, hb, sp))
+            print(lines[-1], flush=True)
+    text = "\n".join(lines) + "\n"
+    if out:
+        with open(out, "w") as f:
+            f.write(text)
+    print(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
-    ap.add_argument("--method", default="single", choices=["single", "average", "complete", "weighted"])
+    ap.add_argument("--method", default="single", choices=["single", "average", "complete", "weighted", "dbscan"])
+    ap.add_argument("--eps", type=float, default=0.9, help="--method dbscan: the neighbourhood radius")
+    ap.add_argument("--min-samples", type=int, default=4, help="--method dbscan: points within eps (itself included) that make a core")
     args = ap.parse_args()
+    if args.method == "dbscan":
+        return main_dbscan(args.eps, args.min_samples, args.out)
     if args.method != "single":
         return main_hier(args.method, args.out)
     lines = ["# single-linkage clustering from unit-norm features, fp32 (tools/linkage_time.py); %s" % torch.cuda.get_device_name(0),
