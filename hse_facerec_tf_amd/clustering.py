@@ -10,6 +10,8 @@ The study's other methods (facial_clustering_test.py:513-514: 'average', 'comple
 merges reciprocal nearest neighbours round by round on an fp64 n x n device matrix (ops.hier_linkage_merges, csrc/hier_linkage.hip).
 The reference's third branch, scikit-learn's DBSCAN on the precomputed matrix (facial_clustering.py:260-265), runs on the device with
 scikit-learn's labels from either source, without an N x N matrix from features (ops.dbscan_labels, csrc/dbscan.hip).
+Its last branch, rank-order clustering (find_clusters, facial_clustering_test.py:23-239), runs on an fp64 n x n device matrix with the
+reference's clusters (ops.rank_order_labels, csrc/rank_order.hip).
 No CPU fallback: the functions that compute distances raise without the library or a GPU.
 """
 from __future__ import annotations
@@ -25,8 +27,10 @@ SAME_PHOTO_PENALTY = 100.0      # facial_clustering.py:254 (inf_dist)
 # scipy's reducible methods with a per-round Lance-Williams update; 'centroid' and 'median' are not reducible (their trees can have
 # inversions), and 'ward''s update of two clusters merged in the same round does not factor into two-way steps
 LINKAGE_METHODS = ("single", "average", "complete", "weighted")
-# get_facial_clusters and cluster_faces also take the reference's DBSCAN branch
-CLUSTER_METHODS = LINKAGE_METHODS + ("dbscan",)
+# get_facial_clusters and cluster_faces also take the reference's DBSCAN and rank-order branches
+CLUSTER_METHODS = LINKAGE_METHODS + ("dbscan", "rankorder")
+RANK_ORDER_NORM_THRESHOLD = 0.9     # find_clusters' defaults (facial_clustering_test.py:193)
+RANK_ORDER_RANK_THRESHOLD = 14
 
 
 def _check_method(method, supported=LINKAGE_METHODS):
@@ -253,6 +257,105 @@ def _clusters(labels) -> List[np.ndarray]:
     return [keep[g] for g in _groups(labels[keep])] if len(keep) else []
 
 
+# ---- rank-order clustering -------------------------------------------------------------------------------------------
+def _check_rank_order_pair(norm_threshold, rank_threshold):
+    for name, v in (("norm_threshold", norm_threshold), ("rank_threshold", rank_threshold)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or not v > 0:
+            raise ValueError("rank_order: %s must be a finite real > 0, got %r" % (name, v))
+    return float(norm_threshold), float(rank_threshold)
+
+
+def _rank_order_pairs(norm_threshold, rank_threshold, thresholds):
+    """-> (list of checked (norm, rank) pairs, whether the caller passed a sequence)"""
+    if thresholds is None:
+        return [_check_rank_order_pair(norm_threshold, rank_threshold)], False
+    pairs = []
+    try:
+        for pair in thresholds:
+            norm, rank = pair
+            pairs.append(_check_rank_order_pair(norm, rank))
+    except TypeError:
+        raise ValueError("rank_order: thresholds must be a sequence of (norm_threshold, rank_threshold) pairs, got %r" % (thresholds,))
+    if not pairs:
+        raise ValueError("rank_order: thresholds is empty")
+    return pairs, True
+
+
+def _rank_order_threshold_pair(threshold):
+    """The study passes distanceThreshold = (norm, rank); a scalar is (scalar, the reference's default rank threshold)."""
+    if isinstance(threshold, numbers.Real):
+        return _check_rank_order_pair(threshold, RANK_ORDER_RANK_THRESHOLD)
+    try:
+        norm, rank = threshold
+    except (TypeError, ValueError):
+        raise ValueError("rank_order: the threshold must be a number or a (norm_threshold, rank_threshold) pair, got %r" % (threshold,))
+    return _check_rank_order_pair(norm, rank)
+
+
+def _rank_order_clusters(labels) -> List[List[int]]:
+    """labels[i] = the smallest face of i's cluster -> the reference's matched_clusters: clusters of at least two faces, longest first,
+    equal lengths by smallest face."""
+    return _finish(_groups(np.asarray(labels)), 2)
+
+
+def _rank_order_results(labels, iters, sweep):
+    labels = labels.cpu().numpy()
+    if not sweep:
+        return _rank_order_clusters(labels), iters
+    return [(_rank_order_clusters(row), it) for row, it in zip(labels, iters)]
+
+
+def rank_order(features, norm_threshold=RANK_ORDER_NORM_THRESHOLD, rank_threshold=RANK_ORDER_RANK_THRESHOLD, born_years=None,
+               photo_years=None, device=None, thresholds=None):
+    """The reference's rank-order clustering (find_clusters, facial_clustering_test.py:23-239; the rule is written out at
+    hsefr_rank_order in include/hsefr.h) for D = the feature distance of perform_clustering (process_photos.py:45-56) from the features
+    [n, d] on the GPU -> (clusters, iterations): clusters of at least two faces as sorted lists of face indices, longest first, equal
+    lengths by their smallest face (the reference's order); iterations as the reference counts them.  Distances are the fp32 ones of
+    linkage, widened to an fp64 n x n device matrix.  ``thresholds`` = a sequence of (norm, rank) pairs returns one (clusters,
+    iterations) per pair from one matrix build.  Bad thresholds, features or age arrays raise ValueError before any device work (for
+    host inputs).  One face gives []."""
+    from . import _lib, ops
+    pairs, sweep = _rank_order_pairs(norm_threshold, rank_threshold, thresholds)
+    if not hasattr(features, "is_cuda"):
+        features = np.asarray(features, dtype=np.float32)
+    if features.ndim != 2 or features.shape[0] < 1:
+        raise ValueError("features must be [n, d] with n >= 1")
+    if isinstance(features, np.ndarray) and not np.isfinite(features).all():
+        raise ValueError("features hold non-finite values")
+    born_years, photo_years = _age_arrays(born_years, photo_years, features.shape[0])
+    torch = _lib.require_gpu()
+    x = _device_tensor(features, torch.float32, device)
+    if not bool(torch.isfinite(x).all()):
+        raise ValueError("features hold non-finite values")
+    born, year = _age_tensors(born_years, photo_years, x.device)
+    if sweep:
+        return _rank_order_results(*ops.rank_order_labels(x=x, born=born, year=year, thresholds=pairs), True)
+    return _rank_order_results(*ops.rank_order_labels(x=x, born=born, year=year, norm_threshold=pairs[0][0], rank_threshold=pairs[0][1]),
+                               False)
+
+
+def rank_order_dense(dist_matrix, norm_threshold=RANK_ORDER_NORM_THRESHOLD, rank_threshold=RANK_ORDER_RANK_THRESHOLD, device=None,
+                     thresholds=None):
+    """rank_order on a distance matrix: the rank-order branch of get_facial_clusters(dist_matrix, (norm_threshold, rank_threshold)) on
+    the GPU -> (clusters, iterations).  The matrix is read as its upper triangle D[min(i,j), max(i,j)] and its diagonal counts as 0 (the
+    reference reads whole rows: the results agree on every symmetric matrix with a zero diagonal).  A non-square, empty, non-finite or
+    negative matrix raises ValueError, as do bad thresholds.  ``thresholds`` as in rank_order."""
+    from . import _lib, ops
+    pairs, sweep = _rank_order_pairs(norm_threshold, rank_threshold, thresholds)
+    D = dist_matrix if hasattr(dist_matrix, "is_cuda") else np.asarray(dist_matrix, dtype=np.float64)
+    if D.ndim != 2 or D.shape[0] != D.shape[1] or D.shape[0] < 1:
+        raise ValueError("dist_matrix must be a non-empty square matrix, got shape %r" % (tuple(D.shape),))
+    if not bool(np.isfinite(D).all() if isinstance(D, np.ndarray) else D.isfinite().all()):
+        raise ValueError("dist_matrix holds non-finite values")
+    if bool((D < 0).any()):
+        raise ValueError("dist_matrix holds negative values")
+    torch = _lib.require_gpu()
+    Dd = _device_tensor(D, torch.float64, device)
+    if sweep:
+        return _rank_order_results(*ops.rank_order_labels(dense=Dd, thresholds=pairs), True)
+    return _rank_order_results(*ops.rank_order_labels(dense=Dd, norm_threshold=pairs[0][0], rank_threshold=pairs[0][1]), False)
+
+
 # ---- flat cuts ------------------------------------------------------------------------------------------------------
 _CUT_CACHE = {}
 
@@ -402,10 +505,15 @@ def get_facial_clusters(dist_matrix, distanceThreshold=1, all_indices=None, no_i
     equal length are ordered by their smallest index (the reference leaves that order to scipy's label numbering).  One face gives
     [[0]] (the reference's linkage raises on it).  Non-finite distances raise ValueError.
     ``method`` 'dbscan' is the DBSCAN branch (:260-265): dbscan_dense with eps = distanceThreshold and min_samples =
-    no_images_in_cluster, noise dropped, ``all_indices`` accepted and ignored, the same order; one face gives scikit-learn's answer."""
+    no_images_in_cluster, noise dropped, ``all_indices`` accepted and ignored, the same order; one face gives scikit-learn's answer.
+    ``method`` 'rankorder' is the rank-order branch (:229-239): rank_order_dense with distanceThreshold = the study's pair (norm, rank),
+    or a scalar norm threshold with the reference's default rank threshold 14; clusters of at least two faces in the reference's order;
+    ``all_indices`` and ``no_images_in_cluster`` accepted and ignored, as that branch does; one face gives []."""
     _check_method(method, CLUSTER_METHODS)
     if method == "dbscan":
         return _finish(_clusters(dbscan_dense(dist_matrix, distanceThreshold, no_images_in_cluster, device)[1]))
+    if method == "rankorder":
+        return rank_order_dense(dist_matrix, *_rank_order_threshold_pair(distanceThreshold), device=device)[0]
     D = np.asarray(dist_matrix, dtype=np.float64)
     if D.ndim != 2 or D.shape[0] != D.shape[1] or D.shape[0] < 1:
         raise ValueError("dist_matrix must be a non-empty square matrix, got shape %r" % (D.shape,))
@@ -437,12 +545,17 @@ def cluster_faces(features, distance_threshold: float, born_years=None, photo_ye
     ops.pairwise_distances plus the host age term, clipped at 0, as feature_distance_matrix builds them), and clusters shorter than
     ``min_cluster_size`` dropped.  Same order as get_facial_clusters.  ``method`` 'dbscan' is perform_clustering's DBSCAN branch:
     dbscan with eps = distance_threshold and min_samples = min_cluster_size, noise dropped, then the clusters shorter than
-    min_cluster_size (a border point claimed by an earlier cluster can leave one short); ``all_indices`` is ignored."""
+    min_cluster_size (a border point claimed by an earlier cluster can leave one short); ``all_indices`` is ignored.  ``method``
+    'rankorder' is rank_order with distance_threshold = (norm, rank) or a scalar norm threshold (rank threshold 14): clusters of at least
+    two faces; ``all_indices`` and ``min_cluster_size`` are ignored, as the reference's branch ignores them."""
     from . import _lib, ops
     _check_method(method, CLUSTER_METHODS)
     if method == "dbscan":
         _, labels = dbscan(features, distance_threshold, min_cluster_size, born_years, photo_years, device)
         return _finish(_clusters(labels), min_cluster_size)
+    if method == "rankorder":
+        return rank_order(features, *_rank_order_threshold_pair(distance_threshold), born_years=born_years, photo_years=photo_years,
+                          device=device)[0]
     torch = _lib.require_gpu()
     x = _device_tensor(features, torch.float32, device)
     if x.dim() != 2 or x.shape[0] < 1:

@@ -6,10 +6,13 @@ set -euo pipefail
 cd "$(dirname "$0")"
 # product sources.  Development builds add round 1's stem (reachable only through lower_graph(stem_fusion="stem")) and the first window 3x3
 # convolution (conv3x3_w2_bf16.hip took its layers in round 5), each kept for A/B timing, plus the calibration kernels of devtools.hip.
-SRCS="engine.hip conv_first.hip dwconv.hip pwconv_f32.hip pwconv_f16s.hip pwconv_ps.hip pool_dense.hip nn1.hip conv_bf16.hip conv1x1_bf16.hip preprocess.hip dwpw_fused.hip dwpw_f16s.hip stem2_fused.hip stem3_fused.hip stem4_fused.hip stem5_stream.hip conv_f32_mfma.hip smallnet.hip area_resize.hip stem7x7_pool.hip stem7s_stream.hip conv_dma_bf16.hip conv3x3_w2_bf16.hip conv1x1_w4_bf16.hip conv1x1_pair_bf16.hip mtcnn_post.hip linkage.hip hier_linkage.hip dbscan.hip"
+SRCS="engine.hip conv_first.hip dwconv.hip pwconv_f32.hip pwconv_f16s.hip pwconv_ps.hip pool_dense.hip nn1.hip conv_bf16.hip conv1x1_bf16.hip preprocess.hip dwpw_fused.hip dwpw_f16s.hip stem2_fused.hip stem3_fused.hip stem4_fused.hip stem5_stream.hip conv_f32_mfma.hip smallnet.hip area_resize.hip stem7x7_pool.hip stem7s_stream.hip conv_dma_bf16.hip conv3x3_w2_bf16.hip conv1x1_w4_bf16.hip conv1x1_pair_bf16.hip mtcnn_post.hip linkage.hip hier_linkage.hip dbscan.hip rank_order.hip"
 # -Wno-inline-asm: the LDS-DMA statements write M0 and say so in their clobber lists; clang warns that M0 is a
 # reserved register for every instantiation -- the declaration is the point (the compiler must not assume M0 survives)
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -Wall -Wno-unused-result -Wno-inline-asm"
+# the device code objects ship without their local symbols (several KB per source; the product stays below 4 MB,
+# tests/test_abi_cpu.py): the runtime, the profilers and tools/isa_lint.py need only the kernel symbols, which stay
+DEVICE_STRIP="-Xoffload-linker --discard-all"
 LINK="--offload-arch=gfx950"
 LINT=1
 if [ "${HSEFR_ASAN:-0}" = "1" ]; then
@@ -21,16 +24,16 @@ if [ "${HSEFR_ASAN:-0}" = "1" ]; then
   OUT=build_asan/libhsefr_asan.so; BUILD=build_asan; LINT=0
   . ./build_asan_flags.sh
 elif [ "${HSEFR_DEV:-0}" = "1" ]; then
-  OUT=../libhsefr_dev.so; BUILD=build_dev; SRCS="$SRCS stem_fused.hip conv3x3_win_bf16.hip devtools.hip"; FLAGS="$FLAGS -DHSEFR_DEV"
+  OUT=../libhsefr_dev.so; BUILD=build_dev; SRCS="$SRCS stem_fused.hip conv3x3_win_bf16.hip devtools.hip"; FLAGS="$FLAGS -DHSEFR_DEV $DEVICE_STRIP"
 else
-  OUT=../libhsefr.so; BUILD=build
+  OUT=../libhsefr.so; BUILD=build; FLAGS="$FLAGS $DEVICE_STRIP"
 fi
 OBJS=""
 PIDS=""
 mkdir -p "$BUILD"
 for s in $SRCS; do
   o="$BUILD/${s%.hip}.o"
-  if [ ! -f "$o" ] || [ "$s" -nt "$o" ] || [ common.h -nt "$o" ] || [ linkage_scan.h -nt "$o" ] || [ hsefr_dev.h -nt "$o" ] || [ ../../include/hsefr.h -nt "$o" ] || [ build.sh -nt "$o" ]; then
+  if [ ! -f "$o" ] || [ "$s" -nt "$o" ] || [ common.h -nt "$o" ] || [ linkage_scan.h -nt "$o" ] || [ hier_build.h -nt "$o" ] || [ hsefr_dev.h -nt "$o" ] || [ ../../include/hsefr.h -nt "$o" ] || [ build.sh -nt "$o" ]; then
     rm -f "$o"
     hipcc $FLAGS ${HSEFR_EXTRA_FLAGS:-} -c "$s" -o "$o" &
     PIDS="$PIDS $!"

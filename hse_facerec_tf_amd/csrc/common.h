@@ -275,6 +275,8 @@ int launch_single_linkage(const float* x, int n, int d, const float* born, const
                           double* edge_h, hipStream_t s);
 int launch_dbscan(const float* x, int n, int d, const float* born, const float* year, const double* dense, double eps, int min_samples,
                   int* labels, unsigned char* core, hipStream_t s);
+int launch_rank_order(const float* x, int n, int d, const float* born, const float* year, const double* dense, const double* thresholds,
+                      int pairs, int* labels, int* iterations, hipStream_t s);
 int launch_hier_linkage(const float* x, int n, int d, const float* born, const float* year, const double* dense, int method, int* merge_a,
                         int* merge_b, double* merge_h, int* merge_round, hipStream_t s);
 

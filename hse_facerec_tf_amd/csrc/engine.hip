@@ -1444,5 +1444,32 @@ int hsefr_dbscan(const float* x, int n, int d, const float* born, const float* y
     return launch_dbscan(x, n, d, born, year, dense, eps, min_samples, labels, core, (hipStream_t)stream);
 }
 
+static int rank_order_checks(const float* x, int n, int d, const float* born, const float* year, const double* dense, int* labels) {
+    HSEFR_REQUIRE(n >= 1, HSEFR_ERR_INVALID, "rank_order: n=%d", n);
+    HSEFR_REQUIRE((x != nullptr) != (dense != nullptr), HSEFR_ERR_INVALID, "rank_order: pass exactly one of x and dense");
+    HSEFR_REQUIRE(labels, HSEFR_ERR_INVALID, "rank_order: null pointer (labels)");
+    HSEFR_REQUIRE(!born == !year, HSEFR_ERR_INVALID, "rank_order: born and year come together");
+    HSEFR_REQUIRE(!(dense && born), HSEFR_ERR_INVALID, "rank_order: the age term belongs to the features path");
+    HSEFR_REQUIRE(dense || (d > 0 && d % 8 == 0), HSEFR_ERR_INVALID, "rank_order: d=%d must be a positive multiple of 8", d);
+    return HSEFR_OK;
+}
+
+int hsefr_rank_order_sweep(const float* x, int n, int d, const float* born, const float* year, const double* dense,
+                           const double* thresholds, int pairs, int* labels, int* iterations, hsefr_stream_t stream) {
+    const int rc = rank_order_checks(x, n, d, born, year, dense, labels);
+    if (rc != HSEFR_OK) return rc;
+    HSEFR_REQUIRE(pairs >= 1 && thresholds, HSEFR_ERR_INVALID, "rank_order: pairs=%d threshold pairs at %p", pairs, (const void*)thresholds);
+    for (int t = 0; t < 2 * pairs; ++t)
+        HSEFR_REQUIRE(isfinite(thresholds[t]) && thresholds[t] > 0, HSEFR_ERR_INVALID, "rank_order: %s_threshold=%g must be finite and > 0",
+                      t % 2 ? "rank" : "norm", thresholds[t]);
+    return launch_rank_order(x, n, d, born, year, dense, thresholds, pairs, labels, iterations, (hipStream_t)stream);
+}
+
+int hsefr_rank_order(const float* x, int n, int d, const float* born, const float* year, const double* dense, double norm_threshold,
+                     double rank_threshold, int* labels, int* iterations, hsefr_stream_t stream) {
+    const double thresholds[2] = {norm_threshold, rank_threshold};
+    return hsefr_rank_order_sweep(x, n, d, born, year, dense, thresholds, 1, labels, iterations, stream);
+}
+
 }  // extern "C"
 #pragma GCC visibility pop

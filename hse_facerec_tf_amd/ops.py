@@ -3,6 +3,7 @@ C ABI of libhsefr (include/hsefr.h "Per-kernel entry points").  Used by the unit
 and by the identification stage; the engine calls the same launchers internally."""
 from __future__ import annotations
 
+import ctypes
 from typing import Optional, Tuple
 
 import numpy as np
@@ -664,6 +665,54 @@ def dbscan_labels(x=None, dense=None, born=None, year=None, eps=0.5, min_samples
     _lib.check(_lib.lib().hsefr_dbscan(ptr(x), n, d, ptr(born), ptr(year), ptr(dense), float(eps), int(min(min_samples, n + 1)),
                                        labels.data_ptr(), core.data_ptr(), _lib.current_stream_ptr()), "hsefr_dbscan")
     return labels, core
+
+
+@_device_guarded
+def rank_order_labels(x=None, dense=None, born=None, year=None, norm_threshold=0.9, rank_threshold=14, thresholds=None):
+    """Rank-order clustering (hsefr_rank_order) -> (labels int32 [n] CUDA tensor, iterations int): labels[i] is the smallest face index of
+    face i's final cluster.  The sources are hier_linkage_merges': x [n,d] float32 features (zero columns pad d to a multiple of 8) with
+    optional born / year float32 [n], or dense [n,n] float64 distances read as their upper triangle with the diagonal counted as 0.
+    With ``thresholds`` = a sequence of (norm, rank) pairs (hsefr_rank_order_sweep) -> (labels int32 [pairs, n], list of iterations):
+    the working matrix and the face lists are built once for the whole sequence.  Needs 8 n^2 bytes of device workspace (16 n^2 for
+    a sequence of more than one pair); returns with the current stream synchronised (the host reads the cluster count every iteration)."""
+    torch = _lib.require_gpu()
+    if (x is None) == (dense is None):
+        raise ValueError("rank_order_labels: pass exactly one of x and dense")
+    if (born is None) != (year is None):
+        raise ValueError("rank_order_labels: born and year come together")
+    sweep = thresholds is not None
+    pairs = [(float(a), float(b)) for a, b in thresholds] if sweep else [(float(norm_threshold), float(rank_threshold))]
+    if not pairs:
+        raise ValueError("rank_order_labels: no threshold pairs")
+    d = 0
+    if x is not None:
+        _f32c(x, "x")
+        if x.dim() != 2:
+            raise ValueError("x must be [n, d]")
+        n, d = x.shape
+        if d % 8:
+            x = torch.nn.functional.pad(x, (0, 8 - d % 8)).contiguous()
+            d = x.shape[1]
+        for v, name in ((born, "born"), (year, "year")):
+            if v is not None and _f32c(v, name).numel() != n:
+                raise ValueError("%s has %d elements for %d rows" % (name, v.numel(), n))
+    else:
+        if born is not None:
+            raise ValueError("rank_order_labels: the age term belongs to the features path")
+        if not (dense.is_cuda and dense.dtype == torch.float64 and dense.is_contiguous() and dense.dim() == 2
+                and dense.shape[0] == dense.shape[1]):
+            raise ValueError("dense must be a contiguous square float64 CUDA tensor")
+        n = dense.shape[0]
+    if n < 1:
+        raise ValueError("rank_order_labels: no points")
+    dev = (x if x is not None else dense).device
+    labels = torch.empty((len(pairs), n), dtype=torch.int32, device=dev)
+    thr = (ctypes.c_double * (2 * len(pairs)))(*[v for pair in pairs for v in pair])
+    iters = (ctypes.c_int * len(pairs))()
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    _lib.check(_lib.lib().hsefr_rank_order_sweep(ptr(x), n, d, ptr(born), ptr(year), ptr(dense), thr, len(pairs), labels.data_ptr(), iters,
+                                                 _lib.current_stream_ptr()), "hsefr_rank_order")
+    return (labels, list(iters)) if sweep else (labels[0], int(iters[0]))
 
 
 # ---- bf16 ResNet-50 kernels -------------------------------------------------------------------------

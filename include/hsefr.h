@@ -678,6 +678,37 @@ int hsefr_hier_linkage(const float* x, int n, int d, const float* born, const fl
 int hsefr_dbscan(const float* x, int n, int d, const float* born, const float* year, const double* dense, double eps, int min_samples,
                  int* labels, unsigned char* core, hsefr_stream_t stream);
 
+/* Rank-order clustering with the reference's clusters (the rankorder_clustering branch of get_facial_clusters,
+ * facial_clustering.py:214-285; find_clusters as facial_clustering_test.py:23-239 states it with the thresholds as parameters) on the
+ * sources of hsefr_hier_linkage: x [n,d] fp32 (d multiple of 8) with optional born / year, or dense [n,n] fp64 read as its upper triangle
+ * D[min(i,j), max(i,j)] and never written; the diagonal is never read and counts as 0.  The rule, with NB = 20 and KN = 12:
+ *   every face i lists the first min(NB, n) faces (itself included) by (D[i,j], j); S[i] = the sum of the first min(KN, n) listed
+ *   distances, added in list order.  Clusters start as single faces and are ordered by their smallest face; C[a,b] = the least D[i,j]
+ *   over i in a, j in b, C[a,a] = 0, and every cluster lists the first min(NB, clusters) clusters by (C[a,b], order of b).
+ *   An iteration joins a and every b != a of a's list for which
+ *     nd = (1 / ((T[a] + T[b]) / min(KN, n) / (|a| + |b|))) * C[a,b] < norm_threshold   (T[c] = the sum of S over c's faces; nd = 0
+ *          when the mean is 0, as the study's copy of find_clusters has it), and
+ *     (pen(a,b) + pen(b,a)) / min(len(a,b), len(b,a)) < rank_threshold, where (pen, len)(a,b) walks a's list: an entry found at
+ *          position j of b's list adds j to pen, and the entry found at position 0 ends the walk (len = entries walked, else a's
+ *          list length);
+ *   the new clusters are the connected components of the joined pairs.  Iterations repeat until one leaves the number of clusters
+ *   unchanged (the first always runs).
+ * Outputs: labels [n] int32 (device) = the smallest face of each face's final cluster; *iterations (HOST int, may be null) = iterations
+ * run, the last unchanged one included.  T of a merged cluster adds its parts' T in ascending order of their smallest face (the
+ * reference adds S in Python set order, so its nd varies in the last bits from run to run).  Workspace 8 n^2 + O(n) bytes,
+ * stream-ordered, refused (HSEFR_ERR_NOMEM) before any launch; the host reads the device cluster count once per iteration, so the call
+ * returns with the stream synchronised.  Arguments are checked before any device call (HSEFR_ERR_INVALID): exactly one source, finite
+ * thresholds > 0. */
+int hsefr_rank_order(const float* x, int n, int d, const float* born, const float* year, const double* dense, double norm_threshold,
+                     double rank_threshold, int* labels, int* iterations, hsefr_stream_t stream);
+
+/* hsefr_rank_order for a sequence of threshold pairs (the clustering study's sweep, facial_clustering_test.py:450-474): thresholds =
+ * HOST [pairs][2] (norm, rank), labels = device [pairs][n], iterations = HOST [pairs] or null.  The working matrix and the face lists
+ * do not depend on the thresholds: with more than one pair they are built once and restored by device copies (workspace 16 n^2 + O(n)
+ * bytes). */
+int hsefr_rank_order_sweep(const float* x, int n, int d, const float* born, const float* year, const double* dense,
+                           const double* thresholds, int pairs, int* labels, int* iterations, hsefr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

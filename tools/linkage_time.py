@@ -7,7 +7,10 @@ nearest-neighbour rounds) for n in {2048, 9164}, against the host matrix + scipy
 With --method dbscan: hsefr_dbscan (csrc/dbscan.hip: degree scan, filtered Boruvka rounds, border scan; no N x N matrix) for the same
 n x d as single linkage at --eps / --min-samples, with the rounds used, clusters and noise, against the host matrix + scikit-learn's
 DBSCAN on it (up to n = 9164).
-usage: python tools/linkage_time.py [--method M] [--eps E] [--min-samples K] [--out FILE]"""
+With --method rankorder: hsefr_rank_order (csrc/rank_order.hip: the fp64 n x n matrix, top-20 lists, pair tests and an in-place cluster
+reduce per iteration) for n in {2048, 9164} at --norm / --rank, with the iterations, clusters and faces left single, and a three-pair
+threshold sequence next to three single calls, against the host matrix + the NumPy restatement of tests/rank_order_ref.py.
+usage: python tools/linkage_time.py [--method M] [--eps E] [--min-samples K] [--norm T] [--rank R] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -184,13 +187,66 @@ def main_dbscan(eps, min_samples, out):
     print(text)
 
 
+def rank_order_ms(x, reps, **kw):
+    ops.rank_order_labels(x=x, **kw)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        out = ops.rank_order_labels(x=x, **kw)
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps, out
+
+
+def main_rankorder(norm, rank, out):
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import rank_order_ref as ror
+    sweep = [(norm, rank), (norm - 0.1, rank), (norm + 0.04, rank + 4)]
+    lines = ["# rank-order clustering from unit-norm features, fp32 distances in an fp64 matrix (tools/linkage_time.py --method rankorder "
+             "--norm %g --rank %g); %s" % (norm, rank, torch.cuda.get_device_name(0)),
+             "# GPU: hsefr_rank_order, CUDA-event time per call (mean of reps after one warm-up): matrix build, top-20 lists, and per",
+             "# iteration the pair tests, components, in-place reduce and new lists; the host reads one count per iteration",
+             "# single = faces left in no cluster of two; sweep3_ms = one call with the three pairs %s (matrix and" % (sweep,),
+             "# first lists built once, restored by device copies), three_ms = the same pairs as three calls",
+             "# host: identification.feature_distance_matrix (GPU distances + copy to a host float64 matrix) + the NumPy restatement of",
+             "# tests/rank_order_ref.py (the reference's own find_clusters is interpreted Python over face objects: 5-18 s for ONE",
+             "# threshold pair at n = 1000 on a development CPU, measured there and not on this machine -- context, not a speed-up)",
+             "%7s %5s %11s %6s %9s %7s %11s %11s %12s %12s %10s" % ("n", "d", "gpu_ms", "iters", "clusters", "single", "sweep3_ms",
+                                                                "three_ms", "host_D_s", "host_ro_s", "speedup")]
+    for n in (2048, 9164):
+        for d in DIMS:
+            x = unit_rows(n, d, n + d)
+            ms, (labels, iters) = rank_order_ms(x, 3, norm_threshold=norm, rank_threshold=rank)
+            sweep_ms, _ = rank_order_ms(x, 2, thresholds=sweep)
+            three_ms = sum(rank_order_ms(x, 2, norm_threshold=a, rank_threshold=b)[0] for a, b in sweep)
+            clusters = ror.clusters_of(labels.cpu().numpy())
+            t0 = time.perf_counter()
+            D = identification.feature_distance_matrix(x.cpu().numpy())
+            t1 = time.perf_counter()
+            host, host_iters, _ = ror.rank_order(D, norm, rank)
+            hd, hr = t1 - t0, time.perf_counter() - t1
+            lines.append("%7d %5d %11.2f %6d %9d %7d %11.2f %11.2f %12.3f %12.3f %10.1f"
+                         % (n, d, ms, iters, len(clusters), n - sum(map(len, clusters)), sweep_ms, three_ms, hd, hr, (hd + hr) * 1e3 / ms))
+            print(lines[-1], flush=True)
+    text = "\n".join(lines) + "\n"
+    if out:
+        with open(out, "w") as f:
+            f.write(text)
+    print(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
-    ap.add_argument("--method", default="single", choices=["single", "average", "complete", "weighted", "dbscan"])
+    ap.add_argument("--method", default="single", choices=["single", "average", "complete", "weighted", "dbscan", "rankorder"])
     ap.add_argument("--eps", type=float, default=0.9, help="--method dbscan: the neighbourhood radius")
     ap.add_argument("--min-samples", type=int, default=4, help="--method dbscan: points within eps (itself included) that make a core")
+    ap.add_argument("--norm", type=float, default=1.06, help="--method rankorder: the normalised-distance threshold")
+    ap.add_argument("--rank", type=float, default=16, help="--method rankorder: the rank-order threshold")
     args = ap.parse_args()
+    if args.method == "rankorder":
+        return main_rankorder(args.norm, args.rank, args.out)
     if args.method == "dbscan":
         return main_dbscan(args.eps, args.min_samples, args.out)
     if args.method != "single":
