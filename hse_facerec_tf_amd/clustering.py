@@ -118,37 +118,6 @@ def _age_arrays(born_years, photo_years, n):
     return by, yr
 
 
-def linkage_single(features, born_years=None, photo_years=None, device=None) -> np.ndarray:
-    """hac.linkage(squareform(D), 'single') for D = the feature distance of perform_clustering (process_photos.py:45-56):
-    |x_i - x_j| (+ the age term with born / photo years), from the features [n, d] on the GPU, with no N x N matrix anywhere."""
-    from . import _lib, ops
-    torch = _lib.require_gpu()
-    x = _device_tensor(features, torch.float32, device)
-    if x.dim() != 2 or x.shape[0] < 1:
-        raise ValueError("features must be [n, d] with n >= 1")
-    n = x.shape[0]
-    born, year = _age_tensors(*_age_arrays(born_years, photo_years, n), x.device)
-    ea, eb, eh = ops.single_linkage_edges(x=x, born=born, year=year)
-    return linkage_from_edges(ea.cpu().numpy(), eb.cpu().numpy(), eh.cpu().numpy(), n)
-
-
-def linkage_single_dense(dist_matrix, device=None) -> np.ndarray:
-    """hac.linkage(squareform(dist_matrix, checks=False), 'single') with the spanning tree built on the GPU from the fp64 matrix's
-    upper triangle: the heights are scipy's, bit for bit."""
-    from . import _lib, ops
-    torch = _lib.require_gpu()
-    D = dist_matrix if isinstance(dist_matrix, torch.Tensor) else np.asarray(dist_matrix, dtype=np.float64)
-    if D.ndim != 2 or D.shape[0] != D.shape[1] or D.shape[0] < 1:
-        raise ValueError("dist_matrix must be a non-empty square matrix, got shape %r" % (tuple(D.shape),))
-    if isinstance(D, np.ndarray) and not np.isfinite(D).all():
-        raise ValueError("dist_matrix holds non-finite values")
-    if isinstance(D, torch.Tensor) and not bool(torch.isfinite(D).all()):
-        raise ValueError("dist_matrix holds non-finite values")
-    n = D.shape[0]
-    ea, eb, eh = ops.single_linkage_edges(dense=_device_tensor(D, torch.float64, device))
-    return linkage_from_edges(ea.cpu().numpy(), eb.cpu().numpy(), eh.cpu().numpy(), n)
-
-
 def _age_tensors(by, yr, dev):
     import torch
     if by is None:
@@ -156,46 +125,84 @@ def _age_tensors(by, yr, dev):
     return torch.from_numpy(by.astype(np.float32)).to(dev), torch.from_numpy(yr.astype(np.float32)).to(dev)
 
 
+# ---- the two distance sources of every entry point: checked on the host (for host inputs) before any device work ------
+def _check_dist_matrix(dist_matrix, negative=None):
+    """A distance-matrix argument, host or CUDA -> the float64 array (or the caller's tensor): square, non-empty and finite, and with
+    ``negative`` = the caller's message for it, free of negative entries (DBSCAN and rank-order demand that, linkage does not)."""
+    D = dist_matrix if hasattr(dist_matrix, "is_cuda") else np.asarray(dist_matrix, dtype=np.float64)
+    if D.ndim != 2 or D.shape[0] != D.shape[1] or D.shape[0] < 1:
+        raise ValueError("dist_matrix must be a non-empty square matrix, got shape %r" % (tuple(D.shape),))
+    if not bool(np.isfinite(D).all() if isinstance(D, np.ndarray) else D.isfinite().all()):
+        raise ValueError("dist_matrix holds non-finite values")
+    if negative is not None and bool((D < 0).any()):
+        raise ValueError(negative)
+    return D
+
+
+def _dist_matrix(dist_matrix, device, negative=None):
+    """_check_dist_matrix -> the float64 device tensor ops' ``dense`` takes."""
+    from . import _lib
+    D = _check_dist_matrix(dist_matrix, negative)
+    return _device_tensor(D, _lib.require_gpu().float64, device)
+
+
+def _features(features, born_years, photo_years, device, finite):
+    """A features argument, host or CUDA, with its optional age arrays -> (x, born, year) as ops takes them: the float32 [n, d] device
+    tensor with n >= 1 and the float32 born / year device tensors (None without an age term).  ``finite``: non-finite features raise
+    (linkage, dbscan and rank_order check; linkage_single and cluster_faces' own pass do not)."""
+    from . import _lib
+    if not hasattr(features, "is_cuda"):
+        features = np.asarray(features, dtype=np.float32)
+    if features.ndim != 2 or features.shape[0] < 1:
+        raise ValueError("features must be [n, d] with n >= 1")
+    if finite and isinstance(features, np.ndarray) and not np.isfinite(features).all():
+        raise ValueError("features hold non-finite values")
+    by, yr = _age_arrays(born_years, photo_years, features.shape[0])
+    torch = _lib.require_gpu()
+    x = _device_tensor(features, torch.float32, device)
+    if finite and not bool(torch.isfinite(x).all()):
+        raise ValueError("features hold non-finite values")
+    return (x,) + _age_tensors(by, yr, x.device)
+
+
+def _linkage(method, n, **source):
+    """Z of ``method`` for n points from ops' source arguments (x, born, year or dense)."""
+    from . import ops
+    if method == "single":
+        return linkage_from_edges(*(t.cpu().numpy() for t in ops.single_linkage_edges(**source)), n)
+    return linkage_from_merges(*(t.cpu().numpy() for t in ops.hier_linkage_merges(method=method, **source)), n)
+
+
+def linkage_single(features, born_years=None, photo_years=None, device=None) -> np.ndarray:
+    """hac.linkage(squareform(D), 'single') for D = the feature distance of perform_clustering (process_photos.py:45-56):
+    |x_i - x_j| (+ the age term with born / photo years), from the features [n, d] on the GPU, with no N x N matrix anywhere."""
+    x, born, year = _features(features, born_years, photo_years, device, finite=False)
+    return _linkage("single", x.shape[0], x=x, born=born, year=year)
+
+
+def linkage_single_dense(dist_matrix, device=None) -> np.ndarray:
+    """hac.linkage(squareform(dist_matrix, checks=False), 'single') with the spanning tree built on the GPU from the fp64 matrix's
+    upper triangle: the heights are scipy's, bit for bit."""
+    return linkage_dense(dist_matrix, "single", device)
+
+
 def linkage(features, method, born_years=None, photo_years=None, device=None) -> np.ndarray:
     """hac.linkage(squareform(D), method) for D = the feature distance of perform_clustering (process_photos.py:45-56) from the
     features [n, d] on the GPU.  'single' is linkage_single (no N x N matrix); 'average', 'complete' and 'weighted' build D as an fp64
     device matrix (fp32 distances widened, 8 n^2 bytes) and merge reciprocal nearest neighbours there.  Non-finite features raise
     ValueError; so does any other method."""
-    from . import _lib, ops
     _check_method(method)
-    torch = _lib.require_gpu()
-    x = _device_tensor(features, torch.float32, device)
-    if x.dim() != 2 or x.shape[0] < 1:
-        raise ValueError("features must be [n, d] with n >= 1")
-    if not bool(torch.isfinite(x).all()):
-        raise ValueError("features hold non-finite values")
-    if method == "single":
-        return linkage_single(x, born_years, photo_years)
-    n = x.shape[0]
-    born, year = _age_tensors(*_age_arrays(born_years, photo_years, n), x.device)
-    ma, mb, mh, mr = ops.hier_linkage_merges(x=x, born=born, year=year, method=method)
-    return linkage_from_merges(ma.cpu().numpy(), mb.cpu().numpy(), mh.cpu().numpy(), mr.cpu().numpy(), n)
+    x, born, year = _features(features, born_years, photo_years, device, finite=True)
+    return _linkage(method, x.shape[0], x=x, born=born, year=year)
 
 
 def linkage_dense(dist_matrix, method, device=None) -> np.ndarray:
     """hac.linkage(squareform(dist_matrix, checks=False), method), the matrix read as its upper triangle: 'single' is
     linkage_single_dense, 'average' / 'complete' / 'weighted' run on an fp64 device copy with scipy's Lance-Williams updates (complete
     linkage's heights are scipy's bit for bit; the two means agree to rounding)."""
-    from . import _lib, ops
     _check_method(method)
-    if method == "single":
-        return linkage_single_dense(dist_matrix, device)
-    torch = _lib.require_gpu()
-    D = dist_matrix if isinstance(dist_matrix, torch.Tensor) else np.asarray(dist_matrix, dtype=np.float64)
-    if D.ndim != 2 or D.shape[0] != D.shape[1] or D.shape[0] < 1:
-        raise ValueError("dist_matrix must be a non-empty square matrix, got shape %r" % (tuple(D.shape),))
-    if isinstance(D, np.ndarray) and not np.isfinite(D).all():
-        raise ValueError("dist_matrix holds non-finite values")
-    if isinstance(D, torch.Tensor) and not bool(torch.isfinite(D).all()):
-        raise ValueError("dist_matrix holds non-finite values")
-    n = D.shape[0]
-    ma, mb, mh, mr = ops.hier_linkage_merges(dense=_device_tensor(D, torch.float64, device), method=method)
-    return linkage_from_merges(ma.cpu().numpy(), mb.cpu().numpy(), mh.cpu().numpy(), mr.cpu().numpy(), n)
+    D = _dist_matrix(dist_matrix, device)
+    return _linkage(method, D.shape[0], dense=D)
 
 
 # ---- DBSCAN ---------------------------------------------------------------------------------------------------------
@@ -216,20 +223,9 @@ def dbscan(features, eps=0.5, min_samples=5, born_years=None, photo_years=None, 
     perform_clustering (process_photos.py:45-56) from the features [n, d] on the GPU, with no N x N matrix anywhere ->
     (core_sample_indices, labels) int64, scikit-learn's.  Distances are the fp32 ones of linkage_single, compared as (double)w <= eps.
     Bad eps, min_samples, features or age arrays raise ValueError before any device work (for host inputs)."""
-    from . import _lib, ops
+    from . import ops
     _check_dbscan_args(eps, min_samples)
-    if not hasattr(features, "is_cuda"):
-        features = np.asarray(features, dtype=np.float32)
-    if features.ndim != 2 or features.shape[0] < 1:
-        raise ValueError("features must be [n, d] with n >= 1")
-    if isinstance(features, np.ndarray) and not np.isfinite(features).all():
-        raise ValueError("features hold non-finite values")
-    born_years, photo_years = _age_arrays(born_years, photo_years, features.shape[0])
-    torch = _lib.require_gpu()
-    x = _device_tensor(features, torch.float32, device)
-    if not bool(torch.isfinite(x).all()):
-        raise ValueError("features hold non-finite values")
-    born, year = _age_tensors(born_years, photo_years, x.device)
+    x, born, year = _features(features, born_years, photo_years, device, finite=True)
     return _dbscan_result(*ops.dbscan_labels(x=x, born=born, year=year, eps=eps, min_samples=min_samples))
 
 
@@ -237,17 +233,10 @@ def dbscan_dense(dist_matrix, eps=0.5, min_samples=5, device=None):
     """sklearn.cluster.dbscan(dist_matrix, eps, min_samples=min_samples, metric="precomputed") on the GPU -> (core_sample_indices,
     labels) int64.  The matrix is read as its upper triangle D[min(i,j), max(i,j)] (scikit-learn reads whole rows: the results agree
     on every symmetric matrix).  A non-square, empty, non-finite or negative matrix raises ValueError, as do bad eps / min_samples."""
-    from . import _lib, ops
+    from . import ops
     _check_dbscan_args(eps, min_samples)
-    D = dist_matrix if hasattr(dist_matrix, "is_cuda") else np.asarray(dist_matrix, dtype=np.float64)
-    if D.ndim != 2 or D.shape[0] != D.shape[1] or D.shape[0] < 1:
-        raise ValueError("dist_matrix must be a non-empty square matrix, got shape %r" % (tuple(D.shape),))
-    if not bool(np.isfinite(D).all() if isinstance(D, np.ndarray) else D.isfinite().all()):
-        raise ValueError("dist_matrix holds non-finite values")
-    if bool((D < 0).any()):
-        raise ValueError("dist_matrix holds negative values (scikit-learn rejects them in a precomputed matrix)")
-    torch = _lib.require_gpu()
-    return _dbscan_result(*ops.dbscan_labels(dense=_device_tensor(D, torch.float64, device), eps=eps, min_samples=min_samples))
+    D = _dist_matrix(dist_matrix, device, "dist_matrix holds negative values (scikit-learn rejects them in a precomputed matrix)")
+    return _dbscan_result(*ops.dbscan_labels(dense=D, eps=eps, min_samples=min_samples))
 
 
 def _clusters(labels) -> List[np.ndarray]:
@@ -298,11 +287,14 @@ def _rank_order_clusters(labels) -> List[List[int]]:
     return _finish(_groups(np.asarray(labels)), 2)
 
 
-def _rank_order_results(labels, iters, sweep):
-    labels = labels.cpu().numpy()
+def _rank_order(pairs, sweep, **source):
+    """ops.rank_order_labels on its source arguments (x, born, year or dense) -> what rank_order returns."""
+    from . import ops
     if not sweep:
-        return _rank_order_clusters(labels), iters
-    return [(_rank_order_clusters(row), it) for row, it in zip(labels, iters)]
+        labels, iters = ops.rank_order_labels(norm_threshold=pairs[0][0], rank_threshold=pairs[0][1], **source)
+        return _rank_order_clusters(labels.cpu().numpy()), iters
+    labels, iters = ops.rank_order_labels(thresholds=pairs, **source)
+    return [(_rank_order_clusters(row), it) for row, it in zip(labels.cpu().numpy(), iters)]
 
 
 def rank_order(features, norm_threshold=RANK_ORDER_NORM_THRESHOLD, rank_threshold=RANK_ORDER_RANK_THRESHOLD, born_years=None,
@@ -314,24 +306,9 @@ def rank_order(features, norm_threshold=RANK_ORDER_NORM_THRESHOLD, rank_threshol
     linkage, widened to an fp64 n x n device matrix.  ``thresholds`` = a sequence of (norm, rank) pairs returns one (clusters,
     iterations) per pair from one matrix build.  Bad thresholds, features or age arrays raise ValueError before any device work (for
     host inputs).  One face gives []."""
-    from . import _lib, ops
     pairs, sweep = _rank_order_pairs(norm_threshold, rank_threshold, thresholds)
-    if not hasattr(features, "is_cuda"):
-        features = np.asarray(features, dtype=np.float32)
-    if features.ndim != 2 or features.shape[0] < 1:
-        raise ValueError("features must be [n, d] with n >= 1")
-    if isinstance(features, np.ndarray) and not np.isfinite(features).all():
-        raise ValueError("features hold non-finite values")
-    born_years, photo_years = _age_arrays(born_years, photo_years, features.shape[0])
-    torch = _lib.require_gpu()
-    x = _device_tensor(features, torch.float32, device)
-    if not bool(torch.isfinite(x).all()):
-        raise ValueError("features hold non-finite values")
-    born, year = _age_tensors(born_years, photo_years, x.device)
-    if sweep:
-        return _rank_order_results(*ops.rank_order_labels(x=x, born=born, year=year, thresholds=pairs), True)
-    return _rank_order_results(*ops.rank_order_labels(x=x, born=born, year=year, norm_threshold=pairs[0][0], rank_threshold=pairs[0][1]),
-                               False)
+    x, born, year = _features(features, born_years, photo_years, device, finite=True)
+    return _rank_order(pairs, sweep, x=x, born=born, year=year)
 
 
 def rank_order_dense(dist_matrix, norm_threshold=RANK_ORDER_NORM_THRESHOLD, rank_threshold=RANK_ORDER_RANK_THRESHOLD, device=None,
@@ -340,20 +317,8 @@ def rank_order_dense(dist_matrix, norm_threshold=RANK_ORDER_NORM_THRESHOLD, rank
     the GPU -> (clusters, iterations).  The matrix is read as its upper triangle D[min(i,j), max(i,j)] and its diagonal counts as 0 (the
     reference reads whole rows: the results agree on every symmetric matrix with a zero diagonal).  A non-square, empty, non-finite or
     negative matrix raises ValueError, as do bad thresholds.  ``thresholds`` as in rank_order."""
-    from . import _lib, ops
     pairs, sweep = _rank_order_pairs(norm_threshold, rank_threshold, thresholds)
-    D = dist_matrix if hasattr(dist_matrix, "is_cuda") else np.asarray(dist_matrix, dtype=np.float64)
-    if D.ndim != 2 or D.shape[0] != D.shape[1] or D.shape[0] < 1:
-        raise ValueError("dist_matrix must be a non-empty square matrix, got shape %r" % (tuple(D.shape),))
-    if not bool(np.isfinite(D).all() if isinstance(D, np.ndarray) else D.isfinite().all()):
-        raise ValueError("dist_matrix holds non-finite values")
-    if bool((D < 0).any()):
-        raise ValueError("dist_matrix holds negative values")
-    torch = _lib.require_gpu()
-    Dd = _device_tensor(D, torch.float64, device)
-    if sweep:
-        return _rank_order_results(*ops.rank_order_labels(dense=Dd, thresholds=pairs), True)
-    return _rank_order_results(*ops.rank_order_labels(dense=Dd, norm_threshold=pairs[0][0], rank_threshold=pairs[0][1]), False)
+    return _rank_order(pairs, sweep, dense=_dist_matrix(dist_matrix, device, "dist_matrix holds negative values"))
 
 
 # ---- flat cuts ------------------------------------------------------------------------------------------------------
@@ -489,6 +454,21 @@ def _split_same_photo(D_sub: np.ndarray, photo: np.ndarray) -> List[np.ndarray]:
     return [np.flatnonzero(lab == v) for v in range(int(lab.max()) + 1)]
 
 
+def _split_groups(groups, all_indices, n, sub_dist) -> List[np.ndarray]:
+    """The same-photo split of every cluster of at least two faces; all_indices = the photo of each of the n faces, sub_dist(g) = the
+    distances among the faces g of one cluster."""
+    photo = np.asarray(all_indices).reshape(-1)
+    if len(photo) != n:
+        raise ValueError("%d faces, %d photo indices" % (n, len(photo)))
+    clusters = []
+    for g in groups:
+        if len(g) > 1:
+            clusters.extend(g[part] for part in _split_same_photo(sub_dist(g), photo[g]))
+        else:
+            clusters.append(g)
+    return clusters
+
+
 def _finish(clusters: List[np.ndarray], min_size: int = 1) -> List[List[int]]:
     out = [sorted(int(i) for i in c) for c in clusters if len(c) >= min_size]
     out.sort(key=lambda c: (-len(c), c[0]))
@@ -514,27 +494,14 @@ def get_facial_clusters(dist_matrix, distanceThreshold=1, all_indices=None, no_i
         return _finish(_clusters(dbscan_dense(dist_matrix, distanceThreshold, no_images_in_cluster, device)[1]))
     if method == "rankorder":
         return rank_order_dense(dist_matrix, *_rank_order_threshold_pair(distanceThreshold), device=device)[0]
-    D = np.asarray(dist_matrix, dtype=np.float64)
-    if D.ndim != 2 or D.shape[0] != D.shape[1] or D.shape[0] < 1:
-        raise ValueError("dist_matrix must be a non-empty square matrix, got shape %r" % (D.shape,))
-    if not np.isfinite(D).all():
-        raise ValueError("dist_matrix holds non-finite values")
+    D = _check_dist_matrix(np.asarray(dist_matrix, dtype=np.float64))
     n = D.shape[0]
     if n == 1:
         return [[0]]
     groups = _groups(fcluster_distance(linkage_dense(D, method, device), distanceThreshold))
     if all_indices is None:
         return _finish(groups)
-    photo = np.asarray(all_indices).reshape(-1)
-    if len(photo) != n:
-        raise ValueError("%d faces, %d photo indices" % (n, len(photo)))
-    clusters = []
-    for g in groups:
-        if len(g) > 1:
-            clusters.extend(g[part] for part in _split_same_photo(D[np.ix_(g, g)], photo[g]))
-        else:
-            clusters.append(g)
-    return _finish(clusters)
+    return _finish(_split_groups(groups, all_indices, n, lambda g: D[np.ix_(g, g)]))
 
 
 def cluster_faces(features, distance_threshold: float, born_years=None, photo_years=None, all_indices=None,
@@ -548,7 +515,7 @@ def cluster_faces(features, distance_threshold: float, born_years=None, photo_ye
     min_cluster_size (a border point claimed by an earlier cluster can leave one short); ``all_indices`` is ignored.  ``method``
     'rankorder' is rank_order with distance_threshold = (norm, rank) or a scalar norm threshold (rank threshold 14): clusters of at least
     two faces; ``all_indices`` and ``min_cluster_size`` are ignored, as the reference's branch ignores them."""
-    from . import _lib, ops
+    from . import ops
     _check_method(method, CLUSTER_METHODS)
     if method == "dbscan":
         _, labels = dbscan(features, distance_threshold, min_cluster_size, born_years, photo_years, device)
@@ -556,10 +523,7 @@ def cluster_faces(features, distance_threshold: float, born_years=None, photo_ye
     if method == "rankorder":
         return rank_order(features, *_rank_order_threshold_pair(distance_threshold), born_years=born_years, photo_years=photo_years,
                           device=device)[0]
-    torch = _lib.require_gpu()
-    x = _device_tensor(features, torch.float32, device)
-    if x.dim() != 2 or x.shape[0] < 1:
-        raise ValueError("features must be [n, d] with n >= 1")
+    x = _features(features, born_years, photo_years, device, finite=False)[0]
     n = x.shape[0]
     by, yr = _age_arrays(born_years, photo_years, n)
     if n == 1:
@@ -568,15 +532,10 @@ def cluster_faces(features, distance_threshold: float, born_years=None, photo_ye
     groups = _groups(fcluster_distance(Z, distance_threshold))
     if all_indices is None:
         return _finish(groups, min_cluster_size)
-    photo = np.asarray(all_indices).reshape(-1)
-    if len(photo) != n:
-        raise ValueError("%d faces, %d photo indices" % (n, len(photo)))
+    import torch
     xp = x if x.shape[1] % 8 == 0 else torch.nn.functional.pad(x, (0, 8 - x.shape[1] % 8)).contiguous()
-    clusters = []
-    for g in groups:
-        if len(g) < 2:
-            clusters.append(g)
-            continue
+
+    def sub_dist(g):
         rows = xp[torch.from_numpy(g).to(x.device)].contiguous()
         D = ops.pairwise_distances(rows).cpu().numpy().astype(np.float64)
         if by is not None:
@@ -584,9 +543,8 @@ def cluster_faces(features, distance_threshold: float, born_years=None, photo_ye
             max_year = np.maximum(y[:, None], y[None, :])
             ai, aj = max_year - b[:, None], max_year - b[None, :]
             D = D + 0.1 * (ai - aj) ** 2 / (ai + aj)
-        D = np.clip(D, 0, None)
-        clusters.extend(g[part] for part in _split_same_photo(D, photo[g]))
-    return _finish(clusters, min_cluster_size)
+        return np.clip(D, 0, None)
+    return _finish(_split_groups(groups, all_indices, n, sub_dist), min_cluster_size)
 
 
 # ---- scoring --------------------------------------------------------------------------------------------------------

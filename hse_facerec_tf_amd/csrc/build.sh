@@ -33,7 +33,12 @@ PIDS=""
 mkdir -p "$BUILD"
 for s in $SRCS; do
   o="$BUILD/${s%.hip}.o"
-  if [ ! -f "$o" ] || [ "$s" -nt "$o" ] || [ common.h -nt "$o" ] || [ linkage_scan.h -nt "$o" ] || [ hier_build.h -nt "$o" ] || [ hsefr_dev.h -nt "$o" ] || [ ../../include/hsefr.h -nt "$o" ] || [ build.sh -nt "$o" ]; then
+  # an object is stale against its source, EVERY header here (by glob: a new header needs no edit of this line), the public header and this script
+  stale=0
+  for dep in "$s" *.h ../../include/hsefr.h build.sh; do
+    if [ ! -f "$o" ] || [ "$dep" -nt "$o" ]; then stale=1; fi
+  done
+  if [ "$stale" = 1 ]; then
     rm -f "$o"
     hipcc $FLAGS ${HSEFR_EXTRA_FLAGS:-} -c "$s" -o "$o" &
     PIDS="$PIDS $!"

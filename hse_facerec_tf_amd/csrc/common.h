@@ -271,14 +271,20 @@ int launch_cv_resize(const unsigned char* in, float* out, int n, int H, int W, i
 int launch_area_level(const unsigned char* src, float* dst, int sh, int sw, int dh, int dw, hipStream_t s);
 int launch_area_crops(const unsigned char* src, const int* boxes, float* dst, int sh, int sw, int n, int size, hipStream_t s);
 int launch_pairwise_dist(const float* x, const float* y, int n, int m, int d, float* out, hipStream_t s);
-int launch_single_linkage(const float* x, int n, int d, const float* born, const float* year, const double* dense, int* edge_a, int* edge_b,
-                          double* edge_h, hipStream_t s);
-int launch_dbscan(const float* x, int n, int d, const float* born, const float* year, const double* dense, double eps, int min_samples,
-                  int* labels, unsigned char* core, hipStream_t s);
-int launch_rank_order(const float* x, int n, int d, const float* born, const float* year, const double* dense, const double* thresholds,
-                      int pairs, int* labels, int* iterations, hipStream_t s);
-int launch_hier_linkage(const float* x, int n, int d, const float* born, const float* year, const double* dense, int method, int* merge_a,
-                        int* merge_b, double* merge_h, int* merge_round, hipStream_t s);
+// The distance source of the clustering entry points (hsefr_single_linkage, _hier_linkage, _dbscan, _rank_order): float32 features x [n,d] (d a multiple of 8) with
+// optional born / year [n], or a caller's float64 dense [n,n] read as its upper triangle -- exactly one of x and dense is set.
+// w(i,j) itself is linkage_scan.h's.
+struct DistSource {
+    const float* x;
+    int n, d;
+    const float* born;
+    const float* year;
+    const double* dense;
+};
+int launch_single_linkage(const DistSource& src, int* edge_a, int* edge_b, double* edge_h, hipStream_t s);
+int launch_dbscan(const DistSource& src, double eps, int min_samples, int* labels, unsigned char* core, hipStream_t s);
+int launch_rank_order(const DistSource& src, const double* thresholds, int pairs, int* labels, int* iterations, hipStream_t s);
+int launch_hier_linkage(const DistSource& src, int method, int* merge_a, int* merge_b, double* merge_h, int* merge_round, hipStream_t s);
 
 bool dwpw_fused_supported(int c, int cout, int stride, int act_dw, int act_pw);
 int launch_dwpw_fused(const float* x, const float* wd, const float* dscale, const float* dshift, const float* wp_t,

@@ -166,8 +166,8 @@ __global__ __launch_bounds__(256) void db_label_kernel(const unsigned char* __re
 
 }  // namespace
 
-int launch_dbscan(const float* x, int n, int d, const float* born, const float* year, const double* dense, double eps, int min_samples,
-                  int* labels, unsigned char* core, hipStream_t s) {
+int launch_dbscan(const DistSource& src, double eps, int min_samples, int* labels, unsigned char* core, hipStream_t s) {
+    const int n = src.n;
     // Boruvka's workspace, then int arrays seed, cs, border, rank, then the core flags when the caller keeps none
     const size_t bytes = boruvka_bytes(n) + (size_t)n * 4 * 4 + (core ? 0 : (size_t)n);
     char* ws = nullptr;
@@ -186,17 +186,17 @@ int launch_dbscan(const float* x, int n, int d, const float* born, const float* 
 
     const dim3 blk(256), g1((n + 255) / 256), gf((n + 31) / 32), gd((n + 63) / 64);
     HSEFR_LAUNCH(db_init_kernel, g1, blk, 0, s, seed, n);
-    if (dense)
-        HSEFR_LAUNCH(db_scan_dense_kernel<false>, gd, blk, 0, s, dense, n, eps, min_samples, cs, core, border);
+    if (src.dense)
+        HSEFR_LAUNCH(db_scan_dense_kernel<false>, gd, blk, 0, s, src.dense, n, eps, min_samples, cs, core, border);
     else
-        HSEFR_LAUNCH(db_scan_feat_kernel<false>, gf, blk, 0, s, x, n, d, born, year, eps_f, min_samples, cs, core, border);
-    const int* label = boruvka_rounds(x, n, d, born, year, dense, core, eps_f, eps, ws, nullptr, nullptr, nullptr, s);
+        HSEFR_LAUNCH(db_scan_feat_kernel<false>, gf, blk, 0, s, src.x, n, src.d, src.born, src.year, eps_f, min_samples, cs, core, border);
+    const int* label = boruvka_rounds(src, core, eps_f, eps, ws, nullptr, nullptr, nullptr, s);
     HSEFR_LAUNCH(db_seed_kernel, g1, blk, 0, s, label, core, seed, n);
     HSEFR_LAUNCH(db_cs_kernel, g1, blk, 0, s, label, core, seed, cs, n);
-    if (dense)
-        HSEFR_LAUNCH(db_scan_dense_kernel<true>, gd, blk, 0, s, dense, n, eps, min_samples, cs, core, border);
+    if (src.dense)
+        HSEFR_LAUNCH(db_scan_dense_kernel<true>, gd, blk, 0, s, src.dense, n, eps, min_samples, cs, core, border);
     else
-        HSEFR_LAUNCH(db_scan_feat_kernel<true>, gf, blk, 0, s, x, n, d, born, year, eps_f, min_samples, cs, core, border);
+        HSEFR_LAUNCH(db_scan_feat_kernel<true>, gf, blk, 0, s, src.x, n, src.d, src.born, src.year, eps_f, min_samples, cs, core, border);
     HSEFR_LAUNCH(db_rank_kernel, dim3(1), dim3(1024), 0, s, core, cs, rank, n);
     HSEFR_LAUNCH(db_label_kernel, g1, blk, 0, s, core, cs, border, rank, labels, n);
     const int rc = launch_status("dbscan");

@@ -1407,62 +1407,53 @@ int hsefr_pairwise_dist(const float* x, const float* y, int n, int m, int d, flo
     return launch_pairwise_dist(x, y, n, m, d, out, (hipStream_t)stream);
 }
 
+// The checks every clustering entry point makes of its distance source, with the operation's name in front of each message
+static int check_dist_source(const char* op, const DistSource& src) {
+    HSEFR_REQUIRE(src.n >= 1, HSEFR_ERR_INVALID, "%s: n=%d", op, src.n);
+    HSEFR_REQUIRE((src.x != nullptr) != (src.dense != nullptr), HSEFR_ERR_INVALID, "%s: pass exactly one of x and dense", op);
+    HSEFR_REQUIRE(!src.born == !src.year, HSEFR_ERR_INVALID, "%s: born and year come together", op);
+    HSEFR_REQUIRE(!(src.dense && src.born), HSEFR_ERR_INVALID, "%s: the age term belongs to the features path", op);
+    HSEFR_REQUIRE(src.dense || (src.d > 0 && src.d % 8 == 0), HSEFR_ERR_INVALID, "%s: d=%d must be a positive multiple of 8", op, src.d);
+    return HSEFR_OK;
+}
 int hsefr_single_linkage(const float* x, int n, int d, const float* born, const float* year, const double* dense, int* edge_a, int* edge_b,
                          double* edge_h, hsefr_stream_t stream) {
-    HSEFR_REQUIRE(n >= 1, HSEFR_ERR_INVALID, "single_linkage: n=%d", n);
-    HSEFR_REQUIRE((x != nullptr) != (dense != nullptr), HSEFR_ERR_INVALID, "single_linkage: pass exactly one of x and dense");
+    const DistSource src = {x, n, d, born, year, dense};
+    if (const int rc = check_dist_source("single_linkage", src)) return rc;
     HSEFR_REQUIRE(edge_a && edge_b && edge_h, HSEFR_ERR_INVALID, "single_linkage: null pointer (edge outputs)");
-    HSEFR_REQUIRE(!born == !year, HSEFR_ERR_INVALID, "single_linkage: born and year come together");
-    HSEFR_REQUIRE(!(dense && born), HSEFR_ERR_INVALID, "single_linkage: the age term belongs to the features path");
-    HSEFR_REQUIRE(dense || (d > 0 && d % 8 == 0), HSEFR_ERR_INVALID, "single_linkage: d=%d must be a positive multiple of 8", d);
-    return launch_single_linkage(x, n, d, born, year, dense, edge_a, edge_b, edge_h, (hipStream_t)stream);
+    return launch_single_linkage(src, edge_a, edge_b, edge_h, (hipStream_t)stream);
 }
 
 int hsefr_hier_linkage(const float* x, int n, int d, const float* born, const float* year, const double* dense, int method, int* merge_a,
                        int* merge_b, double* merge_h, int* merge_round, hsefr_stream_t stream) {
-    HSEFR_REQUIRE(n >= 1, HSEFR_ERR_INVALID, "hier_linkage: n=%d", n);
+    const DistSource src = {x, n, d, born, year, dense};
+    if (const int rc = check_dist_source("hier_linkage", src)) return rc;
     HSEFR_REQUIRE(method == HSEFR_LINK_AVERAGE || method == HSEFR_LINK_COMPLETE || method == HSEFR_LINK_WEIGHTED, HSEFR_ERR_INVALID,
                   "hier_linkage: method=%d (HSEFR_LINK_AVERAGE, _COMPLETE or _WEIGHTED)", method);
-    HSEFR_REQUIRE((x != nullptr) != (dense != nullptr), HSEFR_ERR_INVALID, "hier_linkage: pass exactly one of x and dense");
     HSEFR_REQUIRE(merge_a && merge_b && merge_h && merge_round, HSEFR_ERR_INVALID, "hier_linkage: null pointer (merge outputs)");
-    HSEFR_REQUIRE(!born == !year, HSEFR_ERR_INVALID, "hier_linkage: born and year come together");
-    HSEFR_REQUIRE(!(dense && born), HSEFR_ERR_INVALID, "hier_linkage: the age term belongs to the features path");
-    HSEFR_REQUIRE(dense || (d > 0 && d % 8 == 0), HSEFR_ERR_INVALID, "hier_linkage: d=%d must be a positive multiple of 8", d);
-    return launch_hier_linkage(x, n, d, born, year, dense, method, merge_a, merge_b, merge_h, merge_round, (hipStream_t)stream);
+    return launch_hier_linkage(src, method, merge_a, merge_b, merge_h, merge_round, (hipStream_t)stream);
 }
 
 int hsefr_dbscan(const float* x, int n, int d, const float* born, const float* year, const double* dense, double eps, int min_samples,
                  int* labels, unsigned char* core, hsefr_stream_t stream) {
-    HSEFR_REQUIRE(n >= 1, HSEFR_ERR_INVALID, "dbscan: n=%d", n);
-    HSEFR_REQUIRE((x != nullptr) != (dense != nullptr), HSEFR_ERR_INVALID, "dbscan: pass exactly one of x and dense");
+    const DistSource src = {x, n, d, born, year, dense};
+    if (const int rc = check_dist_source("dbscan", src)) return rc;
     HSEFR_REQUIRE(labels, HSEFR_ERR_INVALID, "dbscan: null pointer (labels)");
-    HSEFR_REQUIRE(!born == !year, HSEFR_ERR_INVALID, "dbscan: born and year come together");
-    HSEFR_REQUIRE(!(dense && born), HSEFR_ERR_INVALID, "dbscan: the age term belongs to the features path");
-    HSEFR_REQUIRE(dense || (d > 0 && d % 8 == 0), HSEFR_ERR_INVALID, "dbscan: d=%d must be a positive multiple of 8", d);
     HSEFR_REQUIRE(isfinite(eps) && eps > 0, HSEFR_ERR_INVALID, "dbscan: eps=%g must be finite and > 0", eps);
     HSEFR_REQUIRE(min_samples >= 1, HSEFR_ERR_INVALID, "dbscan: min_samples=%d must be >= 1", min_samples);
-    return launch_dbscan(x, n, d, born, year, dense, eps, min_samples, labels, core, (hipStream_t)stream);
-}
-
-static int rank_order_checks(const float* x, int n, int d, const float* born, const float* year, const double* dense, int* labels) {
-    HSEFR_REQUIRE(n >= 1, HSEFR_ERR_INVALID, "rank_order: n=%d", n);
-    HSEFR_REQUIRE((x != nullptr) != (dense != nullptr), HSEFR_ERR_INVALID, "rank_order: pass exactly one of x and dense");
-    HSEFR_REQUIRE(labels, HSEFR_ERR_INVALID, "rank_order: null pointer (labels)");
-    HSEFR_REQUIRE(!born == !year, HSEFR_ERR_INVALID, "rank_order: born and year come together");
-    HSEFR_REQUIRE(!(dense && born), HSEFR_ERR_INVALID, "rank_order: the age term belongs to the features path");
-    HSEFR_REQUIRE(dense || (d > 0 && d % 8 == 0), HSEFR_ERR_INVALID, "rank_order: d=%d must be a positive multiple of 8", d);
-    return HSEFR_OK;
+    return launch_dbscan(src, eps, min_samples, labels, core, (hipStream_t)stream);
 }
 
 int hsefr_rank_order_sweep(const float* x, int n, int d, const float* born, const float* year, const double* dense,
                            const double* thresholds, int pairs, int* labels, int* iterations, hsefr_stream_t stream) {
-    const int rc = rank_order_checks(x, n, d, born, year, dense, labels);
-    if (rc != HSEFR_OK) return rc;
+    const DistSource src = {x, n, d, born, year, dense};
+    if (const int rc = check_dist_source("rank_order", src)) return rc;
+    HSEFR_REQUIRE(labels, HSEFR_ERR_INVALID, "rank_order: null pointer (labels)");
     HSEFR_REQUIRE(pairs >= 1 && thresholds, HSEFR_ERR_INVALID, "rank_order: pairs=%d threshold pairs at %p", pairs, (const void*)thresholds);
     for (int t = 0; t < 2 * pairs; ++t)
         HSEFR_REQUIRE(isfinite(thresholds[t]) && thresholds[t] > 0, HSEFR_ERR_INVALID, "rank_order: %s_threshold=%g must be finite and > 0",
                       t % 2 ? "rank" : "norm", thresholds[t]);
-    return launch_rank_order(x, n, d, born, year, dense, thresholds, pairs, labels, iterations, (hipStream_t)stream);
+    return launch_rank_order(src, thresholds, pairs, labels, iterations, (hipStream_t)stream);
 }
 
 int hsefr_rank_order(const float* x, int n, int d, const float* born, const float* year, const double* dense, double norm_threshold,

@@ -2,14 +2,11 @@
 //
 // Replaces hac.linkage(squareform(D), method) of get_facial_clusters (facial_clustering.py:241-245) for the clustering study's
 // 'average' row (facial_clustering_test.py:513) and the 'complete' / 'weighted' rows of its commented list.  Unlike single linkage these
-// need the whole matrix: an fp64 n x n working copy W lives in the workspace, built from one of two sources:
-//   features  W[i,j] = w(i,j) of linkage.hip (the fp32 MFMA contraction, the same fragment row norms, the optional age term, clipped at
-//             0) widened to fp64; each 32 x 32 tile of the upper triangle is computed once and stored to both sides through LDS;
-//   dense     a caller's fp64 D [n,n], read as its upper triangle D[min(i,j), max(i,j)] (what squareform(D, checks=False) reads),
-//             copied to both sides; the caller's buffer is never written.
-// W is bitwise symmetric and its diagonal +inf.  All three methods are reducible -- d(k, i u j) >= min(d(k,i), d(k,j)) -- so every pair of
-// clusters that are each other's nearest neighbour may merge in the same round; under the total order (d, lower, higher) the globally
-// least pair is always such a pair, so every round makes progress.  nn[i] / nnd[i] hold the least (W[i,b], b) over the other alive slots.
+// need the whole matrix: an fp64 n x n working copy W lives in the workspace, built from either distance source by build_working_matrix
+// (hier_build.h; defined here, used by rank_order.hip too).  W is bitwise symmetric and its diagonal +inf.  All three methods are
+// reducible -- d(k, i u j) >= min(d(k,i), d(k,j)) -- so every pair of clusters that are each other's nearest neighbour may merge in the
+// same round; under the total order (d, lower, higher) the globally least pair is always such a pair, so every round makes progress.
+// nn[i] / nnd[i] hold the least (W[i,b], b) over the other alive slots.
 // A round:
 //   1. pair      every alive i with nn[nn[i]] == i marks its partner; of a pair the lower slot survives, appends the record
 //                (i, j, W[i,j], round) and counts one cluster down; the higher slot dies;
@@ -24,6 +21,7 @@
 // into early exits, and the host reads it once per batch (rounds are not bounded by log n: a chain needs up to n - 1).  No grid-wide
 // barriers, no persistent kernels.  Workspace: 8 n^2 + O(n) bytes, stream-ordered (hipMallocAsync), refused before any launch.
 #include "hier_build.h"
+#include "linkage_scan.h"
 
 namespace hsefr {
 
@@ -44,6 +42,67 @@ __device__ __forceinline__ double lw2(int method, double dx, double dy, int sx, 
     if (method == HSEFR_LINK_AVERAGE) return ((double)sx * dx + (double)sy * dy) / (double)(sx + sy);
     if (method == HSEFR_LINK_COMPLETE) return fmax(dx, dy);
     return 0.5 * (dx + dy);
+}
+
+// Writes a staged 32 x 32 tile s (rows R*32.., columns C*32.., C >= R) to W and its mirror.  On the diagonal tile the entry below the
+// diagonal is the one above it and the diagonal itself is +inf; rows/columns past n are not written.
+__device__ __forceinline__ void store_tile_sym(double (*s)[33], double* __restrict__ W, int n, int R, int C, int lane) {
+    const int c = lane & 31, h = lane >> 5;
+    for (int it = 0; it < 16; ++it) {
+        const int r = 2 * it + h;
+        const int gi = R * 32 + r, gj = C * 32 + c;
+        if (gi < n && gj < n) W[(size_t)gi * n + gj] = R != C ? s[r][c] : (c > r ? s[r][c] : (c == r ? (double)INFINITY : s[c][r]));
+        if (R != C) {
+            const int ti = C * 32 + r, tj = R * 32 + c;
+            if (ti < n && tj < n) W[(size_t)ti * n + tj] = s[c][r];
+        }
+    }
+}
+
+// The two build kernels take the grid ((T + 3) / 4, T) with T = ceil(n / 32) and 256 threads.
+// Features: one workgroup = row tile R x column tiles 4 g .. 4 g + 3 (one per wave), only tiles with C >= R; each is one feat_tile of
+// linkage_scan.h (rows on the A operand, columns on B; an inactive wave contracts nothing).
+__global__ __launch_bounds__(256) void hl_build_feat_kernel(const float* __restrict__ x, int n, int d, const float* __restrict__ born,
+                                                            const float* __restrict__ year, double* __restrict__ W) {
+    __shared__ double s_t[4][32][33];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int li = lane & 31, lh = lane >> 5;
+    const int T = (n + 31) / 32;
+    const int R = blockIdx.y, C = blockIdx.x * 4 + wave;
+    if (blockIdx.x * 4 + 3 < R) return;                        // the whole block is below the diagonal
+    const bool active = C >= R && C < T;                       // wave-uniform
+    const float* qp = x + (size_t)min(R * 32 + li, n - 1) * d + 4 * lh;
+    float qq = 0.f;
+    bool qq_done = false;
+    float v[16];
+    link::feat_tile(qp, x, d, min(C * 32 + li, n - 1), born, year, lh, qq, qq_done,
+                    [&](int r, float& b, float& y) {
+                        const int row = min(R * 32 + link::tile_row(r, lh), n - 1);
+                        b = born[row];
+                        y = year[row];
+                    }, v, active);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s_t[wave][link::tile_row(r, lh)][li] = (double)v[r];
+    __syncthreads();
+    if (active) store_tile_sym(s_t[wave], W, n, R, C, lane);
+}
+
+// Dense: one wave = one 32 x 32 tile (R, C >= R) of the caller's matrix, read by rows into LDS and stored to both sides.
+__global__ __launch_bounds__(256) void hl_build_dense_kernel(const double* __restrict__ D, int n, double* __restrict__ W) {
+    __shared__ double s_t[4][32][33];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int T = (n + 31) / 32;
+    const int R = blockIdx.y, C = blockIdx.x * 4 + wave;
+    if (blockIdx.x * 4 + 3 < R) return;
+    const bool active = C >= R && C < T;
+    const int c = lane & 31, h = lane >> 5;
+    for (int it = 0; active && it < 16; ++it) {
+        const int r = 2 * it + h;
+        const int gi = R * 32 + r, gj = C * 32 + c;
+        s_t[wave][r][c] = (gi < n && gj < n) ? D[(size_t)gi * n + gj] : 0.0;
+    }
+    __syncthreads();
+    if (active) store_tile_sym(s_t[wave], W, n, R, C, lane);
 }
 
 __global__ __launch_bounds__(256) void hl_init_kernel(int* __restrict__ alive, int* __restrict__ partner, int* __restrict__ size,
@@ -207,8 +266,17 @@ __global__ __launch_bounds__(256) void hl_finalize_kernel(int n, const int* __re
 
 }  // namespace
 
-int launch_hier_linkage(const float* x, int n, int d, const float* born, const float* year, const double* dense, int method, int* merge_a,
-                        int* merge_b, double* merge_h, int* merge_round, hipStream_t s) {
+void build_working_matrix(const DistSource& src, double* W, hipStream_t s) {
+    const int T = (src.n + 31) / 32;
+    const dim3 gt((T + 3) / 4, T), blk(256);
+    if (src.dense)
+        HSEFR_LAUNCH(hl_build_dense_kernel, gt, blk, 0, s, src.dense, src.n, W);
+    else
+        HSEFR_LAUNCH(hl_build_feat_kernel, gt, blk, 0, s, src.x, src.n, src.d, src.born, src.year, W);
+}
+
+int launch_hier_linkage(const DistSource& src, int method, int* merge_a, int* merge_b, double* merge_h, int* merge_round, hipStream_t s) {
+    const int n = src.n;
     if (n == 1) return HSEFR_OK;
     // W first (n^2 doubles), then nnd (n doubles), then int arrays: nn, alive, partner, size, flag, list, cnt
     const size_t bytes = (size_t)n * n * 8 + (size_t)n * 8 + (size_t)n * 6 * 4 + C_N * 4;
@@ -229,13 +297,8 @@ int launch_hier_linkage(const float* x, int n, int d, const float* born, const f
     int* list = flag + n;
     int* cnt = list + n;
     const dim3 blk(256), g1((n + 255) / 256);
-    const int T = (n + 31) / 32;
-    const dim3 gt((T + 3) / 4, T);
     HSEFR_LAUNCH(hl_init_kernel, g1, blk, 0, s, alive, partner, size, flag, list, cnt, n);
-    if (dense)
-        HSEFR_LAUNCH(hl_build_dense_kernel, gt, blk, 0, s, dense, n, W);
-    else
-        HSEFR_LAUNCH(hl_build_feat_kernel, gt, blk, 0, s, x, n, d, born, year, W);
+    build_working_matrix(src, W, s);
     const dim3 gs(n < SCAN_BLOCKS ? n : SCAN_BLOCKS), gu((n + 255) / 256, UPD_Y);
     HSEFR_LAUNCH(hl_rescan_kernel, gs, blk, 0, s, W, n, alive, list, cnt, nn, nnd);
     int rc = launch_status("hier_linkage");

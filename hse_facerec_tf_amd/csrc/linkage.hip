@@ -264,8 +264,9 @@ int ceil_log2(long long v) {
 // u64 arrays first: row_key, cmin_w, cmin_e; then int arrays: label, par, row_j, cnt[4]
 size_t boruvka_bytes(int n) { return (size_t)n * 3 * 8 + (size_t)n * 3 * 4 + 16; }
 
-int* boruvka_rounds(const float* x, int n, int d, const float* born, const float* year, const double* dense, const unsigned char* core,
-                    float eps_f, double eps, char* ws, int* edge_a, int* edge_b, double* edge_h, hipStream_t s) {
+int* boruvka_rounds(const DistSource& src, const unsigned char* core, float eps_f, double eps, char* ws, int* edge_a, int* edge_b,
+                    double* edge_h, hipStream_t s) {
+    const int n = src.n;
     u64* row_key = (u64*)ws;
     u64* cmin_w = row_key + n;
     u64* cmin_e = cmin_w + n;
@@ -278,16 +279,16 @@ int* boruvka_rounds(const float* x, int n, int d, const float* born, const float
     const int rounds = ceil_log2(n);
     for (int k = 0; k < rounds; ++k) {
         HSEFR_LAUNCH(sl_reset_kernel, g1, blk, 0, s, label, par, cmin_w, cmin_e, cnt, n);
-        if (dense && core)
-            HSEFR_LAUNCH(sl_row_min_dense_kernel<true>, dim3((n + 63) / 64), blk, 0, s, dense, n, label, cnt, core, eps, row_key, row_j);
-        else if (dense)
-            HSEFR_LAUNCH(sl_row_min_dense_kernel<false>, dim3((n + 63) / 64), blk, 0, s, dense, n, label, cnt, core, eps, row_key, row_j);
+        if (src.dense && core)
+            HSEFR_LAUNCH(sl_row_min_dense_kernel<true>, dim3((n + 63) / 64), blk, 0, s, src.dense, n, label, cnt, core, eps, row_key, row_j);
+        else if (src.dense)
+            HSEFR_LAUNCH(sl_row_min_dense_kernel<false>, dim3((n + 63) / 64), blk, 0, s, src.dense, n, label, cnt, core, eps, row_key, row_j);
         else if (core)
-            HSEFR_LAUNCH(sl_row_min_feat_kernel<true>, dim3((n + 31) / 32), blk, 0, s, x, n, d, born, year, label, cnt, core, eps_f, row_key,
-                         row_j);
+            HSEFR_LAUNCH(sl_row_min_feat_kernel<true>, dim3((n + 31) / 32), blk, 0, s, src.x, n, src.d, src.born, src.year, label, cnt, core,
+                         eps_f, row_key, row_j);
         else
-            HSEFR_LAUNCH(sl_row_min_feat_kernel<false>, dim3((n + 31) / 32), blk, 0, s, x, n, d, born, year, label, cnt, core, eps_f, row_key,
-                         row_j);
+            HSEFR_LAUNCH(sl_row_min_feat_kernel<false>, dim3((n + 31) / 32), blk, 0, s, src.x, n, src.d, src.born, src.year, label, cnt, core,
+                         eps_f, row_key, row_j);
         HSEFR_LAUNCH(sl_comp_min1_kernel, g1, blk, 0, s, label, row_key, cmin_w, cnt, n);
         HSEFR_LAUNCH(sl_comp_min2_kernel, g1, blk, 0, s, label, row_key, row_j, cmin_w, cmin_e, cnt, n);
         HSEFR_LAUNCH(sl_hook_kernel, g1, blk, 0, s, label, par, cmin_w, cmin_e, cnt, edge_a, edge_b, edge_h, n);
@@ -301,8 +302,8 @@ int* boruvka_rounds(const float* x, int n, int d, const float* born, const float
     return label;
 }
 
-int launch_single_linkage(const float* x, int n, int d, const float* born, const float* year, const double* dense, int* edge_a, int* edge_b,
-                          double* edge_h, hipStream_t s) {
+int launch_single_linkage(const DistSource& src, int* edge_a, int* edge_b, double* edge_h, hipStream_t s) {
+    const int n = src.n;
     if (n == 1) return HSEFR_OK;
     const size_t bytes = boruvka_bytes(n);
     char* ws = nullptr;
@@ -311,7 +312,7 @@ int launch_single_linkage(const float* x, int n, int d, const float* born, const
         set_error("single_linkage: no stream-ordered workspace (%zu bytes) for n=%d", bytes, n);
         return HSEFR_ERR_NOMEM;
     }
-    boruvka_rounds(x, n, d, born, year, dense, nullptr, 0.f, 0.0, ws, edge_a, edge_b, edge_h, s);
+    boruvka_rounds(src, nullptr, 0.f, 0.0, ws, edge_a, edge_b, edge_h, s);
     const int rc = launch_status("single_linkage");
     (void)hipFreeAsync(ws, s);
     return rc;

@@ -1,40 +1,75 @@
-// Row scans of the distance graph shared by linkage.hip (single linkage) and dbscan.hip.  Two sources:
+// Row scans of the distance graph shared by linkage.hip (single linkage) and dbscan.hip, and the one definition of the clustering
+// distance w(i,j) that every clustering kernel reads.  Two sources (a DistSource of common.h):
 //   features  w(i,j) = max(sqrt(max(|x_i|^2 + |x_j|^2 - 2 x_i.x_j, 0)) + 0.1 (born_j - born_i)^2 / (2 max(year_i, year_j) - born_i - born_j), 0)
-//             (the age term only with born / year), the contraction on the fp32 MFMA as in nn1_kernel -- every w(i,j) is computed by the
-//             same commutative expression from the same row norms and the same FMA chain whichever side of a tile i falls on, so the graph
-//             is bitwise symmetric;
+//             (the age term only with born / year), the contraction on the fp32 MFMA (mfma_dot.h, as in nn1_kernel) -- every w(i,j) is
+//             computed by the same commutative expression from the same row norms and the same FMA chain whichever side of a tile i falls
+//             on, so the graph is bitwise symmetric.  feat_tile below is the only place that expression is written: the row scans here
+//             and the working matrix of hier_build.h (average / complete / weighted linkage, rank-order) both call it, so the distances
+//             are the same bits in every clustering method (tests/test_hier_linkage_gpu.py compares the two families' global minimum);
 //   dense     a caller's fp64 D [n,n], read as its upper triangle D[min(i,j), max(i,j)] (what squareform(D, checks=False) reads).
-// Each kernel built on them keeps its own selection and reduction; the distances are these, bit for bit, in every one.
+// Each kernel built on them keeps its own selection and reduction.
 #pragma once
 #include "common.h"
+#include "mfma_dot.h"
 
 namespace hsefr {
 namespace link {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned long long u64;
 
 template <typename T>
 __device__ __forceinline__ bool better(T v, int i, T bv, int bi) { return v < bv || (v == bv && i < bi); }
 
-// Features: one workgroup = 32 rows x all n columns, its 4 waves take column tiles of 32 round-robin (nn1_kernel's layout).  Lane
-// (li, lh) holds the 16 accumulator rows row(r) of the 32 x 32 tile and column li.  Row norms come from the fragments that feed the
+// the tile row of accumulator r in half-wave lh
+__device__ __forceinline__ int tile_row(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
+
+// One 32 x 32 feature tile: v[r] = w(row tile_row(r, lh) of the tile's 32 rows, point grow), lane (li, lh) holding column li = its own
+// grow.  qp / x + grow d + 4 lh are mfma_dot_32x32's operands (rows on A, columns on B).  Row norms come from the fragments that feed the
 // MFMAs: lane (li, lh) sums the same elements in the same order for a row on either operand, and the halves meet in a commutative add,
-// so |x_i|^2 is one value whichever side i is on.
+// so |x_i|^2 is one value whichever side i is on.  qq (lane t holds |x|^2 of tile row t) is taken from this tile unless qq_done says
+// the caller already holds it: the rows are the same for every tile of a row scan.  row_age(r, born, year) gives the ages of tile row r
+// and is called only with an age term (born != nullptr).
+template <typename RowAge>
+__device__ __forceinline__ void feat_tile(const float* qp, const float* x, int d, int grow, const float* born, const float* year, int lh,
+                                          float& qq, bool& qq_done, RowAge row_age, float (&v)[16], bool on = true) {
+    const bool age = born != nullptr;
+    const float gb = age ? born[grow] : 0.f, gy = age ? year[grow] : 0.f;
+    f32x16 acc;
+    float gg, qs;
+    mfma_dot_32x32(qp, x + (size_t)grow * d + 4 * lh, d, acc, qs, gg, on);
+    gg += __shfl_xor(gg, 32);
+    if (!qq_done) { qq = qs + __shfl_xor(qs, 32); qq_done = true; }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const float s = __shfl(qq, tile_row(r, lh)) + gg;
+        float w = sqrtf(fmaxf(fmaf(-2.f, acc[r], s), 0.f));
+        if (age) {
+            float br, yr;
+            row_age(r, br, yr);
+            const float t = gb - br;
+            const float den = 2.f * fmaxf(yr, gy) - (br + gb);
+            w = fmaxf(w + 0.1f * (t * t) / den, 0.f);
+        }
+        v[r] = w;
+    }
+}
+
+// Features: one workgroup = 32 rows x all n columns, its 4 waves take column tiles of 32 round-robin (nn1_kernel's layout).  Lane
+// (li, lh) holds the 16 accumulator rows row(r) of the 32 x 32 tile and column li.  The rows' ages are read once, their norms on the
+// wave's first tile.
 struct FeatScan {
     const float* x;
     const float* born;
     const float* year;
     const float* qp;
     int n, d, q0, lh;
-    bool age;
     float born_r[16], year_r[16];
     float qq = 0.f;          // |x_row|^2 (lane rr holds row q0 + rr), from the wave's first tile
     bool qq_done = false;
 
     __device__ __forceinline__ FeatScan(const float* x_, int n_, int d_, const float* born_, const float* year_)
-        : x(x_), born(born_), year(year_), n(n_), d(d_), q0(blockIdx.x * 32), lh((threadIdx.x & 63) >> 5), age(born_ != nullptr) {
+        : x(x_), born(born_), year(year_), n(n_), d(d_), q0(blockIdx.x * 32), lh((threadIdx.x & 63) >> 5) {
+        const bool age = born != nullptr;
         qp = x + (size_t)min(q0 + (int)(threadIdx.x & 31), n - 1) * d + 4 * lh;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -44,40 +79,12 @@ struct FeatScan {
         }
     }
     // the tile row of accumulator r, and its point (clamped: rows past n repeat the last one and are never stored)
-    __device__ __forceinline__ int rr(int r) const { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
+    __device__ __forceinline__ int rr(int r) const { return tile_row(r, lh); }
     __device__ __forceinline__ int row(int r) const { return min(q0 + rr(r), n - 1); }
 
     // v[r] = w(row(r), grow)
     __device__ __forceinline__ void tile(int grow, float (&v)[16]) {
-        const float* gp = x + (size_t)grow * d + 4 * lh;
-        const float gb = age ? born[grow] : 0.f, gy = age ? year[grow] : 0.f;
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        float gg = 0.f, qs = 0.f;
-        for (int k = 0; k < d; k += 8) {
-            const f32x4 a = *(const f32x4*)(qp + k);
-            const f32x4 b = *(const f32x4*)(gp + k);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j], b[j], acc, 0, 0, 0);
-                gg = fmaf(b[j], b[j], gg);
-                qs = fmaf(a[j], a[j], qs);
-            }
-        }
-        gg += __shfl_xor(gg, 32);
-        if (!qq_done) { qq = qs + __shfl_xor(qs, 32); qq_done = true; }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float s = __shfl(qq, rr(r)) + gg;
-            float w = sqrtf(fmaxf(fmaf(-2.f, acc[r], s), 0.f));
-            if (age) {
-                const float t = gb - born_r[r];
-                const float den = 2.f * fmaxf(year_r[r], gy) - (born_r[r] + gb);
-                w = fmaxf(w + 0.1f * (t * t) / den, 0.f);
-            }
-            v[r] = w;
-        }
+        feat_tile(qp, x, d, grow, born, year, lh, qq, qq_done, [this](int r, float& b, float& y) { b = born_r[r]; y = year_r[r]; }, v);
     }
 };
 
@@ -109,7 +116,7 @@ __device__ __forceinline__ double dense_at(const double (*s_t)[65], int r0, int 
 // edge is one only if both ends are core and w <= eps (features: compared as w <= eps_f, the largest float <= eps), and edge_* may be
 // null.  ws holds boruvka_bytes(n); nothing is synchronised.
 size_t boruvka_bytes(int n);
-int* boruvka_rounds(const float* x, int n, int d, const float* born, const float* year, const double* dense, const unsigned char* core,
-                    float eps_f, double eps, char* ws, int* edge_a, int* edge_b, double* edge_h, hipStream_t s);
+int* boruvka_rounds(const DistSource& src, const unsigned char* core, float eps_f, double eps, char* ws, int* edge_a, int* edge_b,
+                    double* edge_h, hipStream_t s);
 
 }  // namespace hsefr

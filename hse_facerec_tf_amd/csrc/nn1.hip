@@ -13,13 +13,11 @@
 #include <atomic>
 
 #include "common.h"
+#include "mfma_dot.h"
 
 namespace hsefr {
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ float wave_sum64(float v) {
 #pragma unroll
@@ -66,19 +64,8 @@ __global__ __launch_bounds__(256) void nn1_kernel(const float* __restrict__ q, c
         const int grow = min(gcol, ng - 1);
         const float* gp = g + (size_t)grow * d + 4 * lh;
         f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        float gg = 0.f, qs = 0.f;
-        for (int k = 0; k < d; k += 8) {
-            const f32x4 a = *(const f32x4*)(qp + k);
-            const f32x4 b = *(const f32x4*)(gp + k);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j], b[j], acc, 0, 0, 0);
-                gg = fmaf(b[j], b[j], gg);
-                qs = fmaf(a[j], a[j], qs);
-            }
-        }
+        float gg, qs;
+        mfma_dot_32x32(qp, gp, d, acc, qs, gg);
         gg += __shfl_xor(gg, 32);
         if (!qq_done) { qq = qs + __shfl_xor(qs, 32); qq_done = true; }
 #pragma unroll
@@ -131,19 +118,8 @@ __global__ __launch_bounds__(256) void pairwise_dist_kernel(const float* __restr
     const float* xp = x + (size_t)min(i0 + li, n - 1) * d + 4 * lh;
     const float* yp = y + (size_t)min(j0 + li, m - 1) * d + 4 * lh;
     f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    float xx = 0.f, yy = 0.f;
-    for (int k = 0; k < d; k += 8) {
-        const f32x4 a = *(const f32x4*)(xp + k);
-        const f32x4 b = *(const f32x4*)(yp + k);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], b[e], acc, 0, 0, 0);
-            xx = fmaf(a[e], a[e], xx);
-            yy = fmaf(b[e], b[e], yy);
-        }
-    }
+    float xx, yy;
+    mfma_dot_32x32(xp, yp, d, acc, xx, yy);
     xx += __shfl_xor(xx, 32);
     yy += __shfl_xor(yy, 32);
     const int col = j0 + li;

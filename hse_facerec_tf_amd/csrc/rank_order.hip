@@ -336,8 +336,8 @@ size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 }  // namespace
 
-int launch_rank_order(const float* x, int n, int d, const float* born, const float* year, const double* dense, const double* thresholds,
-                      int pairs, int* labels, int* iterations, hipStream_t s) {
+int launch_rank_order(const DistSource& src, const double* thresholds, int pairs, int* labels, int* iterations, hipStream_t s) {
+    const int n = src.n;
     const bool keep = pairs > 1;                               // a sequence keeps the matrix and the first lists
     const size_t nn = (size_t)n * n * 8, lv = up16((size_t)n * NB * 8), li = up16((size_t)n * NB * 4), nd = up16((size_t)n * 8),
                  ni = up16((size_t)n * 4 + 16);
@@ -372,15 +372,11 @@ int launch_rank_order(const float* x, int n, int d, const float* born, const flo
     unsigned char* alive = (unsigned char*)take(up16((size_t)n));
 
     const dim3 blk(256), g1((n + 255) / 256), gw((n + 3) / 4);
-    const int Tt = (n + 31) / 32;
-    const dim3 gt((Tt + 3) / 4, Tt), gr((n + 255) / 256, n < ROW_Y ? n : ROW_Y), gc(n);
+    const dim3 gr((n + 255) / 256, n < ROW_Y ? n : ROW_Y), gc(n);
     const int kn = n < KN ? n : KN;                            // min(KN, min(NB, n))
 
     HSEFR_LAUNCH(ro_init_kernel, g1, blk, 0, s, alive, fsize, lab, parent, n);
-    if (dense)
-        HSEFR_LAUNCH(hl_build_dense_kernel, gt, blk, 0, s, dense, n, W0);
-    else
-        HSEFR_LAUNCH(hl_build_feat_kernel, gt, blk, 0, s, x, n, d, born, year, W0);
+    build_working_matrix(src, W0, s);
     HSEFR_LAUNCH(ro_topk_kernel<true>, gw, blk, 0, s, W0, n, alive, n < NB ? n : NB, kn, lidx0, lval0, T0);
     int rc = launch_status("rank_order");
     hipError_t e = hipSuccess;

@@ -531,17 +531,15 @@ def pairwise_distances(x, y=None):
     return out
 
 
-@_device_guarded
-def single_linkage_edges(x=None, dense=None, born=None, year=None):
-    """The minimum spanning tree behind single linkage (hsefr_single_linkage) -> (edge_a int32, edge_b int32, edge_h float64), n - 1 CUDA
-    tensors each, edge_a < edge_b, round by round.  Exactly one source: x [n,d] float32 features (zero columns pad d to a multiple of 8,
-    which changes no distance) with optional born / year float32 [n] (the age term of process_photos.py:46-51), or dense [n,n] float64
-    distances read as their upper triangle.  Asynchronous on the current stream."""
+def _dist_source(who, x, dense, born, year):
+    """The distance source of the clustering entry points, checked for ``who``: exactly one of x [n,d] float32 (zero columns pad d to a
+    multiple of 8, which changes no distance; born / year float32 [n] optional) and dense [n,n] float64
+    -> (the padded x, which must outlive the call; n; the device; the C call's leading arguments x, n, d, born, year, dense)."""
     torch = _lib.require_gpu()
     if (x is None) == (dense is None):
-        raise ValueError("single_linkage_edges: pass exactly one of x and dense")
+        raise ValueError("%s: pass exactly one of x and dense" % who)
     if (born is None) != (year is None):
-        raise ValueError("single_linkage_edges: born and year come together")
+        raise ValueError("%s: born and year come together" % who)
     d = 0
     if x is not None:
         _f32c(x, "x")
@@ -556,21 +554,31 @@ def single_linkage_edges(x=None, dense=None, born=None, year=None):
                 raise ValueError("%s has %d elements for %d rows" % (name, v.numel(), n))
     else:
         if born is not None:
-            raise ValueError("single_linkage_edges: the age term belongs to the features path")
+            raise ValueError("%s: the age term belongs to the features path" % who)
         if not (dense.is_cuda and dense.dtype == torch.float64 and dense.is_contiguous() and dense.dim() == 2
                 and dense.shape[0] == dense.shape[1]):
             raise ValueError("dense must be a contiguous square float64 CUDA tensor")
         n = dense.shape[0]
     if n < 1:
-        raise ValueError("single_linkage_edges: no points")
-    dev = (x if x is not None else dense).device
+        raise ValueError("%s: no points" % who)
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    return x, n, (x if x is not None else dense).device, (ptr(x), n, d, ptr(born), ptr(year), ptr(dense))
+
+
+@_device_guarded
+def single_linkage_edges(x=None, dense=None, born=None, year=None):
+    """The minimum spanning tree behind single linkage (hsefr_single_linkage) -> (edge_a int32, edge_b int32, edge_h float64), n - 1 CUDA
+    tensors each, edge_a < edge_b, round by round.  Exactly one source: x [n,d] float32 features (zero columns pad d to a multiple of 8,
+    which changes no distance) with optional born / year float32 [n] (the age term of process_photos.py:46-51), or dense [n,n] float64
+    distances read as their upper triangle.  Asynchronous on the current stream."""
+    torch = _lib.require_gpu()
+    x, n, dev, src = _dist_source("single_linkage_edges", x, dense, born, year)
     m = max(n - 1, 1)
     ea = torch.full((m,), -1, dtype=torch.int32, device=dev)
     eb = torch.full((m,), -1, dtype=torch.int32, device=dev)
     eh = torch.empty((m,), dtype=torch.float64, device=dev)
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    _lib.check(_lib.lib().hsefr_single_linkage(ptr(x), n, d, ptr(born), ptr(year), ptr(dense), ea.data_ptr(), eb.data_ptr(),
-                                               eh.data_ptr(), _lib.current_stream_ptr()), "hsefr_single_linkage")
+    _lib.check(_lib.lib().hsefr_single_linkage(*src, ea.data_ptr(), eb.data_ptr(), eh.data_ptr(), _lib.current_stream_ptr()),
+               "hsefr_single_linkage")
     return ea[:n - 1], eb[:n - 1], eh[:n - 1]
 
 
@@ -587,41 +595,14 @@ def hier_linkage_merges(x=None, dense=None, born=None, year=None, method="averag
     torch = _lib.require_gpu()
     if method not in LINK_METHODS:
         raise ValueError("hier_linkage_merges: method %r is not one of %s" % (method, ", ".join(sorted(LINK_METHODS))))
-    if (x is None) == (dense is None):
-        raise ValueError("hier_linkage_merges: pass exactly one of x and dense")
-    if (born is None) != (year is None):
-        raise ValueError("hier_linkage_merges: born and year come together")
-    d = 0
-    if x is not None:
-        _f32c(x, "x")
-        if x.dim() != 2:
-            raise ValueError("x must be [n, d]")
-        n, d = x.shape
-        if d % 8:
-            x = torch.nn.functional.pad(x, (0, 8 - d % 8)).contiguous()
-            d = x.shape[1]
-        for v, name in ((born, "born"), (year, "year")):
-            if v is not None and _f32c(v, name).numel() != n:
-                raise ValueError("%s has %d elements for %d rows" % (name, v.numel(), n))
-    else:
-        if born is not None:
-            raise ValueError("hier_linkage_merges: the age term belongs to the features path")
-        if not (dense.is_cuda and dense.dtype == torch.float64 and dense.is_contiguous() and dense.dim() == 2
-                and dense.shape[0] == dense.shape[1]):
-            raise ValueError("dense must be a contiguous square float64 CUDA tensor")
-        n = dense.shape[0]
-    if n < 1:
-        raise ValueError("hier_linkage_merges: no points")
-    dev = (x if x is not None else dense).device
+    x, n, dev, src = _dist_source("hier_linkage_merges", x, dense, born, year)
     m = max(n - 1, 1)
     ma = torch.full((m,), -1, dtype=torch.int32, device=dev)
     mb = torch.full((m,), -1, dtype=torch.int32, device=dev)
     mh = torch.empty((m,), dtype=torch.float64, device=dev)
     mr = torch.full((m,), -1, dtype=torch.int32, device=dev)
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    _lib.check(_lib.lib().hsefr_hier_linkage(ptr(x), n, d, ptr(born), ptr(year), ptr(dense), LINK_METHODS[method], ma.data_ptr(),
-                                             mb.data_ptr(), mh.data_ptr(), mr.data_ptr(), _lib.current_stream_ptr()),
-               "hsefr_hier_linkage")
+    _lib.check(_lib.lib().hsefr_hier_linkage(*src, LINK_METHODS[method], ma.data_ptr(), mb.data_ptr(), mh.data_ptr(), mr.data_ptr(),
+                                             _lib.current_stream_ptr()), "hsefr_hier_linkage")
     return ma[:n - 1], mb[:n - 1], mh[:n - 1], mr[:n - 1]
 
 
@@ -632,38 +613,12 @@ def dbscan_labels(x=None, dense=None, born=None, year=None, eps=0.5, min_samples
     pad d to a multiple of 8) with optional born / year float32 [n], or dense [n,n] float64 distances read as their upper triangle.
     O(n) device workspace, no N x N matrix on the features path.  Asynchronous on the current stream."""
     torch = _lib.require_gpu()
-    if (x is None) == (dense is None):
-        raise ValueError("dbscan_labels: pass exactly one of x and dense")
-    if (born is None) != (year is None):
-        raise ValueError("dbscan_labels: born and year come together")
-    d = 0
-    if x is not None:
-        _f32c(x, "x")
-        if x.dim() != 2:
-            raise ValueError("x must be [n, d]")
-        n, d = x.shape
-        if d % 8:
-            x = torch.nn.functional.pad(x, (0, 8 - d % 8)).contiguous()
-            d = x.shape[1]
-        for v, name in ((born, "born"), (year, "year")):
-            if v is not None and _f32c(v, name).numel() != n:
-                raise ValueError("%s has %d elements for %d rows" % (name, v.numel(), n))
-    else:
-        if born is not None:
-            raise ValueError("dbscan_labels: the age term belongs to the features path")
-        if not (dense.is_cuda and dense.dtype == torch.float64 and dense.is_contiguous() and dense.dim() == 2
-                and dense.shape[0] == dense.shape[1]):
-            raise ValueError("dense must be a contiguous square float64 CUDA tensor")
-        n = dense.shape[0]
-    if n < 1:
-        raise ValueError("dbscan_labels: no points")
-    dev = (x if x is not None else dense).device
+    x, n, dev, src = _dist_source("dbscan_labels", x, dense, born, year)
     labels = torch.empty((n,), dtype=torch.int32, device=dev)
     core = torch.empty((n,), dtype=torch.uint8, device=dev)
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     # min_samples above n + 1 makes no point core, as n + 1 does (the C argument is an int)
-    _lib.check(_lib.lib().hsefr_dbscan(ptr(x), n, d, ptr(born), ptr(year), ptr(dense), float(eps), int(min(min_samples, n + 1)),
-                                       labels.data_ptr(), core.data_ptr(), _lib.current_stream_ptr()), "hsefr_dbscan")
+    _lib.check(_lib.lib().hsefr_dbscan(*src, float(eps), int(min(min_samples, n + 1)), labels.data_ptr(), core.data_ptr(),
+                                       _lib.current_stream_ptr()), "hsefr_dbscan")
     return labels, core
 
 
@@ -676,42 +631,16 @@ def rank_order_labels(x=None, dense=None, born=None, year=None, norm_threshold=0
     the working matrix and the face lists are built once for the whole sequence.  Needs 8 n^2 bytes of device workspace (16 n^2 for
     a sequence of more than one pair); returns with the current stream synchronised (the host reads the cluster count every iteration)."""
     torch = _lib.require_gpu()
-    if (x is None) == (dense is None):
-        raise ValueError("rank_order_labels: pass exactly one of x and dense")
-    if (born is None) != (year is None):
-        raise ValueError("rank_order_labels: born and year come together")
+    x, n, dev, src = _dist_source("rank_order_labels", x, dense, born, year)
     sweep = thresholds is not None
     pairs = [(float(a), float(b)) for a, b in thresholds] if sweep else [(float(norm_threshold), float(rank_threshold))]
     if not pairs:
         raise ValueError("rank_order_labels: no threshold pairs")
-    d = 0
-    if x is not None:
-        _f32c(x, "x")
-        if x.dim() != 2:
-            raise ValueError("x must be [n, d]")
-        n, d = x.shape
-        if d % 8:
-            x = torch.nn.functional.pad(x, (0, 8 - d % 8)).contiguous()
-            d = x.shape[1]
-        for v, name in ((born, "born"), (year, "year")):
-            if v is not None and _f32c(v, name).numel() != n:
-                raise ValueError("%s has %d elements for %d rows" % (name, v.numel(), n))
-    else:
-        if born is not None:
-            raise ValueError("rank_order_labels: the age term belongs to the features path")
-        if not (dense.is_cuda and dense.dtype == torch.float64 and dense.is_contiguous() and dense.dim() == 2
-                and dense.shape[0] == dense.shape[1]):
-            raise ValueError("dense must be a contiguous square float64 CUDA tensor")
-        n = dense.shape[0]
-    if n < 1:
-        raise ValueError("rank_order_labels: no points")
-    dev = (x if x is not None else dense).device
     labels = torch.empty((len(pairs), n), dtype=torch.int32, device=dev)
     thr = (ctypes.c_double * (2 * len(pairs)))(*[v for pair in pairs for v in pair])
     iters = (ctypes.c_int * len(pairs))()
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    _lib.check(_lib.lib().hsefr_rank_order_sweep(ptr(x), n, d, ptr(born), ptr(year), ptr(dense), thr, len(pairs), labels.data_ptr(), iters,
-                                                 _lib.current_stream_ptr()), "hsefr_rank_order")
+    _lib.check(_lib.lib().hsefr_rank_order_sweep(*src, thr, len(pairs), labels.data_ptr(), iters, _lib.current_stream_ptr()),
+               "hsefr_rank_order")
     return (labels, list(iters)) if sweep else (labels[0], int(iters[0]))
 
 

@@ -131,6 +131,21 @@ def test_features_path_matches_scipy_on_fp64_distances(method, d, age):
     assert clustering.linkage(X[:1], method).shape == (0, 4)
 
 
+@pytest.mark.parametrize("d,age", [(128, False), (128, True), (12, False), (12, True), (1024, True)])
+def test_working_matrix_and_row_scan_hold_the_same_distances(d, age):
+    """The one observable link between the two families of feature distances: the lowest merge of average, complete and weighted linkage
+    (the least entry of the fp64 working matrix) and the lowest merge of single linkage (the least w(i,j) a row scan sees) are both the
+    global minimum of w(i,j), so they are the same fp32 value widened -- bit for bit, whichever kernel computed it."""
+    from hse_facerec_tf_amd import clustering
+    n = 301
+    X = features(n, d, 70 + d, classes=15)
+    born, photo = ages(n, 7 + d) if age else (None, None)
+    lowest = clustering.linkage_single(X, born, photo)[:, 2].min()
+    assert lowest > 0 and lowest == np.float64(np.float32(lowest))
+    for method in METHODS:
+        assert clustering.linkage(X, method, born, photo)[:, 2].min() == lowest, method
+
+
 def reference_get_facial_clusters(dist_matrix, distanceThreshold, all_indices=None, method="average"):
     """The scipy branch of facial_clustering.get_facial_clusters (:243-261, 284) with clusteringMethod = method, restated with scipy."""
     labels = hac.fcluster(hac.linkage(squareform(dist_matrix, checks=False), method=method), distanceThreshold, "distance")
