@@ -5,8 +5,8 @@
 //
 // Parity contract: the SAME numbers as the host restatement in mtcnn.py (float64 box arithmetic, float32 scores / regressions /
 // landmarks, products and sums rounded separately as NumPy does: every a + b * c below is written with __dmul_rn / __dadd_rn so
-// that hipcc cannot contract it), the same greedy order: descending score, ties by ascending candidate index (for P-Net
-// candidates: the row-major index of the cell in the [W', H'] map, which is the order np.nonzero yields).
+// that hipcc cannot contract it), the same greedy order: descending score, ties by DESCENDING candidate index (see make_key; for
+// P-Net candidates the index is the row-major index of the cell in the [W', H'] map, which is the order np.nonzero yields).
 //
 // One workgroup of 1024 threads per call (a frame has a few hundred candidates per level): candidates are appended unordered
 // with an LDS atomic, a bitonic sort of 64-bit keys (score | index) makes the order deterministic, the greedy pass walks the
@@ -22,7 +22,7 @@ constexpr int CAP = 2048;          // candidates per list (per pyramid level; al
 constexpr int NT = 1024;
 
 struct PostLds {
-    unsigned long long key[CAP];   // (0xFFFFFFFF - score bits) << 32 | index: ascending = score descending, index ascending
+    unsigned long long key[CAP];   // (0xFFFFFFFF - score bits) << 32 | (0xFFFFFFFF - index): ascending = score descending, index descending
     double x1[CAP], y1[CAP], x2[CAP], y2[CAP], area[CAP];   // in SORTED order
     unsigned char alive[CAP], kept[CAP];
     int n, nkeep;

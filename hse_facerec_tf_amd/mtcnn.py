@@ -253,6 +253,82 @@ def _crop_windows(boxes: np.ndarray, img_w: int, img_h: int):
     return bw, bh, x1, y1, x2, y2, tx1, ty1, tx2, ty2
 
 
+# ---- the four stage bodies of the cascade on the host (facial_analysis.py:505-603) -----------------------------------------------
+# Pure functions of the nets' outputs in the layout the nets give them (a P-Net map is [W', H'], an R-/O-Net output [n, channels]):
+# the detector's host path and its overflow fallback run these, csrc/mtcnn_post.hip computes the same lists on the device.
+def _crop_table(boxes: np.ndarray, img_w: int, img_h: int) -> np.ndarray:
+    """int32 [m, 8] = {x1, y1, x2, y2, tx1, ty1, bw, bh}, the rows hsefr_mtcnn_crops takes."""
+    if boxes.shape[0] == 0:
+        return np.empty((0, 8), np.int32)
+    bw, bh, x1, y1, x2, y2, tx1, ty1, _, _ = _crop_windows(boxes, img_w, img_h)
+    return np.stack([x1, y1, x2, y2, tx1, ty1, bw, bh], axis=1).astype(np.int32)
+
+
+def stage1_level(prob: np.ndarray, reg: np.ndarray, scale: float, thr: float) -> np.ndarray:
+    """One pyramid level: prob [W', H'] float32 (the face channel), reg [W', H', 4] float32 -> rows [k, 9] = x1, y1, x2, y2,
+    score, 4 regressions of the cells at or above ``thr`` that survive the 0.5 NMS, in pick order."""
+    xi, yi = np.nonzero(prob >= thr)
+    if xi.size == 0:
+        return np.empty((0, 9))
+    score = prob[xi, yi]
+    # the reference flips the regression maps when exactly one cell fires (:383-387)
+    rr = reg[prob.shape[0] - 1 - xi, yi] if xi.size == 1 else reg[xi, yi]
+    cell = np.stack([xi, yi], axis=1)
+    boxes = np.hstack([np.fix((2 * cell + 1) / scale), np.fix((2 * cell + 12) / scale), score[:, None], rr])
+    return boxes[_iou_suppress(boxes, 0.5, False)]
+
+
+def stage1_finish(found: np.ndarray, img_w: int, img_h: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Every level's rows [n, 9] -> boxes [m, 5] after the 0.7 NMS, the P-Net regression, squaring and truncation, and their
+    crop table [m, 8]."""
+    boxes = np.asarray(found, np.float64)
+    if boxes.shape[0] == 0:
+        return np.empty((0, 5)), np.empty((0, 8), np.int32)
+    boxes = boxes[_iou_suppress(boxes, 0.7, False)]
+    rw, rh = boxes[:, 2] - boxes[:, 0], boxes[:, 3] - boxes[:, 1]
+    boxes = np.stack([boxes[:, 0] + boxes[:, 5] * rw, boxes[:, 1] + boxes[:, 6] * rh, boxes[:, 2] + boxes[:, 7] * rw,
+                      boxes[:, 3] + boxes[:, 8] * rh, boxes[:, 4]], axis=1)
+    boxes = _square(boxes)
+    boxes[:, 0:4] = np.fix(boxes[:, 0:4]).astype(np.int32)
+    return boxes, _crop_table(boxes, img_w, img_h)
+
+
+def stage2_finish(boxes_in: np.ndarray, prob: np.ndarray, reg: np.ndarray, thr: float, img_w: int, img_h: int) -> Tuple[np.ndarray, np.ndarray]:
+    """R-Net's prob [n, 2] and reg [n, 4] on the stage-1 boxes [n, 5] -> int32 boxes [m, 5] (scores above ``thr``, 0.7 NMS,
+    regression, squaring; the whole row truncated, score column included, as the reference's np.fix does) and their crop table."""
+    boxes = np.asarray(boxes_in)
+    score = prob[:, 1]
+    ok = np.nonzero(score > thr)[0]
+    boxes = np.hstack([boxes[ok, 0:4], score[ok][:, None]])
+    reg = reg[ok]
+    if boxes.shape[0] == 0:
+        return np.empty((0, 5)), np.empty((0, 8), np.int32)
+    keep = _iou_suppress(boxes, 0.7, False)
+    boxes = _square(_regress(boxes[keep], reg[keep]))
+    boxes = np.fix(boxes).astype(np.int32)
+    return boxes, _crop_table(boxes, img_w, img_h)
+
+
+def stage3_finish(boxes_in: np.ndarray, prob: np.ndarray, reg: np.ndarray, pts: np.ndarray, thr: float) -> Tuple[np.ndarray, np.ndarray]:
+    """O-Net's prob [n, 2], reg [n, 4] and landmarks pts [n, 10] on the stage-2 boxes [n, 5] -> boxes [m, 5] float64 (regressed,
+    then the 0.7 'Min' NMS) and landmarks [m, 10] float32 in frame pixels, taken relative to the boxes BEFORE the regression."""
+    boxes = np.asarray(boxes_in)
+    score = prob[:, 1]
+    ok = np.nonzero(score > thr)[0]
+    points = pts[ok].T                                           # [10, n]
+    reg = reg[ok]
+    boxes = np.hstack([boxes[ok, 0:4], score[ok][:, None]])
+    bw = boxes[:, 2] - boxes[:, 0] + 1
+    bh = boxes[:, 3] - boxes[:, 1] + 1
+    points[0:5, :] = bw[None, :] * points[0:5, :] + boxes[:, 0][None, :] - 1
+    points[5:10, :] = bh[None, :] * points[5:10, :] + boxes[:, 1][None, :] - 1
+    if boxes.shape[0]:
+        boxes = _regress(boxes, reg)
+        keep = _iou_suppress(boxes, 0.7, True)
+        boxes, points = boxes[keep], points[:, keep]
+    return boxes, np.ascontiguousarray(points.T)
+
+
 class MTCNNDetector:
     """callable(img_rgb_uint8) -> (bounding_boxes [n,5] = x1,y1,x2,y2,score; points [10,n])."""
 
@@ -325,17 +401,7 @@ class MTCNNDetector:
         for scale, (reg_t, prob_t) in zip(scales, maps):             # ... then read the maps back
             prob = prob_t[0, :, :, 1].cpu().numpy()                  # [W', H']
             reg = reg_t[0].cpu().numpy()                             # [W', H', 4]
-            xi, yi = np.nonzero(prob >= self.THRESHOLDS[0])
-            if xi.size == 0:
-                continue
-            score = prob[xi, yi]
-            # the reference flips the regression maps when exactly one cell fires (:383-387)
-            rr = reg[prob.shape[0] - 1 - xi, yi] if xi.size == 1 else reg[xi, yi]
-            cell = np.stack([xi, yi], axis=1)
-            boxes = np.hstack([np.fix((2 * cell + 1) / scale), np.fix((2 * cell + 12) / scale), score[:, None], rr])
-            keep = _iou_suppress(boxes, 0.5, False)
-            if keep.size:
-                found.append(boxes[keep])
+            found.append(stage1_level(prob, reg, scale, self.THRESHOLDS[0]))
         return np.concatenate(found, axis=0)
 
     def _crops(self, img: np.ndarray, boxes: np.ndarray, size: int, frame=None):
@@ -438,38 +504,15 @@ class MTCNNDetector:
                 return res
             self.host_fallbacks += 1
         points = np.array([])
+        h, w = img.shape[:2]
         boxes = self._stage1(img, frame)
         if boxes.shape[0]:
-            boxes = boxes[_iou_suppress(boxes, 0.7, False)]
-            rw, rh = boxes[:, 2] - boxes[:, 0], boxes[:, 3] - boxes[:, 1]
-            boxes = np.stack([boxes[:, 0] + boxes[:, 5] * rw, boxes[:, 1] + boxes[:, 6] * rh, boxes[:, 2] + boxes[:, 7] * rw,
-                              boxes[:, 3] + boxes[:, 8] * rh, boxes[:, 4]], axis=1)
-            boxes = _square(boxes)
-            boxes[:, 0:4] = np.fix(boxes[:, 0:4]).astype(np.int32)
+            boxes, _ = stage1_finish(boxes, w, h)
         if boxes.shape[0]:
             reg_t, prob_t = self.rnet(self._crops(img, boxes, 24, frame))
-            score = prob_t[:, 1].cpu().numpy()
-            reg = reg_t.cpu().numpy()
-            ok = np.nonzero(score > self.THRESHOLDS[1])[0]
-            boxes = np.hstack([boxes[ok, 0:4], score[ok][:, None]])
-            reg = reg[ok]
-            if boxes.shape[0]:
-                keep = _iou_suppress(boxes, 0.7, False)
-                boxes = _square(_regress(boxes[keep], reg[keep]))
+            boxes, _ = stage2_finish(boxes, prob_t.cpu().numpy(), reg_t.cpu().numpy(), self.THRESHOLDS[1], w, h)
         if boxes.shape[0]:
-            boxes = np.fix(boxes).astype(np.int32)
             reg_t, pts_t, prob_t = self.onet(self._crops(img, boxes, 48, frame))
-            score = prob_t[:, 1].cpu().numpy()
-            ok = np.nonzero(score > self.THRESHOLDS[2])[0]
-            points = pts_t.cpu().numpy()[ok].T                       # [10, n]
-            reg = reg_t.cpu().numpy()[ok]
-            boxes = np.hstack([boxes[ok, 0:4], score[ok][:, None]])
-            bw = boxes[:, 2] - boxes[:, 0] + 1
-            bh = boxes[:, 3] - boxes[:, 1] + 1
-            points[0:5, :] = bw[None, :] * points[0:5, :] + boxes[:, 0][None, :] - 1
-            points[5:10, :] = bh[None, :] * points[5:10, :] + boxes[:, 1][None, :] - 1
-            if boxes.shape[0]:
-                boxes = _regress(boxes, reg)
-                keep = _iou_suppress(boxes, 0.7, True)
-                boxes, points = boxes[keep], points[:, keep]
+            boxes, points = stage3_finish(boxes, prob_t.cpu().numpy(), reg_t.cpu().numpy(), pts_t.cpu().numpy(), self.THRESHOLDS[2])
+            points = points.T                                        # [10, n]
         return boxes, points

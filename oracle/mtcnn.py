@@ -205,6 +205,94 @@ def rerec(bbox):                                              # :467-476
     return bbox
 
 
+# ---------------------------------------------------------------------------------------------------
+# the four stage bodies of mtcnn_detect_faces (:478-604), each from the nets' outputs as the nets give them (the images are fed
+# transposed, so a P-Net map is [W', H'] and an R-/O-Net output is [n, channels]) to the lists the next stage reads.  Built only
+# from the helpers above.  ``argsort``: see nms(); the stable sort is the tie rule the product states, and the default here.
+# ---------------------------------------------------------------------------------------------------
+def stable_argsort(s):
+    return np.argsort(s, kind="stable")
+
+
+def crop_table(boxes, img_w, img_h):
+    """pad() as the table hsefr_mtcnn_crops reads: int32 [m, 8] = {x1, y1, x2, y2, tx1, ty1, bw, bh}."""
+    if boxes.shape[0] == 0:
+        return np.empty((0, 8), np.int32)
+    dy, edy, dx, edx, y, ey, x, ex, tmpw, tmph = pad(boxes.copy(), img_w, img_h)
+    return np.stack([x, y, ex, ey, dx, dy, tmpw, tmph], axis=1).astype(np.int32)
+
+
+def stage1_level(prob, reg, scale, thr, argsort=stable_argsort):                   # :505-515
+    """One pyramid level.  prob [W', H'] float32 (the face channel), reg [W', H', 4] float32 -> rows [k, 9] =
+    x1, y1, x2, y2, score, 4 regressions, in the NMS's pick order."""
+    out0 = np.transpose(reg, (1, 0, 2))                     # what detect's transpose(out[0], (0, 2, 1, 3))[0] is
+    out1 = np.transpose(prob)
+    boxes, _ = generate_bounding_box(out1.copy(), out0.copy(), scale, thr)
+    pick = nms(boxes.copy(), 0.5, 'Union', argsort)
+    if boxes.size > 0 and pick.size > 0:
+        return boxes[pick, :]
+    return np.empty((0, 9))
+
+
+def stage1_finish(found, img_w, img_h, argsort=stable_argsort):                    # :517-531
+    """All levels' rows [n, 9] -> boxes [m, 5] (regressed, squared, truncated; score) and their crop table [m, 8]."""
+    total_boxes = np.asarray(found, np.float64)
+    if total_boxes.shape[0] == 0:
+        return np.empty((0, 5)), np.empty((0, 8), np.int32)
+    pick = nms(total_boxes.copy(), 0.7, 'Union', argsort)
+    total_boxes = total_boxes[pick, :]
+    regw = total_boxes[:, 2] - total_boxes[:, 0]
+    regh = total_boxes[:, 3] - total_boxes[:, 1]
+    total_boxes = np.stack([total_boxes[:, 0] + total_boxes[:, 5] * regw, total_boxes[:, 1] + total_boxes[:, 6] * regh,
+                            total_boxes[:, 2] + total_boxes[:, 7] * regw, total_boxes[:, 3] + total_boxes[:, 8] * regh,
+                            total_boxes[:, 4]], axis=1)
+    total_boxes = rerec(total_boxes.copy())
+    total_boxes[:, 0:4] = np.fix(total_boxes[:, 0:4]).astype(np.int32)
+    return total_boxes, crop_table(total_boxes, img_w, img_h)
+
+
+def stage2_finish(boxes_in, prob, reg, thr, img_w, img_h, argsort=stable_argsort):  # :550-565
+    """R-Net's prob [n, 2] and reg [n, 4] on the stage-1 boxes [n, 5] -> int32 boxes [m, 5] (np.fix of the whole row, the score
+    column included, as the reference does before it cuts the O-Net crops) and their crop table [m, 8]."""
+    total_boxes = np.asarray(boxes_in)
+    out0, out1 = np.transpose(reg), np.transpose(prob)
+    score = out1[1, :]
+    ipass = np.where(score > thr)
+    total_boxes = np.hstack([total_boxes[ipass[0], 0:4].copy(), np.expand_dims(score[ipass].copy(), 1)])
+    mv = out0[:, ipass[0]]
+    if total_boxes.shape[0] > 0:
+        pick = nms(total_boxes, 0.7, 'Union', argsort)
+        total_boxes = total_boxes[pick, :]
+        total_boxes = bbreg(total_boxes.copy(), np.transpose(mv[:, pick]))
+        total_boxes = rerec(total_boxes.copy())
+    if total_boxes.shape[0] == 0:
+        return np.empty((0, 5), np.int32), np.empty((0, 8), np.int32)
+    total_boxes = np.fix(total_boxes).astype(np.int32)
+    return total_boxes, crop_table(total_boxes, img_w, img_h)
+
+
+def stage3_finish(boxes_in, prob, reg, pts, thr, argsort=stable_argsort):          # :580-603
+    """O-Net's prob [n, 2], reg [n, 4] and landmarks pts [n, 10] on the stage-2 boxes [n, 5] -> boxes [m, 5] float64 and
+    landmarks [m, 10] float32 (5 x then 5 y, in frame pixels)."""
+    total_boxes = np.asarray(boxes_in)
+    out0, out1, out2 = np.transpose(reg), np.transpose(pts), np.transpose(prob)
+    score = out2[1, :]
+    ipass = np.where(score > thr)
+    points = out1[:, ipass[0]]
+    total_boxes = np.hstack([total_boxes[ipass[0], 0:4].copy(), np.expand_dims(score[ipass].copy(), 1)])
+    mv = out0[:, ipass[0]]
+    bw = total_boxes[:, 2] - total_boxes[:, 0] + 1
+    bh = total_boxes[:, 3] - total_boxes[:, 1] + 1
+    points[0:5, :] = np.tile(bw, (5, 1)) * points[0:5, :] + np.tile(total_boxes[:, 0], (5, 1)) - 1
+    points[5:10, :] = np.tile(bh, (5, 1)) * points[5:10, :] + np.tile(total_boxes[:, 1], (5, 1)) - 1
+    if total_boxes.shape[0] > 0:
+        total_boxes = bbreg(total_boxes.copy(), np.transpose(mv))
+        pick = nms(total_boxes.copy(), 0.7, 'Min', argsort)
+        total_boxes = total_boxes[pick, :]
+        points = points[:, pick]
+    return total_boxes, np.ascontiguousarray(np.transpose(points))
+
+
 class OracleMTCNN:
     def __init__(self, mtcnn_pb: str, minsize: int = 32, compute_dtype=np.float32):
         self.g = GraphOracle(mtcnn_pb, compute_dtype)
@@ -255,50 +343,14 @@ class OracleMTCNN:
             hs, ws = int(np.ceil(h * scale)), int(np.ceil(w * scale))
             im_data = (cv2_resize_area(img, ws, hs) - 127.5) * 0.0078125
             out = self.pnet(np.transpose(im_data[None], (0, 2, 1, 3)))
-            out0 = np.transpose(out[0], (0, 2, 1, 3))
-            out1 = np.transpose(out[1], (0, 2, 1, 3))
-            boxes, _ = generate_bounding_box(out1[0, :, :, 1].copy(), out0[0].copy(), scale, threshold[0])
-            pick = nms(boxes.copy(), 0.5, 'Union')
-            if boxes.size > 0 and pick.size > 0:
-                total_boxes = np.append(total_boxes, boxes[pick, :], axis=0)
+            total_boxes = np.append(total_boxes, stage1_level(out[1][0, :, :, 1], out[0][0], scale, threshold[0]), axis=0)
         if total_boxes.shape[0] > 0:
-            pick = nms(total_boxes.copy(), 0.7, 'Union')
-            total_boxes = total_boxes[pick, :]
-            regw = total_boxes[:, 2] - total_boxes[:, 0]
-            regh = total_boxes[:, 3] - total_boxes[:, 1]
-            total_boxes = np.stack([total_boxes[:, 0] + total_boxes[:, 5] * regw, total_boxes[:, 1] + total_boxes[:, 6] * regh,
-                                    total_boxes[:, 2] + total_boxes[:, 7] * regw, total_boxes[:, 3] + total_boxes[:, 8] * regh,
-                                    total_boxes[:, 4]], axis=1)
-            total_boxes = rerec(total_boxes.copy())
-            total_boxes[:, 0:4] = np.fix(total_boxes[:, 0:4]).astype(np.int32)
+            total_boxes, _ = stage1_finish(total_boxes, w, h)
         if total_boxes.shape[0] > 0:
             out = self.rnet(self._crops(img, total_boxes, 24))
-            out0, out1 = np.transpose(out[0]), np.transpose(out[1])
-            score = out1[1, :]
-            ipass = np.where(score > threshold[1])
-            total_boxes = np.hstack([total_boxes[ipass[0], 0:4].copy(), np.expand_dims(score[ipass].copy(), 1)])
-            mv = out0[:, ipass[0]]
-            if total_boxes.shape[0] > 0:
-                pick = nms(total_boxes, 0.7, 'Union')
-                total_boxes = total_boxes[pick, :]
-                total_boxes = bbreg(total_boxes.copy(), np.transpose(mv[:, pick]))
-                total_boxes = rerec(total_boxes.copy())
+            total_boxes, _ = stage2_finish(total_boxes, out[1], out[0], threshold[1], w, h)
         if total_boxes.shape[0] > 0:
-            total_boxes = np.fix(total_boxes).astype(np.int32)
             out = self.onet(self._crops(img, total_boxes, 48))
-            out0, out1, out2 = np.transpose(out[0]), np.transpose(out[1]), np.transpose(out[2])
-            score = out2[1, :]
-            ipass = np.where(score > threshold[2])
-            points = out1[:, ipass[0]]
-            total_boxes = np.hstack([total_boxes[ipass[0], 0:4].copy(), np.expand_dims(score[ipass].copy(), 1)])
-            mv = out0[:, ipass[0]]
-            bw = total_boxes[:, 2] - total_boxes[:, 0] + 1
-            bh = total_boxes[:, 3] - total_boxes[:, 1] + 1
-            points[0:5, :] = np.tile(bw, (5, 1)) * points[0:5, :] + np.tile(total_boxes[:, 0], (5, 1)) - 1
-            points[5:10, :] = np.tile(bh, (5, 1)) * points[5:10, :] + np.tile(total_boxes[:, 1], (5, 1)) - 1
-            if total_boxes.shape[0] > 0:
-                total_boxes = bbreg(total_boxes.copy(), np.transpose(mv))
-                pick = nms(total_boxes.copy(), 0.7, 'Min')
-                total_boxes = total_boxes[pick, :]
-                points = points[:, pick]
+            total_boxes, points = stage3_finish(total_boxes, out[2], out[0], out[1], threshold[2])
+            points = points.T
         return total_boxes, points

@@ -163,7 +163,7 @@ def test_device_and_host_resizing_find_the_same_faces(z):
 @pytest.mark.parametrize("n,thr,use_min,seed", [(1, 0.5, False, 0), (37, 0.5, False, 1), (400, 0.7, False, 2), (2048, 0.7, True, 3), (300, 0.3, True, 4)])
 def test_device_nms_is_the_host_nms(n, thr, use_min, seed):
     """csrc/mtcnn_post.hip's greedy NMS against mtcnn._iou_suppress: same kept indices in the same order, including score TIES
-    (descending score, ascending index) and heavily overlapping clusters."""
+    (descending score, descending index) and heavily overlapping clusters."""
     import torch
     from hse_facerec_tf_amd import _lib, mtcnn
     rs = np.random.RandomState(seed)
