@@ -145,10 +145,9 @@ def build_plan(weights: Dict[str, np.ndarray], input_hw: Tuple[int, int] = (224,
     if fuse and f32 and subsample:
         lowering.subsample_stage_tails(layers, [gap])
     if fuse and not f32:
-        layers, remap = lowering.fuse_stem_pool(layers, [gap])
-        gap = remap[gap]
-        layers, remap = lowering.fuse_proj(layers, [gap])
-        gap = remap[gap]
+        for fuse_pass in (lowering.fuse_stem_pool, lowering.fuse_proj):
+            layers, remap = fuse_pass(layers, [gap])
+            gap = remap[gap]
         if subsample:
             lowering.subsample_stage_tails(layers, [gap])
         if pair:

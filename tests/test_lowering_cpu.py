@@ -451,3 +451,47 @@ def test_plan_describe_routes_the_baseline_plans_to_product_kernels_only():
         syms = subprocess.run(["nm", "-C", _lib.LIB_PATH], capture_output=True, text=True).stdout
         for dev_only in ("stem_fused_kernel", "conv3x3_win_bf16_kernel"):
             assert dev_only not in syms, dev_only
+
+
+def _chain(*src_res):
+    """Layers 0 .. n-1 of one shape, layer i reading (src, res) = src_res[i]."""
+    return [lowering.Layer(lowering.OP_CONV_BF16, "L%d" % i, s, (4, 4, 64), (4, 4, 64), res=r) for i, (s, r) in enumerate(src_res)]
+
+
+def test_consumers_of_lists_readers_in_layer_order_with_their_role():
+    layers = _chain((-1, -1), (0, -1), (1, 1), (1, 0), (3, -1))
+    cons = lowering.consumers_of(layers)
+    assert cons == {0: [(1, "src"), (3, "res")], 1: [(2, "src"), (2, "res"), (3, "src")], 3: [(4, "src")]}      # nobody reads 2 or 4; -1 is no producer
+    # a layer that reads one producer in both roles counts twice: not a sole reader
+    assert lowering.sole_reader(lowering.consumers_of(_chain((-1, -1), (0, 0))), 0, []) == -1
+    assert lowering.sole_reader(cons, 3, []) == 4 and lowering.sole_reader(cons, 3, [3]) == -1       # kept: stays
+    assert lowering.sole_reader(cons, 0, []) == -1 and lowering.sole_reader(cons, 4, []) == -1       # two readers; none
+    assert lowering.sole_reader(lowering.consumers_of(_chain((-1, -1), (-1, 0))), 0, []) == -1       # one reader, but as `res`
+
+
+def test_rebuild_drops_puts_and_rewires():
+    layers = _chain((-1, -1), (0, -1), (1, -1), (2, 0), (3, 2))
+    fused = lowering.Layer(lowering.OP_CONV_BF16, "F", 0, (4, 4, 64), (4, 4, 64))     # stands where layer 2 stood, reads what layer 1 read
+    layers[3].res = -1
+    new, remap = lowering.rebuild(layers, {1}, {2: fused})
+    assert remap == {0: 0, 1: -1, 2: 1, 3: 2, 4: 3}
+    assert [L.name for L in new] == ["L0", "F", "L3", "L4"] and new[1] is fused
+    assert [(L.src, L.res) for L in new] == [(-1, -1), (0, -1), (1, -1), (2, 1)]
+    # nothing to do: the same layers, the identity remap
+    same, ident = lowering.rebuild(new, set(), {})
+    assert all(a is b for a, b in zip(same, new)) and ident == {0: 0, 1: 1, 2: 2, 3: 3}
+    assert [(L.src, L.res) for L in same] == [(-1, -1), (0, -1), (1, -1), (2, 1)]
+
+
+@pytest.mark.parametrize("how", ["src", "res"])
+def test_rebuild_refuses_a_survivor_that_reads_a_dropped_layer(how):
+    """-1 is both 'dropped' and 'the network input': without the check layer 2 would silently read the image."""
+    layers = _chain((-1, -1), (0, -1), (1, -1) if how == "src" else (0, 1))
+    with pytest.raises(lowering.LoweringError) as e:
+        lowering.rebuild(layers, {1}, {})
+    assert "L2" in str(e.value) and "L1" in str(e.value)
+    # the put layer is checked too, and a dropped layer's own reads are not
+    with pytest.raises(lowering.LoweringError):
+        lowering.rebuild(_chain((-1, -1), (0, -1), (1, -1)), {0, 1}, {2: lowering.Layer(lowering.OP_CONV_BF16, "F", 1, (4, 4, 64), (4, 4, 64))})
+    new, remap = lowering.rebuild(_chain((-1, -1), (0, -1), (-1, -1)), {0, 1}, {})
+    assert remap == {0: -1, 1: -1, 2: 0} and (new[0].src, new[0].res) == (-1, -1)
