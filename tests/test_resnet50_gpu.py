@@ -9,6 +9,8 @@ import pytest
 from oracle import resnet50 as ores
 from oracle import tf_graph as tfo
 
+from bf16_exact_cases import CONV_SHAPES
+
 pytestmark = pytest.mark.gpu
 
 
@@ -31,29 +33,7 @@ def close_bf16(got, want):
     return not bad.any(), float((np.abs(got - want) / (np.abs(want).max() + 1e-30)).max())
 
 
-@pytest.mark.parametrize("n,h,w,c,cout,k,s,res,act", [
-    (2, 14, 14, 64, 64, 1, 1, False, 1), (2, 14, 14, 64, 256, 1, 1, True, 1), (1, 28, 28, 256, 128, 1, 2, False, 1),
-    (2, 13, 11, 128, 128, 3, 1, False, 1), (1, 56, 56, 64, 64, 3, 1, False, 1), (3, 7, 7, 512, 512, 3, 1, False, 1),
-    (2, 7, 7, 512, 2048, 1, 1, True, 1), (1, 15, 15, 256, 512, 1, 2, False, 0), (1, 9, 9, 1024, 256, 1, 1, False, 1),
-    (5, 5, 5, 64, 192, 3, 1, True, 0),
-    # the LDS-DMA implicit GEMM (csrc/conv_dma_bf16.hip): stride-2 projection from 512 channels, many tiles per workgroup with a
-    # ragged last tile, residual + ReLU on a 3x3, a 5x5 kernel, stride 2 with padding
-    (2, 9, 9, 512, 128, 1, 2, False, 0), (37, 14, 14, 64, 256, 3, 1, True, 1), (3, 11, 13, 128, 64, 5, 1, False, 1),
-    (2, 12, 12, 64, 128, 3, 2, False, 1),
-    # the window 3x3 kernel (csrc/conv3x3_win_bf16.hip; maps at least 40 wide): its four tile shapes, ragged image groups, residual
-    (2, 6, 40, 64, 128, 3, 1, True, 1), (1, 4, 48, 128, 256, 3, 1, False, 1), (3, 2, 44, 64, 64, 3, 1, False, 0),
-    (1, 28, 56, 64, 64, 3, 1, True, 1), (2, 5, 41, 192, 192, 3, 1, False, 1),
-    # the four-wave window 3x3 kernel (csrc/conv3x3_w2_bf16.hip, round 5): its three geometries (rows of <= 16 / 32 / 64 pixels),
-    # several channel slabs, residual, heights that are not a multiple of the tile's rows, columns dropped at the right edge,
-    # more tiles than workgroups (a persistent workgroup walks two tiles)
-    (2, 14, 14, 256, 256, 3, 1, False, 1), (3, 13, 12, 64, 128, 3, 1, True, 1), (1, 15, 16, 128, 128, 3, 1, False, 0),
-    (2, 28, 28, 128, 128, 3, 1, False, 1), (1, 9, 25, 64, 128, 3, 1, True, 1), (1, 30, 32, 64, 256, 3, 1, False, 1),
-    (2, 6, 50, 128, 64, 3, 1, True, 1), (1, 7, 64, 64, 192, 3, 1, False, 1), (260, 14, 14, 64, 128, 3, 1, False, 1),
-    # the four-wave 1x1 GEMM (csrc/conv1x1_w4_bf16.hip, round 5: K-deep reductions with >= 20 000 output pixels): stride 1 and 2 (gathered
-    # rows), a ragged last tile, several tiles per workgroup
-    (103, 14, 14, 256, 128, 1, 1, False, 1), (30, 53, 54, 256, 128, 1, 2, False, 1), (27, 28, 28, 512, 256, 1, 1, False, 0),
-    # ... and its FLAT geometry for maps of at most 7 x 7: whole images per tile, ragged image groups, 6-pixel edges, residual
-    (6, 7, 7, 128, 128, 3, 1, False, 1), (5, 6, 7, 64, 64, 3, 1, True, 1), (2, 7, 6, 128, 192, 3, 1, False, 0), (131, 7, 7, 64, 128, 3, 1, True, 1)])
+@pytest.mark.parametrize("n,h,w,c,cout,k,s,res,act", CONV_SHAPES)      # (stated once, with the kernel family of each row)
 def test_conv_bf16_vs_oracle(env, n, h, w, c, cout, k, s, res, act):
     torch, ops, resnet50 = env
     rs = np.random.RandomState(h * 7 + c + cout + k)
