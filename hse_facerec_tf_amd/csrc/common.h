@@ -199,6 +199,8 @@ int launch_heads_fused(const float* x, const float* w1, const float* b1, const f
 int launch_l2_normalize(const float* x, float* y, int n, int d, hipStream_t s);
 int launch_nn1(const float* q, const float* g, int nq, int ng, int d, int* nn_index, float* nn_dist2,
                hipStream_t s);
+int launch_knn(const float* q, const float* g, int nq, int ng, int d, int k, int* nn_index, float* nn_dist2, const int* g_label, int* pred,
+               hipStream_t s);
 long long nn1_fallbacks();
 
 int launch_conv_bf16(const void* x, const void* wt, const float* scale, const float* shift, const void* res, void* y,

@@ -1334,6 +1334,14 @@ int hsefr_nn1(const float* q, const float* g, int nq, int ng, int d, int* nn_ind
     return launch_nn1(q, g, nq, ng, d, nn_index, nn_dist2, (hipStream_t)stream);
 }
 
+int hsefr_knn(const float* q, const float* g, int nq, int ng, int d, int k, int* nn_index, float* nn_dist2, const int* g_label, int* pred,
+              hsefr_stream_t stream) {
+    HSEFR_REQUIRE(!g_label == !pred, HSEFR_ERR_INVALID, "knn: g_label and pred go together (labels at %p, pred at %p)", (const void*)g_label,
+                  (const void*)pred);
+    HSEFR_REQUIRE(nq == 0 || (q && g && nn_index), HSEFR_ERR_INVALID, "knn: null pointer");
+    return launch_knn(q, g, nq, ng, d, k, nn_index, nn_dist2, g_label, pred, (hipStream_t)stream);
+}
+
 long long hsefr_nn1_fallbacks(void) { return nn1_fallbacks(); }
 
 int hsefr_conv2d_direct(const float* x, const float* wgt, const float* bias, const float* alpha, float* y, int n, int h, int w, int c,

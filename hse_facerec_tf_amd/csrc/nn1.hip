@@ -1,8 +1,9 @@
-// Post-extract identification on device: L2 row normalisation and brute-force 1-NN, gfx950.
+// Post-extract identification on device: L2 row normalisation and brute-force 1-NN and k-NN, gfx950.
 //
-// Replaces preprocessing.normalize(X, 'l2') (facerec_test.py:401) and
+// Replaces preprocessing.normalize(X, 'l2') (facerec_test.py:401),
 // KNeighborsClassifier(n_neighbors=1, p=2).fit(gallery).kneighbors(probe)
-// (facerec_test.py:422 scored through classifier_tester :200-207).
+// (facerec_test.py:422 scored through classifier_tester :200-207) and the 3-NN classifiers of
+// facerec_test.py:269-288 (kneighbors and the uniform-weight predict: launch_knn at the end of this file).
 //
 // 1-NN = a [nq x ng x d] contraction (4582 x 4582 x 1024 for LFW, 43 GFLOP) -> fp32 MFMA:
 //   dist2[q, g] = |q|^2 + |g|^2 - 2 q.g ,  arg-min over g, ties to the lowest gallery index.
@@ -106,15 +107,13 @@ __global__ __launch_bounds__(256) void nn1_kernel(const float* __restrict__ q, c
     }
 }
 
-// Full Euclidean distance matrix D[i,j] = |x_i - y_j| (sklearn pairwise_distances at
-// facial_clustering_test.py:396; the feature term of process_photos.py:46-51's O(N^2) Python loop),
-// same MFMA contraction as nn1_kernel.  Workgroup = 64x64 outputs, wave = 32x32.
-__global__ __launch_bounds__(256) void pairwise_dist_kernel(const float* __restrict__ x, const float* __restrict__ y, int n, int m,
-                                                            int d, float* __restrict__ out, int same) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+// One wave's 32 x 32 tile of squared distances max(|x_i|^2 + |y_j|^2 - 2 x_i.y_j, 0) between rows i0.. of x [n,d] and j0.. of y [m,d]: the MFMA
+// contraction, operand arrangement and sum of nn1_kernel (so the same bits), handed to emit(row, col, dist2) for every element inside.
+template <class Emit>
+__device__ __forceinline__ void dist2_tile_32x32(const float* __restrict__ x, const float* __restrict__ y, int n, int m, int d, int i0, int j0,
+                                                 Emit emit) {
+    const int lane = threadIdx.x & 63;
     const int li = lane & 31, lh = lane >> 5;
-    const int i0 = blockIdx.y * 64 + (wave >> 1) * 32, j0 = blockIdx.x * 64 + (wave & 1) * 32;
-    if (i0 >= n || j0 >= m) return;
     const float* xp = x + (size_t)min(i0 + li, n - 1) * d + 4 * lh;
     const float* yp = y + (size_t)min(j0 + li, m - 1) * d + 4 * lh;
     f32x16 acc;
@@ -128,10 +127,31 @@ __global__ __launch_bounds__(256) void pairwise_dist_kernel(const float* __restr
         const int rr = (r & 3) + 8 * (r >> 2) + 4 * lh;
         const float xr = __shfl(xx, rr);
         const int row = i0 + rr;
-        float v = sqrtf(fmaxf(xr + yy - 2.f * acc[r], 0.f));
-        if (same && row == col) v = 0.f;     // pairwise_distances(X) has an exact zero diagonal
-        if (row < n && col < m) out[(size_t)row * m + col] = v;
+        const float v = fmaxf(xr + yy - 2.f * acc[r], 0.f);
+        if (row < n && col < m) emit(row, col, v);
     }
+}
+
+// Full Euclidean distance matrix D[i,j] = |x_i - y_j| (sklearn pairwise_distances at
+// facial_clustering_test.py:396; the feature term of process_photos.py:46-51's O(N^2) Python loop),
+// same MFMA contraction as nn1_kernel.  Workgroup = 64x64 outputs, wave = 32x32.
+__global__ __launch_bounds__(256) void pairwise_dist_kernel(const float* __restrict__ x, const float* __restrict__ y, int n, int m,
+                                                            int d, float* __restrict__ out, int same) {
+    const int wave = threadIdx.x >> 6;
+    const int i0 = blockIdx.y * 64 + (wave >> 1) * 32, j0 = blockIdx.x * 64 + (wave & 1) * 32;
+    if (i0 >= n || j0 >= m) return;
+    dist2_tile_32x32(x, y, n, m, d, i0, j0, [=](int row, int col, float v2) {
+        out[(size_t)row * m + col] = same && row == col ? 0.f : sqrtf(v2);     // pairwise_distances(X) has an exact zero diagonal
+    });
+}
+
+// The k-NN search of everything the split-f16 GEMM does not take: the finished squared distances of a block of probe rows, [n, ld].
+__global__ __launch_bounds__(256) void knn_dist2_tile_kernel(const float* __restrict__ q, const float* __restrict__ g, int n, int ng, int d,
+                                                             float* __restrict__ out, int ld) {
+    const int wave = threadIdx.x >> 6;
+    const int i0 = blockIdx.y * 64 + (wave >> 1) * 32, j0 = blockIdx.x * 64 + (wave & 1) * 32;
+    if (i0 >= n || j0 >= ng) return;
+    dist2_tile_32x32(q, g, n, ng, d, i0, j0, [=](int row, int col, float v2) { out[(size_t)row * ld + col] = v2; });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -236,6 +256,92 @@ __global__ __launch_bounds__(256) void nn1_row_argmin_kernel(const float* __rest
     }
 }
 
+// k nearest rows of a slice y [nq, ld] of squared distances (qq == nullptr: finished, from knn_dist2_tile_kernel) or of |g|^2 - 2 q.g (the
+// split-f16 GEMM's epilogue; qq = |q|^2, finished here exactly as nn1_row_argmin_kernel does), one wave per probe row.  Distances are
+// never NaN (fmaxf(., 0) on both paths, as in nn1).  Each lane strides over the row with a list of its CAP >= k best candidates sorted
+// by (dist2, index) in registers -- insertion and pop are unrolled compare-and-shift, no register is indexed at run time; a comparison
+// with the list's last entry gates the insertion.  The 64 lists are merged by k wave arg-mins over their heads under the same order
+// (the winning lane pops): result t lands in lane t, which writes it, and the lanes below k then hold the neighbours' labels for the
+// vote -- most occurrences, equal counts to the smallest label value (scikit-learn's uniform-weight predict).
+template <int CAP>
+__global__ __launch_bounds__(256) void knn_select_kernel(const float* __restrict__ y, int nq, int ng, int ld, const float* __restrict__ qq,
+                                                         int k, int* __restrict__ nn_index, float* __restrict__ nn_dist2,
+                                                         const int* __restrict__ g_label, int* __restrict__ pred) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= nq) return;
+    const float* r = y + (size_t)row * ld;
+    const float qr = qq ? qq[row] : 0.f;
+    float lv[CAP];
+    int li[CAP];
+#pragma unroll
+    for (int i = 0; i < CAP; ++i) { lv[i] = INFINITY; li[i] = 0x7fffffff; }
+    for (int j0 = lane; j0 < ng; j0 += 256) {
+        float in[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) in[u] = j0 + 64 * u < ng ? r[j0 + 64 * u] : 0.f;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int j = j0 + 64 * u;
+            const float v = qq ? fmaxf(qr + in[u], 0.f) : in[u];
+            // better(v, j, entry) for THIS lane's entries: its columns ascend, so an equal value never goes in front of a held one, and
+            // an empty entry (INFINITY, the sentinel index) gives way to every candidate, one at distance INFINITY included
+            if (j < ng && (v < lv[CAP - 1] || li[CAP - 1] == 0x7fffffff)) {
+                bool front[CAP];
+#pragma unroll
+                for (int i = 0; i < CAP; ++i) front[i] = v < lv[i] || li[i] == 0x7fffffff;
+#pragma unroll
+                for (int i = CAP - 1; i >= 0; --i) {
+                    // entry i takes its upper neighbour when the candidate goes in front of that one, the candidate when it goes exactly here
+                    const bool above = i > 0 && front[i > 0 ? i - 1 : 0];
+                    lv[i] = above ? lv[i > 0 ? i - 1 : 0] : front[i] ? v : lv[i];
+                    li[i] = above ? li[i > 0 ? i - 1 : 0] : front[i] ? j : li[i];
+                }
+            }
+        }
+    }
+    float out_v = INFINITY;
+    int out_i = 0x7fffffff;
+    for (int t = 0; t < k; ++t) {
+        float bv = lv[0];
+        int bi = li[0];
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {
+            const float ov = __shfl_xor(bv, m);
+            const int oi = __shfl_xor(bi, m);
+            if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+        }
+        if (lane == t) { out_v = bv; out_i = bi; }
+        if (li[0] == bi) {                                   // gallery indices are unique: one lane holds the winner (none is left: all hold the sentinel)
+#pragma unroll
+            for (int i = 0; i + 1 < CAP; ++i) { lv[i] = lv[i + 1]; li[i] = li[i + 1]; }
+            lv[CAP - 1] = INFINITY;
+            li[CAP - 1] = 0x7fffffff;
+        }
+    }
+    if (lane < k) {
+        nn_index[(size_t)row * k + lane] = out_i;
+        if (nn_dist2) nn_dist2[(size_t)row * k + lane] = out_v;
+    }
+    if (!g_label) return;
+    const bool found = lane < k && out_i < ng;               // k <= ng results exist; the test keeps the label read in bounds regardless
+    const int lab = found ? g_label[out_i] : 0x7fffffff;
+    int cnt = 0;
+    for (int t = 0; t < k; ++t) {
+        const int other = __shfl(lab, t);
+        const bool other_found = __shfl((int)found, t) != 0;
+        cnt += found && other_found && other == lab;
+    }
+    int bl = lab;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const int oc = __shfl_xor(cnt, m);
+        const int ol = __shfl_xor(bl, m);
+        if (oc > cnt || (oc == cnt && ol < bl)) { cnt = oc; bl = ol; }
+    }
+    if (lane == 0) pred[row] = bl;
+}
+
 }  // namespace
 
 int launch_pairwise_dist(const float* x, const float* y, int n, int m, int d, float* out, hipStream_t s) {
@@ -264,70 +370,129 @@ void set_nn1_y_mb(int v) { g_nn1_y_mb = v > 0 ? v : 1; }
 static std::atomic<long long> g_nn1_fallbacks{0};
 long long nn1_fallbacks() { return g_nn1_fallbacks.load(); }
 
+// The split-f16 GEMM search shared by launch_nn1 and launch_knn: its workspace (scaled probes, split gallery, a [block, ng_pad] slice of
+// |g|^2 - 2 q.g) is stream-ordered.  The matrix is walked in QUERY BLOCKS so that it stays bounded (NN1_Y_BYTES: 100 000 x 100 000 would
+// be 40 GB in one piece -- ADVICE r4); rows are independent, so the blocking changes no bit.  select(y, m, ng_pad, qq, q0) reduces the
+// slice of probe rows q0 .. q0 + m (qq = their |q|^2) and returns its status.  Returns false when not even the smallest workspace could be
+// had (the caller's allocator may hold the memory) and nothing was launched: the caller runs its other path -- not an error, but COUNTED
+// and described, so a perf cliff or a last-bit difference can be traced to it (hsefr_nn1_fallbacks, hsefr_last_error_string).
+template <class Select>
+static bool split_f16_search(const char* what, const float* q, const float* g, int nq, int ng, int d, hipStream_t s, int& rc, Select select) {
+    const int ng_pad = (ng + 63) / 64 * 64;
+    const long long y_rows_max = NN1_Y_BYTES / ((long long)ng_pad * 4);
+    int qb = (int)(y_rows_max >= nq ? nq : (y_rows_max < 256 ? 256 : y_rows_max / 256 * 256));     // query rows per block
+    const size_t b_qs = (size_t)nq * d * 4, b_w = (size_t)ng_pad * d * 4;
+    size_t b_y = (size_t)qb * ng_pad * 4;
+    const size_t b_small = ((size_t)nq + 2 * (size_t)ng_pad + 64) * 4;
+    char* ws = nullptr;
+    // a failed allocation is retried with HALF the query block, down to 256 rows (the slice of the distance matrix is
+    // the only part of the workspace that can shrink), before the search gives up on this path
+    while (hipMallocAsync((void**)&ws, b_qs + b_w + b_y + b_small, s) != hipSuccess || !ws) {
+        (void)hipGetLastError();
+        ws = nullptr;
+        if (qb <= 256) break;
+        qb = qb / 2 < 256 ? 256 : qb / 2 / 256 * 256;
+        b_y = (size_t)qb * ng_pad * 4;
+    }
+    if (!ws) {
+        g_nn1_fallbacks.fetch_add(1);
+        set_error("%s: no stream-ordered workspace (%zu bytes) for the split-f16 search of %d x %d x %d; ran the fp32 kernel", what,
+                  b_qs + b_w + b_y + b_small, nq, ng, d);
+        return false;
+    }
+    float* qs = (float*)ws;
+    unsigned short* w = (unsigned short*)(ws + b_qs);
+    float* y = (float*)(ws + b_qs + b_w);
+    float* qq = (float*)(ws + b_qs + b_w + b_y);
+    float* descale = qq + nq;
+    float* shift = descale + ng_pad;
+    unsigned* qmax = (unsigned*)(shift + ng_pad);
+    rc = HSEFR_OK;
+    if (hipMemsetAsync(qmax, 0, 4, s) != hipSuccess) rc = HSEFR_ERR_HIP;
+    if (rc == HSEFR_OK) {
+        HSEFR_LAUNCH(nn1_prep_queries_kernel, dim3((nq + 3) / 4), dim3(256), 0, s, q, nq, d, qq, qmax);
+        HSEFR_LAUNCH(nn1_split_gallery_kernel, dim3((ng_pad + 3) / 4), dim3(256), 0, s, g, ng, ng_pad, d, w, descale, shift, qmax);
+        const long long n4 = (long long)nq * d / 4;
+        HSEFR_LAUNCH(nn1_scale_queries_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, q, qs, n4, qmax);
+        rc = launch_status("split-f16 search preparation");
+    }
+    for (int q0 = 0; q0 < nq && rc == HSEFR_OK; q0 += qb) {
+        const int m = nq - q0 < qb ? nq - q0 : qb;
+        rc = launch_pwconv_f16s(qs + (size_t)q0 * d, w, descale, shift, y, m, d, ng_pad, 12, HSEFR_ACT_NONE, s);
+        if (rc == HSEFR_OK) rc = select(y, m, ng_pad, qq + q0, q0);
+    }
+    (void)hipFreeAsync(ws, s);
+    return true;
+}
+
+static bool split_f16_shape(int nq, int ng, int d) { return d % 32 == 0 && (long long)nq * ng * d >= (1ll << 28); }
+
 int launch_nn1(const float* q, const float* g, int nq, int ng, int d, int* nn_index, float* nn_dist2, hipStream_t s) {
     HSEFR_REQUIRE(d > 0 && d % 8 == 0, HSEFR_ERR_UNSUPPORTED, "nn1: d=%d must be a multiple of 8", d);
     HSEFR_REQUIRE(nq >= 0 && ng > 0, HSEFR_ERR_INVALID, "nn1: nq=%d ng=%d", nq, ng);
     if (nq == 0) return HSEFR_OK;
-    if (d % 32 == 0 && (long long)nq * ng * d >= (1ll << 28)) {
-        // the split-f16 GEMM path; its workspace (scaled probes, split gallery, a [block, ng_pad] slice of the distance matrix) is
-        // stream-ordered.  The matrix is walked in QUERY BLOCKS so that it stays bounded (NN1_Y_BYTES: 100 000 x 100 000 would be
-        // 40 GB in one piece -- ADVICE r4); rows are independent, so the blocking changes no bit.  If the allocation fails (the
-        // caller's allocator may hold the memory) the search runs on nn1_kernel, which needs no workspace.
-        const int ng_pad = (ng + 63) / 64 * 64;
-        const long long y_rows_max = NN1_Y_BYTES / ((long long)ng_pad * 4);
-        int qb = (int)(y_rows_max >= nq ? nq : (y_rows_max < 256 ? 256 : y_rows_max / 256 * 256));     // query rows per block
-        const size_t b_qs = (size_t)nq * d * 4, b_w = (size_t)ng_pad * d * 4;
-        size_t b_y = (size_t)qb * ng_pad * 4;
-        const size_t b_small = ((size_t)nq + 2 * (size_t)ng_pad + 64) * 4;
-        char* ws = nullptr;
-        // a failed allocation is retried with HALF the query block, down to 256 rows (the slice of the distance matrix is
-        // the only part of the workspace that can shrink), before the search gives up on this path
-        while (hipMallocAsync((void**)&ws, b_qs + b_w + b_y + b_small, s) != hipSuccess || !ws) {
-            (void)hipGetLastError();
-            ws = nullptr;
-            if (qb <= 256) break;
-            qb = qb / 2 < 256 ? 256 : qb / 2 / 256 * 256;
-            b_y = (size_t)qb * ng_pad * 4;
-        }
-        if (ws) {
-            float* qs = (float*)ws;
-            unsigned short* w = (unsigned short*)(ws + b_qs);
-            float* y = (float*)(ws + b_qs + b_w);
-            float* qq = (float*)(ws + b_qs + b_w + b_y);
-            float* descale = qq + nq;
-            float* shift = descale + ng_pad;
-            unsigned* qmax = (unsigned*)(shift + ng_pad);
-            int rc = HSEFR_OK;
-            if (hipMemsetAsync(qmax, 0, 4, s) != hipSuccess) rc = HSEFR_ERR_HIP;
-            if (rc == HSEFR_OK) {
-                HSEFR_LAUNCH(nn1_prep_queries_kernel, dim3((nq + 3) / 4), dim3(256), 0, s, q, nq, d, qq, qmax);
-                HSEFR_LAUNCH(nn1_split_gallery_kernel, dim3((ng_pad + 3) / 4), dim3(256), 0, s, g, ng, ng_pad, d, w, descale, shift, qmax);
-                const long long n4 = (long long)nq * d / 4;
-                HSEFR_LAUNCH(nn1_scale_queries_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, q, qs, n4, qmax);
-                rc = launch_status("nn1 (split-f16 preparation)");
-            }
-            for (int q0 = 0; q0 < nq && rc == HSEFR_OK; q0 += qb) {
-                const int m = nq - q0 < qb ? nq - q0 : qb;
-                rc = launch_pwconv_f16s(qs + (size_t)q0 * d, w, descale, shift, y, m, d, ng_pad, 12, HSEFR_ACT_NONE, s);
-                if (rc == HSEFR_OK) {
-                    HSEFR_LAUNCH(nn1_row_argmin_kernel, dim3((m + 3) / 4), dim3(256), 0, s, y, m, ng, ng_pad, qq + q0, nn_index + q0,
-                                       nn_dist2 ? nn_dist2 + q0 : nullptr);
-                    rc = launch_status("nn1 (row arg-min)");
-                }
-            }
-            (void)hipFreeAsync(ws, s);
-            return rc;
-        }
-        // no workspace even for a 256-row block: the search runs on nn1_kernel (no workspace; another summation order, far slower at
-        // these sizes).  Not an error -- but COUNTED and described, so a perf cliff or a last-bit difference can be traced to it
-        // (hsefr_nn1_fallbacks, hsefr_last_error_string)
-        g_nn1_fallbacks.fetch_add(1);
-        set_error("nn1: no stream-ordered workspace (%zu bytes) for the split-f16 search of %d x %d x %d; ran the workspace-free kernel",
-                  b_qs + b_w + b_y + b_small, nq, ng, d);
-    }
+    int rc;
+    if (split_f16_shape(nq, ng, d) &&
+        split_f16_search("nn1", q, g, nq, ng, d, s, rc, [&](const float* y, int m, int ng_pad, const float* qq, int q0) {
+            HSEFR_LAUNCH(nn1_row_argmin_kernel, dim3((m + 3) / 4), dim3(256), 0, s, y, m, ng, ng_pad, qq, nn_index + q0,
+                               nn_dist2 ? nn_dist2 + q0 : nullptr);
+            return launch_status("nn1 (row arg-min)");
+        }))
+        return rc;
+    // every other search, and a large one without workspace, runs on nn1_kernel (no workspace; another summation order, far slower at
+    // large sizes)
     dim3 grid((nq + 31) / 32), block(256);
     HSEFR_LAUNCH(nn1_kernel, grid, block, 0, s, q, g, nq, ng, d, nn_index, nn_dist2);
     return launch_status("nn1");
+}
+
+static int launch_knn_select(const float* y, int m, int ng, int ld, const float* qq, int k, int* nn_index, float* nn_dist2,
+                             const int* g_label, int* pred, hipStream_t s) {
+    // the list capacity is the kernel's cost in registers and in insertion work (nearly every column enters the list of SOME lane of its
+    // wave): 4 entries serve the reference's 3-NN, 16 every k the entry point takes
+    if (k <= 4) HSEFR_LAUNCH(knn_select_kernel<4>, dim3((m + 3) / 4), dim3(256), 0, s, y, m, ng, ld, qq, k, nn_index, nn_dist2, g_label, pred);
+    else if (k <= 8) HSEFR_LAUNCH(knn_select_kernel<8>, dim3((m + 3) / 4), dim3(256), 0, s, y, m, ng, ld, qq, k, nn_index, nn_dist2, g_label, pred);
+    else HSEFR_LAUNCH(knn_select_kernel<16>, dim3((m + 3) / 4), dim3(256), 0, s, y, m, ng, ld, qq, k, nn_index, nn_dist2, g_label, pred);
+    return launch_status("knn (selection)");
+}
+
+int launch_knn(const float* q, const float* g, int nq, int ng, int d, int k, int* nn_index, float* nn_dist2, const int* g_label, int* pred,
+               hipStream_t s) {
+    HSEFR_REQUIRE(d > 0 && d % 8 == 0, HSEFR_ERR_UNSUPPORTED, "knn: d=%d must be a multiple of 8", d);
+    HSEFR_REQUIRE(nq >= 0 && ng > 0 && ng <= 0x7fffffff - 512, HSEFR_ERR_INVALID, "knn: nq=%d ng=%d", nq, ng);
+    HSEFR_REQUIRE(k >= 1 && k <= 16 && k <= ng, HSEFR_ERR_INVALID, "knn: k=%d must be in 1..16 and at most ng=%d", k, ng);
+    if (nq == 0) return HSEFR_OK;
+    const auto select = [&](const float* y, int m, int ld, const float* qq, int q0) {
+        return launch_knn_select(y, m, ng, ld, qq, k, nn_index + (size_t)q0 * k, nn_dist2 ? nn_dist2 + (size_t)q0 * k : nullptr, g_label,
+                                 pred ? pred + q0 : nullptr, s);
+    };
+    int rc;
+    if (split_f16_shape(nq, ng, d) && split_f16_search("knn", q, g, nq, ng, d, s, rc, select)) return rc;
+    // every other search (small by definition), and a large one without workspace: finished fp32 distances, nn1_kernel's own bits, into a
+    // slice of query rows bounded and halved like the GEMM path's, then the same selection.  A list of k candidates for each of
+    // nn1_kernel's 16 accumulator rows per lane would not fit its registers.
+    const long long rows_max = NN1_Y_BYTES / ((long long)ng * 4);
+    const int grid_rows = 65535 * 64;                       // the tile kernel's grid.y
+    int qb = (int)(rows_max >= nq ? nq : (rows_max < 64 ? 64 : rows_max / 64 * 64));
+    if (qb > grid_rows) qb = grid_rows;
+    float* y = nullptr;
+    while (hipMallocAsync((void**)&y, (size_t)qb * ng * 4, s) != hipSuccess || !y) {
+        (void)hipGetLastError();
+        y = nullptr;
+        if (qb <= 64) break;
+        qb = qb / 2 < 64 ? 64 : qb / 2 / 64 * 64;
+    }
+    HSEFR_REQUIRE(y, HSEFR_ERR_NOMEM, "knn: no stream-ordered workspace (%zu bytes) for a %d-row slice of the %d x %d distance matrix",
+                  (size_t)qb * ng * 4, qb, nq, ng);
+    rc = HSEFR_OK;
+    for (int q0 = 0; q0 < nq && rc == HSEFR_OK; q0 += qb) {
+        const int m = nq - q0 < qb ? nq - q0 : qb;
+        HSEFR_LAUNCH(knn_dist2_tile_kernel, dim3((ng + 63) / 64, (m + 63) / 64), dim3(256), 0, s, q + (size_t)q0 * d, g, m, ng, d, y, ng);
+        rc = launch_status("knn (distance tiles)");
+        if (rc == HSEFR_OK) rc = select(y, m, ng, nullptr, q0);
+    }
+    (void)hipFreeAsync(y, s);
+    return rc;
 }
 
 }  // namespace hsefr

@@ -4,7 +4,7 @@ Host steps stay what the reference does on the host -- including its own scikit-
 for the label encoding and the stratified split (scikit-learn is a dependency of the
 reference's callers, not of the engine); the O(N_test x N_train x D) nearest-neighbour search
 (KNeighborsClassifier(1).fit/predict, :422,:203) and the L2 normalisation (:401) run through
-libhsefr (ops.l2_normalize / ops.nn1).
+libhsefr (ops.l2_normalize / ops.nn1; ops.knn for the reference's '3-NN' rows, facerec_test.py:269-288).
 """
 from __future__ import annotations
 
@@ -63,8 +63,21 @@ def start_split(y: np.ndarray, random_state: int = 0) -> SplitJob:
     return SplitJob(np.asarray(y), random_state)
 
 
+def _knn_predict(ops, qry, gal, y_gallery: np.ndarray, n_neighbors: int):
+    """KNeighborsClassifier(n_neighbors).fit(gal, y_gallery) -> kneighbors + predict of ``qry`` on the device (ops.knn).  The labels are
+    encoded with np.unique, so the vote's smallest-label rule runs over scikit-learn's sorted ``classes_`` and any label type works.
+    Returns (y_pred, nn_index [nq,k], nn_dist [nq,k]) on the host."""
+    from . import _lib
+    torch = _lib.require_gpu()
+    classes, codes = np.unique(np.asarray(y_gallery), return_inverse=True)
+    labels = torch.from_numpy(codes.astype(np.int32).reshape(-1)).to(gal.device)
+    idx, d2, pred = ops.knn(qry, gal, n_neighbors, labels)
+    return classes[pred.cpu().numpy()], idx.cpu().numpy(), np.sqrt(d2.cpu().numpy())
+
+
 def one_nn_identification(X, y: np.ndarray, split=None,
-                          pca_components: Optional[int] = None, timings: Optional[dict] = None, device=None) -> Dict:
+                          pca_components: Optional[int] = None, timings: Optional[dict] = None, device=None,
+                          n_neighbors: int = 1) -> Dict:
     """The protocol of facerec_test.py:401-432: 'k-NN' (pca_components=None) or 'k-NN+PCA'
     (pca_components=128, the Pipeline of :421 -- PCA is fitted on the gallery half by scikit-learn on
     the host, exactly as the reference does, and the projected vectors go back to the device for the search).
@@ -73,9 +86,12 @@ def one_nn_identification(X, y: np.ndarray, split=None,
     split: None (compute it here), a (train, test) pair over the FILTERED samples, or a SplitJob started on the same labels.
     Returns accuracy, the split, predictions and nearest-gallery indices.  ``timings`` (optional dict) receives the
     device-synchronised wall seconds of each phase: normalize_s, host_split_s, select_s, nn1_s, readback_s (indices and
-    distances back to the host + the label comparison)."""
+    distances back to the host + the label comparison).
+    n_neighbors: 1 labels a probe by its nearest gallery row (ops.nn1); more by the uniform vote of that many (ops.knn: 'nn_index' and
+    'nn_dist' become [nq, k]; the search is still timed as nn1_s)."""
     import time
     from . import _lib, ops
+    ops.check_n_neighbors(n_neighbors)
     torch = _lib.require_gpu()
     if isinstance(X, np.ndarray):
         X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(_lib.cuda_device(device))
@@ -110,11 +126,15 @@ def one_nn_identification(X, y: np.ndarray, split=None,
             z = pca.transform(t.cpu().numpy()).astype(np.float32)
             return torch.from_numpy(np.pad(z, ((0, 0), (0, pad)))).to(Xn.device).contiguous()
         gal, qry = proj(gal), proj(qry)
-    nn_idx, nn_d2 = ops.nn1(qry, gal)
-    t = lap("nn1_s", t)
-    nn_idx_h = nn_idx.cpu().numpy()
-    nn_dist_h = np.sqrt(nn_d2.cpu().numpy())
-    y_pred = y_enc[train][nn_idx_h]
+    if n_neighbors == 1:
+        nn_idx, nn_d2 = ops.nn1(qry, gal)
+        t = lap("nn1_s", t)
+        nn_idx_h = nn_idx.cpu().numpy()
+        nn_dist_h = np.sqrt(nn_d2.cpu().numpy())
+        y_pred = y_enc[train][nn_idx_h]
+    else:
+        y_pred, nn_idx_h, nn_dist_h = _knn_predict(ops, qry, gal, y_enc[train], n_neighbors)
+        t = lap("nn1_s", t)
     acc = float((y_pred == y_enc[test]).mean()) if len(test) else float("nan")
     t = lap("readback_s", t)
     if timings is not None:
@@ -148,19 +168,23 @@ def single_image_per_class_splits(y: np.ndarray, n_splits: int = 10, random_stat
     return res_cv
 
 
-def _nn1_predict(torch, ops, Xd, train, test, y):
+def _nn1_predict(torch, ops, Xd, train, test, y, n_neighbors: int = 1):
     gal = Xd[torch.from_numpy(np.asarray(train, dtype=np.int64)).to(Xd.device)].contiguous()
     qry = Xd[torch.from_numpy(np.asarray(test, dtype=np.int64)).to(Xd.device)].contiguous()
+    if n_neighbors != 1:
+        return _knn_predict(ops, qry, gal, y[np.asarray(train)], n_neighbors)
     nn_idx, nn_d2 = ops.nn1(qry, gal)
     nn_idx_h = nn_idx.cpu().numpy()
     return y[np.asarray(train)][nn_idx_h], nn_idx_h, np.sqrt(nn_d2.cpu().numpy())
 
 
-def cross_validated_1nn(X, y: np.ndarray, cv, normalize: bool = True, device=None) -> Dict:
+def cross_validated_1nn(X, y: np.ndarray, cv, normalize: bool = True, device=None, n_neighbors: int = 1) -> Dict:
     """classifier_tester (facerec_test.py:199-207) for KNeighborsClassifier(n_neighbors=1, p=2) over an explicit list of
     (train, test) index pairs -- e.g. single_image_per_class_splits(y) in place of the stratified half split (:200-201) --
-    with every search on the GPU.  Returns the per-split accuracies and their mean / std as the reference prints them."""
+    with every search on the GPU.  Returns the per-split accuracies and their mean / std as the reference prints them.
+    ``n_neighbors`` > 1 scores KNeighborsClassifier(n_neighbors) instead (ops.knn's uniform vote)."""
     from . import _lib, ops
+    ops.check_n_neighbors(n_neighbors)
     torch = _lib.require_gpu()
     if isinstance(X, np.ndarray):
         X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(_lib.cuda_device(device))
@@ -168,7 +192,7 @@ def cross_validated_1nn(X, y: np.ndarray, cv, normalize: bool = True, device=Non
     y = np.asarray(y)
     accs, preds = [], []
     for train, test in cv:
-        y_pred, _, _ = _nn1_predict(torch, ops, Xd, train, test, y)
+        y_pred, _, _ = _nn1_predict(torch, ops, Xd, train, test, y, n_neighbors)
         preds.append(y_pred)
         accs.append(float((y_pred == y[np.asarray(test)]).mean()) if len(test) else float("nan"))
     accs = np.asarray(accs)
@@ -177,14 +201,16 @@ def cross_validated_1nn(X, y: np.ndarray, cv, normalize: bool = True, device=Non
 
 
 def gallery_probe_identification(X_train, y_train: np.ndarray, X_test, y_test: np.ndarray, normalize: bool = False,
-                                 pca_components: Optional[int] = None, device=None) -> Dict:
+                                 pca_components: Optional[int] = None, device=None, n_neighbors: int = 1) -> Dict:
     """The gallery / probe protocol of tf_train_test_recognition (facerec_test.py:260-288): the '1-NN' classifier (and
     '1-NN+PCA' with ``pca_components``, 16 at :269) FITTED on the gallery features, every probe labelled by its nearest
     gallery row; accuracy = share of probes whose label is right (:287).  NB the reference computes L2-normalised copies
     (:262,265) and then fits / predicts on the UN-normalised ``X_train`` / ``X_test`` (:284-285): ``normalize=False`` is what
     it runs, ``normalize=True`` what the copies suggest it meant.  The search runs on the GPU (hsefr_nn1: ties -> the lowest
-    gallery index, scikit-learn's own choice)."""
+    gallery index, scikit-learn's own choice).  ``n_neighbors`` > 1 gives the '3-NN' / '3-NN+PCA' rows of :269-272 (hsefr_knn: the
+    uniform vote, equal counts to the smallest label as in scikit-learn's predict; 'nn_index' and 'nn_dist' become [nq, k])."""
     from . import _lib, ops
+    ops.check_n_neighbors(n_neighbors, len(np.asarray(y_train)))
     torch = _lib.require_gpu()
     dev = _lib.cuda_device(device)
 
@@ -205,11 +231,14 @@ def gallery_probe_identification(X_train, y_train: np.ndarray, X_test, y_test: n
             z = pca.transform(t.cpu().numpy()).astype(np.float32)
             return torch.from_numpy(np.pad(z, ((0, 0), (0, pad)))).to(dev).contiguous()
         gal, qry = proj(gal), proj(qry)
-    nn_idx, nn_d2 = ops.nn1(qry, gal)
-    nn_idx_h = nn_idx.cpu().numpy()
-    y_pred = y_train[nn_idx_h]
+    if n_neighbors == 1:
+        nn_idx, nn_d2 = ops.nn1(qry, gal)
+        nn_idx_h = nn_idx.cpu().numpy()
+        y_pred, nn_dist_h = y_train[nn_idx_h], np.sqrt(nn_d2.cpu().numpy())
+    else:
+        y_pred, nn_idx_h, nn_dist_h = _knn_predict(ops, qry, gal, y_train, n_neighbors)
     acc = float((y_pred == y_test).mean()) if len(y_test) else float("nan")
-    return {"accuracy": acc, "y_pred": y_pred, "nn_index": nn_idx_h, "nn_dist": np.sqrt(nn_d2.cpu().numpy())}
+    return {"accuracy": acc, "y_pred": y_pred, "nn_index": nn_idx_h, "nn_dist": nn_dist_h}
 
 
 def feature_distance_matrix(features, born_years=None, photo_years=None, device=None) -> np.ndarray:

@@ -449,6 +449,45 @@ def nn1(queries, gallery):
     return idx, dist
 
 
+KNN_MAX_K = 16     # hsefr_knn's largest k (the selection kernel's per-lane list)
+
+
+def check_n_neighbors(k, ng=None) -> int:
+    """hsefr_knn's range of k, raised as ValueError before the library is called (scikit-learn raises for k > n_samples_fit too)."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise ValueError("n_neighbors must be an integer, got %r" % (k,))
+    if k < 1 or k > KNN_MAX_K:
+        raise ValueError("n_neighbors=%d must be in 1..%d" % (k, KNN_MAX_K))
+    if ng is not None and k > ng:
+        raise ValueError("n_neighbors=%d exceeds the %d gallery rows" % (k, ng))
+    return int(k)
+
+
+@_device_guarded
+def knn(queries, gallery, k: int, labels=None):
+    """The k nearest gallery rows of each query, sorted by (squared L2 distance, gallery index) -- exact ties to the lowest index --
+    and, with ``labels`` (int32 [ng]), their majority label, equal counts to the smallest label value (hsefr_knn).
+    Returns (index [nq,k] int32, dist2 [nq,k] float32, pred [nq] int32 or None)."""
+    k = check_n_neighbors(k, gallery.shape[0])               # before anything touches a device
+    torch = _lib.require_gpu()
+    _f32c(queries, "queries"), _f32c(gallery, "gallery")
+    nq, d = queries.shape
+    ng = gallery.shape[0]
+    if gallery.shape[1] != d:
+        raise ValueError("queries are %d-D, gallery is %d-D" % (d, gallery.shape[1]))
+    pred = None
+    if labels is not None:
+        if labels.dtype != torch.int32 or not labels.is_contiguous() or tuple(labels.shape) != (ng,) or labels.device != gallery.device:
+            raise ValueError("labels must be a contiguous int32 tensor of %d values on the gallery's device" % ng)
+        pred = torch.empty((nq,), dtype=torch.int32, device=queries.device)
+    idx = torch.empty((nq, k), dtype=torch.int32, device=queries.device)
+    dist = torch.empty((nq, k), dtype=torch.float32, device=queries.device)
+    _lib.check(_lib.lib().hsefr_knn(queries.data_ptr(), gallery.data_ptr(), nq, ng, d, k, idx.data_ptr(), dist.data_ptr(),
+                                    labels.data_ptr() if labels is not None else None, pred.data_ptr() if pred is not None else None,
+                                    _lib.current_stream_ptr()), "hsefr_knn")
+    return idx, dist, pred
+
+
 @_device_guarded
 def conv2d_direct(x, w_hwio, bias=None, alpha=None, stride: int = 1, padding: str = "VALID"):
     """Generic Conv2D + BiasAdd + optional PReLU (MTCNN nets).  padding: 'VALID' | 'SAME' (TensorFlow rule)."""

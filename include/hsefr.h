@@ -13,6 +13,8 @@
  *       -> hsefr_engine_destroy()
  *   - sklearn normalize + KNeighborsClassifier(1).kneighbors   facerec_test.py:401,200-207,422
  *       -> hsefr_l2_normalize() + hsefr_nn1()
+ *   - KNeighborsClassifier(3).fit / predict                    facerec_test.py:269-288 ('3-NN', '3-NN+PCA')
+ *       -> hsefr_knn()
  *   - misc.imresize / cv2.resize + BGR + mean   facerec_test.py:93-106 ; facial_analysis.py:95-107
  *       -> hsefr_preprocess_pil_u8() / hsefr_preprocess_cv_u8()
  *
@@ -555,6 +557,20 @@ int hsefr_l2_normalize(const float* x, float* y, int n, int d, hsefr_stream_t st
  * query row q [nq,d] the index (int32) and squared L2 distance of its nearest gallery row g [ng,d];
  * ties resolve to the lowest gallery index.  d multiple of 4. */
 int hsefr_nn1(const float* q, const float* g, int nq, int ng, int d, int* nn_index, float* nn_dist2,
+              hsefr_stream_t stream);
+/* KNeighborsClassifier(n_neighbors=k, p=2) with uniform weights (facerec_test.py:269-288, the '3-NN' rows): kneighbors and predict.
+ * Row i of nn_index [nq,k] (int32) holds the k gallery rows nearest to query i, of nn_dist2 [nq,k] (may be NULL) their squared L2
+ * distances, sorted ascending by (distance, gallery index): exact ties go to the lowest index at every position, the k-th / (k+1)-th
+ * boundary included -- hsefr_nn1's rule, and with k = 1 its output bit for bit.  (scikit-learn orders exactly tied rows by no index
+ * rule; the two agree wherever the distances are distinct in fp32.)  With g_label [ng] (int32, any values) pred [nq] receives the label
+ * with the most occurrences among the k neighbours, equal counts going to the smallest label VALUE -- scikit-learn's predict: with k = 3
+ * and three different labels that is the smallest of them, not the nearest row's.  g_label and pred are both given or both NULL.
+ * 1 <= k <= 16 and k <= ng (HSEFR_ERR_INVALID otherwise, where scikit-learn raises); d a multiple of 8; nq = 0 is HSEFR_OK.  Arguments
+ * are checked before any device call.  Searches of nq * ng * d >= 2^28 with d a multiple of 32 run on hsefr_nn1's split-f16 GEMM, the
+ * others on fp32 distance tiles; either way the k smallest of each row are selected from a stream-ordered slice of the distance
+ * matrix of at most 256 MiB (HSEFR_ERR_NOMEM when not even 64 rows of it can be had; a large search without the GEMM's workspace
+ * runs on the fp32 tiles and is counted by hsefr_nn1_fallbacks). */
+int hsefr_knn(const float* q, const float* g, int nq, int ng, int d, int k, int* nn_index, float* nn_dist2, const int* g_label, int* pred,
               hsefr_stream_t stream);
 /* Large searches run on the split-f16 GEMM and need a stream-ordered workspace; when even its smallest form cannot be allocated the
  * search runs on the workspace-free kernel instead (same nearest neighbours up to last-bit ties, far slower at 10^5 x 10^5).  This
