@@ -308,6 +308,8 @@ int launch_dwpw_f16s(const float* x, const float* wd, const float* dscale, const
                      const float* descale, const float* pshift, float* y, int n, int h, int w, int c, int stride, int pad_t,
                      int pad_l, int oh, int ow, int cout, int a_log2, int act, hipStream_t s);
 bool dwpw_f16s_supported(int c, int cout, int stride);
+bool dwpw_s2_covered(int c, int cout, int stride);      // the stride-2 block kernel of dwpw_f16s.hip (what HSEFR_OPF_DWPW_NEXT runs)
+bool dwpw_s2_off();                                     // dev builds: the "dwpw_s2_off" knob (always false in the product)
 int launch_stem_fused(const float* x, const float* cw, const float* cshift, const float* wd, const float* dscale,
                       const float* dshift, const void* wsplit, const float* descale, const float* pshift, float* y, int n,
                       int h, int w, int cpad_t, int cpad_l, int oh, int ow, int a_log2, int act, hipStream_t s);
@@ -359,6 +361,7 @@ void set_c11_tile(int v);
 void set_c11_bres(int v);
 void set_c11_adv(int v);
 int read_c11_stamps(void* host_out, size_t bytes);
+void set_dwpw_s2_off(int v);
 void set_dwpws_tw(int v);
 void set_dwpws_bn(int v);
 void set_pw_tile(int v);

@@ -22,6 +22,8 @@
 // per CU interleave their produce / contract phases, which overlaps the streaming with the MFMAs.
 // HBM traffic per patch: (TH*s+2) x (TW*s+2) x C in (halo re-reads hit L2; workgroup ids are XCD-remapped so that
 // neighbouring patches and the N-tiles of one patch share an L2) + 128 x Cout out.
+#include <type_traits>
+
 #include "common.h"
 
 namespace hsefr {
@@ -581,6 +583,282 @@ __global__ __launch_bounds__(256 + 64 * (BN == 256 ? 8 : 4), BN == 256 ? 1 : 2) 
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Stride-2 form (C = 128 -> Cout = 256: conv_dw_4 + conv_pw_4 of the MobileNets): one persistent workgroup per CU, four
+// PRODUCER waves and four CONSUMER waves, one of each per SIMD.
+//
+// A stride-2 patch re-reads only (2 T + 1)^2 / (2 T)^2 of its input, so nothing is gained by staging input pixels in LDS:
+// the producers stream the input through registers with dwconv.hip's sliding window -- a thread owns one channel quad of one
+// output column and two output rows, five input rows x three taps as 16-byte buffer loads from clamped addresses, padding as
+// zeroed tap weights and 0/1 row factors, the same multiply / fma chain in the same order -- and the loads of step g + 1 are
+// requested (into a second register set) before step g is computed.  The result goes through ReLU6, x 2^a_log2 and the f16
+// hi / lo split into a swizzled A stage in LDS, 64 pixels x 32 channels (8 KB), two stages.
+// The pointwise operand -- 256 split rows x 4 K-tiles = 128 KB -- is fetched ONCE per workgroup by LDS-DMA and stays: after
+// the prologue nothing but the activation crosses the CU's memory path.  The consumers contract step g (24 MFMAs per wave,
+// 64 x 64 of the patch's 64 x 256, pwconv_f16s.hip's products in its order) while the producers compute step g + 1: one
+// barrier per step.  A finished patch leaves through a wave-private 2 KB scratch (half a 32 x 32 block at a time) as whole
+// 128-byte lines, offsets out of range for pixels beyond the map.
+// LDS: 128 KB weights + 16 KB A ring + 8 KB epilogue scratch + 5.5 KB depthwise constants + 2 KB descale / shift = 159.5 KB.
+// The (patch, chunk) steps of a workgroup form one flat sequence: the first loads of the next patch are in flight under
+// the last MFMAs and the stores of the current one.  Patches are 8 x 8 output pixels: the 24 x 24 map tiles exactly (3 x 3); the
+// 28 x 28 map of the 224 plan takes 4 x 4 patches with a partial last row and column (12.5 % of its matrix work is padding).
+constexpr unsigned S2_GRID = 256;                            // persistent workgroups: one per CU of the MI355X
+constexpr int S2_C = 128, S2_COUT = 256, S2_KT = S2_C / 32, S2_T = 8, S2_M = S2_T * S2_T;
+constexpr int S2_B_ST = S2_COUT * ROWB;                      // one K-tile of the resident weight rows
+constexpr int S2_A_ST = S2_M * ROWB;
+constexpr int S2_SCR = 16 * ROWB;                            // a consumer's scratch: 16 rows of a 32 x 32 block
+constexpr int S2_A_OFF = S2_KT * S2_B_ST, S2_S_OFF = S2_A_OFF + 2 * S2_A_ST, S2_W_OFF = S2_S_OFF + 4 * S2_SCR;
+constexpr int S2_E_OFF = S2_W_OFF + 11 * S2_C * 4, S2_LDS = S2_E_OFF + 2 * S2_COUT * 4;
+static_assert(S2_LDS <= 160 * 1024, "LDS budget");
+
+template <int ACT>
+__global__ __launch_bounds__(512, 1) void dwpws2_f16s_kernel(DwPwSParams p) {
+    __shared__ __attribute__((aligned(1024))) unsigned char smem[S2_LDS];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x, (long long)p.nimg * p.H * p.W * S2_C * 4);
+    const __amdgpu_buffer_rsrc_t rw = make_rsrc(p.wsplit, (long long)S2_COUT * S2_C * 4);
+    const __amdgpu_buffer_rsrc_t ry = make_rsrc(p.y, (long long)p.nimg * p.OH * p.OW * S2_COUT * 4);
+    const unsigned OOB = 0xFFFFFFF0u;
+    {
+        // prologue: the resident operands.  Weight rows: 128 pieces of 8 rows x 128 B, swizzled source / linear destination
+        // (the fragment reads are then pwconv_f16s.hip's conflict-free ones); stage kt of the image holds K-tile kt of all 256 rows
+        const unsigned lds0 = (unsigned)(unsigned long long)(__attribute__((address_space(3))) unsigned char*)smem;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int pc = wave * 16 + j;
+            const int r = (pc & 31) * 8 + (lane >> 3);
+            const unsigned v = ((unsigned)r * (unsigned)S2_C + 4u * ((lane & 7) ^ ((r >> 1) & 7) ^ ((r & 1) << 2))) * 4u;
+            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(__builtin_amdgcn_readfirstlane(lds0 + pc * 1024)),
+                         "v"(v), "s"(rw), "s"(__builtin_amdgcn_readfirstlane((unsigned)(pc >> 5) * 128u))
+                         : "memory", "m0");
+        }
+        float4* wl = (float4*)(smem + S2_W_OFF);
+        for (int i = tid; i < 11 * (S2_C / 4); i += 512)
+            wl[i] = i < 9 * (S2_C / 4) ? p.wd[i] : (i < 10 * (S2_C / 4) ? p.dscale[i - 9 * (S2_C / 4)] : p.dshift[i - 10 * (S2_C / 4)]);
+        float* el = (float*)(smem + S2_E_OFF);
+        for (int i = tid; i < S2_COUT; i += 512) { el[i] = p.descale[i]; el[S2_COUT + i] = p.pshift[i]; }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    const unsigned nitem = (p.total - blockIdx.x + gridDim.x - 1) / gridDim.x;
+    const int nsteps = (int)(nitem * S2_KT);          // (even: the loops below take two steps per turn)
+    struct Item { int n, oh0, ow0; };
+    auto decode = [&](unsigned i) {                    // past the end: the last item again (prefetched, never consumed)
+        const unsigned lt = xcd_remap_dir(blockIdx.x + (i < nitem ? i : nitem - 1) * gridDim.x, p.total, p.reverse);
+        Item it;
+        const unsigned pr = fastdiv(lt, p.m_w);         // patch row index over all images
+        it.ow0 = (lt - pr * p.tiles_w) * S2_T;
+        it.n = fastdiv(pr, p.m_h);
+        it.oh0 = (pr - it.n * p.tiles_h) * S2_T;
+        return it;
+    };
+    typedef std::integral_constant<int, 0> S0;
+    typedef std::integral_constant<int, 1> S1;
+    __syncthreads();
+
+    if (wave < 4) {
+        // =============================== producer: sliding-window depthwise -> A stage ===============================
+        const int quad = tid & 7, col = (tid >> 3) & 7, row0 = 2 * wave;
+        const f32x4* wl = (const f32x4*)(smem + S2_W_OFF) + quad;
+        f32x4 xr[2][5][3];             // [register set][input row][tap column]
+        unsigned vo[5][3];             // the load cursor's patch: byte offsets of the 15 pieces (clamped: always inside the image)
+        float mk[3], rk[5];            // the compute cursor's patch: 0/1 factors of the tap columns and the input rows
+        unsigned pf_i = 0, ci = 0;
+        int pf_kc = 0, ckc = 0;
+        auto setup_loads = [&](unsigned i) {
+            const Item it = decode(i);
+            const int iw0 = min(it.ow0 + col, p.OW - 1) * 2 - p.pad_l;      // clamped: columns beyond the map are computed, never stored
+            const int cc[3] = {max(iw0, 0), min(max(iw0 + 1, 0), p.W - 1), min(iw0 + 2, p.W - 1)};
+            const int ih0 = (it.oh0 + row0) * 2 - p.pad_t;
+#pragma unroll
+            for (int a = 0; a < 5; ++a) {
+                const unsigned rb = (unsigned)((it.n * p.H + min(max(ih0 + a, 0), p.H - 1)) * p.W);
+#pragma unroll
+                for (int b = 0; b < 3; ++b) vo[a][b] = ((rb + (unsigned)cc[b]) * (unsigned)S2_C + 4u * quad) * 4u;
+            }
+        };
+        auto setup_factors = [&](unsigned i) {
+            const Item it = decode(i);
+            const int iw0 = min(it.ow0 + col, p.OW - 1) * 2 - p.pad_l;
+            mk[0] = iw0 >= 0 ? 1.f : 0.f;
+            mk[1] = (iw0 + 1 >= 0 && iw0 + 1 < p.W) ? 1.f : 0.f;
+            mk[2] = iw0 + 2 < p.W ? 1.f : 0.f;
+            const int ih0 = (it.oh0 + row0) * 2 - p.pad_t;
+#pragma unroll
+            for (int a = 0; a < 5; ++a) rk[a] = (ih0 + a >= 0 && ih0 + a < p.H) ? 1.f : 0.f;
+        };
+        auto gload = [&](auto SET) {      // the load cursor's step into register set SET
+            constexpr int S = decltype(SET)::value;
+            const unsigned so = (unsigned)pf_kc * 128u;
+#pragma unroll
+            for (int a = 0; a < 5; ++a)
+#pragma unroll
+                for (int b = 0; b < 3; ++b) xr[S][a][b] = bload16(rx, vo[a][b], so);
+            if (++pf_kc == S2_KT) {
+                pf_kc = 0;
+                setup_loads(++pf_i);
+            }
+        };
+        // f32x4 arithmetic; per element the operations of dwconv.hip in its order (tap weight x column factor, row sums as
+        // mul / fma / fma, rows as mul / fma / fma with the 0/1 row factors, scale + shift, ReLU6): bit-identical to it
+        auto produce = [&](auto SET, unsigned char* At) {
+            constexpr int S = decltype(SET)::value;
+            f32x4 wk[9];
+#pragma unroll
+            for (int i = 0; i < 9; ++i) wk[i] = wl[i * (S2_C / 4) + ckc * 8] * mk[i % 3];
+            const f32x4 dsc = wl[9 * (S2_C / 4) + ckc * 8], dsh = wl[10 * (S2_C / 4) + ckc * 8];
+            auto row_sum = [&](int a, int b) {
+                f32x4 t = xr[S][a][0] * wk[b];
+                t = __builtin_elementwise_fma(xr[S][a][1], wk[b + 1], t);
+                return __builtin_elementwise_fma(xr[S][a][2], wk[b + 2], t);
+            };
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const f32x4 sa = row_sum(2 * j, 0), sb = row_sum(2 * j + 1, 3), sc = row_sum(2 * j + 2, 6);
+                const float fb = rk[2 * j + 1], fc = rk[2 * j + 2];
+                f32x4 sum = sa * rk[2 * j];
+                sum = __builtin_elementwise_fma(sb, f32x4{fb, fb, fb, fb}, sum);
+                sum = __builtin_elementwise_fma(sc, f32x4{fc, fc, fc, fc}, sum);
+                const f32x4 o = __builtin_elementwise_fma(sum, dsc, dsh);
+                f32x4 v;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = relu6(o[e]);
+                v = v * p.a_scale;
+                const f16x4 hi = __builtin_convertvector(v, f16x4);
+                const f16x4 lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x4), f16x4);
+                const int R = (row0 + j) * S2_T + col;
+                *(f16x4*)(At + swzb(R, quad >> 1) + 8 * (quad & 1)) = hi;
+                *(f16x4*)(At + swzb(R, 4 + (quad >> 1)) + 8 * (quad & 1)) = lo;
+            }
+            if (++ckc == S2_KT) {
+                ckc = 0;
+                setup_factors(++ci);
+            }
+        };
+        setup_loads(0);
+        setup_factors(0);
+        gload(S0());
+        for (int t = 0; t < nsteps; t += 2) {
+            gload(S1());                                   // step t + 1 (past the end: the last patch again, never used)
+            produce(S0(), smem + S2_A_OFF);
+            __syncthreads();                               // step t is published; the consumers are done with step t - 1
+            gload(S0());
+            produce(S1(), smem + S2_A_OFF + S2_A_ST);
+            __syncthreads();
+        }
+    } else {
+        // =============================== consumer: MFMA + epilogue ===============================
+        const int cw = wave - 4;
+        const int li = lane & 31, lh = lane >> 5;
+        const int brow = cw * 64 + li;
+        const int erow = lane >> 3, ech = lane & 7;
+        f32x16 acc[2][2];
+        auto zero_acc = [&]() {
+#pragma unroll
+            for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+                for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+        };
+        auto epilogue = [&](const Item& cur) {
+            // lane (li, lh) holds row m = li, columns 4*lh + 8*(r >> 2) + (r & 3) of each 32 x 32 block (operands swapped); rows 0-15 and
+            // 16-31 of a block take turns in the scratch: 8 lanes read a row back, a store writes 8 rows x 128 B
+            unsigned char* scr = smem + S2_S_OFF + cw * S2_SCR;
+            const float* el = (const float*)(smem + S2_E_OFF);
+            unsigned sv[2][2][2];
+#pragma unroll
+            for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+                for (int hb = 0; hb < 2; ++hb)
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) {
+                        const int R = mi * 32 + hb * 16 + erow + 8 * i;
+                        const int oh = cur.oh0 + R / S2_T, ow = cur.ow0 + R % S2_T;
+                        sv[mi][hb][i] = (oh < p.OH && ow < p.OW)
+                                            ? ((unsigned)((cur.n * p.OH + oh) * p.OW + ow) * (unsigned)S2_COUT + (unsigned)(cw * 64 + 4 * ech)) * 4u
+                                            : OOB;
+                    }
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni) {
+                const int nl = cw * 64 + ni * 32 + 4 * ech;
+                const f32x4 ds = *(const f32x4*)(el + nl), sh = *(const f32x4*)(el + S2_COUT + nl);
+#pragma unroll
+                for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+                    for (int hb = 0; hb < 2; ++hb) {
+                        if ((li >> 4) == hb) {
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) {
+                                f32x4 v;
+#pragma unroll
+                                for (int e = 0; e < 4; ++e) v[e] = acc[mi][ni][4 * j + e];
+                                *(f32x4*)(scr + (li & 15) * 128 + 16 * ((2 * j + lh) ^ (li & 7))) = v;
+                            }
+                        }
+                        f32x4 rv[2];      // (both reads before the first store: a store is an asm statement the LDS reads do not cross)
+#pragma unroll
+                        for (int i = 0; i < 2; ++i) {
+                            const int r = erow + 8 * i;
+                            rv[i] = *(const f32x4*)(scr + r * 128 + 16 * (ech ^ (r & 7)));
+                        }
+#pragma unroll
+                        for (int i = 0; i < 2; ++i) {
+                            const f32x4 z = __builtin_elementwise_fma(rv[i], ds, sh);
+                            f32x4 o;
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) o[e] = apply_act<ACT>(z[e]);
+                            // (no non-temporal hint: the depthwise layer behind this one reads faster with the tensor in the caches, lesson 60)
+                            bstore16_welded(o, ry, sv[mi][hb][i], __builtin_amdgcn_readfirstlane((unsigned)(ni * 32) * 4u));
+                        }
+                    }
+            }
+        };
+        zero_acc();
+        Item cur = decode(0);
+        unsigned ci = 0;
+        int ckc = 0;
+        bool pending = false;             // the previous step closed a patch: its accumulators wait for their epilogue
+        for (int g = 0; g < nsteps; ++g) {
+            if (pending) {                // (ahead of the barrier: the stores leave while the producers finish step g)
+                epilogue(cur);
+                zero_acc();
+                cur = decode(++ci);
+                pending = false;
+            }
+            __syncthreads();              // step g is published
+            const unsigned char* As = smem + S2_A_OFF + (g & 1) * S2_A_ST;
+            const unsigned char* Bs = smem + ckc * S2_B_ST;
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                f16x8 ah[2], al[2], bh[2], bl[2];
+#pragma unroll
+                for (int mi = 0; mi < 2; ++mi) {
+                    ah[mi] = *(const f16x8*)(As + swzb(li + mi * 32, 2 * s + lh));
+                    al[mi] = *(const f16x8*)(As + swzb(li + mi * 32, 4 + 2 * s + lh));
+                }
+#pragma unroll
+                for (int ni = 0; ni < 2; ++ni) {
+                    bh[ni] = *(const f16x8*)(Bs + swzb(brow + ni * 32, 2 * s + lh));
+                    bl[ni] = *(const f16x8*)(Bs + swzb(brow + ni * 32, 4 + 2 * s + lh));
+                }
+#pragma unroll
+                for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+                    for (int ni = 0; ni < 2; ++ni) {
+                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[ni], al[mi], acc[mi][ni], 0, 0, 0);
+                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[ni], ah[mi], acc[mi][ni], 0, 0, 0);
+                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[ni], ah[mi], acc[mi][ni], 0, 0, 0);
+                    }
+            }
+            if (++ckc == S2_KT) { ckc = 0; pending = true; }
+        }
+        epilogue(cur);
+    }
+}
+
+HSEFR_KNOB(g_s2_off, 0);   // dev builds: 1 = stride-2 blocks the kernel above covers take the older routes (A/B timing, tests)
 HSEFR_KNOB(g_tw, 0);   // dev builds: 0 = auto, 8 | 16 = forced patch width
 HSEFR_KNOB(g_bn, 0);   // dev builds: 0 = auto, 64 | 128 | 256 = forced N tile
 
@@ -637,12 +915,39 @@ int launch_v3(DwPwSParams& p, int n, int act, hipStream_t s) {
     return launch_status("dwpw_f16split");
 }
 
+int launch_s2(DwPwSParams& p, int n, int act, hipStream_t s) {
+    p.tiles_w = (p.OW + S2_T - 1) / S2_T;
+    p.tiles_h = (p.OH + S2_T - 1) / S2_T;
+    p.tiles_n = 1;
+    const long long total = (long long)n * p.tiles_w * p.tiles_h;
+    HSEFR_REQUIRE(total < (1ll << 31) / 16, HSEFR_ERR_UNSUPPORTED, "dwpw_f16split: grid too large");
+    p.total = (unsigned)total;
+    auto magic = [](unsigned d) { return d == 1 ? 0u : (unsigned)((0x100000000ull + d - 1) / d); };
+    p.m_n = 0; p.m_w = magic(p.tiles_w); p.m_h = magic(p.tiles_h);
+    HSEFR_REQUIRE(total * (long long)(p.tiles_w > p.tiles_h ? p.tiles_w : p.tiles_h) < (1ll << 32), HSEFR_ERR_UNSUPPORTED,
+                  "dwpw_f16split: grid too large for the quotient multipliers");
+    const unsigned g = p.total < S2_GRID ? p.total : S2_GRID;
+#define HSEFR_DWPWS2(A) HSEFR_LAUNCH((dwpws2_f16s_kernel<A>), dim3(g), dim3(512), 0, s, p)
+    if (act == HSEFR_ACT_RELU6) HSEFR_DWPWS2(HSEFR_ACT_RELU6);
+    else if (act == HSEFR_ACT_RELU) HSEFR_DWPWS2(HSEFR_ACT_RELU);
+    else if (act == HSEFR_ACT_NONE) HSEFR_DWPWS2(HSEFR_ACT_NONE);
+    else { set_error("dwpw_f16split: act %d", act); return HSEFR_ERR_UNSUPPORTED; }
+#undef HSEFR_DWPWS2
+    return launch_status("dwpw_f16split");
+}
+
 }  // namespace
 
 #ifdef HSEFR_DEV
+void set_dwpw_s2_off(int v) { g_s2_off = v; }
 void set_dwpws_tw(int v) { g_tw = v; }
 void set_dwpws_bn(int v) { g_bn = v; }
 #endif
+
+bool dwpw_s2_off() { return g_s2_off != 0; }
+
+// shapes the stride-2 wave-specialised kernel covers (its LDS holds exactly this block's operands)
+bool dwpw_s2_covered(int c, int cout, int stride) { return stride == 2 && c == S2_C && cout == S2_COUT; }
 
 bool dwpw_f16s_supported(int c, int cout, int stride) {
     return c > 0 && c % 32 == 0 && cout > 0 && cout % 64 == 0 && (stride == 1 || stride == 2);
@@ -668,8 +973,8 @@ int launch_dwpw_f16s(const float* x, const float* wd, const float* dscale, const
     p.stamps = stamp_buffer(s);
 #endif
     const long long in_bytes = (long long)n * h * w * c * 4, out_bytes = (long long)n * oh * ow * cout * 4;
-    // wave-specialised LDS-DMA form (resident depthwise constants for up to 256 channels); everything else -- stride 2,
-    // more than 256 channels, cout % 128 != 0, tensors beyond 4 GB -- takes the general K-chunked kernel below
+    // wave-specialised LDS-DMA form (resident depthwise constants for up to 256 channels); everything else -- stride 2 (but for the
+    // 128 -> 256 block, below), more than 256 channels, cout % 128 != 0, tensors beyond 4 GB -- takes the general K-chunked kernel
     if (stride == 1 && c <= 256 && cout <= CMAX2 && cout % 128 == 0 && in_bytes < (1ll << 32) - 16 && out_bytes < (1ll << 32) - 16) {
         // patch shape: 8 x 16 or 16 x 8 output pixels, whichever wastes fewer (partial patches cost compute, not bytes)
         auto padded = [&](int tw) { const int th = 128 / tw; return (long long)((ow + tw - 1) / tw * tw) * ((oh + th - 1) / th * th); };
@@ -680,6 +985,9 @@ int launch_dwpw_f16s(const float* x, const float* wd, const float* dscale, const
         if (bn == 256) return tw == 16 ? launch_v3<16, 256, 2>(p, n, act, s) : launch_v3<8, 256, 2>(p, n, act, s);
         return tw == 16 ? launch_v3<16, 128, 3>(p, n, act, s) : launch_v3<8, 128, 3>(p, n, act, s);
     }
+    // stride 2, 128 -> 256 channels: the wave-specialised streaming form with resident weights (32-bit buffer offsets: same size guard)
+    if (dwpw_s2_covered(c, cout, stride) && !g_s2_off && in_bytes < (1ll << 32) - 16 && out_bytes < (1ll << 32) - 16)
+        return launch_s2(p, n, act, s);
     // N tile: 128 output channels (64 accumulator registers; the 256 variant spills); wider layers redo the depthwise
     // work once per N tile, the tiles of one patch running side by side on one XCD so that the re-read hits its L2
     int bn = cout % 128 == 0 ? 128 : 64;

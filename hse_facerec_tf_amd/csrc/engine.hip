@@ -321,7 +321,8 @@ static int validate_plan(const hsefr_plan_header& h, const hsefr_plan_buffer* bu
     // launch-level fusions (hsefr_op_flags): the pattern behind a flagged op must be exactly the one its fused launch computes
     for (uint32_t i = 0; i < h.n_ops; ++i) {
         const hsefr_plan_op& o = ops[i];
-        HSEFR_REQUIRE((o.flags & ~(HSEFR_OPF_PAIR_NEXT | HSEFR_OPF_HEADS | HSEFR_OPF_OUT_SUB2)) == 0, HSEFR_ERR_INVALID, "plan op %u: unknown flags 0x%x", i, o.flags);
+        HSEFR_REQUIRE((o.flags & ~(HSEFR_OPF_PAIR_NEXT | HSEFR_OPF_HEADS | HSEFR_OPF_OUT_SUB2 | HSEFR_OPF_DWPW_NEXT)) == 0, HSEFR_ERR_INVALID,
+                      "plan op %u: unknown flags 0x%x", i, o.flags);
         HSEFR_REQUIRE(!(o.flags & HSEFR_OPF_OUT_SUB2) || (o.flags & HSEFR_OPF_PAIR_NEXT), HSEFR_ERR_INVALID, "plan op %u: OUT_SUB2 without PAIR_NEXT", i);
         if (o.flags & HSEFR_OPF_PAIR_NEXT) {
             HSEFR_REQUIRE(i + 1 < h.n_ops, HSEFR_ERR_INVALID, "plan op %u: PAIR_NEXT on the last op", i);
@@ -342,6 +343,34 @@ static int validate_plan(const hsefr_plan_header& h, const hsefr_plan_buffer* bu
                           "plan op %u: PAIR_NEXT: the second output (buffer %d) aliases an operand of the first", i, b.out_buf);
             HSEFR_REQUIRE(conv1x1_pair_bf16_shape_supported(o.cin, o.cout, b.cout, c2), HSEFR_ERR_UNSUPPORTED,
                           "plan op %u: PAIR_NEXT %d -> %d -> %d (projection from %d) not covered", i, o.cin, o.cout, b.cout, c2);
+        }
+        if (o.flags & HSEFR_OPF_DWPW_NEXT) {
+            HSEFR_REQUIRE(o.flags == HSEFR_OPF_DWPW_NEXT && i + 1 < h.n_ops, HSEFR_ERR_INVALID, "plan op %u: DWPW_NEXT on the last op or beside another flag", i);
+            const hsefr_plan_op& b = ops[i + 1];
+            HSEFR_REQUIRE(o.kind == HSEFR_OP_DWCONV3X3 && o.stride == 2 && o.act == HSEFR_ACT_RELU6 && o.aux == 0 && o.cout == o.cin &&
+                              b.kind == HSEFR_OP_PWCONV_F16S && b.in_buf == o.out_buf && b.flags == 0 && b.h == o.oh && b.w == o.ow && b.oh == b.h &&
+                              b.ow == b.w && b.cin == o.cin && b.aux > 0 && b.aux <= 12,
+                          HSEFR_ERR_INVALID, "plan op %u: DWPW_NEXT needs a stride-2 depthwise 3x3 with ReLU6 and fp32 output, and behind it a split-f16 "
+                          "pointwise op without flags that reads it at the same pixels (a_log2 in [1, 12])", i);
+            HSEFR_REQUIRE(dwpw_s2_covered(o.cin, b.cout, o.stride), HSEFR_ERR_INVALID, "plan op %u: DWPW_NEXT %d -> %d channels not covered (128 -> 256)", i,
+                          o.cin, b.cout);
+            HSEFR_REQUIRE(b.out_buf != o.out_buf, HSEFR_ERR_INVALID, "plan op %u: DWPW_NEXT: the second output (buffer %d) aliases the depthwise tensor", i,
+                          b.out_buf);
+            // the usual two-buffer plan recycles the depthwise INPUT's buffer for the second output: the one launch then writes into the
+            // (unwritten) depthwise buffer instead and the forward goes on with the two buffers' roles exchanged (run_ops) -- sound only
+            // if they hold the same number of bytes
+            HSEFR_REQUIRE(b.out_buf != o.in_buf || (uint64_t)bufs[o.in_buf].elems_per_image * bufs[o.in_buf].elem_bytes ==
+                                                       (uint64_t)bufs[o.out_buf].elems_per_image * bufs[o.out_buf].elem_bytes,
+                          HSEFR_ERR_INVALID, "plan op %u: DWPW_NEXT: buffers %d and %d exchange roles and must have one size", i, o.in_buf, o.out_buf);
+            // the depthwise tensor is never written: nothing but the second op may read it before the buffer's next writer, and it is no output
+            for (uint32_t k = i + 2; k < h.n_ops; ++k) {
+                HSEFR_REQUIRE(ops[k].in_buf != o.out_buf && ops[k].res_buf != o.out_buf, HSEFR_ERR_INVALID,
+                              "plan op %u: DWPW_NEXT: op %u also reads the depthwise tensor (buffer %d)", i, k, o.out_buf);
+                if (ops[k].out_buf == o.out_buf) break;
+            }
+            for (int sl = 0; sl < HSEFR_N_OUTPUT_SLOTS; ++sl)
+                HSEFR_REQUIRE(h.out_buffer[sl] != o.out_buf && (b.out_buf != o.in_buf || h.out_buffer[sl] != o.in_buf), HSEFR_ERR_INVALID,
+                              "plan op %u: DWPW_NEXT: the depthwise tensor (or the buffer it exchanges roles with) is output slot %d", i, sl);
         }
         if (o.flags & HSEFR_OPF_HEADS) {
             HSEFR_REQUIRE(i + 3 < h.n_ops, HSEFR_ERR_INVALID, "plan op %u: HEADS needs three ops behind it", i);
@@ -510,6 +539,7 @@ int hsefr_debug_set(const char* key, int value) {
     if (!strcmp(key, "dw_look2")) { set_dw_look2(value); return HSEFR_OK; }
     if (!strcmp(key, "sweep_alternate")) { g_sweep_alternate = value; return HSEFR_OK; }
     if (!strcmp(key, "clock_mode")) { set_clock_mode(value); return HSEFR_OK; }
+    if (!strcmp(key, "dwpw_s2_off")) { set_dwpw_s2_off(value); return HSEFR_OK; }
     if (!strcmp(key, "dwpws_tw")) { set_dwpws_tw(value); return HSEFR_OK; }
     if (!strcmp(key, "dwpws_bn")) { set_dwpws_bn(value); return HSEFR_OK; }
     if (!strcmp(key, "pw_ablate")) { set_pw_ablate(value); return HSEFR_OK; }
@@ -682,8 +712,10 @@ int hsefr_engine_op_times_ms(hsefr_engine* e, int slot, float* ms, int n_ops) {
 }
 
 // Launch the needed ops of the plan for a batch of n on stream s (plain launches: also what a graph capture records).
-static int run_ops(hsefr_engine* e, const std::vector<void*>& tab, const void* d_input, int n, const std::vector<char>& needed,
-                   hipStream_t s, hipEvent_t* pev, bool input_u8 = false) {
+// every_tensor: the all-layers debug forward -- a launch that would leave a tensor of the plan unwritten (HSEFR_OPF_DWPW_NEXT) is not used.
+static int run_ops(hsefr_engine* e, const std::vector<void*>& tab_in, const void* d_input, int n, const std::vector<char>& needed,
+                   hipStream_t s, hipEvent_t* pev, bool input_u8 = false, bool every_tensor = false) {
+    std::vector<void*> tab(tab_in);      // (this forward's own copy: a DWPW_NEXT launch may exchange two buffers' roles)
     const bool prof = pev != nullptr;
     unsigned launches = 0;     // (a launch that covers several ops -- hsefr_op_flags -- counts once: the op behind it must still sweep the other way)
     if (prof) HSEFR_HIP_CHECK(hipEventRecord(pev[0], s));
@@ -724,6 +756,19 @@ static int run_ops(hsefr_engine* e, const std::vector<void*>& tab, const void* d
                                     (const float*)blob_ptr(e, g.shift_off), (float*)out, (float*)tab[a.out_buf], (float*)tab[sm.out_buf],
                                     (float*)tab[g.out_buf], n, o.cin, a.cout, s);
             covered = 3;
+        } else if ((o.flags & HSEFR_OPF_DWPW_NEXT) && !every_tensor && !dwpw_s2_off() && needed[i + 1]) {
+            // stride-2 depthwise -> split-f16 pointwise in one launch (csrc/dwpw_f16s.hip; the pattern was checked by validate_plan): the
+            // depthwise tensor stays on the CU and its buffer is not written
+            const hsefr_plan_op& b = e->ops[i + 1];
+            // where the plan recycles the launch's INPUT buffer for the second output (two ping-pong buffers), the result goes into the
+            // depthwise tensor's buffer, which this launch leaves unused, and from here on the two buffers stand for each other
+            // (same size, neither an output slot, the depthwise tensor read by nobody else: validate_plan)
+            if (b.out_buf == o.in_buf) std::swap(tab[o.in_buf], tab[o.out_buf]);
+            rc = launch_dwpw_f16s((const float*)in, (const float*)blob_ptr(e, o.w_off), (const float*)blob_ptr(e, o.scale_off),
+                                  (const float*)blob_ptr(e, o.shift_off), blob_ptr(e, b.w_off), (const float*)blob_ptr(e, b.scale_off),
+                                  (const float*)blob_ptr(e, b.shift_off), (float*)tab[b.out_buf], n, o.h, o.w, o.cin, o.stride, o.pad_t, o.pad_l,
+                                  o.oh, o.ow, b.cout, b.aux, b.act, s);
+            covered = 1;
         } else
         switch (o.kind) {
             case HSEFR_OP_CONV_C3:
@@ -989,7 +1034,7 @@ static int engine_forward(hsefr_engine* e, const void* d_input, bool input_u8, i
         }
         for (int sl = 0; sl < HSEFR_N_OUTPUT_SLOTS; ++sl)                             // an unaligned slot ahead of an aligned one of the same buffer
             if (outs[sl] && src_of[sl] == e->d_bufs[e->hdr.out_buffer[sl]]) src_of[sl] = tab[e->hdr.out_buffer[sl]];
-        const int rc = run_ops(e, tab, d_input, n, needed, s, prof ? pev : nullptr, input_u8);
+        const int rc = run_ops(e, tab, d_input, n, needed, s, prof ? pev : nullptr, input_u8, mask == 0);
         if (rc != HSEFR_OK) return rc;
         for (int sl = 0; sl < HSEFR_N_OUTPUT_SLOTS; ++sl)
             if (outs[sl] && src_of[sl])
@@ -1019,7 +1064,10 @@ int hsefr_plan_describe(const void* plan, size_t plan_bytes, int n, char* out, s
         // op i alone, then with the ops its flags cover (a flagged op's launch needs them `needed`)
         std::fill(only.begin(), only.end(), 0);
         only[i] = 1;
-        const size_t span = (e.ops[i].flags & HSEFR_OPF_PAIR_NEXT) ? 1 : (e.ops[i].flags & HSEFR_OPF_HEADS) ? 3 : 0;
+        const size_t span = (e.ops[i].flags & HSEFR_OPF_PAIR_NEXT)                      ? 1
+                            : (e.ops[i].flags & HSEFR_OPF_HEADS)                        ? 3
+                            : ((e.ops[i].flags & HSEFR_OPF_DWPW_NEXT) && !dwpw_s2_off()) ? 1
+                                                                                        : 0;
         for (size_t k = 1; k <= span && i + k < e.ops.size(); ++k) only[i + k] = 1;
         std::string line = std::to_string(i) + "\t" + std::to_string(e.ops[i].kind) + "\t";
         g_route_sink = &line;

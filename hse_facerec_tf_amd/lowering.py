@@ -48,7 +48,7 @@ NO_OFFSET = 0xFFFFFFFFFFFFFFFF
 _HEADER = struct.Struct("<QIIIIII3i3IQ")          # hsefr_plan_header
 _BUFFER = struct.Struct("<QII")                   # hsefr_plan_buffer
 _OP = struct.Struct("<II3i3i3i3i2iii5Q")         # hsefr_plan_op (112 bytes; `flags` sits where the struct's padding was until round 6)
-OPF_PAIR_NEXT, OPF_HEADS, OPF_OUT_SUB2 = 1, 2, 4  # hsefr_op_flags
+OPF_PAIR_NEXT, OPF_HEADS, OPF_OUT_SUB2, OPF_DWPW_NEXT = 1, 2, 4, 8  # hsefr_op_flags
 # hsefr_plan_op.aux: the geometry word (shift, width of each field), PWCONV_PS_DW's out_log2, STEM3_F16S's in_log2 and uint8 bit,
 # STEM7X7_POOL_BF16's pool pads
 AUX_C2_SHIFT, AUX_C2_BITS, AUX_STRIDE2_SHIFT, AUX_STRIDE2_BITS = 0, 12, 12, 2
@@ -71,7 +71,7 @@ PRODUCT_KERNEL_FAMILIES = frozenset({
     # MobileNet (fp32-grade): stems, depthwise, pointwise GEMMs, fused blocks, pool, heads
     "stem5_stream_kernel", "stem4_fused_kernel", "stem3_fused_kernel", "stem2_fused_kernel", "conv3x3_c3_kernel", "conv3x3_c3_mfma_kernel",
     "dwconv3x3_kernel", "pwconv_f32_dma_kernel", "pwconv_f32_kernel", "pwconv_f16s_kernel", "pwconv_ps_kernel", "dwpw_fused_kernel",
-    "dwpw_f16s_kernel", "dwpw2_f16s_kernel", "dwpw3_f16s_kernel", "gap_kernel", "dense_kernel", "softmax_kernel", "heads_kernel",
+    "dwpw_f16s_kernel", "dwpw2_f16s_kernel", "dwpw3_f16s_kernel", "dwpws2_f16s_kernel", "gap_kernel", "dense_kernel", "softmax_kernel", "heads_kernel",
     # ResNet (bf16, and the fp32-grade mode)
     "stem7s_stream_kernel", "stem7x7_pool_bf16_kernel", "stem7x7_bf16_kernel", "maxpool3x3s2_bf16_kernel", "conv_bf16_kernel", "conv1x1_bf16_kernel",
     "conv1x1_w4_bf16_kernel", "conv1x1_pair_bf16_kernel", "conv3x3_w2_bf16_kernel", "conv_dma_bf16_kernel", "gap_bf16_kernel",
@@ -865,6 +865,12 @@ def assign_buffers(layers: List[Layer], pinned) -> List[int]:
         for j in range(i + 1):
             if last_use[j] == i and j not in pinned and layers[j].out_buf not in free:
                 free.append(layers[j].out_buf)
+    # OPF_DWPW_NEXT keeps the plain assignment (no third buffer): where the pointwise output recycles the depthwise INPUT's buffer, the
+    # engine's one launch writes into the depthwise tensor's buffer instead and exchanges the two buffers' roles -- they must be one size
+    for i, L in enumerate(layers):
+        if L.flags & OPF_DWPW_NEXT and L.src >= 0 and i + 1 < len(layers) and layers[i + 1].out_buf == layers[L.src].out_buf:
+            a, b = layers[L.src].out_buf, L.out_buf
+            buffers[a] = buffers[b] = max(buffers[a], buffers[b])
     return buffers
 
 
@@ -1156,7 +1162,9 @@ def fuse_stem2(layers: List[Layer], keep: Sequence[int]) -> Tuple[List[Layer], D
 
 # (channels in, channels out) of the stride-1 blocks for which one fused kernel beats depthwise + GEMM on MI355X at the
 # BASELINE batch sizes (tools/kbench.py blk): the HBM-bound middle of the network.  Deeper blocks are MFMA-bound (fusing
-# only serialises the depthwise in front of the contraction), the stride-2 ones would need a 4x larger halo in LDS.
+# only serialises the depthwise in front of the contraction).  A stride-2 block whose input patch is STAGED IN LDS would need a 4x
+# larger halo there; that argument holds for LDS-staged patches only -- the stride-2 128 -> 256 block streams its input through
+# registers instead (csrc/dwpw_f16s.hip, dwpws2_f16s_kernel) and is fused at launch level: mark_dwpw_pairs below.
 BLOCK_F16S_AUTO = ((128, 128), (256, 256))
 
 
@@ -1184,6 +1192,30 @@ def fuse_block_f16s(layers: List[Layer], keep: Sequence[int], which: str) -> Tup
                            w2=pw.w, shift2=pw.shift, a_log2=pw.a_log2)
             drop.add(i)
     return rebuild(layers, drop, put)
+
+
+def dwpw_pair_covered(dw: Layer, pw: Layer) -> bool:
+    """Shapes the stride-2 depthwise -> pointwise launch covers (csrc/dwpw_f16s.hip, dwpw_s2_covered): 128 -> 256 channels."""
+    return dw.stride == 2 and dw.in_shape[2] == 128 and pw.out_shape[2] == 256
+
+
+def mark_dwpw_pairs(layers: List[Layer], keep: Sequence[int]) -> int:
+    """Launch-level fusion of a STANDALONE stride-2 depthwise layer (ReLU6, fp32 output, not pre-split) with the split-f16 pointwise
+    layer behind it, its sole reader: both layers stay in the plan, the depthwise carries OPF_DWPW_NEXT and the engine runs the two as
+    one launch in which the depthwise tensor never reaches HBM (bit-identical to the two launches).  In the MobileNet plans that is
+    conv_dw_4 -> conv_pw_4.  Call after the fusion passes.  Returns the number of pairs marked."""
+    consumers = consumers_of(layers)
+    n = 0
+    for i, dw in enumerate(layers):
+        j = sole_reader(consumers, i, keep)
+        if not (dw.kind == OP_DWCONV3X3 and dw.act == ACT_RELU6 and dw.out_split == 0 and dw.flags == 0 and j == i + 1):
+            continue
+        pw = layers[j]
+        if (pw.kind == OP_PWCONV_F32 and 0 < pw.a_log2 <= 12 and not pw.in_split and pw.flags == 0 and pw.res < 0 and
+                tuple(pw.in_shape) == tuple(dw.out_shape) and dwpw_pair_covered(dw, pw)):
+            dw.flags |= OPF_DWPW_NEXT
+            n += 1
+    return n
 
 
 def choose_pointwise_math(layers: List[Layer], pw_math: str) -> None:
@@ -1283,7 +1315,8 @@ def lower_graph(g: Graph, input_tensor: str, outputs: Dict[int, str], input_hw: 
                 feeds: Optional[Dict[str, object]] = None, fuse: bool = True, dtype: str = "f32",
                 pw_math: Optional[str] = None, fuse_stem_block: Optional[bool] = None, stem_fusion: Optional[str] = None,
                 block_fusion: Optional[str] = None, presplit: Optional[str] = None, input_bound: Optional[float] = None,
-                pwdw_fusion: Optional[str] = None, u8_mean_bgr: Optional[Sequence[float]] = None, launch_fusion: bool = True) -> Plan:
+                pwdw_fusion: Optional[str] = None, u8_mean_bgr: Optional[Sequence[float]] = None, launch_fusion: bool = True,
+                s2_fusion: Optional[str] = None) -> Plan:
     """outputs: {slot: 'tensor:0'}.  feeds: constant feeds such as the Keras learning phase.
     fuse: merge depthwise -> pointwise pairs into one kernel where a fused kernel covers the shape.  stem_fusion:
     'stem2' (default) = conv1 + block 1 + the depthwise of block 2 in one
@@ -1308,6 +1341,9 @@ def lower_graph(g: Graph, input_tensor: str, outputs: Dict[int, str], input_hw: 
     average pool the same way: fuse_pwgap); 'none'.
     launch_fusion (default True): groups of adjacent ops the engine runs as one launch (hsefr_op_flags: mark_pairs on bf16 plans, mark_heads
     for the age / gender heads); False keeps one launch per op.
+    s2_fusion: 'auto' (default) = a standalone stride-2 depthwise layer whose only reader is a split-f16 pointwise layer of a covered
+    shape (128 -> 256 channels: conv_dw_4 -> conv_pw_4) runs with it as one launch (mark_dwpw_pairs; the layer list does not change);
+    'none' = two launches.
     dtype 'f32': the MobileNet kernels (exact fp32); 'bf16': ResNet-style graphs on the bf16-MFMA kernels
     (general KxK Conv2D, Pad, FusedBatchNorm / Mul+Add, residual Add, MaxPool 3x3/2, global AvgPool / Mean); 'f32g': the
     same ResNet-style graph patterns on exact-fp32 kernels (OP_CONV_F32 / OP_MAXPOOL_F32 / OP_GAP) -- the fp32-grade mode
@@ -1431,5 +1467,10 @@ def lower_graph(g: Graph, input_tensor: str, outputs: Dict[int, str], input_hw: 
             compact_pair_outputs(layers, keep())
         if dtype == "f32":
             mark_heads(layers)
+    s2_fusion = s2_fusion or "auto"
+    if s2_fusion not in ("auto", "none"):
+        raise ValueError("s2_fusion must be 'auto' or 'none', not %r" % (s2_fusion,))
+    if fuse and launch_fusion and dtype == "f32" and s2_fusion == "auto":
+        mark_dwpw_pairs(layers, keep())
     buffers = assign_buffers(layers, set(keep()))
     return Plan(layers, (input_hw[0], input_hw[1], low.in_c), buffers, out_layers, tensor_layer)

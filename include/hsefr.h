@@ -172,11 +172,19 @@ typedef enum hsefr_op_flags {
                                 product (csrc/conv1x1_pair_bf16.hip): ResNet-50's increase -> next reduce in the 56-pixel stage          */
     HSEFR_OPF_HEADS = 2,     /* DENSE k -> 256 + ReLU followed by DENSE 256 -> A (<= 128) + bias, SOFTMAX over it, and DENSE 256 -> 1 +
                                 sigmoid: the age / gender heads of facial_analysis.py:109 in one launch (csrc/pool_dense.hip)         */
-    HSEFR_OPF_OUT_SUB2 = 4   /* with PAIR_NEXT only: the flagged op's OWN output is stored at the pixels with even row and column only --
+    HSEFR_OPF_OUT_SUB2 = 4,  /* with PAIR_NEXT only: the flagged op's OWN output is stored at the pixels with even row and column only --
                                 oh = (h + 1) / 2, ow = (w + 1) / 2 describe the stored map -- while the covered op reads all h x w pixels
                                 from registers: the tensor's only other reader takes every second pixel of it (the shortcut of a ResNet
                                 stage's last block, lowering.compact_pair_outputs).  Such a pair has no two-launch form: a forward that
                                 cannot run it as one launch fails                                                                      */
+    HSEFR_OPF_DWPW_NEXT = 8  /* DWCONV3X3 with stride 2, ReLU6 and fp32 output whose tensor ONLY the next op reads, a PWCONV_F16S at the
+                                same pixels without flags, with a shape csrc/dwpw_f16s.hip's stride-2 kernel covers (128 -> 256
+                                channels): both in one launch, the depthwise tensor never written (MobileNet's conv_dw_4 -> conv_pw_4;
+                                bit-identical to the two launches).  Where the second output recycles the depthwise INPUT's buffer, the
+                                launch writes into the depthwise tensor's buffer and the rest of that forward uses the two buffers in
+                                each other's place (they must have one size; neither is an output): see hsefr_engine_buffer.  An
+                                all-layers forward (no output pointers) runs the two ops separately, so the depthwise tensor still
+                                exists there.  Added within version 141: a flag bit, not a layout change                              */
 } hsefr_op_flags;
 
 /* hsefr_plan_op.aux, the per-kind aux word.  PWCONV_F16S, PWCONV_PS, PWCONV_PS_GAP, DWPW_F16S, STEM_F16S, STEM2_F16S: a_log2 alone (the
@@ -304,9 +312,12 @@ int hsefr_engine_forward_u8(hsefr_engine* e, const void* d_input_u8, int n, void
  * parity tests.  NULL if `buffer` is out of range.  NOT for the buffers behind the plan's OUTPUT slots: a forward that
  * was given an aligned output pointer writes that tensor into the caller's memory instead, and the engine's buffer keeps
  * whatever an earlier forward left there (run the forward with all three output pointers NULL to have every op write the
- * engine's own buffers -- what Engine.forward_all_layers does). */
+ * engine's own buffers -- what Engine.forward_all_layers does).  In a plan with an HSEFR_OPF_DWPW_NEXT op, a forward WITH output
+ * pointers may leave the tensors behind that op in the other one of two activation buffers than the plan names (the flag's comment):
+ * only after an all-layers forward does every buffer hold the tensor the plan assigns to it. */
 void* hsefr_engine_buffer(hsefr_engine* e, int buffer);
-/* Asynchronous device-to-device copy of the first `bytes` of an activation buffer into d_dst. */
+/* Asynchronous device-to-device copy of the first `bytes` of an activation buffer into d_dst.  The same restriction: in a plan with an
+ * HSEFR_OPF_DWPW_NEXT op, meaningful after an all-layers forward only. */
 int hsefr_engine_copy_buffer(hsefr_engine* e, int buffer, void* d_dst, size_t bytes, hsefr_stream_t stream);
 
 /* Per-op device time: with depth > 0 every forward records HIP events around each launch on

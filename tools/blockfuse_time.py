@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""MobileNet-192 batch 256 (or KN_WHAT=agegender: 224 x 224 x 512) with block_fusion = auto | all: ms / step and the per-op table."""
+"""MobileNet-192 batch 256 (or KN_WHAT=agegender: 224 x 224 x 512) with block_fusion = auto | all: ms / step and the per-op table.
+A mode may carry the stride-2 launch fusion switch after a colon (lower_graph s2_fusion): auto:none = the default plan with conv_dw_4
+and conv_pw_4 as two launches, auto:auto (= auto) = as one (its time is then the depthwise op's, the pointwise op's reads 0)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -13,7 +15,9 @@ B, hw = (512, 224) if ag else (256, 192)
 x = torch.from_numpy(rs.uniform(-128, 128, (B, hw, hw, 3)).astype(np.float32)).cuda()
 outs = {}
 for mode in sys.argv[1:] or ["auto", "all"]:
-    plan = lowering.lower_graph(read_graph(AGE_GENDER_PB), "input_1:0", {0: "global_pooling/Mean:0"}, (hw, hw), input_bound=256.0, block_fusion=mode)
+    bf, _, s2 = mode.partition(":")
+    plan = lowering.lower_graph(read_graph(AGE_GENDER_PB), "input_1:0", {0: "global_pooling/Mean:0"}, (hw, hw), input_bound=256.0, block_fusion=bf,
+                                s2_fusion=s2 or "auto")
     eng = Engine(plan, max_batch=B)
     for _ in range(5): y = eng.forward(x, (0,))
     torch.cuda.synchronize(); t0 = time.perf_counter()
