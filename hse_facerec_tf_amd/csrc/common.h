@@ -160,10 +160,14 @@ void set_sweep_reverse(int v);
 // Tuning knobs exist in DEVELOPMENT builds only (build.sh with HSEFR_DEV=1 -> -DHSEFR_DEV: hsefr_debug_set, devtools.hip,
 // tools/kbench.py).  In the product library every knob is a compile-time constant: the measured-best value, no
 // process-global mutable state, and the variants behind the other values are not even compiled.
+// HSEFR_KNOB(variable, "key", value[, fix]): in development builds an int that hsefr_debug_set finds by its key (the line registers
+// itself in engine.hip's table; `fix`, an int(int), maps a requested value to the one stored).  The comment on that line says what
+// the key means.
 #ifdef HSEFR_DEV
-#define HSEFR_KNOB(name, value) int name = value
+int knob_register(const char* key, int* variable, int value, int (*fix)(int) = nullptr);     // returns `value`
+#define HSEFR_KNOB(name, key, value, ...) int name = knob_register(key, &name, value, ##__VA_ARGS__)
 #else
-#define HSEFR_KNOB(name, value) constexpr int name = value
+#define HSEFR_KNOB(name, key, value, ...) constexpr int name = value
 #endif
 
 // --- launchers implemented in the .hip files (same ones the engine calls) -------------
@@ -353,48 +357,13 @@ unsigned long long* stamp_buffer(hipStream_t s);
 #define STEM_STAMP_FLUSH(buf, lane, wave) do { } while (0)
 #endif
 #ifdef HSEFR_DEV
-void set_stem4_grid(int v);
-void set_stem5_grid(int v);
-void set_stem5_segs(int v);
-void set_c11(int v);
-void set_c11_tile(int v);
-void set_c11_bres(int v);
-void set_c11_adv(int v);
 int read_c11_stamps(void* host_out, size_t bytes);
-void set_dwpw_s2_off(int v);
-void set_dwpws_tw(int v);
-void set_dwpws_bn(int v);
-void set_pw_tile(int v);
-void set_pws_tile(int v);
-void set_ps_mb(int v);
-void set_ps_grid(int v);
-void set_psdw_mode(int v);
-void set_cd_rb(int v);
-void set_w3_off(int v);
-void set_w2_off(int v);
-void set_w4_off(int v);
-void set_w4_bres(int v);
-void set_pair_off(int v);
-void set_stem7s(int v);
-void set_pair_ablate(int v);
-void set_pair_nt(int v);
-void set_nn1_y_mb(int v);
 int read_w4_stamps(void* host_out, size_t bytes);
 int read_s7_stamps(void* host_out, size_t bytes);
 int read_w2_stamps(void* host_out, size_t bytes);
 int read_w3_stamps(void* host_out, size_t bytes);
 int read_cd_stamps(void* host_out, size_t bytes);
-void set_cd_off(int v);
 int read_ps_stamps(void* host_out, size_t bytes);
-void set_pw_ablate(int v);
-void set_pw_dma(int v);
-void set_dw_th(int v);
-void set_dw_variant(int v);
-void set_dw_look(int v);
-void set_dw_look2(int v);
-void set_copy_variant(int v);
-void set_clock_mode(int v);
-void set_c3_impl(int v);
 int launch_clock_probe(unsigned long long* out, int blocks, int iters, hipStream_t s);
 int launch_copy(const void* src, void* dst, size_t bytes, hipStream_t s);
 #endif

@@ -357,8 +357,8 @@ __global__ __launch_bounds__(256, OCC) void conv1x1_bf16_kernel(const u16* __res
     C11_STAMP_FLUSH;
 }
 
-HSEFR_KNOB(g_c11_bres, 1);   // dev builds: 0 = reload the weight tile every step also where it could stay resident (A/B timing)
-HSEFR_KNOB(g_c11_adv, 1);    // 1 = always BM: the product's tiling; dev builds: 0 = choose_adv's estimate, other = that many rows.
+HSEFR_KNOB(g_c11_bres, "c11_bres", 1);   // dev builds: 0 = reload the weight tile every step also where it could stay resident (A/B timing)
+HSEFR_KNOB(g_c11_adv, "c11_adv", 1);    // 1 = always BM: the product's tiling; dev builds: 0 = choose_adv's estimate, other = that many rows.
                              // MEASURED AND LOST (round 6, ResNet-50 batch 128 in the network, same box): the 14 x 14 x 1024 increase layers as
                              // 2048 tiles of 98 own rows (4.0 rounds of 512 slots) 35.5 us against 32.5 us as 1568 tiles of 128 (3.06 rounds);
                              // 112 and 120 rows: 32.3-33.7; the 28 x 28 x 512 layers 45-47 against 43-44.  The "3.06 rounds cost 4" reading of
@@ -439,8 +439,8 @@ int launch_proj_cfg(const u16* x, const u16* wt, const float* scale, const float
     return launch_status("conv1x1_proj_bf16");
 }
 
-HSEFR_KNOB(g_c11_tile, 0);   // dev builds: 1 = 128 x 64 tiles (three workgroups per CU) everywhere, 2 = 128 x 128 everywhere
-HSEFR_KNOB(g_c11, 1);   // dev builds: 0 = route 1x1 stride-1 layers through the general conv_bf16 kernel (A/B timing)
+HSEFR_KNOB(g_c11_tile, "c11_tile", 0);   // dev builds: 1 = 128 x 64 tiles (three workgroups per CU) everywhere, 2 = 128 x 128 everywhere
+HSEFR_KNOB(g_c11, "c11", 1);   // dev builds: 0 = route 1x1 stride-1 layers through the general conv_bf16 kernel (A/B timing)
 
 }  // namespace
 
@@ -456,10 +456,6 @@ int read_c11_stamps(void* host_out, size_t bytes) {
     return HSEFR_ERR_UNSUPPORTED;
 #endif
 }
-void set_c11(int v) { g_c11 = v; }
-void set_c11_tile(int v) { g_c11_tile = v; }
-void set_c11_bres(int v) { g_c11_bres = v; }
-void set_c11_adv(int v) { g_c11_adv = v; }
 #endif
 bool conv1x1_bf16_enabled(bool has_res, int k, int cout) {
     switch (g_c11) {      // values > 1: bisection aids

@@ -344,9 +344,9 @@ __global__ __launch_bounds__(WAVES * 64) void conv1x1_pair_bf16_kernel(PairParam
     }
 }
 
-HSEFR_KNOB(g_pair_off, 0);     // dev builds: 1 = the engine never pairs (A/B timing against the two launches)
-HSEFR_KNOB(g_pair_ablate, 0);  // dev builds: PairParams::ablate
-HSEFR_KNOB(g_pair_nt, 1);      // PairParams::nt.  1 = y1 with the non-temporal hint: 410 MB of y1 + residual stream through a pair while the NEXT launch
+HSEFR_KNOB(g_pair_off, "pair_off", 0);     // dev builds: 1 = the engine never pairs (A/B timing against the two launches)
+HSEFR_KNOB(g_pair_ablate, "pair_ablate", 0);  // dev builds: PairParams::ablate
+HSEFR_KNOB(g_pair_nt, "pair_nt", 1);      // PairParams::nt.  1 = y1 with the non-temporal hint: 410 MB of y1 + residual stream through a pair while the NEXT launch
                                // (a 3x3) reads only the 51 MB of y2 -- measured in the network at batch 128, same box: the 3x3 behind a pair 47.3 -> 40.1 us,
                                // the stage's last increase layer 90 -> 78, the pairs themselves +7 / +8 us; ResNet-50 1.745 -> 1.730 ms (hints on the
                                // residual loads or on y2: slower)
@@ -362,11 +362,6 @@ int launch_pair(PairParams& p, hipStream_t s) {
 
 }  // namespace
 
-#ifdef HSEFR_DEV
-void set_pair_off(int v) { g_pair_off = v; }
-void set_pair_ablate(int v) { g_pair_ablate = v; }
-void set_pair_nt(int v) { g_pair_nt = v; }
-#endif
 
 // c -> cout1 (+ residual, or + the projection of x2 [.., c2]) -> cout2, all at the same pixels
 bool conv1x1_pair_bf16_shape_supported(int c, int cout1, int cout2, int c2) {

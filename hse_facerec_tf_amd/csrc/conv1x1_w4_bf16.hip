@@ -443,8 +443,8 @@ __global__ __launch_bounds__(512) void conv1x1_w4_bf16_kernel(W4Params p) {
 }
 
 
-HSEFR_KNOB(g_w4_off, 0);    // dev builds: 1 = never use this kernel, 2 = for every shape it covers
-HSEFR_KNOB(g_w4_bres, 1);   // dev builds: 0 = reload the weight stages every step also where they could stay resident (A/B timing)
+HSEFR_KNOB(g_w4_off, "w4_off", 0);    // dev builds: 1 = never use this kernel, 2 = for every shape it covers
+HSEFR_KNOB(g_w4_bres, "w4_bres", 1);   // dev builds: 0 = reload the weight stages every step also where they could stay resident (A/B timing)
 
 template <int RB, int WAVES_M, bool PROJ = false>
 int launch_w4(W4Params& p, hipStream_t s) {
@@ -476,8 +476,6 @@ int read_w4_stamps(void* host_out, size_t bytes) {
     return HSEFR_ERR_UNSUPPORTED;
 #endif
 }
-void set_w4_off(int v) { g_w4_off = v; }
-void set_w4_bres(int v) { g_w4_bres = v; }
 #endif
 
 bool conv1x1_w4_forced() { return g_w4_off == 2; }

@@ -436,7 +436,7 @@ __global__ __launch_bounds__(512) void conv3x3_w2_bf16_kernel(W2Params p) {
     W2_STAMP_FLUSH;
 }
 
-HSEFR_KNOB(g_w2_off, 0);    // dev builds: 1 = never use this kernel, 2 = for every shape it covers
+HSEFR_KNOB(g_w2_off, "w2_off", 0);    // dev builds: 1 = never use this kernel, 2 = for every shape it covers
 
 template <int RB, int WAVES_M, int WX, int RBX, bool FLAT = false>
 int launch_w2(W2Params& p, hipStream_t s) {
@@ -477,7 +477,6 @@ int read_w2_stamps(void* host_out, size_t bytes) {
     return HSEFR_ERR_UNSUPPORTED;
 #endif
 }
-void set_w2_off(int v) { g_w2_off = v; }
 #endif
 
 bool conv3x3_w2_forced() { return g_w2_off == 2; }

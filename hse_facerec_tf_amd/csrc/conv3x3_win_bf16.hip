@@ -420,7 +420,7 @@ Win3Cfg choose_win3(int n, int h, int w, int cout) {
     return best;
 }
 
-HSEFR_KNOB(g_w3_off, 0);    // dev builds: 1 = never use this kernel, 2 = for every shape it covers
+HSEFR_KNOB(g_w3_off, "w3_off", 0);    // dev builds: 1 = never use this kernel, 2 = for every shape it covers
 
 template <int RBW, int WAVES_M>
 int launch_w3(Win3Params& p, hipStream_t s) {
@@ -449,7 +449,6 @@ int read_w3_stamps(void* host_out, size_t bytes) {
     return HSEFR_ERR_UNSUPPORTED;
 #endif
 }
-void set_w3_off(int v) { g_w3_off = v; }
 #endif
 
 bool conv3x3_win_forced() { return g_w3_off == 2; }

@@ -373,8 +373,8 @@ DmaCfg choose_cfg(long long m, int cout, int forced_rb) {
     return best;
 }
 
-HSEFR_KNOB(g_cd_rb, 0);     // dev builds: forced RB
-HSEFR_KNOB(g_cd_off, 0);    // dev builds: 1 = never use this kernel, 2 = use it for every shape it covers (A/B timing)
+HSEFR_KNOB(g_cd_rb, "cd_rb", 0);     // dev builds: forced RB
+HSEFR_KNOB(g_cd_off, "cd_off", 0);    // dev builds: 1 = never use this kernel, 2 = use it for every shape it covers (A/B timing)
 
 template <int RB, int WAVES_M>
 int launch_cfg(ConvDmaParams& p, hipStream_t s) {
@@ -403,8 +403,6 @@ int read_cd_stamps(void* host_out, size_t bytes) {
     return HSEFR_ERR_UNSUPPORTED;
 #endif
 }
-void set_cd_rb(int v) { g_cd_rb = v; }
-void set_cd_off(int v) { g_cd_off = v; }
 #endif
 
 bool conv_dma_forced() { return g_cd_off == 2; }

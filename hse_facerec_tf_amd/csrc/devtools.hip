@@ -124,8 +124,8 @@ __global__ __launch_bounds__(256) void clock_probe_f16s_kernel(unsigned long lon
     }
 }
 
-int g_clock_mode = 0;    // hsefr_debug_set "clock_mode": 0 = fp32 MFMA probe, 1 = f16 32x32x16 probe, 2 = f16 16x16x32 probe
-int g_copy_variant = 0;  // unroll: (v & 3) -> {1, 2, 4, 8}; nt bits: (v >> 2) & 3; grid: (v >> 4) & 3 -> {8, 4, 16, 32} WG/CU
+HSEFR_KNOB(g_clock_mode, "clock_mode", 0);      // 0 = fp32 MFMA probe, 1 = f16 32x32x16 probe, 2 = f16 16x16x32 probe
+HSEFR_KNOB(g_copy_variant, "copy_variant", 0);  // shape of the hsefr_debug_copy kernel.  unroll: (v & 3) -> {1, 2, 4, 8}; nt bits: (v >> 2) & 3; grid: (v >> 4) & 3 -> {8, 4, 16, 32} WG/CU
 
 template <int U, int NT>
 void launch_v(const f32x4* s, f32x4* d, size_t n, unsigned blocks, hipStream_t st) {
@@ -143,9 +143,6 @@ void launch_u(int nt, const f32x4* s, f32x4* d, size_t n, unsigned blocks, hipSt
 }
 
 }  // namespace
-
-void set_copy_variant(int v) { g_copy_variant = v; }
-void set_clock_mode(int v) { g_clock_mode = v; }
 
 int launch_clock_probe(unsigned long long* out, int blocks, int iters, hipStream_t s) {
     HSEFR_REQUIRE(out && blocks > 0 && iters > 0, HSEFR_ERR_INVALID, "clock_probe: bad argument");

@@ -22,10 +22,10 @@ namespace hsefr {
 namespace {
 
 // knobs (constants in the product build; see HSEFR_KNOB in common.h)
-HSEFR_KNOB(g_dw_th, 0);         // forced strip height
-HSEFR_KNOB(g_dw_variant, 0);    // load-policy / grid variants
-HSEFR_KNOB(g_dw_look, 4);       // 2..5 rows of load lookahead, stride-1 kernel (measured in situ: 4 is best)
-HSEFR_KNOB(g_dw_look2, 2);      // 2 | 4 = one | two iterations of lookahead, stride-2 kernel
+HSEFR_KNOB(g_dw_th, "dw_th", 0);         // forced strip height
+HSEFR_KNOB(g_dw_variant, "dw_variant", 0);    // load-policy / grid variants
+HSEFR_KNOB(g_dw_look, "dw_look", 4, [](int v) { return v >= 2 && v <= 5 ? v : 2; });       // 2..5 rows of load lookahead, stride-1 kernel (measured in situ: 4 is best)
+HSEFR_KNOB(g_dw_look2, "dw_look2", 2, [](int v) { return v == 4 ? 4 : 2; });      // 2 | 4 = one | two iterations of lookahead, stride-2 kernel
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 
@@ -195,12 +195,6 @@ __global__ __launch_bounds__(256, LOOK == 2 ? 4 : (LOOK <= 4 ? 3 : 2)) void dwco
 
 }  // namespace
 
-#ifdef HSEFR_DEV
-void set_dw_th(int v) { g_dw_th = v; }
-void set_dw_variant(int v) { g_dw_variant = v; }
-void set_dw_look(int v) { g_dw_look = (v >= 2 && v <= 5) ? v : 2; }
-void set_dw_look2(int v) { g_dw_look2 = v == 4 ? 4 : 2; }
-#endif
 
 static int launch_dwconv3x3_impl(const float* x, const float* wgt, const float* scale, const float* shift, float* y,
                                  int n, int h, int w, int c, int stride, int pad_t, int pad_l, int oh, int ow, int act,

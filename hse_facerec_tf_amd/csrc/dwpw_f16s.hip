@@ -858,9 +858,9 @@ __global__ __launch_bounds__(512, 1) void dwpws2_f16s_kernel(DwPwSParams p) {
     }
 }
 
-HSEFR_KNOB(g_s2_off, 0);   // dev builds: 1 = stride-2 blocks the kernel above covers take the older routes (A/B timing, tests)
-HSEFR_KNOB(g_tw, 0);   // dev builds: 0 = auto, 8 | 16 = forced patch width
-HSEFR_KNOB(g_bn, 0);   // dev builds: 0 = auto, 64 | 128 | 256 = forced N tile
+HSEFR_KNOB(g_s2_off, "dwpw_s2_off", 0);   // dev builds: 1 = stride-2 blocks the kernel above covers take the older routes (A/B timing, tests)
+HSEFR_KNOB(g_tw, "dwpws_tw", 0);   // dev builds: 0 = auto, 8 | 16 = forced patch width
+HSEFR_KNOB(g_bn, "dwpws_bn", 0);   // dev builds: 0 = auto, 64 | 128 | 256 = forced N tile
 
 template <int STRIDE, int TW, int BN, int OCC>
 int launch_t(DwPwSParams& p, int n, int act, hipStream_t s) {
@@ -938,11 +938,6 @@ int launch_s2(DwPwSParams& p, int n, int act, hipStream_t s) {
 
 }  // namespace
 
-#ifdef HSEFR_DEV
-void set_dwpw_s2_off(int v) { g_s2_off = v; }
-void set_dwpws_tw(int v) { g_tw = v; }
-void set_dwpws_bn(int v) { g_bn = v; }
-#endif
 
 bool dwpw_s2_off() { return g_s2_off != 0; }
 

@@ -123,6 +123,19 @@ static void* buf_ptr(const std::vector<void*>& tab, int id, const void* d_input)
     return tab[id];
 }
 
+// A strided residual (round 6; the aux word of a CONV_BF16 / CONV_F32 op without a projection): res_buf is a LARGER map [h2, w2, cout] of
+// `elem_bytes` elements that a 1x1 stride-1 convolution reads at every stride2-th pixel.  kernel_reads_it: a kernel of that kind takes one.
+static int check_strided_residual(uint32_t i, const hsefr_plan_op& o, const hsefr_plan_buffer* bufs, int elem_bytes, bool kernel_reads_it) {
+    const Geometry g = geometry(o.aux);
+    HSEFR_REQUIRE(g.c2 == 0 && o.kh == 1 && o.kw == 1 && o.stride == 1 && o.pad_t == 0 && o.pad_l == 0 && o.res_buf >= 0 && g.stride2 >= 1 &&
+                      o.oh == o.h && o.ow == o.w && o.oh * o.ow > 1 && o.ow > 1 && (o.oh - 1) * g.stride2 < g.h2 && (o.ow - 1) * g.stride2 < g.w2 &&
+                      kernel_reads_it,
+                  HSEFR_ERR_INVALID, "plan op %u: bad strided residual (stride %d, %dx%d)", i, g.stride2, g.h2, g.w2);
+    HSEFR_REQUIRE((uint64_t)g.h2 * g.w2 * o.cout * elem_bytes <= bufs[o.res_buf].elems_per_image * bufs[o.res_buf].elem_bytes, HSEFR_ERR_INVALID,
+                  "plan op %u: strided residual exceeds buffer %d", i, o.res_buf);
+    return HSEFR_OK;
+}
+
 static int validate_plan(const hsefr_plan_header& h, const hsefr_plan_buffer* bufs, const hsefr_plan_op* ops) {
     for (uint32_t i = 0; i < h.n_ops; ++i) {
         const hsefr_plan_op& o = ops[i];
@@ -184,14 +197,9 @@ static int validate_plan(const hsefr_plan_header& h, const hsefr_plan_buffer* bu
                 if (o.scale_off != HSEFR_NO_OFFSET && !need(o.scale_off, co * 4, "scale")) return HSEFR_ERR_INVALID;
                 if (o.shift_off != HSEFR_NO_OFFSET && !need(o.shift_off, co * 4, "shift")) return HSEFR_ERR_INVALID;
                 HSEFR_REQUIRE(o.cout % 4 == 0, HSEFR_ERR_UNSUPPORTED, "plan op %u: fp32 convolution with cout=%d (must be a multiple of 4)", i, o.cout);
-                if (o.aux != 0) {      // strided residual, as HSEFR_OP_CONV_BF16's (round 6): only the fp32-MFMA kernel reads one
-                    HSEFR_REQUIRE(g.c2 == 0 && o.kh == 1 && o.kw == 1 && o.stride == 1 && o.pad_t == 0 && o.pad_l == 0 && o.res_buf >= 0 && g.stride2 >= 1 &&
-                                      o.oh == o.h && o.ow == o.w && o.oh * o.ow > 1 && o.ow > 1 && (o.oh - 1) * g.stride2 < g.h2 &&
-                                      (o.ow - 1) * g.stride2 < g.w2 && conv_f32_mfma_supported(o.cin, o.cout),
-                                  HSEFR_ERR_INVALID, "plan op %u: bad strided residual (stride %d, %dx%d)", i, g.stride2, g.h2, g.w2);
-                    HSEFR_REQUIRE((uint64_t)g.h2 * g.w2 * co * 4 <= bufs[o.res_buf].elems_per_image * bufs[o.res_buf].elem_bytes, HSEFR_ERR_INVALID,
-                                  "plan op %u: strided residual exceeds buffer %d", i, o.res_buf);
-                }
+                // strided residual, as HSEFR_OP_CONV_BF16's (round 6): only the fp32-MFMA kernel reads one
+                if (o.aux != 0)
+                    if (int rc = check_strided_residual(i, o, bufs, 4, conv_f32_mfma_supported(o.cin, o.cout))) return rc;
                 break;
             case HSEFR_OP_CONV_C3:
                 if (!need(o.w_off, kk * ci * co * 4, "kernel") || !need(o.shift_off, co * 4, "shift")) return HSEFR_ERR_INVALID;
@@ -222,12 +230,7 @@ static int validate_plan(const hsefr_plan_header& h, const hsefr_plan_buffer* bu
                     HSEFR_REQUIRE((uint64_t)g.h2 * g.w2 * g.c2 * 2 <= bufs[o.res_buf].elems_per_image * bufs[o.res_buf].elem_bytes, HSEFR_ERR_INVALID,
                                   "plan op %u: projected shortcut input exceeds buffer %d", i, o.res_buf);
                 } else if (o.aux != 0) {
-                    // strided residual (round 6): res_buf is a LARGER map [h2, w2, cout] read at every stride-th pixel
-                    HSEFR_REQUIRE(g.c2 == 0 && o.kh == 1 && o.kw == 1 && o.stride == 1 && o.pad_t == 0 && o.pad_l == 0 && o.res_buf >= 0 && g.stride2 >= 1 &&
-                                      o.oh == o.h && o.ow == o.w && o.oh * o.ow > 1 && o.ow > 1 && (o.oh - 1) * g.stride2 < g.h2 && (o.ow - 1) * g.stride2 < g.w2,
-                                  HSEFR_ERR_INVALID, "plan op %u: bad strided residual (stride %d, %dx%d)", i, g.stride2, g.h2, g.w2);
-                    HSEFR_REQUIRE((uint64_t)g.h2 * g.w2 * co * 2 <= bufs[o.res_buf].elems_per_image * bufs[o.res_buf].elem_bytes, HSEFR_ERR_INVALID,
-                                  "plan op %u: strided residual exceeds buffer %d", i, o.res_buf);
+                    if (int rc = check_strided_residual(i, o, bufs, 2, true)) return rc;
                 }
                 break;
             case HSEFR_OP_STEM7X7_POOL_BF16:
@@ -357,7 +360,7 @@ static int validate_plan(const hsefr_plan_header& h, const hsefr_plan_buffer* bu
             HSEFR_REQUIRE(b.out_buf != o.out_buf, HSEFR_ERR_INVALID, "plan op %u: DWPW_NEXT: the second output (buffer %d) aliases the depthwise tensor", i,
                           b.out_buf);
             // the usual two-buffer plan recycles the depthwise INPUT's buffer for the second output: the one launch then writes into the
-            // (unwritten) depthwise buffer instead and the forward goes on with the two buffers' roles exchanged (run_ops) -- sound only
+            // (unwritten) depthwise buffer instead and the forward goes on with the two buffers' roles exchanged (launch_op) -- sound only
             // if they hold the same number of bytes
             HSEFR_REQUIRE(b.out_buf != o.in_buf || (uint64_t)bufs[o.in_buf].elems_per_image * bufs[o.in_buf].elem_bytes ==
                                                        (uint64_t)bufs[o.out_buf].elems_per_image * bufs[o.out_buf].elem_bytes,
@@ -493,11 +496,20 @@ void route_record(const void* host_stub, const char* expr) {
 static thread_local int g_sweep_reverse = 0;    // set per op by the forward running on THIS host thread, read by its launchers
 int sweep_reverse() { return g_sweep_reverse; }
 void set_sweep_reverse(int v) { g_sweep_reverse = v; }
+#ifdef HSEFR_DEV
+// every HSEFR_KNOB line of the library (common.h), in whatever order the sources' initialisers ran: the table is made on first use
+struct Knob { const char* key; int* variable; int (*fix)(int); };
+static std::vector<Knob>& knobs() { static std::vector<Knob> table; return table; }
+int knob_register(const char* key, int* variable, int value, int (*fix)(int)) {
+    knobs().push_back({key, variable, fix});
+    return value;
+}
+#endif
 }  // namespace hsefr
-HSEFR_KNOB(g_sweep_alternate, 1);   // dev builds: 0 turns the alternation off (A/B timing)
-HSEFR_KNOB(g_stem5, 1);             // dev builds: 0 = stem4_fused.hip (round 3's patch kernel) where stem5_stream.hip covers the shape (A/B timing)
-HSEFR_KNOB(g_heads_off, 0);         // dev builds: 1 = the four head launches also where a DENSE op carries HSEFR_OPF_HEADS (A/B timing)
-HSEFR_KNOB(g_stem4, 1);             // dev builds: 0 = stem3_fused.hip also where stem4_fused.hip covers the shape (A/B timing)
+HSEFR_KNOB(g_sweep_alternate, "sweep_alternate", 1);   // dev builds: 0 turns the alternation off (A/B timing)
+HSEFR_KNOB(g_stem5, "stem5", 1);             // dev builds: 0 = stem4_fused.hip (round 3's patch kernel) where stem5_stream.hip covers the shape (A/B timing)
+HSEFR_KNOB(g_heads_off, "heads_off", 0);         // dev builds: 1 = the four head launches also where a DENSE op carries HSEFR_OPF_HEADS (A/B timing)
+HSEFR_KNOB(g_stem4, "stem4", 1);             // dev builds: 0 = stem3_fused.hip also where stem4_fused.hip covers the shape (A/B timing)
 
 #pragma GCC visibility push(default)   // the library is built with -fvisibility=hidden: the C ABI below is ALL it exports
 extern "C" {
@@ -509,45 +521,8 @@ const char* hsefr_last_error_string(void) { return g_err; }
 #ifdef HSEFR_DEV
 int hsefr_debug_set(const char* key, int value) {
     HSEFR_REQUIRE(key, HSEFR_ERR_INVALID, "debug_set: null key");
-    if (!strcmp(key, "pw_tile")) { set_pw_tile(value); return HSEFR_OK; }
-    if (!strcmp(key, "pws_tile")) { set_pws_tile(value); return HSEFR_OK; }
-    if (!strcmp(key, "ps_mb")) { set_ps_mb(value); return HSEFR_OK; }
-    if (!strcmp(key, "ps_grid")) { set_ps_grid(value); return HSEFR_OK; }
-    if (!strcmp(key, "psdw_mode")) { set_psdw_mode(value); return HSEFR_OK; }
-    if (!strcmp(key, "cd_rb")) { set_cd_rb(value); return HSEFR_OK; }
-    if (!strcmp(key, "cd_off")) { set_cd_off(value); return HSEFR_OK; }
-    if (!strcmp(key, "w3_off")) { set_w3_off(value); return HSEFR_OK; }
-    if (!strcmp(key, "w2_off")) { set_w2_off(value); return HSEFR_OK; }
-    if (!strcmp(key, "w4_off")) { set_w4_off(value); return HSEFR_OK; }
-    if (!strcmp(key, "w4_bres")) { set_w4_bres(value); return HSEFR_OK; }
-    if (!strcmp(key, "nn1_y_mb")) { set_nn1_y_mb(value); return HSEFR_OK; }
-    if (!strcmp(key, "c11")) { set_c11(value); return HSEFR_OK; }
-    if (!strcmp(key, "c11_tile")) { set_c11_tile(value); return HSEFR_OK; }
-    if (!strcmp(key, "c11_bres")) { set_c11_bres(value); return HSEFR_OK; }
-    if (!strcmp(key, "c11_adv")) { set_c11_adv(value); return HSEFR_OK; }
-    if (!strcmp(key, "stem4_grid")) { set_stem4_grid(value); return HSEFR_OK; }
-    if (!strcmp(key, "stem4")) { g_stem4 = value; return HSEFR_OK; }
-    if (!strcmp(key, "stem5")) { g_stem5 = value; return HSEFR_OK; }
-    if (!strcmp(key, "stem5_grid")) { set_stem5_grid(value); return HSEFR_OK; }
-    if (!strcmp(key, "stem5_segs")) { set_stem5_segs(value); return HSEFR_OK; }
-    if (!strcmp(key, "pair_off")) { set_pair_off(value); return HSEFR_OK; }
-    if (!strcmp(key, "stem7s")) { set_stem7s(value); return HSEFR_OK; }
-    if (!strcmp(key, "pair_ablate")) { set_pair_ablate(value); return HSEFR_OK; }
-    if (!strcmp(key, "pair_nt")) { set_pair_nt(value); return HSEFR_OK; }
-    if (!strcmp(key, "heads_off")) { g_heads_off = value; return HSEFR_OK; }
-    if (!strcmp(key, "dw_look")) { set_dw_look(value); return HSEFR_OK; }
-    if (!strcmp(key, "dw_look2")) { set_dw_look2(value); return HSEFR_OK; }
-    if (!strcmp(key, "sweep_alternate")) { g_sweep_alternate = value; return HSEFR_OK; }
-    if (!strcmp(key, "clock_mode")) { set_clock_mode(value); return HSEFR_OK; }
-    if (!strcmp(key, "dwpw_s2_off")) { set_dwpw_s2_off(value); return HSEFR_OK; }
-    if (!strcmp(key, "dwpws_tw")) { set_dwpws_tw(value); return HSEFR_OK; }
-    if (!strcmp(key, "dwpws_bn")) { set_dwpws_bn(value); return HSEFR_OK; }
-    if (!strcmp(key, "pw_ablate")) { set_pw_ablate(value); return HSEFR_OK; }
-    if (!strcmp(key, "pw_dma")) { set_pw_dma(value); return HSEFR_OK; }
-    if (!strcmp(key, "dw_th")) { set_dw_th(value); return HSEFR_OK; }
-    if (!strcmp(key, "dw_variant")) { set_dw_variant(value); return HSEFR_OK; }
-    if (!strcmp(key, "copy_variant")) { set_copy_variant(value); return HSEFR_OK; }
-    if (!strcmp(key, "c3_impl")) { set_c3_impl(value); return HSEFR_OK; }
+    for (const Knob& k : knobs())
+        if (!strcmp(key, k.key)) { *k.variable = k.fix ? k.fix(value) : value; return HSEFR_OK; }
     set_error("debug_set: unknown key %s", key);
     return HSEFR_ERR_INVALID;
 }
@@ -711,250 +686,182 @@ int hsefr_engine_op_times_ms(hsefr_engine* e, int slot, float* ms, int n_ops) {
     return HSEFR_OK;
 }
 
+// An op's blob operands, resolved once (null where the op has none: HSEFR_NO_OFFSET)
+struct Operands {
+    const void *w, *w2;
+    const float *scale, *shift, *shift2;
+};
+static Operands operands(const hsefr_engine* e, const hsefr_plan_op& o) {
+    return {blob_ptr(e, o.w_off), blob_ptr(e, o.w2_off), (const float*)blob_ptr(e, o.scale_off), (const float*)blob_ptr(e, o.shift_off),
+            (const float*)blob_ptr(e, o.shift2_off)};
+}
+
+// Launch op i of a forward for a batch of n on stream s: THE place that decides which launch serves a plan op.  `covered` = the ops behind
+// it that the launch computed as well (hsefr_op_flags; their patterns were checked by validate_plan): the caller goes on behind them.
+// tab: the forward's own buffer table (a DWPW_NEXT launch may exchange two buffers' roles in it).  every_tensor: the all-layers debug
+// forward -- a launch that would leave a tensor of the plan unwritten (HSEFR_OPF_DWPW_NEXT) is not used.
+static int launch_op(hsefr_engine* e, size_t i, std::vector<void*>& tab, const void* d_input, int n, const std::vector<char>& needed, hipStream_t s,
+                     bool input_u8, bool every_tensor, size_t& covered) {
+    const hsefr_plan_op& o = e->ops[i];
+    const Operands p = operands(e, o);
+    const void* in = buf_ptr(tab, o.in_buf, d_input);
+    void* out = buf_ptr(tab, o.out_buf, d_input);
+    const long long pixels = (long long)n * o.h * o.w;
+    covered = 0;
+    const bool sub2 = (o.flags & HSEFR_OPF_OUT_SUB2) != 0;
+    const Geometry g = geometry(o.aux);                                     // (CONV_BF16 / CONV_F32 only)
+    const bool proj = o.w2_off != HSEFR_NO_OFFSET;                          // (CONV_BF16: a projected shortcut, w2 = its kernel, shift2 = [scale | shift])
+    const int c2 = proj ? g.c2 : 0;                                         // its input channels
+    const bool pair_ok = (o.flags & HSEFR_OPF_PAIR_NEXT) && needed[i + 1] &&
+                         conv1x1_pair_bf16_supported(pixels, o.cin, o.cout, e->ops[i + 1].cout, c2);
+    HSEFR_REQUIRE(!sub2 || pair_ok, HSEFR_ERR_UNSUPPORTED, "forward: op %zu stores its output at every second pixel (OUT_SUB2) and cannot run without the pair launch", i);
+    if (pair_ok) {
+        // increase (+ residual | + projected shortcut) -> the next block's reduce in one launch (csrc/conv1x1_pair_bf16.hip):
+        // both tensors are written, the second product reads the first from registers
+        const hsefr_plan_op& b = e->ops[i + 1];
+        const Operands pb = operands(e, b);
+        covered = 1;
+        return launch_conv1x1_pair_bf16(in, p.w, p.scale, p.shift, proj ? nullptr : tab[o.res_buf], proj ? tab[o.res_buf] : nullptr, proj ? p.w2 : nullptr,
+                                        proj ? p.shift2 : nullptr, proj ? p.shift2 + o.cout : nullptr, out, pb.w, pb.scale, pb.shift, tab[b.out_buf],
+                                        pixels, o.cin, o.cout, b.cout, c2, o.act, b.act, s, sub2 ? 2 : 1, o.h, o.w);
+    }
+    if ((o.flags & HSEFR_OPF_HEADS) && !g_heads_off && needed[i + 1] && needed[i + 2] && needed[i + 3]) {
+        // the age / gender heads in one launch (csrc/pool_dense.hip): hidden, logits, probabilities and the gender sigmoid are all written
+        const hsefr_plan_op &a = e->ops[i + 1], &sm = e->ops[i + 2], &gd = e->ops[i + 3];
+        const Operands pa = operands(e, a), pg = operands(e, gd);
+        covered = 3;
+        return launch_heads_fused((const float*)in, (const float*)p.w, p.shift, (const float*)pa.w, pa.shift, (const float*)pg.w, pg.shift, (float*)out,
+                                  (float*)tab[a.out_buf], (float*)tab[sm.out_buf], (float*)tab[gd.out_buf], n, o.cin, a.cout, s);
+    }
+    if ((o.flags & HSEFR_OPF_DWPW_NEXT) && !every_tensor && !dwpw_s2_off() && needed[i + 1]) {
+        // stride-2 depthwise -> split-f16 pointwise in one launch (csrc/dwpw_f16s.hip): the depthwise tensor stays on the CU and its
+        // buffer is not written
+        const hsefr_plan_op& b = e->ops[i + 1];
+        const Operands pb = operands(e, b);
+        // where the plan recycles the launch's INPUT buffer for the second output (two ping-pong buffers), the result goes into the
+        // depthwise tensor's buffer, which this launch leaves unused, and from here on the two buffers stand for each other
+        // (same size, neither an output slot, the depthwise tensor read by nobody else: validate_plan)
+        if (b.out_buf == o.in_buf) std::swap(tab[o.in_buf], tab[o.out_buf]);
+        covered = 1;
+        return launch_dwpw_f16s((const float*)in, (const float*)p.w, p.scale, p.shift, pb.w, pb.scale, pb.shift, (float*)tab[b.out_buf], n, o.h, o.w,
+                                o.cin, o.stride, o.pad_t, o.pad_l, o.oh, o.ow, b.cout, b.aux, b.act, s);
+    }
+    const void* res = o.res_buf >= 0 ? tab[o.res_buf] : nullptr;
+    switch (o.kind) {
+        case HSEFR_OP_CONV_C3:
+            return launch_conv_c3((const float*)in, (const float*)p.w, p.shift, (float*)out, n, o.h, o.w, o.kh, o.kw, o.stride, o.pad_t, o.pad_l, o.oh, o.ow,
+                                  o.cout, o.act, s);
+        case HSEFR_OP_DWCONV3X3:
+            if (o.aux > 0)
+                return launch_dwconv3x3_split((const float*)in, (const float*)p.w, p.scale, p.shift, out, n, o.h, o.w, o.cin, o.stride, o.pad_t, o.pad_l,
+                                              o.oh, o.ow, o.act, o.aux, s);
+            return launch_dwconv3x3((const float*)in, (const float*)p.w, p.scale, p.shift, (float*)out, n, o.h, o.w, o.cin, o.stride, o.pad_t, o.pad_l, o.oh,
+                                    o.ow, o.act, s);
+        case HSEFR_OP_PWCONV_PS_GAP:
+            return launch_pwconv_ps_gap(in, p.w, p.scale, p.shift, (float*)out, pixels, o.cin, o.cout, o.act, o.h * o.w, s);
+        case HSEFR_OP_PWCONV_PS_DW:
+            return launch_pwconv_ps_dw(in, p.w, p.scale, p.shift, (const float*)p.w2, out, pixels, o.cin, o.cout, o.act, o.w, o.h * o.w, o.stride,
+                                       ps_dw_aux(o.aux).out_log2, s);
+        case HSEFR_OP_PWCONV_PS:
+            return launch_pwconv_ps(in, p.w, p.scale, p.shift, (float*)out, pixels, o.cin, o.cout, o.act, s);
+        case HSEFR_OP_PWCONV_F32:
+            return launch_pwconv_f32((const float*)in, (const float*)p.w, p.shift, (float*)out, pixels, o.cin, o.cout, o.act, s);
+        case HSEFR_OP_PWCONV_F16S:
+            return launch_pwconv_f16s((const float*)in, p.w, p.scale, p.shift, (float*)out, pixels, o.cin, o.cout, o.aux, o.act, s);
+        case HSEFR_OP_GAP:
+            return launch_gap((const float*)in, (float*)out, n, o.h * o.w, o.cin, s);
+        case HSEFR_OP_DENSE:
+            return launch_dense((const float*)in, (const float*)p.w, p.shift, (float*)out, n, o.cin, o.cout, o.act, s);
+        case HSEFR_OP_SOFTMAX:
+            return launch_softmax((const float*)in, (float*)out, n, o.cout, s);
+        case HSEFR_OP_CONV_BF16:
+            if (proj)      // increase layer + projected shortcut in one launch (csrc/conv1x1_bf16.hip, PROJ)
+                return launch_conv1x1_proj_bf16(in, p.w, p.scale, p.shift, tab[o.res_buf], p.w2, p.shift2, p.shift2 + o.cout, out, n, o.oh, o.ow, o.cin,
+                                                o.cout, g.c2, g.stride2, g.h2, g.w2, o.act, s);
+            if (o.res_buf >= 0 && o.aux != 0)      // the residual is a stride view of a larger map (csrc/conv1x1_bf16.hip, rs_stride)
+                return launch_conv1x1_sres_bf16(in, p.w, p.scale, p.shift, res, out, n, o.oh, o.ow, o.cin, o.cout, g.stride2, g.h2, g.w2, o.act, s);
+            return launch_conv_bf16(in, p.w, p.scale, p.shift, res, out, n, o.h, o.w, o.cin, o.oh, o.ow, o.cout, o.kh, o.kw, o.stride, o.pad_t, o.pad_l,
+                                    o.act, s);
+        case HSEFR_OP_CONV_F32:
+            if (conv_f32_mfma_supported(o.cin, o.cout))       // exact fp32 on the fp32 matrix pipe (csrc/conv_f32_mfma.hip)
+                return launch_conv_f32_mfma((const float*)in, (const float*)p.w, p.scale, p.shift, (const float*)res, (float*)out, n, o.h, o.w, o.cin, o.oh,
+                                            o.ow, o.cout, o.kh, o.kw, o.stride, o.pad_t, o.pad_l, o.act, s, o.res_buf >= 0 ? g.stride2 : 0, g.h2, g.w2);
+            return launch_conv2d_f32((const float*)in, (const float*)p.w, p.scale, p.shift, (const float*)res, (float*)out, n, o.h, o.w, o.cin, o.oh, o.ow,
+                                     o.cout, o.kh, o.kw, o.stride, o.pad_t, o.pad_l, o.act, s);
+        case HSEFR_OP_MAXPOOL_F32:
+            return launch_maxpool_f32((const float*)in, (float*)out, n, o.h, o.w, o.cin, o.oh, o.ow, o.kh, o.stride, o.pad_t, o.pad_l, s);
+        case HSEFR_OP_STEM7X7_BF16:
+            return launch_stem7x7_bf16((const float*)in, p.w, p.scale, p.shift, out, n, o.h, o.w, o.oh, o.ow, o.act, s);
+        case HSEFR_OP_STEM7X7_POOL_BF16:
+            return launch_stem7x7_pool_bf16((const float*)in, p.w, p.scale, p.shift, out, n, o.h, o.w, o.oh, o.ow, pool_pads(o.aux).t, pool_pads(o.aux).l, s,
+                                            i < e->d_derived.size() ? e->d_derived[i] : nullptr);
+        case HSEFR_OP_MAXPOOL_BF16:
+            return launch_maxpool3x3s2_bf16(in, out, n, o.h, o.w, o.cin, o.oh, o.ow, o.pad_t, o.pad_l, s);
+        case HSEFR_OP_GAP_BF16:
+            return launch_gap_bf16(in, (float*)out, n, o.h * o.w, o.cin, s);
+        case HSEFR_OP_DWPW_F32:
+            return launch_dwpw_fused((const float*)in, (const float*)p.w, p.scale, p.shift, (const float*)p.w2, p.shift2, (float*)out, n, o.h, o.w, o.cin,
+                                     o.stride, o.pad_t, o.pad_l, o.oh, o.ow, o.cout, HSEFR_ACT_RELU6, o.act, s);
+        case HSEFR_OP_STEM3_F16S: {
+            const StemPack k = stem_pack(e, o);
+            const StemAux a = stem_aux(o.aux);
+            const StemKw kw = stem_kw(o.kw);
+            if (input_u8)
+                return (g_stem5 ? launch_stem5_stream : launch_stem4_fused)(in, 1, k.conv4_u8, k.u8_descale, k.u8_shift, k.dw1, k.dw1_scale, k.dw1_shift, p.w2,
+                                                                          k.descale, k.pshift, k.dw2, k.dw2_scale, k.dw2_shift, (float*)out, nullptr, n, o.h,
+                                                                          o.w, 0, a.a_log2, o.act, s);
+            if (g_stem4 && stem4_route(o))
+                return (g_stem5 ? launch_stem5_stream : launch_stem4_fused)(in, 0, k.conv4, k.conv_descale, k.conv_shift, k.dw1, k.dw1_scale, k.dw1_shift, p.w2,
+                                                                          k.descale, k.pshift, k.dw2, k.dw2_scale, k.dw2_shift, (float*)out, e->d_overflow, n,
+                                                                          o.h, o.w, a.in_log2, a.a_log2, o.act, s);
+            return launch_stem3_fused((const float*)in, k.conv_split, k.conv_descale, k.conv_shift, k.dw1, k.dw1_scale, k.dw1_shift, p.w2, k.descale, k.pshift,
+                                      k.dw2, k.dw2_scale, k.dw2_shift, (float*)out, e->d_overflow, n, o.h, o.w, o.pad_t, o.pad_l, (o.h + 1) / 2, (o.w + 1) / 2,
+                                      kw.pad_t2, kw.pad_l2, o.oh, o.ow, a.in_log2, a.a_log2, o.act, s);
+        }
+        case HSEFR_OP_STEM2_F16S: {
+            const StemPack k = stem_pack(e, o);
+            const StemKw kw = stem_kw(o.kw);
+            return launch_stem2_fused((const float*)in, k.conv, k.conv_shift, k.dw1, k.dw1_scale, k.dw1_shift, p.w2, k.descale, k.pshift, k.dw2, k.dw2_scale,
+                                      k.dw2_shift, (float*)out, n, o.h, o.w, o.pad_t, o.pad_l, (o.h + 1) / 2, (o.w + 1) / 2, kw.pad_t2, kw.pad_l2, o.oh, o.ow,
+                                      o.aux, o.act, s);
+        }
+#ifdef HSEFR_DEV
+        case HSEFR_OP_STEM_F16S: {
+            const StemPack k = stem_pack(e, o);
+            return launch_stem_fused((const float*)in, k.conv, k.conv_shift, k.dw1, k.dw1_scale, k.dw1_shift, p.w2, k.descale, k.pshift, (float*)out, n, o.h,
+                                     o.w, o.pad_t, o.pad_l, o.oh, o.ow, o.aux, o.act, s);
+        }
+#endif
+        case HSEFR_OP_DWPW_F16S:      // shift2 = [descale | shift] of the pointwise half
+            return launch_dwpw_f16s((const float*)in, (const float*)p.w, p.scale, p.shift, p.w2, p.shift2, p.shift2 + o.cout, (float*)out, n, o.h, o.w, o.cin,
+                                    o.stride, o.pad_t, o.pad_l, o.oh, o.ow, o.cout, o.aux, o.act, s);
+        default:
+            set_error("forward: op %zu has unknown kind %u", i, o.kind);
+            return HSEFR_ERR_UNSUPPORTED;
+    }
+}
+
 // Launch the needed ops of the plan for a batch of n on stream s (plain launches: also what a graph capture records).
-// every_tensor: the all-layers debug forward -- a launch that would leave a tensor of the plan unwritten (HSEFR_OPF_DWPW_NEXT) is not used.
 static int run_ops(hsefr_engine* e, const std::vector<void*>& tab_in, const void* d_input, int n, const std::vector<char>& needed,
                    hipStream_t s, hipEvent_t* pev, bool input_u8 = false, bool every_tensor = false) {
-    std::vector<void*> tab(tab_in);      // (this forward's own copy: a DWPW_NEXT launch may exchange two buffers' roles)
+    std::vector<void*> tab(tab_in);      // (this forward's own copy: launch_op may exchange two buffers' roles)
     const bool prof = pev != nullptr;
     unsigned launches = 0;     // (a launch that covers several ops -- hsefr_op_flags -- counts once: the op behind it must still sweep the other way)
     if (prof) HSEFR_HIP_CHECK(hipEventRecord(pev[0], s));
     for (size_t i = 0; i < e->ops.size(); ++i) {
-        const hsefr_plan_op& o = e->ops[i];
         if (!needed[i]) {
             if (prof) HSEFR_HIP_CHECK(hipEventRecord(pev[i + 1], s));
             continue;
         }
-        const void* in = buf_ptr(tab, o.in_buf, d_input);
-        void* out = buf_ptr(tab, o.out_buf, d_input);
-        int rc = HSEFR_OK;
-        size_t covered = 0;       // ops behind this one that its launch computes as well (hsefr_op_flags)
         set_sweep_reverse(g_sweep_alternate ? (int)(launches++ & 1) : 0);   // consecutive LAUNCHES sweep in opposite directions (common.h)
-        const bool sub2 = (o.flags & HSEFR_OPF_OUT_SUB2) != 0;
-        const Geometry g = geometry(o.aux);                                     // (CONV_BF16 / CONV_F32 only)
-        const int c2 = o.w2_off != HSEFR_NO_OFFSET ? g.c2 : 0;                  // a projected shortcut's input channels
-        const bool pair_ok = (o.flags & HSEFR_OPF_PAIR_NEXT) && needed[i + 1] &&
-                             conv1x1_pair_bf16_supported((long long)n * o.h * o.w, o.cin, o.cout, e->ops[i + 1].cout, c2);
-        HSEFR_REQUIRE(!sub2 || pair_ok, HSEFR_ERR_UNSUPPORTED, "forward: op %zu stores its output at every second pixel (OUT_SUB2) and cannot run without the pair launch", i);
-        if (pair_ok) {
-            // increase (+ residual | + projected shortcut) -> the next block's reduce in one launch (csrc/conv1x1_pair_bf16.hip; the pattern
-            // was checked by validate_plan): both tensors are written, the second product reads the first from registers
-            const hsefr_plan_op& b = e->ops[i + 1];
-            const bool proj = o.w2_off != HSEFR_NO_OFFSET;
-            const float* ssp = (const float*)blob_ptr(e, o.shift2_off);
-            rc = launch_conv1x1_pair_bf16(in, blob_ptr(e, o.w_off), (const float*)blob_ptr(e, o.scale_off), (const float*)blob_ptr(e, o.shift_off),
-                                          proj ? nullptr : tab[o.res_buf], proj ? tab[o.res_buf] : nullptr, proj ? blob_ptr(e, o.w2_off) : nullptr,
-                                          proj ? ssp : nullptr, proj ? ssp + o.cout : nullptr, out, blob_ptr(e, b.w_off),
-                                          (const float*)blob_ptr(e, b.scale_off), (const float*)blob_ptr(e, b.shift_off), tab[b.out_buf],
-                                          (long long)n * o.h * o.w, o.cin, o.cout, b.cout, c2, o.act, b.act, s, sub2 ? 2 : 1, o.h, o.w);
-            covered = 1;
-        } else if ((o.flags & HSEFR_OPF_HEADS) && !g_heads_off && needed[i + 1] && needed[i + 2] && needed[i + 3]) {
-            // the age / gender heads in one launch (csrc/pool_dense.hip): hidden, logits, probabilities and the gender sigmoid are all written
-            const hsefr_plan_op &a = e->ops[i + 1], &sm = e->ops[i + 2], &g = e->ops[i + 3];
-            rc = launch_heads_fused((const float*)in, (const float*)blob_ptr(e, o.w_off), (const float*)blob_ptr(e, o.shift_off),
-                                    (const float*)blob_ptr(e, a.w_off), (const float*)blob_ptr(e, a.shift_off), (const float*)blob_ptr(e, g.w_off),
-                                    (const float*)blob_ptr(e, g.shift_off), (float*)out, (float*)tab[a.out_buf], (float*)tab[sm.out_buf],
-                                    (float*)tab[g.out_buf], n, o.cin, a.cout, s);
-            covered = 3;
-        } else if ((o.flags & HSEFR_OPF_DWPW_NEXT) && !every_tensor && !dwpw_s2_off() && needed[i + 1]) {
-            // stride-2 depthwise -> split-f16 pointwise in one launch (csrc/dwpw_f16s.hip; the pattern was checked by validate_plan): the
-            // depthwise tensor stays on the CU and its buffer is not written
-            const hsefr_plan_op& b = e->ops[i + 1];
-            // where the plan recycles the launch's INPUT buffer for the second output (two ping-pong buffers), the result goes into the
-            // depthwise tensor's buffer, which this launch leaves unused, and from here on the two buffers stand for each other
-            // (same size, neither an output slot, the depthwise tensor read by nobody else: validate_plan)
-            if (b.out_buf == o.in_buf) std::swap(tab[o.in_buf], tab[o.out_buf]);
-            rc = launch_dwpw_f16s((const float*)in, (const float*)blob_ptr(e, o.w_off), (const float*)blob_ptr(e, o.scale_off),
-                                  (const float*)blob_ptr(e, o.shift_off), blob_ptr(e, b.w_off), (const float*)blob_ptr(e, b.scale_off),
-                                  (const float*)blob_ptr(e, b.shift_off), (float*)tab[b.out_buf], n, o.h, o.w, o.cin, o.stride, o.pad_t, o.pad_l,
-                                  o.oh, o.ow, b.cout, b.aux, b.act, s);
-            covered = 1;
-        } else
-        switch (o.kind) {
-            case HSEFR_OP_CONV_C3:
-                rc = launch_conv_c3((const float*)in, (const float*)blob_ptr(e, o.w_off),
-                                    (const float*)blob_ptr(e, o.shift_off), (float*)out, n, o.h, o.w, o.kh, o.kw,
-                                    o.stride, o.pad_t, o.pad_l, o.oh, o.ow, o.cout, o.act, s);
-                break;
-            case HSEFR_OP_DWCONV3X3:
-                if (o.aux > 0)
-                    rc = launch_dwconv3x3_split((const float*)in, (const float*)blob_ptr(e, o.w_off),
-                                                (const float*)blob_ptr(e, o.scale_off), (const float*)blob_ptr(e, o.shift_off),
-                                                out, n, o.h, o.w, o.cin, o.stride, o.pad_t, o.pad_l, o.oh, o.ow, o.act, o.aux, s);
-                else
-                    rc = launch_dwconv3x3((const float*)in, (const float*)blob_ptr(e, o.w_off),
-                                          (const float*)blob_ptr(e, o.scale_off), (const float*)blob_ptr(e, o.shift_off),
-                                          (float*)out, n, o.h, o.w, o.cin, o.stride, o.pad_t, o.pad_l, o.oh, o.ow, o.act, s);
-                break;
-            case HSEFR_OP_PWCONV_PS_GAP:
-                rc = launch_pwconv_ps_gap(in, blob_ptr(e, o.w_off), (const float*)blob_ptr(e, o.scale_off), (const float*)blob_ptr(e, o.shift_off),
-                                          (float*)out, (long long)n * o.h * o.w, o.cin, o.cout, o.act, o.h * o.w, s);
-                break;
-            case HSEFR_OP_PWCONV_PS_DW:
-                rc = launch_pwconv_ps_dw(in, blob_ptr(e, o.w_off), (const float*)blob_ptr(e, o.scale_off), (const float*)blob_ptr(e, o.shift_off),
-                                         (const float*)blob_ptr(e, o.w2_off), out, (long long)n * o.h * o.w, o.cin, o.cout, o.act, o.w,
-                                         o.h * o.w, o.stride, ps_dw_aux(o.aux).out_log2, s);
-                break;
-            case HSEFR_OP_PWCONV_PS:
-                rc = launch_pwconv_ps(in, blob_ptr(e, o.w_off), (const float*)blob_ptr(e, o.scale_off),
-                                      (const float*)blob_ptr(e, o.shift_off), (float*)out, (long long)n * o.h * o.w, o.cin, o.cout,
-                                      o.act, s);
-                break;
-            case HSEFR_OP_PWCONV_F32:
-                rc = launch_pwconv_f32((const float*)in, (const float*)blob_ptr(e, o.w_off),
-                                       (const float*)blob_ptr(e, o.shift_off), (float*)out,
-                                       (long long)n * o.h * o.w, o.cin, o.cout, o.act, s);
-                break;
-            case HSEFR_OP_PWCONV_F16S:
-                rc = launch_pwconv_f16s((const float*)in, blob_ptr(e, o.w_off), (const float*)blob_ptr(e, o.scale_off),
-                                        (const float*)blob_ptr(e, o.shift_off), (float*)out, (long long)n * o.h * o.w,
-                                        o.cin, o.cout, o.aux, o.act, s);
-                break;
-            case HSEFR_OP_GAP:
-                rc = launch_gap((const float*)in, (float*)out, n, o.h * o.w, o.cin, s);
-                break;
-            case HSEFR_OP_DENSE:
-                rc = launch_dense((const float*)in, (const float*)blob_ptr(e, o.w_off),
-                                  (const float*)blob_ptr(e, o.shift_off), (float*)out, n, o.cin, o.cout, o.act, s);
-                break;
-            case HSEFR_OP_SOFTMAX:
-                rc = launch_softmax((const float*)in, (float*)out, n, o.cout, s);
-                break;
-            case HSEFR_OP_CONV_BF16:
-                if (o.w2_off != HSEFR_NO_OFFSET) {      // increase layer + projected shortcut in one launch (csrc/conv1x1_bf16.hip, PROJ)
-                    const float* ss2 = (const float*)blob_ptr(e, o.shift2_off);
-                    rc = launch_conv1x1_proj_bf16(in, blob_ptr(e, o.w_off), (const float*)blob_ptr(e, o.scale_off),
-                                                  (const float*)blob_ptr(e, o.shift_off), tab[o.res_buf], blob_ptr(e, o.w2_off), ss2, ss2 + o.cout,
-                                                  out, n, o.oh, o.ow, o.cin, o.cout, g.c2, g.stride2, g.h2, g.w2, o.act, s);
-                    break;
-                }
-                if (o.res_buf >= 0 && o.aux != 0) {      // the residual is a stride view of a larger map (csrc/conv1x1_bf16.hip, rs_stride)
-                    rc = launch_conv1x1_sres_bf16(in, blob_ptr(e, o.w_off), (const float*)blob_ptr(e, o.scale_off), (const float*)blob_ptr(e, o.shift_off),
-                                                  tab[o.res_buf], out, n, o.oh, o.ow, o.cin, o.cout, g.stride2, g.h2, g.w2, o.act, s);
-                    break;
-                }
-                rc = launch_conv_bf16(in, blob_ptr(e, o.w_off), (const float*)blob_ptr(e, o.scale_off),
-                                      (const float*)blob_ptr(e, o.shift_off),
-                                      o.res_buf >= 0 ? tab[o.res_buf] : nullptr, out, n, o.h, o.w, o.cin, o.oh,
-                                      o.ow, o.cout, o.kh, o.kw, o.stride, o.pad_t, o.pad_l, o.act, s);
-                break;
-            case HSEFR_OP_CONV_F32:
-                if (conv_f32_mfma_supported(o.cin, o.cout)) {       // exact fp32 on the fp32 matrix pipe (csrc/conv_f32_mfma.hip)
-                    rc = launch_conv_f32_mfma((const float*)in, (const float*)blob_ptr(e, o.w_off), (const float*)blob_ptr(e, o.scale_off),
-                                              (const float*)blob_ptr(e, o.shift_off), o.res_buf >= 0 ? (const float*)tab[o.res_buf] : nullptr,
-                                              (float*)out, n, o.h, o.w, o.cin, o.oh, o.ow, o.cout, o.kh, o.kw, o.stride, o.pad_t, o.pad_l, o.act, s,
-                                              o.res_buf >= 0 ? g.stride2 : 0, g.h2, g.w2);
-                    break;
-                }
-                rc = launch_conv2d_f32((const float*)in, (const float*)blob_ptr(e, o.w_off), (const float*)blob_ptr(e, o.scale_off),
-                                       (const float*)blob_ptr(e, o.shift_off), o.res_buf >= 0 ? (const float*)tab[o.res_buf] : nullptr,
-                                       (float*)out, n, o.h, o.w, o.cin, o.oh, o.ow, o.cout, o.kh, o.kw, o.stride, o.pad_t, o.pad_l, o.act, s);
-                break;
-            case HSEFR_OP_MAXPOOL_F32:
-                rc = launch_maxpool_f32((const float*)in, (float*)out, n, o.h, o.w, o.cin, o.oh, o.ow, o.kh, o.stride, o.pad_t, o.pad_l, s);
-                break;
-            case HSEFR_OP_STEM7X7_BF16:
-                rc = launch_stem7x7_bf16((const float*)in, blob_ptr(e, o.w_off), (const float*)blob_ptr(e, o.scale_off),
-                                         (const float*)blob_ptr(e, o.shift_off), out, n, o.h, o.w, o.oh, o.ow, o.act, s);
-                break;
-            case HSEFR_OP_STEM7X7_POOL_BF16:
-                rc = launch_stem7x7_pool_bf16((const float*)in, blob_ptr(e, o.w_off), (const float*)blob_ptr(e, o.scale_off),
-                                              (const float*)blob_ptr(e, o.shift_off), out, n, o.h, o.w, o.oh, o.ow, pool_pads(o.aux).t,
-                                              pool_pads(o.aux).l, s, i < e->d_derived.size() ? e->d_derived[i] : nullptr);
-                break;
-            case HSEFR_OP_MAXPOOL_BF16:
-                rc = launch_maxpool3x3s2_bf16(in, out, n, o.h, o.w, o.cin, o.oh, o.ow, o.pad_t, o.pad_l, s);
-                break;
-            case HSEFR_OP_GAP_BF16:
-                rc = launch_gap_bf16(in, (float*)out, n, o.h * o.w, o.cin, s);
-                break;
-            case HSEFR_OP_DWPW_F32:
-                rc = launch_dwpw_fused((const float*)in, (const float*)blob_ptr(e, o.w_off), (const float*)blob_ptr(e, o.scale_off),
-                                       (const float*)blob_ptr(e, o.shift_off), (const float*)blob_ptr(e, o.w2_off),
-                                       (const float*)blob_ptr(e, o.shift2_off), (float*)out, n, o.h, o.w, o.cin, o.stride,
-                                       o.pad_t, o.pad_l, o.oh, o.ow, o.cout, HSEFR_ACT_RELU6, o.act, s);
-                break;
-            case HSEFR_OP_STEM3_F16S: {
-                const StemPack p = stem_pack(e, o);
-                const StemAux a = stem_aux(o.aux);
-                const StemKw kw = stem_kw(o.kw);
-                const int h1 = (o.h + 1) / 2, w1 = (o.w + 1) / 2;
-                if (input_u8) {
-                    rc = (g_stem5 ? launch_stem5_stream : launch_stem4_fused)(in, 1, p.conv4_u8, p.u8_descale, p.u8_shift, p.dw1, p.dw1_scale, p.dw1_shift,
-                                                                            blob_ptr(e, o.w2_off), p.descale, p.pshift, p.dw2, p.dw2_scale, p.dw2_shift,
-                                                                            (float*)out, nullptr, n, o.h, o.w, 0, a.a_log2, o.act, s);
-                    break;
-                }
-                if (g_stem4 && stem4_route(o)) {
-                    rc = (g_stem5 ? launch_stem5_stream : launch_stem4_fused)(in, 0, p.conv4, p.conv_descale, p.conv_shift, p.dw1, p.dw1_scale, p.dw1_shift,
-                                                                            blob_ptr(e, o.w2_off), p.descale, p.pshift, p.dw2, p.dw2_scale, p.dw2_shift,
-                                                                            (float*)out, e->d_overflow, n, o.h, o.w, a.in_log2, a.a_log2, o.act, s);
-                    break;
-                }
-                rc = launch_stem3_fused((const float*)in, p.conv_split, p.conv_descale, p.conv_shift, p.dw1, p.dw1_scale, p.dw1_shift,
-                                        blob_ptr(e, o.w2_off), p.descale, p.pshift, p.dw2, p.dw2_scale, p.dw2_shift, (float*)out, e->d_overflow, n,
-                                        o.h, o.w, o.pad_t, o.pad_l, h1, w1, kw.pad_t2, kw.pad_l2, o.oh, o.ow, a.in_log2, a.a_log2, o.act, s);
-                break;
-            }
-            case HSEFR_OP_STEM2_F16S: {
-                const StemPack p = stem_pack(e, o);
-                const StemKw kw = stem_kw(o.kw);
-                const int h1 = (o.h + 1) / 2, w1 = (o.w + 1) / 2;
-                rc = launch_stem2_fused((const float*)in, p.conv, p.conv_shift, p.dw1, p.dw1_scale, p.dw1_shift, blob_ptr(e, o.w2_off), p.descale,
-                                        p.pshift, p.dw2, p.dw2_scale, p.dw2_shift, (float*)out, n, o.h, o.w, o.pad_t, o.pad_l, h1, w1,
-                                        kw.pad_t2, kw.pad_l2, o.oh, o.ow, o.aux, o.act, s);
-                break;
-            }
-#ifdef HSEFR_DEV
-            case HSEFR_OP_STEM_F16S: {
-                const StemPack p = stem_pack(e, o);
-                rc = launch_stem_fused((const float*)in, p.conv, p.conv_shift, p.dw1, p.dw1_scale, p.dw1_shift, blob_ptr(e, o.w2_off), p.descale,
-                                       p.pshift, (float*)out, n, o.h, o.w, o.pad_t, o.pad_l, o.oh, o.ow, o.aux, o.act, s);
-                break;
-            }
-#endif
-            case HSEFR_OP_DWPW_F16S: {
-                const float* ds2 = (const float*)blob_ptr(e, o.shift2_off);
-                rc = launch_dwpw_f16s((const float*)in, (const float*)blob_ptr(e, o.w_off), (const float*)blob_ptr(e, o.scale_off),
-                                      (const float*)blob_ptr(e, o.shift_off), blob_ptr(e, o.w2_off), ds2, ds2 + o.cout,
-                                      (float*)out, n, o.h, o.w, o.cin, o.stride, o.pad_t, o.pad_l, o.oh, o.ow, o.cout,
-                                      o.aux, o.act, s);
-                break;
-            }
-            default:
-                set_error("forward: op %zu has unknown kind %u", i, o.kind);
-                rc = HSEFR_ERR_UNSUPPORTED;
-        }
-        if (rc != HSEFR_OK) return rc;
+        size_t covered = 0;
+        if (int rc = launch_op(e, i, tab, d_input, n, needed, s, input_u8, every_tensor, covered)) return rc;
         for (size_t k = 0; k <= covered; ++k)         // (the covered ops' own intervals are empty: their time is the flagged op's)
             if (prof) HSEFR_HIP_CHECK(hipEventRecord(pev[i + 1 + k], s));
         i += covered;
     }
     set_sweep_reverse(0);
     return HSEFR_OK;
-}
-
-static int engine_forward(hsefr_engine* e, const void* d_input, bool input_u8, int n, void* d_features, void* d_age_probs,
-                          void* d_gender, hsefr_stream_t stream);
-
-int hsefr_engine_forward(hsefr_engine* e, const void* d_input, int n, void* d_features, void* d_age_probs,
-                         void* d_gender, hsefr_stream_t stream) {
-    return engine_forward(e, d_input, false, n, d_features, d_age_probs, d_gender, stream);
-}
-
-int hsefr_engine_accepts_u8(const hsefr_engine* e) {
-    if (!e || e->ops.empty()) return 0;
-    const hsefr_plan_op& o = e->ops[0];
-    return o.kind == HSEFR_OP_STEM3_F16S && o.in_buf == HSEFR_BUF_INPUT && stem_aux(o.aux).u8 && stem4_route(o);
-}
-
-int hsefr_engine_forward_u8(hsefr_engine* e, const void* d_input_u8, int n, void* d_features, void* d_age_probs,
-                            void* d_gender, hsefr_stream_t stream) {
-    HSEFR_REQUIRE(e, HSEFR_ERR_INVALID, "forward_u8: null engine");
-    HSEFR_REQUIRE(hsefr_engine_accepts_u8(e), HSEFR_ERR_UNSUPPORTED,
-                  "forward_u8: this plan takes no uint8 input (it needs the fused stem lowered with a BGR mean and an input whose "
-                  "edges are multiples of 4)");
-    return engine_forward(e, d_input_u8, true, n, d_features, d_age_probs, d_gender, stream);
 }
 
 static int engine_forward(hsefr_engine* e, const void* d_input, bool input_u8, int n, void* d_features, void* d_age_probs,
@@ -1045,6 +952,26 @@ static int engine_forward(hsefr_engine* e, const void* d_input, bool input_u8, i
     return HSEFR_OK;
 }
 
+int hsefr_engine_forward(hsefr_engine* e, const void* d_input, int n, void* d_features, void* d_age_probs,
+                         void* d_gender, hsefr_stream_t stream) {
+    return engine_forward(e, d_input, false, n, d_features, d_age_probs, d_gender, stream);
+}
+
+int hsefr_engine_accepts_u8(const hsefr_engine* e) {
+    if (!e || e->ops.empty()) return 0;
+    const hsefr_plan_op& o = e->ops[0];
+    return o.kind == HSEFR_OP_STEM3_F16S && o.in_buf == HSEFR_BUF_INPUT && stem_aux(o.aux).u8 && stem4_route(o);
+}
+
+int hsefr_engine_forward_u8(hsefr_engine* e, const void* d_input_u8, int n, void* d_features, void* d_age_probs,
+                            void* d_gender, hsefr_stream_t stream) {
+    HSEFR_REQUIRE(e, HSEFR_ERR_INVALID, "forward_u8: null engine");
+    HSEFR_REQUIRE(hsefr_engine_accepts_u8(e), HSEFR_ERR_UNSUPPORTED,
+                  "forward_u8: this plan takes no uint8 input (it needs the fused stem lowered with a BGR mean and an input whose "
+                  "edges are multiples of 4)");
+    return engine_forward(e, d_input_u8, true, n, d_features, d_age_probs, d_gender, stream);
+}
+
 int hsefr_plan_describe(const void* plan, size_t plan_bytes, int n, char* out, size_t out_bytes) {
     HSEFR_REQUIRE(out && out_bytes > 0 && n > 0, HSEFR_ERR_INVALID, "plan_describe: bad argument");
     out[0] = 0;
@@ -1059,26 +986,18 @@ int hsefr_plan_describe(const void* plan, size_t plan_bytes, int n, char* out, s
     e.d_bufs.resize(e.hdr.n_buffers);
     for (uint32_t i = 0; i < e.hdr.n_buffers; ++i) e.d_bufs[i] = reinterpret_cast<void*>((uintptr_t(2) << 40) + (uintptr_t(i) << 32));
     std::string text;
-    std::vector<char> only(e.ops.size(), 0);
+    const std::vector<char> all(e.ops.size(), 1);
     for (size_t i = 0; i < e.ops.size(); ++i) {
-        // op i alone, then with the ops its flags cover (a flagged op's launch needs them `needed`)
-        std::fill(only.begin(), only.end(), 0);
-        only[i] = 1;
-        const size_t span = (e.ops[i].flags & HSEFR_OPF_PAIR_NEXT)                      ? 1
-                            : (e.ops[i].flags & HSEFR_OPF_HEADS)                        ? 3
-                            : ((e.ops[i].flags & HSEFR_OPF_DWPW_NEXT) && !dwpw_s2_off()) ? 1
-                                                                                        : 0;
-        for (size_t k = 1; k <= span && i + k < e.ops.size(); ++k) only[i + k] = 1;
         std::string line = std::to_string(i) + "\t" + std::to_string(e.ops[i].kind) + "\t";
+        size_t covered = 0;
         g_route_sink = &line;
-        rc = run_ops(&e, e.d_bufs, reinterpret_cast<const void*>(uintptr_t(3) << 40), n, only, nullptr, nullptr,
-                     false);
+        rc = launch_op(&e, i, e.d_bufs, reinterpret_cast<const void*>(uintptr_t(3) << 40), n, all, nullptr, false, false, covered);
         g_route_sink = nullptr;
         if (rc != HSEFR_OK) { e.d_blob = nullptr; e.d_overflow = nullptr; e.d_bufs.clear(); return rc; }
         text += line + "\n";
-        for (size_t k = 1; k <= span && i + k < e.ops.size(); ++k)
+        for (size_t k = 1; k <= covered; ++k)
             text += std::to_string(i + k) + "\t" + std::to_string(e.ops[i + k].kind) + "\t(inside op " + std::to_string(i) + ")\n";
-        i += span;
+        i += covered;
     }
     e.d_blob = nullptr; e.d_overflow = nullptr; e.d_bufs.clear();     // (stand-ins: nothing to free)
     HSEFR_REQUIRE(text.size() + 1 <= out_bytes, HSEFR_ERR_INVALID, "plan_describe: the table needs %zu bytes, the buffer holds %zu", text.size() + 1, out_bytes);

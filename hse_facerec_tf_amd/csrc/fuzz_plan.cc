@@ -27,15 +27,25 @@ static uint64_t rnd() {
 }
 
 static long long n_ok = 0, n_err = 0, n_silent = 0;
+// FNV-1a over every status the library returned and, for a refusal, its message: two builds that validate alike print one hash
+static uint64_t g_hash = 0xcbf29ce484222325ull;
+static void fold(int rc) {
+    auto mix = [](unsigned char b) { g_hash = (g_hash ^ b) * 0x100000001b3ull; };
+    for (int k = 0; k < 4; ++k) mix((unsigned char)((uint32_t)rc >> (8 * k)));
+    if (rc != HSEFR_OK)
+        for (const char* m = hsefr_last_error_string(); *m; ++m) mix((unsigned char)*m);
+}
 
 static void run_one(const void* blob, size_t bytes, const char* what) {
     int rc = hsefr_plan_validate(blob, bytes);
+    fold(rc);
     if (rc == HSEFR_OK) {
         ++n_ok;
         // the launch wrappers' host side (shape checks, tile choices, grid arithmetic) on the mutant's shapes: every launcher runs with the
         // launch suppressed (hsefr_plan_describe) -- HSEFR_OK or a status with a message
         static char table[1 << 18];
         const int rd = hsefr_plan_describe(blob, bytes, 4, table, sizeof(table));
+        fold(rd);
         if (rd != HSEFR_OK && !hsefr_last_error_string()[0]) { ++n_silent; fprintf(stderr, "no message for status %d (%s, plan_describe)\n", rd, what); }
         hsefr_engine* e = nullptr;
         rc = hsefr_engine_create(blob, bytes, 4, &e);       // valid: goes on to the device (none here: HSEFR_ERR_HIP / NOMEM) or succeeds
@@ -140,6 +150,6 @@ int main(int argc, char** argv) {
         if (memcmp(w, seed.data(), bytes) != 0) { fprintf(stderr, "internal: working copy not restored\n"); return 1; }
         free(w);
     }
-    printf("fuzz_plan: %lld mutants still valid, %lld refused, %lld without a message\n", n_ok, n_err, n_silent);
+    printf("fuzz_plan: %lld mutants still valid, %lld refused, hash %016llx, %lld without a message\n", n_ok, n_err, (unsigned long long)g_hash, n_silent);
     return n_silent ? 1 : 0;
 }

@@ -5,15 +5,7 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
-/* Tuning/debug knobs, process-wide, never needed for correct results.
- * "pw_tile": -1 = choose per layer (default), 0 = 128x128, 1 = 128x64, 2 = 64x64 GEMM tile.
- * "pw_dma":  1 = GEMM tiles staged by LDS-DMA (global_load_lds, default), 0 = through registers.
- * "pw_ablate": timing-only ablations of the GEMM (results are WRONG): bit 0 = no global loads after the first
- *            K-tile, bit 1 = no epilogue stores.  0 = the real kernel (default).
- * "dw_th":   0 = choose per layer (default), >0 = output rows per depthwise strip.
- * "dw_variant": cache policy of the depthwise kernel: bit 0 = nontemporal loads, bit 1 = nontemporal stores.
- * "copy_variant": shape of the hsefr_debug_copy calibration kernel (unroll / nontemporal / grid bits).
- * "c3_impl": 0 = auto (default), 1 = VALU first-conv kernel, 2 = im2col fp32-MFMA first-conv kernel. */
+/* Tuning/debug knobs, process-wide, never needed for correct results.  A key's meaning is the comment on its HSEFR_KNOB line in csrc/. */
 int hsefr_debug_set(const char* key, int value);
 /* Calibration: plain float4 device-to-device copy kernel (the practical HBM ceiling on this GPU). */
 int hsefr_debug_copy(const void* d_src, void* d_dst, size_t bytes, hsefr_stream_t stream);

@@ -361,11 +361,8 @@ int launch_l2_normalize(const float* x, float* y, int n, int d, hipStream_t s) {
     return launch_status("l2_normalize");
 }
 
-HSEFR_KNOB(g_nn1_y_mb, 256);      // dev builds: bound of the distance-matrix slice in MiB (tests force several query blocks with a small one)
+HSEFR_KNOB(g_nn1_y_mb, "nn1_y_mb", 256, [](int v) { return v > 0 ? v : 1; });      // dev builds: bound of the distance-matrix slice in MiB (tests force several query blocks with a small one)
 #define NN1_Y_BYTES ((long long)g_nn1_y_mb << 20)
-#ifdef HSEFR_DEV
-void set_nn1_y_mb(int v) { g_nn1_y_mb = v > 0 ? v : 1; }
-#endif
 
 static std::atomic<long long> g_nn1_fallbacks{0};
 long long nn1_fallbacks() { return g_nn1_fallbacks.load(); }

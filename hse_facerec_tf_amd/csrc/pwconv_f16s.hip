@@ -333,7 +333,7 @@ int choose_tile(long long m, int cout, int forced) {
     return best;
 }
 
-HSEFR_KNOB(g_forced_tile, -1);  // dev builds: 0 = 128x128, 1 = 128x64, 2 = 64x64
+HSEFR_KNOB(g_forced_tile, "pws_tile", -1);  // dev builds: 0 = 128x128, 1 = 128x64, 2 = 64x64
 
 template <int BM, int BN, int WAVES_N, int OCC>
 int launch_cfg(const float* x, const void* wsplit, const float* descale, const float* shift, float* y, long long m, int k,
@@ -357,9 +357,6 @@ int launch_cfg(const float* x, const void* wsplit, const float* descale, const f
 
 }  // namespace
 
-#ifdef HSEFR_DEV
-void set_pws_tile(int v) { g_forced_tile = v; }
-#endif
 
 int read_pws_stamps(void* host_out, size_t bytes) {
 #ifdef HSEFR_PWS_STAMPS

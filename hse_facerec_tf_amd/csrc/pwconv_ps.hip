@@ -698,9 +698,9 @@ int choose_mb(long long m, int cout, int forced) {
     return best;
 }
 
-HSEFR_KNOB(g_ps_mb, 0);   // dev builds: 8 | 9 = forced tile height / 32
-HSEFR_KNOB(g_ps_grid, 0); // dev builds: > 0 = forced number of persistent workgroups (contention experiments)
-HSEFR_KNOB(g_psdw_mode, 0); // dev builds: 1 = the masked depthwise epilogue on 12 x 12 maps too (A/B against the bordered one)
+HSEFR_KNOB(g_ps_mb, "ps_mb", 0);   // dev builds: 8 | 9 = forced tile height / 32
+HSEFR_KNOB(g_ps_grid, "ps_grid", 0); // dev builds: > 0 = forced number of persistent workgroups (contention experiments)
+HSEFR_KNOB(g_psdw_mode, "psdw_mode", 0); // dev builds: 1 = the masked depthwise epilogue on 12 x 12 maps too (A/B against the bordered one)
 
 template <int MB>
 int launch_mb(const void* xs, const void* wsplit, const float* descale, const float* shift, float* y, long long m, int k, int cout,
@@ -726,9 +726,6 @@ int launch_mb(const void* xs, const void* wsplit, const float* descale, const fl
 }  // namespace
 
 #ifdef HSEFR_DEV
-void set_ps_mb(int v) { g_ps_mb = v; }
-void set_ps_grid(int v) { g_ps_grid = v; }
-void set_psdw_mode(int v) { g_psdw_mode = v; }
 int read_ps_stamps(void* host_out, size_t bytes) {
 #ifdef HSEFR_PS_STAMPS
     HSEFR_REQUIRE(bytes <= sizeof(unsigned long long) * 256 * 12 * 8, HSEFR_ERR_INVALID, "read_ps_stamps: too many bytes");

@@ -473,10 +473,7 @@ __global__ __launch_bounds__(256, 2) void stem4_fused_kernel(Stem4Params p) {
 
 }  // namespace
 
-HSEFR_KNOB(g_stem4_grid, 512);      // dev builds: persistent workgroups of the launch (256 = one per CU: latency experiments)
-#ifdef HSEFR_DEV
-void set_stem4_grid(int v) { g_stem4_grid = v; }
-#endif
+HSEFR_KNOB(g_stem4_grid, "stem4_grid", 512);      // dev builds: persistent workgroups of the launch (256 = one per CU: latency experiments)
 
 bool stem4_fused_supported(int cin, int c1, int c2, int conv_stride, int dw1_stride, int dw2_stride, int kh, int kw, int h, int w) {
     return cin == 3 && c1 == 32 && c2 == 64 && conv_stride == 2 && dw1_stride == 1 && dw2_stride == 2 && kh == 3 && kw == 3 &&

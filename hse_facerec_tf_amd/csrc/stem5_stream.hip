@@ -490,12 +490,8 @@ __global__ __launch_bounds__(64 * WAVES, S5_WGS) void stem5_stream_kernel(Stem5P
 
 }  // namespace
 
-HSEFR_KNOB(g_stem5_grid, 256 * S5_WGS);   // dev builds: workgroups of the launch (S5_WGS per CU resident)
-HSEFR_KNOB(g_stem5_segs, 0);        // dev builds: vertical segments per strip (0 = chosen by the launcher)
-#ifdef HSEFR_DEV
-void set_stem5_grid(int v) { g_stem5_grid = v; }
-void set_stem5_segs(int v) { g_stem5_segs = v; }
-#endif
+HSEFR_KNOB(g_stem5_grid, "stem5_grid", 256 * S5_WGS);   // dev builds: workgroups of the launch (S5_WGS per CU resident)
+HSEFR_KNOB(g_stem5_segs, "stem5_segs", 0);        // dev builds: vertical segments per strip (0 = chosen by the launcher)
 
 bool stem5_stream_supported(int cin, int c1, int c2, int conv_stride, int dw1_stride, int dw2_stride, int kh, int kw, int h, int w) {
     return cin == 3 && c1 == 32 && c2 == 64 && conv_stride == 2 && dw1_stride == 1 && dw2_stride == 2 && kh == 3 && kw == 3 &&

@@ -332,12 +332,11 @@ __global__ __launch_bounds__(64 * WAVES, 2) void stem7s_stream_kernel(Stem7sPara
     S7_STAMP_FLUSH;
 }
 
-HSEFR_KNOB(g_stem7s, 1);     // dev builds: 0 = the patch kernel (stem7x7_pool.hip) also where this one covers the shape (A/B timing)
+HSEFR_KNOB(g_stem7s, "stem7s", 1);     // dev builds: 0 = the patch kernel (stem7x7_pool.hip) also where this one covers the shape (A/B timing)
 
 }  // namespace
 
 #ifdef HSEFR_DEV
-void set_stem7s(int v) { g_stem7s = v; }
 int read_s7_stamps(void* host_out, size_t bytes) {
 #ifdef HSEFR_S7_STAMPS
     HSEFR_REQUIRE(bytes <= sizeof(unsigned long long) * 512 * 4 * 10, HSEFR_ERR_INVALID, "read_s7_stamps: too many bytes");

@@ -258,3 +258,42 @@ def test_round_one_stem_left_the_product_library():
     rc = L.hsefr_plan_validate(ctypes.cast(buf, ctypes.c_void_p), len(blob))
     assert rc == _lib.ERR_UNSUPPORTED and "development builds" in _lib.last_error()
     assert os.path.getsize(_lib.LIB_PATH) < 4_000_000
+
+
+KNOB_KEYS = ("pw_tile pws_tile ps_mb ps_grid psdw_mode cd_rb cd_off w3_off w2_off w4_off w4_bres nn1_y_mb c11 c11_tile c11_bres c11_adv stem4_grid "
+             "stem4 stem5 stem5_grid stem5_segs pair_off stem7s pair_ablate pair_nt heads_off dw_look dw_look2 sweep_alternate clock_mode dwpw_s2_off "
+             "dwpws_tw dwpws_bn pw_ablate pw_dma dw_th dw_variant copy_variant c3_impl").split()
+
+
+def test_every_development_knob_is_one_registering_line():
+    """A knob is its HSEFR_KNOB(variable, "key", value) line in csrc/*.hip and nothing else: the 39 keys are each defined exactly once, no
+    per-knob setter is left, and every key a tool or a test passes to hsefr_debug_set (or through KNOBS=) exists."""
+    import glob
+    csrc = os.path.join(ROOT, "hse_facerec_tf_amd", "csrc")
+    found, setters = [], []
+    for path in sorted(glob.glob(os.path.join(csrc, "*.hip"))):
+        src = open(path).read()
+        lines = re.findall(r"HSEFR_KNOB\(([^\n]*)", src)
+        keys = re.findall(r'HSEFR_KNOB\(\s*\w+\s*,\s*"(\w+)"\s*,', src)
+        assert len(keys) == len(lines), (path, lines)              # every use of the macro names its key
+        found += keys
+        setters += re.findall(r"void\s+(set_\w*)\s*\(\s*int\s+v\s*\)", src)
+    assert sorted(found) == sorted(KNOB_KEYS) and len(KNOB_KEYS) == 39
+    assert setters == ["set_sweep_reverse"]
+    for path in glob.glob(os.path.join(csrc, "*.h")):
+        assert re.findall(r"void\s+(set_\w*)\s*\(\s*int\s+v\s*\)", open(path).read()) in ([], ["set_sweep_reverse"]), path
+    used = set()
+    for path in glob.glob(os.path.join(ROOT, "tools", "*.py")) + glob.glob(os.path.join(ROOT, "tests", "*.py")):
+        src = open(path).read()
+        for assignments in re.findall(r"KNOBS=([a-z0-9_=,-]+)", src):
+            used |= {kv.split("=")[0] for kv in assignments.split(",")}
+        used |= set(re.findall(r'hsefr_debug_set\(b"(\w+)"', src))
+        if "hsefr_debug_set" in src and os.path.basename(os.path.dirname(path)) == "tools":       # ... or in a table of (key, ...) a tool's call loops over
+            used |= set(re.findall(r'\(b"([a-z0-9_]+)", ', src))
+    assert len(used) >= 20 and used <= set(KNOB_KEYS), sorted(used - set(KNOB_KEYS))
+    from hse_facerec_tf_amd import _lib
+    L = _lib.lib()
+    if hasattr(L, "hsefr_debug_set"):
+        bogus = b"no_such_knob"
+        assert L.hsefr_debug_set(bogus, 1) == _lib.ERR_INVALID and _lib.last_error() == "debug_set: unknown key no_such_knob"
+        assert L.hsefr_debug_set(None, 1) == _lib.ERR_INVALID and _lib.last_error() == "debug_set: null key"

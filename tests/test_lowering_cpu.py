@@ -453,6 +453,32 @@ def test_plan_describe_routes_the_baseline_plans_to_product_kernels_only():
             assert dev_only not in syms, dev_only
 
 
+def test_plan_describe_lists_the_covered_layers_where_the_fused_launch_is_not_taken():
+    """Plan.describe() asks the function that launches an op, so it shows the launches a forward makes: with the development knob
+    heads_off=1 the three layers behind the flagged DENSE layer of the three-output 224 plan each have their own kernel; with the knob
+    back at 0 they are inside its launch.  (Before that function existed, describe decided the coverage on its own and failed this.)"""
+    from conftest import MODEL_PB
+    from hse_facerec_tf_amd import _lib, graphdef, lowering
+    L = _lib.lib()
+    if not hasattr(L, "hsefr_debug_set"):
+        pytest.skip("the heads_off knob exists in development builds of the library only")
+    outs = {0: "global_pooling/Mean:0", 1: "age_pred/Softmax:0", 2: "gender_pred/Sigmoid:0"}
+    plan = lowering.lower_graph(graphdef.read_graph(MODEL_PB), "input_1:0", outs, (224, 224), input_bound=256.0)
+    head = len(plan.layers) - 4
+    assert plan.layers[head].flags & lowering.OPF_HEADS
+    _lib.check(L.hsefr_debug_set(b"heads_off", 1))
+    try:
+        apart = plan.describe(512)
+    finally:
+        _lib.check(L.hsefr_debug_set(b"heads_off", 0))
+    fused = plan.describe(512)
+    for r in apart[-4:]:
+        assert r["inside"] is None and r["kernels"], r
+    assert [r["family"] for r in apart[-4:]] == [["dense_kernel"], ["dense_kernel"], ["softmax_kernel"], ["dense_kernel"]]
+    assert fused[head]["family"] == ["heads_kernel"] and [r["inside"] for r in fused[-3:]] == [head] * 3
+    assert apart[:head] == fused[:head]
+
+
 def _chain(*src_res):
     """Layers 0 .. n-1 of one shape, layer i reading (src, res) = src_res[i]."""
     return [lowering.Layer(lowering.OP_CONV_BF16, "L%d" % i, s, (4, 4, 64), (4, 4, 64), res=r) for i, (s, r) in enumerate(src_res)]

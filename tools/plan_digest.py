@@ -2,7 +2,12 @@
 
 The instrument for a change to hse_facerec_tf_amd/lowering.py that must not change a plan: run it before and after and diff the two
 listings.  The matrix makes every graph-to-plan pass fire, and makes every pass decline because its tensor is a requested output.
-usage: python tools/plan_digest.py > listing.txt"""
+usage: python tools/plan_digest.py > listing.txt
+
+--describe adds, per plan, a SHA-256 of plan.describe(n) at n = 1, 4 and 256: the instrument for a change to the engine's host code
+that must not change a route.  It asks the loaded library (HSEFR_LIB selects the file; no GPU needed); the product library refuses
+round 1's stem, so there the stem_fusion="stem" rows are left out, as are the requests the lowering refuses.  Every hash of such a listing is cut to its first 12 hex digits:
+enough to tell two listings apart, and a listing that is kept stays small."""
 import hashlib
 import itertools
 import os
@@ -45,16 +50,44 @@ def digest(plan) -> str:
     return h.hexdigest()
 
 
+DESCRIBE_BATCHES = (1, 4, 256)
+describe_routes = False          # --describe
+dev_library = False
+
+
+def routes(plan) -> str:
+    """`n1,n4=... n256=...`: batch sizes with one result share an entry."""
+    results = {}
+    for n in DESCRIBE_BATCHES:
+        try:
+            r = hashlib.sha256(repr(plan.describe(n)).encode()).hexdigest()[:12]
+        except (ValueError, NotImplementedError) as e:          # the library's refusal (_lib.check)
+            r = "%s:%s" % (type(e).__name__, hashlib.sha256(str(e).encode()).hexdigest()[:12])      # (its message, hashed)
+        results.setdefault(r, []).append("n%d" % n)
+    return " ".join("%s=%s" % (",".join(ns), r) for r, ns in results.items())
+
+
 def show(what: str, opts: dict, make) -> None:
     """`make` builds the plan; a request the lowering refuses is listed with its refusal."""
+    if describe_routes and not dev_library and opts.get("stem_fusion") == "stem":
+        return
     try:
-        result = digest(make())
+        plan = make()
+        result = digest(plan)
+        if describe_routes:
+            result = result[:12] + " " + routes(plan)
     except lowering.LoweringError as e:
+        if describe_routes:          # no plan, no routes
+            return
         result = "LoweringError: %s" % e
     print("%s %s %s" % (what, " ".join("%s=%r" % kv for kv in sorted(opts.items())) or "defaults", result))
 
 
 def main() -> None:
+    global describe_routes, dev_library
+    if "--describe" in sys.argv[1:]:
+        from hse_facerec_tf_amd import _lib
+        describe_routes, dev_library = True, hasattr(_lib.lib(), "hsefr_debug_set")
     g = graphdef.read_graph(MODEL_PB)
     for size, opts in itertools.product((96, 98, 100, 192, 224), OPTION_SETS):
         show("mobilenet %d" % size, opts, lambda: lowering.lower_graph(g, "input_1:0", ALL_OUTS, (size, size), **opts))
