@@ -206,6 +206,10 @@ int launch_nn1(const float* q, const float* g, int nq, int ng, int d, int* nn_in
 int launch_knn(const float* q, const float* g, int nq, int ng, int d, int k, int* nn_index, float* nn_dist2, const int* g_label, int* pred,
                hipStream_t s);
 long long nn1_fallbacks();
+int launch_pca_fit(const float* x, int n, int d, int k, int max_iter, double* mean, double* components, double* explained_variance, int* info,
+                   hipStream_t s);
+int launch_pca_transform(const float* x, int n, int d, int k, const double* mean, const double* components, float* z, int ldz,
+                         hipStream_t s);
 
 int launch_conv_bf16(const void* x, const void* wt, const float* scale, const float* shift, const void* res, void* y,
                      int n, int h, int w, int c, int oh, int ow, int cout, int kh, int kw, int stride, int pad_t,

@@ -1311,6 +1311,22 @@ int hsefr_knn(const float* q, const float* g, int nq, int ng, int d, int k, int*
 
 long long hsefr_nn1_fallbacks(void) { return nn1_fallbacks(); }
 
+int hsefr_pca_fit(const float* x, int n, int d, int k, int max_iter, double* mean, double* components, double* explained_variance, int* info,
+                  hsefr_stream_t stream) {
+    HSEFR_REQUIRE(x && mean && components && explained_variance && info, HSEFR_ERR_INVALID,
+                  "pca_fit: null pointer (x %p, mean %p, components %p, explained_variance %p, info %p)", (const void*)x, (const void*)mean,
+                  (const void*)components, (const void*)explained_variance, (const void*)info);
+    return launch_pca_fit(x, n, d, k, max_iter, mean, components, explained_variance, info, (hipStream_t)stream);
+}
+
+int hsefr_pca_transform(const float* x, int n, int d, int k, const double* mean, const double* components, float* z, int ldz,
+                        hsefr_stream_t stream) {
+    HSEFR_REQUIRE(n == 0 || (x && mean && components && z), HSEFR_ERR_INVALID,
+                  "pca_transform: null pointer (x %p, mean %p, components %p, z %p)", (const void*)x, (const void*)mean,
+                  (const void*)components, (const void*)z);
+    return launch_pca_transform(x, n, d, k, mean, components, z, ldz, (hipStream_t)stream);
+}
+
 int hsefr_conv2d_direct(const float* x, const float* wgt, const float* bias, const float* alpha, float* y, int n, int h, int w, int c,
                         int oh, int ow, int cout, int kh, int kw, int stride, int pad_t, int pad_l, hsefr_stream_t stream) {
     HSEFR_REQUIRE(n == 0 || (x && wgt && y), HSEFR_ERR_INVALID, "conv2d_direct: null pointer");

@@ -4,7 +4,9 @@ Host steps stay what the reference does on the host -- including its own scikit-
 for the label encoding and the stratified split (scikit-learn is a dependency of the
 reference's callers, not of the engine); the O(N_test x N_train x D) nearest-neighbour search
 (KNeighborsClassifier(1).fit/predict, :422,:203) and the L2 normalisation (:401) run through
-libhsefr (ops.l2_normalize / ops.nn1; ops.knn for the reference's '3-NN' rows, facerec_test.py:269-288).
+libhsefr (ops.l2_normalize / ops.nn1; ops.knn for the reference's '3-NN' rows, facerec_test.py:269-288).  The PCA of the '+PCA' rows
+is scikit-learn's on the host by default (``pca="host"``) or the library's deterministic fp64 fit and projection on the device
+(``pca="device"``: ops.pca_fit / ops.pca_transform, nothing leaves the GPU between the features and the search).
 """
 from __future__ import annotations
 
@@ -63,6 +65,24 @@ def start_split(y: np.ndarray, random_state: int = 0) -> SplitJob:
     return SplitJob(np.asarray(y), random_state)
 
 
+PCA_MAX_ITER = 1000     # hsefr_pca_fit's iteration cap on the pca="device" path; reaching it raises
+
+
+def check_pca_mode(pca) -> str:
+    if pca not in ("host", "device"):
+        raise ValueError("pca=%r must be 'host' (scikit-learn on the CPU) or 'device' (ops.pca_fit / ops.pca_transform)" % (pca,))
+    return pca
+
+
+def _device_pca(ops, gal, qry, pca_components: int):
+    """Fit on the gallery, project both sets (float32, zero-padded to a multiple of 8 columns), all on the device."""
+    mean, components, _, info = ops.pca_fit(gal, pca_components, max_iter=PCA_MAX_ITER)
+    if not info["converged"]:
+        raise RuntimeError("the device PCA of the %d x %d gallery (%d components) did not converge in %d iterations"
+                           % (gal.shape[0], gal.shape[1], pca_components, info["iterations"]))
+    return ops.pca_transform(gal, mean, components), ops.pca_transform(qry, mean, components)
+
+
 def _knn_predict(ops, qry, gal, y_gallery: np.ndarray, n_neighbors: int):
     """KNeighborsClassifier(n_neighbors).fit(gal, y_gallery) -> kneighbors + predict of ``qry`` on the device (ops.knn).  The labels are
     encoded with np.unique, so the vote's smallest-label rule runs over scikit-learn's sorted ``classes_`` and any label type works.
@@ -77,7 +97,7 @@ def _knn_predict(ops, qry, gal, y_gallery: np.ndarray, n_neighbors: int):
 
 def one_nn_identification(X, y: np.ndarray, split=None,
                           pca_components: Optional[int] = None, timings: Optional[dict] = None, device=None,
-                          n_neighbors: int = 1) -> Dict:
+                          n_neighbors: int = 1, pca: str = "host") -> Dict:
     """The protocol of facerec_test.py:401-432: 'k-NN' (pca_components=None) or 'k-NN+PCA'
     (pca_components=128, the Pipeline of :421 -- PCA is fitted on the gallery half by scikit-learn on
     the host, exactly as the reference does, and the projected vectors go back to the device for the search).
@@ -88,10 +108,16 @@ def one_nn_identification(X, y: np.ndarray, split=None,
     device-synchronised wall seconds of each phase: normalize_s, host_split_s, select_s, nn1_s, readback_s (indices and
     distances back to the host + the label comparison).
     n_neighbors: 1 labels a probe by its nearest gallery row (ops.nn1); more by the uniform vote of that many (ops.knn: 'nn_index' and
-    'nn_dist' become [nq, k]; the search is still timed as nn1_s)."""
+    'nn_dist' become [nq, k]; the search is still timed as nn1_s).
+    pca: "host" fits and applies scikit-learn's PCA on the CPU as above; "device" runs ops.pca_fit on the gallery and
+    ops.pca_transform on both halves without leaving the GPU (deterministic fp64; a fit that does not converge raises RuntimeError)
+    and records the phase in ``timings`` as pca_s."""
     import time
     from . import _lib, ops
     ops.check_n_neighbors(n_neighbors)
+    check_pca_mode(pca)
+    if pca_components and pca == "device":
+        ops.check_pca_components(pca_components)
     torch = _lib.require_gpu()
     if isinstance(X, np.ndarray):
         X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(_lib.cuda_device(device))
@@ -117,13 +143,16 @@ def one_nn_identification(X, y: np.ndarray, split=None,
     gal = Xn[torch.from_numpy(train).to(Xn.device)].contiguous()
     qry = Xn[torch.from_numpy(test).to(Xn.device)].contiguous()
     t = lap("select_s", t)
-    if pca_components:
+    if pca_components and pca == "device":
+        gal, qry = _device_pca(ops, gal, qry, pca_components)
+        t = lap("pca_s", t)
+    elif pca_components:
         from sklearn.decomposition import PCA
-        pca = PCA(n_components=pca_components).fit(gal.cpu().numpy())
+        fitted = PCA(n_components=pca_components).fit(gal.cpu().numpy())
         pad = (-pca_components) % 8                      # hsefr_nn1 wants d % 8 == 0: zero columns change no distance
 
         def proj(t):
-            z = pca.transform(t.cpu().numpy()).astype(np.float32)
+            z = fitted.transform(t.cpu().numpy()).astype(np.float32)
             return torch.from_numpy(np.pad(z, ((0, 0), (0, pad)))).to(Xn.device).contiguous()
         gal, qry = proj(gal), proj(qry)
     if n_neighbors == 1:
@@ -201,16 +230,21 @@ def cross_validated_1nn(X, y: np.ndarray, cv, normalize: bool = True, device=Non
 
 
 def gallery_probe_identification(X_train, y_train: np.ndarray, X_test, y_test: np.ndarray, normalize: bool = False,
-                                 pca_components: Optional[int] = None, device=None, n_neighbors: int = 1) -> Dict:
+                                 pca_components: Optional[int] = None, device=None, n_neighbors: int = 1, pca: str = "host") -> Dict:
     """The gallery / probe protocol of tf_train_test_recognition (facerec_test.py:260-288): the '1-NN' classifier (and
     '1-NN+PCA' with ``pca_components``, 16 at :269) FITTED on the gallery features, every probe labelled by its nearest
     gallery row; accuracy = share of probes whose label is right (:287).  NB the reference computes L2-normalised copies
     (:262,265) and then fits / predicts on the UN-normalised ``X_train`` / ``X_test`` (:284-285): ``normalize=False`` is what
     it runs, ``normalize=True`` what the copies suggest it meant.  The search runs on the GPU (hsefr_nn1: ties -> the lowest
     gallery index, scikit-learn's own choice).  ``n_neighbors`` > 1 gives the '3-NN' / '3-NN+PCA' rows of :269-272 (hsefr_knn: the
-    uniform vote, equal counts to the smallest label as in scikit-learn's predict; 'nn_index' and 'nn_dist' become [nq, k])."""
+    uniform vote, equal counts to the smallest label as in scikit-learn's predict; 'nn_index' and 'nn_dist' become [nq, k]).
+    ``pca``: "host" is scikit-learn's PCA on the CPU; "device" fits on the gallery and projects both sets with ops.pca_fit /
+    ops.pca_transform on the GPU (deterministic fp64; a fit that does not converge raises RuntimeError)."""
     from . import _lib, ops
     ops.check_n_neighbors(n_neighbors, len(np.asarray(y_train)))
+    check_pca_mode(pca)
+    if pca_components and pca == "device":
+        ops.check_pca_components(pca_components, len(np.asarray(y_train)))
     torch = _lib.require_gpu()
     dev = _lib.cuda_device(device)
 
@@ -222,13 +256,15 @@ def gallery_probe_identification(X_train, y_train: np.ndarray, X_test, y_test: n
     if gal.shape[0] != len(y_train) or qry.shape[0] != len(y_test):
         raise ValueError("features and labels differ in length: %d/%d gallery, %d/%d probe"
                          % (gal.shape[0], len(y_train), qry.shape[0], len(y_test)))
-    if pca_components:
+    if pca_components and pca == "device":
+        gal, qry = _device_pca(ops, gal, qry, pca_components)
+    elif pca_components:
         from sklearn.decomposition import PCA
-        pca = PCA(n_components=pca_components).fit(gal.cpu().numpy())
+        fitted = PCA(n_components=pca_components).fit(gal.cpu().numpy())
         pad = (-pca_components) % 8
 
         def proj(t):
-            z = pca.transform(t.cpu().numpy()).astype(np.float32)
+            z = fitted.transform(t.cpu().numpy()).astype(np.float32)
             return torch.from_numpy(np.pad(z, ((0, 0), (0, pad)))).to(dev).contiguous()
         gal, qry = proj(gal), proj(qry)
     if n_neighbors == 1:

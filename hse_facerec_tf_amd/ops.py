@@ -488,6 +488,63 @@ def knn(queries, gallery, k: int, labels=None):
     return idx, dist, pred
 
 
+PCA_MAX_K = 256    # hsefr_pca_fit's largest component count (the largest the reference names)
+
+
+def check_pca_components(k, n=None, d=None) -> int:
+    """hsefr_pca_fit's range of k, raised as ValueError before the library is called: 1 <= k <= min(n - 1, d, 256) (with k = min(n, d)
+    scikit-learn's last component has zero variance and an arbitrary direction)."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise ValueError("pca_components must be an integer, got %r" % (k,))
+    if k < 1 or k > PCA_MAX_K:
+        raise ValueError("pca_components=%d must be in 1..%d" % (k, PCA_MAX_K))
+    if n is not None and k > n - 1:
+        raise ValueError("pca_components=%d exceeds n - 1 for the %d rows to fit on" % (k, n))
+    if d is not None and k > d:
+        raise ValueError("pca_components=%d exceeds the %d features" % (k, d))
+    return int(k)
+
+
+@_device_guarded
+def pca_fit(x, k: int, max_iter: int = 1000):
+    """PCA(n_components=k).fit(x) as a deterministic fp64 computation on the device (hsefr_pca_fit): x [n,d] float32 ->
+    (mean [d], components [k,d], explained_variance [k]) float64 device tensors and info = {"iterations", "converged"}.  The sign of
+    each component is scikit-learn 1.7's (its entry of largest magnitude is positive).  A fit that stops at ``max_iter`` is returned
+    with converged False: the caller decides."""
+    k = check_pca_components(k, x.shape[0], x.shape[1])      # before anything touches a device
+    if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or max_iter < 1:
+        raise ValueError("max_iter must be a positive integer, got %r" % (max_iter,))
+    torch = _lib.require_gpu()
+    _f32c(x, "x")
+    n, d = x.shape
+    mean = torch.empty((d,), dtype=torch.float64, device=x.device)
+    components = torch.empty((k, d), dtype=torch.float64, device=x.device)
+    variance = torch.empty((k,), dtype=torch.float64, device=x.device)
+    info = torch.zeros((2,), dtype=torch.int32, device=x.device)
+    _lib.check(_lib.lib().hsefr_pca_fit(x.data_ptr(), n, d, k, int(max_iter), mean.data_ptr(), components.data_ptr(), variance.data_ptr(),
+                                        info.data_ptr(), _lib.current_stream_ptr()), "hsefr_pca_fit")
+    iterations, converged = info.cpu().tolist()
+    return mean, components, variance, {"iterations": int(iterations), "converged": bool(converged)}
+
+
+@_device_guarded
+def pca_transform(x, mean, components):
+    """(x - mean) . components^T accumulated in fp64 and rounded once to float32 (hsefr_pca_transform): [n, k rounded up to a multiple
+    of 8], the padding columns zero -- the width ops.nn1 / ops.knn want, and zero columns change no distance."""
+    torch = _lib.require_gpu()
+    _f32c(x, "x")
+    n, d = x.shape
+    for t, name, shape in ((mean, "mean", (d,)), (components, "components", (components.shape[0], d))):
+        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError("%s must be a contiguous float64 CUDA tensor of shape %s" % (name, shape))
+    k = check_pca_components(int(components.shape[0]), None, d)
+    ld = (k + 7) // 8 * 8
+    z = torch.empty((n, ld), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().hsefr_pca_transform(x.data_ptr(), n, d, k, mean.data_ptr(), components.data_ptr(), z.data_ptr(), ld,
+                                              _lib.current_stream_ptr()), "hsefr_pca_transform")
+    return z
+
+
 @_device_guarded
 def conv2d_direct(x, w_hwio, bias=None, alpha=None, stride: int = 1, padding: str = "VALID"):
     """Generic Conv2D + BiasAdd + optional PReLU (MTCNN nets).  padding: 'VALID' | 'SAME' (TensorFlow rule)."""

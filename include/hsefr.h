@@ -15,6 +15,8 @@
  *       -> hsefr_l2_normalize() + hsefr_nn1()
  *   - KNeighborsClassifier(3).fit / predict                    facerec_test.py:269-288 ('3-NN', '3-NN+PCA')
  *       -> hsefr_knn()
+ *   - Pipeline(PCA(n_components), KNeighborsClassifier)         facerec_test.py:269-273,417-432 ('1-NN+PCA', '3-NN+PCA', 'k-NN+PCA')
+ *       -> hsefr_pca_fit() on the gallery + hsefr_pca_transform() of both sets, then hsefr_nn1() / hsefr_knn()
  *   - misc.imresize / cv2.resize + BGR + mean   facerec_test.py:93-106 ; facial_analysis.py:95-107
  *       -> hsefr_preprocess_pil_u8() / hsefr_preprocess_cv_u8()
  *
@@ -587,6 +589,28 @@ int hsefr_knn(const float* q, const float* g, int nq, int ng, int d, int k, int*
  * search runs on the workspace-free kernel instead (same nearest neighbours up to last-bit ties, far slower at 10^5 x 10^5).  This
  * counts those searches since the library was loaded, so a perf cliff can be traced to the allocator (hsefr_last_error_string says which). */
 long long hsefr_nn1_fallbacks(void);
+
+/* sklearn.decomposition.PCA(n_components=k).fit (facerec_test.py:269,421) as a deterministic fp64 computation on the device.
+ * x [n,d] fp32 row-major.  mean [d] fp64: the column means, summed in fp64.  explained_variance [k] fp64: the k largest eigenvalues of
+ * C = (x - mean)^T (x - mean) / (n - 1), descending; C is formed in fp64 from rows centred in fp64.  components [k,d] fp64: their unit
+ * eigenvectors, each signed so that its entry of largest magnitude (the first one on ties) is positive -- scikit-learn 1.7's
+ * svd_flip(u_based_decision=False).  Blocked subspace iteration on b = k + max(16, k / 2) vectors (in sixteens, at most min(n - 1, d))
+ * with a Rayleigh-Ritz step every 8 iterations; converged means |C v_i - lambda_i v_i| <= 1e-10 lambda_1 for every i < k.
+ * info [2] (int32, device): the iterations used and 1 / 0 for converged; reaching max_iter is NOT an error here -- the caller reads
+ * info.  Results are bit-identical from run to run on one device (fixed summation orders, a counter-based start block, no atomics).
+ * 1 <= k <= min(n - 1, d, 256) (k = min(n, d) would ask for a component of zero variance and arbitrary direction), n >= 2,
+ * max_iter >= 1 (HSEFR_ERR_INVALID otherwise); d a multiple of 8 (HSEFR_ERR_UNSUPPORTED); rows without any variance, or values that
+ * are not finite, end as HSEFR_ERR_INVALID (a Cholesky pivot that is not positive).  Arguments are checked before any device call.
+ * Workspace 8 d^2 + 32 b d + 40 b^2 bytes, stream-ordered, refused (HSEFR_ERR_NOMEM) before any launch; the host reads eight bytes of
+ * flags per convergence check, so the call synchronises `stream`. */
+int hsefr_pca_fit(const float* x, int n, int d, int k, int max_iter, double* mean, double* components, double* explained_variance,
+                  int* info /* [2]: iterations, converged */, hsefr_stream_t stream);
+/* PCA.transform without whitening: z[i][j] = sum_c (x[i][c] - mean[c]) components[j][c], accumulated in fp64 and rounded once to fp32,
+ * into z [n,ldz] with ldz >= k a multiple of 8 (what hsefr_nn1 / hsefr_knn want); columns k .. ldz - 1 are written as zeros, which
+ * change no distance.  1 <= k <= min(d, 256), n >= 0 (n = 0 is HSEFR_OK); HSEFR_ERR_INVALID otherwise, d not a multiple of 8 is
+ * HSEFR_ERR_UNSUPPORTED.  No workspace, no host synchronisation. */
+int hsefr_pca_transform(const float* x, int n, int d, int k, const double* mean, const double* components, float* z, int ldz,
+                        hsefr_stream_t stream);
 
 /* ---- generic small-CNN kernels: the MTCNN detection cascade (facial_analysis.py:334-352,478-604; mtcnn.pb) ---------- */
 
