@@ -87,6 +87,8 @@ SIGNATURES = {
     "hsefr_dbscan": (c_int, [_fp, c_int, c_int, _fp, _fp, _fp, ctypes.c_double, c_int, _fp, _fp, c_void_p]),
     "hsefr_rank_order": (c_int, [_fp, c_int, c_int, _fp, _fp, _fp, ctypes.c_double, ctypes.c_double, _fp, POINTER(c_int), c_void_p]),
     "hsefr_rank_order_sweep": (c_int, [_fp, c_int, c_int, _fp, _fp, _fp, POINTER(ctypes.c_double), c_int, _fp, POINTER(c_int), c_void_p]),
+    "hsefr_flat_cuts": (c_int, [_fp, _fp, c_int, _fp, c_int, _fp, c_void_p]),
+    "hsefr_partition_scores": (c_int, [_fp, _fp, c_int, c_int, _fp, _fp, c_void_p]),
     "hsefr_nn1": (c_int, [_fp, _fp, c_int, c_int, c_int, _fp, _fp, c_void_p]),
     "hsefr_knn": (c_int, [_fp, _fp, c_int, c_int, c_int, c_int, _fp, _fp, _fp, _fp, c_void_p]),
     "hsefr_nn1_fallbacks": (c_longlong, []),

@@ -12,6 +12,10 @@ The reference's third branch, scikit-learn's DBSCAN on the precomputed matrix (f
 scikit-learn's labels from either source, without an N x N matrix from features (ops.dbscan_labels, csrc/dbscan.hip).
 Its last branch, rank-order clustering (find_clusters, facial_clustering_test.py:23-239), runs on an fp64 n x n device matrix with the
 reference's clusters (ops.rank_order_labels, csrc/rank_order.hip).
+The study's statistics and its threshold selection (get_clustering_statistics, test_avg_clustering_with_model_selection,
+facial_clustering_test.py:416-499) score a whole sweep on the device: one clustering per album, every threshold's labels cut there
+(ops.flat_cuts), every row scored by one call and read back once (ops.partition_scores, csrc/partition_scores.hip): clustering_scores,
+threshold_sweep, select_threshold.
 No CPU fallback: the functions that compute distances raise without the library or a GPU.
 """
 from __future__ import annotations
@@ -19,7 +23,7 @@ from __future__ import annotations
 import hashlib
 import math
 import numbers
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -564,3 +568,236 @@ def bcubed(y_true: Sequence, y_pred: Sequence):
     prec = float(np.mean(both / np.bincount(t)[t]))
     rec = float(np.mean(both / np.bincount(p)[p]))
     return prec, rec, 2.0 * prec * rec / (prec + rec)
+
+
+# ---- the study's statistics on the device: one sweep, one read-back ----------------------------------------------------
+# get_clustering_statistics' ten numbers, in test_avg_clustering's order (facial_clustering_test.py:435)
+STATS_NAMES = ("classes", "clusters", "ARI", "AMI", "homogeneity", "completeness", "v-measure", "BCubed_precision", "BCubed_recall",
+               "BCubed_FMeasure")
+# test_avg_clustering_with_model_selection's grids and bounds (:447-499)
+SWEEP_THRESHOLDS = np.linspace(0.6, 1.3, 71)
+SWEEP_DROP = 0.01
+SWEEP_CEILING = 0.85
+RANK_ORDER_SWEEP_NORMS = np.linspace(1.02, 1.1, 9)
+RANK_ORDER_SWEEP_RANKS = tuple(range(12, 22, 2))
+# which of ops.partition_scores' three cluster counts is the reference's len(clusters): every flat cluster of a linkage cut, the
+# non-noise clusters of DBSCAN, rank-order's clusters of at least two faces
+_CLUSTERS_COLUMN = {"dbscan": 3, "rankorder": 2}
+_EPS = float(np.finfo(np.float64).eps)
+
+
+def scores_from_counts(counts_row, stats_row, n):
+    """One row of ops.partition_scores (8 counts, 6 sums) for n items -> (ARI, AMI, homogeneity, completeness, v-measure,
+    BCubed_precision, BCubed_recall, BCubed_FMeasure) as Python floats, the last eight of STATS_NAMES: scikit-learn 1.7's
+    adjusted_rand_score, adjusted_mutual_info_score(average_method='arithmetic') and homogeneity_completeness_v_measure with their
+    special cases, and bcubed's three numbers.  ARI is exact integer arithmetic up to scikit-learn's own final expression."""
+    R, C, _, _, _, s_nij2, s_a2, s_b2 = (int(v) for v in counts_row)
+    h_true, h_pred, mi, emi, bc_p, bc_r = (float(v) for v in stats_row)
+    N = int(n)
+    tp = s_nij2 - N
+    fp = s_a2 - s_nij2
+    fn = s_b2 - s_nij2
+    tn = N * N - fp - fn - s_nij2
+    if fn == 0 and fp == 0:
+        ari = 1.0
+    else:
+        ari = 2.0 * (tp * tn - fn * fp) / ((tp + fn) * (fn + tn) + (tp + fp) * (fp + tn))
+    mi = 0.0 if R == 1 or C == 1 else max(mi, 0.0)
+    homogeneity = mi / h_true if h_true else 1.0
+    completeness = mi / h_pred if h_pred else 1.0
+    if homogeneity + completeness == 0.0:
+        v_measure = 0.0
+    else:
+        v_measure = 2.0 * homogeneity * completeness / (homogeneity + completeness)
+    if R == 1 and C == 1:
+        ami = 1.0
+    elif R == 1 or C == 1:
+        ami = 0.0
+    else:
+        denominator = 0.5 * (h_true + h_pred) - emi
+        denominator = min(denominator, -_EPS) if denominator < 0 else max(denominator, _EPS)
+        numerator = mi - emi
+        numerator = min(numerator, -_EPS) if numerator < 0 else max(numerator, _EPS)
+        ami = numerator / denominator
+    return (float(ari), float(ami), float(homogeneity), float(completeness), float(v_measure), bc_p, bc_r,
+            2.0 * bc_p * bc_r / (bc_p + bc_r))
+
+
+def _dense_labels(y, what):
+    y = np.asarray(y).reshape(-1)
+    if len(y) == 0:
+        raise ValueError("%s is empty" % what)
+    return np.unique(y, return_inverse=True)[1].reshape(-1).astype(np.int32)
+
+
+def _score_rows(y_true, labels, clusters_column=1):
+    """y_true int32 [n] (host) and labels int32 [rows, n] (device) -> float64 [rows, 10] in STATS_NAMES order: one
+    ops.partition_scores call and one read-back."""
+    from . import ops
+    import torch
+    n = labels.shape[1]
+    if len(y_true) != n:
+        raise ValueError("%d true labels for %d faces" % (len(y_true), n))
+    counts, stats = ops.partition_scores(torch.from_numpy(y_true).to(labels.device), labels)
+    packed = torch.cat([counts, stats.view(torch.int64)], dim=1).cpu().numpy()
+    counts, stats = packed[:, :8], np.ascontiguousarray(packed[:, 8:]).view(np.float64)
+    out = np.empty((len(counts), len(STATS_NAMES)), dtype=np.float64)
+    for r in range(len(counts)):
+        out[r, 0] = counts[r, 0]
+        out[r, 1] = counts[r, clusters_column]
+        out[r, 2:] = scores_from_counts(counts[r], stats[r], n)
+    return out
+
+
+def clustering_scores(y_true, y_pred, device=None) -> np.ndarray:
+    """get_clustering_statistics' ten numbers (STATS_NAMES) for one labelling, scored on the device: y_true and y_pred are sequences
+    of n labels of any kind, compared for equality only; 'clusters' is the number of distinct predicted labels."""
+    from . import _lib
+    torch = _lib.require_gpu()
+    t, p = _dense_labels(y_true, "y_true"), _dense_labels(y_pred, "y_pred")
+    if len(t) != len(p):
+        raise ValueError("%d true labels, %d predicted" % (len(t), len(p)))
+    return _score_rows(t, torch.from_numpy(p).to(_lib.cuda_device(device))[None])[0]
+
+
+def _sweep_labels(source, method, thresholds, born_years, photo_years, dense, min_samples, device):
+    """One clustering of the album -> labels int32 [len(thresholds), n] on the device"""
+    from . import ops
+    import torch
+    if method == "rankorder":
+        pairs = _rank_order_pairs(None, None, thresholds)[0]
+    else:
+        ts = np.asarray(thresholds, dtype=np.float64).reshape(-1)
+        if len(ts) == 0 or not np.isfinite(ts).all():
+            raise ValueError("threshold_sweep: thresholds must be a non-empty sequence of finite numbers")
+        if method == "dbscan":
+            for eps in ts:
+                _check_dbscan_args(float(eps), min_samples)
+    negative = None if method in LINKAGE_METHODS else "dist_matrix holds negative values"
+    if dense:
+        src = dict(dense=_dist_matrix(source, device, negative))
+        n, dev = src["dense"].shape[0], src["dense"].device
+    else:
+        x, born, year = _features(source, born_years, photo_years, device, finite=True)
+        src = dict(x=x, born=born, year=year)
+        n, dev = x.shape[0], x.device
+    if method == "rankorder":
+        return ops.rank_order_labels(thresholds=pairs, **src)[0]
+    if method == "dbscan":
+        return torch.stack([ops.dbscan_labels(eps=float(eps), min_samples=min_samples, **src)[0] for eps in ts])
+    if n == 1:
+        return torch.ones((len(ts), 1), dtype=torch.int32, device=dev)
+    order, gaps = _cut_order(_linkage(method, n, **src))
+    return ops.flat_cuts(torch.from_numpy(order.astype(np.int32)).to(dev), torch.from_numpy(gaps).to(dev), torch.from_numpy(ts).to(dev))
+
+
+def threshold_sweep(source, y_true, method, thresholds, born_years=None, photo_years=None, dense=False, min_samples=1,
+                    device=None) -> np.ndarray:
+    """get_clustering_statistics (facial_clustering_test.py:416-423) for every threshold of a sweep over one album -> float64
+    [len(thresholds), 10] in STATS_NAMES order.  ``source`` is the features [n, d] (with optional born / photo years) or, with
+    ``dense=True``, the distance matrix, as linkage / linkage_dense take them.  The album is clustered once: a linkage method's
+    dendrogram is cut at all thresholds on the device (ops.flat_cuts), 'dbscan' gives one labelling per eps (``min_samples`` as
+    get_facial_clusters' no_images_in_cluster), 'rankorder' takes (norm, rank) pairs through one matrix build; every row is scored by
+    one ops.partition_scores call and read back once.  Faces outside every cluster (DBSCAN's noise, rank-order's single faces) are
+    clusters of their own, as the study's y_pred has them, and 'clusters' is the reference's len(clusters): every flat cluster of a
+    linkage cut, DBSCAN's non-noise clusters, rank-order's clusters of at least two faces."""
+    _check_method(method, CLUSTER_METHODS)
+    t = _dense_labels(y_true, "y_true")
+    labels = _sweep_labels(source, method, thresholds, born_years, photo_years, dense, min_samples, device)
+    return _score_rows(t, labels, _CLUSTERS_COLUMN.get(method, 1))
+
+
+def select_from_curve(thresholds, statistic, drop=SWEEP_DROP, ceiling=SWEEP_CEILING):
+    """The scalar loop of test_avg_clustering_with_model_selection (:476-495) over a statistic known at every threshold ->
+    (best threshold, best statistic, points evaluated): the best is replaced on '>' (it starts as threshold 0 with statistic 0), and
+    the point after which the loop stops -- the statistic fell more than ``drop`` below the previous point's, or exceeds ``ceiling``
+    -- is still evaluated and may be the best."""
+    best, best_threshold, prev, evaluated = 0, 0, 0, 0
+    for threshold, current in zip(thresholds, statistic):
+        evaluated += 1
+        if current > best:
+            best, best_threshold = current, threshold
+        if current < prev - drop:
+            break
+        if current > ceiling:
+            break
+        prev = current
+    return best_threshold, best, evaluated
+
+
+def select_from_grid(norm_thresholds, rank_thresholds, statistic):
+    """The rank-order loops of test_avg_clustering_with_model_selection (:451-474) over a statistic [norms, ranks] known on the whole
+    grid -> (best (norm, rank), best statistic, the (i, j) grid points evaluated, in order): the best is replaced on '>' (it starts as
+    (0, 0) with statistic 0); a row of rank thresholds ends after a point that is not above the one before it (the first is compared
+    with 0), and the norm thresholds end after a row that did not replace the best."""
+    best, best_threshold, evaluated = 0, (0, 0), []
+    for i, norm in enumerate(norm_thresholds):
+        prev, changed = 0, False
+        for j, rank in enumerate(rank_thresholds):
+            current = statistic[i][j]
+            evaluated.append((i, j))
+            if current > best:
+                best, best_threshold, changed = current, (norm, rank), True
+            if current <= prev:
+                break
+            prev = current
+        if not changed:
+            break
+    return best_threshold, best, evaluated
+
+
+class Selection(NamedTuple):
+    """select_threshold's result"""
+    threshold: object           # the best threshold (a (norm, rank) pair for rank-order)
+    statistic: float            # the selection statistic there, averaged over the albums
+    evaluated: list             # [(threshold, statistic)] for the points the reference would have evaluated, in its order
+    mean: np.ndarray            # test_avg_clustering's np.mean of STATS_NAMES over the albums at the best threshold
+    std: np.ndarray             # and its np.std
+
+
+def select_threshold(albums, method, thresholds=None, drop=SWEEP_DROP, ceiling=SWEEP_CEILING, norm_thresholds=None,
+                     rank_thresholds=None, dense=False, min_samples=1, device=None) -> Selection:
+    """test_avg_clustering_with_model_selection (facial_clustering_test.py:447-499) with val_dirs_count = len(albums) (the
+    reference's own "hack"): ``albums`` is a list of (source, y_true), each source as threshold_sweep takes it.  Linkage methods and
+    'dbscan' sweep ``thresholds`` (default np.linspace(0.6, 1.3, 71)) for the study's B-cubed "precision" averaged over the albums
+    with select_from_curve's rules (``drop``, ``ceiling``); 'rankorder' sweeps ``norm_thresholds`` x ``rank_thresholds`` (defaults
+    np.linspace(1.02, 1.1, 9) x range(12, 22, 2)) for the V-measure with select_from_grid's.  Every album is clustered and scored once
+    on the whole grid (threshold_sweep) and the reference's stopping rules are applied to the resulting arrays, which gives the
+    reference's answer.  Returns a Selection: the best threshold, its statistic, the (threshold, statistic) points the reference
+    would have evaluated, and test_avg_clustering's mean and standard deviation of the ten statistics over the albums at the best
+    threshold.  When no point scores above 0 the reference goes on with its initial threshold 0: a linkage method is cut there;
+    'dbscan' and 'rankorder', which accept no zero threshold, raise ValueError."""
+    _check_method(method, CLUSTER_METHODS)
+    albums = list(albums)
+    if not albums:
+        raise ValueError("select_threshold: no albums")
+    kw = dict(dense=dense, min_samples=min_samples, device=device)
+    if method == "rankorder":
+        norms = list(RANK_ORDER_SWEEP_NORMS if norm_thresholds is None else norm_thresholds)
+        ranks = list(RANK_ORDER_SWEEP_RANKS if rank_thresholds is None else rank_thresholds)
+        grid = [(norm, rank) for norm in norms for rank in ranks]
+        column = STATS_NAMES.index("v-measure")
+    else:
+        grid = list(SWEEP_THRESHOLDS if thresholds is None else thresholds)
+        column = STATS_NAMES.index("BCubed_precision")
+    tables = [threshold_sweep(source, y_true, method, grid, **kw) for source, y_true in albums]
+    statistic = np.zeros(len(grid))
+    for table in tables:                         # the reference's running sum over the albums, then one division
+        statistic = statistic + table[:, column]
+    statistic = statistic / len(albums)
+    if method == "rankorder":
+        best_threshold, best, points = select_from_grid(norms, ranks, statistic.reshape(len(norms), len(ranks)))
+        points = [i * len(ranks) + j for i, j in points]
+    else:
+        best_threshold, best, count = select_from_curve(grid, statistic, drop, ceiling)
+        points = list(range(count))
+    evaluated = [(grid[k], float(statistic[k])) for k in points]
+    at_best = [k for k in points if grid[k] == best_threshold]
+    if at_best:
+        rows = np.stack([table[at_best[0]] for table in tables])
+    elif method not in LINKAGE_METHODS:
+        raise ValueError("select_threshold: no point of the %s sweep scored above 0, so nothing was selected (the reference would go on "
+                         "with its initial threshold %r, which that clustering does not accept)" % (method, best_threshold))
+    else:                                        # nothing scored above 0: the reference goes on with its initial threshold 0
+        rows = np.stack([threshold_sweep(source, y_true, method, [best_threshold], **kw)[0] for source, y_true in albums])
+    return Selection(best_threshold, float(best), evaluated, np.mean(rows, axis=0), np.std(rows, axis=0))

@@ -295,6 +295,8 @@ int launch_single_linkage(const DistSource& src, int* edge_a, int* edge_b, doubl
 int launch_dbscan(const DistSource& src, double eps, int min_samples, int* labels, unsigned char* core, hipStream_t s);
 int launch_rank_order(const DistSource& src, const double* thresholds, int pairs, int* labels, int* iterations, hipStream_t s);
 int launch_hier_linkage(const DistSource& src, int method, int* merge_a, int* merge_b, double* merge_h, int* merge_round, hipStream_t s);
+int launch_flat_cuts(const int* order, const double* gaps, int n, const double* thresholds, int rows, int* labels, hipStream_t s);
+int launch_partition_scores(const int* y_true, const int* labels, int n, int rows, long long* counts, double* stats, hipStream_t s);
 
 bool dwpw_fused_supported(int c, int cout, int stride, int act_dw, int act_pw);
 int launch_dwpw_fused(const float* x, const float* wd, const float* dscale, const float* dshift, const float* wp_t,

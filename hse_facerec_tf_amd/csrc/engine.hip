@@ -1453,5 +1453,22 @@ int hsefr_rank_order(const float* x, int n, int d, const float* born, const floa
     return hsefr_rank_order_sweep(x, n, d, born, year, dense, thresholds, 1, labels, iterations, stream);
 }
 
+int hsefr_flat_cuts(const int* order, const double* gaps, int n, const double* thresholds, int rows, int* labels, hsefr_stream_t stream) {
+    HSEFR_REQUIRE(n >= 1 && rows >= 1, HSEFR_ERR_INVALID, "flat_cuts: n=%d, rows=%d (both at least 1)", n, rows);
+    HSEFR_REQUIRE(order && (gaps || n == 1) && thresholds && labels, HSEFR_ERR_INVALID,
+                  "flat_cuts: null pointer (order %p, gaps %p, thresholds %p, labels %p)", (const void*)order, (const void*)gaps,
+                  (const void*)thresholds, (const void*)labels);
+    return launch_flat_cuts(order, gaps, n, thresholds, rows, labels, (hipStream_t)stream);
+}
+
+int hsefr_partition_scores(const int* y_true, const int* labels, int n, int rows, long long* counts, double* stats, hsefr_stream_t stream) {
+    HSEFR_REQUIRE(n >= 1 && n <= HSEFR_SCORES_MAX_N && rows >= 1, HSEFR_ERR_INVALID,
+                  "partition_scores: n=%d (1 .. %d), rows=%d (at least 1)", n, HSEFR_SCORES_MAX_N, rows);
+    HSEFR_REQUIRE(y_true && labels && counts && stats, HSEFR_ERR_INVALID,
+                  "partition_scores: null pointer (y_true %p, labels %p, counts %p, stats %p)", (const void*)y_true, (const void*)labels,
+                  (const void*)counts, (const void*)stats);
+    return launch_partition_scores(y_true, labels, n, rows, counts, stats, (hipStream_t)stream);
+}
+
 }  // extern "C"
 #pragma GCC visibility pop

@@ -740,6 +740,61 @@ def rank_order_labels(x=None, dense=None, born=None, year=None, norm_threshold=0
     return (labels, list(iters)) if sweep else (labels[0], int(iters[0]))
 
 
+SCORES_MAX_N = 65536       # HSEFR_SCORES_MAX_N
+
+
+def _typed(t, dtype, name, what):
+    if not (hasattr(t, "is_cuda") and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
+        raise ValueError("%s must be a contiguous %s CUDA tensor" % (name, what))
+    return t
+
+
+@_device_guarded
+def flat_cuts(order, gaps, thresholds):
+    """fcluster(Z, t, 'distance') for every t of ``thresholds`` from one dendrogram (hsefr_flat_cuts) -> labels int32 [rows, n] CUDA
+    tensor: labels[r, order[p]] = 1 + the number of gaps before position p that exceed thresholds[r] (a gap equal to the threshold
+    stays joined).  order int32 [n] = the leaves in dendrogram order (a permutation of 0 .. n - 1), gaps float64 [n - 1], thresholds
+    float64 [rows], all CUDA tensors (clustering._cut_order makes the first two from Z).  Asynchronous on the current stream."""
+    torch = _lib.require_gpu()
+    _typed(order, torch.int32, "order", "int32")
+    _typed(gaps, torch.float64, "gaps", "float64")
+    _typed(thresholds, torch.float64, "thresholds", "float64")
+    if order.dim() != 1 or gaps.dim() != 1 or thresholds.dim() != 1:
+        raise ValueError("flat_cuts: order [n], gaps [n - 1] and thresholds [rows] are vectors")
+    n, rows = order.shape[0], thresholds.shape[0]
+    if n < 1 or rows < 1 or gaps.shape[0] != n - 1:
+        raise ValueError("flat_cuts: %d leaves, %d gaps, %d thresholds" % (n, gaps.shape[0], rows))
+    labels = torch.zeros((rows, n), dtype=torch.int32, device=order.device)
+    _lib.check(_lib.lib().hsefr_flat_cuts(order.data_ptr(), gaps.data_ptr() if n > 1 else None, n, thresholds.data_ptr(), rows,
+                                          labels.data_ptr(), _lib.current_stream_ptr()), "hsefr_flat_cuts")
+    return labels
+
+
+@_device_guarded
+def partition_scores(y_true, labels):
+    """The counts and sums behind the clustering study's statistics (hsefr_partition_scores) -> (counts int64 [rows, 8], stats float64
+    [rows, 6]) CUDA tensors, one row per labelling: y_true int32 [n] and labels int32 [rows, n] (or [n] for one row) CUDA tensors, any
+    values, a negative label being a cluster of its own.  counts = classes, clusters, clusters of at least 2, non-negative clusters,
+    non-zero cells, sum n_ij^2, sum a_i^2, sum b_j^2; stats = H_true, H_pred, MI, EMI, sum n_ij^2 / a_i / n, sum n_ij^2 / b_j / n
+    (clustering.scores_from_counts turns a row into the scores).  Bit-identical from run to run, every row independent of the others.
+    n <= SCORES_MAX_N.  Asynchronous on the current stream."""
+    torch = _lib.require_gpu()
+    _typed(y_true, torch.int32, "y_true", "int32")
+    _typed(labels, torch.int32, "labels", "int32")
+    if labels.dim() == 1:
+        labels = labels[None]
+    if y_true.dim() != 1 or labels.dim() != 2 or labels.shape[1] != y_true.shape[0]:
+        raise ValueError("partition_scores: y_true [n] and labels [rows, n], got %r and %r" % (tuple(y_true.shape), tuple(labels.shape)))
+    rows, n = labels.shape
+    if n < 1 or rows < 1 or n > SCORES_MAX_N:
+        raise ValueError("partition_scores: n=%d (1 .. %d), rows=%d (at least 1)" % (n, SCORES_MAX_N, rows))
+    counts = torch.empty((rows, 8), dtype=torch.int64, device=y_true.device)
+    stats = torch.empty((rows, 6), dtype=torch.float64, device=y_true.device)
+    _lib.check(_lib.lib().hsefr_partition_scores(y_true.data_ptr(), labels.data_ptr(), n, rows, counts.data_ptr(), stats.data_ptr(),
+                                                 _lib.current_stream_ptr()), "hsefr_partition_scores")
+    return counts, stats
+
+
 # ---- bf16 ResNet-50 kernels -------------------------------------------------------------------------
 def _bf16c(t, name):
     torch = _lib.require_gpu()

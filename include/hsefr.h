@@ -760,6 +760,37 @@ int hsefr_rank_order(const float* x, int n, int d, const float* born, const floa
 int hsefr_rank_order_sweep(const float* x, int n, int d, const float* born, const float* year, const double* dense,
                            const double* thresholds, int pairs, int* labels, int* iterations, hsefr_stream_t stream);
 
+/* fcluster(Z, t, 'distance') for a sequence of thresholds from one dendrogram (the clustering study's sweep,
+ * facial_clustering_test.py:447-499).  order [n] int32 = the leaves in dendrogram order, gaps [n - 1] fp64 = for each pair of
+ * neighbours in that order the largest height inside the smallest cluster that holds both (clustering._cut_order computes both from
+ * Z), thresholds [rows] fp64 -- all device memory.  Output labels [rows][n] int32 (device):
+ *   labels[r][order[p]] = 1 + #{q < p : gaps[q] > thresholds[r]}
+ * -- a gap equal to the threshold stays joined; n = 1 gives label 1 (gaps may then be null).  An entry of order outside 0 .. n - 1 is
+ * skipped.  No workspace, no host synchronisation.  n >= 1, rows >= 1 and non-null pointers, checked before any device call
+ * (HSEFR_ERR_INVALID). */
+int hsefr_flat_cuts(const int* order, const double* gaps, int n, const double* thresholds, int rows, int* labels, hsefr_stream_t stream);
+
+/* What the clustering study's ten statistics (get_clustering_statistics, facial_clustering_test.py:416-423: ARI, AMI, homogeneity,
+ * completeness, V-measure, B-cubed) are made of, for `rows` labellings of the same n items in one call.  y_true [n] int32: any values,
+ * compared for equality only.  labels [rows][n] int32: any values; a NEGATIVE label is a cluster of its own (DBSCAN's noise, which the
+ * study turns into fresh singleton labels at :402-409).  Every row is scored against y_true on its own.  With a_i the class sizes, b_j
+ * the cluster sizes, n_ij the non-zero cells of the contingency table and N = n:
+ *   counts [rows][8] int64, exact: classes R | clusters C (each negative label counted as one) | clusters of at least 2 members |
+ *     non-negative clusters | non-zero cells | sum n_ij^2 | sum a_i^2 | sum b_j^2
+ *   stats [rows][6] fp64: H_true = -sum (a_i/N)(ln a_i - ln N) | H_pred, likewise over b_j | MI = sum (n_ij/N) ln(N n_ij / (a_i b_j)) |
+ *     EMI = scikit-learn's expected_mutual_information, sum_i sum_j sum_{k = max(1, a_i + b_j - N)}^{min(a_i, b_j)} (k/N) ln(N k / (a_i b_j))
+ *     exp(lnG(a_i+1) + lnG(b_j+1) + lnG(N-a_i+1) + lnG(N-b_j+1) - lnG(N+1) - lnG(k+1) - lnG(a_i-k+1) - lnG(b_j-k+1) - lnG(N-a_i-b_j+k+1)) |
+ *     sum n_ij^2 / a_i / N | sum n_ij^2 / b_j / N (the two B-cubed means of the study)
+ * No R x C table is formed: the cells are the runs of each row's sorted (cluster, class) keys, and the EMI term is evaluated once per
+ * pair of DISTINCT sizes, weighted by their multiplicities.  Results are bit-identical from run to run and a row's result does not
+ * depend on the other rows of the call (fixed summation shapes; the only atomics are integer counts).  The first B-cubed sum is added
+ * class by class from integer sums of squares, so labellings that differ by a merge of clusters sharing no class -- which leaves it
+ * unchanged -- give it the same bits, and a threshold selection on it sees the tie.  Workspace about
+ * rows * (8 P + 32 n) bytes with P = n rounded up to a power of two, stream-ordered, refused (HSEFR_ERR_NOMEM) before any launch; no host
+ * synchronisation.  1 <= n <= HSEFR_SCORES_MAX_N, rows >= 1 and non-null pointers, checked before any device call (HSEFR_ERR_INVALID). */
+#define HSEFR_SCORES_MAX_N 65536
+int hsefr_partition_scores(const int* y_true, const int* labels, int n, int rows, long long* counts, double* stats, hsefr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
