@@ -94,6 +94,9 @@ SIGNATURES = {
     "hsefr_nn1_fallbacks": (c_longlong, []),
     "hsefr_pca_fit": (c_int, [_fp, c_int, c_int, c_int, c_int, _fp, _fp, _fp, _fp, c_void_p]),
     "hsefr_pca_transform": (c_int, [_fp, c_int, c_int, c_int, _fp, _fp, _fp, c_int, c_void_p]),
+    "hsefr_linear_svm_fit": (c_int, [_fp, c_int, c_int, _fp, c_int, ctypes.c_double, ctypes.c_double, c_int, _fp, _fp, _fp, c_void_p]),
+    "hsefr_linear_svm_decision": (c_int, [_fp, c_int, c_int, _fp, _fp, c_int, _fp, c_void_p]),
+    "hsefr_linear_svm_predict": (c_int, [_fp, c_int, c_int, _fp, c_void_p]),
 }
 
 # development builds only (csrc/hsefr_dev.h; build.sh with HSEFR_DEV=1): bound when the loaded library has them

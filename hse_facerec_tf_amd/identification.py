@@ -7,6 +7,9 @@ reference's callers, not of the engine); the O(N_test x N_train x D) nearest-nei
 libhsefr (ops.l2_normalize / ops.nn1; ops.knn for the reference's '3-NN' rows, facerec_test.py:269-288).  The PCA of the '+PCA' rows
 is scikit-learn's on the host by default (``pca="host"``) or the library's deterministic fp64 fit and projection on the device
 (``pca="device"``: ops.pca_fit / ops.pca_transform, nothing leaves the GPU between the features and the search).
+``classifier="linear_svm"`` replaces the search by the reference's 'linear svm' / 'linear svm+PCA' rows (LinearSVC(), facerec_test.py:269-288,
+:429): ops.linear_svm_fit on the gallery, solved to the optimum of LinearSVC's objective in fp64, ops.linear_svm_decision and
+ops.linear_svm_predict on the probes.
 """
 from __future__ import annotations
 
@@ -83,6 +86,49 @@ def _device_pca(ops, gal, qry, pca_components: int):
     return ops.pca_transform(gal, mean, components), ops.pca_transform(qry, mean, components)
 
 
+LINEAR_SVM_MAX_ITER = 1000     # hsefr_linear_svm_fit's Newton iteration cap on the classifier="linear_svm" path; reaching it raises
+LINEAR_SVM_TOL = 1e-10         # a class is converged at |grad f_k| <= LINEAR_SVM_TOL |grad f_k(0)|
+
+
+def check_classifier(classifier, n_neighbors=1, svm_C=1.0) -> str:
+    """The classifier keyword of the protocols, raised as ValueError before the library or a device is touched."""
+    if classifier not in ("knn", "linear_svm"):
+        raise ValueError("classifier=%r must be 'knn' (ops.nn1 / ops.knn) or 'linear_svm' (ops.linear_svm_fit)" % (classifier,))
+    if classifier == "linear_svm":
+        from . import ops
+        if n_neighbors != 1:
+            raise ValueError("n_neighbors=%r has no meaning with classifier='linear_svm': leave it at 1" % (n_neighbors,))
+        ops.check_linear_svm_args(1, 1, 2, C=svm_C)
+    return classifier
+
+
+def _linear_svm_predict(ops, qry, gal, y_gallery: np.ndarray, svm_C: float, lap=None):
+    """LinearSVC(C=svm_C).fit(gal, y_gallery) at the objective's optimum -> decision_function + predict of ``qry`` on the device.  The
+    labels are encoded with np.unique (scikit-learn's ``classes_``), so any label type works.  Returns (y_pred, decision [nq,K'] on the
+    host, Newton iterations)."""
+    from . import _lib
+    torch = _lib.require_gpu()
+    classes, codes = np.unique(np.asarray(y_gallery), return_inverse=True)
+    n, d = int(gal.shape[0]), int(gal.shape[1])
+    ops.check_linear_svm_args(n, d, len(classes), C=svm_C, tol=LINEAR_SVM_TOL, max_iter=LINEAR_SVM_MAX_ITER)
+    labels = torch.from_numpy(codes.astype(np.int32).reshape(-1)).to(gal.device)
+    coef, intercept, info = ops.linear_svm_fit(gal, labels, len(classes), C=svm_C, tol=LINEAR_SVM_TOL, max_iter=LINEAR_SVM_MAX_ITER)
+    if not info["converged"]:
+        raise RuntimeError("the device linear SVM fit on the n=%d x d=%d gallery (K=%d classes) did not converge in %d iterations"
+                           % (n, d, len(classes), info["iterations"]))
+    if lap is not None:
+        lap("svm_fit_s")
+    if qry.shape[0] == 0:                                       # no probe: nothing to label (the entry points want at least one row)
+        if lap is not None:
+            lap("svm_predict_s")
+        return classes[:0], np.zeros((0, int(coef.shape[0])), dtype=np.float64), info["iterations"]
+    decision = ops.linear_svm_decision(qry, coef, intercept)
+    pred = ops.linear_svm_predict(decision)
+    if lap is not None:
+        lap("svm_predict_s")
+    return classes[pred.cpu().numpy()], decision.cpu().numpy(), info["iterations"]
+
+
 def _knn_predict(ops, qry, gal, y_gallery: np.ndarray, n_neighbors: int):
     """KNeighborsClassifier(n_neighbors).fit(gal, y_gallery) -> kneighbors + predict of ``qry`` on the device (ops.knn).  The labels are
     encoded with np.unique, so the vote's smallest-label rule runs over scikit-learn's sorted ``classes_`` and any label type works.
@@ -97,7 +143,7 @@ def _knn_predict(ops, qry, gal, y_gallery: np.ndarray, n_neighbors: int):
 
 def one_nn_identification(X, y: np.ndarray, split=None,
                           pca_components: Optional[int] = None, timings: Optional[dict] = None, device=None,
-                          n_neighbors: int = 1, pca: str = "host") -> Dict:
+                          n_neighbors: int = 1, pca: str = "host", classifier: str = "knn", svm_C: float = 1.0) -> Dict:
     """The protocol of facerec_test.py:401-432: 'k-NN' (pca_components=None) or 'k-NN+PCA'
     (pca_components=128, the Pipeline of :421 -- PCA is fitted on the gallery half by scikit-learn on
     the host, exactly as the reference does, and the projected vectors go back to the device for the search).
@@ -111,11 +157,17 @@ def one_nn_identification(X, y: np.ndarray, split=None,
     'nn_dist' become [nq, k]; the search is still timed as nn1_s).
     pca: "host" fits and applies scikit-learn's PCA on the CPU as above; "device" runs ops.pca_fit on the gallery and
     ops.pca_transform on both halves without leaving the GPU (deterministic fp64; a fit that does not converge raises RuntimeError)
-    and records the phase in ``timings`` as pca_s."""
+    and records the phase in ``timings`` as pca_s.
+    classifier: "knn" is all of the above; "linear_svm" is the 'linear svm' row of :429 (with ``pca_components``: the Pipeline of
+    PCA and LinearSVC()) -- LinearSVC(C=svm_C) fitted on the gallery half at the optimum of its objective (ops.linear_svm_fit; a fit
+    that does not converge raises RuntimeError), the probes labelled by ops.linear_svm_predict.  The result then holds 'decision'
+    ([nq, K'] on the host) and 'svm_iterations' in place of 'nn_index' / 'nn_dist', and ``timings`` receives svm_fit_s and
+    svm_predict_s in place of nn1_s.  ``n_neighbors`` must stay 1."""
     import time
     from . import _lib, ops
     ops.check_n_neighbors(n_neighbors)
     check_pca_mode(pca)
+    check_classifier(classifier, n_neighbors, svm_C)
     if pca_components and pca == "device":
         ops.check_pca_components(pca_components)
     torch = _lib.require_gpu()
@@ -155,6 +207,19 @@ def one_nn_identification(X, y: np.ndarray, split=None,
             z = fitted.transform(t.cpu().numpy()).astype(np.float32)
             return torch.from_numpy(np.pad(z, ((0, 0), (0, pad)))).to(Xn.device).contiguous()
         gal, qry = proj(gal), proj(qry)
+    if classifier == "linear_svm":
+        clock = [t]
+
+        def svm_lap(key):
+            clock[0] = lap(key, clock[0])
+        y_pred, decision, svm_iterations = _linear_svm_predict(ops, qry, gal, y_enc[train], svm_C, svm_lap)
+        t = clock[0]
+        acc = float((y_pred == y_enc[test]).mean()) if len(test) else float("nan")
+        t = lap("readback_s", t)
+        if timings is not None:
+            timings.pop("_start", None)
+        return {"accuracy": acc, "indices": indices, "y": y_enc, "train": train, "test": test, "y_pred": y_pred, "decision": decision,
+                "svm_iterations": svm_iterations, "num_classes": int(y_enc.max() + 1) if len(y_enc) else 0}
     if n_neighbors == 1:
         nn_idx, nn_d2 = ops.nn1(qry, gal)
         t = lap("nn1_s", t)
@@ -230,7 +295,8 @@ def cross_validated_1nn(X, y: np.ndarray, cv, normalize: bool = True, device=Non
 
 
 def gallery_probe_identification(X_train, y_train: np.ndarray, X_test, y_test: np.ndarray, normalize: bool = False,
-                                 pca_components: Optional[int] = None, device=None, n_neighbors: int = 1, pca: str = "host") -> Dict:
+                                 pca_components: Optional[int] = None, device=None, n_neighbors: int = 1, pca: str = "host",
+                                 classifier: str = "knn", svm_C: float = 1.0) -> Dict:
     """The gallery / probe protocol of tf_train_test_recognition (facerec_test.py:260-288): the '1-NN' classifier (and
     '1-NN+PCA' with ``pca_components``, 16 at :269) FITTED on the gallery features, every probe labelled by its nearest
     gallery row; accuracy = share of probes whose label is right (:287).  NB the reference computes L2-normalised copies
@@ -239,10 +305,16 @@ def gallery_probe_identification(X_train, y_train: np.ndarray, X_test, y_test: n
     gallery index, scikit-learn's own choice).  ``n_neighbors`` > 1 gives the '3-NN' / '3-NN+PCA' rows of :269-272 (hsefr_knn: the
     uniform vote, equal counts to the smallest label as in scikit-learn's predict; 'nn_index' and 'nn_dist' become [nq, k]).
     ``pca``: "host" is scikit-learn's PCA on the CPU; "device" fits on the gallery and projects both sets with ops.pca_fit /
-    ops.pca_transform on the GPU (deterministic fp64; a fit that does not converge raises RuntimeError)."""
+    ops.pca_transform on the GPU (deterministic fp64; a fit that does not converge raises RuntimeError).
+    ``classifier``: "knn" is all of the above; "linear_svm" gives the 'linear svm' / 'linear svm+PCA' rows of :269-273 -- LinearSVC(C=svm_C)
+    fitted on the gallery (after the projection, when ``pca_components`` is set) at the optimum of its objective (ops.linear_svm_fit; a fit
+    that does not converge raises RuntimeError), the probes labelled by ops.linear_svm_predict: the result holds 'accuracy', 'y_pred',
+    'decision' ([nq, K'] on the host) and 'svm_iterations'.  scikit-learn's default tolerance stops short of the optimum, so its labels
+    can differ on probes whose two largest decision values are closer than about 1e-4 (1e-3 after PCA).  ``n_neighbors`` must stay 1."""
     from . import _lib, ops
     ops.check_n_neighbors(n_neighbors, len(np.asarray(y_train)))
     check_pca_mode(pca)
+    check_classifier(classifier, n_neighbors, svm_C)
     if pca_components and pca == "device":
         ops.check_pca_components(pca_components, len(np.asarray(y_train)))
     torch = _lib.require_gpu()
@@ -267,6 +339,10 @@ def gallery_probe_identification(X_train, y_train: np.ndarray, X_test, y_test: n
             z = fitted.transform(t.cpu().numpy()).astype(np.float32)
             return torch.from_numpy(np.pad(z, ((0, 0), (0, pad)))).to(dev).contiguous()
         gal, qry = proj(gal), proj(qry)
+    if classifier == "linear_svm":
+        y_pred, decision, svm_iterations = _linear_svm_predict(ops, qry, gal, y_train, svm_C)
+        acc = float((y_pred == y_test).mean()) if len(y_test) else float("nan")
+        return {"accuracy": acc, "y_pred": y_pred, "decision": decision, "svm_iterations": svm_iterations}
     if n_neighbors == 1:
         nn_idx, nn_d2 = ops.nn1(qry, gal)
         nn_idx_h = nn_idx.cpu().numpy()

@@ -545,6 +545,85 @@ def pca_transform(x, mean, components):
     return z
 
 
+# hsefr_linear_svm_fit's limits (include/hsefr.h)
+LINEAR_SVM_MAX_N, LINEAR_SVM_MAX_D, LINEAR_SVM_MAX_CLASSES, LINEAR_SVM_MAX_ELEMS = 1 << 20, 1 << 14, 1 << 16, 1 << 30
+
+
+def check_linear_svm_args(n, d, n_classes, C=1.0, tol=1e-10, max_iter=1000) -> None:
+    """hsefr_linear_svm_fit's argument ranges, raised as ValueError before the library or a device is touched."""
+    for name, v, least in (("n", n, 1), ("d", d, 1), ("n_classes", n_classes, 2), ("max_iter", max_iter, 1)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("%s must be an integer, got %r" % (name, v))
+        if v < least:
+            raise ValueError("%s=%d must be at least %d" % (name, v, least))
+    if n > LINEAR_SVM_MAX_N or d > LINEAR_SVM_MAX_D or n_classes > LINEAR_SVM_MAX_CLASSES or n * (d + 1) > LINEAR_SVM_MAX_ELEMS:
+        raise ValueError("n=%d d=%d n_classes=%d over the limits n <= %d, d <= %d, n_classes <= %d, n (d + 1) <= %d"
+                         % (n, d, n_classes, LINEAR_SVM_MAX_N, LINEAR_SVM_MAX_D, LINEAR_SVM_MAX_CLASSES, LINEAR_SVM_MAX_ELEMS))
+    for name, v in (("C", C), ("tol", tol)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError("%s must be a number, got %r" % (name, v))
+    if not (C > 0 and np.isfinite(C)):
+        raise ValueError("C=%r must be positive and finite" % (C,))
+    if not tol > 0:
+        raise ValueError("tol=%r must be positive" % (tol,))
+
+
+@_device_guarded
+def linear_svm_fit(x, labels, n_classes: int, C: float = 1.0, tol: float = 1e-10, max_iter: int = 1000):
+    """LinearSVC(C=C).fit(x, labels) solved to the optimum of its objective, a deterministic fp64 computation on the device
+    (hsefr_linear_svm_fit): x [n,d] float32, labels [n] int32 codes in 0..n_classes-1 -> (coef [K',d], intercept [K']) float64 device
+    tensors, K' = n_classes or 1 for two classes (the row of class 1), and info = {"iterations", "converged", "hessian_products"}.
+    A class is converged when |grad f_k| <= tol |grad f_k(0)|; a fit that stops at ``max_iter`` is returned with converged False: the
+    caller decides.  A label code out of range raises ValueError."""
+    if getattr(x, "ndim", 0) != 2:
+        raise ValueError("x must be [n, d]")
+    check_linear_svm_args(int(x.shape[0]), int(x.shape[1]), n_classes, C, tol, max_iter)      # before anything touches a device
+    torch = _lib.require_gpu()
+    _f32c(x, "x")
+    n, d = x.shape
+    if labels.dtype != torch.int32 or not labels.is_contiguous() or tuple(labels.shape) != (n,) or labels.device != x.device:
+        raise ValueError("labels must be a contiguous int32 tensor of %d values on x's device" % n)
+    rows = 1 if n_classes == 2 else int(n_classes)
+    coef = torch.empty((rows, d), dtype=torch.float64, device=x.device)
+    intercept = torch.empty((rows,), dtype=torch.float64, device=x.device)
+    info = torch.zeros((3,), dtype=torch.int32, device=x.device)
+    _lib.check(_lib.lib().hsefr_linear_svm_fit(x.data_ptr(), n, d, labels.data_ptr(), int(n_classes), float(C), float(tol), int(max_iter),
+                                               coef.data_ptr(), intercept.data_ptr(), info.data_ptr(), _lib.current_stream_ptr()),
+               "hsefr_linear_svm_fit")
+    iterations, converged, products = info.cpu().tolist()
+    return coef, intercept, {"iterations": int(iterations), "converged": bool(converged), "hessian_products": int(products)}
+
+
+@_device_guarded
+def linear_svm_decision(x, coef, intercept):
+    """LinearSVC.decision_function: x . coef^T + intercept accumulated in fp64 (hsefr_linear_svm_decision): [n, K'] float64."""
+    torch = _lib.require_gpu()
+    _f32c(x, "x")
+    n, d = x.shape
+    rows = int(coef.shape[0]) if getattr(coef, "ndim", 0) == 2 else 0
+    for t, name, shape in ((coef, "coef", (rows, d)), (intercept, "intercept", (rows,))):
+        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape and t.device == x.device):
+            raise ValueError("%s must be a contiguous float64 CUDA tensor of shape %s on x's device" % (name, shape))
+    out = torch.empty((n, rows), dtype=torch.float64, device=x.device)
+    _lib.check(_lib.lib().hsefr_linear_svm_decision(x.data_ptr(), n, d, coef.data_ptr(), intercept.data_ptr(), rows, out.data_ptr(),
+                                                    _lib.current_stream_ptr()), "hsefr_linear_svm_decision")
+    return out
+
+
+@_device_guarded
+def linear_svm_predict(decision):
+    """LinearSVC.predict on decision values [n, K'] float64 (hsefr_linear_svm_predict): int32 [n], the column of the largest value with
+    exact ties to the lowest index (np.argmax); K' = 1: decision > 0."""
+    torch = _lib.require_gpu()
+    if not (decision.is_cuda and decision.dtype == torch.float64 and decision.is_contiguous() and decision.ndim == 2):
+        raise ValueError("decision must be a contiguous float64 CUDA tensor [n, K']")
+    n, rows = decision.shape
+    pred = torch.empty((n,), dtype=torch.int32, device=decision.device)
+    _lib.check(_lib.lib().hsefr_linear_svm_predict(decision.data_ptr(), n, rows, pred.data_ptr(), _lib.current_stream_ptr()),
+               "hsefr_linear_svm_predict")
+    return pred
+
+
 @_device_guarded
 def conv2d_direct(x, w_hwio, bias=None, alpha=None, stride: int = 1, padding: str = "VALID"):
     """Generic Conv2D + BiasAdd + optional PReLU (MTCNN nets).  padding: 'VALID' | 'SAME' (TensorFlow rule)."""

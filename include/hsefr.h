@@ -17,6 +17,10 @@
  *       -> hsefr_knn()
  *   - Pipeline(PCA(n_components), KNeighborsClassifier)         facerec_test.py:269-273,417-432 ('1-NN+PCA', '3-NN+PCA', 'k-NN+PCA')
  *       -> hsefr_pca_fit() on the gallery + hsefr_pca_transform() of both sets, then hsefr_nn1() / hsefr_knn()
+ *   - LinearSVC().fit / predict                                 facerec_test.py:269-288 ('linear svm'), :429
+ *       -> hsefr_linear_svm_fit() on the gallery + hsefr_linear_svm_decision() and hsefr_linear_svm_predict() of the probes
+ *   - Pipeline(PCA(n_components), LinearSVC())                  facerec_test.py:269-273 ('linear svm+PCA')
+ *       -> hsefr_pca_fit() + hsefr_pca_transform() as above, then the three hsefr_linear_svm_* calls on the projected rows
  *   - misc.imresize / cv2.resize + BGR + mean   facerec_test.py:93-106 ; facial_analysis.py:95-107
  *       -> hsefr_preprocess_pil_u8() / hsefr_preprocess_cv_u8()
  *
@@ -611,6 +615,34 @@ int hsefr_pca_fit(const float* x, int n, int d, int k, int max_iter, double* mea
  * HSEFR_ERR_UNSUPPORTED.  No workspace, no host synchronisation. */
 int hsefr_pca_transform(const float* x, int n, int d, int k, const double* mean, const double* components, float* z, int ldz,
                         hsefr_stream_t stream);
+
+/* sklearn.svm.LinearSVC(C=C).fit (facerec_test.py:269-288,429) solved to the OPTIMUM of its objective, as a deterministic fp64 computation
+ * on the device: one-vs-rest, L2 penalty, squared hinge loss, fit_intercept with intercept_scaling 1, the bias regularised like any
+ * weight (liblinear).  For class k, with x~ = (x, 1) and y_ik = +1 where labels[i] == k, else -1,
+ *     f_k(w~) = 1/2 |w~|^2 + C sum_i max(0, 1 - y_ik <w~, x~_i>)^2 ,
+ * which is 1-strongly convex: the minimiser is unique and |w~ - w~*| <= |grad f_k(w~)|.  x [n,d] fp32 row-major, labels [n] int32 codes
+ * in 0 .. n_classes - 1.  coef [K',d] and intercept [K'] fp64 with K' = n_classes, except K' = 1 for n_classes == 2: that row belongs
+ * to class 1, as in scikit-learn.  Truncated Newton from W = 0 on every class of a block at once: conjugate gradients on the generalised
+ * Hessian with per-class scalars, an Armijo search over t = 1, 1/2, ... evaluated from X~ w~ and X~ d without a product per trial.  A
+ * class is converged when |grad f_k| <= tol |grad f_k(0)| and is frozen from then on; the call is converged when every class is.
+ * info [3] (int32, device): the Newton iterations used (the most of any block), 1 / 0 for converged, and the batched Hessian-vector
+ * products launched (each covers every unfinished class of its block).  Reaching max_iter, or a step that no search accepts, is NOT
+ * an error here -- the caller reads info.  Results are bit-identical from run to run on one device (sums of fixed shape, no atomics).
+ * n >= 1, d >= 1, n_classes >= 2, C > 0 and finite, tol > 0, max_iter >= 1, and the limits n <= 2^20, d <= 2^14, n_classes <= 2^16,
+ * n (d + 1) <= 2^30: HSEFR_ERR_INVALID otherwise, checked before any device call.  A label code out of range is found on the device
+ * and ends the call as HSEFR_ERR_INVALID before the solver starts.  Classes are solved in blocks of B <= 512 (the rows split evenly):
+ * the stream-ordered workspace is the fp64 copy of X~, n (d + 1) values, plus 3 n B + 6 (d + 1) B values (HSEFR_ERR_NOMEM when it
+ * cannot be had).  The host reads 32 bytes of flags per Newton iteration, so the call synchronises `stream`. */
+int hsefr_linear_svm_fit(const float* x, int n, int d, const int* labels, int n_classes, double C, double tol, int max_iter, double* coef,
+                         double* intercept, int* info /* [3]: iterations, converged, Hessian-vector products */, hsefr_stream_t stream);
+/* LinearSVC.decision_function: out[i][j] = sum_c x[i][c] coef[j][c] + intercept[j], accumulated in fp64, out [n,k_rows] fp64.
+ * n, d, k_rows >= 1 and within hsefr_linear_svm_fit's limits (n k_rows <= 2^30); HSEFR_ERR_INVALID otherwise.  No workspace, no host
+ * synchronisation. */
+int hsefr_linear_svm_decision(const float* x, int n, int d, const double* coef, const double* intercept, int k_rows, double* out,
+                              hsefr_stream_t stream);
+/* LinearSVC.predict on decision values [n,k_rows] fp64: pred [n] int32 = the column of the largest value, exact ties to the lowest
+ * index (np.argmax); with k_rows == 1 the prediction is decision > 0 (0.0 is class 0).  Same limits; no host synchronisation. */
+int hsefr_linear_svm_predict(const double* decision, int n, int k_rows, int* pred, hsefr_stream_t stream);
 
 /* ---- generic small-CNN kernels: the MTCNN detection cascade (facial_analysis.py:334-352,478-604; mtcnn.pb) ---------- */
 
