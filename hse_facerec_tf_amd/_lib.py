@@ -97,6 +97,11 @@ SIGNATURES = {
     "hsefr_linear_svm_fit": (c_int, [_fp, c_int, c_int, _fp, c_int, ctypes.c_double, ctypes.c_double, c_int, _fp, _fp, _fp, c_void_p]),
     "hsefr_linear_svm_decision": (c_int, [_fp, c_int, c_int, _fp, _fp, c_int, _fp, c_void_p]),
     "hsefr_linear_svm_predict": (c_int, [_fp, c_int, c_int, _fp, c_void_p]),
+    "hsefr_rbf_svm_gamma_scale": (c_int, [_fp, c_int, c_int, c_int, _fp, c_void_p]),
+    "hsefr_rbf_svm_fit": (c_int, [_fp, c_int, c_int, _fp, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int, _fp, _fp, _fp,
+                                  c_void_p]),
+    "hsefr_rbf_svm_decision": (c_int, [_fp, c_int, _fp, c_int, c_int, _fp, c_int, ctypes.c_double, _fp, _fp, _fp, c_void_p]),
+    "hsefr_rbf_svm_predict": (c_int, [_fp, c_int, _fp, c_int, c_int, _fp, c_int, ctypes.c_double, _fp, _fp, _fp, _fp, c_void_p]),
 }
 
 # development builds only (csrc/hsefr_dev.h; build.sh with HSEFR_DEV=1): bound when the loaded library has them

@@ -6,7 +6,7 @@ set -euo pipefail
 cd "$(dirname "$0")"
 # product sources.  Development builds add round 1's stem (reachable only through lower_graph(stem_fusion="stem")) and the first window 3x3
 # convolution (conv3x3_w2_bf16.hip took its layers in round 5), each kept for A/B timing, plus the calibration kernels of devtools.hip.
-SRCS="engine.hip conv_first.hip dwconv.hip pwconv_f32.hip pwconv_f16s.hip pwconv_ps.hip pool_dense.hip nn1.hip conv_bf16.hip conv1x1_bf16.hip preprocess.hip dwpw_fused.hip dwpw_f16s.hip stem2_fused.hip stem3_fused.hip stem4_fused.hip stem5_stream.hip conv_f32_mfma.hip smallnet.hip area_resize.hip stem7x7_pool.hip stem7s_stream.hip conv_dma_bf16.hip conv3x3_w2_bf16.hip conv1x1_w4_bf16.hip conv1x1_pair_bf16.hip mtcnn_post.hip linkage.hip hier_linkage.hip dbscan.hip rank_order.hip pca.hip partition_scores.hip linear_svm.hip"
+SRCS="engine.hip conv_first.hip dwconv.hip pwconv_f32.hip pwconv_f16s.hip pwconv_ps.hip pool_dense.hip nn1.hip conv_bf16.hip conv1x1_bf16.hip preprocess.hip dwpw_fused.hip dwpw_f16s.hip stem2_fused.hip stem3_fused.hip stem4_fused.hip stem5_stream.hip conv_f32_mfma.hip smallnet.hip area_resize.hip stem7x7_pool.hip stem7s_stream.hip conv_dma_bf16.hip conv3x3_w2_bf16.hip conv1x1_w4_bf16.hip conv1x1_pair_bf16.hip mtcnn_post.hip linkage.hip hier_linkage.hip dbscan.hip rank_order.hip pca.hip partition_scores.hip linear_svm.hip rbf_svm.hip"
 # -Wno-inline-asm: the LDS-DMA statements write M0 and say so in their clobber lists; clang warns that M0 is a
 # reserved register for every instantiation -- the declaration is the point (the compiler must not assume M0 survives)
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -Wall -Wno-unused-result -Wno-inline-asm"
@@ -15,6 +15,7 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -Wall -Wno
 DEVICE_STRIP="-Xoffload-linker --discard-all"
 LINK="--offload-arch=gfx950"
 LINT=1
+HOST_STRIP=0
 if [ "${HSEFR_ASAN:-0}" = "1" ]; then
   # HSEFR_ASAN=1 build.sh   the HOST half of the same sources under the address + undefined-behaviour sanitizers (no device code is
   #                         compiled and none runs: GPU sanitizers are not available on this pool) -> build_asan/libhsefr_asan.so +
@@ -26,7 +27,10 @@ if [ "${HSEFR_ASAN:-0}" = "1" ]; then
 elif [ "${HSEFR_DEV:-0}" = "1" ]; then
   OUT=../libhsefr_dev.so; BUILD=build_dev; SRCS="$SRCS stem_fused.hip conv3x3_win_bf16.hip devtools.hip"; FLAGS="$FLAGS -DHSEFR_DEV $DEVICE_STRIP"
 else
-  OUT=../libhsefr.so; BUILD=build; FLAGS="$FLAGS $DEVICE_STRIP"
+  # the product also ships without most of its host symbol table (.symtab / .strtab, about 70 KB of 100): the exported functions are in
+  # .dynsym and the device kernels' symbols in .hip_fatbin, both untouched; of .symtab only the kernels' host-side handles stay, the data
+  # symbols from which hsefr_plan_describe reads a launched kernel's name and template arguments (engine.hip, stub_names)
+  OUT=../libhsefr.so; BUILD=build; FLAGS="$FLAGS $DEVICE_STRIP"; HOST_STRIP=1
 fi
 OBJS=""
 PIDS=""
@@ -56,6 +60,9 @@ if [ "$LINT" = "0" ]; then
   OBJS="$OBJS $BUILD/fatbin_stubs.o"
 fi
 hipcc $LINK -shared -fPIC -o "$OUT" $OBJS
+if [ "$HOST_STRIP" = "1" ]; then
+  /opt/rocm/lib/llvm/bin/llvm-strip --strip-all -w --keep-symbol='_ZN5hsefr*_kernel*' --keep-symbol='!*__device_stub__*' "$OUT"
+fi
 if [ "$LINT" = "1" ]; then
   # refuse a library with an unguarded gfx950 store-data hazard (see tools/isa_lint.py)
   python3 ../../tools/isa_lint.py "$OUT"

@@ -17,6 +17,7 @@
 // start is W = 0: two runs give equal bits.  The host reads 32 bytes per Newton iteration: the classes still open, and how the last
 // CG went, from which it sets the number of CG steps it enqueues for the next one.
 #include "common.h"
+#include "svm_gemm.h"
 
 #include <float.h>
 #include <math.h>
@@ -32,9 +33,11 @@ struct SvmOperand {
     long long sr, sk;
     int rows, f32;
 };
-enum { SVM_EP_STORE = 0, SVM_EP_MARGIN = 1, SVM_EP_MASKED = 2, SVM_EP_AXPY = 3, SVM_EP_BIAS = 4 };
+enum { SVM_EP_STORE = 0, SVM_EP_MARGIN = 1, SVM_EP_MASKED = 2, SVM_EP_AXPY = 3, SVM_EP_BIAS = 4, SVM_EP_RBF = 5 };
 // out [M, ncols] with row stride ldo.  MARGIN: out = S, out2 = R, the class of row i is cls0 + i, labels [ncols].  MASKED: mask [M, ncols]
-// (ldo).  AXPY: out = add + alpha * acc, add [M, ncols] (ldo).  BIAS: out = acc + bias[j].
+// (ldo).  AXPY: out = add + alpha * acc, add [M, ncols] (ldo).  BIAS: out = acc + bias[j].  RBF (csrc/rbf_svm.hip, through
+// svm_rbf_kernel_matrix): out = exp(-alpha max(0, aux2[i] + aux[j] - 2 acc)), the squared norms of the rows of A and B; with cls0 != 0
+// (libsvm's training matrix) every value is rounded to fp32 and the diagonal i == j is exactly 1.
 struct SvmEpilogue {
     double* out;
     double* out2;
@@ -44,6 +47,7 @@ struct SvmEpilogue {
     const double* aux;       // mask / add / bias
     const int* labels;
     const int* live;         // per row of the result (a class), or null: a tile without a live row is skipped
+    const double* aux2;      // RBF: the squared norm of each row of A
 };
 
 constexpr int SVM_TM = 32, SVM_TN = 64, SVM_TK = 16;
@@ -128,6 +132,10 @@ __global__ __launch_bounds__(256) void svm_gemm_kernel(SvmOperand A, SvmOperand 
                 v = ep.aux[at] + ep.alpha * v;
             } else if (ep.mode == SVM_EP_BIAS) {
                 v += ep.aux[j];
+            } else if (ep.mode == SVM_EP_RBF) {
+                const double d2 = ep.aux2[i] + ep.aux[j] - 2.0 * v;
+                v = exp(-ep.alpha * (d2 > 0.0 ? d2 : 0.0));
+                if (ep.cls0) v = i == j ? 1.0 : (double)(float)v;
             }
             ep.out[at] = v;
         }
@@ -458,6 +466,14 @@ int svm_fit(const float* x, int n, int d, const int* labels, int n_classes, doub
 }
 
 }  // namespace
+
+int svm_rbf_kernel_matrix(const float* a, int ma, const double* norm_a, const float* b, int mb, const double* norm_b, int d, double gamma,
+                          double* out, long long ldo, int training, const char* what, hipStream_t s) {
+    const SvmOperand ar{a, d, 1, ma, 1}, br{b, d, 1, mb, 1};
+    const SvmEpilogue ep{out, nullptr, ldo, SVM_EP_RBF, mb, training, gamma, norm_b, nullptr, nullptr, norm_a};
+    return svm_gemm(ar, br, ma, mb, d, ep, what, s);
+}
+
 }  // namespace hsefr
 
 using namespace hsefr;

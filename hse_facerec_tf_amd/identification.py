@@ -9,7 +9,8 @@ is scikit-learn's on the host by default (``pca="host"``) or the library's deter
 (``pca="device"``: ops.pca_fit / ops.pca_transform, nothing leaves the GPU between the features and the search).
 ``classifier="linear_svm"`` replaces the search by the reference's 'linear svm' / 'linear svm+PCA' rows (LinearSVC(), facerec_test.py:269-288,
 :429): ops.linear_svm_fit on the gallery, solved to the optimum of LinearSVC's objective in fp64, ops.linear_svm_decision and
-ops.linear_svm_predict on the probes.
+ops.linear_svm_predict on the probes.  ``classifier="rbf_svm"`` gives the 'svm' row (SVC(): libsvm's one-vs-one C-SVC with the RBF kernel):
+ops.rbf_svm_gamma + ops.rbf_svm_fit on the gallery, every pair's dual solved to its optimum in fp64, ops.rbf_svm_predict on the probes.
 """
 from __future__ import annotations
 
@@ -90,10 +91,22 @@ LINEAR_SVM_MAX_ITER = 1000     # hsefr_linear_svm_fit's Newton iteration cap on 
 LINEAR_SVM_TOL = 1e-10         # a class is converged at |grad f_k| <= LINEAR_SVM_TOL |grad f_k(0)|
 
 
-def check_classifier(classifier, n_neighbors=1, svm_C=1.0) -> str:
+RBF_SVM_MAX_ITER = 100000      # hsefr_rbf_svm_fit's iteration cap per pair of classes on the classifier="rbf_svm" path; reaching it raises
+RBF_SVM_TOL = 1e-10            # a pair is converged at m(a) - M(a) <= RBF_SVM_TOL (libsvm's stopping quantity; SVC's default is 1e-3)
+
+
+def check_classifier(classifier, n_neighbors=1, svm_C=1.0, svm_gamma="scale") -> str:
     """The classifier keyword of the protocols, raised as ValueError before the library or a device is touched."""
-    if classifier not in ("knn", "linear_svm"):
-        raise ValueError("classifier=%r must be 'knn' (ops.nn1 / ops.knn) or 'linear_svm' (ops.linear_svm_fit)" % (classifier,))
+    if not isinstance(classifier, str) or classifier not in ("knn", "linear_svm", "rbf_svm"):
+        raise ValueError("classifier=%r must be 'knn' (ops.nn1 / ops.knn), 'linear_svm' (ops.linear_svm_fit) or 'rbf_svm' (ops.rbf_svm_fit)"
+                         % (classifier,))
+    if classifier == "rbf_svm":
+        from . import ops
+        if n_neighbors != 1:
+            raise ValueError("n_neighbors=%r has no meaning with classifier='rbf_svm': leave it at 1" % (n_neighbors,))
+        if isinstance(svm_gamma, str) and svm_gamma != "scale":
+            raise ValueError("svm_gamma=%r must be 'scale' or a positive finite number" % (svm_gamma,))
+        ops.check_rbf_svm_args(2, 1, 2, C=svm_C, gamma=svm_gamma)
     if classifier == "linear_svm":
         from . import ops
         if n_neighbors != 1:
@@ -129,6 +142,33 @@ def _linear_svm_predict(ops, qry, gal, y_gallery: np.ndarray, svm_C: float, lap=
     return classes[pred.cpu().numpy()], decision.cpu().numpy(), info["iterations"]
 
 
+def _rbf_svm_predict(ops, qry, gal, y_gallery: np.ndarray, svm_C: float, svm_gamma, d_used=None, lap=None):
+    """SVC(C=svm_C, gamma=svm_gamma).fit(gal, y_gallery) at the optimum of every pair's dual -> predict of ``qry`` on the device.  The
+    labels are encoded with np.unique (scikit-learn's ``classes_``); ``d_used``: the columns that count for gamma='scale' (the rest is
+    zero padding).  Returns (y_pred, votes [nq,K] on the host, the most iterations of any pair)."""
+    from . import _lib
+    torch = _lib.require_gpu()
+    classes, codes = np.unique(np.asarray(y_gallery), return_inverse=True)
+    n, d = int(gal.shape[0]), int(gal.shape[1])
+    ops.check_rbf_svm_args(n, d, len(classes), C=svm_C, gamma=svm_gamma, tol=RBF_SVM_TOL, max_iter=RBF_SVM_MAX_ITER)
+    labels = torch.from_numpy(codes.astype(np.int32).reshape(-1)).to(gal.device)
+    gamma = ops.rbf_svm_gamma(gal, d_used) if isinstance(svm_gamma, str) else float(svm_gamma)
+    dual_coef, rho, info = ops.rbf_svm_fit(gal, labels, len(classes), gamma, C=svm_C, tol=RBF_SVM_TOL, max_iter=RBF_SVM_MAX_ITER)
+    if not info["converged"]:
+        raise RuntimeError("the device RBF SVM fit on the n=%d x d=%d gallery (K=%d classes) left %d pairs of classes short of the optimum "
+                           "after %d iterations" % (n, d, len(classes), info["pairs_at_max_iter"], info["iterations"]))
+    if lap is not None:
+        lap("svm_fit_s")
+    if qry.shape[0] == 0:                                       # no probe: nothing to label (the entry points want at least one row)
+        if lap is not None:
+            lap("svm_predict_s")
+        return classes[:0], np.zeros((0, len(classes)), dtype=np.int32), info["iterations"]
+    pred, votes = ops.rbf_svm_predict(qry, gal, labels, len(classes), gamma, dual_coef, rho)
+    if lap is not None:
+        lap("svm_predict_s")
+    return classes[pred.cpu().numpy()], votes.cpu().numpy(), info["iterations"]
+
+
 def _knn_predict(ops, qry, gal, y_gallery: np.ndarray, n_neighbors: int):
     """KNeighborsClassifier(n_neighbors).fit(gal, y_gallery) -> kneighbors + predict of ``qry`` on the device (ops.knn).  The labels are
     encoded with np.unique, so the vote's smallest-label rule runs over scikit-learn's sorted ``classes_`` and any label type works.
@@ -143,7 +183,7 @@ def _knn_predict(ops, qry, gal, y_gallery: np.ndarray, n_neighbors: int):
 
 def one_nn_identification(X, y: np.ndarray, split=None,
                           pca_components: Optional[int] = None, timings: Optional[dict] = None, device=None,
-                          n_neighbors: int = 1, pca: str = "host", classifier: str = "knn", svm_C: float = 1.0) -> Dict:
+                          n_neighbors: int = 1, pca: str = "host", classifier: str = "knn", svm_C: float = 1.0, svm_gamma="scale") -> Dict:
     """The protocol of facerec_test.py:401-432: 'k-NN' (pca_components=None) or 'k-NN+PCA'
     (pca_components=128, the Pipeline of :421 -- PCA is fitted on the gallery half by scikit-learn on
     the host, exactly as the reference does, and the projected vectors go back to the device for the search).
@@ -162,12 +202,16 @@ def one_nn_identification(X, y: np.ndarray, split=None,
     PCA and LinearSVC()) -- LinearSVC(C=svm_C) fitted on the gallery half at the optimum of its objective (ops.linear_svm_fit; a fit
     that does not converge raises RuntimeError), the probes labelled by ops.linear_svm_predict.  The result then holds 'decision'
     ([nq, K'] on the host) and 'svm_iterations' in place of 'nn_index' / 'nn_dist', and ``timings`` receives svm_fit_s and
-    svm_predict_s in place of nn1_s.  ``n_neighbors`` must stay 1."""
+    svm_predict_s in place of nn1_s.  ``n_neighbors`` must stay 1.  "rbf_svm" is the 'svm' row, SVC(C=svm_C, gamma=svm_gamma): every pair of
+    classes solved to the optimum of its dual (ops.rbf_svm_fit; a pair that stops at RBF_SVM_MAX_ITER raises RuntimeError), the probes
+    labelled by the pairs' votes (ops.rbf_svm_predict).  ``svm_gamma``: "scale" (from the gallery half, the unpadded columns after a PCA)
+    or a positive finite number.  The result holds 'votes' ([nq, K] on the host) and 'svm_iterations' in place of 'nn_index' /
+    'nn_dist'; ``timings`` as for "linear_svm"."""
     import time
     from . import _lib, ops
     ops.check_n_neighbors(n_neighbors)
     check_pca_mode(pca)
-    check_classifier(classifier, n_neighbors, svm_C)
+    check_classifier(classifier, n_neighbors, svm_C, svm_gamma)
     if pca_components and pca == "device":
         ops.check_pca_components(pca_components)
     torch = _lib.require_gpu()
@@ -207,18 +251,22 @@ def one_nn_identification(X, y: np.ndarray, split=None,
             z = fitted.transform(t.cpu().numpy()).astype(np.float32)
             return torch.from_numpy(np.pad(z, ((0, 0), (0, pad)))).to(Xn.device).contiguous()
         gal, qry = proj(gal), proj(qry)
-    if classifier == "linear_svm":
+    if classifier in ("linear_svm", "rbf_svm"):
         clock = [t]
 
         def svm_lap(key):
             clock[0] = lap(key, clock[0])
-        y_pred, decision, svm_iterations = _linear_svm_predict(ops, qry, gal, y_enc[train], svm_C, svm_lap)
+        if classifier == "linear_svm":
+            y_pred, table, svm_iterations = _linear_svm_predict(ops, qry, gal, y_enc[train], svm_C, svm_lap)
+        else:
+            y_pred, table, svm_iterations = _rbf_svm_predict(ops, qry, gal, y_enc[train], svm_C, svm_gamma, pca_components or None, svm_lap)
         t = clock[0]
         acc = float((y_pred == y_enc[test]).mean()) if len(test) else float("nan")
         t = lap("readback_s", t)
         if timings is not None:
             timings.pop("_start", None)
-        return {"accuracy": acc, "indices": indices, "y": y_enc, "train": train, "test": test, "y_pred": y_pred, "decision": decision,
+        return {"accuracy": acc, "indices": indices, "y": y_enc, "train": train, "test": test, "y_pred": y_pred,
+                "decision" if classifier == "linear_svm" else "votes": table,
                 "svm_iterations": svm_iterations, "num_classes": int(y_enc.max() + 1) if len(y_enc) else 0}
     if n_neighbors == 1:
         nn_idx, nn_d2 = ops.nn1(qry, gal)
@@ -296,7 +344,7 @@ def cross_validated_1nn(X, y: np.ndarray, cv, normalize: bool = True, device=Non
 
 def gallery_probe_identification(X_train, y_train: np.ndarray, X_test, y_test: np.ndarray, normalize: bool = False,
                                  pca_components: Optional[int] = None, device=None, n_neighbors: int = 1, pca: str = "host",
-                                 classifier: str = "knn", svm_C: float = 1.0) -> Dict:
+                                 classifier: str = "knn", svm_C: float = 1.0, svm_gamma="scale") -> Dict:
     """The gallery / probe protocol of tf_train_test_recognition (facerec_test.py:260-288): the '1-NN' classifier (and
     '1-NN+PCA' with ``pca_components``, 16 at :269) FITTED on the gallery features, every probe labelled by its nearest
     gallery row; accuracy = share of probes whose label is right (:287).  NB the reference computes L2-normalised copies
@@ -310,11 +358,17 @@ def gallery_probe_identification(X_train, y_train: np.ndarray, X_test, y_test: n
     fitted on the gallery (after the projection, when ``pca_components`` is set) at the optimum of its objective (ops.linear_svm_fit; a fit
     that does not converge raises RuntimeError), the probes labelled by ops.linear_svm_predict: the result holds 'accuracy', 'y_pred',
     'decision' ([nq, K'] on the host) and 'svm_iterations'.  scikit-learn's default tolerance stops short of the optimum, so its labels
-    can differ on probes whose two largest decision values are closer than about 1e-4 (1e-3 after PCA).  ``n_neighbors`` must stay 1."""
+    can differ on probes whose two largest decision values are closer than about 1e-4 (1e-3 after PCA).  ``n_neighbors`` must stay 1.
+    "rbf_svm" gives the 'svm' row of :269-273, SVC(C=svm_C, gamma=svm_gamma): libsvm's one-vs-one C-SVC with the RBF kernel, every pair of
+    classes solved to the optimum of its dual (ops.rbf_svm_fit; a pair that stops at RBF_SVM_MAX_ITER raises RuntimeError), the probes
+    labelled by the pairs' votes (ops.rbf_svm_predict): the result holds 'accuracy', 'y_pred', 'votes' ([nq, K] on the host) and
+    'svm_iterations'.  ``svm_gamma``: "scale" (1 / (d Var) of the gallery rows, over the unpadded columns after a PCA) or a positive finite
+    number.  scikit-learn's default tolerance stops about 3e-4 short of the optimum in a pair's decision value, so a vote whose value
+    is that close to 0 can differ."""
     from . import _lib, ops
     ops.check_n_neighbors(n_neighbors, len(np.asarray(y_train)))
     check_pca_mode(pca)
-    check_classifier(classifier, n_neighbors, svm_C)
+    check_classifier(classifier, n_neighbors, svm_C, svm_gamma)
     if pca_components and pca == "device":
         ops.check_pca_components(pca_components, len(np.asarray(y_train)))
     torch = _lib.require_gpu()
@@ -343,6 +397,10 @@ def gallery_probe_identification(X_train, y_train: np.ndarray, X_test, y_test: n
         y_pred, decision, svm_iterations = _linear_svm_predict(ops, qry, gal, y_train, svm_C)
         acc = float((y_pred == y_test).mean()) if len(y_test) else float("nan")
         return {"accuracy": acc, "y_pred": y_pred, "decision": decision, "svm_iterations": svm_iterations}
+    if classifier == "rbf_svm":
+        y_pred, votes, svm_iterations = _rbf_svm_predict(ops, qry, gal, y_train, svm_C, svm_gamma, pca_components or None)
+        acc = float((y_pred == y_test).mean()) if len(y_test) else float("nan")
+        return {"accuracy": acc, "y_pred": y_pred, "votes": votes, "svm_iterations": svm_iterations}
     if n_neighbors == 1:
         nn_idx, nn_d2 = ops.nn1(qry, gal)
         nn_idx_h = nn_idx.cpu().numpy()

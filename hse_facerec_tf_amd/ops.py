@@ -624,6 +624,142 @@ def linear_svm_predict(decision):
     return pred
 
 
+# hsefr_rbf_svm_*'s limits (include/hsefr.h)
+RBF_SVM_MAX_N, RBF_SVM_MAX_D, RBF_SVM_MAX_CLASSES, RBF_SVM_MAX_PROBES, RBF_SVM_MAX_DECISIONS = 1 << 14, 1 << 14, 1 << 12, 1 << 20, 1 << 27
+
+
+def check_rbf_svm_args(n, d, n_classes, C=1.0, gamma="scale", tol=1e-10, max_iter=100000) -> None:
+    """hsefr_rbf_svm_fit's argument ranges, raised as ValueError before the library or a device is touched.  ``gamma`` is "scale" or a
+    positive finite number."""
+    for name, v, least in (("n", n, 2), ("d", d, 1), ("n_classes", n_classes, 2), ("max_iter", max_iter, 1)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("%s must be an integer, got %r" % (name, v))
+        if v < least:
+            raise ValueError("%s=%d must be at least %d" % (name, v, least))
+    if n > RBF_SVM_MAX_N or d > RBF_SVM_MAX_D or n_classes > RBF_SVM_MAX_CLASSES or n_classes > n:
+        raise ValueError("n=%d d=%d n_classes=%d over the limits n <= %d, d <= %d, n_classes <= min(n, %d)"
+                         % (n, d, n_classes, RBF_SVM_MAX_N, RBF_SVM_MAX_D, RBF_SVM_MAX_CLASSES))
+    for name, v in (("C", C), ("tol", tol)) + ((("gamma", gamma),) if not (isinstance(gamma, str) and gamma == "scale") else ()):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError("%s must be a number%s, got %r" % (name, " or 'scale'" if name == "gamma" else "", v))
+        if not (v > 0 and np.isfinite(v)):
+            raise ValueError("%s=%r must be positive and finite" % (name, v))
+
+
+def _rbf_svm_model(torch, x, labels, n_classes, gamma, dual_coef, rho):
+    """The fitted model's tensors as hsefr_rbf_svm_decision / _predict want them."""
+    if getattr(x, "ndim", 0) != 2:
+        raise ValueError("x must be [n, d]")
+    check_rbf_svm_args(int(x.shape[0]), int(x.shape[1]), n_classes, gamma=gamma)
+    if isinstance(gamma, str):
+        raise ValueError("gamma must be the number the model was fitted with (ops.rbf_svm_gamma)")
+    _f32c(x, "x")
+    n, K = int(x.shape[0]), int(n_classes)
+    if labels.dtype != torch.int32 or not labels.is_contiguous() or tuple(labels.shape) != (n,) or labels.device != x.device:
+        raise ValueError("labels must be a contiguous int32 tensor of %d values on x's device" % n)
+    for t, name, shape in ((dual_coef, "dual_coef", (K - 1, n)), (rho, "rho", (K * (K - 1) // 2,))):
+        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape and t.device == x.device):
+            raise ValueError("%s must be a contiguous float64 CUDA tensor of shape %s on x's device" % (name, shape))
+
+
+def _rbf_svm_probes(q, x, limit_pairs=None):
+    if getattr(q, "ndim", 0) != 2 or getattr(x, "ndim", 0) != 2 or q.shape[1] != x.shape[1]:
+        raise ValueError("q must be [nq, d] with the d of x")
+    nq = int(q.shape[0])
+    if nq < 1 or nq > RBF_SVM_MAX_PROBES:
+        raise ValueError("nq=%d must be in 1..%d" % (nq, RBF_SVM_MAX_PROBES))
+    if limit_pairs is not None and nq * limit_pairs > RBF_SVM_MAX_DECISIONS:
+        raise ValueError("nq=%d probes x %d pairs over the limit of %d decision values: rbf_svm_predict labels the probes without them"
+                         % (nq, limit_pairs, RBF_SVM_MAX_DECISIONS))
+    return nq
+
+
+@_device_guarded
+def rbf_svm_gamma(x, d_used=None) -> float:
+    """SVC(gamma='scale')'s value 1 / (d_used * Var(x[:, :d_used])) from an fp64 pass over x [n,d] float32 on the device
+    (hsefr_rbf_svm_gamma_scale); 1.0 where the variance is 0.  ``d_used`` (default d) leaves out the zero columns ops.pca_transform pads
+    with."""
+    if getattr(x, "ndim", 0) != 2:
+        raise ValueError("x must be [n, d]")
+    n, d = int(x.shape[0]), int(x.shape[1])
+    d_used = d if d_used is None else d_used
+    if isinstance(d_used, bool) or not isinstance(d_used, (int, np.integer)) or not 1 <= d_used <= d:
+        raise ValueError("d_used=%r must be an integer in 1..%d" % (d_used, d))
+    if n < 1 or n > RBF_SVM_MAX_PROBES or d > RBF_SVM_MAX_D:
+        raise ValueError("n=%d d=%d outside 1 <= n <= %d, d <= %d" % (n, d, RBF_SVM_MAX_PROBES, RBF_SVM_MAX_D))
+    torch = _lib.require_gpu()
+    _f32c(x, "x")
+    gamma = torch.empty((1,), dtype=torch.float64, device=x.device)
+    _lib.check(_lib.lib().hsefr_rbf_svm_gamma_scale(x.data_ptr(), n, d, int(d_used), gamma.data_ptr(), _lib.current_stream_ptr()),
+               "hsefr_rbf_svm_gamma_scale")
+    return float(gamma.cpu()[0])
+
+
+@_device_guarded
+def rbf_svm_fit(x, labels, n_classes: int, gamma, C: float = 1.0, tol: float = 1e-10, max_iter: int = 100000):
+    """SVC(C=C, gamma=gamma).fit(x, labels) -- libsvm's one-vs-one C-SVC with the RBF kernel -- solved to the optimum of every pair's
+    dual, a deterministic fp64 computation on the device (hsefr_rbf_svm_fit): x [n,d] float32, labels [n] int32 codes in
+    0..n_classes-1 in any row order, gamma a positive number (ops.rbf_svm_gamma gives 'scale') -> (dual_coef [n_classes-1, n], rho
+    [n_classes (n_classes-1)/2]) float64 device tensors in libsvm's sv_coef layout and pair order, and info = {"iterations",
+    "converged", "pairs_at_max_iter"}.  A pair is converged at m(a) - M(a) <= tol; a fit in which a pair stops at ``max_iter`` is
+    returned with converged False: the caller decides.  A label code out of range or a class without a row raises ValueError."""
+    if getattr(x, "ndim", 0) != 2:
+        raise ValueError("x must be [n, d]")
+    check_rbf_svm_args(int(x.shape[0]), int(x.shape[1]), n_classes, C, gamma, tol, max_iter)      # before anything touches a device
+    if isinstance(gamma, str):
+        raise ValueError("gamma must be a number here: ops.rbf_svm_gamma(x) gives SVC's 'scale'")
+    torch = _lib.require_gpu()
+    _f32c(x, "x")
+    n, d = x.shape
+    K = int(n_classes)
+    if labels.dtype != torch.int32 or not labels.is_contiguous() or tuple(labels.shape) != (n,) or labels.device != x.device:
+        raise ValueError("labels must be a contiguous int32 tensor of %d values on x's device" % n)
+    dual_coef = torch.empty((K - 1, n), dtype=torch.float64, device=x.device)
+    rho = torch.empty((K * (K - 1) // 2,), dtype=torch.float64, device=x.device)
+    info = torch.zeros((3,), dtype=torch.int32, device=x.device)
+    _lib.check(_lib.lib().hsefr_rbf_svm_fit(x.data_ptr(), n, d, labels.data_ptr(), K, float(gamma), float(C), float(tol), int(max_iter),
+                                            dual_coef.data_ptr(), rho.data_ptr(), info.data_ptr(), _lib.current_stream_ptr()),
+               "hsefr_rbf_svm_fit")
+    iterations, converged, capped = info.cpu().tolist()
+    return dual_coef, rho, {"iterations": int(iterations), "converged": bool(converged), "pairs_at_max_iter": int(capped)}
+
+
+@_device_guarded
+def rbf_svm_decision(q, x, labels, n_classes: int, gamma, dual_coef, rho):
+    """SVC.decision_function(decision_function_shape='ovo') of the probes q [nq,d] (hsefr_rbf_svm_decision): [nq, K (K-1)/2] float64 in
+    libsvm's pair order, at most 2^27 values -- the tests' window into the model; rbf_svm_predict never stores them."""
+    K = int(n_classes) if isinstance(n_classes, (int, np.integer)) and not isinstance(n_classes, bool) else 0
+    nq = _rbf_svm_probes(q, x, K * (K - 1) // 2)
+    torch = _lib.require_gpu()
+    _rbf_svm_model(torch, x, labels, n_classes, gamma, dual_coef, rho)
+    _f32c(q, "q")
+    n, d = x.shape
+    out = torch.empty((nq, K * (K - 1) // 2), dtype=torch.float64, device=x.device)
+    _lib.check(_lib.lib().hsefr_rbf_svm_decision(q.data_ptr(), nq, x.data_ptr(), n, d, labels.data_ptr(), K, float(gamma),
+                                                 dual_coef.data_ptr(), rho.data_ptr(), out.data_ptr(), _lib.current_stream_ptr()),
+               "hsefr_rbf_svm_decision")
+    return out
+
+
+@_device_guarded
+def rbf_svm_predict(q, x, labels, n_classes: int, gamma, dual_coef, rho, return_votes: bool = True):
+    """SVC.predict of the probes q [nq,d] (hsefr_rbf_svm_predict): (pred [nq] int32, votes [nq, K] int32 or None).  A pair's decision
+    > 0 votes for its first class, anything else for its second; the label is the first class with the most votes (libsvm)."""
+    nq = _rbf_svm_probes(q, x)
+    torch = _lib.require_gpu()
+    _rbf_svm_model(torch, x, labels, n_classes, gamma, dual_coef, rho)
+    _f32c(q, "q")
+    n, d = x.shape
+    K = int(n_classes)
+    pred = torch.empty((nq,), dtype=torch.int32, device=x.device)
+    votes = torch.empty((nq, K), dtype=torch.int32, device=x.device) if return_votes else None
+    _lib.check(_lib.lib().hsefr_rbf_svm_predict(q.data_ptr(), nq, x.data_ptr(), n, d, labels.data_ptr(), K, float(gamma),
+                                                dual_coef.data_ptr(), rho.data_ptr(), pred.data_ptr(),
+                                                votes.data_ptr() if votes is not None else None, _lib.current_stream_ptr()),
+               "hsefr_rbf_svm_predict")
+    return pred, votes
+
+
 @_device_guarded
 def conv2d_direct(x, w_hwio, bias=None, alpha=None, stride: int = 1, padding: str = "VALID"):
     """Generic Conv2D + BiasAdd + optional PReLU (MTCNN nets).  padding: 'VALID' | 'SAME' (TensorFlow rule)."""

@@ -21,6 +21,9 @@
  *       -> hsefr_linear_svm_fit() on the gallery + hsefr_linear_svm_decision() and hsefr_linear_svm_predict() of the probes
  *   - Pipeline(PCA(n_components), LinearSVC())                  facerec_test.py:269-273 ('linear svm+PCA')
  *       -> hsefr_pca_fit() + hsefr_pca_transform() as above, then the three hsefr_linear_svm_* calls on the projected rows
+ *   - SVC().fit / predict                                       facerec_test.py:269-288 ('svm')
+ *       -> hsefr_rbf_svm_gamma_scale() + hsefr_rbf_svm_fit() on the gallery, hsefr_rbf_svm_predict() of the probes
+ *          (hsefr_rbf_svm_decision() shows the pair decisions of a few probes)
  *   - misc.imresize / cv2.resize + BGR + mean   facerec_test.py:93-106 ; facial_analysis.py:95-107
  *       -> hsefr_preprocess_pil_u8() / hsefr_preprocess_cv_u8()
  *
@@ -643,6 +646,50 @@ int hsefr_linear_svm_decision(const float* x, int n, int d, const double* coef, 
 /* LinearSVC.predict on decision values [n,k_rows] fp64: pred [n] int32 = the column of the largest value, exact ties to the lowest
  * index (np.argmax); with k_rows == 1 the prediction is decision > 0 (0.0 is class 0).  Same limits; no host synchronisation. */
 int hsefr_linear_svm_predict(const double* decision, int n, int k_rows, int* pred, hsefr_stream_t stream);
+
+/* sklearn.svm.SVC(C=C, gamma=gamma) (facerec_test.py:269-288 'svm': libsvm's C-SVC with the RBF kernel, one-vs-one) solved to the OPTIMUM of
+ * its objective, as a deterministic fp64 computation on the device.  For every pair of classes (i, j), i < j, class i is +1 and
+ *     min 1/2 a^T Q a - e^T a ,  0 <= a <= C ,  y^T a = 0 ,  Q_ab = y_a y_b exp(-gamma |x_a - x_b|^2)
+ * over the rows of the two classes; for distinct rows Q is positive definite and the minimiser unique (rows that are equal in two
+ * classes leave it open: out of scope).
+ *
+ * hsefr_rbf_svm_gamma_scale: gamma [1] fp64 (device) = 1 / (d_used * Var(x[:, :d_used])), the variance of all those elements in fp64
+ * about their fp64 mean -- SVC(gamma='scale'); 1.0 where the variance is 0.  d_used <= d leaves out the zero columns that
+ * hsefr_pca_transform pads with: they change no kernel value but would change the variance.  Sums of a fixed shape, no atomics.
+ * 1 <= d_used <= d <= 2^14, 1 <= n <= 2^20 (HSEFR_ERR_INVALID otherwise); a workspace of 257 doubles; no host synchronisation. */
+int hsefr_rbf_svm_gamma_scale(const float* x, int n, int d, int d_used, double* gamma, hsefr_stream_t stream);
+/* The fit.  x [n,d] fp32 row-major, labels [n] int32 codes in 0 .. n_classes - 1 in ANY row order.  dual_coef [(n_classes - 1), n] fp64 in
+ * the caller's row order: row r of column a is y a of row a in its pair with the opponent class r if r < labels[a], else r + 1
+ * (libsvm's sv_coef; scikit-learn's dual_coef_ scattered by support_).  rho [n_classes (n_classes - 1) / 2] fp64 in libsvm's pair order
+ * (0,1), (0,2), ..., (1,2), ...: the mean of y G over the free variables, without one the midpoint of the bounded ones' range.
+ * The rows are grouped by class on the device, one Gram matrix is formed in fp64 (diagonal exactly 1, |a|^2 + |b|^2 - 2 <a,b> clamped at
+ * 0; every other value rounded once to fp32, as libsvm's solver holds its Q: SVC's optimum is that of the rounded matrix, 1e-8 in
+ * decision values from the unrounded one's) and every pair is solved from a = 0 by SMO with libsvm's second-order working set selection until m(a) - M(a) <= tol (m the largest
+ * -y G over I_up, M the smallest over I_low), a clipped exactly to [0, C]: a workgroup for a pair of more than 64 rows, the largest
+ * first, a wave for the others.  info [3] (int32, device): the most iterations of any pair, 1 / 0 for converged (every pair), and the
+ * number of pairs that stopped at max_iter.  Reaching max_iter is NOT an error here -- the caller reads info.  Results are bit-identical
+ * from run to run on one device (sums of fixed shape, integer atomics only).
+ * n >= 2, d >= 1, 2 <= n_classes <= n, gamma, C and tol > 0 and finite, max_iter >= 1, and the limits n <= 2^14, d <= 2^14,
+ * n_classes <= 2^12: HSEFR_ERR_INVALID otherwise, checked before any device call.  A label code out of range or a class without a row is
+ * found on the device and ends the call as HSEFR_ERR_INVALID before the solver starts.  Stream-ordered workspace: 8 n^2 bytes of Gram
+ * matrix, 4 n d of grouped rows, 8 bytes per pair, and 16 bytes per row of every pair of more than 1024 rows (HSEFR_ERR_NOMEM when it
+ * cannot be had).  The host reads the class sizes and orders the pairs, so the call synchronises `stream`. */
+int hsefr_rbf_svm_fit(const float* x, int n, int d, const int* labels, int n_classes, double gamma, double C, double tol, int max_iter,
+                      double* dual_coef, double* rho, int* info /* [3]: iterations, converged, pairs at max_iter */, hsefr_stream_t stream);
+/* SVC.decision_function(decision_function_shape='ovo') of the probes q [nq,d]: out [nq, n_classes (n_classes - 1) / 2] fp64,
+ * out[q][(i,j)] = sum over the rows a of classes i and j of dual_coef[.][a] exp(-gamma |q - x_a|^2) - rho[(i,j)], the rows of i in the
+ * caller's order, then those of j.  x, labels, n_classes and gamma are the fit's.  The model's limits, 1 <= nq <= 2^20, and
+ * nq n_classes (n_classes - 1) / 2 <= 2^27 (1 GiB of values: the table of an LFW-sized protocol would be 51 GB -- hsefr_rbf_svm_predict
+ * labels the probes without it); HSEFR_ERR_INVALID otherwise.  Workspace: dual_coef over the grouped rows and one kernel matrix of n x
+ * min(nq, 1024) fp64.  Synchronises `stream`. */
+int hsefr_rbf_svm_decision(const float* q, int nq, const float* x, int n, int d, const int* labels, int n_classes, double gamma,
+                           const double* dual_coef, const double* rho, double* out, hsefr_stream_t stream);
+/* SVC.predict: pred [nq] int32 and, where not NULL, votes [nq, n_classes] int32.  The same pair values as hsefr_rbf_svm_decision, bit for
+ * bit, never stored: a value > 0 is a vote for i, anything else (exactly 0 too) for j; the label is the FIRST class with the most votes
+ * (libsvm).  Per tile of at most 1024 probes one kernel matrix and one pass over dual_coef.  Limits, workspace (plus 4 n_classes x 1024
+ * bytes of votes) and synchronisation as above. */
+int hsefr_rbf_svm_predict(const float* q, int nq, const float* x, int n, int d, const int* labels, int n_classes, double gamma,
+                          const double* dual_coef, const double* rho, int* pred, int* votes, hsefr_stream_t stream);
 
 /* ---- generic small-CNN kernels: the MTCNN detection cascade (facial_analysis.py:334-352,478-604; mtcnn.pb) ---------- */
 
