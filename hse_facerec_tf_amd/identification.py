@@ -4,17 +4,37 @@ Host steps stay what the reference does on the host -- including its own scikit-
 for the label encoding and the stratified split (scikit-learn is a dependency of the
 reference's callers, not of the engine); the O(N_test x N_train x D) nearest-neighbour search
 (KNeighborsClassifier(1).fit/predict, :422,:203) and the L2 normalisation (:401) run through
-libhsefr (ops.l2_normalize / ops.nn1; ops.knn for the reference's '3-NN' rows, facerec_test.py:269-288).  The PCA of the '+PCA' rows
-is scikit-learn's on the host by default (``pca="host"``) or the library's deterministic fp64 fit and projection on the device
-(``pca="device"``: ops.pca_fit / ops.pca_transform, nothing leaves the GPU between the features and the search).
-``classifier="linear_svm"`` replaces the search by the reference's 'linear svm' / 'linear svm+PCA' rows (LinearSVC(), facerec_test.py:269-288,
-:429): ops.linear_svm_fit on the gallery, solved to the optimum of LinearSVC's objective in fp64, ops.linear_svm_decision and
-ops.linear_svm_predict on the probes.  ``classifier="rbf_svm"`` gives the 'svm' row (SVC(): libsvm's one-vs-one C-SVC with the RBF kernel):
-ops.rbf_svm_gamma + ops.rbf_svm_fit on the gallery, every pair's dual solved to its optimum in fp64, ops.rbf_svm_predict on the probes.
+libhsefr (ops.l2_normalize / ops.nn1).
+
+Every protocol is upload / normalise / select of its own, then the same two steps on (gallery, probes): the projection of the '+PCA'
+rows and the classifier.  Their keywords, shared by one_nn_identification and gallery_probe_identification:
+
+n_neighbors: 1 labels a probe by its nearest gallery row (ops.nn1: ties -> the lowest gallery index, scikit-learn's own choice); more
+    gives the '3-NN' / '3-NN+PCA' rows (facerec_test.py:269-288, :269-272) by the uniform vote of that many (ops.knn: equal counts to the
+    smallest label as in scikit-learn's predict; 'nn_index' and 'nn_dist' become [nq, k]; the search is still timed as nn1_s).
+pca_components, pca: the PCA is fitted on the gallery and applied to both sets, zero-padded to a multiple of 8 columns.  pca="host" is
+    scikit-learn's PCA on the CPU, exactly as the reference does, the projected vectors going back to the device; pca="device" is the
+    library's deterministic fp64 fit and projection (ops.pca_fit / ops.pca_transform: nothing leaves the GPU between the features and
+    the search; a fit that does not converge in PCA_MAX_ITER iterations raises RuntimeError), timed as pca_s.
+classifier: "knn" is all of the above.  "linear_svm" replaces the search by the reference's 'linear svm' / 'linear svm+PCA' rows
+    (LinearSVC(), facerec_test.py:269-288, :269-273, :429; with ``pca_components``: the Pipeline of PCA and LinearSVC()): LinearSVC(C=svm_C)
+    fitted on the gallery, after the projection, solved to the optimum of its objective in fp64 (ops.linear_svm_fit; a fit that does
+    not converge raises RuntimeError), the probes labelled by ops.linear_svm_decision + ops.linear_svm_predict.  The result holds
+    'decision' ([nq, K'] on the host) and 'svm_iterations' in place of 'nn_index' / 'nn_dist', and ``timings`` receives svm_fit_s and
+    svm_predict_s in place of nn1_s.  scikit-learn's default tolerance stops short of the optimum, so its labels can differ on probes
+    whose two largest decision values are closer than about 1e-4 (1e-3 after PCA).  ``n_neighbors`` must stay 1.
+    "rbf_svm" gives the 'svm' row of :269-273, SVC(C=svm_C, gamma=svm_gamma): libsvm's one-vs-one C-SVC with the RBF kernel, every pair
+    of classes solved to the optimum of its dual in fp64 (ops.rbf_svm_gamma + ops.rbf_svm_fit; a pair that stops at RBF_SVM_MAX_ITER
+    raises RuntimeError), the probes labelled by the pairs' votes (ops.rbf_svm_predict).  The result holds 'votes' ([nq, K] on the host)
+    and 'svm_iterations' in place of 'nn_index' / 'nn_dist'; ``timings`` as for "linear_svm".  scikit-learn's default tolerance stops
+    about 3e-4 short of the optimum in a pair's decision value, so a vote whose value is that close to 0 can differ.  ``n_neighbors``
+    must stay 1.
+svm_C: the C of either SVM.  svm_gamma: "scale" (1 / (d Var) of the gallery rows, over the unpadded columns after a PCA) or a positive
+    finite number.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -71,28 +91,17 @@ def start_split(y: np.ndarray, random_state: int = 0) -> SplitJob:
 
 PCA_MAX_ITER = 1000     # hsefr_pca_fit's iteration cap on the pca="device" path; reaching it raises
 
+LINEAR_SVM_MAX_ITER = 1000     # hsefr_linear_svm_fit's Newton iteration cap on the classifier="linear_svm" path; reaching it raises
+LINEAR_SVM_TOL = 1e-10         # a class is converged at |grad f_k| <= LINEAR_SVM_TOL |grad f_k(0)|
+
+RBF_SVM_MAX_ITER = 100000      # hsefr_rbf_svm_fit's iteration cap per pair of classes on the classifier="rbf_svm" path; reaching it raises
+RBF_SVM_TOL = 1e-10            # a pair is converged at m(a) - M(a) <= RBF_SVM_TOL (libsvm's stopping quantity; SVC's default is 1e-3)
+
 
 def check_pca_mode(pca) -> str:
     if pca not in ("host", "device"):
         raise ValueError("pca=%r must be 'host' (scikit-learn on the CPU) or 'device' (ops.pca_fit / ops.pca_transform)" % (pca,))
     return pca
-
-
-def _device_pca(ops, gal, qry, pca_components: int):
-    """Fit on the gallery, project both sets (float32, zero-padded to a multiple of 8 columns), all on the device."""
-    mean, components, _, info = ops.pca_fit(gal, pca_components, max_iter=PCA_MAX_ITER)
-    if not info["converged"]:
-        raise RuntimeError("the device PCA of the %d x %d gallery (%d components) did not converge in %d iterations"
-                           % (gal.shape[0], gal.shape[1], pca_components, info["iterations"]))
-    return ops.pca_transform(gal, mean, components), ops.pca_transform(qry, mean, components)
-
-
-LINEAR_SVM_MAX_ITER = 1000     # hsefr_linear_svm_fit's Newton iteration cap on the classifier="linear_svm" path; reaching it raises
-LINEAR_SVM_TOL = 1e-10         # a class is converged at |grad f_k| <= LINEAR_SVM_TOL |grad f_k(0)|
-
-
-RBF_SVM_MAX_ITER = 100000      # hsefr_rbf_svm_fit's iteration cap per pair of classes on the classifier="rbf_svm" path; reaching it raises
-RBF_SVM_TOL = 1e-10            # a pair is converged at m(a) - M(a) <= RBF_SVM_TOL (libsvm's stopping quantity; SVC's default is 1e-3)
 
 
 def check_classifier(classifier, n_neighbors=1, svm_C=1.0, svm_gamma="scale") -> str:
@@ -115,175 +124,177 @@ def check_classifier(classifier, n_neighbors=1, svm_C=1.0, svm_gamma="scale") ->
     return classifier
 
 
-def _linear_svm_predict(ops, qry, gal, y_gallery: np.ndarray, svm_C: float, lap=None):
-    """LinearSVC(C=svm_C).fit(gal, y_gallery) at the objective's optimum -> decision_function + predict of ``qry`` on the device.  The
-    labels are encoded with np.unique (scikit-learn's ``classes_``), so any label type works.  Returns (y_pred, decision [nq,K'] on the
-    host, Newton iterations)."""
-    from . import _lib
-    torch = _lib.require_gpu()
-    classes, codes = np.unique(np.asarray(y_gallery), return_inverse=True)
-    n, d = int(gal.shape[0]), int(gal.shape[1])
-    ops.check_linear_svm_args(n, d, len(classes), C=svm_C, tol=LINEAR_SVM_TOL, max_iter=LINEAR_SVM_MAX_ITER)
-    labels = torch.from_numpy(codes.astype(np.int32).reshape(-1)).to(gal.device)
-    coef, intercept, info = ops.linear_svm_fit(gal, labels, len(classes), C=svm_C, tol=LINEAR_SVM_TOL, max_iter=LINEAR_SVM_MAX_ITER)
+class _Keywords(NamedTuple):
+    """The keywords of the module docstring, checked."""
+    n_neighbors: int
+    pca: str
+    pca_components: Optional[int]
+    classifier: str
+    svm_C: float
+    svm_gamma: object
+
+
+def _check_keywords(n_neighbors=1, pca="host", pca_components=None, classifier="knn", svm_C=1.0, svm_gamma="scale",
+                    n_gallery=None) -> _Keywords:
+    """Every keyword check of the protocols, raised as ValueError before the library is loaded or a device is touched; ``n_gallery``:
+    the gallery rows, where the protocol knows them this early."""
+    from . import ops
+    ops.check_n_neighbors(n_neighbors, n_gallery)
+    check_pca_mode(pca)
+    check_classifier(classifier, n_neighbors, svm_C, svm_gamma)
+    if pca_components and pca == "device":
+        ops.check_pca_components(pca_components, n_gallery)
+    return _Keywords(n_neighbors, pca, pca_components, classifier, svm_C, svm_gamma)
+
+
+def _phase_clock(torch, device, timings: Optional[dict]):
+    """lap(key): ``timings[key]`` = the device-synchronised wall seconds since the previous lap (the first: since this call).  Without
+    ``timings`` a lap does nothing, and synchronises nothing."""
+    import time
+    if timings is None:
+        return lambda key: None
+    torch.cuda.synchronize(device)
+    t_prev = time.perf_counter()
+
+    def lap(key):
+        nonlocal t_prev
+        torch.cuda.synchronize(device)
+        t = time.perf_counter()
+        timings[key] = t - t_prev
+        t_prev = t
+    return lap
+
+
+def _rows(torch, X, index):
+    return X[torch.from_numpy(np.asarray(index, dtype=np.int64)).to(X.device)].contiguous()
+
+
+def _accuracy(y_pred: np.ndarray, y_true: np.ndarray) -> float:
+    return float((y_pred == y_true).mean()) if len(y_true) else float("nan")
+
+
+def _device_pca(ops, gal, qry, pca_components: int):
+    """Fit on the gallery, project both sets (float32, zero-padded to a multiple of 8 columns), all on the device."""
+    mean, components, _, info = ops.pca_fit(gal, pca_components, max_iter=PCA_MAX_ITER)
     if not info["converged"]:
-        raise RuntimeError("the device linear SVM fit on the n=%d x d=%d gallery (K=%d classes) did not converge in %d iterations"
-                           % (n, d, len(classes), info["iterations"]))
-    if lap is not None:
-        lap("svm_fit_s")
-    if qry.shape[0] == 0:                                       # no probe: nothing to label (the entry points want at least one row)
-        if lap is not None:
-            lap("svm_predict_s")
-        return classes[:0], np.zeros((0, int(coef.shape[0])), dtype=np.float64), info["iterations"]
-    decision = ops.linear_svm_decision(qry, coef, intercept)
-    pred = ops.linear_svm_predict(decision)
-    if lap is not None:
-        lap("svm_predict_s")
-    return classes[pred.cpu().numpy()], decision.cpu().numpy(), info["iterations"]
+        raise RuntimeError("the device PCA of the %d x %d gallery (%d components) did not converge in %d iterations"
+                           % (gal.shape[0], gal.shape[1], pca_components, info["iterations"]))
+    return ops.pca_transform(gal, mean, components), ops.pca_transform(qry, mean, components)
 
 
-def _rbf_svm_predict(ops, qry, gal, y_gallery: np.ndarray, svm_C: float, svm_gamma, d_used=None, lap=None):
-    """SVC(C=svm_C, gamma=svm_gamma).fit(gal, y_gallery) at the optimum of every pair's dual -> predict of ``qry`` on the device.  The
-    labels are encoded with np.unique (scikit-learn's ``classes_``); ``d_used``: the columns that count for gamma='scale' (the rest is
-    zero padding).  Returns (y_pred, votes [nq,K] on the host, the most iterations of any pair)."""
-    from . import _lib
-    torch = _lib.require_gpu()
+def _reduce(torch, ops, gal, qry, kw: _Keywords, device, lap=lambda key: None):
+    """The PCA of the '+PCA' rows (the Pipeline of facerec_test.py:421): (gal, qry) -> (gal, qry) in ``pca_components`` columns,
+    fitted on the gallery; the host's projection goes to ``device``.  Only the device's fit is a phase of its own (pca_s)."""
+    if not kw.pca_components:
+        return gal, qry
+    if kw.pca == "device":
+        gal, qry = _device_pca(ops, gal, qry, kw.pca_components)
+        lap("pca_s")
+        return gal, qry
+    from sklearn.decomposition import PCA
+    fitted = PCA(n_components=kw.pca_components).fit(gal.cpu().numpy())
+    pad = (-kw.pca_components) % 8                      # hsefr_nn1 wants d % 8 == 0: zero columns change no distance
+
+    def proj(t):
+        z = fitted.transform(t.cpu().numpy()).astype(np.float32)
+        return torch.from_numpy(np.pad(z, ((0, 0), (0, pad)))).to(device).contiguous()
+    return proj(gal), proj(qry)
+
+
+def _encode_labels(torch, y_gallery: np.ndarray, device):
+    """np.unique's sorted classes (scikit-learn's ``classes_``, so any label type works and a vote's smallest-label rule runs over
+    them) and the gallery's codes as an int32 tensor on ``device``."""
     classes, codes = np.unique(np.asarray(y_gallery), return_inverse=True)
-    n, d = int(gal.shape[0]), int(gal.shape[1])
-    ops.check_rbf_svm_args(n, d, len(classes), C=svm_C, gamma=svm_gamma, tol=RBF_SVM_TOL, max_iter=RBF_SVM_MAX_ITER)
-    labels = torch.from_numpy(codes.astype(np.int32).reshape(-1)).to(gal.device)
-    gamma = ops.rbf_svm_gamma(gal, d_used) if isinstance(svm_gamma, str) else float(svm_gamma)
-    dual_coef, rho, info = ops.rbf_svm_fit(gal, labels, len(classes), gamma, C=svm_C, tol=RBF_SVM_TOL, max_iter=RBF_SVM_MAX_ITER)
-    if not info["converged"]:
-        raise RuntimeError("the device RBF SVM fit on the n=%d x d=%d gallery (K=%d classes) left %d pairs of classes short of the optimum "
-                           "after %d iterations" % (n, d, len(classes), info["pairs_at_max_iter"], info["iterations"]))
-    if lap is not None:
-        lap("svm_fit_s")
-    if qry.shape[0] == 0:                                       # no probe: nothing to label (the entry points want at least one row)
-        if lap is not None:
-            lap("svm_predict_s")
-        return classes[:0], np.zeros((0, len(classes)), dtype=np.int32), info["iterations"]
-    pred, votes = ops.rbf_svm_predict(qry, gal, labels, len(classes), gamma, dual_coef, rho)
-    if lap is not None:
+    return classes, torch.from_numpy(codes.astype(np.int32).reshape(-1)).to(device)
+
+
+def _classify(torch, ops, gal, qry, y_gallery: np.ndarray, kw: _Keywords, lap=lambda key: None):
+    """The classifier of ``kw`` fitted on (gal, y_gallery) and applied to ``qry`` on the device -> (y_pred, extras), everything on the
+    host.  extras: 'nn_index' + 'nn_dist' of the searches, 'decision' + 'svm_iterations' of the linear SVM, 'votes' + 'svm_iterations'
+    of the RBF SVM.  ``lap`` (a _phase_clock) is called with nn1_s after the search -- for n_neighbors = 1 before anything is copied
+    to the host, for more after the copies -- or with svm_fit_s and svm_predict_s."""
+    if kw.classifier == "knn" and kw.n_neighbors == 1:
+        nn_idx, nn_d2 = ops.nn1(qry, gal)
+        lap("nn1_s")
+        nn_idx_h = nn_idx.cpu().numpy()
+        return y_gallery[nn_idx_h], {"nn_index": nn_idx_h, "nn_dist": np.sqrt(nn_d2.cpu().numpy())}
+    classes, labels = _encode_labels(torch, y_gallery, gal.device)
+    if kw.classifier == "knn":                  # KNeighborsClassifier(n_neighbors): kneighbors + predict
+        idx, d2, pred = ops.knn(qry, gal, kw.n_neighbors, labels)
+        y_pred, extras = classes[pred.cpu().numpy()], {"nn_index": idx.cpu().numpy(), "nn_dist": np.sqrt(d2.cpu().numpy())}
+        lap("nn1_s")
+        return y_pred, extras
+    n, d, K = int(gal.shape[0]), int(gal.shape[1]), len(classes)
+    if kw.classifier == "linear_svm":           # LinearSVC(C=svm_C): decision_function + predict
+        coef, intercept, info = ops.linear_svm_fit(gal, labels, K, C=kw.svm_C, tol=LINEAR_SVM_TOL, max_iter=LINEAR_SVM_MAX_ITER)
+        if not info["converged"]:
+            raise RuntimeError("the device linear SVM fit on the n=%d x d=%d gallery (K=%d classes) did not converge in %d iterations"
+                               % (n, d, K, info["iterations"]))
+        table, no_probe = "decision", np.zeros((0, int(coef.shape[0])), dtype=np.float64)
+
+        def predict():
+            decision = ops.linear_svm_decision(qry, coef, intercept)
+            return ops.linear_svm_predict(decision), decision
+    else:                                       # SVC(C=svm_C, gamma=svm_gamma): predict and the pairs' votes
+        # before ops.rbf_svm_gamma, which words a gallery over the limits in its own way
+        ops.check_rbf_svm_args(n, d, K, C=kw.svm_C, gamma=kw.svm_gamma, tol=RBF_SVM_TOL, max_iter=RBF_SVM_MAX_ITER)
+        # gamma='scale' counts the columns of the projection, not its zero padding
+        gamma = ops.rbf_svm_gamma(gal, kw.pca_components or None) if isinstance(kw.svm_gamma, str) else float(kw.svm_gamma)
+        dual_coef, rho, info = ops.rbf_svm_fit(gal, labels, K, gamma, C=kw.svm_C, tol=RBF_SVM_TOL, max_iter=RBF_SVM_MAX_ITER)
+        if not info["converged"]:
+            raise RuntimeError("the device RBF SVM fit on the n=%d x d=%d gallery (K=%d classes) left %d pairs of classes short of the "
+                               "optimum after %d iterations" % (n, d, K, info["pairs_at_max_iter"], info["iterations"]))
+        table, no_probe = "votes", np.zeros((0, K), dtype=np.int32)
+
+        def predict():
+            return ops.rbf_svm_predict(qry, gal, labels, K, gamma, dual_coef, rho)
+    lap("svm_fit_s")
+    if qry.shape[0] == 0:                       # no probe: nothing to label (the entry points want at least one row)
         lap("svm_predict_s")
-    return classes[pred.cpu().numpy()], votes.cpu().numpy(), info["iterations"]
-
-
-def _knn_predict(ops, qry, gal, y_gallery: np.ndarray, n_neighbors: int):
-    """KNeighborsClassifier(n_neighbors).fit(gal, y_gallery) -> kneighbors + predict of ``qry`` on the device (ops.knn).  The labels are
-    encoded with np.unique, so the vote's smallest-label rule runs over scikit-learn's sorted ``classes_`` and any label type works.
-    Returns (y_pred, nn_index [nq,k], nn_dist [nq,k]) on the host."""
-    from . import _lib
-    torch = _lib.require_gpu()
-    classes, codes = np.unique(np.asarray(y_gallery), return_inverse=True)
-    labels = torch.from_numpy(codes.astype(np.int32).reshape(-1)).to(gal.device)
-    idx, d2, pred = ops.knn(qry, gal, n_neighbors, labels)
-    return classes[pred.cpu().numpy()], idx.cpu().numpy(), np.sqrt(d2.cpu().numpy())
+        return classes[:0], {table: no_probe, "svm_iterations": info["iterations"]}
+    pred, values = predict()
+    lap("svm_predict_s")
+    return classes[pred.cpu().numpy()], {table: values.cpu().numpy(), "svm_iterations": info["iterations"]}
 
 
 def one_nn_identification(X, y: np.ndarray, split=None,
                           pca_components: Optional[int] = None, timings: Optional[dict] = None, device=None,
                           n_neighbors: int = 1, pca: str = "host", classifier: str = "knn", svm_C: float = 1.0, svm_gamma="scale") -> Dict:
-    """The protocol of facerec_test.py:401-432: 'k-NN' (pca_components=None) or 'k-NN+PCA'
-    (pca_components=128, the Pipeline of :421 -- PCA is fitted on the gallery half by scikit-learn on
-    the host, exactly as the reference does, and the projected vectors go back to the device for the search).
+    """The protocol of facerec_test.py:401-432: 'k-NN' (pca_components=None) or 'k-NN+PCA' (pca_components=128, the Pipeline of :421)
+    on a stratified half split of the samples whose class has more than one; ``classifier`` gives the 'linear svm' row of :429 and the
+    'svm' row instead.  n_neighbors, pca, classifier, svm_C and svm_gamma: see the module docstring; the gallery is the train half.
 
     X: [N, D] float32 embeddings, CUDA tensor or NumPy array (uploaded to ``device``, default: the current one); y: [N] labels.
     split: None (compute it here), a (train, test) pair over the FILTERED samples, or a SplitJob started on the same labels.
-    Returns accuracy, the split, predictions and nearest-gallery indices.  ``timings`` (optional dict) receives the
-    device-synchronised wall seconds of each phase: normalize_s, host_split_s, select_s, nn1_s, readback_s (indices and
-    distances back to the host + the label comparison).
-    n_neighbors: 1 labels a probe by its nearest gallery row (ops.nn1); more by the uniform vote of that many (ops.knn: 'nn_index' and
-    'nn_dist' become [nq, k]; the search is still timed as nn1_s).
-    pca: "host" fits and applies scikit-learn's PCA on the CPU as above; "device" runs ops.pca_fit on the gallery and
-    ops.pca_transform on both halves without leaving the GPU (deterministic fp64; a fit that does not converge raises RuntimeError)
-    and records the phase in ``timings`` as pca_s.
-    classifier: "knn" is all of the above; "linear_svm" is the 'linear svm' row of :429 (with ``pca_components``: the Pipeline of
-    PCA and LinearSVC()) -- LinearSVC(C=svm_C) fitted on the gallery half at the optimum of its objective (ops.linear_svm_fit; a fit
-    that does not converge raises RuntimeError), the probes labelled by ops.linear_svm_predict.  The result then holds 'decision'
-    ([nq, K'] on the host) and 'svm_iterations' in place of 'nn_index' / 'nn_dist', and ``timings`` receives svm_fit_s and
-    svm_predict_s in place of nn1_s.  ``n_neighbors`` must stay 1.  "rbf_svm" is the 'svm' row, SVC(C=svm_C, gamma=svm_gamma): every pair of
-    classes solved to the optimum of its dual (ops.rbf_svm_fit; a pair that stops at RBF_SVM_MAX_ITER raises RuntimeError), the probes
-    labelled by the pairs' votes (ops.rbf_svm_predict).  ``svm_gamma``: "scale" (from the gallery half, the unpadded columns after a PCA)
-    or a positive finite number.  The result holds 'votes' ([nq, K] on the host) and 'svm_iterations' in place of 'nn_index' /
-    'nn_dist'; ``timings`` as for "linear_svm"."""
-    import time
+    Returns accuracy, the split, predictions and the classifier's extras (nearest-gallery indices and distances).  ``timings``
+    (optional dict) receives the device-synchronised wall seconds of each phase: normalize_s, host_split_s, select_s, pca_s (with
+    pca="device"), the classifier's (nn1_s, and nn1_shape with it), readback_s (indices and distances back to the host + the label
+    comparison)."""
     from . import _lib, ops
-    ops.check_n_neighbors(n_neighbors)
-    check_pca_mode(pca)
-    check_classifier(classifier, n_neighbors, svm_C, svm_gamma)
-    if pca_components and pca == "device":
-        ops.check_pca_components(pca_components)
+    kw = _check_keywords(n_neighbors, pca, pca_components, classifier, svm_C, svm_gamma)
     torch = _lib.require_gpu()
     if isinstance(X, np.ndarray):
         X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(_lib.cuda_device(device))
-
-    def lap(key, t_prev):
-        if timings is None:
-            return 0.0
-        torch.cuda.synchronize(X.device)
-        t = time.perf_counter()
-        timings[key] = t - t_prev
-        return t
-
-    t = lap("_start", 0.0)
+    lap = _phase_clock(torch, X.device, timings)
     Xn = ops.l2_normalize(X.contiguous())                       # :401
-    t = lap("normalize_s", t)
+    lap("normalize_s")
     if isinstance(split, SplitJob):                             # started earlier on the same labels: wait for it
         indices, y_enc, train, test = split.result()
     else:
         indices, y_enc = filter_classes(y)                      # :407-412
         train, test = split if split is not None else stratified_half_split(y_enc)
-    t = lap("host_split_s", t)
-    Xn = Xn[torch.from_numpy(indices).to(Xn.device)].contiguous()   # :413
-    gal = Xn[torch.from_numpy(train).to(Xn.device)].contiguous()
-    qry = Xn[torch.from_numpy(test).to(Xn.device)].contiguous()
-    t = lap("select_s", t)
-    if pca_components and pca == "device":
-        gal, qry = _device_pca(ops, gal, qry, pca_components)
-        t = lap("pca_s", t)
-    elif pca_components:
-        from sklearn.decomposition import PCA
-        fitted = PCA(n_components=pca_components).fit(gal.cpu().numpy())
-        pad = (-pca_components) % 8                      # hsefr_nn1 wants d % 8 == 0: zero columns change no distance
-
-        def proj(t):
-            z = fitted.transform(t.cpu().numpy()).astype(np.float32)
-            return torch.from_numpy(np.pad(z, ((0, 0), (0, pad)))).to(Xn.device).contiguous()
-        gal, qry = proj(gal), proj(qry)
-    if classifier in ("linear_svm", "rbf_svm"):
-        clock = [t]
-
-        def svm_lap(key):
-            clock[0] = lap(key, clock[0])
-        if classifier == "linear_svm":
-            y_pred, table, svm_iterations = _linear_svm_predict(ops, qry, gal, y_enc[train], svm_C, svm_lap)
-        else:
-            y_pred, table, svm_iterations = _rbf_svm_predict(ops, qry, gal, y_enc[train], svm_C, svm_gamma, pca_components or None, svm_lap)
-        t = clock[0]
-        acc = float((y_pred == y_enc[test]).mean()) if len(test) else float("nan")
-        t = lap("readback_s", t)
-        if timings is not None:
-            timings.pop("_start", None)
-        return {"accuracy": acc, "indices": indices, "y": y_enc, "train": train, "test": test, "y_pred": y_pred,
-                "decision" if classifier == "linear_svm" else "votes": table,
-                "svm_iterations": svm_iterations, "num_classes": int(y_enc.max() + 1) if len(y_enc) else 0}
-    if n_neighbors == 1:
-        nn_idx, nn_d2 = ops.nn1(qry, gal)
-        t = lap("nn1_s", t)
-        nn_idx_h = nn_idx.cpu().numpy()
-        nn_dist_h = np.sqrt(nn_d2.cpu().numpy())
-        y_pred = y_enc[train][nn_idx_h]
-    else:
-        y_pred, nn_idx_h, nn_dist_h = _knn_predict(ops, qry, gal, y_enc[train], n_neighbors)
-        t = lap("nn1_s", t)
-    acc = float((y_pred == y_enc[test]).mean()) if len(test) else float("nan")
-    t = lap("readback_s", t)
-    if timings is not None:
-        timings.pop("_start", None)
+    lap("host_split_s")
+    Xn = _rows(torch, Xn, indices)                              # :413
+    gal, qry = _rows(torch, Xn, train), _rows(torch, Xn, test)
+    lap("select_s")
+    gal, qry = _reduce(torch, ops, gal, qry, kw, Xn.device, lap)
+    y_pred, extras = _classify(torch, ops, gal, qry, y_enc[train], kw, lap)
+    acc = _accuracy(y_pred, y_enc[test])
+    lap("readback_s")
+    if timings is not None and "nn_index" in extras:             # the searches' shape, beside the nn1_s that _classify lapped
         timings["nn1_shape"] = (int(qry.shape[0]), int(gal.shape[0]), int(qry.shape[1]))
-    return {"accuracy": acc, "indices": indices, "y": y_enc, "train": train, "test": test, "y_pred": y_pred,
-            "nn_index": nn_idx_h, "nn_dist": nn_dist_h, "num_classes": int(y_enc.max() + 1) if len(y_enc) else 0}
+    return {"accuracy": acc, "indices": indices, "y": y_enc, "train": train, "test": test, "y_pred": y_pred, **extras,
+            "num_classes": int(y_enc.max() + 1) if len(y_enc) else 0}
 
 
 def single_image_per_class_splits(y: np.ndarray, n_splits: int = 10, random_state: int = 0):
@@ -310,23 +321,13 @@ def single_image_per_class_splits(y: np.ndarray, n_splits: int = 10, random_stat
     return res_cv
 
 
-def _nn1_predict(torch, ops, Xd, train, test, y, n_neighbors: int = 1):
-    gal = Xd[torch.from_numpy(np.asarray(train, dtype=np.int64)).to(Xd.device)].contiguous()
-    qry = Xd[torch.from_numpy(np.asarray(test, dtype=np.int64)).to(Xd.device)].contiguous()
-    if n_neighbors != 1:
-        return _knn_predict(ops, qry, gal, y[np.asarray(train)], n_neighbors)
-    nn_idx, nn_d2 = ops.nn1(qry, gal)
-    nn_idx_h = nn_idx.cpu().numpy()
-    return y[np.asarray(train)][nn_idx_h], nn_idx_h, np.sqrt(nn_d2.cpu().numpy())
-
-
 def cross_validated_1nn(X, y: np.ndarray, cv, normalize: bool = True, device=None, n_neighbors: int = 1) -> Dict:
     """classifier_tester (facerec_test.py:199-207) for KNeighborsClassifier(n_neighbors=1, p=2) over an explicit list of
     (train, test) index pairs -- e.g. single_image_per_class_splits(y) in place of the stratified half split (:200-201) --
     with every search on the GPU.  Returns the per-split accuracies and their mean / std as the reference prints them.
     ``n_neighbors`` > 1 scores KNeighborsClassifier(n_neighbors) instead (ops.knn's uniform vote)."""
     from . import _lib, ops
-    ops.check_n_neighbors(n_neighbors)
+    kw = _check_keywords(n_neighbors)
     torch = _lib.require_gpu()
     if isinstance(X, np.ndarray):
         X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(_lib.cuda_device(device))
@@ -334,9 +335,10 @@ def cross_validated_1nn(X, y: np.ndarray, cv, normalize: bool = True, device=Non
     y = np.asarray(y)
     accs, preds = [], []
     for train, test in cv:
-        y_pred, _, _ = _nn1_predict(torch, ops, Xd, train, test, y, n_neighbors)
+        train, test = np.asarray(train, dtype=np.int64), np.asarray(test, dtype=np.int64)     # an empty fold is no float index
+        y_pred, _ = _classify(torch, ops, _rows(torch, Xd, train), _rows(torch, Xd, test), y[train], kw)
         preds.append(y_pred)
-        accs.append(float((y_pred == y[np.asarray(test)]).mean()) if len(test) else float("nan"))
+        accs.append(_accuracy(y_pred, y[test]))
     accs = np.asarray(accs)
     return {"accuracies": accs, "mean": float(accs.mean()) if len(accs) else float("nan"),
             "std": float(accs.std()) if len(accs) else float("nan"), "y_pred": preds}
@@ -349,28 +351,10 @@ def gallery_probe_identification(X_train, y_train: np.ndarray, X_test, y_test: n
     '1-NN+PCA' with ``pca_components``, 16 at :269) FITTED on the gallery features, every probe labelled by its nearest
     gallery row; accuracy = share of probes whose label is right (:287).  NB the reference computes L2-normalised copies
     (:262,265) and then fits / predicts on the UN-normalised ``X_train`` / ``X_test`` (:284-285): ``normalize=False`` is what
-    it runs, ``normalize=True`` what the copies suggest it meant.  The search runs on the GPU (hsefr_nn1: ties -> the lowest
-    gallery index, scikit-learn's own choice).  ``n_neighbors`` > 1 gives the '3-NN' / '3-NN+PCA' rows of :269-272 (hsefr_knn: the
-    uniform vote, equal counts to the smallest label as in scikit-learn's predict; 'nn_index' and 'nn_dist' become [nq, k]).
-    ``pca``: "host" is scikit-learn's PCA on the CPU; "device" fits on the gallery and projects both sets with ops.pca_fit /
-    ops.pca_transform on the GPU (deterministic fp64; a fit that does not converge raises RuntimeError).
-    ``classifier``: "knn" is all of the above; "linear_svm" gives the 'linear svm' / 'linear svm+PCA' rows of :269-273 -- LinearSVC(C=svm_C)
-    fitted on the gallery (after the projection, when ``pca_components`` is set) at the optimum of its objective (ops.linear_svm_fit; a fit
-    that does not converge raises RuntimeError), the probes labelled by ops.linear_svm_predict: the result holds 'accuracy', 'y_pred',
-    'decision' ([nq, K'] on the host) and 'svm_iterations'.  scikit-learn's default tolerance stops short of the optimum, so its labels
-    can differ on probes whose two largest decision values are closer than about 1e-4 (1e-3 after PCA).  ``n_neighbors`` must stay 1.
-    "rbf_svm" gives the 'svm' row of :269-273, SVC(C=svm_C, gamma=svm_gamma): libsvm's one-vs-one C-SVC with the RBF kernel, every pair of
-    classes solved to the optimum of its dual (ops.rbf_svm_fit; a pair that stops at RBF_SVM_MAX_ITER raises RuntimeError), the probes
-    labelled by the pairs' votes (ops.rbf_svm_predict): the result holds 'accuracy', 'y_pred', 'votes' ([nq, K] on the host) and
-    'svm_iterations'.  ``svm_gamma``: "scale" (1 / (d Var) of the gallery rows, over the unpadded columns after a PCA) or a positive finite
-    number.  scikit-learn's default tolerance stops about 3e-4 short of the optimum in a pair's decision value, so a vote whose value
-    is that close to 0 can differ."""
+    it runs, ``normalize=True`` what the copies suggest it meant.  n_neighbors, pca, classifier, svm_C and svm_gamma give the other
+    rows of :269-273: see the module docstring.  Returns 'accuracy', 'y_pred' and the classifier's extras."""
     from . import _lib, ops
-    ops.check_n_neighbors(n_neighbors, len(np.asarray(y_train)))
-    check_pca_mode(pca)
-    check_classifier(classifier, n_neighbors, svm_C, svm_gamma)
-    if pca_components and pca == "device":
-        ops.check_pca_components(pca_components, len(np.asarray(y_train)))
+    kw = _check_keywords(n_neighbors, pca, pca_components, classifier, svm_C, svm_gamma, n_gallery=len(np.asarray(y_train)))
     torch = _lib.require_gpu()
     dev = _lib.cuda_device(device)
 
@@ -382,33 +366,9 @@ def gallery_probe_identification(X_train, y_train: np.ndarray, X_test, y_test: n
     if gal.shape[0] != len(y_train) or qry.shape[0] != len(y_test):
         raise ValueError("features and labels differ in length: %d/%d gallery, %d/%d probe"
                          % (gal.shape[0], len(y_train), qry.shape[0], len(y_test)))
-    if pca_components and pca == "device":
-        gal, qry = _device_pca(ops, gal, qry, pca_components)
-    elif pca_components:
-        from sklearn.decomposition import PCA
-        fitted = PCA(n_components=pca_components).fit(gal.cpu().numpy())
-        pad = (-pca_components) % 8
-
-        def proj(t):
-            z = fitted.transform(t.cpu().numpy()).astype(np.float32)
-            return torch.from_numpy(np.pad(z, ((0, 0), (0, pad)))).to(dev).contiguous()
-        gal, qry = proj(gal), proj(qry)
-    if classifier == "linear_svm":
-        y_pred, decision, svm_iterations = _linear_svm_predict(ops, qry, gal, y_train, svm_C)
-        acc = float((y_pred == y_test).mean()) if len(y_test) else float("nan")
-        return {"accuracy": acc, "y_pred": y_pred, "decision": decision, "svm_iterations": svm_iterations}
-    if classifier == "rbf_svm":
-        y_pred, votes, svm_iterations = _rbf_svm_predict(ops, qry, gal, y_train, svm_C, svm_gamma, pca_components or None)
-        acc = float((y_pred == y_test).mean()) if len(y_test) else float("nan")
-        return {"accuracy": acc, "y_pred": y_pred, "votes": votes, "svm_iterations": svm_iterations}
-    if n_neighbors == 1:
-        nn_idx, nn_d2 = ops.nn1(qry, gal)
-        nn_idx_h = nn_idx.cpu().numpy()
-        y_pred, nn_dist_h = y_train[nn_idx_h], np.sqrt(nn_d2.cpu().numpy())
-    else:
-        y_pred, nn_idx_h, nn_dist_h = _knn_predict(ops, qry, gal, y_train, n_neighbors)
-    acc = float((y_pred == y_test).mean()) if len(y_test) else float("nan")
-    return {"accuracy": acc, "y_pred": y_pred, "nn_index": nn_idx_h, "nn_dist": nn_dist_h}
+    gal, qry = _reduce(torch, ops, gal, qry, kw, dev)
+    y_pred, extras = _classify(torch, ops, gal, qry, y_train, kw)
+    return {"accuracy": _accuracy(y_pred, y_test), "y_pred": y_pred, **extras}
 
 
 def feature_distance_matrix(features, born_years=None, photo_years=None, device=None) -> np.ndarray:

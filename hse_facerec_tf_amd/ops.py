@@ -449,18 +449,48 @@ def nn1(queries, gallery):
     return idx, dist
 
 
+def _int_arg(name, v, least, greatest=None, says=None) -> int:
+    """``v`` as an int: a real integer (no bool) in least..greatest.  ``says``: the one message (a %r for ``v``) of a site that has one."""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise ValueError(says % (v,) if says else "%s must be an integer, got %r" % (name, v))
+    if v < least or (greatest is not None and v > greatest):
+        raise ValueError(says % (v,) if says else "%s=%d must be %s" % (name, v, "at least %d" % least if greatest is None
+                                                                            else "in %d..%d" % (least, greatest)))
+    return int(v)
+
+
+def _number_arg(name, v, finite=None, also=""):
+    """``v``: a number (no bool); with ``finite`` given it is positive too, and below infinity where ``finite`` is True."""
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise ValueError("%s must be a number%s, got %r" % (name, also, v))
+    if finite is not None and not (v > 0 and (np.isfinite(v) or not finite)):
+        raise ValueError("%s=%r must be positive%s" % (name, v, " and finite" if finite else ""))
+
+
+def _labels_arg(torch, labels, n, like, where="x's device"):
+    """``labels``: a contiguous int32 tensor of ``n`` values on the device of ``like`` (``where`` in the site's words)."""
+    if labels.dtype != torch.int32 or not labels.is_contiguous() or tuple(labels.shape) != (n,) or labels.device != like.device:
+        raise ValueError("labels must be a contiguous int32 tensor of %d values on %s" % (n, where))
+
+
+def _typed(t, dtype, name, what, shape=None, like=None):
+    """``t``: a contiguous CUDA tensor of ``dtype`` (``what`` in words) -- of ``shape`` and on the device of ``like`` (x), where given."""
+    if not (hasattr(t, "is_cuda") and t.is_cuda and t.dtype == dtype and t.is_contiguous()
+            and (shape is None or tuple(t.shape) == shape) and (like is None or t.device == like.device)):
+        raise ValueError("%s must be a contiguous %s CUDA tensor%s%s" % (name, what, "" if shape is None else " of shape %s" % (shape,),
+                                                                         "" if like is None else " on x's device"))
+    return t
+
+
 KNN_MAX_K = 16     # hsefr_knn's largest k (the selection kernel's per-lane list)
 
 
 def check_n_neighbors(k, ng=None) -> int:
     """hsefr_knn's range of k, raised as ValueError before the library is called (scikit-learn raises for k > n_samples_fit too)."""
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
-        raise ValueError("n_neighbors must be an integer, got %r" % (k,))
-    if k < 1 or k > KNN_MAX_K:
-        raise ValueError("n_neighbors=%d must be in 1..%d" % (k, KNN_MAX_K))
+    k = _int_arg("n_neighbors", k, 1, KNN_MAX_K)
     if ng is not None and k > ng:
         raise ValueError("n_neighbors=%d exceeds the %d gallery rows" % (k, ng))
-    return int(k)
+    return k
 
 
 @_device_guarded
@@ -477,8 +507,7 @@ def knn(queries, gallery, k: int, labels=None):
         raise ValueError("queries are %d-D, gallery is %d-D" % (d, gallery.shape[1]))
     pred = None
     if labels is not None:
-        if labels.dtype != torch.int32 or not labels.is_contiguous() or tuple(labels.shape) != (ng,) or labels.device != gallery.device:
-            raise ValueError("labels must be a contiguous int32 tensor of %d values on the gallery's device" % ng)
+        _labels_arg(torch, labels, ng, gallery, "the gallery's device")
         pred = torch.empty((nq,), dtype=torch.int32, device=queries.device)
     idx = torch.empty((nq, k), dtype=torch.int32, device=queries.device)
     dist = torch.empty((nq, k), dtype=torch.float32, device=queries.device)
@@ -494,15 +523,12 @@ PCA_MAX_K = 256    # hsefr_pca_fit's largest component count (the largest the re
 def check_pca_components(k, n=None, d=None) -> int:
     """hsefr_pca_fit's range of k, raised as ValueError before the library is called: 1 <= k <= min(n - 1, d, 256) (with k = min(n, d)
     scikit-learn's last component has zero variance and an arbitrary direction)."""
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
-        raise ValueError("pca_components must be an integer, got %r" % (k,))
-    if k < 1 or k > PCA_MAX_K:
-        raise ValueError("pca_components=%d must be in 1..%d" % (k, PCA_MAX_K))
+    k = _int_arg("pca_components", k, 1, PCA_MAX_K)
     if n is not None and k > n - 1:
         raise ValueError("pca_components=%d exceeds n - 1 for the %d rows to fit on" % (k, n))
     if d is not None and k > d:
         raise ValueError("pca_components=%d exceeds the %d features" % (k, d))
-    return int(k)
+    return k
 
 
 @_device_guarded
@@ -512,8 +538,7 @@ def pca_fit(x, k: int, max_iter: int = 1000):
     each component is scikit-learn 1.7's (its entry of largest magnitude is positive).  A fit that stops at ``max_iter`` is returned
     with converged False: the caller decides."""
     k = check_pca_components(k, x.shape[0], x.shape[1])      # before anything touches a device
-    if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or max_iter < 1:
-        raise ValueError("max_iter must be a positive integer, got %r" % (max_iter,))
+    max_iter = _int_arg("max_iter", max_iter, 1, says="max_iter must be a positive integer, got %r")
     torch = _lib.require_gpu()
     _f32c(x, "x")
     n, d = x.shape
@@ -534,9 +559,8 @@ def pca_transform(x, mean, components):
     torch = _lib.require_gpu()
     _f32c(x, "x")
     n, d = x.shape
-    for t, name, shape in ((mean, "mean", (d,)), (components, "components", (components.shape[0], d))):
-        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape):
-            raise ValueError("%s must be a contiguous float64 CUDA tensor of shape %s" % (name, shape))
+    _typed(mean, torch.float64, "mean", "float64", (d,))
+    _typed(components, torch.float64, "components", "float64", (components.shape[0], d))
     k = check_pca_components(int(components.shape[0]), None, d)
     ld = (k + 7) // 8 * 8
     z = torch.empty((n, ld), dtype=torch.float32, device=x.device)
@@ -552,20 +576,12 @@ LINEAR_SVM_MAX_N, LINEAR_SVM_MAX_D, LINEAR_SVM_MAX_CLASSES, LINEAR_SVM_MAX_ELEMS
 def check_linear_svm_args(n, d, n_classes, C=1.0, tol=1e-10, max_iter=1000) -> None:
     """hsefr_linear_svm_fit's argument ranges, raised as ValueError before the library or a device is touched."""
     for name, v, least in (("n", n, 1), ("d", d, 1), ("n_classes", n_classes, 2), ("max_iter", max_iter, 1)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise ValueError("%s must be an integer, got %r" % (name, v))
-        if v < least:
-            raise ValueError("%s=%d must be at least %d" % (name, v, least))
+        _int_arg(name, v, least)
     if n > LINEAR_SVM_MAX_N or d > LINEAR_SVM_MAX_D or n_classes > LINEAR_SVM_MAX_CLASSES or n * (d + 1) > LINEAR_SVM_MAX_ELEMS:
         raise ValueError("n=%d d=%d n_classes=%d over the limits n <= %d, d <= %d, n_classes <= %d, n (d + 1) <= %d"
                          % (n, d, n_classes, LINEAR_SVM_MAX_N, LINEAR_SVM_MAX_D, LINEAR_SVM_MAX_CLASSES, LINEAR_SVM_MAX_ELEMS))
-    for name, v in (("C", C), ("tol", tol)):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
-            raise ValueError("%s must be a number, got %r" % (name, v))
-    if not (C > 0 and np.isfinite(C)):
-        raise ValueError("C=%r must be positive and finite" % (C,))
-    if not tol > 0:
-        raise ValueError("tol=%r must be positive" % (tol,))
+    _number_arg("C", C), _number_arg("tol", tol)                # both types before either range
+    _number_arg("C", C, finite=True), _number_arg("tol", tol, finite=False)
 
 
 @_device_guarded
@@ -581,8 +597,7 @@ def linear_svm_fit(x, labels, n_classes: int, C: float = 1.0, tol: float = 1e-10
     torch = _lib.require_gpu()
     _f32c(x, "x")
     n, d = x.shape
-    if labels.dtype != torch.int32 or not labels.is_contiguous() or tuple(labels.shape) != (n,) or labels.device != x.device:
-        raise ValueError("labels must be a contiguous int32 tensor of %d values on x's device" % n)
+    _labels_arg(torch, labels, n, x)
     rows = 1 if n_classes == 2 else int(n_classes)
     coef = torch.empty((rows, d), dtype=torch.float64, device=x.device)
     intercept = torch.empty((rows,), dtype=torch.float64, device=x.device)
@@ -601,9 +616,8 @@ def linear_svm_decision(x, coef, intercept):
     _f32c(x, "x")
     n, d = x.shape
     rows = int(coef.shape[0]) if getattr(coef, "ndim", 0) == 2 else 0
-    for t, name, shape in ((coef, "coef", (rows, d)), (intercept, "intercept", (rows,))):
-        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape and t.device == x.device):
-            raise ValueError("%s must be a contiguous float64 CUDA tensor of shape %s on x's device" % (name, shape))
+    _typed(coef, torch.float64, "coef", "float64", (rows, d), x)
+    _typed(intercept, torch.float64, "intercept", "float64", (rows,), x)
     out = torch.empty((n, rows), dtype=torch.float64, device=x.device)
     _lib.check(_lib.lib().hsefr_linear_svm_decision(x.data_ptr(), n, d, coef.data_ptr(), intercept.data_ptr(), rows, out.data_ptr(),
                                                     _lib.current_stream_ptr()), "hsefr_linear_svm_decision")
@@ -632,18 +646,13 @@ def check_rbf_svm_args(n, d, n_classes, C=1.0, gamma="scale", tol=1e-10, max_ite
     """hsefr_rbf_svm_fit's argument ranges, raised as ValueError before the library or a device is touched.  ``gamma`` is "scale" or a
     positive finite number."""
     for name, v, least in (("n", n, 2), ("d", d, 1), ("n_classes", n_classes, 2), ("max_iter", max_iter, 1)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise ValueError("%s must be an integer, got %r" % (name, v))
-        if v < least:
-            raise ValueError("%s=%d must be at least %d" % (name, v, least))
+        _int_arg(name, v, least)
     if n > RBF_SVM_MAX_N or d > RBF_SVM_MAX_D or n_classes > RBF_SVM_MAX_CLASSES or n_classes > n:
         raise ValueError("n=%d d=%d n_classes=%d over the limits n <= %d, d <= %d, n_classes <= min(n, %d)"
                          % (n, d, n_classes, RBF_SVM_MAX_N, RBF_SVM_MAX_D, RBF_SVM_MAX_CLASSES))
-    for name, v in (("C", C), ("tol", tol)) + ((("gamma", gamma),) if not (isinstance(gamma, str) and gamma == "scale") else ()):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
-            raise ValueError("%s must be a number%s, got %r" % (name, " or 'scale'" if name == "gamma" else "", v))
-        if not (v > 0 and np.isfinite(v)):
-            raise ValueError("%s=%r must be positive and finite" % (name, v))
+    _number_arg("C", C, finite=True), _number_arg("tol", tol, finite=True)
+    if not (isinstance(gamma, str) and gamma == "scale"):
+        _number_arg("gamma", gamma, finite=True, also=" or 'scale'")
 
 
 def _rbf_svm_model(torch, x, labels, n_classes, gamma, dual_coef, rho):
@@ -655,11 +664,9 @@ def _rbf_svm_model(torch, x, labels, n_classes, gamma, dual_coef, rho):
         raise ValueError("gamma must be the number the model was fitted with (ops.rbf_svm_gamma)")
     _f32c(x, "x")
     n, K = int(x.shape[0]), int(n_classes)
-    if labels.dtype != torch.int32 or not labels.is_contiguous() or tuple(labels.shape) != (n,) or labels.device != x.device:
-        raise ValueError("labels must be a contiguous int32 tensor of %d values on x's device" % n)
-    for t, name, shape in ((dual_coef, "dual_coef", (K - 1, n)), (rho, "rho", (K * (K - 1) // 2,))):
-        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape and t.device == x.device):
-            raise ValueError("%s must be a contiguous float64 CUDA tensor of shape %s on x's device" % (name, shape))
+    _labels_arg(torch, labels, n, x)
+    _typed(dual_coef, torch.float64, "dual_coef", "float64", (K - 1, n), x)
+    _typed(rho, torch.float64, "rho", "float64", (K * (K - 1) // 2,), x)
 
 
 def _rbf_svm_probes(q, x, limit_pairs=None):
@@ -682,9 +689,7 @@ def rbf_svm_gamma(x, d_used=None) -> float:
     if getattr(x, "ndim", 0) != 2:
         raise ValueError("x must be [n, d]")
     n, d = int(x.shape[0]), int(x.shape[1])
-    d_used = d if d_used is None else d_used
-    if isinstance(d_used, bool) or not isinstance(d_used, (int, np.integer)) or not 1 <= d_used <= d:
-        raise ValueError("d_used=%r must be an integer in 1..%d" % (d_used, d))
+    d_used = _int_arg("d_used", d if d_used is None else d_used, 1, d, says="d_used=%%r must be an integer in 1..%d" % d)
     if n < 1 or n > RBF_SVM_MAX_PROBES or d > RBF_SVM_MAX_D:
         raise ValueError("n=%d d=%d outside 1 <= n <= %d, d <= %d" % (n, d, RBF_SVM_MAX_PROBES, RBF_SVM_MAX_D))
     torch = _lib.require_gpu()
@@ -712,8 +717,7 @@ def rbf_svm_fit(x, labels, n_classes: int, gamma, C: float = 1.0, tol: float = 1
     _f32c(x, "x")
     n, d = x.shape
     K = int(n_classes)
-    if labels.dtype != torch.int32 or not labels.is_contiguous() or tuple(labels.shape) != (n,) or labels.device != x.device:
-        raise ValueError("labels must be a contiguous int32 tensor of %d values on x's device" % n)
+    _labels_arg(torch, labels, n, x)
     dual_coef = torch.empty((K - 1, n), dtype=torch.float64, device=x.device)
     rho = torch.empty((K * (K - 1) // 2,), dtype=torch.float64, device=x.device)
     info = torch.zeros((3,), dtype=torch.int32, device=x.device)
@@ -956,12 +960,6 @@ def rank_order_labels(x=None, dense=None, born=None, year=None, norm_threshold=0
 
 
 SCORES_MAX_N = 65536       # HSEFR_SCORES_MAX_N
-
-
-def _typed(t, dtype, name, what):
-    if not (hasattr(t, "is_cuda") and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
-        raise ValueError("%s must be a contiguous %s CUDA tensor" % (name, what))
-    return t
 
 
 @_device_guarded
