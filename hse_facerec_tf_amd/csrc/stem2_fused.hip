@@ -25,56 +25,21 @@
 // patch share 39 KB -> 2 workgroups per CU.
 #include <type_traits>
 
-#include "common.h"
+#include "stem_patch.h"     // the patch geometry, the patch cursor and the launchers' common part
 
 namespace hsefr {
 
+using namespace stem;
+using namespace stem::patch;
+
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-struct __attribute__((packed, aligned(4))) F3 { float a, b, c; };
-
-struct Stem2Params {
+struct Stem2Params : PatchParams {
     const float* x;        // [N,H,W,3]
     const float* cw;       // conv1 kernel, TF HWIO [3,3,3,32]
     const float* cshift;   // [32]
-    const float4* wd1;     // depthwise 1 [9][8] float4
-    const float4* d1scale; // [8]
-    const float4* d1shift; // [8]
-    const float* wsplit;   // pointwise split rows [64][1][64 f16]
-    const float* descale;  // [64]
-    const float* pshift;   // [64]
-    const float4* wd2;     // depthwise 2 [9][16] float4
-    const float4* d2scale; // [16]
-    const float4* d2shift; // [16]
-    float* y;              // [N,OH2,OW2,64]
-    int H, W, H1, W1, OH2, OW2, cpad_t, cpad_l, pad_t2, pad_l2, tiles_w, tiles_h;
-    unsigned total;
-    float a_scale;
-    int reverse;
-    unsigned long long* stamps;   // diagnostic builds (-DHSEFR_STEM_STAMPS) only
+    int cpad_t, cpad_l, pad_t2, pad_l2;
 };
-
-constexpr int PH = 4, PW = 8;                         // output patch (of the stride-2 depthwise)
-constexpr int R1H = 2 * PH + 1, R1W = 2 * PW + 1;     // block-1 region 9 x 17
-constexpr int R1PIX = R1H * R1W;                      // 153
-constexpr int R1ROWS = 160;                           // 10 MFMA row blocks of 16
-constexpr int R0H = R1H + 2, R0W = R1W + 2;           // conv1 region 11 x 19
-constexpr int R0PIX = R0H * R0W;                      // 209
-constexpr int R0ROWS = 224;                           // 14 MFMA row blocks of 16
-constexpr int COP = 36;                               // floats per pixel row of the conv1 region in LDS (32 + 4): taps sit at
-                                                      // compile-time offsets from one base (no per-tap swizzle arithmetic)
-constexpr int P1P = 68;                               // floats per pixel row of the 96x96x64 patch in LDS (64 + 4: rows 4 banks apart)
-
-__device__ __forceinline__ int swz32(int row, int chunk) { return row * 32 + 4 * (chunk ^ ((row >> 1) & 7) ^ ((row & 1) << 2)); }       // floats
-__device__ __forceinline__ int swzb(int row, int chunk) { return row * 128 + 16 * (chunk ^ ((row >> 1) & 7) ^ ((row & 1) << 2)); }      // bytes; b64 writes of adjacent rows land in different halves of the 128-B bank window
-__device__ __forceinline__ float relu6(float v) { return fminf(fmaxf(v, 0.f), 6.f); }
-// 4-wide fused multiply-add on vector types: lowers to two v_pk_fma_f32 (same rounding as fmaf, half the instructions);
-// used where no MFMA shares the issue slots (the depthwise stages).
-__device__ __forceinline__ f32x4 vfma(f32x4 a, f32x4 b, f32x4 c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ f32x4 as_v(float4 a) { return (f32x4){a.x, a.y, a.z, a.w}; }
 
 template <int ACT>
 __global__ __launch_bounds__(256, 2) void stem2_fused_kernel(Stem2Params p) {
@@ -86,7 +51,6 @@ __global__ __launch_bounds__(256, 2) void stem2_fused_kernel(Stem2Params p) {
     __shared__ __attribute__((aligned(16))) float4 W2[9 * 16];              // depthwise-2 weights
     __shared__ float Cv[R0ROWS];                                            // 1 = conv1 pixel inside its map
     __shared__ float Pv[R1ROWS];                                            // 1 = block-1 pixel inside its map
-    static_assert(R0ROWS * COP <= R1PIX * P1P, "conv1 region fits in U2");
     float* Ic = U1;
     unsigned char* As = (unsigned char*)U1;
     float* Co = U2;
@@ -117,30 +81,7 @@ __global__ __launch_bounds__(256, 2) void stem2_fused_kernel(Stem2Params p) {
     for (int nb = 0; nb < 2; ++nb) csh[nb] = *(const f32x4*)(p.cshift + nb * 16 + 4 * q4);
     const f32x4 pds = *(const f32x4*)(p.descale + wave * 16 + 4 * q4), psh = *(const f32x4*)(p.pshift + wave * 16 + 4 * q4);
 
-    // ---- patch cursor (advanced with carries: no divisions in the loop) ----
-    struct Cur { int n, th, tw; };
-    auto decode = [&](unsigned t) {
-        const unsigned lt = xcd_remap_dir(t, p.total, p.reverse);
-        Cur c;
-        c.tw = lt % p.tiles_w;
-        c.th = (lt / p.tiles_w) % p.tiles_h;
-        c.n = lt / (p.tiles_w * p.tiles_h);
-        return c;
-    };
-    const int stride_lt = gridDim.x / 8;             // launch guarantees gridDim.x % 8 == 0 whenever the kernel loops
-    const int dtw_ = stride_lt % p.tiles_w, dth_ = (stride_lt / p.tiles_w) % p.tiles_h, dn_ = stride_lt / (p.tiles_w * p.tiles_h);
-    auto advance = [&](Cur c) {
-        if (!p.reverse) {
-            c.tw += dtw_; if (c.tw >= p.tiles_w) { c.tw -= p.tiles_w; c.th += 1; }
-            c.th += dth_; if (c.th >= p.tiles_h) { c.th -= p.tiles_h; c.n += 1; }
-            c.n += dn_;
-        } else {
-            c.tw -= dtw_; if (c.tw < 0) { c.tw += p.tiles_w; c.th -= 1; }
-            c.th -= dth_; if (c.th < 0) { c.th += p.tiles_h; c.n -= 1; }
-            c.n -= dn_;
-        }
-        return c;
-    };
+    const Cur step = cursor_step(p);
 
     // ---- stage A: gather one conv1 pixel's 3x3x3 window, scatter it as an im2col row ----
     F3 g[9];
@@ -197,7 +138,7 @@ __global__ __launch_bounds__(256, 2) void stem2_fused_kernel(Stem2Params p) {
 
     unsigned t = blockIdx.x;
     if (t >= p.total) return;
-    Cur cur = decode(t);
+    Cur cur = decode(p, t);
     gather(cur);
     scatter();
     __syncthreads();
@@ -206,7 +147,7 @@ __global__ __launch_bounds__(256, 2) void stem2_fused_kernel(Stem2Params p) {
     while (true) {
         const unsigned tn = t + gridDim.x;
         const bool more = tn < p.total;
-        const Cur nxt = advance(cur);
+        const Cur nxt = advance(p, cur, step);
         STEM_STAMP(0);
 
         // ---- stage B: conv1 on the fp32 MFMA; 14 row blocks x 2 channel blocks = 28 pairs, 7 per wave ----
@@ -352,30 +293,15 @@ int launch_stem2_fused(const float* x, const float* cw, const float* cshift, con
     HSEFR_REQUIRE(h1 == (h + 1) / 2 && w1 == (w + 1) / 2 && oh2 == (h1 + 1) / 2 && ow2 == (w1 + 1) / 2, HSEFR_ERR_INVALID,
                   "stem2_fused: %dx%d -> %dx%d -> %dx%d is not two SAME stride-2 steps", h, w, h1, w1, oh2, ow2);
     HSEFR_REQUIRE(pad_t2 >= 0 && pad_t2 <= 1 && pad_l2 >= 0 && pad_l2 <= 1, HSEFR_ERR_INVALID, "stem2_fused: depthwise-2 padding %d,%d", pad_t2, pad_l2);
-    HSEFR_REQUIRE(a_log2 > 0 && a_log2 <= 12, HSEFR_ERR_INVALID, "stem2_fused: a_log2=%d", a_log2);
+    HSEFR_REQUIRE(a_log2_ok(a_log2), HSEFR_ERR_INVALID, "stem2_fused: a_log2=%d", a_log2);
     if (n == 0) return HSEFR_OK;
     Stem2Params p;
-    p.x = x; p.cw = cw; p.cshift = cshift; p.wd1 = (const float4*)wd1; p.d1scale = (const float4*)d1scale;
-    p.d1shift = (const float4*)d1shift; p.wsplit = (const float*)wsplit; p.descale = descale; p.pshift = pshift;
-    p.wd2 = (const float4*)wd2; p.d2scale = (const float4*)d2scale; p.d2shift = (const float4*)d2shift; p.y = y;
-    p.H = h; p.W = w; p.H1 = h1; p.W1 = w1; p.OH2 = oh2; p.OW2 = ow2; p.cpad_t = cpad_t; p.cpad_l = cpad_l;
-    p.pad_t2 = pad_t2; p.pad_l2 = pad_l2;
-    p.tiles_w = (ow2 + PW - 1) / PW; p.tiles_h = (oh2 + PH - 1) / PH;
-    const long long total = (long long)n * p.tiles_w * p.tiles_h;
-    HSEFR_REQUIRE(total < (1ll << 31), HSEFR_ERR_UNSUPPORTED, "stem2_fused: grid too large");
-    p.total = (unsigned)total;
-    p.a_scale = ldexpf(1.f, a_log2);
-    p.reverse = sweep_reverse();
-    p.stamps = nullptr;
-#ifdef HSEFR_STEM_STAMPS
-    p.stamps = stamp_buffer(s);
-#endif
+    p.x = x; p.cw = cw; p.cshift = cshift; p.cpad_t = cpad_t; p.cpad_l = cpad_l; p.pad_t2 = pad_t2; p.pad_l2 = pad_l2;
+    if (const int rc = fill_params(p, "stem2_fused", wd1, d1scale, d1shift, wsplit, descale, pshift, wd2, d2scale, d2shift, y, n, h, w, h1, w1,
+                                   oh2, ow2, a_log2, s)) return rc;
     const unsigned g = p.total < 512u ? p.total : 512u;      // 512 % 8 == 0: the kernel's incremental patch cursor relies on it
 #define HSEFR_STEM2(A) HSEFR_LAUNCH((stem2_fused_kernel<A>), dim3(g), dim3(256), 0, s, p)
-    if (act == HSEFR_ACT_RELU6) HSEFR_STEM2(HSEFR_ACT_RELU6);
-    else if (act == HSEFR_ACT_RELU) HSEFR_STEM2(HSEFR_ACT_RELU);
-    else if (act == HSEFR_ACT_NONE) HSEFR_STEM2(HSEFR_ACT_NONE);
-    else { set_error("stem2_fused: act %d", act); return HSEFR_ERR_UNSUPPORTED; }
+    HSEFR_STEM_ACT_DISPATCH("stem2_fused", act, HSEFR_STEM2);
 #undef HSEFR_STEM2
     return launch_status("stem2_fused");
 }

@@ -23,60 +23,32 @@
 //   * pointwise and depthwise 2: loops of dependent MFMA / FMA chains at `unroll 2`.  -> fully unrolled, independent
 //     accumulators, all LDS reads of a stage in flight together.
 // Results: conv1's products carry the same 3 * 2^-22 bound as the pointwise layers' (the test bar stays 2e-6 per layer,
-// 1e-4 end to end); everything behind conv1 keeps the operation order of stem2_fused.hip.
+// 1e-4 end to end); the patch cursor and stages C-E (the depthwise chains of stem2_fused.hip) are stem_patch.h's.
 #include <type_traits>
 
-#include "common.h"
+#include "stem_patch.h"
 
 namespace hsefr {
 
+using namespace stem;
+using namespace stem::patch;
+
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-struct Stem3Params {
+struct Stem3Params : PatchParams {
     const float* x;        // [N,H,W,3]
     const void* cw_split;  // conv1 split rows [32][hi 32 x f16 | lo 32 x f16], k = dy*9 + dx*3 + ci, k >= 27 zero
     const float* cdescale; // [32]  2^-(e_n + in_log2)
     const float* cshift;   // [32]
-    const float4* wd1;     // depthwise 1 [9][8] float4
-    const float4* d1scale; // [8]
-    const float4* d1shift; // [8]
-    const float* wsplit;   // pointwise split rows [64][1][64 f16]
-    const float* descale;  // [64]
-    const float* pshift;   // [64]
-    const float4* wd2;     // depthwise 2 [9][16] float4
-    const float4* d2scale; // [16]
-    const float4* d2shift; // [16]
-    float* y;              // [N,OH2,OW2,64]
     int* overflow;         // set to 1 if an input value breaks the declared bound (may be null)
-    int H, W, H1, W1, OH2, OW2, cpad_t, cpad_l, pad_t2, pad_l2, tiles_w, tiles_h;
-    unsigned total;
-    float a_scale, in_scale, in_bound;
-    int reverse;
+    int cpad_t, cpad_l, pad_t2, pad_l2;
+    float in_scale, in_bound;
     long long x_bytes, x_floats;   // size of the whole input tensor
-    unsigned long long* stamps;    // diagnostic builds (-DHSEFR_STEM_STAMPS) only
 };
 
-constexpr int PH = 4, PW = 8;                         // output patch (of the stride-2 depthwise)
-constexpr int R1H = 2 * PH + 1, R1W = 2 * PW + 1;     // block-1 region 9 x 17
-constexpr int R1PIX = R1H * R1W;                      // 153
-constexpr int R1ROWS = 160;                           // 10 MFMA row blocks of 16
-constexpr int R0H = R1H + 2, R0W = R1W + 2;           // conv1 region 11 x 19
-constexpr int R0PIX = R0H * R0W;                      // 209
-constexpr int R0ROWS = 224;                           // 14 MFMA row blocks of 16
 constexpr int RAWH = 2 * R0H + 1;                     // input window: 23 rows x 39 pixels
 constexpr int RAWQ = 30;                              // 16-byte pieces per window row (39 * 3 = 117 floats -> 120)
 constexpr int RAWP = RAWQ * 4;                        // floats per window row in LDS
-constexpr int COP = 36;                               // floats per pixel of the conv1 region in LDS (32 + 4)
-constexpr int P1P = 68;                               // floats per pixel of the 96x96x64 patch in LDS (64 + 4)
-
-__device__ __forceinline__ int swzb(int row, int chunk) { return row * 128 + 16 * (chunk ^ ((row >> 1) & 7) ^ ((row & 1) << 2)); }
-__device__ __forceinline__ float relu6(float v) { return fminf(fmaxf(v, 0.f), 6.f); }
-__device__ __forceinline__ f32x4 vfma(f32x4 a, f32x4 b, f32x4 c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ f32x4 as_v(float4 a) { return (f32x4){a.x, a.y, a.z, a.w}; }
 
 template <int ACT>
 __global__ __launch_bounds__(256, 2) void stem3_fused_kernel(Stem3Params p) {
@@ -87,7 +59,7 @@ __global__ __launch_bounds__(256, 2) void stem3_fused_kernel(Stem3Params p) {
     __shared__ __attribute__((aligned(16))) float4 W1[9 * 8];                           // depthwise-1 weights
     __shared__ float Cv[R0ROWS];                                                        // 1 = conv1 pixel inside its map
     __shared__ float Pv[R1ROWS];                                                        // 1 = block-1 pixel inside its map
-    static_assert(R0ROWS * COP <= R1PIX * P1P && RAWH * RAWP <= R1PIX * P1P, "conv1 region and input window fit in U2");
+    static_assert(RAWH * RAWP <= R1PIX * P1P, "the input window fits in U2");
     float* Raw = U2;
     float* Co = U2;
     float* P1 = U2;
@@ -100,8 +72,7 @@ __global__ __launch_bounds__(256, 2) void stem3_fused_kernel(Stem3Params p) {
     if (tid < 9 * 16) W2[tid] = p.wd2[tid];
     if (tid < 9 * 8) W1[tid] = p.wd1[tid];
     const int c4l = tid & 7;                         // depthwise-1 channel quad of this thread
-    // depthwise 1 feeds the split: its scale / shift carry the 2^a_log2 pre-scale (a power of two commutes with every rounding
-    // here: relu6(s * sc + sh) * 2^a == clamp(s * (sc 2^a) + sh 2^a, 0, 6 * 2^a) bit for bit)
+    // (depthwise 1's scale / shift carry the 2^a_log2 pre-scale of the split: stage_dw1)
     float4 d1sc = p.d1scale[c4l], d1sh = p.d1shift[c4l];
     d1sc.x *= p.a_scale; d1sc.y *= p.a_scale; d1sc.z *= p.a_scale; d1sc.w *= p.a_scale;
     d1sh.x *= p.a_scale; d1sh.y *= p.a_scale; d1sh.z *= p.a_scale; d1sh.w *= p.a_scale;
@@ -123,30 +94,7 @@ __global__ __launch_bounds__(256, 2) void stem3_fused_kernel(Stem3Params p) {
     const f16x8 bl = *(const f16x8*)((const unsigned char*)p.wsplit + (size_t)(wave * 16 + l16) * 128 + 64 + 16 * q4);
     const f32x4 pds = *(const f32x4*)(p.descale + wave * 16 + 4 * q4), psh = *(const f32x4*)(p.pshift + wave * 16 + 4 * q4);
 
-    // ---- patch cursor (advanced with carries: no divisions in the loop) ----
-    struct Cur { int n, th, tw; };
-    auto decode = [&](unsigned t) {
-        const unsigned lt = xcd_remap_dir(t, p.total, p.reverse);
-        Cur c;
-        c.tw = lt % p.tiles_w;
-        c.th = (lt / p.tiles_w) % p.tiles_h;
-        c.n = lt / (p.tiles_w * p.tiles_h);
-        return c;
-    };
-    const int stride_lt = gridDim.x / 8;             // launch guarantees gridDim.x % 8 == 0 whenever the kernel loops
-    const int dtw_ = stride_lt % p.tiles_w, dth_ = (stride_lt / p.tiles_w) % p.tiles_h, dn_ = stride_lt / (p.tiles_w * p.tiles_h);
-    auto advance = [&](Cur c) {
-        if (!p.reverse) {
-            c.tw += dtw_; if (c.tw >= p.tiles_w) { c.tw -= p.tiles_w; c.th += 1; }
-            c.th += dth_; if (c.th >= p.tiles_h) { c.th -= p.tiles_h; c.n += 1; }
-            c.n += dn_;
-        } else {
-            c.tw -= dtw_; if (c.tw < 0) { c.tw += p.tiles_w; c.th -= 1; }
-            c.th -= dth_; if (c.th < 0) { c.th += p.tiles_h; c.n -= 1; }
-            c.n -= dn_;
-        }
-        return c;
-    };
+    const Cur step = cursor_step(p);
 
     // ---- the input window of a patch: 23 rows x 30 sixteen-byte pieces, three per thread, whole image rows ----
     // Rows outside the image get an out-of-range offset (the buffer returns zeros); columns outside it are masked when the
@@ -195,7 +143,7 @@ __global__ __launch_bounds__(256, 2) void stem3_fused_kernel(Stem3Params p) {
 
     unsigned t = blockIdx.x;
     if (t >= p.total) return;
-    Cur cur = decode(t);
+    Cur cur = decode(p, t);
     load_window(cur);
     park_window();
     __syncthreads();
@@ -204,16 +152,12 @@ __global__ __launch_bounds__(256, 2) void stem3_fused_kernel(Stem3Params p) {
     while (true) {
         const unsigned tn = t + gridDim.x;
         const bool more = tn < p.total;
-        const Cur nxt = advance(cur);
+        const Cur nxt = advance(p, cur, step);
         const int y10 = 2 * cur.th * PH - p.pad_t2, x10 = 2 * cur.tw * PW - p.pad_l2;
         // a patch whose conv1 region lies inside the 96x96 map has no pixel to zero: the validity factors are all 1 (uniform test)
         const bool interior = y10 - 1 >= 0 && x10 - 1 >= 0 && y10 - 1 + R0H <= p.H1 && x10 - 1 + R0W <= p.W1;
         STEM_STAMP(0);
-        // The thread index is made opaque once per patch: every stage's LDS addresses are then re-derived (a few VALU) instead
-        // of being hoisted out of the loop as ~100 loop-invariant VGPRs -- which had the compiler spill to scratch.
-        int tix = threadIdx.x;
-        asm volatile("" : "+v"(tix));
-        const int tid = tix, lane = tid & 63, l16 = lane & 15, q4 = lane >> 4, c4l = tid & 7, c4o = tid & 15;
+        const int tid = opaque((int)threadIdx.x), lane = tid & 63, l16 = lane & 15, q4 = lane >> 4, c4l = tid & 7, c4o = tid & 15;
 
         // ---- stage A': cut the im2col rows (k = dy*9 + dx*3 + ci) of the 209 conv1 pixels from the window, split into f16 hi + lo ----
         if (tid < R0ROWS) {
@@ -315,112 +259,17 @@ __global__ __launch_bounds__(256, 2) void stem3_fused_kernel(Stem3Params p) {
         __syncthreads();     // conv1 region complete; im2col rows dead
         STEM_STAMP(2);
 
-        // ---- stage C: depthwise 1.  Thread = (channel quad, run of <= 6 pixels of one region row): 3 x 8 taps read once ----
-        {
-            const int grp = tid >> 3;                              // 27 runs: row = grp / 3, columns 6 * (grp % 3) ..
-            if (grp < 27) {
-                const int ry = grp / 3, c0 = 6 * (grp - 3 * ry);
-                // row by row: 8 taps of a region row feed 6 running sums (the products of a pixel are added in the order
-                // dy = 0 (dx 0,1,2), dy = 1, dy = 2 of stem2_fused.hip / dwconv.hip: same bits)
-                f32x4 sum[6];
-#pragma unroll
-                for (int j = 0; j < 6; ++j) sum[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int dy = 0; dy < 3; ++dy) {
-                    f32x4 tap[8];
-#pragma unroll
-                    // (the last run is 5 pixels wide: its eighth tap is the next row's first pixel, read and never used --
-                    // all 24 addresses are one base plus a constant)
-                    for (int col = 0; col < 8; ++col) tap[col] = *(const f32x4*)(&Co[((ry + dy) * R0W + c0 + col) * COP + 4 * c4l]);
-                    const f32x4 w0 = as_v(W1[(dy * 3 + 0) * 8 + c4l]), w1 = as_v(W1[(dy * 3 + 1) * 8 + c4l]), w2 = as_v(W1[(dy * 3 + 2) * 8 + c4l]);
-#pragma unroll
-                    for (int j = 0; j < 6; ++j) {
-                        sum[j] = vfma(tap[j], w0, sum[j]);
-                        sum[j] = vfma(tap[j + 1], w1, sum[j]);
-                        sum[j] = vfma(tap[j + 2], w2, sum[j]);
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < 6; ++j) {
-                    if (c0 + j < R1W) {
-                        const f32x4 o = vfma(sum[j], as_v(d1sc), as_v(d1sh));
-                        f32x4 v;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = fminf(fmaxf(o[e], 0.f), cap6);
-                        const f16x4 hi = __builtin_convertvector(v, f16x4);
-                        const f16x4 lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x4), f16x4);
-                        const int q = ry * R1W + c0 + j;
-                        *(f16x4*)(&As[swzb(q, c4l >> 1) + 8 * (c4l & 1)]) = hi;
-                        *(f16x4*)(&As[swzb(q, 4 + (c4l >> 1)) + 8 * (c4l & 1)]) = lo;
-                    }
-                }
-            }
-        }
+        stage_dw1(Co, W1, As, tid, c4l, as_v(d1sc), as_v(d1sh), cap6);     // stage C: depthwise 1 -> split-f16 A tile
         STEM_STAMP(4);
-        __syncthreads();     // A tile complete (rows 153..159 hold stale bytes: their products are never stored); conv1 region dead
+        __syncthreads();     // A tile complete; conv1 region dead
         STEM_STAMP(2);
 
-        // ---- stage D: pointwise on the f16 MFMA (K = 32 in one instruction); wave w = channels 16w..16w+15, all 10 row blocks
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-            f16x8 ah[5], al[5];
-#pragma unroll
-            for (int i = 0; i < 5; ++i) {
-                ah[i] = *(const f16x8*)(&As[swzb((5 * half + i) * 16 + l16, q4)]);
-                al[i] = *(const f16x8*)(&As[swzb((5 * half + i) * 16 + l16, 4 + q4)]);
-            }
-            f32x4 acc[5];
-#pragma unroll
-            for (int i = 0; i < 5; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int pdt = 0; pdt < 3; ++pdt)
-#pragma unroll
-                for (int i = 0; i < 5; ++i)
-                    acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pdt == 1 ? bl : bh, pdt == 0 ? al[i] : ah[i], acc[i], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < 5; ++i) {
-                // lane: block-1 pixel m = 16*mb + l16, channels 16*wave + 4*q4 + (0..3)
-                const int m = (5 * half + i) * 16 + l16;
-                if (m < R1PIX) {
-                    f32x4 o;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = relu6(fmaf(acc[i][e], pds[e], psh[e]));
-                    if (!interior) o = o * Pv[m];
-                    *(f32x4*)(&P1[m * P1P + wave * 16 + 4 * q4]) = o;
-                }
-            }
-        }
+        stage_pw(As, P1, Pv, interior, wave, l16, q4, bh, bl, pds, psh);   // stage D: pointwise -> 96x96x64 patch
         STEM_STAMP(5);
         __syncthreads();     // 96x96x64 patch complete; A tile dead
         STEM_STAMP(2);
 
-        // ---- stage E: depthwise 2 (stride 2) from LDS -> global; both output pixels of a thread in flight together ----
-        {
-            const __amdgpu_buffer_rsrc_t ry = make_rsrc(p.y + (size_t)cur.n * p.OH2 * p.OW2 * 64, (long long)p.OH2 * p.OW2 * 256);
-            f32x4 tp[2][9];
-#pragma unroll
-            for (int it = 0; it < 2; ++it) {
-                const int px = (tid >> 4) + 16 * it, i = px >> 3, j = px & 7;
-#pragma unroll
-                for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-                    for (int dx = 0; dx < 3; ++dx) tp[it][dy * 3 + dx] = *(const f32x4*)(&P1[((2 * i + dy) * R1W + 2 * j + dx) * P1P + 4 * c4o]);
-            }
-#pragma unroll
-            for (int it = 0; it < 2; ++it) {
-                const int px = (tid >> 4) + 16 * it, i = px >> 3, j = px & 7;
-                f32x4 s = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int k = 0; k < 9; ++k) s = vfma(tp[it][k], as_v(W2[k * 16 + c4o]), s);
-                const f32x4 o = vfma(s, as_v(d2sc), as_v(d2sh));
-                f32x4 v;
-                v[0] = apply_act<ACT>(o[0]); v[1] = apply_act<ACT>(o[1]); v[2] = apply_act<ACT>(o[2]); v[3] = apply_act<ACT>(o[3]);
-                const int oh = cur.th * PH + i, ow = cur.tw * PW + j;
-                // a pixel outside the map gets an offset beyond the resource and the store is dropped (no branch)
-                const unsigned voff = (oh < p.OH2 && ow < p.OW2) ? (unsigned)(oh * p.OW2 + ow) * 256u + 16u * c4o : 0x80000000u;
-                bstore16(v, ry, voff, 0);
-            }
-        }
+        stage_dw2<ACT>(p, cur, P1, W2, tid, c4o, as_v(d2sc), as_v(d2sh));  // stage E: depthwise 2 -> global
         STEM_STAMP(6);
         STEM_STAMP_COUNT;
         if (!more) break;
@@ -448,37 +297,23 @@ int launch_stem3_fused(const float* x, const void* cw_split, const float* cdesca
     HSEFR_REQUIRE(h1 == (h + 1) / 2 && w1 == (w + 1) / 2 && oh2 == (h1 + 1) / 2 && ow2 == (w1 + 1) / 2, HSEFR_ERR_INVALID,
                   "stem3_fused: %dx%d -> %dx%d -> %dx%d is not two SAME stride-2 steps", h, w, h1, w1, oh2, ow2);
     HSEFR_REQUIRE(pad_t2 >= 0 && pad_t2 <= 1 && pad_l2 >= 0 && pad_l2 <= 1, HSEFR_ERR_INVALID, "stem3_fused: depthwise-2 padding %d,%d", pad_t2, pad_l2);
-    HSEFR_REQUIRE(a_log2 > 0 && a_log2 <= 12, HSEFR_ERR_INVALID, "stem3_fused: a_log2=%d", a_log2);
-    HSEFR_REQUIRE(in_log2 >= -8 && in_log2 <= 14, HSEFR_ERR_INVALID, "stem3_fused: in_log2=%d", in_log2);
+    HSEFR_REQUIRE(a_log2_ok(a_log2), HSEFR_ERR_INVALID, "stem3_fused: a_log2=%d", a_log2);
+    HSEFR_REQUIRE(in_log2_ok(in_log2), HSEFR_ERR_INVALID, "stem3_fused: in_log2=%d", in_log2);
     HSEFR_REQUIRE((long long)n * h * w * 12 < (1ll << 32) - 64 && (long long)n * h * w * 3 < (1ll << 31) - 64, HSEFR_ERR_UNSUPPORTED,
                   "stem3_fused: the input batch must stay below 4 GB (its offsets travel in 32 bits)");
     if (n == 0) return HSEFR_OK;
     Stem3Params p;
-    p.x = x; p.cw_split = cw_split; p.cdescale = cdescale; p.cshift = cshift; p.wd1 = (const float4*)wd1; p.d1scale = (const float4*)d1scale;
-    p.d1shift = (const float4*)d1shift; p.wsplit = (const float*)wsplit; p.descale = descale; p.pshift = pshift;
-    p.wd2 = (const float4*)wd2; p.d2scale = (const float4*)d2scale; p.d2shift = (const float4*)d2shift; p.y = y; p.overflow = overflow;
-    p.H = h; p.W = w; p.H1 = h1; p.W1 = w1; p.OH2 = oh2; p.OW2 = ow2; p.cpad_t = cpad_t; p.cpad_l = cpad_l;
-    p.pad_t2 = pad_t2; p.pad_l2 = pad_l2;
-    p.tiles_w = (ow2 + PW - 1) / PW; p.tiles_h = (oh2 + PH - 1) / PH;
-    const long long total = (long long)n * p.tiles_w * p.tiles_h;
-    HSEFR_REQUIRE(total < (1ll << 31), HSEFR_ERR_UNSUPPORTED, "stem3_fused: grid too large");
-    p.total = (unsigned)total;
-    p.a_scale = ldexpf(1.f, a_log2);
+    p.x = x; p.cw_split = cw_split; p.cdescale = cdescale; p.cshift = cshift; p.overflow = overflow;
+    p.cpad_t = cpad_t; p.cpad_l = cpad_l; p.pad_t2 = pad_t2; p.pad_l2 = pad_l2;
+    if (const int rc = fill_params(p, "stem3_fused", wd1, d1scale, d1shift, wsplit, descale, pshift, wd2, d2scale, d2shift, y, n, h, w, h1, w1,
+                                   oh2, ow2, a_log2, s)) return rc;
     p.in_scale = ldexpf(1.f, in_log2);
     p.in_bound = ldexpf(1.f, 15 - in_log2);
-    p.reverse = sweep_reverse();
     p.x_floats = (long long)n * h * w * 3;
     p.x_bytes = p.x_floats * 4;
-    p.stamps = nullptr;
-#ifdef HSEFR_STEM_STAMPS
-    p.stamps = stamp_buffer(s);
-#endif
     const unsigned g = p.total < 512u ? p.total : 512u;      // 512 % 8 == 0: the kernel's incremental patch cursor relies on it
 #define HSEFR_STEM3(A) HSEFR_LAUNCH((stem3_fused_kernel<A>), dim3(g), dim3(256), 0, s, p)
-    if (act == HSEFR_ACT_RELU6) HSEFR_STEM3(HSEFR_ACT_RELU6);
-    else if (act == HSEFR_ACT_RELU) HSEFR_STEM3(HSEFR_ACT_RELU);
-    else if (act == HSEFR_ACT_NONE) HSEFR_STEM3(HSEFR_ACT_NONE);
-    else { set_error("stem3_fused: act %d", act); return HSEFR_ERR_UNSUPPORTED; }
+    HSEFR_STEM_ACT_DISPATCH("stem3_fused", act, HSEFR_STEM3);
 #undef HSEFR_STEM3
     return launch_status("stem3_fused");
 }

@@ -25,18 +25,13 @@
 // Shapes: H % 4 == 0 and W % 4 == 0 (SAME padding then pads bottom / right only in both stride-2 layers), as stem4.
 #include <type_traits>
 
-#include "common.h"
+#include "stem_patch.h"     // namespace stem only: the vector types, Frag4 and the one-line helpers
 
 namespace hsefr {
 
-namespace {
+using namespace stem;
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-struct __attribute__((packed, aligned(4))) Frag4 { f16x8 v; };      // a 16-byte MFMA fragment at a 4-byte-aligned LDS address
+namespace {
 
 struct Stem5Params {
     const void* x;         // [N,H,W,3] fp32 (preprocessed) or uint8 RGB (U8)
@@ -105,10 +100,6 @@ static_assert(OFF_AS + PMB * 16 * 128 <= WAVE_LDS, "the A tile's over-read stays
 static_assert(4 + 12 * (CXW - 1) + 32 <= WRP, "the second K step of a row's last pixel stays inside the row");
 static_assert(S5_WGS * (WAVES * WAVE_LDS + 14 * 1024) <= 160 * 1024, "S5_WGS workgroups per CU");
 
-__device__ __forceinline__ int swzb(int row, int chunk) { return row * 128 + 16 * (chunk ^ ((row >> 1) & 7) ^ ((row & 1) << 2)); }
-[[maybe_unused]] __device__ __forceinline__ float relu6(float v) { return fminf(fmaxf(v, 0.f), 6.f); }
-__device__ __forceinline__ f32x4 vfma(f32x4 a, f32x4 b, f32x4 c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ f32x4 as_v(float4 a) { return (f32x4){a.x, a.y, a.z, a.w}; }
 // the waves of a workgroup do not synchronise: what one lane wrote to LDS another lane of the SAME wave reads back, in
 // program order (the LDS serves a wave's instructions in order) -- the compiler only has to keep that order
 __device__ __forceinline__ void wave_order() { asm volatile("" ::: "memory"); }
