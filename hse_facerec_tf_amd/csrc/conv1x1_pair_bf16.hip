@@ -22,7 +22,7 @@
 //   * every vector-memory operation is a compiler-visible builtin (loads AND stores), so hipcc's own in-order vmcnt arithmetic is exact.
 // Every output element is accumulated over K in one fixed order by one wave: bit-identical run to run, independent of the grid; and K
 // is walked in the order the separate kernels walk it.
-#include "common.h"
+#include "bf16_dma.h"
 
 #ifndef PAIR_XAUX
 #define PAIR_XAUX 0     // cache policy of the activation loads: bits 0-1 x (the 3x3 layer's output: this launch is its only reader), bits 2-3 x2 (the
@@ -33,10 +33,7 @@ namespace hsefr {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ float bfround(float f) { return __uint_as_float(hsefr_bf16_bits(f) << 16); }
+using namespace bf16_dma;
 
 struct PairParams {
     const void* x;        // [M][K1] bf16
@@ -66,14 +63,6 @@ struct PairParams {
     hsefr_udiv d_hw, d_w;           // ... exact division by H W and by W (common.h)
     long long y1_bytes;
 };
-
-// LDS row R of a weight image <-> output channel (conv1x1_w4_bf16.hip's permutation, per 32 channels): rows 16 b + i of a pair of
-// 16-row blocks hold channel 8 (i >> 2) + 4 b + (i & 3), so that accumulator element e of block b in lane (l16, lq) is channel
-// 8 lq + 4 b + e
-__device__ __forceinline__ int perm_channel(int R) {
-    const int i = R & 15, b = (R >> 4) & 1;
-    return (R & ~31) + 8 * (i >> 2) + 4 * b + (i & 3);
-}
 
 template <int K1, int K2, int N1, int N2, int PB, int WAVES, bool PROJ>
 __global__ __launch_bounds__(WAVES * 64) void conv1x1_pair_bf16_kernel(PairParams p) {
@@ -143,7 +132,6 @@ __global__ __launch_bounds__(WAVES * 64) void conv1x1_pair_bf16_kernel(PairParam
 #else
     constexpr int abl = 0;
 #endif
-    constexpr unsigned OOR = 0x80000000u;        // beyond every resource (tensors < 2 GiB): loads return zeros, move no bytes
     // the lane's pixel in pixel block 0 of wave tile t (tiles past the last: out of range)
     auto tile_pix = [&](unsigned t) __attribute__((always_inline)) -> unsigned {
         const unsigned tt = p.reverse ? p.ntiles - 1u - t : t;
@@ -234,22 +222,12 @@ __global__ __launch_bounds__(WAVES * 64) void conv1x1_pair_bf16_kernel(PairParam
                         for (int pb = 0; pb < PB; ++pb)
                             acc[b][pb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, x2f[PROJ ? pb : 0][PROJ ? hh : 0], acc[b][pb], 0, 0, 0);
                     }
-                f32x4 sc[2], sh[2];
+                ScaleShift c[2];
 #pragma unroll
-                for (int b = 0; b < 2; ++b) {
-                    sc[b] = *(const f32x4*)(cst + C_SP + 32 * j + 8 * lq + 4 * b);
-                    sh[b] = *(const f32x4*)(cst + C_SP + N1 + 32 * j + 8 * lq + 4 * b);
-                }
+                for (int b = 0; b < 2; ++b)
+                    c[b] = ScaleShift{*(const f32x4*)(cst + C_SP + 32 * j + 8 * lq + 4 * b), *(const f32x4*)(cst + C_SP + N1 + 32 * j + 8 * lq + 4 * b)};
 #pragma unroll
-                for (int pb = 0; pb < PB; ++pb) {
-                    float v[8];
-#pragma unroll
-                    for (int b = 0; b < 2; ++b)
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[4 * b + e] = fmaf(acc[b][pb][e], sc[b][e], sh[b][e]);
-#pragma unroll
-                    for (int d = 0; d < 4; ++d) rr[0][pb][d] = __uint_as_float(hsefr_pack_bf16x2(v[2 * d], v[2 * d + 1]));
-                }
+                for (int pb = 0; pb < PB; ++pb) rr[0][pb] = park8(acc[0][pb], acc[1][pb], c[0], c[1]);
             }
 #pragma unroll
             for (int b = 0; b < 2; ++b)
@@ -264,33 +242,14 @@ __global__ __launch_bounds__(WAVES * 64) void conv1x1_pair_bf16_kernel(PairParam
                     for (int pb = 0; pb < PB; ++pb) acc[b][pb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, xf[pb][hh], acc[b][pb], 0, 0, 0);
                 }
             // ---- epilogue of the chunk: Y1's 32 channels, stored AND kept (rounded) as the second product's B operand ----
-            f32x4 sc[2], sh[2];
+            ScaleShift c[2];
 #pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                sc[b] = *(const f32x4*)(cst + 32 * j + 8 * lq + 4 * b);
-                sh[b] = *(const f32x4*)(cst + N1 + 32 * j + 8 * lq + 4 * b);
-            }
+            for (int b = 0; b < 2; ++b) c[b] = ScaleShift{*(const f32x4*)(cst + 32 * j + 8 * lq + 4 * b), *(const f32x4*)(cst + N1 + 32 * j + 8 * lq + 4 * b)};
             bf16x8 yf[PB];
             f32x4 o[PB];
 #pragma unroll
             for (int pb = 0; pb < PB; ++pb) {
-                float v[8];
-#pragma unroll
-                for (int b = 0; b < 2; ++b)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[4 * b + e] = fmaf(acc[b][pb][e], sc[b][e], sh[b][e]);
-                const f32x4 r = rr[PROJ ? 0 : j][pb];
-#pragma unroll
-                for (int d = 0; d < 4; ++d) {
-                    const unsigned rw = __float_as_uint(r[d]);
-                    v[2 * d] = bfround(v[2 * d]) + __uint_as_float(rw << 16);
-                    v[2 * d + 1] = bfround(v[2 * d + 1]) + __uint_as_float(rw & 0xFFFF0000u);
-                }
-#pragma unroll
-                for (int d = 0; d < 4; ++d) {
-                    const float f0 = fminf(fmaxf(v[2 * d], p.act1_lo), p.act1_hi), f1 = fminf(fmaxf(v[2 * d + 1], p.act1_lo), p.act1_hi);
-                    o[pb][d] = __uint_as_float(hsefr_pack_bf16x2(f0, f1));
-                }
+                o[pb] = epilogue8(acc[0][pb], acc[1][pb], c[0], c[1], true, rr[PROJ ? 0 : j][pb], p.act1_lo, p.act1_hi);
                 yf[pb] = __builtin_bit_cast(bf16x8, o[pb]);
             }
             if (!PROJ && !(abl & 1)) load_res(j, t + nw);                     // this chunk of the NEXT tile, into the registers just read
@@ -310,25 +269,13 @@ __global__ __launch_bounds__(WAVES * 64) void conv1x1_pair_bf16_kernel(PairParam
         const unsigned y2lane = pix0 * (N2 * 2u) + (unsigned)(16 * lq);
 #pragma unroll
         for (int m2 = 0; m2 < MB2 / 2; ++m2) {
-            f32x4 sc[2], sh[2];
+            ScaleShift c[2];
 #pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                sc[b] = *(const f32x4*)(cst + C_S2 + 32 * m2 + 8 * lq + 4 * b);
-                sh[b] = *(const f32x4*)(cst + C_S2 + N2 + 32 * m2 + 8 * lq + 4 * b);
-            }
+            for (int b = 0; b < 2; ++b)
+                c[b] = ScaleShift{*(const f32x4*)(cst + C_S2 + 32 * m2 + 8 * lq + 4 * b), *(const f32x4*)(cst + C_S2 + N2 + 32 * m2 + 8 * lq + 4 * b)};
 #pragma unroll
             for (int pb = 0; pb < PB; ++pb) {
-                float v[8];
-#pragma unroll
-                for (int b = 0; b < 2; ++b)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[4 * b + e] = fmaf(acc2[2 * m2 + b][pb][e], sc[b][e], sh[b][e]);
-                f32x4 o;
-#pragma unroll
-                for (int d = 0; d < 4; ++d) {
-                    const float f0 = fminf(fmaxf(v[2 * d], p.act2_lo), p.act2_hi), f1 = fminf(fmaxf(v[2 * d + 1], p.act2_lo), p.act2_hi);
-                    o[d] = __uint_as_float(hsefr_pack_bf16x2(f0, f1));
-                }
+                const f32x4 o = epilogue8(acc2[2 * m2][pb], acc2[2 * m2 + 1][pb], c[0], c[1], false, f32x4{}, p.act2_lo, p.act2_hi);
                 if (!(abl & 4)) store16(o, ry2, y2lane + (unsigned)(16 * pb * N2 * 2 + 64 * m2), p.nt & 4);
             }
         }
@@ -379,9 +326,9 @@ int launch_conv1x1_pair_bf16(const void* x, const void* w1, const float* scale1,
     HSEFR_REQUIRE(conv1x1_pair_bf16_supported(pixels, c, cout1, cout2, c2), HSEFR_ERR_UNSUPPORTED,
                   "conv1x1_pair_bf16: %d -> %d -> %d (projection from %d) over %lld pixels not covered", c, cout1, cout2, c2, pixels);
     HSEFR_REQUIRE((c2 > 0) != (res != nullptr), HSEFR_ERR_INVALID, "conv1x1_pair_bf16: exactly one of residual / projected shortcut");
-    for (int a : {act1, act2})
-        HSEFR_REQUIRE(a == HSEFR_ACT_NONE || a == HSEFR_ACT_RELU || a == HSEFR_ACT_RELU6, HSEFR_ERR_UNSUPPORTED, "conv1x1_pair_bf16: act %d", a);
     PairParams p;
+    if (const int rc = act_bounds(act1, "conv1x1_pair_bf16", &p.act1_lo, &p.act1_hi)) return rc;
+    if (const int rc = act_bounds(act2, "conv1x1_pair_bf16", &p.act2_lo, &p.act2_hi)) return rc;
     p.x = x; p.w1 = w1; p.scale1 = scale1; p.shift1 = shift1; p.res = res; p.x2 = x2; p.wp = wp; p.scale_p = scale_p; p.shift_p = shift_p;
     p.y1 = y1; p.w2 = w2; p.scale2 = scale2; p.shift2 = shift2; p.y2 = y2;
     p.M = (unsigned)pixels;
@@ -399,10 +346,6 @@ int launch_conv1x1_pair_bf16(const void* x, const void* w1, const float* scale1,
     p.reverse = sweep_reverse();
     p.ablate = g_pair_ablate;
     p.nt = g_pair_nt;
-    p.act1_lo = act1 == HSEFR_ACT_NONE ? -INFINITY : 0.f;
-    p.act1_hi = act1 == HSEFR_ACT_RELU6 ? 6.f : INFINITY;
-    p.act2_lo = act2 == HSEFR_ACT_NONE ? -INFINITY : 0.f;
-    p.act2_hi = act2 == HSEFR_ACT_RELU6 ? 6.f : INFINITY;
     if (c2 > 0) return launch_pair<64, 64, 256, 64, 2, 8, true>(p, s);
     return launch_pair<64, 64, 256, 64, 2, 8, false>(p, s);
 }

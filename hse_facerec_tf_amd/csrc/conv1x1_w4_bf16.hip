@@ -29,7 +29,7 @@
 // by what the CU's vector-memory path moves (DESIGN.md lesson 54).
 #include <type_traits>
 
-#include "common.h"
+#include "bf16_dma.h"
 
 #ifndef W4_RESAUX
 #define W4_RESAUX 0     // cache policy of the residual loads (buffer aux bits: 1 glc, 2 slc), as conv1x1_bf16.hip's C11_RESAUX
@@ -38,32 +38,11 @@ namespace hsefr {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+using namespace bf16_dma;
 
-constexpr int ROWB = 128;                 // bytes per LDS row: 64 bf16 = one K-step
 constexpr int NA = 3, NB = 4;             // ring stages: activations, weights
 
-#ifdef HSEFR_CD_STAMPS
-__device__ unsigned long long g_w4_stamps[256 * 8 * 8];
-#define W4_STAMP(i) do { const unsigned long long _t = __builtin_amdgcn_s_memtime(); st[i] += _t - tprev; tprev = _t; } while (0)
-#define W4_STAMP_DECL unsigned long long st[6] = {0, 0, 0, 0, 0, 0}; unsigned long long tprev = __builtin_amdgcn_s_memtime(); const unsigned long long tstart = tprev
-#define W4_STAMP_FLUSH do { if (lane == 0 && blockIdx.x < 256) { unsigned long long* o = g_w4_stamps + (blockIdx.x * 8 + wave) * 8; \
-    for (int i_ = 0; i_ < 6; ++i_) o[i_] = st[i_]; o[6] = __builtin_amdgcn_s_memtime() - tstart; o[7] = nsteps; } } while (0)
-#else
-#define W4_STAMP(i) do { } while (0)
-#define W4_STAMP_DECL do { } while (0)
-#define W4_STAMP_FLUSH do { } while (0)
-#endif
-
-__device__ __forceinline__ float bfround(float f) { return __uint_as_float(hsefr_bf16_bits(f) << 16); }
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc_sgpr(const void* ptr, long long bytes) {
-    const unsigned long long a = (unsigned long long)ptr;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-    const unsigned n = __builtin_amdgcn_readfirstlane(bytes <= 0 ? 0u : (bytes > 0xffffffffll ? 0xffffffffu : (unsigned)bytes));
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)hi << 32) | lo), 0, n, 0x00020000);
-}
-__device__ __forceinline__ void step_barrier() { asm volatile("s_barrier" ::: "memory"); }
+BF16_STAMP_ARRAY(g_w4_stamps, 8);
 
 struct W4Params {
     const void* x;       // [N,H,W,K] bf16
@@ -111,13 +90,13 @@ __global__ __launch_bounds__(512) void conv1x1_w4_bf16_kernel(W4Params p) {
     const int KT2 = PROJ ? p.K2 / 64 : 0;          // a tile's K loop: the projection's steps first, then the main product's
     const int KT = p.K / 64 + KT2;
     if (blockIdx.x >= p.total_tiles) return;
-    const unsigned ntile = (p.total_tiles - blockIdx.x + gridDim.x - 1) / gridDim.x;
+    const unsigned ntile = tiles_of_workgroup(p.total_tiles);
     const unsigned nsteps = ntile * (unsigned)KT;
     const unsigned wrowbytes = (unsigned)p.K * 2u;
     const unsigned wrowbytes2 = PROJ ? (unsigned)p.K2 * 2u : 0u;
 
     auto tile_origin = [&](unsigned i, unsigned& mm0, int& nn0) __attribute__((always_inline)) {
-        const unsigned lt = xcd_remap_dir(blockIdx.x + (i < ntile ? i : ntile - 1) * gridDim.x, p.total_tiles, p.reverse);
+        const unsigned lt = tile_index(i, ntile, p.total_tiles, p.reverse);
         const unsigned tm = lt / p.tiles_n;
         mm0 = tm * BM;
         nn0 = (int)(lt - tm * p.tiles_n) * BN;
@@ -127,19 +106,14 @@ __global__ __launch_bounds__(512) void conv1x1_w4_bf16_kernel(W4Params p) {
     if (wave >= 4) {
         // =================================== loader waves 4..7 ===================================
         const int lw = wave - 4;
-        auto piece = [&](const __amdgpu_buffer_rsrc_t& r, unsigned lds_addr, unsigned voff) __attribute__((always_inline)) {
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(__builtin_amdgcn_readfirstlane(lds_addr)), "v"(voff), "s"(r)
-                         : "memory", "m0");
-        };
         const __amdgpu_buffer_rsrc_t rx = make_rsrc_sgpr(p.x, p.x_bytes);
-        // weight pieces: LDS row R = 64 wn + 16 nb + i holds output channel 64 wn + 32 (nb >> 1) + 8 (i >> 2) + 4 (nb & 1) + (i & 3)
+        // weight pieces: LDS row R holds output channel perm_channel(R)
         unsigned pvb[BPW], pvb2[PROJ ? BPW : 1];
         const __amdgpu_buffer_rsrc_t rx2 = make_rsrc_sgpr(PROJ ? p.x2 : nullptr, PROJ ? p.x2_bytes : 0);
 #pragma unroll
         for (int j = 0; j < BPW; ++j) {
             const int R = (lw * BPW + j) * 8 + (lane >> 3);
-            const int nb = (R >> 4) & 3, i = R & 15;
-            const int ch = (R & ~63) + 32 * (nb >> 1) + 8 * (i >> 2) + 4 * (nb & 1) + (i & 3);
+            const int ch = perm_channel(R);
             pvb[j] = (unsigned)ch * wrowbytes + 16u * (unsigned)((lane & 7) ^ (R & 6));
             if (PROJ) pvb2[PROJ ? j : 0] = (unsigned)ch * wrowbytes2 + 16u * (unsigned)((lane & 7) ^ (R & 6));
         }
@@ -163,12 +137,12 @@ __global__ __launch_bounds__(512) void conv1x1_w4_bf16_kernel(W4Params p) {
                     const unsigned oh = rem / (unsigned)p.OW, ow = rem - oh * (unsigned)p.OW;
                     pix = (n * (unsigned)p.H + oh * (unsigned)p.stride) * (unsigned)p.W + ow * (unsigned)p.stride;
                 }
-                pa[j] = m < p.M ? pix * wrowbytes + 16u * chunk : 0x80000000u;
+                pa[j] = m < p.M ? pix * wrowbytes + 16u * chunk : OOR;
                 if (PROJ) {      // output pixel (n, oh, ow) is projected from input pixel (n, oh stride2, ow stride2) of the block's input
                     const unsigned n = m / ohow, rem = m - n * ohow;
                     const unsigned oh = rem / (unsigned)p.OW, ow = rem - oh * (unsigned)p.OW;
                     const unsigned pix2 = (n * (unsigned)p.H2 + oh * (unsigned)p.stride2) * (unsigned)p.W2 + ow * (unsigned)p.stride2;
-                    pa2[PROJ ? j : 0] = m < p.M ? pix2 * wrowbytes2 + 16u * chunk : 0x80000000u;
+                    pa2[PROJ ? j : 0] = m < p.M ? pix2 * wrowbytes2 + 16u * chunk : OOR;
                 }
             }
         };
@@ -179,19 +153,19 @@ __global__ __launch_bounds__(512) void conv1x1_w4_bf16_kernel(W4Params p) {
             const bool proj_step = PROJ && a_kt < (unsigned)KT2;       // (wave-uniform)
             if (proj_step) {
 #pragma unroll
-                for (int j = 0; j < APW; ++j) voff[j] = (live && pa2[PROJ ? j : 0] != 0x80000000u) ? pa2[PROJ ? j : 0] + a_kt * 128u : 0x80000000u;
+                for (int j = 0; j < APW; ++j) voff[j] = (live && pa2[PROJ ? j : 0] != OOR) ? pa2[PROJ ? j : 0] + a_kt * 128u : OOR;
             } else {
 #pragma unroll
-                for (int j = 0; j < APW; ++j) voff[j] = (live && pa[j] != 0x80000000u) ? pa[j] + (a_kt - (unsigned)KT2) * 128u : 0x80000000u;
+                for (int j = 0; j < APW; ++j) voff[j] = (live && pa[j] != OOR) ? pa[j] + (a_kt - (unsigned)KT2) * 128u : OOR;
             }
 #pragma unroll
             for (int j = 0; j < APW; ++j) asm volatile("" : "+v"(voff[j]));
             if (proj_step) {
 #pragma unroll
-                for (int j = 0; j < APW; ++j) piece(rx2, base + (lw * APW + j) * 1024, voff[j]);
+                for (int j = 0; j < APW; ++j) dma_piece(rx2, base + (lw * APW + j) * 1024, voff[j]);
             } else {
 #pragma unroll
-                for (int j = 0; j < APW; ++j) piece(rx, base + (lw * APW + j) * 1024, voff[j]);
+                for (int j = 0; j < APW; ++j) dma_piece(rx, base + (lw * APW + j) * 1024, voff[j]);
             }
             ++a_step;
             if (++a_kt == (unsigned)KT) { a_kt = 0; setup_a(++a_tile); }
@@ -220,11 +194,11 @@ __global__ __launch_bounds__(512) void conv1x1_w4_bf16_kernel(W4Params p) {
                 unsigned voff[BPW];
 #pragma unroll
                 for (int j = 0; j < BPW; ++j)
-                    voff[j] = !live ? 0x80000000u : proj_step ? pvb2[PROJ ? j : 0] + b_kt * 128u : pvb[j] + (b_kt - (unsigned)KT2) * 128u;
+                    voff[j] = !live ? OOR : proj_step ? pvb2[PROJ ? j : 0] + b_kt * 128u : pvb[j] + (b_kt - (unsigned)KT2) * 128u;
 #pragma unroll
                 for (int j = 0; j < BPW; ++j) asm volatile("" : "+v"(voff[j]));
 #pragma unroll
-                for (int j = 0; j < BPW; ++j) piece(rw, base + (lw * BPW + j) * 1024, voff[j]);
+                for (int j = 0; j < BPW; ++j) dma_piece(rw, base + (lw * BPW + j) * 1024, voff[j]);
             }
             ++b_step;
             if (++b_kt == (unsigned)KT) { b_kt = 0; setup_b(++b_tile); }
@@ -241,39 +215,36 @@ __global__ __launch_bounds__(512) void conv1x1_w4_bf16_kernel(W4Params p) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         step_barrier();                                        // P
         unsigned ci = 0, ckt = 0;
-        W4_STAMP_DECL;
+        BF16_STAMP_DECL;
         for (unsigned g = 0; g < nsteps; ++g) {
             if (ckt == 0 && lw == 3) {
-                // the tile's epilogue constants by LDS-DMA (scale as lanes 0-31 of one piece, shift as lanes 32-63 of a second one),
-                // ahead of this step's pieces: the counted wait of the NEXT step covers them
+                // the tile's epilogue constants, ahead of this step's pieces: the counted wait of the NEXT step covers them
                 unsigned mm0;
                 int e_n0;
                 tile_origin(ci, mm0, e_n0);
                 const __amdgpu_buffer_rsrc_t rd = make_rsrc_sgpr(p.scale + e_n0, (long long)(p.Cout - e_n0) * 4),
                                              rs = make_rsrc_sgpr(p.shift + e_n0, (long long)(p.Cout - e_n0) * 4);
                 const unsigned eb = lds0 + E_OFF + (ci & 1u) * E_PAR;
-                piece(rd, eb, lane < 32 ? 16u * lane : 0x80000000u);
-                piece(rs, eb + 1024, lane >= 32 ? 16u * (unsigned)(lane - 32) : 0x80000000u);
+                stage_scale_shift(rd, rs, eb, lane);
                 if (PROJ) {
                     const __amdgpu_buffer_rsrc_t rd2 = make_rsrc_sgpr(p.scale2 + e_n0, (long long)(p.Cout - e_n0) * 4),
                                                  rs2 = make_rsrc_sgpr(p.shift2 + e_n0, (long long)(p.Cout - e_n0) * 4);
-                    piece(rd2, eb + 2048, lane < 32 ? 16u * lane : 0x80000000u);
-                    piece(rs2, eb + 3072, lane >= 32 ? 16u * (unsigned)(lane - 32) : 0x80000000u);
+                    stage_scale_shift(rd2, rs2, eb + 2048, lane);
                 }
             }
             issue_a();                                          // step g + 2: its slot held step g - 1, released at the last barrier
             issue_b();                                          // step g + 3: likewise
-            W4_STAMP(0);
+            BF16_STAMP(0);
             // everything older than this iteration's pieces has landed (resident weights: from its second iteration on a loader issues none)
             if (p.b_resident && g + 3u >= (unsigned)NB) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(APW) : "memory");
             else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(APW + BPW) : "memory");
-            W4_STAMP(1);
+            BF16_STAMP(1);
             step_barrier();                                     // B_g: activations of step g + 1 and weights of step g + 2 are there
-            W4_STAMP(2);
+            BF16_STAMP(2);
             if (++ckt == (unsigned)KT) { ckt = 0; ++ci; }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        W4_STAMP_FLUSH;
+        BF16_STAMP_FLUSH(g_w4_stamps, 8);
         return;
     }
 
@@ -317,7 +288,7 @@ __global__ __launch_bounds__(512) void conv1x1_w4_bf16_kernel(W4Params p) {
 #pragma unroll
         for (int nb = 0; nb < 4; ++nb) { bfr[nb][0] = ldb(bfirst, nb, 0); bfr[nb][1] = ldb(bfirst, nb, 1); }
     }
-    W4_STAMP_DECL;
+    BF16_STAMP_DECL;
 
     for (unsigned g = 0; g < nsteps; ++g) {
         const unsigned as0 = a0 + (g % NA) * ASTAGE;
@@ -365,81 +336,47 @@ __global__ __launch_bounds__(512) void conv1x1_w4_bf16_kernel(W4Params p) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
             }
         }
-        W4_STAMP(0);
+        BF16_STAMP(0);
         step_barrier();                                     // B_g
-        W4_STAMP(1);
+        BF16_STAMP(1);
         __builtin_amdgcn_sched_barrier(0);
         ++ckt;
         if (PROJ && ckt == KT2) {
             // the projection is complete: scale2 / shift2, rounded to bf16 where its tensor used to be stored, parked as bf16 pairs in
             // the registers (and the layout) of the plain kernel's residual fragments; the accumulators start again
-            f32x4 e_sc[4], e_sh[4];
+            ScaleShift e_c[4];
 #pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                const int cch = wn * 64 + 32 * (v >> 1) + 8 * lq + 4 * (v & 1);
-                e_sc[v] = *(const f32x4*)(smem + E_OFF + (ci & 1u) * E_PAR + 2048 + cch * 4);
-                e_sh[v] = *(const f32x4*)(smem + E_OFF + (ci & 1u) * E_PAR + 3072 + 512 + cch * 4);
-            }
+            for (int v = 0; v < 4; ++v) e_c[v] = read_scale_shift(smem + E_OFF + (ci & 1u) * E_PAR + 2048, wn * 64 + 32 * (v >> 1) + 8 * lq + 4 * (v & 1));
 #pragma unroll
             for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    float v[8];
-#pragma unroll
-                    for (int h = 0; h < 2; ++h)
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[4 * h + e] = fmaf(acc[rb][2 * j + h][e], e_sc[2 * j + h][e], e_sh[2 * j + h][e]);
-#pragma unroll
-                    for (int d = 0; d < 4; ++d) rres[rb][j][d] = __uint_as_float(hsefr_pack_bf16x2(v[2 * d], v[2 * d + 1]));
-                }
+                for (int j = 0; j < 2; ++j) rres[rb][j] = park8(acc[rb][2 * j], acc[rb][2 * j + 1], e_c[2 * j], e_c[2 * j + 1]);
             zero_acc();
         }
         if (ckt == KT) {
             ckt = 0;
             const long long yorg = ((long long)m0 * p.Cout + n0) * 2ll, ybytes = ((long long)(p.M - m0) * p.Cout - n0) * 2ll;
             const __amdgpu_buffer_rsrc_t ry = make_rsrc_sgpr((char*)p.y + yorg, ybytes);
-            f32x4 e_sc[4], e_sh[4];
+            ScaleShift e_c[4];
 #pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                const int cch = wn * 64 + 32 * (v >> 1) + 8 * lq + 4 * (v & 1);
-                e_sc[v] = *(const f32x4*)(smem + E_OFF + (ci & 1u) * E_PAR + cch * 4);
-                e_sh[v] = *(const f32x4*)(smem + E_OFF + (ci & 1u) * E_PAR + 1024 + 512 + cch * 4);
-            }
+            for (int v = 0; v < 4; ++v) e_c[v] = read_scale_shift(smem + E_OFF + (ci & 1u) * E_PAR, wn * 64 + 32 * (v >> 1) + 8 * lq + 4 * (v & 1));
 #pragma unroll
             for (int rb = 0; rb < RB; ++rb) {
                 const unsigned soff = __builtin_amdgcn_readfirstlane((unsigned)(16 * rb) * (unsigned)p.Cout * 2u);
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-                    float v[8];
-#pragma unroll
-                    for (int h = 0; h < 2; ++h)
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[4 * h + e] = fmaf(acc[rb][2 * j + h][e], e_sc[2 * j + h][e], e_sh[2 * j + h][e]);
-                    if (PROJ || p.res) {
-#pragma unroll
-                        for (int d = 0; d < 4; ++d) {
-                            const unsigned rw2 = __float_as_uint(rres[rb][j][d]);
-                            v[2 * d] = bfround(v[2 * d]) + __uint_as_float(rw2 << 16);
-                            v[2 * d + 1] = bfround(v[2 * d + 1]) + __uint_as_float(rw2 & 0xFFFF0000u);
-                        }
-                    }
-                    f32x4 o;
-#pragma unroll
-                    for (int d = 0; d < 4; ++d) {
-                        const float f0 = fminf(fmaxf(v[2 * d], p.act_lo), p.act_hi), f1 = fminf(fmaxf(v[2 * d + 1], p.act_lo), p.act_hi);
-                        o[d] = __uint_as_float(hsefr_pack_bf16x2(f0, f1));
-                    }
+                    const f32x4 o = epilogue8(acc[rb][2 * j], acc[rb][2 * j + 1], e_c[2 * j], e_c[2 * j + 1], PROJ || p.res, rres[rb][j], p.act_lo, p.act_hi);
                     // (rows past M belong to no tile: the resource ends with the tensor and the hardware drops them)
                     bstore16_welded(o, ry, ylane + 64u * (unsigned)j, soff);
                 }
             }
             zero_acc();
             tile_origin(++ci, m0, n0);
-            W4_STAMP(2);
+            BF16_STAMP(2);
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // stores issued from asm: drained before the wave ends
-    W4_STAMP_FLUSH;
+    BF16_STAMP_FLUSH(g_w4_stamps, 8);
 }
 
 
@@ -452,9 +389,8 @@ int launch_w4(W4Params& p, hipStream_t s) {
     const long long tiles_m = ((long long)p.M + BM - 1) / BM;
     p.tiles_n = (unsigned)(p.Cout / BN);
     const long long total = tiles_m * p.tiles_n;
-    HSEFR_REQUIRE(total < (1ll << 31), HSEFR_ERR_UNSUPPORTED, "conv1x1_w4: too many tiles");
-    p.total_tiles = (unsigned)total;
-    const unsigned g = (unsigned)(total < 256 ? total : 256);
+    unsigned g;
+    if (const int rc = persistent_grid(total, "conv1x1_w4", &p.total_tiles, &g)) return rc;
     // resident weights: the steps of a tile divide the ring (K = 64 / 128 / 256) and the grid's stride keeps a workgroup on one channel origin
     // (xcd_remap_dir permutes inside blocks of eight: conv1x1_bf16.hip's rule)
     p.b_resident = (!PROJ && g_w4_bres && total > g && (p.K == 64 || p.K == 128 || p.K == 256) && g % 8 == 0 && (g / 8) % p.tiles_n == 0) ? 1 : 0;
@@ -465,17 +401,7 @@ int launch_w4(W4Params& p, hipStream_t s) {
 }  // namespace
 
 #ifdef HSEFR_DEV
-int read_w4_stamps(void* host_out, size_t bytes) {
-#ifdef HSEFR_CD_STAMPS
-    HSEFR_REQUIRE(bytes <= sizeof(unsigned long long) * 256 * 8 * 8, HSEFR_ERR_INVALID, "read_w4_stamps: too many bytes");
-    HSEFR_HIP_CHECK(hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_w4_stamps), bytes));
-    return HSEFR_OK;
-#else
-    (void)host_out; (void)bytes;
-    set_error("read_w4_stamps: library built without -DHSEFR_CD_STAMPS");
-    return HSEFR_ERR_UNSUPPORTED;
-#endif
-}
+int read_w4_stamps(void* host_out, size_t bytes) { return read_stamps_impl(BF16_STAMP_SYMBOL(g_w4_stamps), "read_w4_stamps", host_out, bytes); }
 #endif
 
 bool conv1x1_w4_forced() { return g_w4_off == 2; }
@@ -500,13 +426,11 @@ bool conv1x1_w4_bf16_preferred(long long pixels, int c, int cout, bool has_res) 
 int launch_conv1x1_w4_bf16(const void* x, const void* wt, const float* scale, const float* shift, const void* res, void* y, int n, int h,
                            int w, int c, int oh, int ow, int cout, int stride, int act, hipStream_t s) {
     HSEFR_REQUIRE(conv1x1_w4_bf16_supported(n, h, w, c, oh, ow, cout, stride), HSEFR_ERR_UNSUPPORTED, "conv1x1_w4_bf16: shape not covered");
-    HSEFR_REQUIRE(act == HSEFR_ACT_NONE || act == HSEFR_ACT_RELU || act == HSEFR_ACT_RELU6, HSEFR_ERR_UNSUPPORTED, "conv1x1_w4_bf16: act %d", act);
     W4Params p;
+    if (const int rc = act_bounds(act, "conv1x1_w4_bf16", &p.act_lo, &p.act_hi)) return rc;
     p.x = x; p.wt = wt; p.scale = scale; p.shift = shift; p.res = res; p.y = y;
     p.x_bytes = (long long)n * h * w * c * 2;
     p.K = c; p.Cout = cout; p.stride = stride; p.H = h; p.W = w; p.OH = oh; p.OW = ow;
-    p.act_lo = act == HSEFR_ACT_NONE ? -INFINITY : 0.f;
-    p.act_hi = act == HSEFR_ACT_RELU6 ? 6.f : INFINITY;
     p.M = (unsigned)((long long)n * oh * ow);
     p.reverse = sweep_reverse();
     p.x2 = nullptr; p.wt2 = nullptr; p.scale2 = nullptr; p.shift2 = nullptr; p.x2_bytes = 0; p.K2 = 0; p.stride2 = 1; p.H2 = 0; p.W2 = 0;
@@ -530,11 +454,10 @@ int launch_conv1x1_w4_proj_bf16(const void* x, const void* wt, const float* scal
     HSEFR_REQUIRE(cout % 128 == 0 && conv1x1_w4_bf16_supported(n, oh, ow, c, oh, ow, cout, 1) && conv1x1_w4_bf16_supported(n, h2, w2, c2, oh, ow, cout, stride2),
                   HSEFR_ERR_UNSUPPORTED, "conv1x1_w4_proj_bf16: shape not covered");
     W4Params p;
+    if (const int rc = act_bounds(act, "conv1x1_w4_proj_bf16", &p.act_lo, &p.act_hi)) return rc;
     p.x = x; p.wt = wt; p.scale = scale; p.shift = shift; p.res = nullptr; p.y = y;
     p.x_bytes = (long long)n * oh * ow * c * 2;
     p.K = c; p.Cout = cout; p.stride = 1; p.H = oh; p.W = ow; p.OH = oh; p.OW = ow;
-    p.act_lo = act == HSEFR_ACT_NONE ? -INFINITY : 0.f;
-    p.act_hi = act == HSEFR_ACT_RELU6 ? 6.f : INFINITY;
     p.M = (unsigned)((long long)n * oh * ow);
     p.reverse = sweep_reverse();
     p.x2 = x2; p.wt2 = wt2; p.scale2 = scale2; p.shift2 = shift2;

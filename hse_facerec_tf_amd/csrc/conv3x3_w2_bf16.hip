@@ -29,41 +29,17 @@
 // Every output element is accumulated in one fixed order by one wave: bit-identical run to run, independent of the grid.
 #include <type_traits>
 
-#include "common.h"
+#include "bf16_dma.h"
 
 namespace hsefr {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+using namespace bf16_dma;
 
-constexpr int ROWB = 128;                 // bytes per LDS row: 64 bf16 = one K-step of one pixel / one weight row
 constexpr int NSTG = 4;                   // weight ring stages
 
-#ifdef HSEFR_CD_STAMPS
-__device__ unsigned long long g_w2_stamps[256 * 8 * 8];
-#define W2_STAMP(i) do { const unsigned long long _t = __builtin_amdgcn_s_memtime(); st[i] += _t - tprev; tprev = _t; } while (0)
-#define W2_STAMP_DECL unsigned long long st[6] = {0, 0, 0, 0, 0, 0}; unsigned long long tprev = __builtin_amdgcn_s_memtime(); const unsigned long long tstart = tprev
-#define W2_STAMP_FLUSH do { if (lane == 0 && blockIdx.x < 256) { unsigned long long* o = g_w2_stamps + (blockIdx.x * 8 + wave) * 8; \
-    for (int i_ = 0; i_ < 6; ++i_) o[i_] = st[i_]; o[6] = __builtin_amdgcn_s_memtime() - tstart; o[7] = nsteps; } } while (0)
-#else
-#define W2_STAMP(i) do { } while (0)
-#define W2_STAMP_DECL do { } while (0)
-#define W2_STAMP_FLUSH do { } while (0)
-#endif
-
-__device__ __forceinline__ unsigned f2bf_bits(float f) { return hsefr_bf16_bits(f); }      // round-to-nearest-even (common.h)
-__device__ __forceinline__ float bfround(float f) { return __uint_as_float(f2bf_bits(f) << 16); }
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc_sgpr(const void* ptr, long long bytes) {
-    const unsigned long long a = (unsigned long long)ptr;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-    const unsigned n = __builtin_amdgcn_readfirstlane(bytes <= 0 ? 0u : (bytes > 0xffffffffll ? 0xffffffffu : (unsigned)bytes));
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)hi << 32) | lo), 0, n, 0x00020000);
-}
-// the workgroup barrier WITHOUT __syncthreads()'s waits: LDS reads of the next step may stay in flight across it (see the header);
-// the "memory" clobber keeps hipcc from moving LDS accesses over it
-__device__ __forceinline__ void step_barrier() { asm volatile("s_barrier" ::: "memory"); }
+BF16_STAMP_ARRAY(g_w2_stamps, 8);
 
 struct W2Params {
     const void* x;       // [N,H,W,C] bf16
@@ -114,14 +90,14 @@ __global__ __launch_bounds__(512) void conv3x3_w2_bf16_kernel(W2Params p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int CS = p.C / 64;
     if (blockIdx.x >= p.total_tiles) return;
-    const unsigned ntile = (p.total_tiles - blockIdx.x + gridDim.x - 1) / gridDim.x;
+    const unsigned ntile = tiles_of_workgroup(p.total_tiles);
     const unsigned nq = ntile * (unsigned)CS;       // slab-windows this workgroup goes through
     const unsigned nsteps = nq * 9u;
     const unsigned wrowbytes = (unsigned)(9 * CS) * 128u;
 
     // tile i of this workgroup -> image, first row, first output channel
     auto tile_origin = [&](unsigned i, int& tn, int& ty0, int& cc0) __attribute__((always_inline)) {
-        const unsigned lt = xcd_remap_dir(blockIdx.x + (i < ntile ? i : ntile - 1) * gridDim.x, p.total_tiles, p.reverse);
+        const unsigned lt = tile_index(i, ntile, p.total_tiles, p.reverse);
         const unsigned tm = lt / p.tiles_n;
         cc0 = (int)(lt - tm * p.tiles_n) * BN;
         if (FLAT) { tn = (int)tm * IMG; ty0 = 0; return; }
@@ -133,21 +109,13 @@ __global__ __launch_bounds__(512) void conv3x3_w2_bf16_kernel(W2Params p) {
     if (wave >= 4) {
         // =================================== loader waves 4..7 ===================================
         const int lw = wave - 4;
-        auto piece = [&](const __amdgpu_buffer_rsrc_t& r, unsigned lds_addr, unsigned voff) __attribute__((always_inline)) {
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(__builtin_amdgcn_readfirstlane(lds_addr)), "v"(voff), "s"(r)
-                         : "memory", "m0");
-        };
         const __amdgpu_buffer_rsrc_t rx = make_rsrc_sgpr(p.x, p.x_bytes);
-        // weight pieces: LDS rows 8 (lw BPW + j) .. + 7 of the stage.  LDS row R = 64 wn + 16 nb + i holds output channel
-        // 64 wn + 32 (nb >> 1) + 8 (i >> 2) + 4 (nb & 1) + (i & 3): with the weights as the first MFMA operand a lane then owns
-        // 8 consecutive channels per pair of channel blocks (16-byte stores from the accumulators)
+        // weight pieces: LDS rows 8 (lw BPW + j) .. + 7 of the stage; LDS row R holds output channel perm_channel(R)
         unsigned pvb[BPW];
 #pragma unroll
         for (int j = 0; j < BPW; ++j) {
             const int R = (lw * BPW + j) * 8 + (lane >> 3);
-            const int nb = (R >> 4) & 3, i = R & 15;
-            const int ch = (R & ~63) + 32 * (nb >> 1) + 8 * (i >> 2) + 4 * (nb & 1) + (i & 3);
-            pvb[j] = (unsigned)ch * wrowbytes + 16u * (unsigned)((lane & 7) ^ (R & 6));
+            pvb[j] = (unsigned)perm_channel(R) * wrowbytes + 16u * (unsigned)((lane & 7) ^ (R & 6));
         }
         // window pieces of this wave: piece lw + 4 s, s = 0 .. WSLOTS - 1 (those >= WPIECES do not exist)
         unsigned wbase[WSLOTS];
@@ -163,7 +131,7 @@ __global__ __launch_bounds__(512) void conv3x3_w2_bf16_kernel(W2Params p) {
                 else { wy = w / PX; wx = w - wy * PX; }
                 const int iy = ty0 - 1 + wy, ix = wx - 1;
                 const bool ok = w < NWR && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W && tn + img < p.N && (!FLAT || img < IMG);
-                wbase[s] = ok ? (unsigned)(((tn + img) * p.H + iy) * p.W + ix) * (unsigned)(p.C * 2) + 16u * (unsigned)((lane & 7) ^ (wx & 6)) : 0x80000000u;
+                wbase[s] = ok ? (unsigned)(((tn + img) * p.H + iy) * p.W + ix) * (unsigned)(p.C * 2) + 16u * (unsigned)((lane & 7) ^ (wx & 6)) : OOR;
             }
         };
         // issue window slots [s0, s0 + cnt) of the window with sequence number wq (buffer wq & 1), slab offset wsl; slots that do not
@@ -172,14 +140,14 @@ __global__ __launch_bounds__(512) void conv3x3_w2_bf16_kernel(W2Params p) {
             constexpr int cnt = decltype(CNT)::value;
             unsigned voff[cnt];
 #pragma unroll
-            for (int s = 0; s < cnt; ++s) voff[s] = (live && s0 + s < WSLOTS) ? wbase[s0 + s < WSLOTS ? s0 + s : 0] + wsl * 128u : 0x80000000u;
+            for (int s = 0; s < cnt; ++s) voff[s] = (live && s0 + s < WSLOTS) ? wbase[s0 + s < WSLOTS ? s0 + s : 0] + wsl * 128u : OOR;
 #pragma unroll
             for (int s = 0; s < cnt; ++s) asm volatile("" : "+v"(voff[s]));
 #pragma unroll
             for (int s = 0; s < cnt; ++s) {
                 const int pw = lw + 4 * (s0 + s);
                 const unsigned dst = (live && s0 + s < WSLOTS && pw < WPIECES) ? lds0 + (wq & 1u) * WIN_BYTES + (unsigned)pw * 1024u : lds0 + DUMMY_OFF;
-                piece(rx, dst, voff[s]);
+                dma_piece(rx, dst, voff[s]);
             }
         };
         // weight cursor: the step whose weights go out next (three ahead of the step the MFMA waves are on)
@@ -199,11 +167,11 @@ __global__ __launch_bounds__(512) void conv3x3_w2_bf16_kernel(W2Params p) {
             const bool live = pf_step < nsteps;
             unsigned voff[BPW];
 #pragma unroll
-            for (int j = 0; j < BPW; ++j) voff[j] = live ? pvb[j] + b_adv : 0x80000000u;
+            for (int j = 0; j < BPW; ++j) voff[j] = live ? pvb[j] + b_adv : OOR;
 #pragma unroll
             for (int j = 0; j < BPW; ++j) asm volatile("" : "+v"(voff[j]));
 #pragma unroll
-            for (int j = 0; j < BPW; ++j) piece(rw, base + (lw * BPW + j) * 1024, voff[j]);
+            for (int j = 0; j < BPW; ++j) dma_piece(rw, base + (lw * BPW + j) * 1024, voff[j]);
             ++pf_step;
             if (++pf_tap == 9u) {
                 pf_tap = 0;
@@ -227,33 +195,30 @@ __global__ __launch_bounds__(512) void conv3x3_w2_bf16_kernel(W2Params p) {
         step_barrier();                                        // P: window 0 and steps 0..2 have landed
         unsigned ci = 0;                                        // tile the MFMA waves are on (for the epilogue constants)
         unsigned slab_in_tile = 0;
-        W2_STAMP_DECL;
+        BF16_STAMP_DECL;
         for (unsigned q = 0; q < nq; ++q) {
             const bool next_live = q + 1 < nq;                  // window q + 1 exists
 #pragma unroll
             for (int t = 0; t < 9; ++t) {
                 if (t == 0 && slab_in_tile == 0 && lw == 3) {
-                    // the tile's epilogue constants by LDS-DMA: scale[c0 ..] as lanes 0-31 of one piece, shift[..] as lanes 32-63 of a
-                    // second one; issued AHEAD of this step's pieces so the counted wait of the NEXT step covers them
+                    // the tile's epilogue constants, issued AHEAD of this step's pieces so the counted wait of the NEXT step covers them
                     int tn, ty0, e_c0;
                     tile_origin(ci, tn, ty0, e_c0);
                     const __amdgpu_buffer_rsrc_t rd = make_rsrc_sgpr(p.scale + e_c0, (long long)(p.Cout - e_c0) * 4),
                                                  rs = make_rsrc_sgpr(p.shift + e_c0, (long long)(p.Cout - e_c0) * 4);
-                    const unsigned eb = lds0 + E_OFF + (ci & 1u) * 2048u;
-                    piece(rd, eb, lane < 32 ? 16u * lane : 0x80000000u);
-                    piece(rs, eb + 1024, lane >= 32 ? 16u * (unsigned)(lane - 32) : 0x80000000u);
+                    stage_scale_shift(rd, rs, lds0 + E_OFF + (ci & 1u) * 2048u, lane);
                 }
                 // window q + 1 during taps 0..6: its buffer was last read in the final step of slab q - 1, behind the barrier this
                 // iteration started from; it is complete at the barrier that ends tap 7 (the wait of tap 7 covers tap 6's pieces),
                 // one step before its first fragment is read
                 if (t <= 6) issue_window(WPT * t, std::integral_constant<int, WPT>{}, q + 1, nw_slab, next_live);
                 issue_weights();                                // step 9 q + t + 3
-                W2_STAMP(0);
+                BF16_STAMP(0);
                 if (t <= 6) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(BPW + WPT) : "memory");     // everything older than this iteration's pieces
                 else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(BPW) : "memory");
-                W2_STAMP(1);
+                BF16_STAMP(1);
                 step_barrier();                                 // B_g: step g + 2 has landed, the slots of step g are free
-                W2_STAMP(2);
+                BF16_STAMP(2);
             }
             if (++slab_in_tile == (unsigned)CS) { slab_in_tile = 0; ++ci; }
             if (++nw_slab == (unsigned)CS) {
@@ -262,7 +227,7 @@ __global__ __launch_bounds__(512) void conv3x3_w2_bf16_kernel(W2Params p) {
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        W2_STAMP_FLUSH;
+        BF16_STAMP_FLUSH(g_w2_stamps, 8);
         return;
     }
 
@@ -315,7 +280,7 @@ __global__ __launch_bounds__(512) void conv3x3_w2_bf16_kernel(W2Params p) {
 #pragma unroll
         for (int blk = 0; blk < 2; ++blk) { ar[blk][0] = lda(acur, 0, aimm(blk, 0), 0); ar[blk][1] = lda(acur, 0, aimm(blk, 0), 1); }
     }
-    W2_STAMP_DECL;
+    BF16_STAMP_DECL;
 
     unsigned slab_in_tile = 0;
     for (unsigned q = 0; q < nq; ++q) {
@@ -366,9 +331,9 @@ __global__ __launch_bounds__(512) void conv3x3_w2_bf16_kernel(W2Params p) {
                 }
             }
             ++g;
-            W2_STAMP(0);
+            BF16_STAMP(0);
             step_barrier();                                 // B_g
-            W2_STAMP(1);
+            BF16_STAMP(1);
             __builtin_amdgcn_sched_barrier(0);
         }
         // the next slab reads the other window buffer
@@ -384,13 +349,9 @@ __global__ __launch_bounds__(512) void conv3x3_w2_bf16_kernel(W2Params p) {
             const long long ybytes = (long long)p.M * p.Cout * 2ll - yorg;
             const __amdgpu_buffer_rsrc_t ry = make_rsrc_sgpr((char*)p.y + yorg, ybytes);
             const __amdgpu_buffer_rsrc_t rr = make_rsrc_sgpr((const char*)p.res + yorg, p.res ? ybytes : 0);
-            f32x4 e_sc[4], e_sh[4];
+            ScaleShift e_c[4];
 #pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                const int cch = wn * 64 + 32 * (v >> 1) + 8 * lq + 4 * (v & 1);
-                e_sc[v] = *(const f32x4*)(smem + E_OFF + (ci & 1u) * 2048 + cch * 4);
-                e_sh[v] = *(const f32x4*)(smem + E_OFF + (ci & 1u) * 2048 + 1024 + 512 + cch * 4);
-            }
+            for (int v = 0; v < 4; ++v) e_c[v] = read_scale_shift(smem + E_OFF + (ci & 1u) * 2048, wn * 64 + 32 * (v >> 1) + 8 * lq + 4 * (v & 1));
             // FLAT: a block is two 8-slot rows of one image: lane -> (row l16 >> 3, column l16 & 7)
             const unsigned ylane = (FLAT ? (unsigned)((l16 >> 3) * p.W + (l16 & 7)) : (unsigned)l16) * (unsigned)p.Cout * 2u + 16u * (unsigned)lq;
 #pragma unroll
@@ -403,37 +364,21 @@ __global__ __launch_bounds__(512) void conv3x3_w2_bf16_kernel(W2Params p) {
                                                                           : (unsigned)(dy * p.W + dx) * (unsigned)p.Cout * 2u);
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-                    const unsigned voff = ok ? ylane + 64u * (unsigned)j : 0x80000000u;
+                    const unsigned voff = ok ? ylane + 64u * (unsigned)j : OOR;
                     float v[8];
-#pragma unroll
-                    for (int h = 0; h < 2; ++h)
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[4 * h + e] = fmaf(acc[rb][2 * j + h][e], e_sc[2 * j + h][e], e_sh[2 * j + h][e]);
-                    if (p.res) {
-                        const f32x4 rres = bload16(rr, voff, soff);
-#pragma unroll
-                        for (int d = 0; d < 4; ++d) {
-                            const unsigned rw2 = __float_as_uint(rres[d]);
-                            v[2 * d] = bfround(v[2 * d]) + __uint_as_float(rw2 << 16);
-                            v[2 * d + 1] = bfround(v[2 * d + 1]) + __uint_as_float(rw2 & 0xFFFF0000u);
-                        }
-                    }
-                    f32x4 o;
-#pragma unroll
-                    for (int d = 0; d < 4; ++d) {
-                        const float f0 = fminf(fmaxf(v[2 * d], p.act_lo), p.act_hi), f1 = fminf(fmaxf(v[2 * d + 1], p.act_lo), p.act_hi);
-                        o[d] = __uint_as_float(hsefr_pack_bf16x2(f0, f1));
-                    }
+                    scale_shift8(v, acc[rb][2 * j], acc[rb][2 * j + 1], e_c[2 * j], e_c[2 * j + 1]);
+                    if (p.res) add_residual8(v, bload16(rr, voff, soff));      // (the load stays inside the branch, next to its use)
+                    const f32x4 o = clamp_pack8(v, p.act_lo, p.act_hi);
                     bstore16_welded(o, ry, voff, soff);
                 }
             }
             zero_acc();
             tile_origin(++ci, tn, ty0, c0);
-            W2_STAMP(2);
+            BF16_STAMP(2);
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // stores issued from asm: drained before the wave ends
-    W2_STAMP_FLUSH;
+    BF16_STAMP_FLUSH(g_w2_stamps, 8);
 }
 
 HSEFR_KNOB(g_w2_off, "w2_off", 0);    // dev builds: 1 = never use this kernel, 2 = for every shape it covers
@@ -446,9 +391,8 @@ int launch_w2(W2Params& p, hipStream_t s) {
     p.tiles_n = (unsigned)(p.Cout / BN);
     p.tiles_y = FLAT ? 1 : (p.H + TR - 1) / TR;
     const long long total = (FLAT ? (long long)((p.N + IMG - 1) / IMG) : (long long)p.N * p.tiles_y) * p.tiles_n;
-    HSEFR_REQUIRE(total < (1ll << 31), HSEFR_ERR_UNSUPPORTED, "conv3x3_w2: too many tiles");
-    p.total_tiles = (unsigned)total;
-    const unsigned g = (unsigned)(total < 256 ? total : 256);
+    unsigned g;
+    if (const int rc = persistent_grid(total, "conv3x3_w2", &p.total_tiles, &g)) return rc;
     HSEFR_LAUNCH((conv3x3_w2_bf16_kernel<RB, WAVES_M, WX, RBX, FLAT>), dim3(g), dim3(512), 0, s, p);
     return launch_status("conv3x3_w2_bf16");
 }
@@ -466,17 +410,7 @@ int w2_config(int h, int w, int cout) {
 }  // namespace
 
 #ifdef HSEFR_DEV
-int read_w2_stamps(void* host_out, size_t bytes) {
-#ifdef HSEFR_CD_STAMPS
-    HSEFR_REQUIRE(bytes <= sizeof(unsigned long long) * 256 * 8 * 8, HSEFR_ERR_INVALID, "read_w2_stamps: too many bytes");
-    HSEFR_HIP_CHECK(hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_w2_stamps), bytes));
-    return HSEFR_OK;
-#else
-    (void)host_out; (void)bytes;
-    set_error("read_w2_stamps: library built without -DHSEFR_CD_STAMPS");
-    return HSEFR_ERR_UNSUPPORTED;
-#endif
-}
+int read_w2_stamps(void* host_out, size_t bytes) { return read_stamps_impl(BF16_STAMP_SYMBOL(g_w2_stamps), "read_w2_stamps", host_out, bytes); }
 #endif
 
 bool conv3x3_w2_forced() { return g_w2_off == 2; }
@@ -502,13 +436,11 @@ bool conv3x3_w2_bf16_preferred(int h, int w, int cout) {
 int launch_conv3x3_w2_bf16(const void* x, const void* wt, const float* scale, const float* shift, const void* res, void* y, int n, int h,
                            int w, int c, int cout, int act, hipStream_t s) {
     HSEFR_REQUIRE(conv3x3_w2_bf16_supported(n, h, w, c, cout), HSEFR_ERR_UNSUPPORTED, "conv3x3_w2_bf16: shape not covered");
-    HSEFR_REQUIRE(act == HSEFR_ACT_NONE || act == HSEFR_ACT_RELU || act == HSEFR_ACT_RELU6, HSEFR_ERR_UNSUPPORTED, "conv3x3_w2_bf16: act %d", act);
     W2Params p;
+    if (const int rc = act_bounds(act, "conv3x3_w2_bf16", &p.act_lo, &p.act_hi)) return rc;
     p.x = x; p.wt = wt; p.scale = scale; p.shift = shift; p.res = res; p.y = y;
     p.x_bytes = (long long)n * h * w * c * 2;
     p.N = n; p.H = h; p.W = w; p.C = c; p.Cout = cout;
-    p.act_lo = act == HSEFR_ACT_NONE ? -INFINITY : 0.f;
-    p.act_hi = act == HSEFR_ACT_RELU6 ? 6.f : INFINITY;
     p.M = (unsigned)((long long)n * h * w);
     p.reverse = sweep_reverse();
     switch (w2_config(h, w, cout)) {

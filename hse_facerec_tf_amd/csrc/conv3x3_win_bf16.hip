@@ -22,40 +22,18 @@
 // 7x7: two images.  Every output element is accumulated in one fixed order by one wave: bit-identical run to run.
 #include <type_traits>
 
-#include "common.h"
+#include "bf16_dma.h"
 
 namespace hsefr {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+using namespace bf16_dma;
 
-constexpr int ROWB = 128;                 // bytes per LDS row: 64 bf16
-
-#ifdef HSEFR_CD_STAMPS
-__device__ unsigned long long g_w3_stamps[256 * 12 * 8];
-#define W3_STAMP(i) do { const unsigned long long _t = __builtin_amdgcn_s_memtime(); st[i] += _t - tprev; tprev = _t; } while (0)
-#define W3_STAMP_DECL unsigned long long st[6] = {0, 0, 0, 0, 0, 0}; unsigned long long tprev = __builtin_amdgcn_s_memtime(); const unsigned long long tstart = tprev
-#define W3_STAMP_FLUSH do { if (lane == 0 && blockIdx.x < 256) { unsigned long long* o = g_w3_stamps + (blockIdx.x * 12 + wave) * 8; \
-    for (int i_ = 0; i_ < 6; ++i_) o[i_] = st[i_]; o[6] = __builtin_amdgcn_s_memtime() - tstart; o[7] = nsteps; } } while (0)
-#else
-#define W3_STAMP(i) do { } while (0)
-#define W3_STAMP_DECL do { } while (0)
-#define W3_STAMP_FLUSH do { } while (0)
-#endif
 constexpr int WIN_BYTES = 384 * ROWB;     // one window buffer: up to 384 rows (48 KiB)
 constexpr int WSLOTS = 12;                // window pieces per loader wave (4 x 12 x 8 rows = 384)
 
-__device__ __forceinline__ int swz_key(int row) { return ((row >> 1) & 7) ^ ((row & 1) << 2); }
-__device__ __forceinline__ unsigned f2bf_bits(float f) { return hsefr_bf16_bits(f); }      // round-to-nearest-even (common.h)
-__device__ __forceinline__ float bfround(float f) { return __uint_as_float(f2bf_bits(f) << 16); }
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc_sgpr(const void* ptr, long long bytes) {
-    const unsigned long long a = (unsigned long long)ptr;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-    const unsigned n = __builtin_amdgcn_readfirstlane(bytes <= 0 ? 0u : (bytes > 0xffffffffll ? 0xffffffffu : (unsigned)bytes));
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)hi << 32) | lo), 0, n, 0x00020000);
-}
+BF16_STAMP_ARRAY(g_w3_stamps, 12);
 
 struct Win3Params {
     const void* x;       // [N,H,W,C] bf16
@@ -91,7 +69,7 @@ __global__ __launch_bounds__(768, 1) void conv3x3_win_bf16_kernel(Win3Params p) 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int CS = p.C / 64;
     if (blockIdx.x >= p.total_tiles) return;
-    const unsigned ntile = (p.total_tiles - blockIdx.x + gridDim.x - 1) / gridDim.x;
+    const unsigned ntile = tiles_of_workgroup(p.total_tiles);
     const unsigned nq = ntile * (unsigned)CS;       // slab-windows this workgroup goes through
     const unsigned nsteps = nq * 9u;
     const unsigned wrowbytes = (unsigned)(9 * CS) * 128u;
@@ -101,7 +79,7 @@ __global__ __launch_bounds__(768, 1) void conv3x3_win_bf16_kernel(Win3Params p) 
 
     // tile i of this workgroup -> first image, first row, first output pixel, first output channel
     auto tile_origin = [&](unsigned i, int& tn0, int& ty0, unsigned& mm0, int& cc0) __attribute__((always_inline)) {
-        const unsigned lt = xcd_remap_dir(blockIdx.x + (i < ntile ? i : ntile - 1) * gridDim.x, p.total_tiles, p.reverse);
+        const unsigned lt = tile_index(i, ntile, p.total_tiles, p.reverse);
         const unsigned tm = lt / p.tiles_n;
         cc0 = (int)(lt - tm * p.tiles_n) * BN;
         const unsigned ng = tm / (unsigned)p.tiles_y;
@@ -114,10 +92,6 @@ __global__ __launch_bounds__(768, 1) void conv3x3_win_bf16_kernel(Win3Params p) 
     if (wave >= 8) {
         // =================================== loader waves 8..11 ===================================
         const int lw = wave - 8;
-        auto piece = [&](const __amdgpu_buffer_rsrc_t& r, unsigned lds_addr, unsigned voff) {
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(__builtin_amdgcn_readfirstlane(lds_addr)), "v"(voff), "s"(r)
-                         : "memory", "m0");
-        };
         const __amdgpu_buffer_rsrc_t rx = make_rsrc_sgpr(p.x, p.x_bytes);
         // weight pieces: rows lw * BPW * 8 .. of the tile's BN rows
         unsigned pvb[BPW];
@@ -140,7 +114,7 @@ __global__ __launch_bounds__(768, 1) void conv3x3_win_bf16_kernel(Win3Params p) 
                 const int wy = rem / p.PITCH, wx = rem - wy * p.PITCH;
                 const int n = tn0 + img, iy = ty0 - 1 + wy, ix = wx - 1;
                 const bool ok = pw < WP && n < p.N && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
-                wbase[s] = ok ? (unsigned)((n * p.H + iy) * p.W + ix) * (unsigned)(p.C * 2) + 16u * (unsigned)((lane & 7) ^ swz_key(w)) : 0x80000000u;
+                wbase[s] = ok ? (unsigned)((n * p.H + iy) * p.W + ix) * (unsigned)(p.C * 2) + 16u * (unsigned)((lane & 7) ^ swz_key(w)) : OOR;
             }
         };
         // issue window slots [s0, s0 + cnt) of the window with sequence number wq (buffer wq & 1), slab offset wsl; slots that do not
@@ -149,14 +123,14 @@ __global__ __launch_bounds__(768, 1) void conv3x3_win_bf16_kernel(Win3Params p) 
             constexpr int cnt = decltype(CNT)::value;      // (s0 is a constant after unrolling: wbase stays in registers)
             unsigned voff[cnt];
 #pragma unroll
-            for (int s = 0; s < cnt; ++s) voff[s] = live ? wbase[s0 + s] + wsl * 128u : 0x80000000u;
+            for (int s = 0; s < cnt; ++s) voff[s] = live ? wbase[s0 + s] + wsl * 128u : OOR;
 #pragma unroll
             for (int s = 0; s < cnt; ++s) asm volatile("" : "+v"(voff[s]));
 #pragma unroll
             for (int s = 0; s < cnt; ++s) {
                 const int pw = lw + 4 * (s0 + s);
                 const unsigned dst = (live && pw < WP) ? lds0 + (wq & 1u) * WIN_BYTES + (unsigned)pw * 1024u : lds0 + DUMMY_OFF;
-                piece(rx, dst, voff[s]);
+                dma_piece(rx, dst, voff[s]);
             }
         };
         // weights of one step: tile's channel origin cc0, K offset (tap * CS + slab) * 128
@@ -180,7 +154,7 @@ __global__ __launch_bounds__(768, 1) void conv3x3_win_bf16_kernel(Win3Params p) 
         unsigned ci = 0;                                        // tile the MFMA waves are on (for the epilogue constants)
         unsigned ckt = 0;
         unsigned k = 0;
-        W3_STAMP_DECL;
+        BF16_STAMP_DECL;
         for (unsigned q = 0; q <= nq; ++q) {
             const bool next_live = q + 1 < nq;                  // window q + 1 exists
 #pragma unroll
@@ -192,9 +166,7 @@ __global__ __launch_bounds__(768, 1) void conv3x3_win_bf16_kernel(Win3Params p) 
                     tile_origin(ci, tn0, ty0, mm0, e_c0);
                     const __amdgpu_buffer_rsrc_t rd = make_rsrc_sgpr(p.scale + e_c0, (long long)(p.Cout - e_c0) * 4),
                                                  rs = make_rsrc_sgpr(p.shift + e_c0, (long long)(p.Cout - e_c0) * 4);
-                    const unsigned eb = lds0 + E_OFF + (ci & 1u) * 2048u;
-                    piece(rd, eb, lane < 32 ? 16u * lane : 0x80000000u);
-                    piece(rs, eb + 1024, lane >= 32 ? 16u * (unsigned)(lane - 32) : 0x80000000u);
+                    stage_scale_shift(rd, rs, lds0 + E_OFF + (ci & 1u) * 2048u, lane);
                 }
                 // window q + 1 during taps 2..7 (its buffer was last read by slab q - 1, whose final step retires at the barrier
                 // before issue step 9 q + 2), two slots per step
@@ -210,22 +182,22 @@ __global__ __launch_bounds__(768, 1) void conv3x3_win_bf16_kernel(Win3Params p) 
 #pragma unroll
                     for (int j = 0; j < BPW; ++j) asm volatile("" : "+v"(voff[j]));
 #pragma unroll
-                    for (int j = 0; j < BPW; ++j) piece(rw, base + (lw * BPW + j) * 1024, voff[j]);
+                    for (int j = 0; j < BPW; ++j) dma_piece(rw, base + (lw * BPW + j) * 1024, voff[j]);
                     ++pf_step;
                 }
                 ++k;
-                W3_STAMP(0);
+                BF16_STAMP(0);
                 if (k == 1) continue;      // (after the first issue step there is nothing to hand over yet)
                 if (t >= 2 && t <= 7) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(BPW + 2) : "memory");
                 else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(BPW) : "memory");
-                W3_STAMP(1);
+                BF16_STAMP(1);
                 __syncthreads();
-                W3_STAMP(2);
+                BF16_STAMP(2);
                 if (k >= 3 && ++ckt == 9u * (unsigned)CS) {
                     ckt = 0;
                     ++ci;
                     __syncthreads();                            // pause while the MFMA waves store the tile
-                    W3_STAMP(3);
+                    BF16_STAMP(3);
                 }
             }
             // the issue cursor moves to the next slab; the window after the next one is then (tile, slab) + 1
@@ -239,7 +211,7 @@ __global__ __launch_bounds__(768, 1) void conv3x3_win_bf16_kernel(Win3Params p) 
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        W3_STAMP_FLUSH;
+        BF16_STAMP_FLUSH(g_w3_stamps, 12);
         return;
     }
 
@@ -291,7 +263,7 @@ __global__ __launch_bounds__(768, 1) void conv3x3_win_bf16_kernel(Win3Params p) 
     unsigned ci = 0, g = 0;
     tile_origin(0, tn0, ty0, m0, c0);
     __syncthreads();                                        // (the loaders' first hand-over: window 0 and step 0 have landed)
-    W3_STAMP_DECL;
+    BF16_STAMP_DECL;
 
     auto mfma_block = [&](int rb, const bf16x8& x0, const bf16x8& x1, const bf16x8& w00, const bf16x8& w01, const bf16x8& w10, const bf16x8& w11) __attribute__((always_inline)) {
         acc[rb][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w00, x0, acc[rb][0], 0, 0, 0);
@@ -332,24 +304,21 @@ __global__ __launch_bounds__(768, 1) void conv3x3_win_bf16_kernel(Win3Params p) 
                 if (grp + PRE < RBW) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
             }
             ++g;
-            W3_STAMP(0);
+            BF16_STAMP(0);
             __syncthreads();                            // the next step's weights (and, at t == 8, the next window) have landed
-            W3_STAMP(1);
+            BF16_STAMP(1);
         }
         if (++slab_in_tile == (unsigned)CS) {
             slab_in_tile = 0;
             const long long yorg = ((long long)m0 * p.Cout + c0) * 2ll, ybytes = ((long long)(p.M - m0) * p.Cout - c0) * 2ll;
             const __amdgpu_buffer_rsrc_t ry = make_rsrc_sgpr((char*)p.y + yorg, ybytes);
             const __amdgpu_buffer_rsrc_t rr = make_rsrc_sgpr((const char*)p.res + yorg, p.res ? ybytes : 0);
-            f32x4 e_sc[2], e_sh[2];
+            ScaleShift e_c[2];
 #pragma unroll
-            for (int nb = 0; nb < 2; ++nb) {
-                e_sc[nb] = *(const f32x4*)(smem + E_OFF + (ci & 1u) * 2048 + (wn * 32 + 8 * lq + 4 * nb) * 4);
-                e_sh[nb] = *(const f32x4*)(smem + E_OFF + (ci & 1u) * 2048 + 1024 + 512 + (wn * 32 + 8 * lq + 4 * nb) * 4);
-            }
+            for (int nb = 0; nb < 2; ++nb) e_c[nb] = read_scale_shift(smem + E_OFF + (ci & 1u) * 2048, wn * 32 + 8 * lq + 4 * nb);
             // residual rows two row blocks ahead of their use (not all RBW at once: registers)
             auto res_load = [&](int rb) __attribute__((always_inline)) {
-                return bload16(rr, (row0 + 16 * rb) < NPIX ? yvoff : 0x80000000u, __builtin_amdgcn_readfirstlane((unsigned)(16 * rb) * (unsigned)p.Cout * 2u));
+                return bload16(rr, (row0 + 16 * rb) < NPIX ? yvoff : OOR, __builtin_amdgcn_readfirstlane((unsigned)(16 * rb) * (unsigned)p.Cout * 2u));
             };
             f32x4 rres[RBW];
             if (p.res) {
@@ -359,38 +328,20 @@ __global__ __launch_bounds__(768, 1) void conv3x3_win_bf16_kernel(Win3Params p) 
 #pragma unroll
             for (int rb = 0; rb < RBW; ++rb) {
                 if (p.res && rb + 2 < RBW) rres[rb + 2] = res_load(rb + 2);
-                float v[8];
-#pragma unroll
-                for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[4 * nb + e] = fmaf(acc[rb][nb][e], e_sc[nb][e], e_sh[nb][e]);
-                if (p.res) {
-#pragma unroll
-                    for (int d = 0; d < 4; ++d) {
-                        const unsigned rw2 = __float_as_uint(rres[rb][d]);
-                        v[2 * d] = bfround(v[2 * d]) + __uint_as_float(rw2 << 16);
-                        v[2 * d + 1] = bfround(v[2 * d + 1]) + __uint_as_float(rw2 & 0xFFFF0000u);
-                    }
-                }
-                f32x4 o;
-#pragma unroll
-                for (int d = 0; d < 4; ++d) {
-                    const float f0 = fminf(fmaxf(v[2 * d], p.act_lo), p.act_hi), f1 = fminf(fmaxf(v[2 * d + 1], p.act_lo), p.act_hi);
-                    o[d] = __uint_as_float(hsefr_pack_bf16x2(f0, f1));
-                }
+                const f32x4 o = epilogue8(acc[rb][0], acc[rb][1], e_c[0], e_c[1], p.res != nullptr, rres[rb], p.act_lo, p.act_hi);
                 // rows past the tile's pixels belong to the NEXT tile: an out-of-range offset drops them
-                bstore16_welded(o, ry, (row0 + 16 * rb) < NPIX ? yvoff : 0x80000000u,
+                bstore16_welded(o, ry, (row0 + 16 * rb) < NPIX ? yvoff : OOR,
                                 __builtin_amdgcn_readfirstlane((unsigned)(16 * rb) * (unsigned)p.Cout * 2u));
             }
             zero_acc();
             tile_origin(++ci, tn0, ty0, m0, c0);
-            W3_STAMP(2);
+            BF16_STAMP(2);
             __syncthreads();                            // lets the loaders go on
-            W3_STAMP(3);
+            BF16_STAMP(3);
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    W3_STAMP_FLUSH;
+    BF16_STAMP_FLUSH(g_w3_stamps, 12);
 }
 
 struct Win3Cfg { int rbw, waves_m, tr, img, pitch; };
@@ -427,10 +378,8 @@ int launch_w3(Win3Params& p, hipStream_t s) {
     constexpr int BN = (8 / WAVES_M) * 32;
     p.tiles_n = (unsigned)(p.Cout / BN);
     const long long tiles_m = (long long)((p.N + p.IMG - 1) / p.IMG) * p.tiles_y;
-    const long long total = tiles_m * p.tiles_n;
-    HSEFR_REQUIRE(total < (1ll << 31), HSEFR_ERR_UNSUPPORTED, "conv3x3_win: too many tiles");
-    p.total_tiles = (unsigned)total;
-    const unsigned g = (unsigned)(total < 256 ? total : 256);
+    unsigned g;
+    if (const int rc = persistent_grid(tiles_m * p.tiles_n, "conv3x3_win", &p.total_tiles, &g)) return rc;
     HSEFR_LAUNCH((conv3x3_win_bf16_kernel<RBW, WAVES_M>), dim3(g), dim3(768), 0, s, p);
     return launch_status("conv3x3_win_bf16");
 }
@@ -438,17 +387,7 @@ int launch_w3(Win3Params& p, hipStream_t s) {
 }  // namespace
 
 #ifdef HSEFR_DEV
-int read_w3_stamps(void* host_out, size_t bytes) {
-#ifdef HSEFR_CD_STAMPS
-    HSEFR_REQUIRE(bytes <= sizeof(unsigned long long) * 256 * 12 * 8, HSEFR_ERR_INVALID, "read_w3_stamps: too many bytes");
-    HSEFR_HIP_CHECK(hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_w3_stamps), bytes));
-    return HSEFR_OK;
-#else
-    (void)host_out; (void)bytes;
-    set_error("read_w3_stamps: library built without -DHSEFR_CD_STAMPS");
-    return HSEFR_ERR_UNSUPPORTED;
-#endif
-}
+int read_w3_stamps(void* host_out, size_t bytes) { return read_stamps_impl(BF16_STAMP_SYMBOL(g_w3_stamps), "read_w3_stamps", host_out, bytes); }
 #endif
 
 bool conv3x3_win_forced() { return g_w3_off == 2; }
@@ -464,15 +403,13 @@ bool conv3x3_win_bf16_supported(long long n, int h, int w, int c, int cout) {
 int launch_conv3x3_win_bf16(const void* x, const void* wt, const float* scale, const float* shift, const void* res, void* y, int n, int h,
                             int w, int c, int cout, int act, hipStream_t s) {
     HSEFR_REQUIRE(conv3x3_win_bf16_supported(n, h, w, c, cout), HSEFR_ERR_UNSUPPORTED, "conv3x3_win_bf16: shape not covered");
-    HSEFR_REQUIRE(act == HSEFR_ACT_NONE || act == HSEFR_ACT_RELU || act == HSEFR_ACT_RELU6, HSEFR_ERR_UNSUPPORTED, "conv3x3_win_bf16: act %d", act);
     const Win3Cfg cfg = choose_win3(n, h, w, cout);
     Win3Params p;
     p.x = x; p.wt = wt; p.scale = scale; p.shift = shift; p.res = res; p.y = y;
     p.x_bytes = (long long)n * h * w * c * 2;
     p.N = n; p.H = h; p.W = w; p.C = c; p.Cout = cout;
     p.TR = cfg.tr; p.IMG = cfg.img; p.PITCH = cfg.pitch; p.tiles_y = h / cfg.tr;
-    p.act_lo = act == HSEFR_ACT_NONE ? -INFINITY : 0.f;
-    p.act_hi = act == HSEFR_ACT_RELU6 ? 6.f : INFINITY;
+    if (const int rc = act_bounds(act, "conv3x3_win_bf16", &p.act_lo, &p.act_hi)) return rc;
     p.M = (unsigned)((long long)n * h * w);
     p.reverse = sweep_reverse();
     if (cfg.waves_m == 2) return cfg.rbw == 7 ? launch_w3<7, 2>(p, s) : launch_w3<4, 2>(p, s);

@@ -24,44 +24,15 @@
 //     for Cout = 64; RB is picked per layer so that the tiles fill whole rounds of 256 workgroups (ResNet-50 at batch 128 has
 //     M = 49 * 2^k pixels: 25088 x 256 is 224 tiles of 224 x 128, one round on 7/8 of the chip).
 // Every output element is accumulated over K in one fixed order by one wave: bit-identical run to run, independent of the grid.
-#include "common.h"
+#include "bf16_dma.h"
 
 namespace hsefr {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
+using namespace bf16_dma;
 
-constexpr int ROWB = 128;       // bytes per LDS row: 64 bf16 = one K-step
-
-#ifdef HSEFR_CD_STAMPS
-// Diagnostic build only (HSEFR_DEV=1 HSEFR_EXTRA_FLAGS=-DHSEFR_CD_STAMPS build.sh): per-wave s_memtime sums of the step phases.
-__device__ unsigned long long g_cd_stamps[256 * 12 * 8];
-#define CD_STAMP(i) do { const unsigned long long _t = __builtin_amdgcn_s_memtime(); st[i] += _t - tprev; tprev = _t; } while (0)
-#define CD_STAMP_DECL unsigned long long st[6] = {0, 0, 0, 0, 0, 0}; unsigned long long tprev = __builtin_amdgcn_s_memtime(); const unsigned long long tstart = tprev
-#define CD_STAMP_FLUSH do { if (lane == 0 && blockIdx.x < 256) { unsigned long long* o = g_cd_stamps + (blockIdx.x * 12 + wave) * 8; \
-    for (int i_ = 0; i_ < 6; ++i_) o[i_] = st[i_]; o[6] = __builtin_amdgcn_s_memtime() - tstart; o[7] = nsteps; } } while (0)
-#else
-#define CD_STAMP(i) do { } while (0)
-#define CD_STAMP_DECL do { } while (0)
-#define CD_STAMP_FLUSH do { } while (0)
-#endif
-
-__device__ __forceinline__ int swz_key(int row) { return ((row >> 1) & 7) ^ ((row & 1) << 2); }
-__device__ __forceinline__ unsigned f2bf_bits(float f) { return hsefr_bf16_bits(f); }      // round-to-nearest-even (common.h)
-__device__ __forceinline__ float bfround(float f) { return __uint_as_float(f2bf_bits(f) << 16); }
-
-// A buffer resource whose words are pinned to SGPRs: the inline-asm DMA / store take it under an "s" constraint, and with the
-// parameter block behind by-reference lambdas hipcc otherwise keeps (selects between) resources in VGPRs -- which assembles to
-// an invalid instruction, not to a waterfall loop.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc_sgpr(const void* ptr, long long bytes) {
-    const unsigned long long a = (unsigned long long)ptr;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-    const unsigned n = __builtin_amdgcn_readfirstlane(bytes <= 0 ? 0u : (bytes > 0xffffffffll ? 0xffffffffu : (unsigned)bytes));
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)hi << 32) | lo), 0, n, 0x00020000);
-}
+BF16_STAMP_ARRAY(g_cd_stamps, 12);
 
 struct ConvDmaParams {
     const void* x;       // [N,H,W,C] bf16
@@ -97,12 +68,12 @@ __global__ __launch_bounds__(768, 1) void conv_dma_bf16_kernel(ConvDmaParams p) 
     const int CS = p.C / 64;                        // channel slabs per tap
     const int KT = p.KH * p.KW * CS;
     if (blockIdx.x >= p.total_tiles) return;
-    const unsigned ntile = (p.total_tiles - blockIdx.x + gridDim.x - 1) / gridDim.x;
+    const unsigned ntile = tiles_of_workgroup(p.total_tiles);
     const unsigned nsteps = ntile * KT;
     const unsigned wrowbytes = (unsigned)KT * 128u;
 
     auto tile_origin = [&](unsigned i, unsigned& mm0, int& nn0) __attribute__((always_inline)) {
-        const unsigned lt = xcd_remap_dir(blockIdx.x + (i < ntile ? i : ntile - 1) * gridDim.x, p.total_tiles, p.reverse);
+        const unsigned lt = tile_index(i, ntile, p.total_tiles, p.reverse);
         const unsigned tm = lt / p.tiles_n;
         mm0 = tm * BM;
         nn0 = (int)(lt - tm * p.tiles_n) * BN;
@@ -122,11 +93,6 @@ __global__ __launch_bounds__(768, 1) void conv_dma_bf16_kernel(ConvDmaParams p) 
             const int r = (lw * BPW + j) * 8 + (lane >> 3);
             pvb[j] = (unsigned)r * wrowbytes + 16u * (unsigned)((lane & 7) ^ swz_key(r));
         }
-        auto piece = [&](const __amdgpu_buffer_rsrc_t& r, unsigned lds_addr, unsigned voff, unsigned soff) {
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(__builtin_amdgcn_readfirstlane(lds_addr)), "v"(voff),
-                         "s"(r), "s"(__builtin_amdgcn_readfirstlane(soff))
-                         : "memory", "m0");
-        };
         unsigned pf_i = 0, pf_step = 0;
         int pf_kt = 0, pf_tap = 0, pf_cs = 0, pf_kh = 0, pf_kw = 0, pf_n0 = 0;
         const unsigned ohow = (unsigned)(p.OH * p.OW);
@@ -166,15 +132,15 @@ __global__ __launch_bounds__(768, 1) void conv_dma_bf16_kernel(ConvDmaParams p) 
             // instead of 8 neighbouring pixels were tried: no effect on the issue rate)
             unsigned voff[PPW];
 #pragma unroll
-            for (int j = 0; j < APW; ++j) voff[j] = ((pmask[j] >> pf_tap) & 1u) ? pbase[j] + a_adv : 0x80000000u;
+            for (int j = 0; j < APW; ++j) voff[j] = ((pmask[j] >> pf_tap) & 1u) ? pbase[j] + a_adv : OOR;
 #pragma unroll
             for (int j = 0; j < BPW; ++j) voff[APW + j] = pvb[j] + b_adv;
 #pragma unroll
             for (int j = 0; j < PPW; ++j) asm volatile("" : "+v"(voff[j]));
 #pragma unroll
-            for (int j = 0; j < APW; ++j) piece(rx, base + (lw * APW + j) * 1024, voff[j], 0u);
+            for (int j = 0; j < APW; ++j) dma_piece(rx, base + (lw * APW + j) * 1024, voff[j], 0u);
 #pragma unroll
-            for (int j = 0; j < BPW; ++j) piece(rw, base + BM * ROWB + (lw * BPW + j) * 1024, voff[APW + j], 0u);
+            for (int j = 0; j < BPW; ++j) dma_piece(rw, base + BM * ROWB + (lw * BPW + j) * 1024, voff[APW + j], 0u);
             ++pf_step;
             ++pf_kt;
             ++pf_tap;
@@ -193,34 +159,31 @@ __global__ __launch_bounds__(768, 1) void conv_dma_bf16_kernel(ConvDmaParams p) 
         int ckt = 0;
         // k counts ISSUED steps: step k goes out, then (k >= 1) step k - 1 is waited for and handed over at the barrier; the MFMA
         // waves work on step k - 2.  One call site of issue_step: the per-tile address decode is inlined once.
-        CD_STAMP_DECL;
+        BF16_STAMP_DECL;
         for (unsigned k = 0; k < nsteps + 2; ++k) {
             if (k >= 2 && ckt == 0 && lw == 3) {
-                // the tile's epilogue constants by LDS-DMA: scale[n0 .. n0 + 127] as lanes 0-31 of one piece, shift[..] as lanes
-                // 32-63 of a second one; issued AHEAD of this step's pieces so the counted wait covers them; two copies by tile parity
+                // the tile's epilogue constants, issued AHEAD of this step's pieces so the counted wait covers them; two copies by tile parity
                 const __amdgpu_buffer_rsrc_t rd = make_rsrc_sgpr(p.scale + e_n0, (long long)(p.Cout - e_n0) * 4),
                                              rs = make_rsrc_sgpr(p.shift + e_n0, (long long)(p.Cout - e_n0) * 4);
-                const unsigned eb = lds0 + E_OFF + (ci & 1u) * 2048u;
-                piece(rd, eb, lane < 32 ? 16u * lane : 0x80000000u, 0u);
-                piece(rs, eb + 1024, lane >= 32 ? 16u * (unsigned)(lane - 32) : 0x80000000u, 0u);
+                stage_scale_shift(rd, rs, lds0 + E_OFF + (ci & 1u) * 2048u, lane);
             }
             issue_step();
-            CD_STAMP(0);
+            BF16_STAMP(0);
             if (k == 0) continue;
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW) : "memory");   // step k - 1 (and the constants) have landed: vmcnt retires in order
-            CD_STAMP(1);
+            BF16_STAMP(1);
             __syncthreads();
-            CD_STAMP(2);
+            BF16_STAMP(2);
             if (k >= 2 && ++ckt == KT) {
                 ckt = 0;
                 unsigned mm0;
                 tile_origin(++ci, mm0, e_n0);
                 __syncthreads();                            // pause while the MFMA waves store the tile
-                CD_STAMP(3);
+                BF16_STAMP(3);
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        CD_STAMP_FLUSH;
+        BF16_STAMP_FLUSH(g_cd_stamps, 12);
         return;
     }
 
@@ -254,7 +217,7 @@ __global__ __launch_bounds__(768, 1) void conv_dma_bf16_kernel(ConvDmaParams p) 
     int ckt = 0;
     tile_origin(0, m0, n0);
     __syncthreads();                                        // (the loaders' prologue barrier: step 0 has landed)
-    CD_STAMP_DECL;
+    BF16_STAMP_DECL;
 
     constexpr int HB = RB >= 4 ? 2 : 1;                     // row blocks whose MFMAs are held back behind the step barrier
     const bf16x8 fzero = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -292,9 +255,9 @@ __global__ __launch_bounds__(768, 1) void conv_dma_bf16_kernel(ConvDmaParams p) 
 #pragma unroll
         for (int i = 0; i < HB; ++i) { h_a0[i] = a0[RB - HB + i]; h_a1[i] = a1[RB - HB + i]; }
         h_b00 = b00; h_b01 = b01; h_b10 = b10; h_b11 = b11;
-        CD_STAMP(0);
+        BF16_STAMP(0);
         __syncthreads();                                // step g + 1 has landed; slot g % 3 is released
-        CD_STAMP(1);
+        BF16_STAMP(1);
         if (++ckt == KT) {
 #pragma unroll
             for (int i = 0; i < HB; ++i) mfma_block(RB - HB + i, h_a0[i], h_a1[i], h_b00, h_b01, h_b10, h_b11);
@@ -313,11 +276,16 @@ __global__ __launch_bounds__(768, 1) void conv_dma_bf16_kernel(ConvDmaParams p) 
             f32x4 e_sc[2], e_sh[2];
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb) {
-                e_sc[nb] = *(const f32x4*)(smem + E_OFF + (ci & 1u) * 2048 + (wn * 32 + 8 * lq + 4 * nb) * 4);
-                e_sh[nb] = *(const f32x4*)(smem + E_OFF + (ci & 1u) * 2048 + 1024 + 512 + (wn * 32 + 8 * lq + 4 * nb) * 4);
+                const ScaleShift c = read_scale_shift(smem + E_OFF + (ci & 1u) * 2048, wn * 32 + 8 * lq + 4 * nb);
+                e_sc[nb] = c.sc;
+                e_sh[nb] = c.sh;
             }
 #pragma unroll
             for (int rb = 0; rb < RB; ++rb) {
+                // (scale_shift8 / add_residual8 spelled out, on constants in two arrays: through the shared functions, or with the constants
+                // kept as ScaleShift, hipcc pairs the two roundings of a residual word into one v_cvt_pk_bf16_f32; the epilogue shrinks by
+                // ~200 bytes and the loader loop behind it moves -- same bits, but the RB = 4 tiles measured 2 % slower on the layers the
+                // product routes here.  In this form every instantiation keeps the text it had, but for s_or in place of s_add.)
                 float v[8];
 #pragma unroll
                 for (int nb = 0; nb < 2; ++nb)
@@ -326,29 +294,24 @@ __global__ __launch_bounds__(768, 1) void conv_dma_bf16_kernel(ConvDmaParams p) 
                 if (p.res) {
 #pragma unroll
                     for (int d = 0; d < 4; ++d) {
-                        const unsigned rw2 = __float_as_uint(rres[rb][d]);
-                        v[2 * d] = bfround(v[2 * d]) + __uint_as_float(rw2 << 16);
-                        v[2 * d + 1] = bfround(v[2 * d + 1]) + __uint_as_float(rw2 & 0xFFFF0000u);
+                        const unsigned rw = __float_as_uint(rres[rb][d]);
+                        v[2 * d] = bfround(v[2 * d]) + __uint_as_float(rw << 16);
+                        v[2 * d + 1] = bfround(v[2 * d + 1]) + __uint_as_float(rw & 0xFFFF0000u);
                     }
                 }
-                f32x4 o;
-#pragma unroll
-                for (int d = 0; d < 4; ++d) {
-                    const float f0 = fminf(fmaxf(v[2 * d], p.act_lo), p.act_hi), f1 = fminf(fmaxf(v[2 * d + 1], p.act_lo), p.act_hi);
-                    o[d] = __uint_as_float(hsefr_pack_bf16x2(f0, f1));
-                }
+                const f32x4 o = clamp_pack8(v, p.act_lo, p.act_hi);
                 bstore16_welded(o, ry, yvoff, __builtin_amdgcn_readfirstlane((unsigned)(16 * rb) * (unsigned)p.Cout * 2u));
             }
             zero_acc();
             ckt = 0;
             tile_origin(++ci, m0, n0);
-            CD_STAMP(2);
+            BF16_STAMP(2);
             __syncthreads();                            // lets the loaders go on
-            CD_STAMP(3);
+            BF16_STAMP(3);
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // stores issued from asm: drained before the wave ends
-    CD_STAMP_FLUSH;
+    BF16_STAMP_FLUSH(g_cd_stamps, 12);
 }
 
 struct DmaCfg { int waves_m, rb; };
@@ -381,10 +344,8 @@ int launch_cfg(ConvDmaParams& p, hipStream_t s) {
     constexpr int BM = WAVES_M * 16 * RB, BN = (8 / WAVES_M) * 32;
     const long long tiles_m = ((long long)p.M + BM - 1) / BM;
     p.tiles_n = (unsigned)(p.Cout / BN);
-    const long long total = tiles_m * p.tiles_n;
-    HSEFR_REQUIRE(total < (1ll << 31), HSEFR_ERR_UNSUPPORTED, "conv_dma_bf16: too many tiles");
-    p.total_tiles = (unsigned)total;
-    const unsigned g = (unsigned)(total < 256 ? total : 256);
+    unsigned g;
+    if (const int rc = persistent_grid(tiles_m * p.tiles_n, "conv_dma_bf16", &p.total_tiles, &g)) return rc;
     HSEFR_LAUNCH((conv_dma_bf16_kernel<RB, WAVES_M>), dim3(g), dim3(768), 0, s, p);
     return launch_status("conv_dma_bf16");
 }
@@ -392,17 +353,7 @@ int launch_cfg(ConvDmaParams& p, hipStream_t s) {
 }  // namespace
 
 #ifdef HSEFR_DEV
-int read_cd_stamps(void* host_out, size_t bytes) {
-#ifdef HSEFR_CD_STAMPS
-    HSEFR_REQUIRE(bytes <= sizeof(unsigned long long) * 256 * 12 * 8, HSEFR_ERR_INVALID, "read_cd_stamps: too many bytes");
-    HSEFR_HIP_CHECK(hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_cd_stamps), bytes));
-    return HSEFR_OK;
-#else
-    (void)host_out; (void)bytes;
-    set_error("read_cd_stamps: library built without -DHSEFR_CD_STAMPS");
-    return HSEFR_ERR_UNSUPPORTED;
-#endif
-}
+int read_cd_stamps(void* host_out, size_t bytes) { return read_stamps_impl(BF16_STAMP_SYMBOL(g_cd_stamps), "read_cd_stamps", host_out, bytes); }
 #endif
 
 bool conv_dma_forced() { return g_cd_off == 2; }
@@ -422,9 +373,7 @@ int launch_conv_dma_bf16(const void* x, const void* wt, const float* scale, cons
     p.x = x; p.wt = wt; p.scale = scale; p.shift = shift; p.res = res; p.y = y;
     p.x_bytes = (long long)n * h * w * c * 2;
     p.H = h; p.W = w; p.C = c; p.OH = oh; p.OW = ow; p.Cout = cout; p.KH = kh; p.KW = kw; p.stride = stride; p.pad_t = pad_t; p.pad_l = pad_l;
-    p.act_lo = act == HSEFR_ACT_NONE ? -INFINITY : 0.f;
-    p.act_hi = act == HSEFR_ACT_RELU6 ? 6.f : INFINITY;
-    HSEFR_REQUIRE(act == HSEFR_ACT_NONE || act == HSEFR_ACT_RELU || act == HSEFR_ACT_RELU6, HSEFR_ERR_UNSUPPORTED, "conv_dma_bf16: act %d", act);
+    if (const int rc = act_bounds(act, "conv_dma_bf16", &p.act_lo, &p.act_hi)) return rc;
     p.M = (unsigned)((long long)n * oh * ow);
     p.reverse = sweep_reverse();
     const DmaCfg cfg = choose_cfg(p.M, cout, g_cd_rb);
