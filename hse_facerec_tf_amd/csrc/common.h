@@ -320,6 +320,11 @@ int launch_dwpw_f16s(const float* x, const float* wd, const float* dscale, const
 bool dwpw_f16s_supported(int c, int cout, int stride);
 bool dwpw_s2_covered(int c, int cout, int stride);      // the stride-2 block kernel of dwpw_f16s.hip (what HSEFR_OPF_DWPW_NEXT runs)
 bool dwpw_s2_off();                                     // dev builds: the "dwpw_s2_off" knob (always false in the product)
+// conv_pw_2 + the 48 x 48 block as one row-streaming launch (csrc/pwblk_stream.hip: what HSEFR_OPF_PWBLK_NEXT runs); segs 0 = automatic
+bool pwblk_covered(int cin, int cmid, int cout, int w);
+int launch_pwblk_f16s(const float* x, const void* w2split, const float* descale2, const float* shift2, const float* wd, const float* dscale,
+                      const float* dshift, const void* w3split, const float* descale3, const float* shift3, float* y, int n, int h, int w,
+                      int a_log2, int a_log2_blk, int act, int segs, hipStream_t s);
 int launch_stem_fused(const float* x, const float* cw, const float* cshift, const float* wd, const float* dscale,
                       const float* dshift, const void* wsplit, const float* descale, const float* pshift, float* y, int n,
                       int h, int w, int cpad_t, int cpad_l, int oh, int ow, int a_log2, int act, hipStream_t s);

@@ -324,7 +324,7 @@ static int validate_plan(const hsefr_plan_header& h, const hsefr_plan_buffer* bu
     // launch-level fusions (hsefr_op_flags): the pattern behind a flagged op must be exactly the one its fused launch computes
     for (uint32_t i = 0; i < h.n_ops; ++i) {
         const hsefr_plan_op& o = ops[i];
-        HSEFR_REQUIRE((o.flags & ~(HSEFR_OPF_PAIR_NEXT | HSEFR_OPF_HEADS | HSEFR_OPF_OUT_SUB2 | HSEFR_OPF_DWPW_NEXT)) == 0, HSEFR_ERR_INVALID,
+        HSEFR_REQUIRE((o.flags & ~(HSEFR_OPF_PAIR_NEXT | HSEFR_OPF_HEADS | HSEFR_OPF_OUT_SUB2 | HSEFR_OPF_DWPW_NEXT | HSEFR_OPF_PWBLK_NEXT)) == 0, HSEFR_ERR_INVALID,
                       "plan op %u: unknown flags 0x%x", i, o.flags);
         HSEFR_REQUIRE(!(o.flags & HSEFR_OPF_OUT_SUB2) || (o.flags & HSEFR_OPF_PAIR_NEXT), HSEFR_ERR_INVALID, "plan op %u: OUT_SUB2 without PAIR_NEXT", i);
         if (o.flags & HSEFR_OPF_PAIR_NEXT) {
@@ -374,6 +374,33 @@ static int validate_plan(const hsefr_plan_header& h, const hsefr_plan_buffer* bu
             for (int sl = 0; sl < HSEFR_N_OUTPUT_SLOTS; ++sl)
                 HSEFR_REQUIRE(h.out_buffer[sl] != o.out_buf && (b.out_buf != o.in_buf || h.out_buffer[sl] != o.in_buf), HSEFR_ERR_INVALID,
                               "plan op %u: DWPW_NEXT: the depthwise tensor (or the buffer it exchanges roles with) is output slot %d", i, sl);
+        }
+        if (o.flags & HSEFR_OPF_PWBLK_NEXT) {
+            HSEFR_REQUIRE(o.flags == HSEFR_OPF_PWBLK_NEXT && i + 1 < h.n_ops, HSEFR_ERR_INVALID, "plan op %u: PWBLK_NEXT on the last op or beside another flag", i);
+            const hsefr_plan_op& b = ops[i + 1];
+            HSEFR_REQUIRE(o.kind == HSEFR_OP_PWCONV_F16S && o.act == HSEFR_ACT_RELU6 && o.res_buf == HSEFR_BUF_NONE && o.aux > 0 && o.aux <= 12 &&
+                              b.kind == HSEFR_OP_DWPW_F16S && b.stride == 1 && b.pad_t == 1 && b.pad_l == 1 && b.in_buf == o.out_buf && b.flags == 0 &&
+                              b.h == o.h && b.w == o.w && b.oh == b.h && b.ow == b.w && b.cin == o.cout,
+                          HSEFR_ERR_INVALID, "plan op %u: PWBLK_NEXT needs a split-f16 pointwise op with ReLU6 and no residual (a_log2 in [1, 12]), and behind "
+                          "it a stride-1 split-f16 depthwise-pointwise block without flags that reads it at the same pixels", i);
+            HSEFR_REQUIRE(pwblk_covered(o.cin, o.cout, b.cout, o.w), HSEFR_ERR_INVALID,
+                          "plan op %u: PWBLK_NEXT %d -> %d -> %d channels on rows of %d pixels not covered (64 -> 128 -> 128, at most 48)", i, o.cin, o.cout,
+                          b.cout, o.w);
+            HSEFR_REQUIRE(b.out_buf != o.out_buf, HSEFR_ERR_INVALID, "plan op %u: PWBLK_NEXT: the second output (buffer %d) aliases the pointwise tensor", i,
+                          b.out_buf);
+            // as for DWPW_NEXT: where the block's output recycles the pointwise INPUT's buffer, the one launch writes into the (unwritten)
+            // pointwise tensor's buffer and the forward goes on with the two buffers' roles exchanged (launch_op)
+            HSEFR_REQUIRE(b.out_buf != o.in_buf || (o.in_buf >= 0 && (uint64_t)bufs[o.in_buf].elems_per_image * bufs[o.in_buf].elem_bytes ==
+                                                                        (uint64_t)bufs[o.out_buf].elems_per_image * bufs[o.out_buf].elem_bytes),
+                          HSEFR_ERR_INVALID, "plan op %u: PWBLK_NEXT: buffers %d and %d exchange roles and must have one size", i, o.in_buf, o.out_buf);
+            for (uint32_t k = i + 2; k < h.n_ops; ++k) {
+                HSEFR_REQUIRE(ops[k].in_buf != o.out_buf && ops[k].res_buf != o.out_buf, HSEFR_ERR_INVALID,
+                              "plan op %u: PWBLK_NEXT: op %u also reads the pointwise tensor (buffer %d)", i, k, o.out_buf);
+                if (ops[k].out_buf == o.out_buf) break;
+            }
+            for (int sl = 0; sl < HSEFR_N_OUTPUT_SLOTS; ++sl)
+                HSEFR_REQUIRE(h.out_buffer[sl] != o.out_buf && (b.out_buf != o.in_buf || h.out_buffer[sl] != o.in_buf), HSEFR_ERR_INVALID,
+                              "plan op %u: PWBLK_NEXT: the pointwise tensor (or the buffer it exchanges roles with) is output slot %d", i, sl);
         }
         if (o.flags & HSEFR_OPF_HEADS) {
             HSEFR_REQUIRE(i + 3 < h.n_ops, HSEFR_ERR_INVALID, "plan op %u: HEADS needs three ops behind it", i);
@@ -698,8 +725,8 @@ static Operands operands(const hsefr_engine* e, const hsefr_plan_op& o) {
 
 // Launch op i of a forward for a batch of n on stream s: THE place that decides which launch serves a plan op.  `covered` = the ops behind
 // it that the launch computed as well (hsefr_op_flags; their patterns were checked by validate_plan): the caller goes on behind them.
-// tab: the forward's own buffer table (a DWPW_NEXT launch may exchange two buffers' roles in it).  every_tensor: the all-layers debug
-// forward -- a launch that would leave a tensor of the plan unwritten (HSEFR_OPF_DWPW_NEXT) is not used.
+// tab: the forward's own buffer table (a DWPW_NEXT or PWBLK_NEXT launch may exchange two buffers' roles in it).  every_tensor: the all-layers debug
+// forward -- a launch that would leave a tensor of the plan unwritten (HSEFR_OPF_DWPW_NEXT, HSEFR_OPF_PWBLK_NEXT) is not used.
 static int launch_op(hsefr_engine* e, size_t i, std::vector<void*>& tab, const void* d_input, int n, const std::vector<char>& needed, hipStream_t s,
                      bool input_u8, bool every_tensor, size_t& covered) {
     const hsefr_plan_op& o = e->ops[i];
@@ -745,6 +772,17 @@ static int launch_op(hsefr_engine* e, size_t i, std::vector<void*>& tab, const v
         covered = 1;
         return launch_dwpw_f16s((const float*)in, (const float*)p.w, p.scale, p.shift, pb.w, pb.scale, pb.shift, (float*)tab[b.out_buf], n, o.h, o.w,
                                 o.cin, o.stride, o.pad_t, o.pad_l, o.oh, o.ow, b.cout, b.aux, b.act, s);
+    }
+    if ((o.flags & HSEFR_OPF_PWBLK_NEXT) && !every_tensor && needed[i + 1]) {
+        // conv_pw_2 -> the stride-1 depthwise-pointwise block in one row-streaming launch (csrc/pwblk_stream.hip): the pointwise tensor stays
+        // in LDS and its buffer is not written.  Where the plan recycles the launch's INPUT buffer for the block's output, the result goes
+        // into the pointwise tensor's buffer and from here on the two buffers stand for each other (validate_plan)
+        const hsefr_plan_op& b = e->ops[i + 1];
+        const Operands pb = operands(e, b);
+        if (b.out_buf == o.in_buf) std::swap(tab[o.in_buf], tab[o.out_buf]);
+        covered = 1;
+        return launch_pwblk_f16s((const float*)in, p.w, p.scale, p.shift, (const float*)pb.w, pb.scale, pb.shift, pb.w2, pb.shift2, pb.shift2 + b.cout,
+                                 (float*)tab[b.out_buf], n, o.h, o.w, o.aux, b.aux, b.act, 0, s);
     }
     const void* res = o.res_buf >= 0 ? tab[o.res_buf] : nullptr;
     switch (o.kind) {
@@ -1168,6 +1206,21 @@ int hsefr_dwpw_f16split(const float* x, const float* wd, const float* dscale, co
                   "dwpw_f16split: null pointer");
     return launch_dwpw_f16s(x, wd, dscale, dshift, w_split, descale, pshift, y, n, h, w, c, stride, pad_t, pad_l, oh, ow, cout,
                             a_log2, act, (hipStream_t)stream);
+}
+
+int hsefr_pwblk_f16split(const float* x, const void* w2_split, const float* descale2, const float* shift2, const float* wd, const float* dscale,
+                         const float* dshift, const void* w3_split, const float* descale3, const float* shift3, float* mid, float* y, int n, int h,
+                         int w, int cin, int cmid, int cout, int a_log2, int a_log2_blk, int act, int segs, hsefr_stream_t stream) {
+    HSEFR_REQUIRE(n == 0 || (x && w2_split && descale2 && shift2 && wd && dscale && dshift && w3_split && descale3 && shift3 && y), HSEFR_ERR_INVALID,
+                  "pwblk_f16split: null pointer");
+    if (pwblk_covered(cin, cmid, cout, w))
+        return launch_pwblk_f16s(x, w2_split, descale2, shift2, wd, dscale, dshift, w3_split, descale3, shift3, y, n, h, w, a_log2, a_log2_blk, act, segs,
+                                 (hipStream_t)stream);
+    // a shape the streaming launch does not cover: the two launches it stands for, through `mid`
+    HSEFR_REQUIRE(n == 0 || mid, HSEFR_ERR_INVALID, "pwblk_f16split: %d -> %d -> %d channels on rows of %d pixels take two launches and need `mid`", cin, cmid,
+                  cout, w);
+    if (int rc = launch_pwconv_f16s(x, w2_split, descale2, shift2, mid, (long long)n * h * w, cin, cmid, a_log2, HSEFR_ACT_RELU6, (hipStream_t)stream)) return rc;
+    return launch_dwpw_f16s(mid, wd, dscale, dshift, w3_split, descale3, shift3, y, n, h, w, cmid, 1, 1, 1, h, w, cout, a_log2_blk, act, (hipStream_t)stream);
 }
 
 int hsefr_dwpw_fused(const float* x, const float* wd, const float* dscale, const float* dshift, const float* wp_t,

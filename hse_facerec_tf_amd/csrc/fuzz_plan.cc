@@ -66,8 +66,9 @@ static void run_one(const void* blob, size_t bytes, const char* what) {
 int main(int argc, char** argv) {
     if (argc < 3) { fprintf(stderr, "usage: fuzz_plan <mutants per seed> <plan file>...\n"); return 2; }
     const long long per_seed = atoll(argv[1]);
-    // (8 = HSEFR_OPF_DWPW_NEXT: a flags word set to it, or the fields around a seed's own flagged depthwise, reach that branch of validate_plan)
-    static const int32_t edge32[] = {0, 1, -1, -2, -3, 2, 3, 7, 8, 63, 64, 65, 127, 128, 255, 256, 511, 512, 4095, 4096, 65535, 65536, 0x7fffffff,
+    // (8 = HSEFR_OPF_DWPW_NEXT, 16 = HSEFR_OPF_PWBLK_NEXT: a flags word set to one of them, or the fields around a seed's own flagged depthwise /
+    // pointwise op -- conv_dw_4 and conv_pw_2 of the MobileNet seeds -- reach those branches of validate_plan; 48 and 49 sit on the row bound)
+    static const int32_t edge32[] = {0, 1, -1, -2, -3, 2, 3, 7, 8, 16, 24, 48, 49, 63, 64, 65, 127, 128, 255, 256, 511, 512, 4095, 4096, 65535, 65536, 0x7fffffff,
                                      (int32_t)0x80000000, (int32_t)0xffff0000, 1 << 20, 1 << 24, 1 << 30};
     static const uint64_t edge64[] = {0ull, 1ull, 15ull, 16ull, 17ull, 0xffffffffull, 0x100000000ull, 0x7fffffffffffffffull, 0x8000000000000000ull,
                                       0xffffffffffffffffull, 0xfffffffffffffff0ull};

@@ -170,7 +170,7 @@ class Engine:
 
     def layer_output(self, layer_index: int, n: int):
         """Copy of a layer's activation buffer as a CUDA tensor [n, oh, ow, c].  Only meaningful
-        right after the op ran and before a later op recycled the buffer -- and, in a plan with an OPF_DWPW_NEXT layer, after
+        right after the op ran and before a later op recycled the buffer -- and, in a plan with an OPF_DWPW_NEXT or OPF_PWBLK_NEXT layer, after
         forward_all_layers only (a forward with outputs may exchange two buffers' roles).  A layer whose result is stored as split
         rows for the GEMM behind it (Layer.out_split) is decoded back to fp32 values."""
         torch = self._torch

@@ -48,7 +48,7 @@ NO_OFFSET = 0xFFFFFFFFFFFFFFFF
 _HEADER = struct.Struct("<QIIIIII3i3IQ")          # hsefr_plan_header
 _BUFFER = struct.Struct("<QII")                   # hsefr_plan_buffer
 _OP = struct.Struct("<II3i3i3i3i2iii5Q")         # hsefr_plan_op (112 bytes; `flags` sits where the struct's padding was until round 6)
-OPF_PAIR_NEXT, OPF_HEADS, OPF_OUT_SUB2, OPF_DWPW_NEXT = 1, 2, 4, 8  # hsefr_op_flags
+OPF_PAIR_NEXT, OPF_HEADS, OPF_OUT_SUB2, OPF_DWPW_NEXT, OPF_PWBLK_NEXT = 1, 2, 4, 8, 16  # hsefr_op_flags
 # hsefr_plan_op.aux: the geometry word (shift, width of each field), PWCONV_PS_DW's out_log2, STEM3_F16S's in_log2 and uint8 bit,
 # STEM7X7_POOL_BF16's pool pads
 AUX_C2_SHIFT, AUX_C2_BITS, AUX_STRIDE2_SHIFT, AUX_STRIDE2_BITS = 0, 12, 12, 2
@@ -71,7 +71,7 @@ PRODUCT_KERNEL_FAMILIES = frozenset({
     # MobileNet (fp32-grade): stems, depthwise, pointwise GEMMs, fused blocks, pool, heads
     "stem5_stream_kernel", "stem4_fused_kernel", "stem3_fused_kernel", "stem2_fused_kernel", "conv3x3_c3_kernel", "conv3x3_c3_mfma_kernel",
     "dwconv3x3_kernel", "pwconv_f32_dma_kernel", "pwconv_f32_kernel", "pwconv_f16s_kernel", "pwconv_ps_kernel", "dwpw_fused_kernel",
-    "dwpw_f16s_kernel", "dwpw2_f16s_kernel", "dwpw3_f16s_kernel", "dwpws2_f16s_kernel", "gap_kernel", "dense_kernel", "softmax_kernel", "heads_kernel",
+    "dwpw_f16s_kernel", "dwpw2_f16s_kernel", "dwpw3_f16s_kernel", "dwpws2_f16s_kernel", "pwblk_stream_f16s_kernel", "gap_kernel", "dense_kernel", "softmax_kernel", "heads_kernel",
     # ResNet (bf16, and the fp32-grade mode)
     "stem7s_stream_kernel", "stem7x7_pool_bf16_kernel", "stem7x7_bf16_kernel", "maxpool3x3s2_bf16_kernel", "conv_bf16_kernel", "conv1x1_bf16_kernel",
     "conv1x1_w4_bf16_kernel", "conv1x1_pair_bf16_kernel", "conv3x3_w2_bf16_kernel", "conv_dma_bf16_kernel", "gap_bf16_kernel",
@@ -865,10 +865,11 @@ def assign_buffers(layers: List[Layer], pinned) -> List[int]:
         for j in range(i + 1):
             if last_use[j] == i and j not in pinned and layers[j].out_buf not in free:
                 free.append(layers[j].out_buf)
-    # OPF_DWPW_NEXT keeps the plain assignment (no third buffer): where the pointwise output recycles the depthwise INPUT's buffer, the
-    # engine's one launch writes into the depthwise tensor's buffer instead and exchanges the two buffers' roles -- they must be one size
+    # OPF_DWPW_NEXT / OPF_PWBLK_NEXT keep the plain assignment (no third buffer): where the second output recycles the flagged layer's
+    # INPUT buffer, the engine's one launch writes into the flagged layer's own (unwritten) buffer instead and exchanges the two buffers'
+    # roles -- they must be one size
     for i, L in enumerate(layers):
-        if L.flags & OPF_DWPW_NEXT and L.src >= 0 and i + 1 < len(layers) and layers[i + 1].out_buf == layers[L.src].out_buf:
+        if L.flags & (OPF_DWPW_NEXT | OPF_PWBLK_NEXT) and L.src >= 0 and i + 1 < len(layers) and layers[i + 1].out_buf == layers[L.src].out_buf:
             a, b = layers[L.src].out_buf, L.out_buf
             buffers[a] = buffers[b] = max(buffers[a], buffers[b])
     return buffers
@@ -1218,6 +1219,34 @@ def mark_dwpw_pairs(layers: List[Layer], keep: Sequence[int]) -> int:
     return n
 
 
+PW_BLOCK_MAX_W = 48      # widest map row csrc/pwblk_stream.hip's LDS budget takes (the 224 plan's 56-pixel rows keep two launches)
+
+
+def pw_block_covered(pw: Layer, blk: Layer) -> bool:
+    """Shapes the pointwise -> block launch covers (csrc/pwblk_stream.hip, pwblk_covered): 64 -> 128 -> 128 channels, rows of at most 48 pixels."""
+    return pw.in_shape[2] == 64 and pw.out_shape[2] == 128 and blk.out_shape[2] == 128 and pw.out_shape[1] <= PW_BLOCK_MAX_W
+
+
+def mark_pw_blocks(layers: List[Layer], keep: Sequence[int]) -> int:
+    """Launch-level fusion of a split-f16 pointwise layer (fp32 input, no residual, ReLU6) with the stride-1 split-f16 depthwise-pointwise
+    block behind it, its sole reader: both layers stay in the plan, the pointwise layer carries OPF_PWBLK_NEXT and the engine runs the two
+    as one row-streaming launch in which the pointwise tensor never reaches HBM (bit-identical to the two launches).  In the MobileNet plan
+    at 192 x 192 that is conv_pw_2 -> conv_pw_3 (the block conv_dw_3 + conv_pw_3).  Call after the fusion passes.  Returns the number marked."""
+    consumers = consumers_of(layers)
+    n = 0
+    for i, pw in enumerate(layers):
+        j = sole_reader(consumers, i, keep)
+        if not (pw.kind == OP_PWCONV_F32 and 0 < pw.a_log2 <= 12 and not pw.in_split and pw.flags == 0 and pw.res < 0 and pw.act == ACT_RELU6 and
+                j == i + 1):
+            continue
+        blk = layers[j]
+        if (blk.kind == OP_DWPW_F16S and blk.stride == 1 and (blk.pad_t, blk.pad_l) == (1, 1) and blk.flags == 0 and
+                tuple(blk.in_shape) == tuple(pw.out_shape) and tuple(blk.out_shape[:2]) == tuple(blk.in_shape[:2]) and pw_block_covered(pw, blk)):
+            pw.flags |= OPF_PWBLK_NEXT
+            n += 1
+    return n
+
+
 def choose_pointwise_math(layers: List[Layer], pw_math: str) -> None:
     """Mark the pointwise layers that may form their products on the f16 MFMA (csrc/pwconv_f16s.hip): the two-term f16
     split needs a bounded input, which the graph proves when the producing layer ends in ReLU6 ([0, 6] -> a_log2 12)."""
@@ -1316,7 +1345,7 @@ def lower_graph(g: Graph, input_tensor: str, outputs: Dict[int, str], input_hw: 
                 pw_math: Optional[str] = None, fuse_stem_block: Optional[bool] = None, stem_fusion: Optional[str] = None,
                 block_fusion: Optional[str] = None, presplit: Optional[str] = None, input_bound: Optional[float] = None,
                 pwdw_fusion: Optional[str] = None, u8_mean_bgr: Optional[Sequence[float]] = None, launch_fusion: bool = True,
-                s2_fusion: Optional[str] = None) -> Plan:
+                s2_fusion: Optional[str] = None, pw_block_fusion: Optional[str] = None) -> Plan:
     """outputs: {slot: 'tensor:0'}.  feeds: constant feeds such as the Keras learning phase.
     fuse: merge depthwise -> pointwise pairs into one kernel where a fused kernel covers the shape.  stem_fusion:
     'stem2' (default) = conv1 + block 1 + the depthwise of block 2 in one
@@ -1344,6 +1373,9 @@ def lower_graph(g: Graph, input_tensor: str, outputs: Dict[int, str], input_hw: 
     s2_fusion: 'auto' (default) = a standalone stride-2 depthwise layer whose only reader is a split-f16 pointwise layer of a covered
     shape (128 -> 256 channels: conv_dw_4 -> conv_pw_4) runs with it as one launch (mark_dwpw_pairs; the layer list does not change);
     'none' = two launches.
+    pw_block_fusion: 'auto' (default) = a split-f16 pointwise layer whose only reader is a stride-1 fused block of a covered shape
+    (64 -> 128 -> 128 channels on rows of at most 48 pixels: conv_pw_2 -> conv_dw_3 + conv_pw_3 at 192 x 192) runs with it as one
+    row-streaming launch (mark_pw_blocks; the layer list does not change); 'none' = two launches.
     dtype 'f32': the MobileNet kernels (exact fp32); 'bf16': ResNet-style graphs on the bf16-MFMA kernels
     (general KxK Conv2D, Pad, FusedBatchNorm / Mul+Add, residual Add, MaxPool 3x3/2, global AvgPool / Mean); 'f32g': the
     same ResNet-style graph patterns on exact-fp32 kernels (OP_CONV_F32 / OP_MAXPOOL_F32 / OP_GAP) -- the fp32-grade mode
@@ -1472,5 +1504,10 @@ def lower_graph(g: Graph, input_tensor: str, outputs: Dict[int, str], input_hw: 
         raise ValueError("s2_fusion must be 'auto' or 'none', not %r" % (s2_fusion,))
     if fuse and launch_fusion and dtype == "f32" and s2_fusion == "auto":
         mark_dwpw_pairs(layers, keep())
+    pw_block_fusion = pw_block_fusion or "auto"
+    if pw_block_fusion not in ("auto", "none"):
+        raise ValueError("pw_block_fusion must be 'auto' or 'none', not %r" % (pw_block_fusion,))
+    if fuse and launch_fusion and dtype == "f32" and pw_block_fusion == "auto":
+        mark_pw_blocks(layers, keep())
     buffers = assign_buffers(layers, set(keep()))
     return Plan(layers, (input_hw[0], input_hw[1], low.in_c), buffers, out_layers, tensor_layer)

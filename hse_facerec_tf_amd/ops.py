@@ -229,6 +229,32 @@ def dwpw_f16split(x, w_hwc, dscale, dshift, wp_t, pshift, stride: int = 1, act: 
 
 
 @_device_guarded
+def pwblk_f16split(x, w2_t, shift2, w_hwc, dscale, dshift, w3_t, shift3, act: int = ACT_RELU6, a_log2: int = 12, a_log2_blk: int = 12, segs: int = 0,
+                   prepared2=None, prepared3=None):
+    """pwconv1x1_f16split (+ ReLU6) -> dwpw_f16split (stride 1) as one row-streaming launch, bit for bit the two calls
+    (csrc/pwblk_stream.hip: 64 -> 128 -> 128 channels on rows of at most 48 pixels; other shapes run as the two launches).  x [n,h,w,cin];
+    w2_t [cmid, cin], w3_t [cout, cmid] fp32 are split on the host (or pass prepared2 / prepared3 = split_weights_device(...)).
+    segs: 0 = automatic, s > 0 = s row segments per image -- the result does not depend on it."""
+    torch = _lib.require_gpu()
+    for t, nm in ((x, "x"), (shift2, "shift2"), (w_hwc, "w"), (dscale, "dscale"), (dshift, "dshift"), (shift3, "shift3")):
+        _f32c(t, nm)
+    img2, ds2 = prepared2 if prepared2 is not None else split_weights_device(w2_t, x.device, a_log2)
+    img3, ds3 = prepared3 if prepared3 is not None else split_weights_device(w3_t, x.device, a_log2_blk)
+    n, h, w, cin = x.shape
+    cmid, cout = img2.shape[0], img3.shape[0]
+    if tuple(w_hwc.shape) != (3, 3, cmid) or dscale.numel() != cmid or dshift.numel() != cmid or shift2.numel() != cmid or shift3.numel() != cout:
+        raise ValueError("depthwise operands must be [3,3,%d], [%d], [%d]; shifts [%d], [%d]" % (cmid, cmid, cmid, cmid, cout))
+    y = torch.empty((n, h, w, cout), dtype=torch.float32, device=x.device)
+    covered = cin == 64 and cmid == 128 and cout == 128 and w <= 48
+    mid = None if covered else torch.empty((n, h, w, cmid), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().hsefr_pwblk_f16split(x.data_ptr(), img2.data_ptr(), ds2.data_ptr(), shift2.data_ptr(), w_hwc.data_ptr(), dscale.data_ptr(),
+                                               dshift.data_ptr(), img3.data_ptr(), ds3.data_ptr(), shift3.data_ptr(),
+                                               None if mid is None else mid.data_ptr(), y.data_ptr(), n, h, w, cin, cmid, cout, a_log2, a_log2_blk,
+                                               act, segs, _lib.current_stream_ptr()), "hsefr_pwblk_f16split")
+    return y
+
+
+@_device_guarded
 def stem_fused(x, conv_w, conv_shift, w_hwc, dscale, dshift, wp_t, pshift, act: int = ACT_RELU6, a_log2: int = 12, prepared=None):
     """The MobileNet stem in one kernel (csrc/stem_fused.hip): conv 3x3/2 SAME 3->32 + shift + ReLU6 -> depthwise 3x3/1 +
     scale + shift + ReLU6 -> pointwise 32->64 + shift + act.  conv_w TF HWIO [3,3,3,32], w_hwc [3,3,32], wp_t [64,32]."""

@@ -186,7 +186,7 @@ typedef enum hsefr_op_flags {
                                 from registers: the tensor's only other reader takes every second pixel of it (the shortcut of a ResNet
                                 stage's last block, lowering.compact_pair_outputs).  Such a pair has no two-launch form: a forward that
                                 cannot run it as one launch fails                                                                      */
-    HSEFR_OPF_DWPW_NEXT = 8  /* DWCONV3X3 with stride 2, ReLU6 and fp32 output whose tensor ONLY the next op reads, a PWCONV_F16S at the
+    HSEFR_OPF_DWPW_NEXT = 8, /* DWCONV3X3 with stride 2, ReLU6 and fp32 output whose tensor ONLY the next op reads, a PWCONV_F16S at the
                                 same pixels without flags, with a shape csrc/dwpw_f16s.hip's stride-2 kernel covers (128 -> 256
                                 channels): both in one launch, the depthwise tensor never written (MobileNet's conv_dw_4 -> conv_pw_4;
                                 bit-identical to the two launches).  Where the second output recycles the depthwise INPUT's buffer, the
@@ -194,6 +194,13 @@ typedef enum hsefr_op_flags {
                                 each other's place (they must have one size; neither is an output): see hsefr_engine_buffer.  An
                                 all-layers forward (no output pointers) runs the two ops separately, so the depthwise tensor still
                                 exists there.  Added within version 141: a flag bit, not a layout change                              */
+    HSEFR_OPF_PWBLK_NEXT = 16 /* PWCONV_F16S 64 -> 128 with ReLU6, no residual and fp32 output on rows of at most 48 pixels whose tensor ONLY
+                                the next op reads, a stride-1 DWPW_F16S 128 -> 128 at the same pixels without flags: both in one
+                                row-streaming launch, the pointwise tensor never written (csrc/pwblk_stream.hip: MobileNet's conv_pw_2 ->
+                                conv_dw_3 + conv_pw_3 at 192 x 192 input; bit-identical to the two launches).  Buffers as for DWPW_NEXT:
+                                where the block's output recycles the pointwise INPUT's buffer, the launch writes into the pointwise
+                                tensor's buffer and the rest of that forward uses the two in each other's place (one size; neither an
+                                output).  An all-layers forward runs the two ops separately.  Added within version 141: a flag bit      */
 } hsefr_op_flags;
 
 /* hsefr_plan_op.aux, the per-kind aux word.  PWCONV_F16S, PWCONV_PS, PWCONV_PS_GAP, DWPW_F16S, STEM_F16S, STEM2_F16S: a_log2 alone (the
@@ -321,12 +328,12 @@ int hsefr_engine_forward_u8(hsefr_engine* e, const void* d_input_u8, int n, void
  * parity tests.  NULL if `buffer` is out of range.  NOT for the buffers behind the plan's OUTPUT slots: a forward that
  * was given an aligned output pointer writes that tensor into the caller's memory instead, and the engine's buffer keeps
  * whatever an earlier forward left there (run the forward with all three output pointers NULL to have every op write the
- * engine's own buffers -- what Engine.forward_all_layers does).  In a plan with an HSEFR_OPF_DWPW_NEXT op, a forward WITH output
+ * engine's own buffers -- what Engine.forward_all_layers does).  In a plan with an HSEFR_OPF_DWPW_NEXT or _PWBLK_NEXT op, a forward WITH output
  * pointers may leave the tensors behind that op in the other one of two activation buffers than the plan names (the flag's comment):
  * only after an all-layers forward does every buffer hold the tensor the plan assigns to it. */
 void* hsefr_engine_buffer(hsefr_engine* e, int buffer);
 /* Asynchronous device-to-device copy of the first `bytes` of an activation buffer into d_dst.  The same restriction: in a plan with an
- * HSEFR_OPF_DWPW_NEXT op, meaningful after an all-layers forward only. */
+ * HSEFR_OPF_DWPW_NEXT or _PWBLK_NEXT op, meaningful after an all-layers forward only. */
 int hsefr_engine_copy_buffer(hsefr_engine* e, int buffer, void* d_dst, size_t bytes, hsefr_stream_t stream);
 
 /* Per-op device time: with depth > 0 every forward records HIP events around each launch on
@@ -415,6 +422,16 @@ int hsefr_pwconv1x1_presplit_dw(const void* x_split, const void* w_split, const 
 int hsefr_dwpw_f16split(const float* x, const float* wd, const float* dscale, const float* dshift, const void* w_split,
                         const float* descale, const float* pshift, float* y, int n, int h, int w, int c, int stride,
                         int pad_t, int pad_l, int oh, int ow, int cout, int a_log2, int act, hsefr_stream_t stream);
+
+/* hsefr_pwconv1x1_f16split (+ ReLU6) followed by hsefr_dwpw_f16split (stride 1, SAME) as ONE row-streaming launch, the tensor between them
+ * never written (csrc/pwblk_stream.hip): x [n,h,w,cin] with |x| * 2^a_log2 < 32768 -> pointwise cin -> cmid + shift2 + ReLU6 -> depthwise 3x3
+ * + scale + shift + ReLU6 -> pointwise cmid -> cout + shift3 + act -> y [n,h,w,cout], bit for bit the two calls.  The launch covers
+ * 64 -> 128 -> 128 channels on rows of w <= 48 pixels; any other shape the two kernels cover runs as those two launches through
+ * mid [n,h,w,cmid] (may be NULL for a covered shape).  a_log2 / a_log2_blk in 1..12.  segs: 0 = the launcher splits an image into as many
+ * row segments as fill the GPU at small batches, s > 0 = s segments per image (at most h); the result does not depend on it. */
+int hsefr_pwblk_f16split(const float* x, const void* w2_split, const float* descale2, const float* shift2, const float* wd, const float* dscale,
+                         const float* dshift, const void* w3_split, const float* descale3, const float* shift3, float* mid, float* y, int n, int h,
+                         int w, int cin, int cmid, int cout, int a_log2, int a_log2_blk, int act, int segs, hsefr_stream_t stream);
 
 /* The stem plus the depthwise half of block 2 (graph nodes #30-#55) in one kernel: ... -> pointwise 32->64 + shift + ReLU6
  * -> depthwise 3x3 stride 2 SAME + scale + shift + act.  wd2 [3,3,64]; y [n,oh2,ow2,64] with h1 = ceil(h/2),
