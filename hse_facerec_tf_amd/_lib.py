@@ -93,6 +93,8 @@ SIGNATURES = {
     "hsefr_nn1": (c_int, [_fp, _fp, c_int, c_int, c_int, _fp, _fp, c_void_p]),
     "hsefr_knn": (c_int, [_fp, _fp, c_int, c_int, c_int, c_int, _fp, _fp, _fp, _fp, c_void_p]),
     "hsefr_nn1_fallbacks": (c_longlong, []),
+    "hsefr_metric_dist": (c_int, [_fp, _fp, c_int, c_int, c_int, c_int, _fp, c_void_p]),
+    "hsefr_knn_metric": (c_int, [_fp, _fp, c_int, c_int, c_int, c_int, c_int, _fp, _fp, _fp, _fp, c_void_p]),
     "hsefr_pca_fit": (c_int, [_fp, c_int, c_int, c_int, c_int, _fp, _fp, _fp, _fp, c_void_p]),
     "hsefr_pca_transform": (c_int, [_fp, c_int, c_int, c_int, _fp, _fp, _fp, c_int, c_void_p]),
     "hsefr_linear_svm_fit": (c_int, [_fp, c_int, c_int, _fp, c_int, ctypes.c_double, ctypes.c_double, c_int, _fp, _fp, _fp, c_void_p]),

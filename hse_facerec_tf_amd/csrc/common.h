@@ -206,6 +206,9 @@ int launch_nn1(const float* q, const float* g, int nq, int ng, int d, int* nn_in
 int launch_knn(const float* q, const float* g, int nq, int ng, int d, int k, int* nn_index, float* nn_dist2, const int* g_label, int* pred,
                hipStream_t s);
 long long nn1_fallbacks();
+int launch_metric_dist(const float* x, const float* y, int n, int m, int d, int metric, float* out, hipStream_t s);
+int launch_knn_metric(const float* q, const float* g, int nq, int ng, int d, int k, int metric, int* nn_index, float* nn_dist, const int* g_label,
+                      int* pred, hipStream_t s);
 int launch_pca_fit(const float* x, int n, int d, int k, int max_iter, double* mean, double* components, double* explained_variance, int* info,
                    hipStream_t s);
 int launch_pca_transform(const float* x, int n, int d, int k, const double* mean, const double* components, float* z, int ldz,

@@ -1364,6 +1364,19 @@ int hsefr_knn(const float* q, const float* g, int nq, int ng, int d, int k, int*
 
 long long hsefr_nn1_fallbacks(void) { return nn1_fallbacks(); }
 
+int hsefr_metric_dist(const float* x, const float* y, int n, int m, int d, int metric, float* out, hsefr_stream_t stream) {
+    HSEFR_REQUIRE(n == 0 || m == 0 || (x && y && out), HSEFR_ERR_INVALID, "metric_dist: null pointer");
+    return launch_metric_dist(x, y, n, m, d, metric, out, (hipStream_t)stream);
+}
+
+int hsefr_knn_metric(const float* q, const float* g, int nq, int ng, int d, int k, int metric, int* nn_index, float* nn_dist,
+                     const int* g_label, int* pred, hsefr_stream_t stream) {
+    HSEFR_REQUIRE(!g_label == !pred, HSEFR_ERR_INVALID, "knn_metric: g_label and pred go together (labels at %p, pred at %p)",
+                  (const void*)g_label, (const void*)pred);
+    HSEFR_REQUIRE(nq == 0 || (q && g && nn_index), HSEFR_ERR_INVALID, "knn_metric: null pointer");
+    return launch_knn_metric(q, g, nq, ng, d, k, metric, nn_index, nn_dist, g_label, pred, (hipStream_t)stream);
+}
+
 int hsefr_pca_fit(const float* x, int n, int d, int k, int max_iter, double* mean, double* components, double* explained_variance, int* info,
                   hsefr_stream_t stream) {
     HSEFR_REQUIRE(x && mean && components && explained_variance && info, HSEFR_ERR_INVALID,

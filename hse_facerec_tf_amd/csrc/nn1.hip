@@ -3,7 +3,9 @@
 // Replaces preprocessing.normalize(X, 'l2') (facerec_test.py:401),
 // KNeighborsClassifier(n_neighbors=1, p=2).fit(gallery).kneighbors(probe)
 // (facerec_test.py:422 scored through classifier_tester :200-207) and the 3-NN classifiers of
-// facerec_test.py:269-288 (kneighbors and the uniform-weight predict: launch_knn at the end of this file).
+// facerec_test.py:269-288 (kneighbors and the uniform-weight predict: launch_knn at the end of this file), and the same
+// search under the study's chi-square and KL distances (facerec_test.py:157-164, :275-276, :424-425: metric_dist_tile_kernel,
+// launch_knn_metric).
 //
 // 1-NN = a [nq x ng x d] contraction (4582 x 4582 x 1024 for LFW, 43 GFLOP) -> fp32 MFMA:
 //   dist2[q, g] = |q|^2 + |g|^2 - 2 q.g ,  arg-min over g, ties to the lowest gallery index.
@@ -342,6 +344,135 @@ __global__ __launch_bounds__(256) void knn_select_kernel(const float* __restrict
     if (lane == 0) pred[row] = bl;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The study's other two k-NN distances (chi2dist and KL_dist, facerec_test.py:157-164, the metric= callables of :275-276 and :424-425).
+// Neither is a dot product, so the tile is vector-ALU work: a workgroup takes 64 probe rows x 64 gallery rows, thread (ty, tx) the 4 x 4
+// pairs of probe rows ty + 16 i and gallery rows tx + 16 j in registers.  Both row blocks go through the LDS in chunks of METRIC_KC
+// columns with a row stride of METRIC_KC + 4 floats: the sixteen gallery rows that the sixteen lanes of one 16-byte LDS read's group ask
+// for then start at 36 tx mod 64 dwords, sixteen different 4-bank slots (the group's other operand, a probe row, is one or two
+// addresses, which broadcast).  A metric is a functor: PX values per probe element and one per gallery element, computed when a chunk is
+// staged (the logs of kl: once per row element and tile, never per pair), and the per-element term.
+//
+// A distance is a function of its two rows alone: every pair adds its d terms to one accumulator in column order by the same
+// instructions, whatever the tile, n, m, ld or the query slice; rows and columns that pad a tile are clamped copies whose results are not
+// written, and the columns of a last partial chunk are not visited at all.  Identical gallery rows therefore tie bit for bit, a search
+// done in halves gives the same bits, and a NaN sum is written as +INFINITY (knn_select_kernel's order has no place for a NaN).
+constexpr int METRIC_KC = 32, METRIC_LD = METRIC_KC + 4;
+
+// chi2: sum_c (x - y)^2 / (x + y) over the columns with x + y > 0 (np.where(sum > 0, ., 0): a zero, negative or NaN sum adds 0).
+// Four roundings per term (sum, difference, square, the correctly rounded IEEE quotient: exact wherever the quotient is representable,
+// so features in {0, 1, 3} give the integer distances) and d - 1 additions of non-negative terms: |error| <= (d + 3) u D, u = 2^-24.
+// Equal rows: every difference is 0, the distance exactly 0.
+struct Chi2Metric {
+    static constexpr int PX = 1;
+    static __device__ __forceinline__ void stage_x(float x, float* v) { v[0] = x; }
+    static __device__ __forceinline__ float stage_y(float y) { return y; }
+    static __device__ __forceinline__ float add(float acc, const float* x, float y) {
+        const float s = x[0] + y, df = x[0] - y;
+        const float t = df * df / s;                         // for every s: a select, not a branch per term, drops the others
+        return acc + (s > 0.f ? t : 0.f);
+    }
+};
+
+// kl: sum_c a (log a - log b), a = fl32(x + 0.001f), b = fl32(y + 0.001f) -- (x+0.001)*log((x+0.001)/(y+0.001)) on float32 arrays, not
+// symmetric (x the probe, y the gallery row), not clamped at 0.  One logf (ocml's, within 1 ulp = 2 u |log|) serves both sides, so equal
+// rows give log a - log b = 0 and the distance exactly 0.  Per term: the two logs 2 u a (|log a| + |log b|), their difference u |t|; the
+// product and the addition are one fma, d roundings of partial sums that are at most sum |t|:
+// |error| <= u [(d + 1) sum |t_c| + 2 sum a_c (|log a_c| + |log b_c|)].  An entry <= -0.001 has a <= 0 (or b: log b = -inf or NaN): the
+// sum is NaN or +inf, written as +INFINITY.
+struct KlMetric {
+    static constexpr int PX = 2;
+    static __device__ __forceinline__ void stage_x(float x, float* v) { v[0] = x + 0.001f; v[1] = logf(v[0]); }
+    static __device__ __forceinline__ float stage_y(float y) { return logf(y + 0.001f); }
+    static __device__ __forceinline__ float add(float acc, const float* x, float y) { return fmaf(x[0], x[1] - y, acc); }
+};
+
+template <class M>
+__global__ __launch_bounds__(256) void metric_dist_tile_kernel(const float* __restrict__ q, const float* __restrict__ g, int n, int ng, int d,
+                                                               float* __restrict__ out, int ld) {
+    __shared__ __attribute__((aligned(16))) float sx[M::PX][64 * METRIC_LD];
+    __shared__ __attribute__((aligned(16))) float sy[64 * METRIC_LD];
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    const int i0 = blockIdx.y * 64, j0 = blockIdx.x * 64;
+    // staging: this thread's 4 columns (lc) of rows lr and lr + 32 of both blocks; rows past the end are copies of the last one
+    const int lr = threadIdx.x >> 3, lc = (threadIdx.x & 7) * 4;
+    const float* qp[2];
+    const float* gp[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        qp[h] = q + (size_t)min(i0 + lr + 32 * h, n - 1) * d + lc;
+        gp[h] = g + (size_t)min(j0 + lr + 32 * h, ng - 1) * d + lc;
+    }
+    float acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    f32x4 rq[2], rg[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {                            // d is a multiple of 4: a thread's 4 columns are inside or outside together
+        rq[h] = lc < d ? *(const f32x4*)qp[h] : zero;
+        rg[h] = lc < d ? *(const f32x4*)gp[h] : zero;
+    }
+    for (int c0 = 0; c0 < d; c0 += METRIC_KC) {
+        __syncthreads();                                     // the previous chunk has been read
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            f32x4 vx[M::PX], vy;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float v[M::PX];
+                M::stage_x(rq[h][e], v);
+#pragma unroll
+                for (int p = 0; p < M::PX; ++p) vx[p][e] = v[p];
+                vy[e] = M::stage_y(rg[h][e]);
+            }
+            const int at = (lr + 32 * h) * METRIC_LD + lc;
+#pragma unroll
+            for (int p = 0; p < M::PX; ++p) *(f32x4*)&sx[p][at] = vx[p];
+            *(f32x4*)&sy[at] = vy;
+        }
+        __syncthreads();
+        const int cn = c0 + METRIC_KC + lc;                  // the next chunk's loads fly during this one's arithmetic
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            rq[h] = cn < d ? *(const f32x4*)(qp[h] + c0 + METRIC_KC) : zero;
+            rg[h] = cn < d ? *(const f32x4*)(gp[h] + c0 + METRIC_KC) : zero;
+        }
+        const int kc = min(METRIC_KC, d - c0);
+        for (int c = 0; c < kc; c += 4) {
+            f32x4 x[4][M::PX], y[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int p = 0; p < M::PX; ++p) x[i][p] = *(const f32x4*)&sx[p][(ty + 16 * i) * METRIC_LD + c];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) y[j] = *(const f32x4*)&sy[(tx + 16 * j) * METRIC_LD + c];
+#pragma unroll
+            for (int e = 0; e < 4; ++e)                      // column order, one accumulator per pair
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    float xe[M::PX];
+#pragma unroll
+                    for (int p = 0; p < M::PX; ++p) xe[p] = x[i][p][e];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[i][j] = M::add(acc[i][j], xe, y[j][e]);
+                }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int row = i0 + ty + 16 * i;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int col = j0 + tx + 16 * j;
+            const float v = acc[i][j];
+            if (row < n && col < ng) out[(size_t)row * ld + col] = v != v ? INFINITY : v;
+        }
+    }
+}
+
 }  // namespace
 
 int launch_pairwise_dist(const float* x, const float* y, int n, int m, int d, float* out, hipStream_t s) {
@@ -453,6 +584,36 @@ static int launch_knn_select(const float* y, int m, int ng, int ld, const float*
     return launch_status("knn (selection)");
 }
 
+constexpr int KNN_GRID_ROWS = 65535 * 64;                   // the distance-tile kernels' grid.y, in rows
+
+// The searches on finished distance tiles: a stream-ordered slice y [qb, ng] of the distance matrix, of query rows bounded (NN1_Y_BYTES)
+// and halved on a failed allocation like the GEMM path's, down to 64 rows; tiles(q0, m, y) launches the distances of probe rows
+// q0 .. q0 + m into it, select(y, m, ng, nullptr, q0) reduces them.  Rows are independent, so the walk changes no bit.
+template <class Select, class Tiles>
+static int knn_slice_walk(const char* what, int nq, int ng, hipStream_t s, Select select, Tiles tiles) {
+    const long long rows_max = NN1_Y_BYTES / ((long long)ng * 4);
+    int qb = (int)(rows_max >= nq ? nq : (rows_max < 64 ? 64 : rows_max / 64 * 64));
+    if (qb > KNN_GRID_ROWS) qb = KNN_GRID_ROWS;
+    float* y = nullptr;
+    while (hipMallocAsync((void**)&y, (size_t)qb * ng * 4, s) != hipSuccess || !y) {
+        (void)hipGetLastError();
+        y = nullptr;
+        if (qb <= 64) break;
+        qb = qb / 2 < 64 ? 64 : qb / 2 / 64 * 64;
+    }
+    HSEFR_REQUIRE(y, HSEFR_ERR_NOMEM, "%s: no stream-ordered workspace (%zu bytes) for a %d-row slice of the %d x %d distance matrix", what,
+                  (size_t)qb * ng * 4, qb, nq, ng);
+    int rc = HSEFR_OK;
+    for (int q0 = 0; q0 < nq && rc == HSEFR_OK; q0 += qb) {
+        const int m = nq - q0 < qb ? nq - q0 : qb;
+        tiles(q0, m, y);
+        rc = launch_status("knn (distance tiles)");
+        if (rc == HSEFR_OK) rc = select(y, m, ng, nullptr, q0);
+    }
+    (void)hipFreeAsync(y, s);
+    return rc;
+}
+
 int launch_knn(const float* q, const float* g, int nq, int ng, int d, int k, int* nn_index, float* nn_dist2, const int* g_label, int* pred,
                hipStream_t s) {
     HSEFR_REQUIRE(d > 0 && d % 8 == 0, HSEFR_ERR_UNSUPPORTED, "knn: d=%d must be a multiple of 8", d);
@@ -465,31 +626,47 @@ int launch_knn(const float* q, const float* g, int nq, int ng, int d, int k, int
     };
     int rc;
     if (split_f16_shape(nq, ng, d) && split_f16_search("knn", q, g, nq, ng, d, s, rc, select)) return rc;
-    // every other search (small by definition), and a large one without workspace: finished fp32 distances, nn1_kernel's own bits, into a
-    // slice of query rows bounded and halved like the GEMM path's, then the same selection.  A list of k candidates for each of
-    // nn1_kernel's 16 accumulator rows per lane would not fit its registers.
-    const long long rows_max = NN1_Y_BYTES / ((long long)ng * 4);
-    const int grid_rows = 65535 * 64;                       // the tile kernel's grid.y
-    int qb = (int)(rows_max >= nq ? nq : (rows_max < 64 ? 64 : rows_max / 64 * 64));
-    if (qb > grid_rows) qb = grid_rows;
-    float* y = nullptr;
-    while (hipMallocAsync((void**)&y, (size_t)qb * ng * 4, s) != hipSuccess || !y) {
-        (void)hipGetLastError();
-        y = nullptr;
-        if (qb <= 64) break;
-        qb = qb / 2 < 64 ? 64 : qb / 2 / 64 * 64;
-    }
-    HSEFR_REQUIRE(y, HSEFR_ERR_NOMEM, "knn: no stream-ordered workspace (%zu bytes) for a %d-row slice of the %d x %d distance matrix",
-                  (size_t)qb * ng * 4, qb, nq, ng);
-    rc = HSEFR_OK;
-    for (int q0 = 0; q0 < nq && rc == HSEFR_OK; q0 += qb) {
-        const int m = nq - q0 < qb ? nq - q0 : qb;
+    // every other search (small by definition), and a large one without workspace: finished fp32 distances, nn1_kernel's own bits, then
+    // the same selection.  A list of k candidates for each of nn1_kernel's 16 accumulator rows per lane would not fit its registers.
+    return knn_slice_walk("knn", nq, ng, s, select, [&](int q0, int m, float* y) {
         HSEFR_LAUNCH(knn_dist2_tile_kernel, dim3((ng + 63) / 64, (m + 63) / 64), dim3(256), 0, s, q + (size_t)q0 * d, g, m, ng, d, y, ng);
-        rc = launch_status("knn (distance tiles)");
-        if (rc == HSEFR_OK) rc = select(y, m, ng, nullptr, q0);
-    }
-    (void)hipFreeAsync(y, s);
-    return rc;
+    });
+}
+
+// metric: HSEFR_METRIC_CHI2 or HSEFR_METRIC_KL (checked by the callers); the tiles of probe rows x [n,d] against y [m,d] into out, row stride ld
+static void launch_metric_tiles(int metric, const float* x, const float* y, int n, int m, int d, float* out, int ld, hipStream_t s) {
+    const dim3 grid((m + 63) / 64, (n + 63) / 64), block(256);
+    if (metric == HSEFR_METRIC_CHI2) HSEFR_LAUNCH(metric_dist_tile_kernel<Chi2Metric>, grid, block, 0, s, x, y, n, m, d, out, ld);
+    else HSEFR_LAUNCH(metric_dist_tile_kernel<KlMetric>, grid, block, 0, s, x, y, n, m, d, out, ld);
+}
+
+static int check_metric_args(const char* what, int metric, int d) {
+    HSEFR_REQUIRE(metric == HSEFR_METRIC_CHI2 || metric == HSEFR_METRIC_KL, HSEFR_ERR_INVALID,
+                  "%s: metric=%d must be HSEFR_METRIC_CHI2 (1) or HSEFR_METRIC_KL (2)", what, metric);
+    HSEFR_REQUIRE(d > 0 && d % 4 == 0, HSEFR_ERR_INVALID, "%s: d=%d must be a positive multiple of 4", what, d);
+    return HSEFR_OK;
+}
+
+int launch_metric_dist(const float* x, const float* y, int n, int m, int d, int metric, float* out, hipStream_t s) {
+    if (const int rc = check_metric_args("metric_dist", metric, d)) return rc;
+    HSEFR_REQUIRE(n >= 0 && m >= 0 && n <= KNN_GRID_ROWS, HSEFR_ERR_INVALID, "metric_dist: n=%d m=%d (n at most %d)", n, m, KNN_GRID_ROWS);
+    if (n == 0 || m == 0) return HSEFR_OK;
+    launch_metric_tiles(metric, x, y, n, m, d, out, m, s);
+    return launch_status("metric_dist");
+}
+
+int launch_knn_metric(const float* q, const float* g, int nq, int ng, int d, int k, int metric, int* nn_index, float* nn_dist, const int* g_label,
+                      int* pred, hipStream_t s) {
+    if (const int rc = check_metric_args("knn_metric", metric, d)) return rc;
+    HSEFR_REQUIRE(nq >= 0 && ng > 0 && ng <= 0x7fffffff - 512, HSEFR_ERR_INVALID, "knn_metric: nq=%d ng=%d", nq, ng);
+    HSEFR_REQUIRE(k >= 1 && k <= 16 && k <= ng, HSEFR_ERR_INVALID, "knn_metric: k=%d must be in 1..16 and at most ng=%d", k, ng);
+    if (nq == 0) return HSEFR_OK;
+    const auto select = [&](const float* y, int m, int ld, const float* qq, int q0) {
+        return launch_knn_select(y, m, ng, ld, qq, k, nn_index + (size_t)q0 * k, nn_dist ? nn_dist + (size_t)q0 * k : nullptr, g_label,
+                                 pred ? pred + q0 : nullptr, s);
+    };
+    return knn_slice_walk("knn_metric", nq, ng, s, select,
+                          [&](int q0, int m, float* y) { launch_metric_tiles(metric, q + (size_t)q0 * d, g, m, ng, d, y, ng, s); });
 }
 
 }  // namespace hsefr

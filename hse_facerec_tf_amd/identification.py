@@ -29,6 +29,13 @@ classifier: "knn" is all of the above.  "linear_svm" replaces the search by the 
     and 'svm_iterations' in place of 'nn_index' / 'nn_dist'; ``timings`` as for "linear_svm".  scikit-learn's default tolerance stops
     about 3e-4 short of the optimum in a pair's decision value, so a vote whose value is that close to 0 can differ.  ``n_neighbors``
     must stay 1.
+metric: "l2" is all of the above.  "chi2" and "kl" give the reference's k-NN rows under its other two distances, chi2dist and KL_dist
+    (facerec_test.py:157-164; KNeighborsClassifier(n_neighbors=1, metric=chi2dist) and metric=KL_dist at :275-276 and :424-425, which
+    scikit-learn evaluates pair by pair in Python): every search, n_neighbors = 1 included, goes through ops.knn(metric=), the probe
+    being the callable's first argument; 'nn_dist' holds the distance itself (no square root), shaped [nq] for n_neighbors = 1 and
+    [nq, k] otherwise as above, and the search is timed as nn1_s.  The features are meant to be non-negative (GAP after ReLU6,
+    probabilities); ``normalize`` and one_nn_identification's L2 normalisation apply as for "l2" (the reference feeds X_norm to these
+    rows).  Only with classifier="knn" and without ``pca_components``: projections are signed, and the reference never combines them.
 svm_C: the C of either SVM.  svm_gamma: "scale" (1 / (d Var) of the gallery rows, over the unpadded columns after a PCA) or a positive
     finite number.
 """
@@ -132,10 +139,11 @@ class _Keywords(NamedTuple):
     classifier: str
     svm_C: float
     svm_gamma: object
+    metric: str = "l2"
 
 
 def _check_keywords(n_neighbors=1, pca="host", pca_components=None, classifier="knn", svm_C=1.0, svm_gamma="scale",
-                    n_gallery=None) -> _Keywords:
+                    n_gallery=None, metric="l2") -> _Keywords:
     """Every keyword check of the protocols, raised as ValueError before the library is loaded or a device is touched; ``n_gallery``:
     the gallery rows, where the protocol knows them this early."""
     from . import ops
@@ -144,7 +152,13 @@ def _check_keywords(n_neighbors=1, pca="host", pca_components=None, classifier="
     check_classifier(classifier, n_neighbors, svm_C, svm_gamma)
     if pca_components and pca == "device":
         ops.check_pca_components(pca_components, n_gallery)
-    return _Keywords(n_neighbors, pca, pca_components, classifier, svm_C, svm_gamma)
+    if ops.check_metric(metric) != "l2":
+        if classifier != "knn":
+            raise ValueError("metric=%r is a k-NN distance: it has no meaning with classifier=%r" % (metric, classifier))
+        if pca_components:
+            raise ValueError("metric=%r wants non-negative features, and a PCA's projections are signed: leave pca_components unset"
+                             % (metric,))
+    return _Keywords(n_neighbors, pca, pca_components, classifier, svm_C, svm_gamma, metric)
 
 
 def _phase_clock(torch, device, timings: Optional[dict]):
@@ -213,12 +227,19 @@ def _classify(torch, ops, gal, qry, y_gallery: np.ndarray, kw: _Keywords, lap=la
     host.  extras: 'nn_index' + 'nn_dist' of the searches, 'decision' + 'svm_iterations' of the linear SVM, 'votes' + 'svm_iterations'
     of the RBF SVM.  ``lap`` (a _phase_clock) is called with nn1_s after the search -- for n_neighbors = 1 before anything is copied
     to the host, for more after the copies -- or with svm_fit_s and svm_predict_s."""
-    if kw.classifier == "knn" and kw.n_neighbors == 1:
+    if kw.classifier == "knn" and kw.n_neighbors == 1 and kw.metric == "l2":
         nn_idx, nn_d2 = ops.nn1(qry, gal)
         lap("nn1_s")
         nn_idx_h = nn_idx.cpu().numpy()
         return y_gallery[nn_idx_h], {"nn_index": nn_idx_h, "nn_dist": np.sqrt(nn_d2.cpu().numpy())}
     classes, labels = _encode_labels(torch, y_gallery, gal.device)
+    if kw.classifier == "knn" and kw.metric != "l2":        # KNeighborsClassifier(n_neighbors, metric=chi2dist | KL_dist)
+        idx, dist, pred = ops.knn(qry, gal, kw.n_neighbors, labels, metric=kw.metric)
+        if kw.n_neighbors == 1:
+            idx, dist = idx[:, 0], dist[:, 0]
+        y_pred, extras = classes[pred.cpu().numpy()], {"nn_index": idx.cpu().numpy(), "nn_dist": dist.cpu().numpy()}
+        lap("nn1_s")
+        return y_pred, extras
     if kw.classifier == "knn":                  # KNeighborsClassifier(n_neighbors): kneighbors + predict
         idx, d2, pred = ops.knn(qry, gal, kw.n_neighbors, labels)
         y_pred, extras = classes[pred.cpu().numpy()], {"nn_index": idx.cpu().numpy(), "nn_dist": np.sqrt(d2.cpu().numpy())}
@@ -259,10 +280,12 @@ def _classify(torch, ops, gal, qry, y_gallery: np.ndarray, kw: _Keywords, lap=la
 
 def one_nn_identification(X, y: np.ndarray, split=None,
                           pca_components: Optional[int] = None, timings: Optional[dict] = None, device=None,
-                          n_neighbors: int = 1, pca: str = "host", classifier: str = "knn", svm_C: float = 1.0, svm_gamma="scale") -> Dict:
+                          n_neighbors: int = 1, pca: str = "host", classifier: str = "knn", svm_C: float = 1.0, svm_gamma="scale",
+                          metric: str = "l2") -> Dict:
     """The protocol of facerec_test.py:401-432: 'k-NN' (pca_components=None) or 'k-NN+PCA' (pca_components=128, the Pipeline of :421)
     on a stratified half split of the samples whose class has more than one; ``classifier`` gives the 'linear svm' row of :429 and the
-    'svm' row instead.  n_neighbors, pca, classifier, svm_C and svm_gamma: see the module docstring; the gallery is the train half.
+    'svm' row instead, ``metric`` the chi2dist / KL_dist rows of :424-425.  n_neighbors, pca, classifier, svm_C, svm_gamma and metric: see
+    the module docstring; the gallery is the train half.
 
     X: [N, D] float32 embeddings, CUDA tensor or NumPy array (uploaded to ``device``, default: the current one); y: [N] labels.
     split: None (compute it here), a (train, test) pair over the FILTERED samples, or a SplitJob started on the same labels.
@@ -271,7 +294,7 @@ def one_nn_identification(X, y: np.ndarray, split=None,
     pca="device"), the classifier's (nn1_s, and nn1_shape with it), readback_s (indices and distances back to the host + the label
     comparison)."""
     from . import _lib, ops
-    kw = _check_keywords(n_neighbors, pca, pca_components, classifier, svm_C, svm_gamma)
+    kw = _check_keywords(n_neighbors, pca, pca_components, classifier, svm_C, svm_gamma, metric=metric)
     torch = _lib.require_gpu()
     if isinstance(X, np.ndarray):
         X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(_lib.cuda_device(device))
@@ -321,13 +344,14 @@ def single_image_per_class_splits(y: np.ndarray, n_splits: int = 10, random_stat
     return res_cv
 
 
-def cross_validated_1nn(X, y: np.ndarray, cv, normalize: bool = True, device=None, n_neighbors: int = 1) -> Dict:
+def cross_validated_1nn(X, y: np.ndarray, cv, normalize: bool = True, device=None, n_neighbors: int = 1, metric: str = "l2") -> Dict:
     """classifier_tester (facerec_test.py:199-207) for KNeighborsClassifier(n_neighbors=1, p=2) over an explicit list of
     (train, test) index pairs -- e.g. single_image_per_class_splits(y) in place of the stratified half split (:200-201) --
     with every search on the GPU.  Returns the per-split accuracies and their mean / std as the reference prints them.
-    ``n_neighbors`` > 1 scores KNeighborsClassifier(n_neighbors) instead (ops.knn's uniform vote)."""
+    ``n_neighbors`` > 1 scores KNeighborsClassifier(n_neighbors) instead (ops.knn's uniform vote), ``metric`` "chi2" or "kl" the
+    classifier under chi2dist / KL_dist (the module docstring)."""
     from . import _lib, ops
-    kw = _check_keywords(n_neighbors)
+    kw = _check_keywords(n_neighbors, metric=metric)
     torch = _lib.require_gpu()
     if isinstance(X, np.ndarray):
         X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(_lib.cuda_device(device))
@@ -346,15 +370,15 @@ def cross_validated_1nn(X, y: np.ndarray, cv, normalize: bool = True, device=Non
 
 def gallery_probe_identification(X_train, y_train: np.ndarray, X_test, y_test: np.ndarray, normalize: bool = False,
                                  pca_components: Optional[int] = None, device=None, n_neighbors: int = 1, pca: str = "host",
-                                 classifier: str = "knn", svm_C: float = 1.0, svm_gamma="scale") -> Dict:
+                                 classifier: str = "knn", svm_C: float = 1.0, svm_gamma="scale", metric: str = "l2") -> Dict:
     """The gallery / probe protocol of tf_train_test_recognition (facerec_test.py:260-288): the '1-NN' classifier (and
     '1-NN+PCA' with ``pca_components``, 16 at :269) FITTED on the gallery features, every probe labelled by its nearest
     gallery row; accuracy = share of probes whose label is right (:287).  NB the reference computes L2-normalised copies
     (:262,265) and then fits / predicts on the UN-normalised ``X_train`` / ``X_test`` (:284-285): ``normalize=False`` is what
-    it runs, ``normalize=True`` what the copies suggest it meant.  n_neighbors, pca, classifier, svm_C and svm_gamma give the other
-    rows of :269-273: see the module docstring.  Returns 'accuracy', 'y_pred' and the classifier's extras."""
+    it runs, ``normalize=True`` what the copies suggest it meant.  n_neighbors, pca, classifier, svm_C, svm_gamma and metric give the
+    other rows of :269-276: see the module docstring.  Returns 'accuracy', 'y_pred' and the classifier's extras."""
     from . import _lib, ops
-    kw = _check_keywords(n_neighbors, pca, pca_components, classifier, svm_C, svm_gamma, n_gallery=len(np.asarray(y_train)))
+    kw = _check_keywords(n_neighbors, pca, pca_components, classifier, svm_C, svm_gamma, n_gallery=len(np.asarray(y_train)), metric=metric)
     torch = _lib.require_gpu()
     dev = _lib.cuda_device(device)
 

@@ -519,12 +519,60 @@ def check_n_neighbors(k, ng=None) -> int:
     return k
 
 
+METRICS = {"l2": 0, "chi2": 1, "kl": 2}     # the k-NN distances: squared L2 (hsefr_nn1 / hsefr_knn), HSEFR_METRIC_CHI2, HSEFR_METRIC_KL
+
+
+def check_metric(metric) -> str:
+    """The distances of the k-NN searches, raised as ValueError before the library is loaded: "l2", or the study's chi2dist ("chi2") and
+    KL_dist ("kl") of facerec_test.py:157-164."""
+    if not isinstance(metric, str) or metric not in METRICS:
+        raise ValueError("metric=%r must be 'l2', 'chi2' (sum (x - y)^2 / (x + y)) or 'kl' (sum (x + 0.001) log((x + 0.001) / (y + 0.001)))"
+                         % (metric,))
+    return metric
+
+
+def _pad4(torch, t):
+    """``t`` with zero columns up to a multiple of 4: neutral under both metrics (chi2's (0, 0) term is 0, kl's a (log a - log a))."""
+    pad = (-t.shape[1]) % 4
+    return torch.nn.functional.pad(t, (0, pad)).contiguous() if pad else t
+
+
 @_device_guarded
-def knn(queries, gallery, k: int, labels=None):
+def metric_distances(x, y=None, metric: str = "chi2"):
+    """The matrix [n, m] (float32) of chi2dist or KL_dist (facerec_test.py:157-164) between the rows of x [n,d] (the first argument of
+    the reference's callable) and of y [m,d] (default: x itself) -- hsefr_metric_dist: equal rows are at exactly 0, a NaN sum comes
+    back as +inf."""
+    if check_metric(metric) == "l2":
+        raise ValueError("metric='l2' is ops.pairwise_distances; metric_distances takes 'chi2' or 'kl'")
+    torch = _lib.require_gpu()
+    _f32c(x, "x")
+    if y is None:
+        y = x
+    else:
+        _f32c(y, "y")
+        if y.shape[1] != x.shape[1]:
+            raise ValueError("x is %d-D, y is %d-D" % (x.shape[1], y.shape[1]))
+    if x.shape[1] < 1:
+        raise ValueError("x has no columns")
+    xp = _pad4(torch, x)
+    yp = xp if y is x else _pad4(torch, y)
+    n, d = xp.shape
+    m = yp.shape[0]
+    out = torch.empty((n, m), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().hsefr_metric_dist(xp.data_ptr(), yp.data_ptr(), n, m, d, METRICS[metric], out.data_ptr(),
+                                            _lib.current_stream_ptr()), "hsefr_metric_dist")
+    return out
+
+
+@_device_guarded
+def knn(queries, gallery, k: int, labels=None, metric: str = "l2"):
     """The k nearest gallery rows of each query, sorted by (squared L2 distance, gallery index) -- exact ties to the lowest index --
     and, with ``labels`` (int32 [ng]), their majority label, equal counts to the smallest label value (hsefr_knn).
-    Returns (index [nq,k] int32, dist2 [nq,k] float32, pred [nq] int32 or None)."""
+    Returns (index [nq,k] int32, dist2 [nq,k] float32, pred [nq] int32 or None).
+    ``metric`` "chi2" or "kl": the same search under chi2dist / KL_dist with the query as the callable's first argument
+    (hsefr_knn_metric); the distances returned are then the metric's own values."""
     k = check_n_neighbors(k, gallery.shape[0])               # before anything touches a device
+    metric = check_metric(metric)
     torch = _lib.require_gpu()
     _f32c(queries, "queries"), _f32c(gallery, "gallery")
     nq, d = queries.shape
@@ -537,9 +585,16 @@ def knn(queries, gallery, k: int, labels=None):
         pred = torch.empty((nq,), dtype=torch.int32, device=queries.device)
     idx = torch.empty((nq, k), dtype=torch.int32, device=queries.device)
     dist = torch.empty((nq, k), dtype=torch.float32, device=queries.device)
-    _lib.check(_lib.lib().hsefr_knn(queries.data_ptr(), gallery.data_ptr(), nq, ng, d, k, idx.data_ptr(), dist.data_ptr(),
-                                    labels.data_ptr() if labels is not None else None, pred.data_ptr() if pred is not None else None,
-                                    _lib.current_stream_ptr()), "hsefr_knn")
+    tail = (idx.data_ptr(), dist.data_ptr(), labels.data_ptr() if labels is not None else None,
+            pred.data_ptr() if pred is not None else None, _lib.current_stream_ptr())
+    if metric == "l2":
+        _lib.check(_lib.lib().hsefr_knn(queries.data_ptr(), gallery.data_ptr(), nq, ng, d, k, *tail), "hsefr_knn")
+    else:
+        if d < 1:
+            raise ValueError("queries have no columns")
+        queries, gallery = _pad4(torch, queries), _pad4(torch, gallery)
+        _lib.check(_lib.lib().hsefr_knn_metric(queries.data_ptr(), gallery.data_ptr(), nq, ng, int(queries.shape[1]), k, METRICS[metric],
+                                               *tail), "hsefr_knn_metric")
     return idx, dist, pred
 
 

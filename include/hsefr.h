@@ -15,6 +15,10 @@
  *       -> hsefr_l2_normalize() + hsefr_nn1()
  *   - KNeighborsClassifier(3).fit / predict                    facerec_test.py:269-288 ('3-NN', '3-NN+PCA')
  *       -> hsefr_knn()
+ *   - KNeighborsClassifier(n_neighbors=1, metric=chi2dist)     facerec_test.py:157-160,275,424
+ *       -> hsefr_knn_metric(HSEFR_METRIC_CHI2)
+ *   - KNeighborsClassifier(n_neighbors=1, metric=KL_dist)      facerec_test.py:162-164,276,425
+ *       -> hsefr_knn_metric(HSEFR_METRIC_KL)
  *   - Pipeline(PCA(n_components), KNeighborsClassifier)         facerec_test.py:269-273,417-432 ('1-NN+PCA', '3-NN+PCA', 'k-NN+PCA')
  *       -> hsefr_pca_fit() on the gallery + hsefr_pca_transform() of both sets, then hsefr_nn1() / hsefr_knn()
  *   - LinearSVC().fit / predict                                 facerec_test.py:269-288 ('linear svm'), :429
@@ -49,7 +53,8 @@ extern "C" {
 #define HSEFR_VERSION 141 /* 0.1.4: round-6 ABI (added: hsefr_plan_op.flags with HSEFR_OPF_PAIR_NEXT / HSEFR_OPF_HEADS, hsefr_conv1x1_pair_bf16, hsefr_heads_fused,
                              hsefr_plan_validate, hsefr_plan_describe, hsefr_nn1_fallbacks; 141: HSEFR_OPF_OUT_SUB2, hsefr_conv1x1_sres_bf16, hsefr_conv1x1_pair_sub2_bf16, the
                              strided-residual word of HSEFR_OP_CONV_BF16; removed from the product library: hsefr_stem_fused / HSEFR_OP_STEM_F16S (development builds only);
-                             130 = round 5, 120 = round 4, 110 = round 3, 100 = round 1-2) */
+                             130 = round 5, 120 = round 4, 110 = round 3, 100 = round 1-2).
+                             hsefr_metric_dist, hsefr_knn_metric and HSEFR_METRIC_*: additions, without a new number */
 
 typedef enum hsefr_status {
     HSEFR_OK = 0,
@@ -609,6 +614,28 @@ int hsefr_nn1(const float* q, const float* g, int nq, int ng, int d, int* nn_ind
  * runs on the fp32 tiles and is counted by hsefr_nn1_fallbacks). */
 int hsefr_knn(const float* q, const float* g, int nq, int ng, int d, int k, int* nn_index, float* nn_dist2, const int* g_label, int* pred,
               hsefr_stream_t stream);
+/* The study's other two k-NN distances (chi2dist and KL_dist, facerec_test.py:157-164), between float32 rows x (the probe) and y (the
+ * gallery row):
+ *   HSEFR_METRIC_CHI2  sum_c (x_c - y_c)^2 / (x_c + y_c) over the columns with x_c + y_c > 0; a zero, negative or NaN sum adds 0
+ *                      (np.where(sum > 0, ., 0)).  The division is IEEE's, so features in {0, 1, 3} give exact integers.
+ *   HSEFR_METRIC_KL    sum_c a_c (log a_c - log b_c), a = fl32(x + 0.001f), b = fl32(y + 0.001f): not symmetric, not clamped at 0 (it can be
+ *                      negative for rows that are not normalised, and the nearest row is then not the identical one).
+ * A distance depends on its two rows alone -- one summation order per pair, whatever n, m or the position of the rows -- so identical
+ * gallery rows tie bit for bit and a search done in parts gives the same bits; equal rows are at exactly 0 under both.  A distance is
+ * never NaN: a NaN sum (an overflowing term, a kl entry <= -0.001) is returned as +INFINITY and sorts last, in index order.  Error
+ * against the exact value on the float32 inputs, u = 2^-24: chi2 at most (d + 6) u D; kl at most
+ * u [(d + 2) sum |t_c| + 4 sum a_c (|log a_c| + |log b_c|)], t_c the terms.  d is a positive multiple of 4 and the rows 16-byte aligned. */
+#define HSEFR_METRIC_CHI2 1
+#define HSEFR_METRIC_KL 2
+/* The full matrix out [n,m] (fp32) of one of them between the rows of x [n,d] and y [m,d]; n <= 65535 * 64; n = 0 or m = 0 is HSEFR_OK. */
+int hsefr_metric_dist(const float* x, const float* y, int n, int m, int d, int metric, float* out, hsefr_stream_t stream);
+/* KNeighborsClassifier(n_neighbors=k, metric=chi2dist | KL_dist) (facerec_test.py:275-276, :424-425): hsefr_knn's contract -- the order by
+ * (distance, gallery index) with exact ties to the lowest index, 1 <= k <= 16 and k <= ng, g_label and pred both or neither and the vote
+ * they ask for, nq = 0 is HSEFR_OK -- with nn_dist [nq,k] (may be NULL) holding the metric's own value.  The k smallest of each row are
+ * selected from a stream-ordered slice of the distance matrix of at most 256 MiB, halved when it cannot be had (HSEFR_ERR_NOMEM when not
+ * even 64 rows of it can).  A bad metric, k, d or shape is HSEFR_ERR_INVALID; arguments are checked before any device call. */
+int hsefr_knn_metric(const float* q, const float* g, int nq, int ng, int d, int k, int metric, int* nn_index, float* nn_dist,
+                     const int* g_label, int* pred, hsefr_stream_t stream);
 /* Large searches run on the split-f16 GEMM and need a stream-ordered workspace; when even its smallest form cannot be allocated the
  * search runs on the workspace-free kernel instead (same nearest neighbours up to last-bit ties, far slower at 10^5 x 10^5).  This
  * counts those searches since the library was loaded, so a perf cliff can be traced to the allocator (hsefr_last_error_string says which). */
