@@ -82,6 +82,11 @@ SIGNATURES = {
     "hsefr_mtcnn_stage_finish": (c_int, [c_int, _fp, c_int, _fp, _fp, _fp, ctypes.c_float, _fp, _fp, _fp, _fp, c_int, c_int, c_void_p]),
     "hsefr_mtcnn_nms": (c_int, [_fp, c_int, ctypes.c_double, c_int, _fp, _fp, c_void_p]),
     "hsefr_mtcnn_crops": (c_int, [_fp, _fp, _fp, c_int, c_int, c_int, c_int, c_void_p]),
+    "hsefr_mtcnn_pyramid_level_batch": (c_int, [_fp, _fp] + [c_int] * 5 + [c_void_p]),
+    "hsefr_mtcnn_stage1_level_batch": (c_int, [_fp, _fp, c_int, c_int, c_int, ctypes.c_double, ctypes.c_float, _fp, _fp, c_void_p]),
+    "hsefr_mtcnn_stage1_finish_batch": (c_int, [_fp, _fp, _fp, _fp, c_int, c_int, c_int, c_void_p]),
+    "hsefr_mtcnn_crops_batch": (c_int, [_fp, _fp, _fp, _fp] + [c_int] * 5 + [c_void_p]),
+    "hsefr_mtcnn_stage_finish_batch": (c_int, [c_int, _fp, _fp, c_int, _fp, _fp, _fp, ctypes.c_float, _fp, _fp, _fp, _fp, c_int, c_int, c_int, c_void_p]),
     "hsefr_pairwise_dist": (c_int, [_fp, _fp, c_int, c_int, c_int, _fp, c_void_p]),
     "hsefr_single_linkage": (c_int, [_fp, c_int, c_int, _fp, _fp, _fp, _fp, _fp, _fp, c_void_p]),
     "hsefr_hier_linkage": (c_int, [_fp, c_int, c_int, _fp, _fp, _fp, c_int, _fp, _fp, _fp, _fp, c_void_p]),

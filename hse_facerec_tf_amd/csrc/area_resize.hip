@@ -47,10 +47,14 @@ __device__ __forceinline__ void linear_tap(int d, int ssize, double scale, int& 
 }
 
 // ---- pyramid level: uint8 [H,W,3] -> float32 [dw,dh,3] (transposed), value = (u8(resized) - 127.5) * 0.0078125 ---------------
+// blockIdx.y is the frame of a stack of same-size frames [B,H,W,3] -> [B,dw,dh,3] (one frame: a grid of height 1): a frame's pixels
+// come from that frame alone, by the operations below in their order, whatever stands next to it.
 __global__ __launch_bounds__(256) void area_level_kernel(const unsigned char* __restrict__ src, float* __restrict__ dst, int sh, int sw, int dh,
                                                          int dw) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= dh * dw) return;
+    src += (size_t)blockIdx.y * sh * sw * 3;
+    dst += (size_t)blockIdx.y * dh * dw * 3;
     const int dy = i / dw, dx = i - dy * dw;
     const double fx = (double)sw / dw, fy = (double)sh / dh;
     float out[3];
@@ -131,6 +135,8 @@ __global__ __launch_bounds__(256) void area_level_rows_kernel(const unsigned cha
     XCell* xc = (XCell*)lds;
     float* hbuf = (float*)(lds + hoff);                                       // [rows of the cell][dw][3]
     const int dy = blockIdx.x;
+    src += (size_t)blockIdx.y * sh * sw * 3;                                   // the frame of a stack, as in area_level_kernel
+    dst += (size_t)blockIdx.y * dh * dw * 3;
     const double fx = (double)sw / dw, fy = (double)sh / dh;
     for (int dx = threadIdx.x; dx < dw; dx += 256) {
         int xa, xb;
@@ -190,14 +196,10 @@ __global__ __launch_bounds__(256) void area_level_rows_kernel(const unsigned cha
 }
 
 // ---- crops: box k = {x1, y1, x2, y2 (1-based inclusive window inside the frame), tx1, ty1 (where it lands in the tile), bw, bh} ----
-__global__ __launch_bounds__(256) void area_crops_kernel(const unsigned char* __restrict__ src, const int* __restrict__ boxes,
-                                                         float* __restrict__ dst, int sh, int sw, int n, int S) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (long long)n * S * S) return;
-    const int k = (int)(i / (S * S)), rem = (int)(i - (long long)k * S * S), dy = rem / S, dx = rem - dy * S;
-    const int* bx = boxes + k * 8;
+// pixel (dy, dx) of the crop of table row bx from the frame src, written to o[0..2]
+__device__ __forceinline__ void area_crop_pixel(const unsigned char* __restrict__ src, const int* __restrict__ bx, float* __restrict__ o, int sw, int S,
+                                                int dy, int dx) {
     const int x1 = bx[0], y1 = bx[1], x2 = bx[2], y2 = bx[3], tx1 = bx[4], ty1 = bx[5], bw = bx[6], bh = bx[7];
-    (void)sh;
     // tile(y, x) of the box-sized zero-padded tile, 0-based
     auto tile = [&](int y, int x, int c) -> double {
         const int fy = y - (ty1 - 1) + (y1 - 1), fx_ = x - (tx1 - 1) + (x1 - 1);
@@ -258,14 +260,43 @@ __global__ __launch_bounds__(256) void area_crops_kernel(const unsigned char* __
             out[c] = __dadd_rn(__dmul_rn(h0, b0), __dmul_rn(h1, b1));
         }
     }
-    float* o = dst + (((long long)k * S + dx) * S + dy) * 3;                  // transposed: the nets see (W, H)
     for (int c = 0; c < 3; ++c) o[c] = (float)((out[c] - 127.5) * 0.0078125);
+}
+
+// One frame (offsets == nullptr): crop k is row k of the table `boxes` [n, 8].  A stack of B same-size frames with the crops of all
+// frames as ONE list [n, S, S, 3]: crop k belongs to the frame b with offsets[b] <= k < offsets[b + 1] and is row k - offsets[b] of that
+// frame's table (tables [B, rows, 8]); offsets [B + 1] ascending from 0 to n, and a crop whose frame or row cannot be found there (a
+// malformed list) is left unwritten.  (One kernel for both: the product library has no room for the body twice, tests/test_abi_cpu.py.)
+__global__ __launch_bounds__(256) void area_crops_kernel(const unsigned char* __restrict__ src, const int* __restrict__ boxes,
+                                                         const int* __restrict__ offsets, float* __restrict__ dst, int B, int rows, int sh,
+                                                         int sw, int n, int S) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)n * S * S) return;
+    const int k = (int)(i / (S * S)), rem = (int)(i - (long long)k * S * S), dy = rem / S, dx = rem - dy * S;
+    const int* bx = boxes + k * 8;
+    if (offsets) {
+        int lo = 0, hi = B;                                                   // the last b with offsets[b] <= k
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (offsets[mid] <= k) lo = mid; else hi = mid;
+        }
+        const int row = k - offsets[lo];
+        if (row < 0 || row >= rows || k >= offsets[lo + 1]) return;
+        src += (size_t)lo * sh * sw * 3;
+        bx = boxes + ((size_t)lo * rows + row) * 8;
+    }
+    area_crop_pixel(src, bx, dst + (((long long)k * S + dx) * S + dy) * 3, sw, S, dy, dx);   // transposed: the nets see (W, H)
 }
 
 }  // namespace
 
 int launch_area_level(const unsigned char* src, float* dst, int sh, int sw, int dh, int dw, hipStream_t s) {
+    return launch_area_level_batch(src, dst, 1, sh, sw, dh, dw, s);
+}
+
+int launch_area_level_batch(const unsigned char* src, float* dst, int frames, int sh, int sw, int dh, int dw, hipStream_t s) {
     HSEFR_REQUIRE(sh > 0 && sw > 0 && dh > 0 && dw > 0, HSEFR_ERR_INVALID, "area_level: bad shape");
+    HSEFR_REQUIRE(frames >= 1 && frames <= 65535, HSEFR_ERR_INVALID, "area_level: %d frames (1 .. 65535)", frames);
     // the general decimation case (both factors >= 1, not both integers: every level of MTCNN's 0.709 pyramid) row by row
     const double fx = (double)sw / dw, fy = (double)sh / dh;
     if (fx >= 1.0 && fy >= 1.0 && !(sh == dh && sw == dw)) {
@@ -274,11 +305,11 @@ int launch_area_level(const unsigned char* src, float* dst, int sh, int sw, int 
         const size_t hoff = ((size_t)dw * sizeof(XCell) + 15) & ~(size_t)15;
         const size_t lds = hoff + ((size_t)fy + 3) * (size_t)dw * 3 * sizeof(float);
         if (!integer && lds <= 64 * 1024) {
-            HSEFR_LAUNCH(area_level_rows_kernel, dim3(dh), dim3(256), lds, s, src, dst, sh, sw, dh, dw, (int)hoff);
+            HSEFR_LAUNCH(area_level_rows_kernel, dim3(dh, frames), dim3(256), lds, s, src, dst, sh, sw, dh, dw, (int)hoff);
             return launch_status("area_level_rows");
         }
     }
-    HSEFR_LAUNCH(area_level_kernel, dim3((dh * dw + 255) / 256), dim3(256), 0, s, src, dst, sh, sw, dh, dw);
+    HSEFR_LAUNCH(area_level_kernel, dim3((dh * dw + 255) / 256, frames), dim3(256), 0, s, src, dst, sh, sw, dh, dw);
     return launch_status("area_level");
 }
 
@@ -286,8 +317,24 @@ int launch_area_crops(const unsigned char* src, const int* boxes, float* dst, in
     HSEFR_REQUIRE(sh > 0 && sw > 0 && n >= 0 && size > 0, HSEFR_ERR_INVALID, "area_crops: bad shape");
     if (n == 0) return HSEFR_OK;
     const long long total = (long long)n * size * size;
-    HSEFR_LAUNCH(area_crops_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src, boxes, dst, sh, sw, n, size);
+    HSEFR_LAUNCH(area_crops_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src, boxes, (const int*)nullptr, dst, 1, n, sh, sw, n,
+                 size);
     return launch_status("area_crops");
+}
+
+int launch_area_crops_batch(const unsigned char* frames, const int* tables, const int* offsets, float* dst, int n_frames, int rows, int sh, int sw,
+                            int n, int size, hipStream_t s) {
+    HSEFR_REQUIRE(n_frames >= 1 && rows > 0 && sh > 0 && sw > 0 && n >= 0 && size > 0, HSEFR_ERR_INVALID, "area_crops_batch: bad shape");
+    // the kernel indexes a frame's bytes, the tables' rows and a crop's position in the list with int
+    HSEFR_REQUIRE((long long)sh * sw * 3 < (1ll << 31) && (long long)n_frames * rows < (1ll << 31) && (long long)size * size < (1ll << 31),
+                  HSEFR_ERR_UNSUPPORTED, "area_crops_batch: %d frames of %dx%d with %d table rows, size %d: an index leaves 31 bits", n_frames, sh, sw,
+                  rows, size);
+    if (n == 0) return HSEFR_OK;
+    const long long total = (long long)n * size * size;
+    HSEFR_REQUIRE((total + 255) / 256 < (1ll << 31), HSEFR_ERR_UNSUPPORTED, "area_crops_batch: %d crops of size %d", n, size);
+    HSEFR_LAUNCH(area_crops_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, frames, tables, offsets, dst, n_frames, rows, sh, sw, n,
+                 size);
+    return launch_status("area_crops_batch");
 }
 
 }  // namespace hsefr

@@ -234,6 +234,13 @@ int launch_mtcnn_stage1_finish(const double* found, int* counters, double* boxes
 int launch_mtcnn_stage23_finish(int stage, const double* boxes_in, int n, const float* prob, const float* reg, const float* pts, float thr,
                                 double* boxes_out, int* tab_out, float* points_out, int* counters, int img_w, int img_h, hipStream_t s);
 int launch_mtcnn_nms(const double* boxes, int n, double thr, int use_min, int* keep, int* n_keep, hipStream_t s);
+// the same stages over a stack of frames, one workgroup per frame: lists [frames, capacity, .], counters [frames, 8]
+int launch_mtcnn_stage1_level_batch(const float* prob, const float* reg, int frames, int w, int h, double scale, float thr, double* found,
+                                    int* counters, hipStream_t s);
+int launch_mtcnn_stage1_finish_batch(const double* found, int* counters, double* boxes, int* tab, int frames, int img_w, int img_h, hipStream_t s);
+int launch_mtcnn_stage23_finish_batch(int stage, const double* boxes_in, const int* offsets, const float* prob, const float* reg, const float* pts,
+                                      float thr, double* boxes_out, int* tab_out, float* points_out, int* counters, int frames, int n_total, int img_w,
+                                      int img_h, hipStream_t s);
 bool conv3x3_win_forced();
 bool conv3x3_win_bf16_supported(long long n, int h, int w, int c, int cout);
 int launch_conv3x3_win_bf16(const void* x, const void* wt, const float* scale, const float* shift, const void* res, void* y, int n, int h,
@@ -283,6 +290,9 @@ int launch_cv_resize(const unsigned char* in, float* out, int n, int H, int W, i
 
 int launch_area_level(const unsigned char* src, float* dst, int sh, int sw, int dh, int dw, hipStream_t s);
 int launch_area_crops(const unsigned char* src, const int* boxes, float* dst, int sh, int sw, int n, int size, hipStream_t s);
+int launch_area_level_batch(const unsigned char* src, float* dst, int frames, int sh, int sw, int dh, int dw, hipStream_t s);
+int launch_area_crops_batch(const unsigned char* frames, const int* tables, const int* offsets, float* dst, int n_frames, int rows, int sh, int sw,
+                            int n, int size, hipStream_t s);
 int launch_pairwise_dist(const float* x, const float* y, int n, int m, int d, float* out, hipStream_t s);
 // The distance source of the clustering entry points (hsefr_single_linkage, _hier_linkage, _dbscan, _rank_order): float32 features x [n,d] (d a multiple of 8) with
 // optional born / year [n], or a caller's float64 dense [n,n] read as its upper triangle -- exactly one of x and dense is set.

@@ -1459,6 +1459,45 @@ int hsefr_mtcnn_crops(const unsigned char* d_frame, const int* d_boxes, float* d
     return launch_area_crops(d_frame, d_boxes, d_dst, sh, sw, n, size, (hipStream_t)stream);
 }
 
+// ---- the cascade over a stack of same-size frames (hsefr.h) ----
+int hsefr_mtcnn_pyramid_level_batch(const unsigned char* d_frames, float* d_dst, int frames, int sh, int sw, int dh, int dw, hsefr_stream_t stream) {
+    HSEFR_REQUIRE(d_frames && d_dst, HSEFR_ERR_INVALID, "mtcnn_pyramid_level_batch: null pointer");
+    HSEFR_REQUIRE(frames >= 1 && sh > 0 && sw > 0 && dh > 0 && dw > 0, HSEFR_ERR_INVALID, "mtcnn_pyramid_level_batch: %d frames %dx%d -> %dx%d", frames,
+                  sh, sw, dh, dw);
+    HSEFR_REQUIRE((long long)sh * sw * 3 < (1ll << 31) && (long long)dh * dw * 3 < (1ll << 31), HSEFR_ERR_UNSUPPORTED,
+                  "mtcnn_pyramid_level_batch: a frame of %dx%d or a level of %dx%d leaves 31 bits", sh, sw, dh, dw);
+    return launch_area_level_batch(d_frames, d_dst, frames, sh, sw, dh, dw, (hipStream_t)stream);
+}
+
+int hsefr_mtcnn_stage1_level_batch(const float* prob, const float* reg, int frames, int w, int h, double scale, float thr, double* found,
+                                   int* counters, hsefr_stream_t stream) {
+    HSEFR_REQUIRE(prob && reg && found && counters, HSEFR_ERR_INVALID, "mtcnn_stage1_level_batch: null pointer");
+    return launch_mtcnn_stage1_level_batch(prob, reg, frames, w, h, scale, thr, found, counters, (hipStream_t)stream);
+}
+
+int hsefr_mtcnn_stage1_finish_batch(const double* found, int* counters, double* boxes, int* crop_tables, int frames, int img_w, int img_h,
+                                    hsefr_stream_t stream) {
+    HSEFR_REQUIRE(found && counters && boxes && crop_tables && img_w > 0 && img_h > 0, HSEFR_ERR_INVALID, "mtcnn_stage1_finish_batch: bad argument");
+    return launch_mtcnn_stage1_finish_batch(found, counters, boxes, crop_tables, frames, img_w, img_h, (hipStream_t)stream);
+}
+
+int hsefr_mtcnn_crops_batch(const unsigned char* d_frames, const int* d_tables, const int* d_offsets, float* d_dst, int frames, int sh, int sw,
+                            int n_total, int size, hsefr_stream_t stream) {
+    HSEFR_REQUIRE(n_total == 0 || (d_frames && d_tables && d_offsets && d_dst), HSEFR_ERR_INVALID, "mtcnn_crops_batch: null pointer");
+    return launch_area_crops_batch(d_frames, d_tables, d_offsets, d_dst, frames, mtcnn_post_capacity(), sh, sw, n_total, size, (hipStream_t)stream);
+}
+
+int hsefr_mtcnn_stage_finish_batch(int stage, const double* boxes_in, const int* d_offsets, int n_total, const float* prob, const float* reg,
+                                   const float* pts, float thr, double* boxes_out, int* crop_tables, float* points_out, int* counters, int frames,
+                                   int img_w, int img_h, hsefr_stream_t stream) {
+    HSEFR_REQUIRE(counters && boxes_out && boxes_in && d_offsets && (n_total == 0 || (prob && reg)), HSEFR_ERR_INVALID,
+                  "mtcnn_stage_finish_batch: null pointer");
+    HSEFR_REQUIRE(stage == 2 ? crop_tables != nullptr : (stage == 3 && (n_total == 0 || pts) && points_out), HSEFR_ERR_INVALID,
+                  "mtcnn_stage_finish_batch: stage %d needs %s", stage, stage == 2 ? "crop tables" : "landmarks in and out");
+    return launch_mtcnn_stage23_finish_batch(stage, boxes_in, d_offsets, prob, reg, pts, thr, boxes_out, crop_tables, points_out, counters, frames,
+                                             n_total, img_w, img_h, (hipStream_t)stream);
+}
+
 int hsefr_pairwise_dist(const float* x, const float* y, int n, int m, int d, float* out, hsefr_stream_t stream) {
     HSEFR_REQUIRE(n == 0 || m == 0 || (x && y && out), HSEFR_ERR_INVALID, "pairwise_dist: null pointer");
     return launch_pairwise_dist(x, y, n, m, d, out, (hipStream_t)stream);

@@ -111,9 +111,9 @@ __device__ void square_box(double& x1, double& y1, double& x2, double& y2) {
 extern __shared__ unsigned char post_smem[];
 
 // ---- stage 1, one pyramid level: threshold the face map, boxes of the firing cells, NMS 0.5, append the survivors ----------------
-__global__ __launch_bounds__(NT) void stage1_level_kernel(const float* __restrict__ prob /*[w,h,2]*/, const float* __restrict__ reg /*[w,h,4]*/,
-                                                          int w, int h, double scale, float thr, double* __restrict__ found /*[CAP,9]*/,
-                                                          int* __restrict__ counters) {
+// (the bodies are __device__ functions of ONE frame's pointers; the __global__ entries hand workgroup b the rows of frame b)
+__device__ __forceinline__ void stage1_level_frame(const float* __restrict__ prob /*[w,h,2]*/, const float* __restrict__ reg /*[w,h,4]*/, int w, int h,
+                                                   double scale, float thr, double* __restrict__ found /*[CAP,9]*/, int* __restrict__ counters) {
     PostLds& L = *(PostLds*)post_smem;
     const int tid = threadIdx.x;
     if (tid == 0) L.n = 0;
@@ -163,9 +163,20 @@ __global__ __launch_bounds__(NT) void stage1_level_kernel(const float* __restric
     if (tid == 0) counters[0] = base + nk;
 }
 
+// One workgroup per frame (blockIdx.x) over prob [B,w,h,2], reg [B,w,h,4], found [B,CAP,9], counters [B,8]; one frame is a grid of 1.
+// Here and in the two entries below a frame's workgroup touches its own rows and its own counters only, overflow flag included: what
+// a frame gets does not depend on its neighbours.  PostLds takes 108 KB of the CU's 160 KB, so the B workgroups spread one per CU.
+// (One entry serves both the single-frame and the batched C functions: a second instantiation of each body would take the product
+// library past the size tests/test_abi_cpu.py holds it to.)
+__global__ __launch_bounds__(NT) void stage1_level_kernel(const float* __restrict__ prob, const float* __restrict__ reg, int w, int h, double scale,
+                                                          float thr, double* __restrict__ found, int* __restrict__ counters) {
+    const size_t b = blockIdx.x, cells = (size_t)w * h;
+    stage1_level_frame(prob + b * cells * 2, reg + b * cells * 4, w, h, scale, thr, found + b * CAP * 9, counters + b * 8);
+}
+
 // ---- stage 1, after the last level: NMS 0.7 over all survivors, regression by the P-Net offsets, square, truncate, crop windows ----
-__global__ __launch_bounds__(NT) void stage1_finish_kernel(const double* __restrict__ found, int* __restrict__ counters, double* __restrict__ boxes /*[CAP,5]*/,
-                                                           int* __restrict__ tab /*[CAP,8]*/, int img_w, int img_h) {
+__device__ __forceinline__ void stage1_finish_frame(const double* __restrict__ found, int* __restrict__ counters, double* __restrict__ boxes /*[CAP,5]*/,
+                                                    int* __restrict__ tab /*[CAP,8]*/, int img_w, int img_h) {
     PostLds& L = *(PostLds*)post_smem;
     const int tid = threadIdx.x;
     const int n = counters[0];
@@ -194,14 +205,21 @@ __global__ __launch_bounds__(NT) void stage1_finish_kernel(const double* __restr
     if (tid == 0) counters[1] = nk;
 }
 
+// found [B,CAP,9], counters [B,8] -> boxes [B,CAP,5], tab [B,CAP,8]
+__global__ __launch_bounds__(NT) void stage1_finish_kernel(const double* __restrict__ found, int* __restrict__ counters, double* __restrict__ boxes,
+                                                           int* __restrict__ tab, int img_w, int img_h) {
+    const size_t b = blockIdx.x;
+    stage1_finish_frame(found + b * CAP * 9, counters + b * 8, boxes + b * CAP * 5, tab + b * CAP * 8, img_w, img_h);
+}
+
 // ---- stage 2 / 3 after the net: score filter, NMS 0.7, regression, (stage 2) square + truncate + crop windows, (stage 3) landmarks ----
 // STAGE 2: boxes_out [m,5] = truncated square boxes (score column truncated too, as np.fix(boxes) does), tab_out rows.
 // STAGE 3: regression BEFORE the NMS ('Min' overlap), boxes_out = regressed boxes + score, points_out [m,10] float32.
 template <int STAGE>
-__global__ __launch_bounds__(NT) void stage23_finish_kernel(const double* __restrict__ boxes_in /*[n,5]*/, int n, const float* __restrict__ prob /*[n,2]*/,
-                                                            const float* __restrict__ reg /*[n,4]*/, const float* __restrict__ pts /*[n,10]*/, float thr,
-                                                            double* __restrict__ boxes_out, int* __restrict__ tab_out, float* __restrict__ points_out,
-                                                            int* __restrict__ counters, int img_w, int img_h) {
+__device__ __forceinline__ void stage23_finish_frame(const double* __restrict__ boxes_in /*[n,5]*/, int n, const float* __restrict__ prob /*[n,2]*/,
+                                                     const float* __restrict__ reg /*[n,4]*/, const float* __restrict__ pts /*[n,10]*/, float thr,
+                                                     double* __restrict__ boxes_out, int* __restrict__ tab_out, float* __restrict__ points_out,
+                                                     int* __restrict__ counters, int img_w, int img_h) {
     PostLds& L = *(PostLds*)post_smem;
     const int tid = threadIdx.x;
     if (tid == 0) L.n = 0;
@@ -265,6 +283,29 @@ __global__ __launch_bounds__(NT) void stage23_finish_kernel(const double* __rest
     if (tid == 0) counters[STAGE] = nk;
 }
 
+// offsets == nullptr: one frame, the nets ran on its n boxes.  Otherwise B frames with boxes_in / boxes_out [B,CAP,5], tab_out [B,CAP,8],
+// points_out [B,CAP,10], counters [B,8], and the nets ran on the crops of all frames as one list of n_total rows: rows offsets[b] ..
+// offsets[b + 1] of prob / reg / pts are frame b's, in the order of its boxes_in rows.  An empty range writes count 0; a range that is
+// not inside the list is refused the way a list above the capacity is: flag, count 0, nothing read.
+template <int STAGE>
+__global__ __launch_bounds__(NT) void stage23_finish_kernel(const double* __restrict__ boxes_in, int n, const int* __restrict__ offsets /*[B+1]*/,
+                                                            int n_total, const float* __restrict__ prob, const float* __restrict__ reg,
+                                                            const float* __restrict__ pts, float thr, double* __restrict__ boxes_out,
+                                                            int* __restrict__ tab_out, float* __restrict__ points_out, int* __restrict__ counters,
+                                                            int img_w, int img_h) {
+    const size_t b = blockIdx.x;
+    size_t first = 0;
+    if (offsets) {
+        const int lo = offsets[b], hi = offsets[b + 1];
+        const bool inside = lo >= 0 && lo <= hi && hi <= n_total;
+        first = inside ? (size_t)lo : 0;
+        n = inside ? hi - lo : CAP + 1;
+    }
+    stage23_finish_frame<STAGE>(boxes_in + b * CAP * 5, n, prob + first * 2, reg + first * 4, STAGE == 3 ? pts + first * 10 : nullptr, thr,
+                                boxes_out + b * CAP * 5, STAGE == 2 ? tab_out + b * CAP * 8 : nullptr,
+                                STAGE == 3 ? points_out + b * CAP * 10 : nullptr, counters + b * 8, img_w, img_h);
+}
+
 // a plain NMS over a box list, for the unit tests: keep[] = kept ORIGINAL indices in pick order, *n_keep their number
 __global__ __launch_bounds__(NT) void nms_kernel(const double* __restrict__ boxes /*[n,5]*/, int n, double thr, int use_min, int* __restrict__ keep,
                                                  int* __restrict__ n_keep) {
@@ -298,31 +339,56 @@ int mtcnn_post_capacity() { return CAP; }
 
 int launch_mtcnn_stage1_level(const float* prob, const float* reg, int w, int h, double scale, float thr, double* found, int* counters,
                               hipStream_t s) {
-    HSEFR_REQUIRE(w > 0 && h > 0 && scale > 0 && (long long)w * h < (1ll << 31), HSEFR_ERR_INVALID, "mtcnn_stage1_level: bad map %dx%d", w, h);
-    if (int rc = set_lds(stage1_level_kernel)) return rc;
-    HSEFR_LAUNCH(stage1_level_kernel, dim3(1), dim3(NT), sizeof(PostLds), s, prob, reg, w, h, scale, thr, found, counters);
-    return launch_status("mtcnn_stage1_level");
+    return launch_mtcnn_stage1_level_batch(prob, reg, 1, w, h, scale, thr, found, counters, s);
 }
 
 int launch_mtcnn_stage1_finish(const double* found, int* counters, double* boxes, int* tab, int img_w, int img_h, hipStream_t s) {
-    if (int rc = set_lds(stage1_finish_kernel)) return rc;
-    HSEFR_LAUNCH(stage1_finish_kernel, dim3(1), dim3(NT), sizeof(PostLds), s, found, counters, boxes, tab, img_w, img_h);
-    return launch_status("mtcnn_stage1_finish");
+    return launch_mtcnn_stage1_finish_batch(found, counters, boxes, tab, 1, img_w, img_h, s);
+}
+
+static int launch_stage23(int stage, const double* boxes_in, int n, const int* offsets, int n_total, const float* prob, const float* reg,
+                          const float* pts, float thr, double* boxes_out, int* tab_out, float* points_out, int* counters, int frames, int img_w,
+                          int img_h, hipStream_t s) {
+    if (stage == 2) {
+        if (int rc = set_lds(stage23_finish_kernel<2>)) return rc;
+        HSEFR_LAUNCH(stage23_finish_kernel<2>, dim3(frames), dim3(NT), sizeof(PostLds), s, boxes_in, n, offsets, n_total, prob, reg, pts, thr,
+                           boxes_out, tab_out, points_out, counters, img_w, img_h);
+    } else {
+        if (int rc = set_lds(stage23_finish_kernel<3>)) return rc;
+        HSEFR_LAUNCH(stage23_finish_kernel<3>, dim3(frames), dim3(NT), sizeof(PostLds), s, boxes_in, n, offsets, n_total, prob, reg, pts, thr,
+                           boxes_out, tab_out, points_out, counters, img_w, img_h);
+    }
+    return launch_status("mtcnn_stage_finish");
 }
 
 int launch_mtcnn_stage23_finish(int stage, const double* boxes_in, int n, const float* prob, const float* reg, const float* pts, float thr,
                                 double* boxes_out, int* tab_out, float* points_out, int* counters, int img_w, int img_h, hipStream_t s) {
     HSEFR_REQUIRE((stage == 2 || stage == 3) && n >= 0, HSEFR_ERR_INVALID, "mtcnn_stage_finish: stage %d, n %d", stage, n);
-    if (stage == 2) {
-        if (int rc = set_lds(stage23_finish_kernel<2>)) return rc;
-        HSEFR_LAUNCH(stage23_finish_kernel<2>, dim3(1), dim3(NT), sizeof(PostLds), s, boxes_in, n, prob, reg, pts, thr, boxes_out, tab_out,
-                           points_out, counters, img_w, img_h);
-    } else {
-        if (int rc = set_lds(stage23_finish_kernel<3>)) return rc;
-        HSEFR_LAUNCH(stage23_finish_kernel<3>, dim3(1), dim3(NT), sizeof(PostLds), s, boxes_in, n, prob, reg, pts, thr, boxes_out, tab_out,
-                           points_out, counters, img_w, img_h);
-    }
-    return launch_status("mtcnn_stage_finish");
+    return launch_stage23(stage, boxes_in, n, nullptr, n, prob, reg, pts, thr, boxes_out, tab_out, points_out, counters, 1, img_w, img_h, s);
+}
+
+int launch_mtcnn_stage1_level_batch(const float* prob, const float* reg, int frames, int w, int h, double scale, float thr, double* found,
+                                    int* counters, hipStream_t s) {
+    HSEFR_REQUIRE(frames >= 1 && w > 0 && h > 0 && scale > 0 && (long long)w * h < (1ll << 31), HSEFR_ERR_INVALID,
+                  "mtcnn_stage1_level: %d frames, bad map %dx%d", frames, w, h);
+    if (int rc = set_lds(stage1_level_kernel)) return rc;
+    HSEFR_LAUNCH(stage1_level_kernel, dim3(frames), dim3(NT), sizeof(PostLds), s, prob, reg, w, h, scale, thr, found, counters);
+    return launch_status("mtcnn_stage1_level");
+}
+
+int launch_mtcnn_stage1_finish_batch(const double* found, int* counters, double* boxes, int* tab, int frames, int img_w, int img_h, hipStream_t s) {
+    HSEFR_REQUIRE(frames >= 1, HSEFR_ERR_INVALID, "mtcnn_stage1_finish: %d frames", frames);
+    if (int rc = set_lds(stage1_finish_kernel)) return rc;
+    HSEFR_LAUNCH(stage1_finish_kernel, dim3(frames), dim3(NT), sizeof(PostLds), s, found, counters, boxes, tab, img_w, img_h);
+    return launch_status("mtcnn_stage1_finish");
+}
+
+int launch_mtcnn_stage23_finish_batch(int stage, const double* boxes_in, const int* offsets, const float* prob, const float* reg, const float* pts,
+                                      float thr, double* boxes_out, int* tab_out, float* points_out, int* counters, int frames, int n_total, int img_w,
+                                      int img_h, hipStream_t s) {
+    HSEFR_REQUIRE((stage == 2 || stage == 3) && frames >= 1 && n_total >= 0 && offsets, HSEFR_ERR_INVALID,
+                  "mtcnn_stage_finish: stage %d, %d frames, %d rows", stage, frames, n_total);
+    return launch_stage23(stage, boxes_in, 0, offsets, n_total, prob, reg, pts, thr, boxes_out, tab_out, points_out, counters, frames, img_w, img_h, s);
 }
 
 int launch_mtcnn_nms(const double* boxes, int n, double thr, int use_min, int* keep, int* n_keep, hipStream_t s) {

@@ -136,6 +136,14 @@ class FacialImageProcessing:
                                       "(bounding_boxes, points); the MTCNN cascade is the step before this path")
         return self.detector(img)
 
+    def detect_faces_batch(self, imgs, max_frames: int = 32):
+        """detect_faces for a list of RGB frames -> [(bounding_boxes, points)] in list order: one call of the detector's
+        ``detect_batch`` where it has one (MTCNNDetector: same-size frames share their launches), a loop over detect_faces otherwise."""
+        batch = getattr(self.detector, "detect_batch", None)
+        if batch is None:
+            return [self.detect_faces(img) for img in imgs]       # (no detector at all: raises as detect_faces does)
+        return batch(imgs, max_frames=max_frames)
+
     # ---- facial_analysis.py:225-294 -----------------------------------------------------------------
     @staticmethod
     def face_boxes(bounding_boxes, img_w: int, img_h: int) -> List[List[int]]:
@@ -161,14 +169,19 @@ class FacialImageProcessing:
                 out.append(box)
         return out
 
-    def process_image(self, draw, bounding_boxes=None, points=None):
-        """draw: BGR uint8 frame, as cv2.imread returns it (:225-226).  Detection runs unless
-        ``bounding_boxes`` is supplied.  Returns (bboxes, points, ages, genders, facial_features)."""
+    @staticmethod
+    def _bgr_to_rgb(draw) -> np.ndarray:
         draw = np.asarray(draw)
         # cv2.cvtColor(draw, COLOR_BGR2RGB): plane by plane (np.ascontiguousarray(draw[..., ::-1]) walks a 3-element inner loop with
         # a negative stride: 1.2 ms for a 784x588 frame, a quarter of this call, against 0.3 ms)
         img = np.empty(draw.shape, draw.dtype)
         img[..., 0], img[..., 1], img[..., 2] = draw[..., 2], draw[..., 1], draw[..., 0]
+        return img
+
+    def process_image(self, draw, bounding_boxes=None, points=None):
+        """draw: BGR uint8 frame, as cv2.imread returns it (:225-226).  Detection runs unless
+        ``bounding_boxes`` is supplied.  Returns (bboxes, points, ages, genders, facial_features)."""
+        img = self._bgr_to_rgb(draw)
         t = time.time()
         if bounding_boxes is None:
             bounding_boxes, points = self.detect_faces(img)
@@ -183,3 +196,30 @@ class FacialImageProcessing:
         if self.print_stat:
             print('age gender elapsed', time.time() - t)
         return bboxes, points if points is not None else [], ages, genders, facial_features
+
+    def process_images(self, draws, max_frames: int = 32):
+        """process_image for a list of BGR uint8 frames (the photos of an album, the frames of a video: process_photos.py:92-118,
+        :238-247) -> a list of process_image's 5-tuples, in list order.  One detect_faces_batch call over all frames, then ONE
+        age_gender_batch call over the crops of all frames on the bulk plan (it chunks by max_batch itself), split back per frame.
+        With latency_plan=False process_image runs the same plan and the results are equal bit for bit; the small-batch plan of
+        latency_plan=True differs from them in the last bits (see __init__)."""
+        from .mtcnn import split_by_counts
+        imgs = [self._bgr_to_rgb(d) for d in draws]
+        t = time.time()
+        detections = self.detect_faces_batch(imgs, max_frames=max_frames)
+        if self.print_stat:
+            print('detection elapsed', time.time() - t)
+        all_bboxes, crops = [], []
+        for img, (bounding_boxes, _) in zip(imgs, detections):
+            img_h, img_w, _ = img.shape
+            bboxes = self.face_boxes(bounding_boxes, img_w, img_h)
+            all_bboxes.append(bboxes)
+            crops += [img[y1:y2, x1:x2, :] for (x1, y1, x2, y2) in bboxes]
+        t = time.time()
+        ages, genders, features = self.age_gender_batch(crops, latency=False) if crops else ([], [], [])
+        if self.print_stat:
+            print('age gender elapsed', time.time() - t)
+        counts = [len(b) for b in all_bboxes]
+        return [(bboxes, points if points is not None else [], a, g, f)
+                for bboxes, (_, points), a, g, f in zip(all_bboxes, detections, split_by_counts(ages, counts), split_by_counts(genders, counts),
+                                                        split_by_counts(features, counts))]

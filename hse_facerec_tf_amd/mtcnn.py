@@ -16,6 +16,8 @@ from ONE upload of the frame (csrc/area_resize.hip: hsefr_mtcnn_pyramid_level / 
 (threshold, NMS over a few hundred boxes, regression, squaring, window clipping) is host NumPy, written to give the
 reference's numbers including its conventions: boxes are 1-based inclusive, ``np.fix`` truncation.
 ``device_resize=False`` keeps the round-1 path (host resizes through preprocess.resize_area).
+``MTCNNDetector.detect_batch`` runs same-size frames through that launch sequence together (the ``*_batch`` entry points of
+include/hsefr.h), each frame's result bit for bit its single-frame result.
 """
 from __future__ import annotations
 
@@ -329,6 +331,37 @@ def stage3_finish(boxes_in: np.ndarray, prob: np.ndarray, reg: np.ndarray, pts: 
     return boxes, np.ascontiguousarray(points.T)
 
 
+# ---- bookkeeping of the batched entry points (pure functions: tests/test_mtcnn_batch_cpu.py) ----------------------------------------
+def plan_passes(shapes, max_frames: int) -> List[Tuple[Tuple[int, int], List[int]]]:
+    """The passes of ``MTCNNDetector.detect_batch`` over frames of the given (h, w): frames of one size form a group (groups in the
+    order their first frame appears, a group's frames in list order), a group runs in passes of at most ``max_frames`` frames.
+    -> [((h, w), [indices into the list])]; every index appears exactly once."""
+    max_frames = int(max_frames)
+    if max_frames < 1:
+        raise ValueError("max_frames must be at least 1, not %d" % max_frames)
+    groups: Dict[Tuple[int, int], List[int]] = {}
+    for i, hw in enumerate(shapes):
+        groups.setdefault((int(hw[0]), int(hw[1])), []).append(i)
+    return [(hw, idx[a:a + max_frames]) for hw, idx in groups.items() for a in range(0, len(idx), max_frames)]
+
+
+def split_by_counts(items, counts) -> List[list]:
+    """A flat list that holds ``counts[0]`` items of frame 0, then ``counts[1]`` of frame 1, ... -> one list per frame."""
+    items = list(items)
+    if sum(int(c) for c in counts) != len(items):
+        raise ValueError("%d items for counts that sum to %d" % (len(items), sum(int(c) for c in counts)))
+    out, at = [], 0
+    for c in counts:
+        out.append(items[at:at + int(c)])
+        at += int(c)
+    return out
+
+
+def empty_detection() -> Tuple[np.ndarray, np.ndarray]:
+    """What detect_batch returns for a frame without faces."""
+    return np.empty((0, 5), np.float64), np.empty((10, 0), np.float32)
+
+
 class MTCNNDetector:
     """callable(img_rgb_uint8) -> (bounding_boxes [n,5] = x1,y1,x2,y2,score; points [10,n])."""
 
@@ -487,6 +520,145 @@ class MTCNNDetector:
             if n3 == 0:
                 return np.empty((0, 5)), np.empty((10, 0), np.float32)
             return boxes3[:n3].cpu().numpy(), np.ascontiguousarray(points3[:n3].cpu().numpy().T)
+
+    # ---- many frames per pass (csrc/mtcnn_post.hip, the *_batch entries) -----------------------------------------------------------
+    def _batch_work_tensors(self, cap: int, n_frames: int):
+        """_work_tensors for a pass of n_frames frames: [frames, cap, .] lists per detector and thread, grown to the largest pass seen
+        (a pass takes the first n_frames frames' rows, which are contiguous)."""
+        import threading
+        torch, dev = self._torch, self.device
+        if self._work is None:
+            self._work = threading.local()
+        wk = self._work
+        if getattr(wk, "bcap", None) != cap or wk.bframes < n_frames:
+            wk.bcap, wk.bframes = cap, n_frames
+            wk.bfound = torch.empty((n_frames, cap, 9), dtype=torch.float64, device=dev)
+            wk.bboxes = [torch.empty((n_frames, cap, 5), dtype=torch.float64, device=dev) for _ in range(3)]
+            wk.btab = torch.empty((n_frames, cap, 8), dtype=torch.int32, device=dev)
+            wk.bpoints = torch.empty((n_frames, cap, 10), dtype=torch.float32, device=dev)
+        return wk
+
+    def _detect_pass(self, imgs: List[np.ndarray]) -> List[Optional[Tuple[np.ndarray, np.ndarray]]]:
+        """One pass over same-size frames: the launches of _detect_device, each covering every frame, and three read-backs.  Per
+        frame (boxes, points), or None where that frame's candidate list overflowed (the caller redoes that frame alone).
+
+        Bit identity with _detect_device frame by frame: the pyramid, the crops and the box logic compute a frame's values from that
+        frame's data by the same operations (the kernels take the frame as a grid index); the nets run on the stacked levels and on
+        the concatenated crop lists, and conv2d_direct, maxpool_f32 and softmax (csrc/smallnet.hip) compute each output element from
+        its own image alone in a fixed FMA order, so a row's values do not depend on the batch it stands in
+        (tests/test_mtcnn_batch_gpu.py checks both)."""
+        torch, L = self._torch, _lib.lib()
+        n_frames = len(imgs)
+        h, w = imgs[0].shape[:2]
+        cap = int(L.hsefr_mtcnn_post_capacity())
+        dev = self.device
+        results: List[Optional[Tuple[np.ndarray, np.ndarray]]] = [empty_detection() for _ in range(n_frames)]
+        stack = torch.from_numpy(np.stack(imgs)).to(dev)                   # one upload per pass
+        with _lib.on_device(stack):
+            st = _lib.current_stream_ptr()
+            wk = self._batch_work_tensors(cap, n_frames)
+            counters = torch.zeros((n_frames, 8), dtype=torch.int32, device=dev)
+            found, (boxes1, boxes2, boxes3), tab, points3 = wk.bfound, wk.bboxes, wk.btab, wk.bpoints
+            thr = [float(np.float32(t)) for t in self.THRESHOLDS]
+            for scale in self.pyramid_scales(h, w):
+                hs, ws = int(np.ceil(h * scale)), int(np.ceil(w * scale))
+                level = torch.empty((n_frames, ws, hs, 3), dtype=torch.float32, device=dev)
+                _lib.check(L.hsefr_mtcnn_pyramid_level_batch(stack.data_ptr(), level.data_ptr(), n_frames, h, w, hs, ws, st),
+                           "hsefr_mtcnn_pyramid_level_batch")
+                reg_t, prob_t = self.pnet(level)
+                reg_t, prob_t = reg_t.contiguous(), prob_t.contiguous()
+                _lib.check(L.hsefr_mtcnn_stage1_level_batch(prob_t.data_ptr(), reg_t.data_ptr(), n_frames, int(prob_t.shape[1]), int(prob_t.shape[2]),
+                                                            float(scale), thr[0], found.data_ptr(), counters.data_ptr(), st),
+                           "hsefr_mtcnn_stage1_level_batch")
+            _lib.check(L.hsefr_mtcnn_stage1_finish_batch(found.data_ptr(), counters.data_ptr(), boxes1.data_ptr(), tab.data_ptr(), n_frames, w, h, st),
+                       "hsefr_mtcnn_stage1_finish_batch")
+            c = counters.cpu().numpy()                                     # read-back 1
+            over = c[:, 4] != 0                                            # (only a pyramid level can overflow: later lists are no longer)
+            for b in np.nonzero(over)[0]:
+                results[int(b)] = None
+
+            def offsets_of(counts):                                        # host scan of the counts just read; a 4(B+1)-byte upload
+                counts = np.where(over, 0, counts).astype(np.int64)
+                off = np.concatenate([[0], np.cumsum(counts)])
+                return int(off[-1]), torch.from_numpy(off.astype(np.int32)).to(dev)
+
+            total, d_off = offsets_of(c[:, 1])
+            if total == 0:
+                return results
+            crops = torch.empty((total, 24, 24, 3), dtype=torch.float32, device=dev)
+            _lib.check(L.hsefr_mtcnn_crops_batch(stack.data_ptr(), tab.data_ptr(), d_off.data_ptr(), crops.data_ptr(), n_frames, h, w, total, 24, st),
+                       "hsefr_mtcnn_crops_batch")
+            reg_t, prob_t = self.rnet(crops)
+            reg_t, prob_t = reg_t.contiguous(), prob_t.contiguous()
+            _lib.check(L.hsefr_mtcnn_stage_finish_batch(2, boxes1.data_ptr(), d_off.data_ptr(), total, prob_t.data_ptr(), reg_t.data_ptr(), None, thr[1],
+                                                        boxes2.data_ptr(), tab.data_ptr(), None, counters.data_ptr(), n_frames, w, h, st),
+                       "hsefr_mtcnn_stage_finish_batch")
+            c = counters.cpu().numpy()                                     # read-back 2
+            n2 = np.where(over, 0, c[:, 2])
+            total, d_off = offsets_of(c[:, 2])
+            if total == 0:
+                return results
+            crops = torch.empty((total, 48, 48, 3), dtype=torch.float32, device=dev)
+            _lib.check(L.hsefr_mtcnn_crops_batch(stack.data_ptr(), tab.data_ptr(), d_off.data_ptr(), crops.data_ptr(), n_frames, h, w, total, 48, st),
+                       "hsefr_mtcnn_crops_batch")
+            reg_t, pts_t, prob_t = self.onet(crops)
+            reg_t, pts_t, prob_t = reg_t.contiguous(), pts_t.contiguous(), prob_t.contiguous()
+            _lib.check(L.hsefr_mtcnn_stage_finish_batch(3, boxes2.data_ptr(), d_off.data_ptr(), total, prob_t.data_ptr(), reg_t.data_ptr(),
+                                                        pts_t.data_ptr(), thr[2], boxes3.data_ptr(), None, points3.data_ptr(), counters.data_ptr(),
+                                                        n_frames, w, h, st), "hsefr_mtcnn_stage_finish_batch")
+            # read-back 3: the counts and the first max(n2) rows of every frame's lists (stage 3 keeps at most its n2 inputs) as one copy
+            m = int(n2.max())
+            packed = torch.cat([counters.view(torch.uint8).reshape(-1), boxes3[:n_frames, :m].contiguous().view(torch.uint8).reshape(-1),
+                                points3[:n_frames, :m].contiguous().view(torch.uint8).reshape(-1)]).cpu().numpy()
+        at_boxes = n_frames * 32
+        at_points = at_boxes + n_frames * m * 40
+        c = np.frombuffer(packed, np.int32, n_frames * 8, 0).reshape(n_frames, 8)
+        boxes = np.frombuffer(packed, np.float64, n_frames * m * 5, at_boxes).reshape(n_frames, m, 5)
+        points = np.frombuffer(packed, np.float32, n_frames * m * 10, at_points).reshape(n_frames, m, 10)
+        for b in range(n_frames):
+            n3 = int(c[b, 3])
+            if results[b] is not None and n3 > 0:
+                results[b] = (boxes[b, :n3].copy(), np.ascontiguousarray(points[b, :n3].T))
+        return results
+
+    def _check_frame(self, img) -> np.ndarray:
+        """The input rules of __call__."""
+        img = np.asarray(img)
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError("the detector takes an RGB frame [H, W, 3]")
+        if self.device_resize and img.dtype != np.uint8:
+            raise ValueError("device_resize takes a uint8 RGB frame [H, W, 3]; construct the detector with device_resize=False "
+                             "for %s frames" % img.dtype)
+        return img
+
+    def _alone(self, img: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """self(img) with detect_batch's empty shapes."""
+        boxes, points = self(img)
+        return (boxes, points) if boxes.shape[0] else empty_detection()
+
+    def detect_batch(self, frames, max_frames: int = 32) -> List[Tuple[np.ndarray, np.ndarray]]:
+        """[(boxes [n,5] float64, points [10,n] float32)] in the order of ``frames`` (uint8 RGB [H, W, 3] each), every entry bit for bit
+        what ``self(frame)`` returns; a frame without faces gives shapes (0, 5) and (10, 0).  Frames of one size run together, at most
+        ``max_frames`` per pass: one upload, the launches of one frame and three read-backs per pass (a pass of ONE frame is the
+        single-frame call).  A frame whose candidate list
+        overflows the device capacity is redone alone through ``self(frame)`` (counted in ``host_fallbacks``); the others of its pass
+        keep their results.  A detector without ``device_boxes`` has no batched path and runs the frames one by one."""
+        imgs = [self._check_frame(f) for f in frames]
+        passes = plan_passes([f.shape[:2] for f in imgs], max_frames)
+        if not self.device_boxes:
+            return [self._alone(f) for f in imgs]
+        results: List[Optional[Tuple[np.ndarray, np.ndarray]]] = [None] * len(imgs)
+        for (h, w), idx in passes:
+            if not self.pyramid_scales(h, w):                              # smaller than minsize: no level, no launch
+                for i in idx:
+                    results[i] = empty_detection()
+                continue
+            if len(idx) == 1:                                              # nothing to share: the single-frame call, without the stacking
+                results[idx[0]] = self._alone(imgs[idx[0]])
+                continue
+            for i, res in zip(idx, self._detect_pass([imgs[i] for i in idx])):
+                results[i] = res if res is not None else self._alone(imgs[i])
+        return results
 
     def __call__(self, img: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
         img = np.asarray(img)

@@ -778,6 +778,32 @@ int hsefr_mtcnn_nms(const double* boxes, int n, double thr, int use_min, int* ke
 int hsefr_mtcnn_crops(const unsigned char* d_frame, const int* d_boxes, float* d_dst, int sh, int sw, int n, int size,
                       hsefr_stream_t stream);
 
+/* The cascade over a stack of B same-size frames, d_frames uint8 [B,sh,sw,3]: the launches of one frame, each covering all B.  Every
+ * frame's outputs are, bit for bit, what the single-frame entry point above gives for that frame alone.  One workgroup per frame
+ * runs the box logic on that frame's rows of found [B,cap,9], boxes [B,cap,5], crop tables [B,cap,8], points [B,cap,10] and
+ * counters [B,8] (cap = hsefr_mtcnn_post_capacity(); counters zeroed by the caller per pass); counters[b][4] is frame b's overflow flag
+ * and touches no other frame.  Levels are launched one after another, as for one frame: the order of a frame's found rows is the
+ * levels' order.  B >= 1.
+ *   pyramid_level_batch: d_dst float32 [B,dw,dh,3]
+ *   stage1_level_batch : prob [B,w,h,2], reg [B,w,h,4]
+ *   stage1_finish_batch: counters[b][1] = boxes of frame b
+ *   crops_batch        : the crops of all frames as one list d_dst [n_total,size,size,3]; rows d_offsets[b] .. d_offsets[b+1] are cut
+ *                        from frame b by rows 0 .. of its crop table.  d_offsets int32 [B+1] on the device, ascending from 0 to n_total
+ *   stage_finish_batch : prob [n_total,2], reg [n_total,4], pts [n_total,10] in the order of that list; frame b reads its own range
+ *                        (more than cap rows, or a range outside 0 .. n_total: flag and count 0) and its rows of boxes_in [B,cap,5]
+ * Sizes whose products leave 31 bits where the kernels index with int are refused (HSEFR_ERR_UNSUPPORTED). */
+int hsefr_mtcnn_pyramid_level_batch(const unsigned char* d_frames, float* d_dst, int frames, int sh, int sw, int dh, int dw,
+                                    hsefr_stream_t stream);
+int hsefr_mtcnn_stage1_level_batch(const float* prob, const float* reg, int frames, int w, int h, double scale, float thr, double* found,
+                                   int* counters, hsefr_stream_t stream);
+int hsefr_mtcnn_stage1_finish_batch(const double* found, int* counters, double* boxes, int* crop_tables, int frames, int img_w, int img_h,
+                                    hsefr_stream_t stream);
+int hsefr_mtcnn_crops_batch(const unsigned char* d_frames, const int* d_tables, const int* d_offsets, float* d_dst, int frames, int sh, int sw,
+                            int n_total, int size, hsefr_stream_t stream);
+int hsefr_mtcnn_stage_finish_batch(int stage, const double* boxes_in, const int* d_offsets, int n_total, const float* prob, const float* reg,
+                                   const float* pts, float thr, double* boxes_out, int* crop_tables, float* points_out, int* counters, int frames,
+                                   int img_w, int img_h, hsefr_stream_t stream);
+
 /* hsefr_conv2d_f32 as an implicit GEMM on the fp32 matrix pipe (v_mfma_f32_32x32x2_f32: exact fp32 FMA chains, 155 TFLOP/s):
  * same arguments and results to fp32 round-off (another summation order); cout multiple of 64.  What HSEFR_OP_CONV_F32 runs
  * when it covers the layer (csrc/conv_f32_mfma.hip): the fp32-grade mode of vgg2_resnet.pb (facerec_test.py:213). */
