@@ -122,6 +122,16 @@ DEV_SIGNATURES = {
 }
 
 
+# libhsefr_album.so (include/hsefr_album.h): the album organiser's device code, a library of its own.  HSEFR_ALBUM_LIB selects another build
+ALBUM_LIB_PATH = os.path.join(_HERE, os.environ.get("HSEFR_ALBUM_LIB", "libhsefr_album.so"))
+_album_lib = None
+ALBUM_SIGNATURES = {
+    "hsefr_album_version": (c_int, []),
+    "hsefr_album_last_error_string": (c_char_p, []),
+    "hsefr_album_face_crops": (c_int, [_fp, c_int, c_int, c_int, c_void_p, c_int, _fp, c_int, c_int, c_void_p]),
+}
+
+
 class HsefrError(RuntimeError):
     pass
 
@@ -150,6 +160,34 @@ def lib() -> ctypes.CDLL:
     return _lib
 
 
+def album_lib() -> ctypes.CDLL:
+    """Load libhsefr_album.so once (torch first, as lib() does and for the same reason).  Missing is an error: there is no fallback."""
+    global _album_lib
+    if _album_lib is None:
+        import torch  # noqa: F401
+        if not os.path.exists(ALBUM_LIB_PATH):
+            raise ImportError("%s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                              "(hipcc --offload-arch=gfx950). There is no CPU fallback." % ALBUM_LIB_PATH)
+        L = ctypes.CDLL(ALBUM_LIB_PATH)
+        for name, (res, args) in ALBUM_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        _album_lib = L
+    return _album_lib
+
+
+def album_last_error() -> str:
+    s = album_lib().hsefr_album_last_error_string()
+    return s.decode("utf-8", "replace") if s else ""
+
+
+def album_check(status: int, what: str = "") -> None:
+    """check() for a status of libhsefr_album.so (its own error string)."""
+    if status != OK:
+        _raise(status, "%s%s (hsefr_album status %d)" % (what + ": " if what else "", album_last_error(), status))
+
+
 def last_error() -> str:
     s = lib().hsefr_last_error_string()
     return s.decode("utf-8", "replace") if s else ""
@@ -158,7 +196,10 @@ def last_error() -> str:
 def check(status: int, what: str = "") -> None:
     if status == OK:
         return
-    msg = "%s%s (hsefr status %d)" % (what + ": " if what else "", last_error(), status)
+    _raise(status, "%s%s (hsefr status %d)" % (what + ": " if what else "", last_error(), status))
+
+
+def _raise(status: int, msg: str) -> None:
     if status == ERR_SHAPE or status == ERR_INVALID:
         raise ValueError(msg)
     if status == ERR_UNSUPPORTED:

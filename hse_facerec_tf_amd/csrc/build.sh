@@ -1,5 +1,6 @@
 #!/bin/bash
-# Builds libhsefr.so for gfx950 in-tree (hipcc cross-compiles without a GPU).
+# Builds libhsefr.so for gfx950 in-tree (hipcc cross-compiles without a GPU), and right after it libhsefr_album.so (include/hsefr_album.h:
+# the album organiser's device code, a library of its own because libhsefr.so is held below 4 MB by its tests).
 #   HSEFR_DEV=1 build.sh   builds libhsefr_dev.so instead: the same sources with -DHSEFR_DEV (tuning knobs as run-time
 #                          variables, hsefr_debug_*, the calibration kernels of devtools.hip) -- for tools/kbench.py only.
 set -euo pipefail
@@ -14,6 +15,10 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -Wall -Wno
 # tests/test_abi_cpu.py): the runtime, the profilers and tools/isa_lint.py need only the kernel symbols, which stay
 DEVICE_STRIP="-Xoffload-linker --discard-all"
 LINK="--offload-arch=gfx950"
+# libhsefr_album.so: its own source list, the same flags in every mode (no -DHSEFR_DEV code in it).  -ffp-contract=off: album.hip computes
+# OpenCV's resize taps in the kernel, where a product fused with the subtraction behind it would round once instead of twice
+ALBUM_SRCS="album.hip"
+ALBUM_FLAGS="$FLAGS $DEVICE_STRIP -ffp-contract=off"
 LINT=1
 HOST_STRIP=0
 HOST_SIZE_FLAGS=""
@@ -76,3 +81,25 @@ else
   hipcc $SAN_EXE_FLAGS -x c++ fuzz_plan.cc -o "$BUILD/fuzz_plan" -L"$BUILD" -lhsefr_asan -Wl,-rpath,"$(realpath $BUILD)"
 fi
 echo "built $(realpath $OUT)"
+if [ "$LINT" = "1" ]; then
+  # the second library (product and development builds alike; the host-only sanitizer recipe above has nothing of it): built, stripped
+  # and linted as the first
+  ALBUM_OUT=../libhsefr_album.so
+  ALBUM_OBJS=""
+  for s in $ALBUM_SRCS; do
+    o="$BUILD/${s%.hip}.o"
+    stale=0
+    for dep in "$s" ../../include/hsefr_album.h build.sh; do
+      if [ ! -f "$o" ] || [ "$dep" -nt "$o" ]; then stale=1; fi
+    done
+    if [ "$stale" = 1 ]; then
+      rm -f "$o"
+      hipcc $ALBUM_FLAGS -Xarch_host -Os ${HSEFR_EXTRA_FLAGS:-} -c "$s" -o "$o"
+    fi
+    ALBUM_OBJS="$ALBUM_OBJS $o"
+  done
+  hipcc $LINK -shared -fPIC -o "$ALBUM_OUT" $ALBUM_OBJS
+  /opt/rocm/lib/llvm/bin/llvm-strip --strip-all -w --keep-symbol='_ZN*_kernel*' --keep-symbol='!*__device_stub__*' "$ALBUM_OUT"
+  python3 ../../tools/isa_lint.py "$ALBUM_OUT"
+  echo "built $(realpath $ALBUM_OUT)"
+fi

@@ -197,16 +197,78 @@ class FacialImageProcessing:
             print('age gender elapsed', time.time() - t)
         return bboxes, points if points is not None else [], ages, genders, facial_features
 
-    def process_images(self, draws, max_frames: int = 32):
+    def _forward_u8_batch(self, x8):
+        """age_gender_batch's forward and read-back for resized faces that are already on the device: ``x8`` CUDA uint8 [m, h, w, 3]
+        RGB, in chunks of max_batch on the bulk plan -> (ages, genders, features)."""
+        torch = _lib.require_gpu()
+        ages, genders, feats = [], [], []
+        mb = self.sess.max_batch
+        for i in range(0, int(x8.shape[0]), mb):
+            r = self.sess.forward_u8(x8[i:i + mb], (OUT_FEATURES, OUT_AGE, OUT_GENDER), latency=False)
+            packed = torch.cat([r["age_probs"], r["gender"], r["features"]], dim=1).cpu().numpy()
+            na, ng = r["age_probs"].shape[1], r["gender"].shape[1]
+            age_p, gen, fea = packed[:, :na], packed[:, na:na + ng].copy(), packed[:, na + ng:].copy()
+            for j in range(packed.shape[0]):
+                ages.append(decode_age(age_p[j])[0])
+                genders.append(gen[j])
+                feats.append(fea[j])
+        return ages, genders, feats
+
+    def _resized_faces(self, imgs, all_bboxes, sources):
+        """The resized faces of process_images on the device, CUDA uint8 [m, h, w, 3] RGB in list order.  The frames of a detector
+        pass (``sources[i]`` = the pass's stack on the device and the frame's row in it) are cut from that stack by ONE launch per pass
+        (preprocess_device.face_crops: one [m, 5] table uploaded, no frame and no crop uploaded again, no launch per crop size); the
+        frames that took the single-frame call are cut on the host and resized by preprocess_faces_cv, as without device_crops."""
+        from . import preprocess_device
+        torch = _lib.require_gpu()
+        counts = [len(b) for b in all_bboxes]
+        starts = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        x8 = torch.empty((int(starts[-1]), self.h, self.w, 3), dtype=torch.uint8, device=self.sess.device)
+        passes, alone = {}, []                      # id(stack) -> (stack, [frame index]) in list order
+        for i, src in enumerate(sources):
+            if not counts[i]:
+                continue
+            if src is None:
+                alone.append(i)
+            else:
+                passes.setdefault(id(src[0]), (src[0], []))[1].append(i)
+        for stack, idx in passes.values():
+            table = np.array([[sources[i][1]] + list(box) for i in idx for box in all_bboxes[i]], dtype=np.int32)
+            where = np.concatenate([np.arange(starts[i], starts[i + 1]) for i in idx])
+            if where[-1] - where[0] + 1 == len(where):            # the pass's faces stand together in the batch: written in place
+                preprocess_device.face_crops(stack, table, (self.h, self.w), out=x8[int(where[0]):int(where[-1]) + 1])
+            else:
+                x8[torch.from_numpy(where).to(x8.device)] = preprocess_device.face_crops(stack, table, (self.h, self.w))
+        if alone:
+            crops = [imgs[i][y1:y2, x1:x2, :] for i in alone for (x1, y1, x2, y2) in all_bboxes[i]]
+            where = np.concatenate([np.arange(starts[i], starts[i + 1]) for i in alone])
+            x8[torch.from_numpy(where).to(x8.device)] = preprocess_device.preprocess_faces_cv(crops, (self.h, self.w), device=self.sess.device,
+                                                                                           raw_u8=True)
+        return x8
+
+    def process_images(self, draws, max_frames: int = 32, device_crops: bool = False, return_crops: bool = False):
         """process_image for a list of BGR uint8 frames (the photos of an album, the frames of a video: process_photos.py:92-118,
         :238-247) -> a list of process_image's 5-tuples, in list order.  One detect_faces_batch call over all frames, then ONE
         age_gender_batch call over the crops of all frames on the bulk plan (it chunks by max_batch itself), split back per frame.
         With latency_plan=False process_image runs the same plan and the results are equal bit for bit; the small-batch plan of
-        latency_plan=True differs from them in the last bits (see __init__)."""
+        latency_plan=True differs from them in the last bits (see __init__).
+        device_crops: the faces are cut and resized on the device from the frame stacks the detector's passes uploaded (_resized_faces)
+        instead of cut on the host and uploaded again grouped by size; the same bytes reach the net in the same batches, so the results
+        are those of device_crops=False bit for bit.  Needs device_preprocess=True and an engine that takes bytes (ValueError otherwise,
+        before any device work).
+        return_crops: -> (that list, crops) with crops[i] the frame's resized faces, RGB uint8 [n_i, h, w, 3] (process_photos.py:38's
+        facial_images up to channel order), read back in one copy."""
         from .mtcnn import split_by_counts
+        byte_path = self.device_preprocess and self.sess.accepts_u8
+        if device_crops and not byte_path:
+            raise ValueError("device_crops needs device_preprocess=True and an engine that accepts bytes")
         imgs = [self._bgr_to_rgb(d) for d in draws]
         t = time.time()
-        detections = self.detect_faces_batch(imgs, max_frames=max_frames)
+        if device_crops and getattr(self.detector, "detect_batch", None) is not None:
+            # (a detector whose detect_batch cannot hand its stacks back raises here: device_crops was asked for)
+            detections, sources = self.detector.detect_batch(imgs, max_frames=max_frames, return_stacks=True)
+        else:                                      # no batched detector: every frame takes the single-frame call and the host crops
+            detections, sources = self.detect_faces_batch(imgs, max_frames=max_frames), [None] * len(imgs)
         if self.print_stat:
             print('detection elapsed', time.time() - t)
         all_bboxes, crops = [], []
@@ -214,12 +276,29 @@ class FacialImageProcessing:
             img_h, img_w, _ = img.shape
             bboxes = self.face_boxes(bounding_boxes, img_w, img_h)
             all_bboxes.append(bboxes)
-            crops += [img[y1:y2, x1:x2, :] for (x1, y1, x2, y2) in bboxes]
+            if not device_crops:
+                crops += [img[y1:y2, x1:x2, :] for (x1, y1, x2, y2) in bboxes]
+        counts = [len(b) for b in all_bboxes]
         t = time.time()
-        ages, genders, features = self.age_gender_batch(crops, latency=False) if crops else ([], [], [])
+        resized = None
+        if sum(counts) == 0:
+            ages, genders, features = [], [], []
+        elif device_crops or (return_crops and byte_path):
+            x8 = self._resized_faces(imgs, all_bboxes, sources)
+            ages, genders, features = self._forward_u8_batch(x8)
+            if return_crops:
+                resized = x8.cpu().numpy()
+        else:
+            ages, genders, features = self.age_gender_batch(crops, latency=False)
         if self.print_stat:
             print('age gender elapsed', time.time() - t)
-        counts = [len(b) for b in all_bboxes]
-        return [(bboxes, points if points is not None else [], a, g, f)
-                for bboxes, (_, points), a, g, f in zip(all_bboxes, detections, split_by_counts(ages, counts), split_by_counts(genders, counts),
-                                                        split_by_counts(features, counts))]
+        out = [(bboxes, points if points is not None else [], a, g, f)
+               for bboxes, (_, points), a, g, f in zip(all_bboxes, detections, split_by_counts(ages, counts), split_by_counts(genders, counts),
+                                                       split_by_counts(features, counts))]
+        if not return_crops:
+            return out
+        if resized is None:       # no faces at all, or a host-preprocess configuration: OpenCV's resize restated on the host
+            resized = np.stack([preprocess.resize_linear_u8(c, self.w, self.h) for c in crops]) if crops else \
+                np.empty((0, self.h, self.w, 3), np.uint8)
+        at = np.concatenate([[0], np.cumsum(counts)])
+        return out, [resized[at[i]:at[i + 1]] for i in range(len(counts))]

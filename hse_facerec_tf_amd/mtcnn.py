@@ -538,9 +538,11 @@ class MTCNNDetector:
             wk.bpoints = torch.empty((n_frames, cap, 10), dtype=torch.float32, device=dev)
         return wk
 
-    def _detect_pass(self, imgs: List[np.ndarray]) -> List[Optional[Tuple[np.ndarray, np.ndarray]]]:
+    def _detect_pass(self, imgs: List[np.ndarray], stack_out: Optional[list] = None) -> List[Optional[Tuple[np.ndarray, np.ndarray]]]:
         """One pass over same-size frames: the launches of _detect_device, each covering every frame, and three read-backs.  Per
         frame (boxes, points), or None where that frame's candidate list overflowed (the caller redoes that frame alone).
+        ``stack_out``: a list that receives the pass's uploaded frame stack (CUDA uint8 [frames, h, w, 3]), for a caller that cuts
+        the faces from it on the device.
 
         Bit identity with _detect_device frame by frame: the pyramid, the crops and the box logic compute a frame's values from that
         frame's data by the same operations (the kernels take the frame as a grid index); the nets run on the stacked levels and on
@@ -554,6 +556,8 @@ class MTCNNDetector:
         dev = self.device
         results: List[Optional[Tuple[np.ndarray, np.ndarray]]] = [empty_detection() for _ in range(n_frames)]
         stack = torch.from_numpy(np.stack(imgs)).to(dev)                   # one upload per pass
+        if stack_out is not None:
+            stack_out.append(stack)
         with _lib.on_device(stack):
             st = _lib.current_stream_ptr()
             wk = self._batch_work_tensors(cap, n_frames)
@@ -636,17 +640,22 @@ class MTCNNDetector:
         boxes, points = self(img)
         return (boxes, points) if boxes.shape[0] else empty_detection()
 
-    def detect_batch(self, frames, max_frames: int = 32) -> List[Tuple[np.ndarray, np.ndarray]]:
+    def detect_batch(self, frames, max_frames: int = 32, return_stacks: bool = False):
         """[(boxes [n,5] float64, points [10,n] float32)] in the order of ``frames`` (uint8 RGB [H, W, 3] each), every entry bit for bit
         what ``self(frame)`` returns; a frame without faces gives shapes (0, 5) and (10, 0).  Frames of one size run together, at most
         ``max_frames`` per pass: one upload, the launches of one frame and three read-backs per pass (a pass of ONE frame is the
         single-frame call).  A frame whose candidate list
         overflows the device capacity is redone alone through ``self(frame)`` (counted in ``host_fallbacks``); the others of its pass
-        keep their results.  A detector without ``device_boxes`` has no batched path and runs the frames one by one."""
+        keep their results.  A detector without ``device_boxes`` has no batched path and runs the frames one by one.
+        ``return_stacks``: -> (that list, sources), where sources[i] is (stack, row) -- the CUDA uint8 [frames, h, w, 3] stack the
+        frame's pass uploaded and the frame's row in it -- or None for a frame that took the single-frame call (a pass of one, a frame
+        redone after an overflow, any frame of a detector without ``device_boxes``) or had no pyramid level."""
         imgs = [self._check_frame(f) for f in frames]
         passes = plan_passes([f.shape[:2] for f in imgs], max_frames)
+        sources: list = [None] * len(imgs)
         if not self.device_boxes:
-            return [self._alone(f) for f in imgs]
+            alone = [self._alone(f) for f in imgs]
+            return (alone, sources) if return_stacks else alone
         results: List[Optional[Tuple[np.ndarray, np.ndarray]]] = [None] * len(imgs)
         for (h, w), idx in passes:
             if not self.pyramid_scales(h, w):                              # smaller than minsize: no level, no launch
@@ -656,9 +665,16 @@ class MTCNNDetector:
             if len(idx) == 1:                                              # nothing to share: the single-frame call, without the stacking
                 results[idx[0]] = self._alone(imgs[idx[0]])
                 continue
-            for i, res in zip(idx, self._detect_pass([imgs[i] for i in idx])):
-                results[i] = res if res is not None else self._alone(imgs[i])
-        return results
+            kept: list = []
+            group = [imgs[i] for i in idx]
+            for row, (i, res) in enumerate(zip(idx, self._detect_pass(group, kept) if return_stacks else self._detect_pass(group))):
+                if res is not None:
+                    results[i] = res
+                    if return_stacks:
+                        sources[i] = (kept[0], row)
+                else:
+                    results[i] = self._alone(imgs[i])
+        return (results, sources) if return_stacks else results
 
     def __call__(self, img: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
         img = np.asarray(img)

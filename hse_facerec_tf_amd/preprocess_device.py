@@ -167,3 +167,29 @@ def preprocess_faces_cv(crops: Sequence[np.ndarray], out_hw: Tuple[int, int], de
         batch = np.stack([np.ascontiguousarray(crops[i], dtype=np.uint8) for i in idx])
         out[torch.tensor(idx, device=dev)] = preprocess_cv(batch, out_hw, dev, raw_u8=raw_u8)
     return out
+
+
+def face_crops(frames, boxes, out_hw: Tuple[int, int], out=None):
+    """Every box of a stack of frames cut and resized in ONE launch (libhsefr_album.so, csrc/album.hip): ``frames`` a CUDA uint8
+    [n, h, w, 3] stack (the one a detector pass uploaded), ``boxes`` host int32 [m, 5] rows (frame, x1, y1, x2, y2) with x2, y2
+    exclusive -> CUDA uint8 [m, oh, ow, 3] with out[i] = cv2.resize(frames[f][y1:y2, x1:x2], (ow, oh)) byte for byte, channel order
+    kept.  The library checks every box before any device work (ValueError) and uploads the table itself: one upload, whatever the box
+    sizes.  ``out``: a contiguous CUDA uint8 [m, oh, ow, 3] tensor to write into (a slice of a larger batch)."""
+    torch = _lib.require_gpu()
+    if not (hasattr(frames, "is_cuda") and frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3
+            and frames.is_contiguous()):
+        raise ValueError("frames must be a contiguous CUDA uint8 [n, h, w, 3] stack")
+    table = np.ascontiguousarray(boxes, dtype=np.int32)
+    if table.ndim != 2 or table.shape[1] != 5:
+        raise ValueError("boxes must be [m, 5] rows of (frame, x1, y1, x2, y2), got shape %r" % (table.shape,))
+    m, oh, ow = table.shape[0], int(out_hw[0]), int(out_hw[1])
+    if out is None:
+        out = torch.empty((m, oh, ow, 3), dtype=torch.uint8, device=frames.device)
+    elif not (out.is_cuda and out.device == frames.device and out.dtype == torch.uint8 and tuple(out.shape) == (m, oh, ow, 3)
+              and out.is_contiguous()):
+        raise ValueError("out must be a contiguous uint8 [%d, %d, %d, 3] tensor on %s" % (m, oh, ow, frames.device))
+    n, h, w, _ = frames.shape
+    with _lib.on_device(frames):
+        _lib.album_check(_lib.album_lib().hsefr_album_face_crops(frames.data_ptr(), n, h, w, table.ctypes.data, m, out.data_ptr(), oh, ow,
+                                                                 _lib.current_stream_ptr()), "hsefr_album_face_crops")
+    return out
