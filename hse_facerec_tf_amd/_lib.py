@@ -131,6 +131,16 @@ ALBUM_SIGNATURES = {
     "hsefr_album_face_crops": (c_int, [_fp, c_int, c_int, c_int, c_void_p, c_int, _fp, c_int, c_int, c_void_p]),
 }
 
+# libhsefr_frames.so (include/hsefr_frames.h): the frame stack's channel swap and quarter turns, a third library.  HSEFR_FRAMES_LIB selects
+# another build
+FRAMES_LIB_PATH = os.path.join(_HERE, os.environ.get("HSEFR_FRAMES_LIB", "libhsefr_frames.so"))
+_frames_lib = None
+FRAMES_SIGNATURES = {
+    "hsefr_frames_version": (c_int, []),
+    "hsefr_frames_last_error_string": (c_char_p, []),
+    "hsefr_frames_prepare": (c_int, [_fp, _fp, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+}
+
 
 class HsefrError(RuntimeError):
     pass
@@ -186,6 +196,34 @@ def album_check(status: int, what: str = "") -> None:
     """check() for a status of libhsefr_album.so (its own error string)."""
     if status != OK:
         _raise(status, "%s%s (hsefr_album status %d)" % (what + ": " if what else "", album_last_error(), status))
+
+
+def frames_lib() -> ctypes.CDLL:
+    """Load libhsefr_frames.so once (torch first, as lib() does and for the same reason).  Missing is an error: there is no fallback."""
+    global _frames_lib
+    if _frames_lib is None:
+        import torch  # noqa: F401
+        if not os.path.exists(FRAMES_LIB_PATH):
+            raise ImportError("%s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                              "(hipcc --offload-arch=gfx950). There is no CPU fallback." % FRAMES_LIB_PATH)
+        L = ctypes.CDLL(FRAMES_LIB_PATH)
+        for name, (res, args) in FRAMES_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        _frames_lib = L
+    return _frames_lib
+
+
+def frames_last_error() -> str:
+    s = frames_lib().hsefr_frames_last_error_string()
+    return s.decode("utf-8", "replace") if s else ""
+
+
+def frames_check(status: int, what: str = "") -> None:
+    """check() for a status of libhsefr_frames.so (its own error string)."""
+    if status != OK:
+        _raise(status, "%s%s (hsefr_frames status %d)" % (what + ": " if what else "", frames_last_error(), status))
 
 
 def last_error() -> str:

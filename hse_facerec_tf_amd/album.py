@@ -16,11 +16,16 @@ from typing import Iterable, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 
-from . import _lib, clustering, preprocess
+from . import _lib, clustering, preprocess, preprocess_device
 
 # process_images(device_crops=...) of both loops when the caller does not say: decided by tools/album_time.py on an MI355X
 # (profiles/album_time.txt, README "Album organiser"): the device crops are used where the engine takes bytes
 DEVICE_CROPS_DEFAULT = True
+# process_images(device_frames=...) of both loops when the caller does not say: decided by the same run against device_crops alone --
+# faster by more than the spread between repetitions at 8, 16 and 32 frames per call (0.44 against 0.78 ms per frame at 16) and the
+# 64-photo album not slower (43 against 113 ms) -- so the frames are turned and converted on the device where the detector can read a
+# stack and the device crops are in use
+DEVICE_FRAMES_DEFAULT = True
 
 DECISION_TEMPLATES = ((0.875, 0.125), (0.353, 0.647))      # process_photos.py:209: rows = classes (male, female), columns = (p, 1 - p)
 
@@ -171,19 +176,18 @@ def video_frame_schedule(face_counts) -> List[int]:
     return processed
 
 
-def _rotate(draw: np.ndarray, rotation: int) -> np.ndarray:
-    """process_photos.py:102-107: cv2.flip(cv2.transpose(x), 1) is a quarter turn clockwise, flip 0 a quarter turn counter-clockwise."""
-    if rotation == 90:
-        return np.ascontiguousarray(np.rot90(draw, -1))
-    if rotation == 270:
-        return np.ascontiguousarray(np.rot90(draw, 1))
-    return draw
-
-
 def _use_device_crops(img_processing, device_crops: Optional[bool]) -> bool:
     if device_crops is not None:
         return bool(device_crops)
     return bool(DEVICE_CROPS_DEFAULT and img_processing.device_preprocess and img_processing.sess.accepts_u8)
+
+
+def _use_device_frames(img_processing, device_frames: Optional[bool], use_device_crops: bool) -> bool:
+    """(Unasked, the device frames follow the device crops they imply: a caller who turned those off keeps the host path.)"""
+    if device_frames is not None:
+        return bool(device_frames)
+    supported = getattr(img_processing, "device_frames_supported", None)          # process_images' own rule
+    return bool(DEVICE_FRAMES_DEFAULT and use_device_crops and supported is not None and supported())
 
 
 def _normalized_on_device(features: Sequence[np.ndarray], device):
@@ -196,21 +200,25 @@ def _normalized_on_device(features: Sequence[np.ndarray], device):
 
 
 def process_video(img_processing, frames: Iterable[np.ndarray], mdate, rotation: int = 0, config: AlbumConfig = AlbumConfig(),
-                  max_frames: int = 32, device_crops: Optional[bool] = None) -> VideoResult:
+                  max_frames: int = 32, device_crops: Optional[bool] = None, device_frames: Optional[bool] = None) -> VideoResult:
     """process_photos.py:80-156 for the BGR uint8 frames of a video, in grab order.  Whether frame k is processed depends on the faces
     of earlier frames, but only counters divisible by 3 or 5 can ever be: those candidate frames run through
     ``process_images`` in windows of ``max_frames`` (batched detector passes), the rule is then replayed on the host over the face
     counts (video_frame_schedule), and the faces of frames the rule skips are dropped before clustering -- the result is that of the
-    sequential loop.  Clusters need config.min_frames faces; no date rule."""
+    sequential loop.  Clusters need config.min_frames faces; no date rule.  ``rotation`` (0, 90 or 270: :102-107) is applied by
+    process_images, on the device with ``device_frames`` (None: DEVICE_FRAMES_DEFAULT where the configuration allows it)."""
+    rotation = preprocess_device.check_rotation(rotation)
     video_year = _fractional_year(mdate)
     use_device = _use_device_crops(img_processing, device_crops)
+    use_frames = _use_device_frames(img_processing, device_frames, use_device)
     per_frame = {}                     # candidate frame index -> (ages, genders, features, crops)
     n_frames = 0
 
     def flush(window):
         if not window:
             return
-        res, crops = img_processing.process_images([f for _, f in window], max_frames=max_frames, device_crops=use_device, return_crops=True)
+        res, crops = img_processing.process_images([f for _, f in window], max_frames=max_frames, device_crops=use_device, return_crops=True,
+                                                   rotation=rotation, device_frames=use_frames)
         for (k, _), (_, _, ages, genders, feats), c in zip(window, res, crops):
             per_frame[k] = (ages, genders, feats, c)
 
@@ -218,7 +226,7 @@ def process_video(img_processing, frames: Iterable[np.ndarray], mdate, rotation:
     for k, draw in enumerate(frames):
         n_frames = k + 1
         if (k + 1) % 3 == 0 or (k + 1) % 5 == 0:
-            window.append((k, _rotate(np.asarray(draw), rotation)))
+            window.append((k, np.asarray(draw)))
             if len(window) == max_frames:
                 flush(window)
                 window = []
@@ -255,20 +263,25 @@ def _as_bgr(photo) -> np.ndarray:
 
 
 def process_album(img_processing, photos, mdates, videos=(), config: AlbumConfig = AlbumConfig(), max_frames: int = 32,
-                  device_crops: Optional[bool] = None) -> AlbumResult:
+                  device_crops: Optional[bool] = None, device_frames: Optional[bool] = None) -> AlbumResult:
     """process_photos.py:219-358.  ``photos``: BGR uint8 arrays or paths, ``mdates`` their dates; ``videos``: (frames, mdate) or
     (frames, mdate, rotation) per video, frames as process_video takes them.  Pass 1 runs every photo, pass 2 the quarter turns
     clockwise of the photos without a face, pass 3 the quarter turns counter-clockwise of those still without one (:241-247) -- each pass
     through ``process_images`` in calls of a few detector passes.  The faces' features are L2-normalised on the device and stay there
     until the clustering is done; born years follow :257-258; a video contributes its clusters' faces, with the cluster means as
     features (:284-297).  Then perform_clustering with config.min_photos and the date rule, the summaries, and the private / public
-    split (:345-346) over the files (photos, then videos)."""
-    use_device = _use_device_crops(img_processing, device_crops)
+    split (:345-346) over the files (photos, then videos).  The quarter turns of passes 2 and 3 and of a turned video are made by
+    process_images(rotation=...): on the device, in the launch that converts the frames to RGB, with ``device_frames`` (None:
+    DEVICE_FRAMES_DEFAULT where the configuration allows it)."""
     photos = list(photos)
     mdates = list(mdates)
     videos = list(videos)
     if len(mdates) != len(photos):
         raise ValueError("%d photos, %d dates" % (len(photos), len(mdates)))
+    for video in videos:
+        preprocess_device.check_rotation(video[2] if len(video) > 2 else 0)
+    use_device = _use_device_crops(img_processing, device_crops)
+    use_frames = _use_device_frames(img_processing, device_frames, use_device)
     n_photos = len(photos)
     found = [None] * n_photos          # per photo: (ages, genders, features, crops, has_center_face)
     call = 4 * max_frames              # frames per process_images call: bounds the frame stacks held on the device at one time
@@ -276,10 +289,11 @@ def process_album(img_processing, photos, mdates, videos=(), config: AlbumConfig
     def run_pass(todo, rotation):
         for a in range(0, len(todo), call):
             part = todo[a:a + call]
-            draws = [_rotate(_as_bgr(photos[i]), rotation) for i in part]
-            res, crops = img_processing.process_images(draws, max_frames=max_frames, device_crops=use_device, return_crops=True)
+            draws = [_as_bgr(photos[i]) for i in part]
+            res, crops = img_processing.process_images(draws, max_frames=max_frames, device_crops=use_device, return_crops=True,
+                                                       rotation=rotation, device_frames=use_frames)
             for i, d, (bboxes, _, ages, genders, feats), c in zip(part, draws, res, crops):
-                found[i] = (ages, genders, feats, c, has_center_face(bboxes, d.shape[1], config))
+                found[i] = (ages, genders, feats, c, has_center_face(bboxes, d.shape[0] if rotation else d.shape[1], config))   # the turned width
 
     todo = list(range(n_photos))
     for rotation in (0, 90, 270):
@@ -299,7 +313,7 @@ def process_album(img_processing, photos, mdates, videos=(), config: AlbumConfig
         born.extend(photo_year - (age - 0.5) for age in ages)
     for j, video in enumerate(videos):
         frames, vdate = video[0], video[1]
-        v = process_video(img_processing, frames, vdate, video[2] if len(video) > 2 else 0, config, max_frames, use_device)
+        v = process_video(img_processing, frames, vdate, video[2] if len(video) > 2 else 0, config, max_frames, use_device, use_frames)
         if v.video_has_faces:
             private.append(n_photos + j)
         images.extend(v.cluster_images)

@@ -1,6 +1,7 @@
 #!/bin/bash
 # Builds libhsefr.so for gfx950 in-tree (hipcc cross-compiles without a GPU), and right after it libhsefr_album.so (include/hsefr_album.h:
-# the album organiser's device code, a library of its own because libhsefr.so is held below 4 MB by its tests).
+# the album organiser's device code, a library of its own because libhsefr.so is held below 4 MB by its tests) and libhsefr_frames.so
+# (include/hsefr_frames.h: the frame stack's channel swap and quarter turns, a library of its own for the same reason).
 #   HSEFR_DEV=1 build.sh   builds libhsefr_dev.so instead: the same sources with -DHSEFR_DEV (tuning knobs as run-time
 #                          variables, hsefr_debug_*, the calibration kernels of devtools.hip) -- for tools/kbench.py only.
 set -euo pipefail
@@ -19,6 +20,10 @@ LINK="--offload-arch=gfx950"
 # OpenCV's resize taps in the kernel, where a product fused with the subtraction behind it would round once instead of twice
 ALBUM_SRCS="album.hip"
 ALBUM_FLAGS="$FLAGS $DEVICE_STRIP -ffp-contract=off"
+# libhsefr_frames.so (include/hsefr_frames.h: the frames of a pass turned upright and converted to RGB on the device): a third library for
+# the same reason, built as the second -- its own source list, the same flags in every mode
+FRAMES_SRCS="frames.hip"
+FRAMES_FLAGS="$FLAGS $DEVICE_STRIP"
 LINT=1
 HOST_STRIP=0
 HOST_SIZE_FLAGS=""
@@ -102,4 +107,23 @@ if [ "$LINT" = "1" ]; then
   /opt/rocm/lib/llvm/bin/llvm-strip --strip-all -w --keep-symbol='_ZN*_kernel*' --keep-symbol='!*__device_stub__*' "$ALBUM_OUT"
   python3 ../../tools/isa_lint.py "$ALBUM_OUT"
   echo "built $(realpath $ALBUM_OUT)"
+  # the third library: built, stripped and linted as the second
+  FRAMES_OUT=../libhsefr_frames.so
+  FRAMES_OBJS=""
+  for s in $FRAMES_SRCS; do
+    o="$BUILD/${s%.hip}.o"
+    stale=0
+    for dep in "$s" ../../include/hsefr_frames.h build.sh; do
+      if [ ! -f "$o" ] || [ "$dep" -nt "$o" ]; then stale=1; fi
+    done
+    if [ "$stale" = 1 ]; then
+      rm -f "$o"
+      hipcc $FRAMES_FLAGS -Xarch_host -Os ${HSEFR_EXTRA_FLAGS:-} -c "$s" -o "$o"
+    fi
+    FRAMES_OBJS="$FRAMES_OBJS $o"
+  done
+  hipcc $LINK -shared -fPIC -o "$FRAMES_OUT" $FRAMES_OBJS
+  /opt/rocm/lib/llvm/bin/llvm-strip --strip-all -w --keep-symbol='_ZN*_kernel*' --keep-symbol='!*__device_stub__*' "$FRAMES_OUT"
+  python3 ../../tools/isa_lint.py "$FRAMES_OUT"
+  echo "built $(realpath $FRAMES_OUT)"
 fi

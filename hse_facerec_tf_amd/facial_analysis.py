@@ -246,7 +246,58 @@ class FacialImageProcessing:
                                                                                            raw_u8=True)
         return x8
 
-    def process_images(self, draws, max_frames: int = 32, device_crops: bool = False, return_crops: bool = False):
+    def device_frames_supported(self) -> bool:
+        """process_images(device_frames=True)'s rule: the byte path (device_preprocess and an engine that accepts bytes) and a detector
+        that can detect from a stack on the device -- it has ``detect_stack`` and keeps its box logic on the device (``device_boxes``:
+        an MTCNNDetector without it has the method but no batched path to run it on)."""
+        return bool(self.device_preprocess and self.sess.accepts_u8 and getattr(self.detector, "detect_stack", None) is not None
+                    and getattr(self.detector, "device_boxes", False))
+
+    def _detect_device_frames(self, draws, rotation: int, max_frames: int):
+        """process_images' detection with device_frames: the frames grouped by their TURNED size (mtcnn.plan_passes); a group of two or
+        more is stacked as decoded (BGR, unrotated), uploaded, turned and converted by ONE launch (preprocess_device.prepare_frames; in
+        place for rotation 0, and a quarter turn's raw stack is dropped as soon as the prepared one is written) and detected from that
+        stack (MTCNNDetector.detect_stack).  -> (imgs, shapes, detections, sources): ``sources`` as detect_batch(return_stacks=True)
+        gives them; ``imgs[i]`` the frame's turned RGB host array where it took the single-frame call -- a frame alone in its size group
+        (converted on the host, as without device_frames) and a frame whose candidate list overflowed (read back from its row of the
+        prepared stack) -- and None for the others, whose pixels the host never touches; ``shapes[i]`` the turned (h, w)."""
+        from . import preprocess_device
+        from .mtcnn import empty_detection, plan_passes
+        torch = _lib.require_gpu()
+        raw = []
+        for d in draws:
+            d = np.asarray(d)
+            if d.ndim != 3 or d.shape[2] != 3 or d.dtype != np.uint8:
+                raise ValueError("device_frames takes uint8 BGR frames [H, W, 3]")
+            raw.append(d)
+        shapes = [(d.shape[1], d.shape[0]) if rotation else (d.shape[0], d.shape[1]) for d in raw]
+        imgs, detections, sources = [None] * len(raw), [None] * len(raw), [None] * len(raw)
+
+        def alone(i, img):                         # the single-frame call, through the path a lone frame takes without device_frames
+            imgs[i] = img
+            detections[i] = self.detector.detect_batch([img], max_frames=max_frames)[0]
+        for (h, w), idx in plan_passes(shapes, max_frames):
+            if not self.detector.pyramid_scales(h, w):                     # smaller than minsize: no level, no launch, no upload
+                for i in idx:
+                    detections[i] = empty_detection()
+                continue
+            if len(idx) == 1:
+                alone(idx[0], self._bgr_to_rgb(preprocess_device.turn_frame(raw[idx[0]], rotation)))
+                continue
+            stack = torch.from_numpy(np.stack([raw[i] for i in idx])).to(self.detector.device)      # one upload per pass, as decoded
+            if rotation == 0:
+                preprocess_device.prepare_frames(stack, 0, True, out=stack)                         # in place: never a second stack
+            else:
+                stack = preprocess_device.prepare_frames(stack, rotation, True)                     # (the raw stack is released here)
+            for row, (i, res) in enumerate(zip(idx, self.detector.detect_stack(stack))):
+                if res is not None:
+                    detections[i], sources[i] = res, (stack, row)
+                else:
+                    alone(i, stack[row].cpu().numpy())
+        return imgs, shapes, detections, sources
+
+    def process_images(self, draws, max_frames: int = 32, device_crops: bool = False, return_crops: bool = False, rotation: int = 0,
+                       device_frames: bool = False):
         """process_image for a list of BGR uint8 frames (the photos of an album, the frames of a video: process_photos.py:92-118,
         :238-247) -> a list of process_image's 5-tuples, in list order.  One detect_faces_batch call over all frames, then ONE
         age_gender_batch call over the crops of all frames on the bulk plan (it chunks by max_batch itself), split back per frame.
@@ -257,14 +308,30 @@ class FacialImageProcessing:
         are those of device_crops=False bit for bit.  Needs device_preprocess=True and an engine that takes bytes (ValueError otherwise,
         before any device work).
         return_crops: -> (that list, crops) with crops[i] the frame's resized faces, RGB uint8 [n_i, h, w, 3] (process_photos.py:38's
-        facial_images up to channel order), read back in one copy."""
+        facial_images up to channel order), read back in one copy.
+        rotation: 0, 90 or 270 -- every frame of the call is turned by that many degrees clockwise first (process_photos.py:102-107,
+        :242-247: the retry passes of an album, a video stored turned); boxes and points refer to the turned frame.
+        device_frames: the frames are uploaded as decoded and turned and converted to RGB on the device, a pass in one launch
+        (_detect_device_frames), instead of copied twice on the host; the detector and the crop kernel read that stack.  Implies
+        device_crops and has its rule: ValueError without device_preprocess=True, an engine that accepts bytes and a detector with
+        ``detect_stack``.  Results are those of device_frames=False bit for bit."""
+        from . import preprocess_device
         from .mtcnn import split_by_counts
+        rotation = preprocess_device.check_rotation(rotation)
         byte_path = self.device_preprocess and self.sess.accepts_u8
+        if device_frames and not self.device_frames_supported():
+            raise ValueError("device_frames needs device_preprocess=True, an engine that accepts bytes and a detector with detect_stack "
+                             "(an MTCNNDetector with device_boxes)")
         if device_crops and not byte_path:
             raise ValueError("device_crops needs device_preprocess=True and an engine that accepts bytes")
-        imgs = [self._bgr_to_rgb(d) for d in draws]
+        device_crops = bool(device_crops or device_frames)
+        if not device_frames:
+            imgs = [self._bgr_to_rgb(preprocess_device.turn_frame(np.asarray(d), rotation) if rotation else d) for d in draws]
+            shapes = [img.shape[:2] for img in imgs]
         t = time.time()
-        if device_crops and getattr(self.detector, "detect_batch", None) is not None:
+        if device_frames:
+            imgs, shapes, detections, sources = self._detect_device_frames(draws, rotation, max_frames)
+        elif device_crops and getattr(self.detector, "detect_batch", None) is not None:
             # (a detector whose detect_batch cannot hand its stacks back raises here: device_crops was asked for)
             detections, sources = self.detector.detect_batch(imgs, max_frames=max_frames, return_stacks=True)
         else:                                      # no batched detector: every frame takes the single-frame call and the host crops
@@ -272,8 +339,7 @@ class FacialImageProcessing:
         if self.print_stat:
             print('detection elapsed', time.time() - t)
         all_bboxes, crops = [], []
-        for img, (bounding_boxes, _) in zip(imgs, detections):
-            img_h, img_w, _ = img.shape
+        for img, (img_h, img_w), (bounding_boxes, _) in zip(imgs, shapes, detections):
             bboxes = self.face_boxes(bounding_boxes, img_w, img_h)
             all_bboxes.append(bboxes)
             if not device_crops:

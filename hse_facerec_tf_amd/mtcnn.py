@@ -549,15 +549,36 @@ class MTCNNDetector:
         the concatenated crop lists, and conv2d_direct, maxpool_f32 and softmax (csrc/smallnet.hip) compute each output element from
         its own image alone in a fixed FMA order, so a row's values do not depend on the batch it stands in
         (tests/test_mtcnn_batch_gpu.py checks both)."""
+        stack = self._torch.from_numpy(np.stack(imgs)).to(self.device)     # one upload per pass
+        if stack_out is not None:
+            stack_out.append(stack)
+        return self._detect_stack_body(stack)
+
+    def detect_stack(self, stack) -> List[Optional[Tuple[np.ndarray, np.ndarray]]]:
+        """_detect_pass for a pass whose frames are on the device already: ``stack`` a contiguous CUDA uint8 RGB [frames, h, w, 3]
+        tensor on the detector's device (preprocess_device.prepare_frames writes one).  Nothing is uploaded; the launches, the
+        read-backs and the results are those of _detect_pass on the same frames.  Per frame (boxes, points), or None where that frame's
+        candidate list overflowed (the caller redoes that frame alone: ``self(stack[row].cpu().numpy())``).  A stack of frames too small
+        for a pyramid level gives empty detections without a launch.  Needs ``device_boxes``."""
+        torch = self._torch
+        if not self.device_boxes:
+            raise ValueError("detect_stack needs a detector with device_boxes")
+        if not (isinstance(stack, torch.Tensor) and stack.is_cuda and stack.dtype == torch.uint8 and stack.dim() == 4 and stack.shape[3] == 3
+                and stack.is_contiguous()):
+            raise ValueError("detect_stack takes a contiguous CUDA uint8 RGB stack [frames, H, W, 3]")
+        if stack.device != self.device:
+            raise ValueError("the stack is on %s, the detector on %s" % (stack.device, self.device))
+        if stack.shape[0] == 0 or not self.pyramid_scales(int(stack.shape[1]), int(stack.shape[2])):
+            return [empty_detection() for _ in range(int(stack.shape[0]))]
+        return self._detect_stack_body(stack)
+
+    def _detect_stack_body(self, stack) -> List[Optional[Tuple[np.ndarray, np.ndarray]]]:
+        """_detect_pass behind its upload."""
         torch, L = self._torch, _lib.lib()
-        n_frames = len(imgs)
-        h, w = imgs[0].shape[:2]
+        n_frames, h, w = int(stack.shape[0]), int(stack.shape[1]), int(stack.shape[2])
         cap = int(L.hsefr_mtcnn_post_capacity())
         dev = self.device
         results: List[Optional[Tuple[np.ndarray, np.ndarray]]] = [empty_detection() for _ in range(n_frames)]
-        stack = torch.from_numpy(np.stack(imgs)).to(dev)                   # one upload per pass
-        if stack_out is not None:
-            stack_out.append(stack)
         with _lib.on_device(stack):
             st = _lib.current_stream_ptr()
             wk = self._batch_work_tensors(cap, n_frames)

@@ -193,3 +193,58 @@ def face_crops(frames, boxes, out_hw: Tuple[int, int], out=None):
         _lib.album_check(_lib.album_lib().hsefr_album_face_crops(frames.data_ptr(), n, h, w, table.ctypes.data, m, out.data_ptr(), oh, ow,
                                                                  _lib.current_stream_ptr()), "hsefr_album_face_crops")
     return out
+
+
+FRAME_ROTATIONS = (0, 90, 270)
+
+
+def check_rotation(rotation) -> int:
+    """0, 90 or 270 (degrees clockwise), as process_photos.py turns a photo or a video frame; anything else is a ValueError."""
+    if rotation not in FRAME_ROTATIONS:
+        raise ValueError("rotation must be 0, 90 or 270, not %r" % (rotation,))
+    return int(rotation)
+
+
+def turn_frame(frame: np.ndarray, rotation: int) -> np.ndarray:
+    """The host turn (process_photos.py:102-107): cv2.flip(cv2.transpose(x), 1) is a quarter turn clockwise (90), flip 0 a quarter
+    turn counter-clockwise (270); a contiguous copy, or the frame itself for 0."""
+    rotation = check_rotation(rotation)
+    if rotation == 90:
+        return np.ascontiguousarray(np.rot90(frame, -1))
+    if rotation == 270:
+        return np.ascontiguousarray(np.rot90(frame, 1))
+    return frame
+
+
+def prepare_frames(stack, rotation: int = 0, swap_rb: bool = True, out=None):
+    """A stack of frames as decoded, turned upright and converted, in ONE launch (libhsefr_frames.so, csrc/frames.hip): ``stack`` a
+    contiguous CUDA uint8 [n, h, w, 3] tensor -> CUDA uint8 [n, h, w, 3] for rotation 0, [n, w, h, 3] for 90 (np.rot90(x, -1) per
+    frame, a quarter turn clockwise) and 270 (np.rot90(x, 1)), with channels 0 and 2 exchanged when ``swap_rb`` (BGR <-> RGB), byte for
+    byte.  ``out``: a contiguous CUDA uint8 tensor of that shape to write into (a slice of a larger tensor will do); ``out=stack`` with
+    rotation 0 runs in place.  ValueError before any launch for a host tensor, a wrong dtype or shape, a non-contiguous stack, a bad
+    rotation and an ``out`` that does not fit."""
+    import torch
+    rotation = check_rotation(rotation)
+    if not isinstance(stack, torch.Tensor):
+        raise ValueError("stack must be a CUDA uint8 [n, h, w, 3] tensor, not %s" % type(stack).__name__)
+    if stack.dtype != torch.uint8 or stack.dim() != 4 or stack.shape[3] != 3:
+        raise ValueError("stack must be a uint8 [n, h, w, 3] tensor, got %s %r" % (stack.dtype, tuple(stack.shape)))
+    if not stack.is_contiguous():
+        raise ValueError("stack must be contiguous")
+    if not stack.is_cuda:
+        raise ValueError("stack must be a CUDA tensor (the caller uploads the decoded frames)")
+    n, h, w, _ = (int(s) for s in stack.shape)
+    shape = (n, h, w, 3) if rotation == 0 else (n, w, h, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=stack.device)
+    elif not (getattr(out, "is_cuda", False) and out.device == stack.device and out.dtype == torch.uint8 and tuple(out.shape) == shape
+              and out.is_contiguous()):
+        raise ValueError("out must be a contiguous uint8 %r tensor on %s" % (shape, stack.device))
+    if rotation != 0 and out.data_ptr() == stack.data_ptr() and n > 0:
+        raise ValueError("a quarter turn cannot run in place")
+    if n == 0 or h == 0 or w == 0:
+        return out
+    with _lib.on_device(stack):
+        _lib.frames_check(_lib.frames_lib().hsefr_frames_prepare(stack.data_ptr(), out.data_ptr(), n, h, w, rotation, 1 if swap_rb else 0,
+                                                                  _lib.current_stream_ptr()), "hsefr_frames_prepare")
+    return out

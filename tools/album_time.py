@@ -4,9 +4,14 @@
 
   crops : FacialImageProcessing.process_images(frames, max_frames=B, device_crops=True)   against   the same call with
           device_crops=False (the host crops: the yardstick), at B = 1, 2, 8, 16, 32 frames per call; next to them the detector alone
-          (detect_batch on the RGB frames) and the BGR -> RGB copy alone, which say where a frame's time goes
+          (detect_batch on the RGB frames) and the BGR -> RGB copy alone, which say where a frame's time goes;
+          and the same call with device_frames=True (the frames uploaded as decoded, converted on the device)   against   the
+          device_crops=True side, with the np.stack of the raw frames alone next to them
   album : album.process_album on a 64-photo album (every fourth photo stored a quarter turn off, every eighth blank)   against   the
-          loop a user stitches by hand from process_image, the rotation retries, cluster_faces, the filters and the summaries
+          loop a user stitches by hand from process_image, the rotation retries, cluster_faces, the filters and the summaries;
+          and with device_frames=True   against   device_frames=False
+  kernel: hsefr_frames_prepare alone on 16 frames of that size at each rotation, by device events
+The last line is the rule for album.DEVICE_FRAMES_DEFAULT applied to these numbers.
 
 All sides of a section run in ONE process: after a warm-up of each, REPS repetitions of each, alternating; a repetition is as many calls
 as fill --seconds, timed with a host clock (every side ends in a device-to-host copy of its results, so the clock sees finished work).
@@ -32,6 +37,7 @@ from mtcnn_batch_time import make_frames, wall_ms
 BATCHES = [1, 2, 8, 16, 32]
 ALBUM_PHOTOS = 64
 REPS = 5
+KERNEL_REPS = 30
 
 
 def alternated(sides, seconds):
@@ -95,12 +101,35 @@ def section(name, seconds):
             sides = [lambda: fip.process_images(fs, max_frames=b, device_crops=True),
                      lambda: fip.process_images(fs, max_frames=b),
                      lambda: fip.detector.detect_batch(fr, max_frames=b),
-                     lambda: [fip._bgr_to_rgb(f) for f in fs]]
+                     lambda: [fip._bgr_to_rgb(f) for f in fs],
+                     lambda: fip.process_images(fs, max_frames=b, device_frames=True),
+                     lambda: np.stack(fs)]
             faces = sum(len(r[0]) for r in sides[0]())
-            assert faces == sum(len(r[0]) for r in sides[1]())
+            assert faces == sum(len(r[0]) for r in sides[1]()) == sum(len(r[0]) for r in sides[4]())
             times, calls = alternated(sides, seconds)
             rows.append(dict(b=b, faces=faces, calls=calls, times=[[t / b for t in side] for side in times]))
-            print(name, b, "device min %.3f host min %.3f ms/frame" % (min(rows[-1]["times"][0]), min(rows[-1]["times"][1])), flush=True)
+            print(name, b, "frames min %.3f device min %.3f host min %.3f ms/frame"
+                  % (min(rows[-1]["times"][4]), min(rows[-1]["times"][0]), min(rows[-1]["times"][1])), flush=True)
+    elif name == "kernel":
+        # the launch alone, by device events: 16 frames of the photo's size, each rotation, out of place and (rotation 0) in place
+        from hse_facerec_tf_amd import preprocess_device
+        n, (h, w) = 16, make_frames(1)[0].shape[:2]
+        src = torch.randint(0, 256, (n, h, w, 3), dtype=torch.uint8, device="cuda")
+        for rotation, in_place in ((0, False), (0, True), (90, False), (270, False)):
+            work = src.clone()
+            out = work if in_place else torch.empty((n, h, w, 3) if rotation == 0 else (n, w, h, 3), dtype=torch.uint8, device="cuda")
+            for _ in range(5):
+                preprocess_device.prepare_frames(work, rotation, True, out=out)
+            ms = []
+            for _ in range(KERNEL_REPS):
+                a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                preprocess_device.prepare_frames(work, rotation, True, out=out)
+                z.record()
+                z.synchronize()
+                ms.append(a.elapsed_time(z))
+            rows.append(dict(rotation=rotation, in_place=in_place, n=n, h=h, w=w, bytes=2 * n * h * w * 3, ms=ms))
+            print(name, rotation, "in place" if in_place else "", "min %.4f ms" % min(ms), flush=True)
     else:
         base = make_frames(ALBUM_PHOTOS)
         photos = []
@@ -109,11 +138,15 @@ def section(name, seconds):
             photos.append(np.ascontiguousarray(f[..., ::-1]))
         mdates = [time.gmtime(1551693600 + i * 11 * 3600) for i in range(ALBUM_PHOTOS)]
         config = album.AlbumConfig()
-        sides = [lambda: album.process_album(fip, photos, mdates, config=config, device_crops=True),
-                 lambda: album.process_album(fip, photos, mdates, config=config, device_crops=False),
-                 lambda: sequential_album(fip, photos, mdates, config)]
+        sides = [lambda: album.process_album(fip, photos, mdates, config=config, device_crops=True, device_frames=False),
+                 lambda: album.process_album(fip, photos, mdates, config=config, device_crops=False, device_frames=False),
+                 lambda: sequential_album(fip, photos, mdates, config),
+                 lambda: album.process_album(fip, photos, mdates, config=config, device_frames=True)]
         got, want = sides[0](), sides[2]()
         assert got.clusters == want[0] and (got.private_photos, got.public_photos) == want[2], "the two albums differ"
+        third = sides[3]()
+        assert (third.clusters, third.all_indices, third.private_photos, third.public_photos) == \
+            (got.clusters, got.all_indices, got.private_photos, got.public_photos), "the device-frames album differs"
         times, calls = alternated(sides, seconds)
         rows.append(dict(b=ALBUM_PHOTOS, faces=len(got.all_indices), clusters=len(got.clusters), calls=calls, times=times))
     return dict(device=torch.cuda.get_device_name(0), host_fallbacks=int(fip.detector.host_fallbacks), rows=rows)
@@ -128,7 +161,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "album_time.txt"))
     ap.add_argument("--seconds", type=float, default=0.3, help="wall time one repetition of one side is sized to")
     ap.add_argument("--limit", type=int, default=240, help="time limit of one section's process, seconds")
-    ap.add_argument("--section", choices=["crops", "album"], help="(internal) run one section in this process and write --json")
+    ap.add_argument("--section", choices=["crops", "album", "kernel"], help="(internal) run one section in this process and write --json")
     ap.add_argument("--json")
     args = ap.parse_args()
     if args.section:
@@ -138,7 +171,7 @@ def main():
         return
     results = {}
     with tempfile.TemporaryDirectory() as tmp:
-        for name in ("crops", "album"):
+        for name in ("crops", "album", "kernel"):
             path = os.path.join(tmp, name + ".json")
             cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--section", name, "--json", path,
                    "--seconds", str(args.seconds)]
@@ -158,14 +191,27 @@ def main():
              "%3s %6s %11s %11s %10s %10s %11s %12s %8s %7s %7s %15s"
              % ("B", "faces", "device_min", "device_med", "host_min", "host_med", "detect_min", "bgr2rgb_min", "spread", "ratio", "slower", "calls")]
     for r in results["crops"]["rows"]:
-        dev, host, det, copy = r["times"]
+        dev, host, det, copy = r["times"][:4]
         spread = max(max(s) - min(s) for s in (dev, host))
         lines.append("%3d %6d %11.3f %11.3f %10.3f %10.3f %11.3f %12.3f %8.3f %7.2f %7s %15s"
                      % (r["b"], r["faces"], *stats(dev), *stats(host), min(det), min(copy), spread, min(host) / min(dev),
-                        "yes" if min(dev) - min(host) > spread else "no", "/".join(str(c) for c in r["calls"])))
+                        "yes" if min(dev) - min(host) > spread else "no", "/".join(str(c) for c in r["calls"][:4])))
+    lines += ["# frames: the same call with device_frames=True (frames) against the device_crops=True side above (device: the parent path), ms per",
+              "#   FRAME; stack = np.stack of the raw frames alone (the host work device_frames keeps); spread = the largest max - min of the",
+              "#   two sides; faster = device_min - frames_min > spread.  At B = 1 the frame is alone in its group: the host path on both sides",
+              "%3s %11s %11s %11s %11s %10s %8s %7s %7s %9s"
+              % ("B", "frames_min", "frames_med", "device_min", "device_med", "stack_min", "spread", "ratio", "faster", "calls")]
+    faster_at = {}
+    for r in results["crops"]["rows"]:
+        dev, fra, stk = r["times"][0], r["times"][4], r["times"][5]
+        spread = max(max(s) - min(s) for s in (dev, fra))
+        faster_at[r["b"]] = min(dev) - min(fra) > spread
+        lines.append("%3d %11.3f %11.3f %11.3f %11.3f %10.3f %8.3f %7.2f %7s %9s"
+                     % (r["b"], *stats(fra), *stats(dev), min(stk), spread, min(dev) / min(fra), "yes" if faster_at[r["b"]] else "no",
+                        "%d/%d" % (r["calls"][4], r["calls"][0])))
     lines.append("# frames redone on the host in this section: %d" % results["crops"]["host_fallbacks"])
     r = results["album"]["rows"][0]
-    dev, host, loop = r["times"]
+    dev, host, loop, fra = r["times"]
     lines += ["# album: process_album on %d photos (every fourth a quarter turn off: found in the retry pass; every eighth blank: all three passes),"
               % r["b"],
               "#   %d faces, %d clusters, ms per ALBUM; loop = process_image per photo, the retries, cluster_faces, filters and summaries by hand"
@@ -174,8 +220,24 @@ def main():
               % ("device_min", "device_med", "host_min", "host_med", "loop_min", "loop_med", "spread", "loop/device", "calls"),
               "%12.1f %12.1f %10.1f %10.1f %10.1f %10.1f %8.1f %11.2f %9s"
               % (*stats(dev), *stats(host), *stats(loop), max(max(s) - min(s) for s in (dev, host, loop)), min(loop) / min(dev),
-                 "/".join(str(c) for c in r["calls"])),
-              "# frames redone on the host in this section: %d" % results["album"]["host_fallbacks"]]
+                 "/".join(str(c) for c in r["calls"][:3])),
+              "# the same album with device_frames=True (frames) against device_frames=False (device, the columns above); slower = frames_min -",
+              "#   device_min > spread of the two",
+              "%12s %12s %8s %7s %7s %6s" % ("frames_min", "frames_med", "spread", "ratio", "slower", "calls")]
+    album_spread = max(max(s) - min(s) for s in (dev, fra))
+    album_slower = min(fra) - min(dev) > album_spread
+    lines += ["%12.1f %12.1f %8.1f %7.2f %7s %6d" % (*stats(fra), album_spread, min(dev) / min(fra), "yes" if album_slower else "no", r["calls"][3]),
+              "# frames redone on the host in this section: %d" % results["album"]["host_fallbacks"],
+              "# kernel: hsefr_frames_prepare alone, %d frames of %d x %d, swap_rb = 1, device events around one launch, %d launches each;"
+              % (results["kernel"]["rows"][0]["n"], results["kernel"]["rows"][0]["w"], results["kernel"]["rows"][0]["h"], KERNEL_REPS),
+              "#   GB/s = bytes read + bytes written over the minimum (both stacks, 22 MB each, fit the Infinity Cache: not an HBM rate)",
+              "%9s %9s %9s %9s %9s" % ("rotation", "in_place", "min_us", "med_us", "GB/s")]
+    for k in results["kernel"]["rows"]:
+        lines.append("%9d %9s %9.1f %9.1f %9.0f" % (k["rotation"], "yes" if k["in_place"] else "no", 1e3 * min(k["ms"]), 1e3 * float(np.median(k["ms"])),
+                                                    k["bytes"] / (min(k["ms"]) * 1e-3) / 1e9))
+    decided = all(faster_at[b] for b in (8, 16, 32)) and not album_slower
+    lines.append("# album.DEVICE_FRAMES_DEFAULT: %s (rule: faster by more than the spread at B = 8, 16 and 32 -- %s -- and the album not slower by more"
+                 " than its spread -- %s)" % (decided, "/".join("yes" if faster_at[b] else "no" for b in (8, 16, 32)), "no" if not album_slower else "yes: slower"))
     text = "\n".join(lines) + "\n"
     with open(args.out, "w") as f:
         f.write(text)
