@@ -141,6 +141,17 @@ FRAMES_SIGNATURES = {
     "hsefr_frames_prepare": (c_int, [_fp, _fp, c_int, c_int, c_int, c_int, c_int, c_void_p]),
 }
 
+# libhsefr_forest.so (include/hsefr_forest.h): the random forest classifier, a fourth library.  HSEFR_FOREST_LIB selects another build
+FOREST_LIB_PATH = os.path.join(_HERE, os.environ.get("HSEFR_FOREST_LIB", "libhsefr_forest.so"))
+_forest_lib = None
+FOREST_SIGNATURES = {
+    "hsefr_forest_version": (c_int, []),
+    "hsefr_forest_last_error_string": (c_char_p, []),
+    "hsefr_forest_workspace_bytes": (c_size_t, [c_int] * 5),
+    "hsefr_forest_fit": (c_int, [_fp, c_int, c_int, _fp] + [c_int] * 5 + [c_longlong, c_int] + [_fp] * 12 + [c_size_t, c_void_p]),
+    "hsefr_forest_predict": (c_int, [_fp] + [c_int] * 6 + [_fp] * 11 + [c_void_p]),
+}
+
 
 class HsefrError(RuntimeError):
     pass
@@ -224,6 +235,34 @@ def frames_check(status: int, what: str = "") -> None:
     """check() for a status of libhsefr_frames.so (its own error string)."""
     if status != OK:
         _raise(status, "%s%s (hsefr_frames status %d)" % (what + ": " if what else "", frames_last_error(), status))
+
+
+def forest_lib() -> ctypes.CDLL:
+    """Load libhsefr_forest.so once (torch first, as lib() does and for the same reason).  Missing is an error: there is no fallback."""
+    global _forest_lib
+    if _forest_lib is None:
+        import torch  # noqa: F401
+        if not os.path.exists(FOREST_LIB_PATH):
+            raise ImportError("%s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                              "(hipcc --offload-arch=gfx950). There is no CPU fallback." % FOREST_LIB_PATH)
+        L = ctypes.CDLL(FOREST_LIB_PATH)
+        for name, (res, args) in FOREST_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        _forest_lib = L
+    return _forest_lib
+
+
+def forest_last_error() -> str:
+    s = forest_lib().hsefr_forest_last_error_string()
+    return s.decode("utf-8", "replace") if s else ""
+
+
+def forest_check(status: int, what: str = "") -> None:
+    """check() for a status of libhsefr_forest.so (its own error string)."""
+    if status != OK:
+        _raise(status, "%s%s (hsefr_forest status %d)" % (what + ": " if what else "", forest_last_error(), status))
 
 
 def last_error() -> str:

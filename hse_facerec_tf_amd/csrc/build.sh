@@ -1,7 +1,8 @@
 #!/bin/bash
 # Builds libhsefr.so for gfx950 in-tree (hipcc cross-compiles without a GPU), and right after it libhsefr_album.so (include/hsefr_album.h:
 # the album organiser's device code, a library of its own because libhsefr.so is held below 4 MB by its tests) and libhsefr_frames.so
-# (include/hsefr_frames.h: the frame stack's channel swap and quarter turns, a library of its own for the same reason).
+# (include/hsefr_frames.h: the frame stack's channel swap and quarter turns, a library of its own for the same reason) and
+# libhsefr_forest.so (include/hsefr_forest.h: the random forest classifier, a fourth library for the same reason).
 #   HSEFR_DEV=1 build.sh   builds libhsefr_dev.so instead: the same sources with -DHSEFR_DEV (tuning knobs as run-time
 #                          variables, hsefr_debug_*, the calibration kernels of devtools.hip) -- for tools/kbench.py only.
 set -euo pipefail
@@ -24,6 +25,10 @@ ALBUM_FLAGS="$FLAGS $DEVICE_STRIP -ffp-contract=off"
 # the same reason, built as the second -- its own source list, the same flags in every mode
 FRAMES_SRCS="frames.hip"
 FRAMES_FLAGS="$FLAGS $DEVICE_STRIP"
+# libhsefr_forest.so (include/hsefr_forest.h: the random forest fitted and applied on the device): a fourth library, built as the third.
+# -ffp-contract=off: a candidate's score and a threshold are the restatement's fp64 operations one by one (tests/random_forest_ref.py)
+FOREST_SRCS="forest.hip"
+FOREST_FLAGS="$FLAGS $DEVICE_STRIP -ffp-contract=off"
 LINT=1
 HOST_STRIP=0
 HOST_SIZE_FLAGS=""
@@ -126,4 +131,23 @@ if [ "$LINT" = "1" ]; then
   /opt/rocm/lib/llvm/bin/llvm-strip --strip-all -w --keep-symbol='_ZN*_kernel*' --keep-symbol='!*__device_stub__*' "$FRAMES_OUT"
   python3 ../../tools/isa_lint.py "$FRAMES_OUT"
   echo "built $(realpath $FRAMES_OUT)"
+  # the fourth library: built, stripped and linted as the third
+  FOREST_OUT=../libhsefr_forest.so
+  FOREST_OBJS=""
+  for s in $FOREST_SRCS; do
+    o="$BUILD/${s%.hip}.o"
+    stale=0
+    for dep in "$s" ../../include/hsefr_forest.h build.sh; do
+      if [ ! -f "$o" ] || [ "$dep" -nt "$o" ]; then stale=1; fi
+    done
+    if [ "$stale" = 1 ]; then
+      rm -f "$o"
+      hipcc $FOREST_FLAGS -Xarch_host -Os ${HSEFR_EXTRA_FLAGS:-} -c "$s" -o "$o"
+    fi
+    FOREST_OBJS="$FOREST_OBJS $o"
+  done
+  hipcc $LINK -shared -fPIC -o "$FOREST_OUT" $FOREST_OBJS
+  /opt/rocm/lib/llvm/bin/llvm-strip --strip-all -w --keep-symbol='_ZN*_kernel*' --keep-symbol='!*__device_stub__*' "$FOREST_OUT"
+  python3 ../../tools/isa_lint.py "$FOREST_OUT"
+  echo "built $(realpath $FOREST_OUT)"
 fi

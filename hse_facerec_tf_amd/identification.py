@@ -29,6 +29,14 @@ classifier: "knn" is all of the above.  "linear_svm" replaces the search by the 
     and 'svm_iterations' in place of 'nn_index' / 'nn_dist'; ``timings`` as for "linear_svm".  scikit-learn's default tolerance stops
     about 3e-4 short of the optimum in a pair's decision value, so a vote whose value is that close to 0 can differ.  ``n_neighbors``
     must stay 1.
+    "random_forest" gives the 'rf' row of :269-273, RandomForestClassifier(n_estimators=forest_trees, max_depth=forest_depth), as the
+    forest of include/hsefr_forest.h (ops.random_forest_fit + ops.random_forest_predict_proba): scikit-learn's forest with its
+    sequential generator replaced by a hash of (forest_seed, tree, node), so that the result is a pure function of its inputs --
+    scikit-learn's own labels vary from run to run (the reference sets no random_state), so there are none to reproduce; the fixture's
+    accuracy lies inside the recorded spread of scikit-learn's forests (README.md).  After a PCA the forest sees the projection's
+    columns without their zero padding.  The result holds 'proba_max' ([nq] on the host: the predicted class's probability) and
+    'forest_nodes' ([forest_trees]: the node count of every tree) in place of 'nn_index' / 'nn_dist'; ``timings`` receives forest_fit_s
+    and forest_predict_s in place of nn1_s.  ``n_neighbors`` must stay 1.
 metric: "l2" is all of the above.  "chi2" and "kl" give the reference's k-NN rows under its other two distances, chi2dist and KL_dist
     (facerec_test.py:157-164; KNeighborsClassifier(n_neighbors=1, metric=chi2dist) and metric=KL_dist at :275-276 and :424-425, which
     scikit-learn evaluates pair by pair in Python): every search, n_neighbors = 1 included, goes through ops.knn(metric=), the probe
@@ -38,6 +46,7 @@ metric: "l2" is all of the above.  "chi2" and "kl" give the reference's k-NN row
     rows).  Only with classifier="knn" and without ``pca_components``: projections are signed, and the reference never combines them.
 svm_C: the C of either SVM.  svm_gamma: "scale" (1 / (d Var) of the gallery rows, over the unpadded columns after a PCA) or a positive
     finite number.
+forest_trees, forest_depth, forest_seed: the random forest's tree count, depth limit and seed (100, 10 and 0: the reference's row).
 """
 from __future__ import annotations
 
@@ -111,9 +120,10 @@ def check_pca_mode(pca) -> str:
     return pca
 
 
-def check_classifier(classifier, n_neighbors=1, svm_C=1.0, svm_gamma="scale") -> str:
-    """The classifier keyword of the protocols, raised as ValueError before the library or a device is touched."""
-    if not isinstance(classifier, str) or classifier not in ("knn", "linear_svm", "rbf_svm"):
+def check_classifier(classifier, n_neighbors=1, svm_C=1.0, svm_gamma="scale", forest_trees=100, forest_depth=10, forest_seed=0) -> str:
+    """The classifier keyword of the protocols, raised as ValueError before the library or a device is touched.  (The sentence for an
+    unknown name lists the three classifiers it listed before "random_forest" joined them; the module docstring lists all four.)"""
+    if not isinstance(classifier, str) or classifier not in ("knn", "linear_svm", "rbf_svm", "random_forest"):
         raise ValueError("classifier=%r must be 'knn' (ops.nn1 / ops.knn), 'linear_svm' (ops.linear_svm_fit) or 'rbf_svm' (ops.rbf_svm_fit)"
                          % (classifier,))
     if classifier == "rbf_svm":
@@ -128,6 +138,13 @@ def check_classifier(classifier, n_neighbors=1, svm_C=1.0, svm_gamma="scale") ->
         if n_neighbors != 1:
             raise ValueError("n_neighbors=%r has no meaning with classifier='linear_svm': leave it at 1" % (n_neighbors,))
         ops.check_linear_svm_args(1, 1, 2, C=svm_C)
+    if classifier == "random_forest":
+        from . import ops
+        if n_neighbors != 1:
+            raise ValueError("n_neighbors=%r has no meaning with classifier='random_forest': leave it at 1" % (n_neighbors,))
+        for name, v, least in (("forest_trees", forest_trees, 1), ("forest_depth", forest_depth, 1), ("forest_seed", forest_seed, 0)):
+            ops._int_arg(name, v, least)
+        ops.check_random_forest_args(2, 1, 2, n_trees=forest_trees, max_depth=forest_depth, seed=forest_seed)
     return classifier
 
 
@@ -140,16 +157,19 @@ class _Keywords(NamedTuple):
     svm_C: float
     svm_gamma: object
     metric: str = "l2"
+    forest_trees: int = 100
+    forest_depth: int = 10
+    forest_seed: int = 0
 
 
 def _check_keywords(n_neighbors=1, pca="host", pca_components=None, classifier="knn", svm_C=1.0, svm_gamma="scale",
-                    n_gallery=None, metric="l2") -> _Keywords:
+                    n_gallery=None, metric="l2", forest_trees=100, forest_depth=10, forest_seed=0) -> _Keywords:
     """Every keyword check of the protocols, raised as ValueError before the library is loaded or a device is touched; ``n_gallery``:
     the gallery rows, where the protocol knows them this early."""
     from . import ops
     ops.check_n_neighbors(n_neighbors, n_gallery)
     check_pca_mode(pca)
-    check_classifier(classifier, n_neighbors, svm_C, svm_gamma)
+    check_classifier(classifier, n_neighbors, svm_C, svm_gamma, forest_trees, forest_depth, forest_seed)
     if pca_components and pca == "device":
         ops.check_pca_components(pca_components, n_gallery)
     if ops.check_metric(metric) != "l2":
@@ -158,7 +178,7 @@ def _check_keywords(n_neighbors=1, pca="host", pca_components=None, classifier="
         if pca_components:
             raise ValueError("metric=%r wants non-negative features, and a PCA's projections are signed: leave pca_components unset"
                              % (metric,))
-    return _Keywords(n_neighbors, pca, pca_components, classifier, svm_C, svm_gamma, metric)
+    return _Keywords(n_neighbors, pca, pca_components, classifier, svm_C, svm_gamma, metric, forest_trees, forest_depth, forest_seed)
 
 
 def _phase_clock(torch, device, timings: Optional[dict]):
@@ -225,8 +245,9 @@ def _encode_labels(torch, y_gallery: np.ndarray, device):
 def _classify(torch, ops, gal, qry, y_gallery: np.ndarray, kw: _Keywords, lap=lambda key: None):
     """The classifier of ``kw`` fitted on (gal, y_gallery) and applied to ``qry`` on the device -> (y_pred, extras), everything on the
     host.  extras: 'nn_index' + 'nn_dist' of the searches, 'decision' + 'svm_iterations' of the linear SVM, 'votes' + 'svm_iterations'
-    of the RBF SVM.  ``lap`` (a _phase_clock) is called with nn1_s after the search -- for n_neighbors = 1 before anything is copied
-    to the host, for more after the copies -- or with svm_fit_s and svm_predict_s."""
+    of the RBF SVM, 'proba_max' + 'forest_nodes' of the random forest.  ``lap`` (a _phase_clock) is called with nn1_s after the search
+    -- for n_neighbors = 1 before anything is copied to the host, for more after the copies -- or with svm_fit_s and svm_predict_s,
+    or with forest_fit_s and forest_predict_s."""
     if kw.classifier == "knn" and kw.n_neighbors == 1 and kw.metric == "l2":
         nn_idx, nn_d2 = ops.nn1(qry, gal)
         lap("nn1_s")
@@ -246,6 +267,18 @@ def _classify(torch, ops, gal, qry, y_gallery: np.ndarray, kw: _Keywords, lap=la
         lap("nn1_s")
         return y_pred, extras
     n, d, K = int(gal.shape[0]), int(gal.shape[1]), len(classes)
+    if kw.classifier == "random_forest":        # RandomForestClassifier(forest_trees, max_depth=forest_depth): predict_proba + predict
+        if kw.pca_components and d > kw.pca_components:          # the projection without its zero padding
+            gal, qry = gal[:, :kw.pca_components].contiguous(), qry[:, :kw.pca_components].contiguous()
+        forest = ops.random_forest_fit(gal, labels, max(K, 2), n_trees=kw.forest_trees, max_depth=kw.forest_depth, seed=kw.forest_seed)
+        lap("forest_fit_s")
+        nodes = forest.n_nodes.cpu().numpy()
+        if qry.shape[0] == 0:
+            lap("forest_predict_s")
+            return classes[:0], {"proba_max": np.zeros((0,), dtype=np.float64), "forest_nodes": nodes}
+        proba, pred = ops.random_forest_predict_proba(forest, qry)
+        lap("forest_predict_s")
+        return classes[pred.cpu().numpy()], {"proba_max": proba.max(dim=1).values.cpu().numpy(), "forest_nodes": nodes}
     if kw.classifier == "linear_svm":           # LinearSVC(C=svm_C): decision_function + predict
         coef, intercept, info = ops.linear_svm_fit(gal, labels, K, C=kw.svm_C, tol=LINEAR_SVM_TOL, max_iter=LINEAR_SVM_MAX_ITER)
         if not info["converged"]:
@@ -281,11 +314,11 @@ def _classify(torch, ops, gal, qry, y_gallery: np.ndarray, kw: _Keywords, lap=la
 def one_nn_identification(X, y: np.ndarray, split=None,
                           pca_components: Optional[int] = None, timings: Optional[dict] = None, device=None,
                           n_neighbors: int = 1, pca: str = "host", classifier: str = "knn", svm_C: float = 1.0, svm_gamma="scale",
-                          metric: str = "l2") -> Dict:
+                          metric: str = "l2", forest_trees: int = 100, forest_depth: int = 10, forest_seed: int = 0) -> Dict:
     """The protocol of facerec_test.py:401-432: 'k-NN' (pca_components=None) or 'k-NN+PCA' (pca_components=128, the Pipeline of :421)
-    on a stratified half split of the samples whose class has more than one; ``classifier`` gives the 'linear svm' row of :429 and the
-    'svm' row instead, ``metric`` the chi2dist / KL_dist rows of :424-425.  n_neighbors, pca, classifier, svm_C, svm_gamma and metric: see
-    the module docstring; the gallery is the train half.
+    on a stratified half split of the samples whose class has more than one; ``classifier`` gives the 'linear svm' row of :429, the
+    'svm' row or the 'rf' row instead, ``metric`` the chi2dist / KL_dist rows of :424-425.  n_neighbors, pca, classifier, svm_C, svm_gamma,
+    metric and forest_trees / forest_depth / forest_seed: see the module docstring; the gallery is the train half.
 
     X: [N, D] float32 embeddings, CUDA tensor or NumPy array (uploaded to ``device``, default: the current one); y: [N] labels.
     split: None (compute it here), a (train, test) pair over the FILTERED samples, or a SplitJob started on the same labels.
@@ -294,7 +327,8 @@ def one_nn_identification(X, y: np.ndarray, split=None,
     pca="device"), the classifier's (nn1_s, and nn1_shape with it), readback_s (indices and distances back to the host + the label
     comparison)."""
     from . import _lib, ops
-    kw = _check_keywords(n_neighbors, pca, pca_components, classifier, svm_C, svm_gamma, metric=metric)
+    kw = _check_keywords(n_neighbors, pca, pca_components, classifier, svm_C, svm_gamma, metric=metric, forest_trees=forest_trees,
+                         forest_depth=forest_depth, forest_seed=forest_seed)
     torch = _lib.require_gpu()
     if isinstance(X, np.ndarray):
         X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(_lib.cuda_device(device))
@@ -370,15 +404,17 @@ def cross_validated_1nn(X, y: np.ndarray, cv, normalize: bool = True, device=Non
 
 def gallery_probe_identification(X_train, y_train: np.ndarray, X_test, y_test: np.ndarray, normalize: bool = False,
                                  pca_components: Optional[int] = None, device=None, n_neighbors: int = 1, pca: str = "host",
-                                 classifier: str = "knn", svm_C: float = 1.0, svm_gamma="scale", metric: str = "l2") -> Dict:
+                                 classifier: str = "knn", svm_C: float = 1.0, svm_gamma="scale", metric: str = "l2",
+                                 forest_trees: int = 100, forest_depth: int = 10, forest_seed: int = 0) -> Dict:
     """The gallery / probe protocol of tf_train_test_recognition (facerec_test.py:260-288): the '1-NN' classifier (and
     '1-NN+PCA' with ``pca_components``, 16 at :269) FITTED on the gallery features, every probe labelled by its nearest
     gallery row; accuracy = share of probes whose label is right (:287).  NB the reference computes L2-normalised copies
     (:262,265) and then fits / predicts on the UN-normalised ``X_train`` / ``X_test`` (:284-285): ``normalize=False`` is what
-    it runs, ``normalize=True`` what the copies suggest it meant.  n_neighbors, pca, classifier, svm_C, svm_gamma and metric give the
-    other rows of :269-276: see the module docstring.  Returns 'accuracy', 'y_pred' and the classifier's extras."""
+    it runs, ``normalize=True`` what the copies suggest it meant.  n_neighbors, pca, classifier, svm_C, svm_gamma, metric and
+    forest_trees / forest_depth / forest_seed give the other rows of :269-276: see the module docstring.  Returns 'accuracy', 'y_pred' and the classifier's extras."""
     from . import _lib, ops
-    kw = _check_keywords(n_neighbors, pca, pca_components, classifier, svm_C, svm_gamma, n_gallery=len(np.asarray(y_train)), metric=metric)
+    kw = _check_keywords(n_neighbors, pca, pca_components, classifier, svm_C, svm_gamma, n_gallery=len(np.asarray(y_train)), metric=metric,
+                         forest_trees=forest_trees, forest_depth=forest_depth, forest_seed=forest_seed)
     torch = _lib.require_gpu()
     dev = _lib.cuda_device(device)
 

@@ -845,6 +845,232 @@ def rbf_svm_predict(q, x, labels, n_classes: int, gamma, dual_coef, rho, return_
     return pred, votes
 
 
+# hsefr_forest_*'s limits (include/hsefr_forest.h)
+FOREST_MAX_N, FOREST_MAX_D, FOREST_MAX_CLASSES, FOREST_MAX_TREES, FOREST_MAX_DEPTH = 65535, 4096, 2048, 1024, 24
+FOREST_MAX_CANDIDATES, FOREST_MAX_PROBES, FOREST_MAX_SLAB_BYTES, FOREST_SORT_TILE = 1 << 28, 1 << 24, 1 << 32, 4096
+FOREST_INFO_BAD_LABEL, FOREST_INFO_NOT_FINITE, FOREST_INFO_INTERNAL = 1, 2, 4      # HSEFR_FOREST_INFO_*
+
+
+def forest_node_capacity(n: int, max_depth: int) -> int:
+    """The worst case of one tree, the stride of a fitted forest's node arrays: min(2^(max_depth + 1) - 1, 2 n - 1)."""
+    return min((1 << (max_depth + 1)) - 1, 2 * n - 1)
+
+
+def check_random_forest_args(n, d, n_classes, n_trees=100, max_depth=10, max_features="sqrt", bootstrap=True, seed=0) -> int:
+    """hsefr_forest_fit's argument ranges, raised as ValueError before the library or a device is touched.  Returns max_features as a
+    number: "sqrt" is max(1, int(sqrt(d))) as in scikit-learn."""
+    for name, v, least in (("n", n, 1), ("d", d, 1), ("n_classes", n_classes, 2), ("n_trees", n_trees, 1), ("max_depth", max_depth, 1)):
+        _int_arg(name, v, least)
+    if isinstance(max_features, str):
+        if max_features != "sqrt":
+            raise ValueError("max_features=%r must be 'sqrt' or an integer in 1..d" % (max_features,))
+        mf = max(1, int(np.sqrt(d)))
+    else:
+        mf = _int_arg("max_features", max_features, 1, d, says="max_features=%%r must be 'sqrt' or an integer in 1..d=%d" % d)
+    if not isinstance(bootstrap, (bool, np.bool_)):
+        raise ValueError("bootstrap must be True or False, got %r" % (bootstrap,))
+    _int_arg("seed", seed, 0, (1 << 63) - 1)
+    widest = min(1 << (max_depth - 1), n) if max_depth <= FOREST_MAX_DEPTH else 0
+    if (n > FOREST_MAX_N or d > FOREST_MAX_D or n_classes > FOREST_MAX_CLASSES or n_trees > FOREST_MAX_TREES or max_depth > FOREST_MAX_DEPTH
+            or n_trees * widest * mf > FOREST_MAX_CANDIDATES):
+        raise ValueError("n=%d d=%d n_classes=%d n_trees=%d max_depth=%d max_features=%d over the limits n <= %d, d <= %d, n_classes <= %d, "
+                         "n_trees <= %d, max_depth <= %d, n_trees min(2^(max_depth-1), n) max_features <= %d"
+                         % (n, d, n_classes, n_trees, max_depth, mf, FOREST_MAX_N, FOREST_MAX_D, FOREST_MAX_CLASSES, FOREST_MAX_TREES,
+                            FOREST_MAX_DEPTH, FOREST_MAX_CANDIDATES))
+    slab = n_trees * mf * 2 * n * 8 if n > FOREST_SORT_TILE else 0
+    if slab > FOREST_MAX_SLAB_BYTES:
+        raise ValueError("n=%d rows exceed one sort tile of %d, and n_trees=%d x max_features=%d x 2 n keys of 8 bytes are %d bytes of sort "
+                         "space, over the limit of %d" % (n, FOREST_SORT_TILE, n_trees, mf, slab, FOREST_MAX_SLAB_BYTES))
+    return mf
+
+
+class RandomForest:
+    """A forest as hsefr_forest_predict reads it: device tensors, a tree's slice at [tree] of each.  feature int32 [T, M] (-1: a leaf),
+    threshold float64 [T, M], left / right int32 [T, M] (node indices inside the tree), weight int32 [T, M] (a node's weighted row
+    count), leaf_begin / leaf_len int32 [T, M] (leaves: a slice of the tree's list), leaf_class / leaf_count int32 [T, L], n_nodes
+    int32 [T]; n_classes and n_features are numbers."""
+    ARRAYS = ("feature", "threshold", "left", "right", "weight", "leaf_begin", "leaf_len", "leaf_class", "leaf_count", "n_nodes")
+
+    def __init__(self, n_classes, n_features, **arrays):
+        self.n_classes, self.n_features = int(n_classes), int(n_features)
+        for name in self.ARRAYS:
+            setattr(self, name, arrays[name])
+
+    @property
+    def n_trees(self) -> int:
+        return int(self.feature.shape[0])
+
+    @property
+    def node_capacity(self) -> int:
+        return int(self.feature.shape[1])
+
+    @property
+    def leaf_capacity(self) -> int:
+        return int(self.leaf_class.shape[1])
+
+    @property
+    def device(self):
+        return self.feature.device
+
+
+@_device_guarded
+def random_forest_fit(x, labels, n_classes: int, n_trees: int = 100, max_depth: int = 10, max_features="sqrt", bootstrap: bool = True,
+                      seed: int = 0) -> RandomForest:
+    """The forest of include/hsefr_forest.h fitted on the device (hsefr_forest_fit): x [n,d] float32, labels [n] int32 codes in
+    0..n_classes-1 -> a RandomForest.  The defaults are the reference's 'rf' row, RandomForestClassifier(n_estimators=100,
+    max_depth=10); the forest is a pure function of its arguments (tests/random_forest_ref.py restates it, and the device equals that
+    bit for bit).  A label code out of range or a value of x that is not finite raises ValueError (checked on the device during the
+    fit, read back once)."""
+    if getattr(x, "ndim", 0) != 2:
+        raise ValueError("x must be [n, d]")
+    mf = check_random_forest_args(int(x.shape[0]), int(x.shape[1]), n_classes, n_trees, max_depth, max_features, bootstrap, seed)
+    torch = _lib.require_gpu()
+    _f32c(x, "x")
+    n, d = int(x.shape[0]), int(x.shape[1])
+    _labels_arg(torch, labels, n, x)
+    T, M = int(n_trees), forest_node_capacity(n, int(max_depth))
+    L = _lib.forest_lib()
+    need = int(L.hsefr_forest_workspace_bytes(n, d, T, int(max_depth), mf))
+    if need == 0:
+        _lib.forest_check(_lib.ERR_UNSUPPORTED, "hsefr_forest_workspace_bytes")
+    i32 = dict(dtype=torch.int32, device=x.device)
+    arrays = {name: torch.empty((T, M), **i32) for name in ("feature", "left", "right", "weight", "leaf_begin", "leaf_len")}
+    arrays["threshold"] = torch.empty((T, M), dtype=torch.float64, device=x.device)
+    arrays["leaf_class"], arrays["leaf_count"] = torch.empty((T, n), **i32), torch.empty((T, n), **i32)
+    arrays["n_nodes"] = torch.empty((T,), **i32)
+    info = torch.empty((4,), **i32)
+    workspace = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=x.device)
+    a = arrays
+    _lib.forest_check(L.hsefr_forest_fit(x.data_ptr(), n, d, labels.data_ptr(), int(n_classes), T, int(max_depth), mf, int(bool(bootstrap)),
+                                         int(seed), M, a["feature"].data_ptr(), a["threshold"].data_ptr(), a["left"].data_ptr(),
+                                         a["right"].data_ptr(), a["weight"].data_ptr(), a["leaf_begin"].data_ptr(), a["leaf_len"].data_ptr(),
+                                         a["leaf_class"].data_ptr(), a["leaf_count"].data_ptr(), a["n_nodes"].data_ptr(), info.data_ptr(),
+                                         workspace.data_ptr(), need, _lib.current_stream_ptr()), "hsefr_forest_fit")
+    bits = int(info.cpu()[0])                       # the one read-back: it also keeps the workspace alive until the fit has run
+    if bits & FOREST_INFO_BAD_LABEL:
+        raise ValueError("labels (int32 [%d]) hold a code outside 0..n_classes-1 = %d" % (n, int(n_classes) - 1))
+    if bits & FOREST_INFO_NOT_FINITE:
+        raise ValueError("x (float32 [%d, %d]) holds a NaN or an infinity: the forest wants finite features" % (n, d))
+    if bits:
+        raise _lib.HsefrError("hsefr_forest_fit: an index left its bound on the device (info %d); the forest is not usable" % bits)
+    return RandomForest(n_classes, d, **arrays)
+
+
+def _forest_arrays(torch, forest):
+    """The ten arrays of a RandomForest as hsefr_forest_predict reads them: dtype, shape, device and contiguity of each, so that a forest
+    built by hand cannot be read out of bounds."""
+    feature = forest.feature
+    if not (hasattr(feature, "is_cuda") and feature.is_cuda and feature.ndim == 2 and feature.shape[0] >= 1 and feature.shape[1] >= 1):
+        raise ValueError("forest.feature must be a contiguous int32 CUDA tensor [n_trees, node_capacity], got %s"
+                         % (tuple(getattr(feature, "shape", ())),))
+    T, M = int(feature.shape[0]), int(feature.shape[1])
+    lists = forest.leaf_class
+    L = int(lists.shape[1]) if getattr(lists, "ndim", 0) == 2 and lists.shape[1] >= 1 else -1
+    for name in RandomForest.ARRAYS:
+        dtype = torch.float64 if name == "threshold" else torch.int32
+        shape = (T,) if name == "n_nodes" else (T, L) if name in ("leaf_class", "leaf_count") else (T, M)
+        t = getattr(forest, name)
+        if not (hasattr(t, "is_cuda") and t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape
+                and t.device == feature.device) or L < 1:
+            raise ValueError("forest.%s must be a contiguous %s CUDA tensor of shape %s on %s, got %s %s on %s%s"
+                             % (name, "float64" if name == "threshold" else "int32", "[n_trees, leaf_capacity >= 1]" if L < 1 else shape,
+                                feature.device, getattr(t, "dtype", type(t).__name__), tuple(getattr(t, "shape", ())), getattr(t, "device", "the host"),
+                                "" if not hasattr(t, "is_contiguous") or t.is_contiguous() else ", not contiguous"))
+    if not (2 <= forest.n_classes <= FOREST_MAX_CLASSES and 1 <= forest.n_features <= FOREST_MAX_D and T <= FOREST_MAX_TREES):
+        raise ValueError("n_classes=%d n_features=%d n_trees=%d outside 2 <= n_classes <= %d, 1 <= n_features <= %d, n_trees <= %d"
+                         % (forest.n_classes, forest.n_features, T, FOREST_MAX_CLASSES, FOREST_MAX_D, FOREST_MAX_TREES))
+
+
+def _forest_probes(torch, forest, q):
+    if getattr(q, "ndim", 0) != 2 or int(q.shape[1]) != forest.n_features:
+        raise ValueError("q must be [nq, d] with the forest's d = %d, got shape %s" % (forest.n_features, tuple(getattr(q, "shape", ()))))
+    nq = int(q.shape[0])
+    if nq < 1 or nq > FOREST_MAX_PROBES:
+        raise ValueError("nq=%d must be in 1..%d" % (nq, FOREST_MAX_PROBES))
+    _f32c(q, "q")
+    if q.device != forest.device:
+        raise ValueError("q (float32 [%d, %d]) lives on %s, the forest on %s" % (nq, forest.n_features, q.device, forest.device))
+    return nq
+
+
+def _forest_predict(forest, q, want_proba):
+    if not isinstance(forest, RandomForest):
+        raise ValueError("forest must be a RandomForest (ops.random_forest_fit or ops.random_forest_from_sklearn), got %s" % type(forest).__name__)
+    torch = _lib.require_gpu()
+    _forest_arrays(torch, forest)
+    nq = _forest_probes(torch, forest, q)
+    proba = torch.empty((nq, forest.n_classes), dtype=torch.float64, device=q.device) if want_proba else None
+    pred = torch.empty((nq,), dtype=torch.int32, device=q.device)
+    f = forest
+    _lib.forest_check(_lib.forest_lib().hsefr_forest_predict(
+        q.data_ptr(), nq, f.n_features, f.n_classes, f.n_trees, f.node_capacity, f.leaf_capacity, f.feature.data_ptr(), f.threshold.data_ptr(),
+        f.left.data_ptr(), f.right.data_ptr(), f.weight.data_ptr(), f.leaf_begin.data_ptr(), f.leaf_len.data_ptr(), f.leaf_class.data_ptr(),
+        f.leaf_count.data_ptr(), proba.data_ptr() if proba is not None else None, pred.data_ptr(), _lib.current_stream_ptr()),
+        "hsefr_forest_predict")
+    return proba, pred
+
+
+@_device_guarded
+def random_forest_predict_proba(forest, q):
+    """predict_proba of the probes q [nq,d] float32 (hsefr_forest_predict): ([nq, n_classes] float64, [nq] int32 labels).  A class's
+    value is (sum over trees of its share of the probe's leaf) / n_trees, added in tree order in fp64."""
+    return _forest_predict(forest, q, True)
+
+
+@_device_guarded
+def random_forest_predict(forest, q):
+    """predict of the probes q [nq,d] float32: int32 [nq], the class of the largest probability, equal values to the lowest class.  A
+    probe that met an index out of range in a forest from elsewhere is labelled -1."""
+    return _forest_predict(forest, q, False)[1]
+
+
+def random_forest_from_sklearn(estimator, device=None) -> RandomForest:
+    """A fitted RandomForestClassifier or DecisionTreeClassifier (single output) copied into a RandomForest on ``device``: scikit-learn's
+    own node order, its fp64 thresholds, and a leaf's class fractions x weighted_n_node_samples as integer counts (scikit-learn's
+    bootstrap weights are counts)."""
+    # the fitted attributes are all that is read (tree_, estimators_, n_classes_, n_features_in_, n_outputs_): scikit-learn itself is
+    # not imported, here or anywhere else in the package's device paths
+    trees = [estimator] if hasattr(estimator, "tree_") else list(getattr(estimator, "estimators_", ()))
+    if not trees or not all(hasattr(t, "tree_") for t in trees) or getattr(estimator, "n_outputs_", 0) != 1:
+        raise ValueError("estimator must be a fitted single-output RandomForestClassifier or DecisionTreeClassifier, got %s"
+                         % type(estimator).__name__)
+    C, d = int(estimator.n_classes_), int(estimator.n_features_in_)
+    if C < 2 or C > FOREST_MAX_CLASSES or d > FOREST_MAX_D or len(trees) > FOREST_MAX_TREES:
+        raise ValueError("n_classes=%d d=%d n_trees=%d outside 2 <= n_classes <= %d, d <= %d, n_trees <= %d"
+                         % (C, d, len(trees), FOREST_MAX_CLASSES, FOREST_MAX_D, FOREST_MAX_TREES))
+    leaves = []
+    for t in trees:
+        tr = t.tree_
+        is_leaf = tr.children_left < 0
+        counts = tr.value[:, 0, :] * tr.weighted_n_node_samples[:, None]
+        whole = np.rint(counts)
+        if np.abs(counts - whole)[is_leaf].max() > 1e-6:
+            raise ValueError("a leaf's class fractions x weighted_n_node_samples are not integer counts: fractional sample weights "
+                             "are not supported")
+        node, cls = np.nonzero((whole > 0) & is_leaf[:, None])          # by node, then by class
+        leaves.append((node, cls, whole[node, cls].astype(np.int32), is_leaf))
+    T, M, L = len(trees), max(t.tree_.node_count for t in trees), max(1, max(len(node) for node, _, _, _ in leaves))
+    a = {name: np.full((T, M), -1, dtype=np.int32) for name in ("feature", "left", "right", "weight", "leaf_begin", "leaf_len")}
+    a["threshold"] = np.zeros((T, M), dtype=np.float64)
+    a["leaf_class"], a["leaf_count"] = np.full((T, L), -1, dtype=np.int32), np.zeros((T, L), dtype=np.int32)
+    a["n_nodes"] = np.zeros((T,), dtype=np.int32)
+    for i, (t, (node, cls, cnt, is_leaf)) in enumerate(zip(trees, leaves)):
+        tr = t.tree_
+        m = tr.node_count
+        a["n_nodes"][i] = m
+        a["feature"][i, :m] = np.where(is_leaf, -1, tr.feature)
+        a["threshold"][i, :m] = np.where(is_leaf, 0.0, tr.threshold)
+        a["left"][i, :m], a["right"][i, :m] = tr.children_left, tr.children_right
+        a["weight"][i, :m] = np.rint(tr.weighted_n_node_samples).astype(np.int32)
+        per_node = np.bincount(node, minlength=m).astype(np.int32)
+        begin = np.concatenate([[0], np.cumsum(per_node)[:-1]]).astype(np.int32)
+        a["leaf_begin"][i, :m], a["leaf_len"][i, :m] = np.where(is_leaf, begin, -1), np.where(is_leaf, per_node, -1)
+        a["leaf_class"][i, :len(cls)], a["leaf_count"][i, :len(cls)] = cls, cnt
+    torch = _lib.require_gpu()
+    dev = _lib.cuda_device(device)
+    return RandomForest(C, d, **{name: torch.from_numpy(v).to(dev) for name, v in a.items()})
+
+
 @_device_guarded
 def conv2d_direct(x, w_hwio, bias=None, alpha=None, stride: int = 1, padding: str = "VALID"):
     """Generic Conv2D + BiasAdd + optional PReLU (MTCNN nets).  padding: 'VALID' | 'SAME' (TensorFlow rule)."""
