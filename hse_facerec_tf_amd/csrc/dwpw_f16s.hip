@@ -50,6 +50,10 @@ struct DwPwSParams {
     int reverse;           // sweep direction (common.h)
     int nimg;              // batch (LDS-DMA form: buffer resource sizes)
     unsigned m_n, m_w, m_h;   // v3: ceil(2^32 / d) for d = tiles_n, tiles_w, tiles_h (exact quotients for x * d < 2^32; 0 for d = 1)
+    // v3 strip mode (seam != 0, 16 x 8 patches only): the batch is ONE map of rows = n * OH rows, an image seam every `seam` = OH = H of
+    // them, and a patch row index counts over that whole map (tiles_h patches tall, decode's image index is always 0)
+    int rows, seam;        // rows a store may reach (per-image tiling: OH), rows between seams (per-image tiling: 0)
+    unsigned m_seam;       // ceil(2^32 / seam)
     unsigned long long* stamps;   // diagnostic builds (-DHSEFR_STEM_STAMPS) only
 };
 
@@ -255,7 +259,7 @@ __global__ __launch_bounds__(256, OCC) void dwpw_f16s_kernel(DwPwSParams p) {
 //     per-lane offsets are out of range for pixels beyond the map (partial patches cost no branches).
 // The (patch, chunk) steps of a workgroup form one flat sequence, so the first chunk of the next patch streams in under
 // the last MFMAs and the stores of the current one.
-constexpr int HALO_B = 192 * 128;   // 180 pixels used, 24 wave-instructions of 8 pixels
+constexpr int HALO_B = 192 * 128;   // 180 pixels used (190 by a strip-mode patch with an image seam in it), 24 wave-instructions of 8 pixels
 constexpr int CMAX2 = 512;          // channel bound of the resident depthwise constants (11 floats per channel)
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -333,14 +337,28 @@ __global__ __launch_bounds__(256 + 64 * (BN == 256 ? 8 : 4), BN == 256 ? 1 : 2) 
     unsigned hv[HPW];
     unsigned pf_i = 0;
     int pf_kc = 0, pf_step = 0;
+    // Strip mode: a patch of 16 rows may hold the last rows of one image and the first rows of the next (OH % 4 == 0 and OH >= 16: at most
+    // one seam, at patch row 4, 8 or 12, so the four rows of a producer thread lie on one side of it).  The halo stage then takes the source
+    // rows above the seam, ONE zero row -- the padding below the upper image and above the lower one -- and the rows below the seam: 19 rows
+    // of 10 cells in the stage's 192.  Producer threads below the seam read one halo row further down; the arithmetic does not change.
+    auto seam_row = [&](const Item& it) {      // patch row at which the next image starts (16 and more: not inside this patch)
+        return ((int)fastdiv(it.oh0, p.m_seam) + 1) * p.seam - it.oh0;
+    };
     auto setup_halo = [&](unsigned i) {
         const Item it = decode(i);
+        int zr = 99, lo = 0, hi = p.H;          // halo row that stays zero; source rows [lo, hi) belong to this patch's image(s)
+        if (TW == 8 && p.seam) {
+            zr = seam_row(it) + 1;
+            lo = it.oh0 + zr - 1 - p.seam;      // first row of the upper image (a seam on the patch's edge is an ordinary top / bottom border)
+            hi = p.rows;
+        }
+        const int nq = (TH + 2 + (zr <= TH ? 1 : 0)) * HC;
 #pragma unroll
         for (int j = 0; j < HPW; ++j) {
             const int q = (hw * HPW + j) * 8 + (lane >> 3);
             const int hr = q / HC, hc = q - hr * HC;
-            const int ih = it.oh0 - p.pad_t + hr, iw = it.ow0 - p.pad_l + hc;
-            const bool ok = q < (TH + 2) * HC && ih >= 0 && ih < p.H && iw >= 0 && iw < p.W;
+            const int ih = it.oh0 - p.pad_t + hr - (hr > zr ? 1 : 0), iw = it.ow0 - p.pad_l + hc;
+            const bool ok = q < nq && hr != zr && ih >= lo && ih < hi && iw >= 0 && iw < p.W;
             hv[j] = ok ? ((unsigned)((it.n * p.H + ih) * p.W + iw) * (unsigned)C + 4u * (lane & 7)) * 4u : OOB;
         }
     };
@@ -370,6 +388,9 @@ __global__ __launch_bounds__(256 + 64 * (BN == 256 ? 8 : 4), BN == 256 ? 1 : 2) 
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         int dkc = 0;                      // chunk of the step the depthwise works on (step g + 1)
+        unsigned di = 0;                  // ... and its patch; hx: this thread's rows lie below that patch's seam, one halo row further down
+        auto seam_shift = [&](unsigned i) { return TW == 8 && p.seam && r0 >= seam_row(decode(i)) ? HC * 128 : 0; };
+        int hx = seam_shift(0);
         for (int g = -1; g < nsteps; ++g) {
             const bool issued = !HALO_BY_CONSUMER && pf_step < nsteps;
             if (issued) halo_dma();
@@ -383,7 +404,7 @@ __global__ __launch_bounds__(256 + 64 * (BN == 256 ? 8 : 4), BN == 256 ? 1 : 2) 
 #pragma unroll
                 for (int i = 0; i < 9; ++i) wk[i] = wl[i * p.C4];
                 const f32x4 dsc = wl[9 * p.C4], dsh = wl[10 * p.C4];
-                const unsigned char* hs = hsrc0 + ((g + 1) % HS) * HALO_B;
+                const unsigned char* hs = hsrc0 + ((g + 1) % HS) * HALO_B + hx;
                 unsigned char* At = smem + A_OFF + ((g + 1) & 1) * (128 * ROWB);
                 f32x4 h[6][3];
 #pragma unroll
@@ -410,7 +431,7 @@ __global__ __launch_bounds__(256 + 64 * (BN == 256 ? 8 : 4), BN == 256 ? 1 : 2) 
                     *(f16x4*)(At + swzb(R, quad >> 1) + 8 * (quad & 1)) = hi;
                     *(f16x4*)(At + swzb(R, 4 + (quad >> 1)) + 8 * (quad & 1)) = lo;
                 }
-                if (++dkc == KT) { dkc = 0; STEM_STAMP_COUNT; }
+                if (++dkc == KT) { dkc = 0; hx = seam_shift(++di); STEM_STAMP_COUNT; }
             }
             STEM_STAMP(2);
             // the halo of step g + 2 must have landed before the next iteration reads it; with a 3-deep ring the pieces
@@ -470,7 +491,7 @@ __global__ __launch_bounds__(256 + 64 * (BN == 256 ? 8 : 4), BN == 256 ? 1 : 2) 
                 for (int i = 0; i < 4; ++i) {
                     const int R = wm * 64 + mi * 32 + erow + 8 * i;
                     const int oh = cur.oh0 + R / TW, ow = cur.ow0 + R % TW;
-                    sv[mi][i] = (oh < p.OH && ow < p.OW)
+                    sv[mi][i] = (oh < p.rows && ow < p.OW)      // (strip mode: cur.n = 0 and oh counts over the whole batch)
                                     ? ((unsigned)((cur.n * p.OH + oh) * p.OW + ow) * (unsigned)p.Cout + (unsigned)(cur.n0 + wn * WN + 4 * ech)) * 4u
                                     : OOB;
                 }
@@ -893,15 +914,20 @@ int launch_bn(DwPwSParams& p, int n, int bn, int act, hipStream_t s) {
 }
 
 template <int TW, int BN, int HS>
-int launch_v3(DwPwSParams& p, int n, int act, hipStream_t s) {
+int launch_v3(DwPwSParams& p, int n, int act, bool strip, hipStream_t s) {
     constexpr int TH = 128 / TW;
+    auto magic = [](unsigned d) { return d == 1 ? 0u : (unsigned)((0x100000000ull + d - 1) / d); };
+    if (strip) {      // the batch as one map of n * OH rows (the kernel's strip mode: 16 x 8 patches)
+        HSEFR_REQUIRE(TW == 8 && (long long)n * p.OH * p.OH < (1ll << 32), HSEFR_ERR_UNSUPPORTED, "dwpw_f16split: strip tiling");
+        p.rows = n * p.OH; p.seam = p.OH; p.m_seam = magic(p.OH);
+        n = 1;
+    }
     p.tiles_w = (p.OW + TW - 1) / TW;
-    p.tiles_h = (p.OH + TH - 1) / TH;
+    p.tiles_h = (p.rows + TH - 1) / TH;
     p.tiles_n = p.Cout / BN;
     const long long total = (long long)n * p.tiles_w * p.tiles_h * p.tiles_n;
     HSEFR_REQUIRE(total < (1ll << 31) / 16, HSEFR_ERR_UNSUPPORTED, "dwpw_f16split: grid too large");
     p.total = (unsigned)total;
-    auto magic = [](unsigned d) { return d == 1 ? 0u : (unsigned)((0x100000000ull + d - 1) / d); };
     p.m_n = magic(p.tiles_n); p.m_w = magic(p.tiles_w); p.m_h = magic(p.tiles_h);
     HSEFR_REQUIRE(total * (long long)(p.tiles_n > p.tiles_w ? (p.tiles_n > p.tiles_h ? p.tiles_n : p.tiles_h) : (p.tiles_w > p.tiles_h ? p.tiles_w : p.tiles_h)) < (1ll << 32),
                   HSEFR_ERR_UNSUPPORTED, "dwpw_f16split: grid too large for the quotient multipliers");
@@ -963,6 +989,7 @@ int launch_dwpw_f16s(const float* x, const float* wd, const float* dscale, const
     p.a_scale = ldexpf(1.f, a_log2);
     p.reverse = sweep_reverse();
     p.nimg = n;
+    p.rows = oh; p.seam = 0; p.m_seam = 0;
     p.stamps = nullptr;
 #ifdef HSEFR_STEM_STAMPS
     p.stamps = stamp_buffer(s);
@@ -975,10 +1002,16 @@ int launch_dwpw_f16s(const float* x, const float* wd, const float* dscale, const
         auto padded = [&](int tw) { const int th = 128 / tw; return (long long)((ow + tw - 1) / tw * tw) * ((oh + th - 1) / th * th); };
         int tw = padded(16) <= padded(8) ? 16 : 8;
         if (g_tw == 8 || g_tw == 16) tw = g_tw;
+        // ... or 16 x 8 patches over the batch as one map of n * oh rows (strip mode: images are contiguous in NHWC), where that takes fewer
+        // patches: 24 x 24 is 6 patches per image either way above and 4.5 so, 28 x 28 is 8 and 7.  SAME padding only (one zero row serves
+        // both sides of an image seam), seams at multiples of 4 rows and at most one per patch
+        const bool strip = g_tw != 16 && oh % 4 == 0 && oh >= 16 && h == oh && pad_t == 1 && (long long)n * oh * oh < (1ll << 32) &&
+                           (long long)((ow + 7) / 8 * 8) * (((long long)n * oh + 15) / 16 * 16) < n * padded(tw);
+        if (strip) tw = 8;
         int bn = cout % 256 == 0 ? 256 : 128;
         if ((g_bn == 128 || g_bn == 256) && cout % g_bn == 0) bn = g_bn;
-        if (bn == 256) return tw == 16 ? launch_v3<16, 256, 2>(p, n, act, s) : launch_v3<8, 256, 2>(p, n, act, s);
-        return tw == 16 ? launch_v3<16, 128, 3>(p, n, act, s) : launch_v3<8, 128, 3>(p, n, act, s);
+        if (bn == 256) return tw == 16 ? launch_v3<16, 256, 2>(p, n, act, false, s) : launch_v3<8, 256, 2>(p, n, act, strip, s);
+        return tw == 16 ? launch_v3<16, 128, 3>(p, n, act, false, s) : launch_v3<8, 128, 3>(p, n, act, strip, s);
     }
     // stride 2, 128 -> 256 channels: the wave-specialised streaming form with resident weights (32-bit buffer offsets: same size guard)
     if (dwpw_s2_covered(c, cout, stride) && !g_s2_off && in_bytes < (1ll << 32) - 16 && out_bytes < (1ll << 32) - 16)
