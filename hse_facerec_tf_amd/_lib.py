@@ -152,6 +152,23 @@ FOREST_SIGNATURES = {
     "hsefr_forest_predict": (c_int, [_fp] + [c_int] * 6 + [_fp] * 11 + [c_void_p]),
 }
 
+# libhsefr_ragged.so (include/hsefr_ragged.h): one detector pass over frames of different sizes, a fifth library.  HSEFR_RAGGED_LIB selects
+# another build
+RAGGED_LIB_PATH = os.path.join(_HERE, os.environ.get("HSEFR_RAGGED_LIB", "libhsefr_ragged.so"))
+_ragged_lib = None
+_i64 = ctypes.c_int64
+RAGGED_SIGNATURES = {
+    "hsefr_ragged_version": (c_int, []),
+    "hsefr_ragged_last_error_string": (c_char_p, []),
+    "hsefr_ragged_capacity": (c_int, []),
+    "hsefr_ragged_pyramid": (c_int, [_fp, _i64, _fp, c_int, _fp, c_int, _fp, c_int, _fp, _i64, c_int, c_void_p]),
+    "hsefr_ragged_conv2d": (c_int, [_fp, _i64, _fp, _fp, _fp, _fp, _i64, _fp, c_int, _fp, c_int] + [c_int] * 8 + [c_void_p]),
+    "hsefr_ragged_maxpool": (c_int, [_fp, _i64, _fp, _i64, _fp, c_int, _fp, c_int, c_int, c_int, c_int, c_void_p]),
+    "hsefr_ragged_stage1": (c_int, [_fp, _fp, _i64, _fp, c_int, _fp, c_int, ctypes.c_float, _fp, _fp, _fp, _fp, c_void_p]),
+    "hsefr_ragged_crops": (c_int, [_fp, _i64, _fp, c_int, _fp, _fp, _fp, c_int, c_int, c_int, c_void_p]),
+    "hsefr_ragged_stage_finish": (c_int, [c_int, _fp, _fp, c_int, _fp, _fp, _fp, ctypes.c_float, _fp, _fp, _fp, _fp, _fp, c_int, c_void_p]),
+}
+
 
 class HsefrError(RuntimeError):
     pass
@@ -263,6 +280,34 @@ def forest_check(status: int, what: str = "") -> None:
     """check() for a status of libhsefr_forest.so (its own error string)."""
     if status != OK:
         _raise(status, "%s%s (hsefr_forest status %d)" % (what + ": " if what else "", forest_last_error(), status))
+
+
+def ragged_lib() -> ctypes.CDLL:
+    """Load libhsefr_ragged.so once (torch first, as lib() does and for the same reason).  Missing is an error: there is no fallback."""
+    global _ragged_lib
+    if _ragged_lib is None:
+        import torch  # noqa: F401
+        if not os.path.exists(RAGGED_LIB_PATH):
+            raise ImportError("%s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                              "(hipcc --offload-arch=gfx950). There is no CPU fallback." % RAGGED_LIB_PATH)
+        L = ctypes.CDLL(RAGGED_LIB_PATH)
+        for name, (res, args) in RAGGED_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        _ragged_lib = L
+    return _ragged_lib
+
+
+def ragged_last_error() -> str:
+    s = ragged_lib().hsefr_ragged_last_error_string()
+    return s.decode("utf-8", "replace") if s else ""
+
+
+def ragged_check(status: int, what: str = "") -> None:
+    """check() for a status of libhsefr_ragged.so (its own error string)."""
+    if status != OK:
+        _raise(status, "%s%s (hsefr_ragged status %d)" % (what + ": " if what else "", ragged_last_error(), status))
 
 
 def last_error() -> str:

@@ -26,6 +26,12 @@ DEVICE_CROPS_DEFAULT = True
 # 64-photo album not slower (43 against 113 ms) -- so the frames are turned and converted on the device where the detector can read a
 # stack and the device crops are in use
 DEVICE_FRAMES_DEFAULT = True
+# process_images(mixed_sizes=...) of both loops when the caller does not say.  The rule, applied by tools/mtcnn_ragged_time.py in the last
+# line of profiles/mtcnn_ragged_time.txt: True if detect_batch(mixed_sizes=True) is faster than one single-frame call per frame by more than
+# the spread between repetitions at 4, 8 and 16 frames of different sizes per call AND the 64-photo album of 64 sizes is not slower by more
+# than its spread; otherwise False.  Measured on an MI355X: 0.51 / 0.37 / 0.30 against 1.55 / 1.52 / 1.45 ms per frame (spreads 0.12 / 0.004 /
+# 0.013) and the album 86 against 150 ms -- so the frames whose size nothing shares go through mixed-size passes where the detector has them
+MIXED_SIZES_DEFAULT = True
 
 DECISION_TEMPLATES = ((0.875, 0.125), (0.353, 0.647))      # process_photos.py:209: rows = classes (male, female), columns = (p, 1 - p)
 
@@ -190,6 +196,14 @@ def _use_device_frames(img_processing, device_frames: Optional[bool], use_device
     return bool(DEVICE_FRAMES_DEFAULT and use_device_crops and supported is not None and supported())
 
 
+def _use_mixed_sizes(img_processing, mixed_sizes: Optional[bool]) -> bool:
+    """(Unasked, the mixed-size passes need a detector that has them: an MTCNNDetector with its box logic on the device.)"""
+    if mixed_sizes is not None:
+        return bool(mixed_sizes)
+    detector = getattr(img_processing, "detector", None)
+    return bool(MIXED_SIZES_DEFAULT and getattr(detector, "detect_ragged", None) is not None and getattr(detector, "device_boxes", False))
+
+
 def _normalized_on_device(features: Sequence[np.ndarray], device):
     """[n, d] raw features -> their L2-normalised rows as a CUDA tensor (ops.l2_normalize); they stay there for the clustering."""
     from . import ops
@@ -200,17 +214,21 @@ def _normalized_on_device(features: Sequence[np.ndarray], device):
 
 
 def process_video(img_processing, frames: Iterable[np.ndarray], mdate, rotation: int = 0, config: AlbumConfig = AlbumConfig(),
-                  max_frames: int = 32, device_crops: Optional[bool] = None, device_frames: Optional[bool] = None) -> VideoResult:
+                  max_frames: int = 32, device_crops: Optional[bool] = None, device_frames: Optional[bool] = None,
+                  mixed_sizes: Optional[bool] = None) -> VideoResult:
     """process_photos.py:80-156 for the BGR uint8 frames of a video, in grab order.  Whether frame k is processed depends on the faces
     of earlier frames, but only counters divisible by 3 or 5 can ever be: those candidate frames run through
     ``process_images`` in windows of ``max_frames`` (batched detector passes), the rule is then replayed on the host over the face
     counts (video_frame_schedule), and the faces of frames the rule skips are dropped before clustering -- the result is that of the
     sequential loop.  Clusters need config.min_frames faces; no date rule.  ``rotation`` (0, 90 or 270: :102-107) is applied by
-    process_images, on the device with ``device_frames`` (None: DEVICE_FRAMES_DEFAULT where the configuration allows it)."""
+    process_images, on the device with ``device_frames`` (None: DEVICE_FRAMES_DEFAULT where the configuration allows it).
+    ``mixed_sizes`` (None: MIXED_SIZES_DEFAULT where the detector has ragged passes): frames whose size no other frame of their
+    call shares are detected together (process_images(mixed_sizes=True)); the keyword is passed on only when it is in use."""
     rotation = preprocess_device.check_rotation(rotation)
     video_year = _fractional_year(mdate)
     use_device = _use_device_crops(img_processing, device_crops)
     use_frames = _use_device_frames(img_processing, device_frames, use_device)
+    mixed = dict(mixed_sizes=True) if _use_mixed_sizes(img_processing, mixed_sizes) else {}
     per_frame = {}                     # candidate frame index -> (ages, genders, features, crops)
     n_frames = 0
 
@@ -218,7 +236,7 @@ def process_video(img_processing, frames: Iterable[np.ndarray], mdate, rotation:
         if not window:
             return
         res, crops = img_processing.process_images([f for _, f in window], max_frames=max_frames, device_crops=use_device, return_crops=True,
-                                                   rotation=rotation, device_frames=use_frames)
+                                                   rotation=rotation, device_frames=use_frames, **mixed)
         for (k, _), (_, _, ages, genders, feats), c in zip(window, res, crops):
             per_frame[k] = (ages, genders, feats, c)
 
@@ -263,7 +281,7 @@ def _as_bgr(photo) -> np.ndarray:
 
 
 def process_album(img_processing, photos, mdates, videos=(), config: AlbumConfig = AlbumConfig(), max_frames: int = 32,
-                  device_crops: Optional[bool] = None, device_frames: Optional[bool] = None) -> AlbumResult:
+                  device_crops: Optional[bool] = None, device_frames: Optional[bool] = None, mixed_sizes: Optional[bool] = None) -> AlbumResult:
     """process_photos.py:219-358.  ``photos``: BGR uint8 arrays or paths, ``mdates`` their dates; ``videos``: (frames, mdate) or
     (frames, mdate, rotation) per video, frames as process_video takes them.  Pass 1 runs every photo, pass 2 the quarter turns
     clockwise of the photos without a face, pass 3 the quarter turns counter-clockwise of those still without one (:241-247) -- each pass
@@ -272,7 +290,10 @@ def process_album(img_processing, photos, mdates, videos=(), config: AlbumConfig
     features (:284-297).  Then perform_clustering with config.min_photos and the date rule, the summaries, and the private / public
     split (:345-346) over the files (photos, then videos).  The quarter turns of passes 2 and 3 and of a turned video are made by
     process_images(rotation=...): on the device, in the launch that converts the frames to RGB, with ``device_frames`` (None:
-    DEVICE_FRAMES_DEFAULT where the configuration allows it)."""
+    DEVICE_FRAMES_DEFAULT where the configuration allows it).  ``mixed_sizes`` (None: MIXED_SIZES_DEFAULT where the detector has ragged
+    passes): the photos of a call whose size no other shares -- most of a real album -- are detected together in mixed-size passes
+    (process_images(mixed_sizes=True)) instead of one by one; it goes to the videos too, and the keyword is passed on only when it is
+    in use, so an ``img_processing`` written without it keeps working."""
     photos = list(photos)
     mdates = list(mdates)
     videos = list(videos)
@@ -282,6 +303,7 @@ def process_album(img_processing, photos, mdates, videos=(), config: AlbumConfig
         preprocess_device.check_rotation(video[2] if len(video) > 2 else 0)
     use_device = _use_device_crops(img_processing, device_crops)
     use_frames = _use_device_frames(img_processing, device_frames, use_device)
+    mixed = dict(mixed_sizes=True) if _use_mixed_sizes(img_processing, mixed_sizes) else {}
     n_photos = len(photos)
     found = [None] * n_photos          # per photo: (ages, genders, features, crops, has_center_face)
     call = 4 * max_frames              # frames per process_images call: bounds the frame stacks held on the device at one time
@@ -291,7 +313,7 @@ def process_album(img_processing, photos, mdates, videos=(), config: AlbumConfig
             part = todo[a:a + call]
             draws = [_as_bgr(photos[i]) for i in part]
             res, crops = img_processing.process_images(draws, max_frames=max_frames, device_crops=use_device, return_crops=True,
-                                                       rotation=rotation, device_frames=use_frames)
+                                                       rotation=rotation, device_frames=use_frames, **mixed)
             for i, d, (bboxes, _, ages, genders, feats), c in zip(part, draws, res, crops):
                 found[i] = (ages, genders, feats, c, has_center_face(bboxes, d.shape[0] if rotation else d.shape[1], config))   # the turned width
 
@@ -313,7 +335,8 @@ def process_album(img_processing, photos, mdates, videos=(), config: AlbumConfig
         born.extend(photo_year - (age - 0.5) for age in ages)
     for j, video in enumerate(videos):
         frames, vdate = video[0], video[1]
-        v = process_video(img_processing, frames, vdate, video[2] if len(video) > 2 else 0, config, max_frames, use_device, use_frames)
+        v = process_video(img_processing, frames, vdate, video[2] if len(video) > 2 else 0, config, max_frames, use_device, use_frames,
+                          bool(mixed))
         if v.video_has_faces:
             private.append(n_photos + j)
         images.extend(v.cluster_images)

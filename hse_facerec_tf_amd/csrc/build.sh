@@ -2,7 +2,8 @@
 # Builds libhsefr.so for gfx950 in-tree (hipcc cross-compiles without a GPU), and right after it libhsefr_album.so (include/hsefr_album.h:
 # the album organiser's device code, a library of its own because libhsefr.so is held below 4 MB by its tests) and libhsefr_frames.so
 # (include/hsefr_frames.h: the frame stack's channel swap and quarter turns, a library of its own for the same reason) and
-# libhsefr_forest.so (include/hsefr_forest.h: the random forest classifier, a fourth library for the same reason).
+# libhsefr_forest.so (include/hsefr_forest.h: the random forest classifier, a fourth library for the same reason) and
+# libhsefr_ragged.so (include/hsefr_ragged.h: the detector pass over frames of different sizes, a fifth library for the same reason).
 #   HSEFR_DEV=1 build.sh   builds libhsefr_dev.so instead: the same sources with -DHSEFR_DEV (tuning knobs as run-time
 #                          variables, hsefr_debug_*, the calibration kernels of devtools.hip) -- for tools/kbench.py only.
 set -euo pipefail
@@ -29,6 +30,11 @@ FRAMES_FLAGS="$FLAGS $DEVICE_STRIP"
 # -ffp-contract=off: a candidate's score and a threshold are the restatement's fp64 operations one by one (tests/random_forest_ref.py)
 FOREST_SRCS="forest.hip"
 FOREST_FLAGS="$FLAGS $DEVICE_STRIP -ffp-contract=off"
+# libhsefr_ragged.so (include/hsefr_ragged.h: one detector pass over frames of different sizes): a fifth library, built as the fourth.
+# The flags are libhsefr.so's own: mtcnn_ragged.hip compiles the one-frame bodies that library compiles (mtcnn_post_frame.h,
+# area_resize_px.h) and must give their bits
+RAGGED_SRCS="mtcnn_ragged.hip"
+RAGGED_FLAGS="$FLAGS $DEVICE_STRIP"
 LINT=1
 HOST_STRIP=0
 HOST_SIZE_FLAGS=""
@@ -150,4 +156,23 @@ if [ "$LINT" = "1" ]; then
   /opt/rocm/lib/llvm/bin/llvm-strip --strip-all -w --keep-symbol='_ZN*_kernel*' --keep-symbol='!*__device_stub__*' "$FOREST_OUT"
   python3 ../../tools/isa_lint.py "$FOREST_OUT"
   echo "built $(realpath $FOREST_OUT)"
+  # the fifth library: built, stripped and linted as the fourth; stale against the headers it shares with libhsefr.so too
+  RAGGED_OUT=../libhsefr_ragged.so
+  RAGGED_OBJS=""
+  for s in $RAGGED_SRCS; do
+    o="$BUILD/${s%.hip}.o"
+    stale=0
+    for dep in "$s" mtcnn_post_frame.h area_resize_px.h ../../include/hsefr_ragged.h build.sh; do
+      if [ ! -f "$o" ] || [ "$dep" -nt "$o" ]; then stale=1; fi
+    done
+    if [ "$stale" = 1 ]; then
+      rm -f "$o"
+      hipcc $RAGGED_FLAGS -Xarch_host -Os ${HSEFR_EXTRA_FLAGS:-} -c "$s" -o "$o"
+    fi
+    RAGGED_OBJS="$RAGGED_OBJS $o"
+  done
+  hipcc $LINK -shared -fPIC -o "$RAGGED_OUT" $RAGGED_OBJS
+  /opt/rocm/lib/llvm/bin/llvm-strip --strip-all -w --keep-symbol='_ZN*_kernel*' --keep-symbol='!*__device_stub__*' "$RAGGED_OUT"
+  python3 ../../tools/isa_lint.py "$RAGGED_OUT"
+  echo "built $(realpath $RAGGED_OUT)"
 fi

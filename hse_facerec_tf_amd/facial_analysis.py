@@ -136,13 +136,19 @@ class FacialImageProcessing:
                                       "(bounding_boxes, points); the MTCNN cascade is the step before this path")
         return self.detector(img)
 
-    def detect_faces_batch(self, imgs, max_frames: int = 32):
+    def detect_faces_batch(self, imgs, max_frames: int = 32, mixed_sizes: bool = False):
         """detect_faces for a list of RGB frames -> [(bounding_boxes, points)] in list order: one call of the detector's
-        ``detect_batch`` where it has one (MTCNNDetector: same-size frames share their launches), a loop over detect_faces otherwise."""
+        ``detect_batch`` where it has one (MTCNNDetector: same-size frames share their launches, and with ``mixed_sizes`` the others
+        share mixed-size passes), a loop over detect_faces otherwise."""
         batch = getattr(self.detector, "detect_batch", None)
         if batch is None:
             return [self.detect_faces(img) for img in imgs]       # (no detector at all: raises as detect_faces does)
-        return batch(imgs, max_frames=max_frames)
+        return batch(imgs, max_frames=max_frames, **self._mixed_kw(mixed_sizes))
+
+    @staticmethod
+    def _mixed_kw(mixed_sizes: bool) -> dict:
+        """detect_batch's keyword, passed only when it is in use (a detector written without it keeps working)."""
+        return dict(mixed_sizes=True) if mixed_sizes else {}
 
     # ---- facial_analysis.py:225-294 -----------------------------------------------------------------
     @staticmethod
@@ -253,14 +259,16 @@ class FacialImageProcessing:
         return bool(self.device_preprocess and self.sess.accepts_u8 and getattr(self.detector, "detect_stack", None) is not None
                     and getattr(self.detector, "device_boxes", False))
 
-    def _detect_device_frames(self, draws, rotation: int, max_frames: int):
+    def _detect_device_frames(self, draws, rotation: int, max_frames: int, mixed_sizes: bool = False):
         """process_images' detection with device_frames: the frames grouped by their TURNED size (mtcnn.plan_passes); a group of two or
         more is stacked as decoded (BGR, unrotated), uploaded, turned and converted by ONE launch (preprocess_device.prepare_frames; in
         place for rotation 0, and a quarter turn's raw stack is dropped as soon as the prepared one is written) and detected from that
         stack (MTCNNDetector.detect_stack).  -> (imgs, shapes, detections, sources): ``sources`` as detect_batch(return_stacks=True)
         gives them; ``imgs[i]`` the frame's turned RGB host array where it took the single-frame call -- a frame alone in its size group
         (converted on the host, as without device_frames) and a frame whose candidate list overflowed (read back from its row of the
-        prepared stack) -- and None for the others, whose pixels the host never touches; ``shapes[i]`` the turned (h, w)."""
+        prepared stack) -- and None for the others, whose pixels the host never touches; ``shapes[i]`` the turned (h, w).
+        ``mixed_sizes``: the frames alone in their size group are converted on the host as before and then detected TOGETHER, in the
+        detector's mixed-size passes (detect_batch(mixed_sizes=True)), instead of one by one."""
         from . import preprocess_device
         from .mtcnn import empty_detection, plan_passes
         torch = _lib.require_gpu()
@@ -276,13 +284,18 @@ class FacialImageProcessing:
         def alone(i, img):                         # the single-frame call, through the path a lone frame takes without device_frames
             imgs[i] = img
             detections[i] = self.detector.detect_batch([img], max_frames=max_frames)[0]
+        lone: list = []                            # mixed_sizes: the frames alone in their size group, in list order
         for (h, w), idx in plan_passes(shapes, max_frames):
             if not self.detector.pyramid_scales(h, w):                     # smaller than minsize: no level, no launch, no upload
                 for i in idx:
                     detections[i] = empty_detection()
                 continue
             if len(idx) == 1:
-                alone(idx[0], self._bgr_to_rgb(preprocess_device.turn_frame(raw[idx[0]], rotation)))
+                if mixed_sizes:
+                    lone.append(idx[0])
+                    imgs[idx[0]] = self._bgr_to_rgb(preprocess_device.turn_frame(raw[idx[0]], rotation))
+                else:
+                    alone(idx[0], self._bgr_to_rgb(preprocess_device.turn_frame(raw[idx[0]], rotation)))
                 continue
             stack = torch.from_numpy(np.stack([raw[i] for i in idx])).to(self.detector.device)      # one upload per pass, as decoded
             if rotation == 0:
@@ -294,10 +307,13 @@ class FacialImageProcessing:
                     detections[i], sources[i] = res, (stack, row)
                 else:
                     alone(i, stack[row].cpu().numpy())
+        if lone:
+            for i, res in zip(lone, self.detector.detect_batch([imgs[i] for i in lone], max_frames=max_frames, mixed_sizes=True)):
+                detections[i] = res
         return imgs, shapes, detections, sources
 
     def process_images(self, draws, max_frames: int = 32, device_crops: bool = False, return_crops: bool = False, rotation: int = 0,
-                       device_frames: bool = False):
+                       device_frames: bool = False, mixed_sizes: bool = False):
         """process_image for a list of BGR uint8 frames (the photos of an album, the frames of a video: process_photos.py:92-118,
         :238-247) -> a list of process_image's 5-tuples, in list order.  One detect_faces_batch call over all frames, then ONE
         age_gender_batch call over the crops of all frames on the bulk plan (it chunks by max_batch itself), split back per frame.
@@ -314,7 +330,12 @@ class FacialImageProcessing:
         device_frames: the frames are uploaded as decoded and turned and converted to RGB on the device, a pass in one launch
         (_detect_device_frames), instead of copied twice on the host; the detector and the crop kernel read that stack.  Implies
         device_crops and has its rule: ValueError without device_preprocess=True, an engine that accepts bytes and a detector with
-        ``detect_stack``.  Results are those of device_frames=False bit for bit."""
+        ``detect_stack``.  Results are those of device_frames=False bit for bit.
+        mixed_sizes: the frames whose (turned) size no other frame of the call shares -- today one single-frame detector call each --
+        are detected together in mixed-size passes (MTCNNDetector.detect_batch(mixed_sizes=True)); with device_frames they are converted
+        on the host as before, and their faces are cut on the host, as for any frame without a source stack.  Same-size groups keep
+        the device frames and the device crops.  Results are those of mixed_sizes=False bit for bit.  Needs a detector whose
+        detect_batch takes the keyword."""
         from . import preprocess_device
         from .mtcnn import split_by_counts
         rotation = preprocess_device.check_rotation(rotation)
@@ -330,12 +351,12 @@ class FacialImageProcessing:
             shapes = [img.shape[:2] for img in imgs]
         t = time.time()
         if device_frames:
-            imgs, shapes, detections, sources = self._detect_device_frames(draws, rotation, max_frames)
+            imgs, shapes, detections, sources = self._detect_device_frames(draws, rotation, max_frames, mixed_sizes)
         elif device_crops and getattr(self.detector, "detect_batch", None) is not None:
             # (a detector whose detect_batch cannot hand its stacks back raises here: device_crops was asked for)
-            detections, sources = self.detector.detect_batch(imgs, max_frames=max_frames, return_stacks=True)
+            detections, sources = self.detector.detect_batch(imgs, max_frames=max_frames, return_stacks=True, **self._mixed_kw(mixed_sizes))
         else:                                      # no batched detector: every frame takes the single-frame call and the host crops
-            detections, sources = self.detect_faces_batch(imgs, max_frames=max_frames), [None] * len(imgs)
+            detections, sources = self.detect_faces_batch(imgs, max_frames=max_frames, mixed_sizes=mixed_sizes), [None] * len(imgs)
         if self.print_stat:
             print('detection elapsed', time.time() - t)
         all_bboxes, crops = [], []

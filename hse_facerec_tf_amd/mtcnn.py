@@ -17,7 +17,9 @@ from ONE upload of the frame (csrc/area_resize.hip: hsefr_mtcnn_pyramid_level / 
 reference's numbers including its conventions: boxes are 1-based inclusive, ``np.fix`` truncation.
 ``device_resize=False`` keeps the round-1 path (host resizes through preprocess.resize_area).
 ``MTCNNDetector.detect_batch`` runs same-size frames through that launch sequence together (the ``*_batch`` entry points of
-include/hsefr.h), each frame's result bit for bit its single-frame result.
+include/hsefr.h), each frame's result bit for bit its single-frame result.  ``MTCNNDetector.detect_ragged`` runs frames of ANY sizes
+through one pass (include/hsefr_ragged.h, mtcnn_ragged.py: one list of (frame, level) items, one launch per P-Net layer), with the same
+bits; ``detect_batch(mixed_sizes=True)`` sends the frames that are alone in their size group through such passes.
 """
 from __future__ import annotations
 
@@ -28,6 +30,7 @@ import numpy as np
 
 from . import _lib, ops, preprocess
 from .graphdef import Graph, GraphNode, read_graph
+from .mtcnn_ragged import DevicePlan, RaggedMaps, RaggedPlan, frame_workspace_bytes, ragged_plan  # noqa: F401  (ragged_plan: part of this module's face)
 
 MTCNN_PB = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "models", "mtcnn.pb")
 
@@ -150,7 +153,9 @@ class _DeviceNet:
         src, wnode = self._ins(lin)
         if lin.op == "Conv2D":
             stride, padding, wdev = lin.attr_ints("strides")[1], lin.attr_s("padding"), self._dev(wnode)
-            return (lambda xin: ops.conv2d_direct(xin, wdev, bias, alpha, stride, padding)), [src]
+            # (the maps of a ragged pass run the same step with the same weight tensors: one launch over all their items)
+            return (lambda xin: xin.conv2d(wdev, bias, alpha, stride, padding) if isinstance(xin, RaggedMaps)
+                    else ops.conv2d_direct(xin, wdev, bias, alpha, stride, padding)), [src]
         if lin.op == "MatMul":
             w = self._const_np(wnode)
             cout = int(w.shape[1])
@@ -171,12 +176,13 @@ class _DeviceNet:
             return self._compile_linear(pr[0], pr[1])
         sm = self._match_softmax(node)
         if sm is not None:
-            return (lambda x: ops.softmax(x.reshape(-1, x.shape[-1]).contiguous()).reshape(x.shape)), [sm]
+            return (lambda x: x.softmax() if isinstance(x, RaggedMaps)
+                    else ops.softmax(x.reshape(-1, x.shape[-1]).contiguous()).reshape(x.shape)), [sm]
         if op in ("BiasAdd", "Conv2D", "MatMul"):
             return self._compile_linear(node, None)
         if op == "MaxPool":
             k, st, padding = node.attr_ints("ksize")[1], node.attr_ints("strides")[1], node.attr_s("padding")
-            return (lambda x: ops.maxpool(x, k, st, padding)), [self._ins(node)[0]]
+            return (lambda x: x.maxpool(k, st, padding) if isinstance(x, RaggedMaps) else ops.maxpool(x, k, st, padding)), [self._ins(node)[0]]
         if op == "Reshape":
             shape = [int(d) for d in self._const_np(self._ins(node)[1]).reshape(-1)]
             return (lambda x: x.reshape(shape).contiguous()), [self._ins(node)[0]]
@@ -345,6 +351,45 @@ def plan_passes(shapes, max_frames: int) -> List[Tuple[Tuple[int, int], List[int
     return [(hw, idx[a:a + max_frames]) for hw, idx in groups.items() for a in range(0, len(idx), max_frames)]
 
 
+def plan_mixed_passes(shapes, max_frames: int, max_bytes: int = 4 << 30, minsize: int = 32,
+                      factor: float = 0.709) -> List[Tuple[Optional[Tuple[int, int]], List[int]]]:
+    """The passes of ``detect_batch(mixed_sizes=True)``: the same-size groups of two or more frames stay the passes plan_passes gives,
+    -> ((h, w), [indices]); the frames left alone in their group are gathered, in list order, into ragged passes -> (None, [indices])
+    of at most ``max_frames`` frames whose planned workspace (mtcnn_ragged.frame_workspace_bytes, summed; ``minsize`` and ``factor``
+    are the detector's) is at most ``max_bytes`` -- a pass closes before the frame that would exceed either limit, and a frame that
+    exceeds ``max_bytes`` alone stands alone.  A ragged pass of ONE frame is the single-frame call: ((h, w), [index]), what
+    plan_passes gives.  So is a lone frame without a pyramid level, which needs no launch and joins no pass.  Same-size passes come
+    first, then the ragged passes, then the single frames, each in list order; every index appears exactly once."""
+    max_bytes = int(max_bytes)
+    shapes = [(int(hw[0]), int(hw[1])) for hw in shapes]
+    passes: List[Tuple[Optional[Tuple[int, int]], List[int]]] = []
+    lone: List[int] = []
+    for hw, idx in plan_passes(shapes, max_frames):
+        if len(idx) > 1:
+            passes.append((hw, idx))
+        else:
+            lone.append(idx[0])                # (a group's last pass may be a single frame too: it is alone in ITS pass)
+    lone.sort()
+    singles: List[int] = []                    # frames that take the single-frame call
+    ragged: List[List[int]] = []
+    used = 0
+    for i in lone:
+        h, w = shapes[i]
+        need = frame_workspace_bytes(h, w, minsize, factor)
+        if need == h * w * 3:                  # no pyramid level: no launch, nothing to share
+            singles.append(i)
+            continue
+        if not ragged or len(ragged[-1]) >= int(max_frames) or used + need > max_bytes:
+            ragged.append([])
+            used = 0
+        ragged[-1].append(i)
+        used += need
+    singles += [g[0] for g in ragged if len(g) == 1]
+    passes += [(None, g) for g in ragged if len(g) > 1]
+    passes += [(shapes[i], [i]) for i in sorted(singles)]
+    return passes
+
+
 def split_by_counts(items, counts) -> List[list]:
     """A flat list that holds ``counts[0]`` items of frame 0, then ``counts[1]`` of frame 1, ... -> one list per frame."""
     items = list(items)
@@ -381,6 +426,9 @@ class MTCNNDetector:
         if self.device_boxes and not device_resize:
             raise ValueError("device_boxes needs device_resize (the crops are cut from the frame on the device)")
         self.host_fallbacks = 0            # frames redone on the host because a candidate list overflowed
+        self.ragged_passes = 0             # mixed-size passes detect_batch(mixed_sizes=True) ran, and the frames in them
+        self.ragged_frames = 0
+        self._ragged_plans: Dict[tuple, DevicePlan] = {}      # (shapes, minsize) -> the plan and its tables on the device
         self._work = None                  # cap-sized work tensors of the device box logic, allocated once (_detect_device)
         self.device = _lib.cuda_device(device)
         self.net = _DeviceNet(read_graph(mtcnn_pb or MTCNN_PB), self.device)
@@ -583,7 +631,7 @@ class MTCNNDetector:
             st = _lib.current_stream_ptr()
             wk = self._batch_work_tensors(cap, n_frames)
             counters = torch.zeros((n_frames, 8), dtype=torch.int32, device=dev)
-            found, (boxes1, boxes2, boxes3), tab, points3 = wk.bfound, wk.bboxes, wk.btab, wk.bpoints
+            found, boxes1, tab = wk.bfound, wk.bboxes[0], wk.btab
             thr = [float(np.float32(t)) for t in self.THRESHOLDS]
             for scale in self.pyramid_scales(h, w):
                 hs, ws = int(np.ceil(h * scale)), int(np.ceil(w * scale))
@@ -597,44 +645,56 @@ class MTCNNDetector:
                            "hsefr_mtcnn_stage1_level_batch")
             _lib.check(L.hsefr_mtcnn_stage1_finish_batch(found.data_ptr(), counters.data_ptr(), boxes1.data_ptr(), tab.data_ptr(), n_frames, w, h, st),
                        "hsefr_mtcnn_stage1_finish_batch")
-            c = counters.cpu().numpy()                                     # read-back 1
-            over = c[:, 4] != 0                                            # (only a pyramid level can overflow: later lists are no longer)
-            for b in np.nonzero(over)[0]:
-                results[int(b)] = None
+            crops_of = lambda tab, d_off, total, size, out: _lib.check(      # noqa: E731
+                L.hsefr_mtcnn_crops_batch(stack.data_ptr(), tab.data_ptr(), d_off.data_ptr(), out.data_ptr(), n_frames, h, w, total, size, st),
+                "hsefr_mtcnn_crops_batch")
+            finish = lambda stage, b_in, d_off, total, prob, reg, pts, t, b_out, tab, points: _lib.check(      # noqa: E731
+                L.hsefr_mtcnn_stage_finish_batch(stage, b_in.data_ptr(), d_off.data_ptr(), total, prob.data_ptr(), reg.data_ptr(),
+                                                 None if pts is None else pts.data_ptr(), t, b_out.data_ptr(), None if tab is None else tab.data_ptr(),
+                                                 None if points is None else points.data_ptr(), counters.data_ptr(), n_frames, w, h, st),
+                "hsefr_mtcnn_stage_finish_batch")
+            return self._finish_pass(n_frames, counters, wk, results, crops_of, finish)
 
-            def offsets_of(counts):                                        # host scan of the counts just read; a 4(B+1)-byte upload
-                counts = np.where(over, 0, counts).astype(np.int64)
-                off = np.concatenate([[0], np.cumsum(counts)])
-                return int(off[-1]), torch.from_numpy(off.astype(np.int32)).to(dev)
+    def _finish_pass(self, n_frames: int, counters, wk, results, crops_of, finish) -> List[Optional[Tuple[np.ndarray, np.ndarray]]]:
+        """A pass behind its stage 1 (run under on_device): the three read-backs, R-Net and O-Net on the concatenated crop lists, the
+        results per frame.  ``crops_of(tab, d_off, total, size, out)`` cuts the crops of all frames and ``finish(stage, boxes_in, d_off,
+        total, prob, reg, pts, thr, boxes_out, tab, points)`` runs stage 2 / 3 of all frames: the same-size pass and the ragged pass
+        differ only in where those two read a frame's place and size."""
+        torch, dev = self._torch, self.device
+        (boxes1, boxes2, boxes3), tab, points3 = wk.bboxes, wk.btab, wk.bpoints
+        thr = [float(np.float32(t)) for t in self.THRESHOLDS]
+        c = counters.cpu().numpy()                                     # read-back 1
+        over = c[:, 4] != 0                                            # (only a pyramid level can overflow: later lists are no longer)
+        for b in np.nonzero(over)[0]:
+            results[int(b)] = None
 
-            total, d_off = offsets_of(c[:, 1])
-            if total == 0:
-                return results
-            crops = torch.empty((total, 24, 24, 3), dtype=torch.float32, device=dev)
-            _lib.check(L.hsefr_mtcnn_crops_batch(stack.data_ptr(), tab.data_ptr(), d_off.data_ptr(), crops.data_ptr(), n_frames, h, w, total, 24, st),
-                       "hsefr_mtcnn_crops_batch")
-            reg_t, prob_t = self.rnet(crops)
-            reg_t, prob_t = reg_t.contiguous(), prob_t.contiguous()
-            _lib.check(L.hsefr_mtcnn_stage_finish_batch(2, boxes1.data_ptr(), d_off.data_ptr(), total, prob_t.data_ptr(), reg_t.data_ptr(), None, thr[1],
-                                                        boxes2.data_ptr(), tab.data_ptr(), None, counters.data_ptr(), n_frames, w, h, st),
-                       "hsefr_mtcnn_stage_finish_batch")
-            c = counters.cpu().numpy()                                     # read-back 2
-            n2 = np.where(over, 0, c[:, 2])
-            total, d_off = offsets_of(c[:, 2])
-            if total == 0:
-                return results
-            crops = torch.empty((total, 48, 48, 3), dtype=torch.float32, device=dev)
-            _lib.check(L.hsefr_mtcnn_crops_batch(stack.data_ptr(), tab.data_ptr(), d_off.data_ptr(), crops.data_ptr(), n_frames, h, w, total, 48, st),
-                       "hsefr_mtcnn_crops_batch")
-            reg_t, pts_t, prob_t = self.onet(crops)
-            reg_t, pts_t, prob_t = reg_t.contiguous(), pts_t.contiguous(), prob_t.contiguous()
-            _lib.check(L.hsefr_mtcnn_stage_finish_batch(3, boxes2.data_ptr(), d_off.data_ptr(), total, prob_t.data_ptr(), reg_t.data_ptr(),
-                                                        pts_t.data_ptr(), thr[2], boxes3.data_ptr(), None, points3.data_ptr(), counters.data_ptr(),
-                                                        n_frames, w, h, st), "hsefr_mtcnn_stage_finish_batch")
-            # read-back 3: the counts and the first max(n2) rows of every frame's lists (stage 3 keeps at most its n2 inputs) as one copy
-            m = int(n2.max())
-            packed = torch.cat([counters.view(torch.uint8).reshape(-1), boxes3[:n_frames, :m].contiguous().view(torch.uint8).reshape(-1),
-                                points3[:n_frames, :m].contiguous().view(torch.uint8).reshape(-1)]).cpu().numpy()
+        def offsets_of(counts):                                        # host scan of the counts just read; a 4(B+1)-byte upload
+            counts = np.where(over, 0, counts).astype(np.int64)
+            off = np.concatenate([[0], np.cumsum(counts)])
+            return int(off[-1]), torch.from_numpy(off.astype(np.int32)).to(dev)
+
+        total, d_off = offsets_of(c[:, 1])
+        if total == 0:
+            return results
+        crops = torch.empty((total, 24, 24, 3), dtype=torch.float32, device=dev)
+        crops_of(tab, d_off, total, 24, crops)
+        reg_t, prob_t = self.rnet(crops)
+        reg_t, prob_t = reg_t.contiguous(), prob_t.contiguous()
+        finish(2, boxes1, d_off, total, prob_t, reg_t, None, thr[1], boxes2, tab, None)
+        c = counters.cpu().numpy()                                     # read-back 2
+        n2 = np.where(over, 0, c[:, 2])
+        total, d_off = offsets_of(c[:, 2])
+        if total == 0:
+            return results
+        crops = torch.empty((total, 48, 48, 3), dtype=torch.float32, device=dev)
+        crops_of(tab, d_off, total, 48, crops)
+        reg_t, pts_t, prob_t = self.onet(crops)
+        reg_t, pts_t, prob_t = reg_t.contiguous(), pts_t.contiguous(), prob_t.contiguous()
+        finish(3, boxes2, d_off, total, prob_t, reg_t, pts_t, thr[2], boxes3, None, points3)
+        # read-back 3: the counts and the first max(n2) rows of every frame's lists (stage 3 keeps at most its n2 inputs) as one copy
+        m = int(n2.max())
+        packed = torch.cat([counters.view(torch.uint8).reshape(-1), boxes3[:n_frames, :m].contiguous().view(torch.uint8).reshape(-1),
+                            points3[:n_frames, :m].contiguous().view(torch.uint8).reshape(-1)]).cpu().numpy()
         at_boxes = n_frames * 32
         at_points = at_boxes + n_frames * m * 40
         c = np.frombuffer(packed, np.int32, n_frames * 8, 0).reshape(n_frames, 8)
@@ -645,6 +705,72 @@ class MTCNNDetector:
             if results[b] is not None and n3 > 0:
                 results[b] = (boxes[b, :n3].copy(), np.ascontiguousarray(points[b, :n3].T))
         return results
+
+    # ---- frames of different sizes in one pass (csrc/mtcnn_ragged.hip, mtcnn_ragged.py) ----------------------------------------------
+    RAGGED_PLANS_KEPT = 32             # plans (and their tables on the device) a detector keeps, most recently used last
+
+    def _ragged_device_plan(self, shapes: tuple) -> DevicePlan:
+        """The plan of a ragged pass over frames of these shapes with its tables on the device: built and uploaded once per
+        (shapes, minsize), then reused (an album's retry passes, a video's frames)."""
+        key = (shapes, self.minsize)
+        dplan = self._ragged_plans.pop(key, None)
+        if dplan is None:
+            dplan = DevicePlan(ragged_plan(shapes, self.minsize, self.FACTOR), self.device)
+            while len(self._ragged_plans) >= self.RAGGED_PLANS_KEPT:
+                self._ragged_plans.pop(next(iter(self._ragged_plans)))
+        self._ragged_plans[key] = dplan
+        return dplan
+
+    def detect_ragged(self, frames) -> List[Optional[Tuple[np.ndarray, np.ndarray]]]:
+        """ONE pass over frames of any sizes (uint8 RGB [H, W, 3] each): per frame (boxes [n,5] float64, points [10,n] float32), bit
+        for bit what ``self(frame)`` returns (a frame without faces gives shapes (0, 5) and (10, 0)), or None where that frame's
+        candidate list overflowed (the caller redoes that frame alone).  Uploads: the frames' bytes packed back to back, the plan's
+        tables (once per list of shapes), the two small offset tables of the crop lists; launches: one per P-Net layer over ALL pyramid
+        levels of ALL frames (the same-size pass makes one per level), R-Net and O-Net on the concatenated crop lists; the three
+        read-backs of the same-size pass.  Needs ``device_boxes``.
+
+        Bit identity with the single-frame call: the pyramid, the crops and the box logic run the one-frame bodies the single-frame
+        entries run (csrc/area_resize_px.h, csrc/mtcnn_post_frame.h), with a frame's place and size read from the plan's tables; P-Net
+        runs through the program _DeviceNet compiled, with the same weight tensors, each output's FMA chain in conv2d_direct's order
+        (tests/test_mtcnn_ragged_gpu.py checks every step and the whole)."""
+        if not self.device_boxes:
+            raise ValueError("detect_ragged needs a detector with device_boxes")
+        imgs = [self._check_frame(f) for f in frames]
+        if not imgs:
+            return []
+        torch, L, R = self._torch, _lib.lib(), _lib.ragged_lib()
+        dplan = self._ragged_device_plan(tuple((int(f.shape[0]), int(f.shape[1])) for f in imgs))
+        plan = dplan.plan
+        n_frames, dev = plan.n_frames, self.device
+        results: List[Optional[Tuple[np.ndarray, np.ndarray]]] = [empty_detection() for _ in range(n_frames)]
+        if plan.n_items == 0:                                              # no frame has a pyramid level: no upload, no launch
+            return results
+        cap = int(L.hsefr_mtcnn_post_capacity())
+        if int(R.hsefr_ragged_capacity()) != cap:
+            raise RuntimeError("libhsefr.so and libhsefr_ragged.so were built from different sources (list capacity %d / %d)"
+                               % (cap, int(R.hsefr_ragged_capacity())))
+        packed = torch.from_numpy(np.concatenate([np.ascontiguousarray(f).reshape(-1) for f in imgs])).to(dev)      # one upload per pass
+        with _lib.on_device(packed):
+            st = _lib.current_stream_ptr()
+            wk = self._batch_work_tensors(cap, n_frames)
+            counters = torch.zeros((n_frames, 8), dtype=torch.int32, device=dev)
+            levels = torch.empty(plan.pixels[0] * 3, dtype=torch.float32, device=dev)
+            _lib.ragged_check(R.hsefr_ragged_pyramid(packed.data_ptr(), plan.frames_bytes, dplan.frames, n_frames, dplan.levels, plan.n_items,
+                                                     dplan.level_block_item, len(plan.level_block_item), levels.data_ptr(), plan.pixels[0] * 3,
+                                                     plan.level_lds, st), "hsefr_ragged_pyramid")
+            reg_m, prob_m = self.pnet(RaggedMaps(dplan, 0, 3, levels))
+            _lib.ragged_check(R.hsefr_ragged_stage1(prob_m.data.data_ptr(), reg_m.data.data_ptr(), plan.pixels[-1], dplan.frames, n_frames, dplan.cells,
+                                                    plan.n_items, float(np.float32(self.THRESHOLDS[0])), wk.bfound.data_ptr(), counters.data_ptr(),
+                                                    wk.bboxes[0].data_ptr(), wk.btab.data_ptr(), st), "hsefr_ragged_stage1")
+            crops_of = lambda tab, d_off, total, size, out: _lib.ragged_check(      # noqa: E731
+                R.hsefr_ragged_crops(packed.data_ptr(), plan.frames_bytes, dplan.frames, n_frames, tab.data_ptr(), d_off.data_ptr(), out.data_ptr(),
+                                     cap, total, size, st), "hsefr_ragged_crops")
+            finish = lambda stage, b_in, d_off, total, prob, reg, pts, t, b_out, tab, points: _lib.ragged_check(      # noqa: E731
+                R.hsefr_ragged_stage_finish(stage, b_in.data_ptr(), d_off.data_ptr(), total, prob.data_ptr(), reg.data_ptr(),
+                                            None if pts is None else pts.data_ptr(), t, b_out.data_ptr(), None if tab is None else tab.data_ptr(),
+                                            None if points is None else points.data_ptr(), counters.data_ptr(), dplan.frames, n_frames, st),
+                "hsefr_ragged_stage_finish")
+            return self._finish_pass(n_frames, counters, wk, results, crops_of, finish)
 
     def _check_frame(self, img) -> np.ndarray:
         """The input rules of __call__."""
@@ -661,7 +787,7 @@ class MTCNNDetector:
         boxes, points = self(img)
         return (boxes, points) if boxes.shape[0] else empty_detection()
 
-    def detect_batch(self, frames, max_frames: int = 32, return_stacks: bool = False):
+    def detect_batch(self, frames, max_frames: int = 32, return_stacks: bool = False, mixed_sizes: bool = False):
         """[(boxes [n,5] float64, points [10,n] float32)] in the order of ``frames`` (uint8 RGB [H, W, 3] each), every entry bit for bit
         what ``self(frame)`` returns; a frame without faces gives shapes (0, 5) and (10, 0).  Frames of one size run together, at most
         ``max_frames`` per pass: one upload, the launches of one frame and three read-backs per pass (a pass of ONE frame is the
@@ -670,15 +796,27 @@ class MTCNNDetector:
         keep their results.  A detector without ``device_boxes`` has no batched path and runs the frames one by one.
         ``return_stacks``: -> (that list, sources), where sources[i] is (stack, row) -- the CUDA uint8 [frames, h, w, 3] stack the
         frame's pass uploaded and the frame's row in it -- or None for a frame that took the single-frame call (a pass of one, a frame
-        redone after an overflow, any frame of a detector without ``device_boxes``) or had no pyramid level."""
+        redone after an overflow, any frame of a detector without ``device_boxes``) or had no pyramid level.
+        ``mixed_sizes``: the frames that would take the single-frame call because nothing shares their size run together in ragged
+        passes instead (plan_mixed_passes, detect_ragged), with the same results; ``ragged_passes`` and ``ragged_frames`` count them,
+        a frame that overflows there is redone alone as above, and ``sources`` stays None for the frames of a ragged pass."""
         imgs = [self._check_frame(f) for f in frames]
-        passes = plan_passes([f.shape[:2] for f in imgs], max_frames)
+        shapes = [f.shape[:2] for f in imgs]
+        passes = plan_mixed_passes(shapes, max_frames, minsize=self.minsize, factor=self.FACTOR) if mixed_sizes and self.device_boxes else \
+            plan_passes(shapes, max_frames)
         sources: list = [None] * len(imgs)
         if not self.device_boxes:
             alone = [self._alone(f) for f in imgs]
             return (alone, sources) if return_stacks else alone
         results: List[Optional[Tuple[np.ndarray, np.ndarray]]] = [None] * len(imgs)
-        for (h, w), idx in passes:
+        for hw, idx in passes:
+            if hw is None:                                                 # frames of different sizes: one ragged pass
+                self.ragged_passes += 1
+                self.ragged_frames += len(idx)
+                for i, res in zip(idx, self.detect_ragged([imgs[i] for i in idx])):
+                    results[i] = res if res is not None else self._alone(imgs[i])
+                continue
+            h, w = hw
             if not self.pyramid_scales(h, w):                              # smaller than minsize: no level, no launch
                 for i in idx:
                     results[i] = empty_detection()
