@@ -11,6 +11,9 @@ float64 (integer-valued corners), prob [n, 2], reg [n, 4], pts [n, 10], all floa
 The generator promises, and test_mtcnn_stages_cpu.py asserts on the oracle's output: every firing count and boundary listed
 there is present, and every box a stage hands on overlaps the frame (crop row x1 <= x2, y1 <= y2): what the cascade does with a
 box wholly outside the frame is the reference's own failure and not a case here.
+
+ragged_net_cases / ragged_edge_frames are the lists of a launch over frames of DIFFERENT sizes (tests/test_mtcnn_ragged_stages_cpu.py
+asserts what they promise, tests/test_mtcnn_ragged_stages_gpu.py feeds them to libhsefr_ragged.so).
 """
 import zlib
 
@@ -177,8 +180,27 @@ def sequence_cases(cap=NOMINAL_CAP):
 # ---------------------------------------------------------------------------------------------------------------------------
 # boxes that clip: one list per frame, squares (so squaring leaves them alone) to be fed with zero regressions
 # ---------------------------------------------------------------------------------------------------------------------------
-def edge_boxes():
-    """-> list of (label, img_w, img_h, corners [n, 4]): boxes over each edge, two opposite edges at once, and corners."""
+def _edge_corners(w, h):
+    """The eight boxes of edge_boxes()'s first list, placed against the edges of a w x h frame (at least 90 x 70): left, top, right,
+    bottom, three corners and one inside.  Every box overlaps the frame."""
+    assert w >= 90 and h >= 70
+    mx, my = w // 2 - 20, h // 2 - 20
+    return np.asarray([[-10, my, 29, my + 39],                # left
+                       [mx, -5, mx + 29, 24],                 # top
+                       [w - 20, my, w + 19, my + 39],         # right
+                       [mx, h - 20, mx + 39, h + 19],         # bottom
+                       [-8, -8, 21, 21],                      # corner: left + top
+                       [w - 15, h - 15, w + 24, h + 24],      # corner: right + bottom
+                       [w - 50, -12, w + 39, 77],             # corner: right + top (the bottom too where h < 77)
+                       [mx, my, mx + 29, my + 29]], np.float64)   # inside
+
+
+def edge_boxes(size=None):
+    """-> list of (label, img_w, img_h, corners [n, 4]): boxes over each edge, two opposite edges at once, and corners.
+    ``size`` = (img_w, img_h): one list of eight boxes placed against the edges of a frame of that size instead."""
+    if size is not None:
+        w, h = size
+        return [("%dx%d" % (w, h), w, h, _edge_corners(w, h))]
     wide = [[-10, 60, 29, 99],           # left
             [80, -5, 109, 24],           # top
             [180, 60, 219, 99],          # right
@@ -251,18 +273,20 @@ def finish_cases(cap=NOMINAL_CAP):
 ISOLATED = np.asarray([282.0, 202.0, 311.0, 231.0])     # a box no cluster reaches (cluster centres stay left of x = 200)
 
 
-def _net_list(name, stage, n, mode, img_w=320, img_h=240):
+def _net_list(name, stage, n, mode, img_w=320, img_h=240, x_hi=200, isolated=ISOLATED):
+    """``x_hi``: the cluster centres' right end (they start 20 px inside the frame on the other three sides); ``isolated``: the box of
+    the at-threshold mode, which no cluster may reach.  The defaults are fitted to 320 x 240."""
     rs = _rs(name)
     thr = THR[stage - 1]
     t = thr32(thr)
-    corners = _clustered_squares(rs, n, img_w, img_h, x_hi=200)
+    corners = _clustered_squares(rs, n, img_w, img_h, x_hi=x_hi)
     score = rs.uniform(float(t) - 0.25, 1.0, n).astype(F32)
     if n > 4:
         score[1::5] = F32(1.0)                                       # saturated softmax: ties
     at_thr = None
     if mode == "at-threshold":                                       # stages 2 and 3 pass on >: this one must not
         at_thr = 5
-        corners[at_thr] = ISOLATED
+        corners[at_thr] = isolated
         score[at_thr] = t
     elif mode == "none-pass":
         score = np.minimum(score, t)
@@ -307,6 +331,36 @@ def net_cases(stage, cap=NOMINAL_CAP):
             c["crops"] = True
             out.append(c)
     return out
+
+
+# frames of different sizes in one launch (tests/test_mtcnn_ragged_stages_*.py): (img_w, img_h) per frame, the counts of
+# test_mtcnn_batch_stages_gpu.NET_LABELS.  Small frames hold the long lists, so that boxes leave them over every edge and pair of
+# edges; 160 x 100 and 100 x 160 have one area; 251 * 187 * 3 is odd; 784 x 588 holds the at-threshold list with its isolated box.
+RAGGED_SIZES = [(100, 160), (200, 150), (90, 70), (640, 480), (251, 187), (160, 100), (784, 588)]
+RAGGED_LABELS = ["700", "0", "5", "cap+1", "1", "cap", "17"]
+
+
+def ragged_net_cases(stage, cap=NOMINAL_CAP):
+    """-> seven cases as net_cases gives them, one per frame of a mixed-size launch, every frame of another size.  Cluster centres lie
+    at least 20 px inside their frame, so every box overlaps it."""
+    assert stage in (2, 3)
+    counts = dict(net_counts(cap))
+    out = []
+    for b, ((img_w, img_h), label) in enumerate(zip(RAGGED_SIZES, RAGGED_LABELS)):
+        name = "stage%d/ragged/%d-%dx%d/%s" % (stage, b, img_w, img_h, label)
+        if label == "17":           # clusters in the left 60 % of the frame, the isolated box in its bottom right corner
+            c = _net_list(name, stage, 17, "at-threshold", img_w, img_h, x_hi=int(0.6 * img_w),
+                          isolated=np.asarray([img_w - 38.0, img_h - 38.0, img_w - 9.0, img_h - 9.0]))
+        else:
+            c = _net_list(name, stage, counts[label], "random", img_w, img_h, x_hi=img_w - 20)
+        out.append(c)
+    return out
+
+
+def ragged_edge_frames():
+    """-> three lists of edge boxes on frames of three sizes: edge_boxes()'s 200 x 150, 251 x 187 (an odd number of bytes: the next
+    frame of a packed buffer starts on an odd address) and the portrait 120 x 160."""
+    return [edge_boxes()[0], edge_boxes((251, 187))[0], edge_boxes((120, 160))[0]]
 
 
 def names(cases):

@@ -43,24 +43,76 @@ def item_sizes(k, tpp):
     return [(a + k - 1, b + k - 1) for a, b in outs]
 
 
-def ragged_conv(items, w, bias, alpha, co):
+SLACK_FILL = 1.5                   # what the allocated pixels outside the declared buffers hold: finite, so a read of them shows in a result
+
+
+def packed_input(items, c, base, slack):
+    """The items back to back, ``base`` floats into a larger tensor (the pointer is 4 * base bytes past the allocation's alignment)
+    with ``slack`` pixels behind: what lies in front of and behind the packed input is allocated and holds SLACK_FILL."""
+    import torch
+    flat = torch.cat([t.reshape(-1) for t in items]) if items else torch.empty(0, device="cuda")
+    whole = torch.full((base + flat.numel() + slack * c,), SLACK_FILL, dtype=torch.float32, device="cuda")
+    assert whole.data_ptr() % 16 == 0
+    whole[base:base + flat.numel()] = flat
+    return whole, whole[base:]
+
+
+def upload_maps(maps):
+    """The map table with one more row in front and one behind: maps[-1] and maps[n_items] are allocated, and hold a copy of the item of
+    the most workgroups as map_tables laid it out (a workgroup that followed a table entry there would write).
+    -> (the tensor, the pointer to row 0)."""
+    big = int(np.argmax(maps["oh"].astype(np.int64) * maps["ow"]))
+    spare = maps[big:big + 1]
+    t = upload(np.concatenate([spare, maps, spare]))
+    return t, t.data_ptr() + maps.dtype.itemsize
+
+
+def ragged_conv(items, w, bias, alpha, co, base=0, tweak=None, slack=0):
+    """hsefr_ragged_conv2d over the items -> (every item's output, the whole output buffer).  ``base``, ``slack``: see packed_input; the
+    output has ``slack`` pixels behind too, and the entry point is told the sizes WITHOUT the slack.  ``tweak(maps, block_item, x_pixels,
+    y_pixels)`` edits the tables in place before they go up."""
     import torch
     from hse_facerec_tf_amd import _lib
     from hse_facerec_tf_amd import mtcnn_ragged as mr
     k, c, cout = int(w.shape[0]), int(w.shape[2]), int(w.shape[3])
     d0, d1 = np.array([t.shape[0] for t in items]), np.array([t.shape[1] for t in items])
     maps, block_item, in_px, out_px = mr.map_tables((d0, d1), (d0 - k + 1, d1 - k + 1), cout // co)
-    x = torch.cat([t.reshape(-1) for t in items]) if items else torch.empty(0, device="cuda")
-    y = torch.full((max(out_px * cout, 1),), float("nan"), dtype=torch.float32, device="cuda")
-    d_maps, d_blocks = upload(maps) if len(items) else None, upload(block_item) if len(items) else None
+    if tweak is not None:
+        tweak(maps, block_item, in_px, out_px)
+    whole, x = packed_input(items, c, base, slack)
+    y = torch.full((max((out_px + slack) * cout, 1),), float("nan"), dtype=torch.float32, device="cuda")
+    (t_maps, p_maps), d_blocks = (upload_maps(maps), upload(block_item)) if len(items) else ((None, None), None)
     _lib.ragged_check(_lib.ragged_lib().hsefr_ragged_conv2d(
         x.data_ptr(), in_px, w.data_ptr(), bias.data_ptr(), None if alpha is None else alpha.data_ptr(), y.data_ptr(), out_px,
-        None if d_maps is None else d_maps.data_ptr(), len(items), None if d_blocks is None else d_blocks.data_ptr(), len(block_item), c, cout,
+        p_maps, len(items), None if d_blocks is None else d_blocks.data_ptr(), len(block_item), c, cout,
         k, k, 1, 0, 0, co, _lib.current_stream_ptr()), "hsefr_ragged_conv2d")
     torch.cuda.synchronize()
     out, at = [], 0
     for a, b in zip(d0 - k + 1, d1 - k + 1):
         out.append(y[at * cout:(at + int(a * b)) * cout].reshape(int(a), int(b), cout))
+        at += int(a * b)
+    return out, y
+
+
+def ragged_pool(items, c, tweak=None, slack=0, base=0):
+    """hsefr_ragged_maxpool 2 x 2 / 2 over the items -> (every item's output, the whole output buffer); the arguments of ragged_conv."""
+    import torch
+    from hse_facerec_tf_amd import _lib
+    from hse_facerec_tf_amd import mtcnn_ragged as mr
+    d0, d1 = np.array([t.shape[0] for t in items], np.int64), np.array([t.shape[1] for t in items], np.int64)
+    maps, block_item, in_px, out_px = mr.map_tables((d0, d1), (-(-d0 // 2), -(-d1 // 2)), c)
+    if tweak is not None:
+        tweak(maps, block_item, in_px, out_px)
+    whole, x = packed_input(items, c, base, slack)
+    y = torch.full((max((out_px + slack) * c, 1),), float("nan"), dtype=torch.float32, device="cuda")
+    (t_maps, p_maps), d_blocks = (upload_maps(maps), upload(block_item)) if len(items) else ((None, None), None)
+    _lib.ragged_check(_lib.ragged_lib().hsefr_ragged_maxpool(
+        x.data_ptr(), in_px, y.data_ptr(), out_px, p_maps, len(items), None if d_blocks is None else d_blocks.data_ptr(), len(block_item), c, 2, 2,
+        _lib.current_stream_ptr()), "hsefr_ragged_maxpool")
+    torch.cuda.synchronize()
+    out, at = [], 0
+    for a, b in zip(-(-d0 // 2), -(-d1 // 2)):
+        out.append(y[at * c:(at + int(a * b)) * c].reshape(int(a), int(b), c))
         at += int(a * b)
     return out, y
 
@@ -94,8 +146,7 @@ def test_ragged_conv_equals_conv2d_direct_item_by_item(c, cout, k):
 
 def test_ragged_maxpool_equals_maxpool_item_by_item():
     import torch
-    from hse_facerec_tf_amd import _lib, ops
-    from hse_facerec_tf_amd import mtcnn_ragged as mr
+    from hse_facerec_tf_amd import ops
     rs = np.random.RandomState(11)
     c = 10
     # 7 x 10: the first axis' last window is clipped, the second axis' is not; 1 x 1 and 3 x 3 inputs; 32 x 32 -> 16 x 16 x 10 threads = 10
@@ -107,15 +158,7 @@ def test_ragged_maxpool_equals_maxpool_item_by_item():
     assert tuple(want[3].shape) == (4, 5, c)
     for order in (list(range(len(items))), list(range(len(items)))[::-1], [3], []):
         sel = [items[i] for i in order]
-        d0, d1 = np.array([t.shape[0] for t in sel], np.int64), np.array([t.shape[1] for t in sel], np.int64)
-        maps, block_item, in_px, out_px = mr.map_tables((d0, d1), (-(-d0 // 2), -(-d1 // 2)), c)
-        x = torch.cat([t.reshape(-1) for t in sel]) if sel else torch.empty(0, device="cuda")
-        y = torch.full((max(out_px * c, 1),), float("nan"), dtype=torch.float32, device="cuda")
-        d_maps, d_blocks = (upload(maps), upload(block_item)) if sel else (None, None)
-        _lib.ragged_check(_lib.ragged_lib().hsefr_ragged_maxpool(
-            x.data_ptr(), in_px, y.data_ptr(), out_px, None if d_maps is None else d_maps.data_ptr(), len(sel),
-            None if d_blocks is None else d_blocks.data_ptr(), len(block_item), c, 2, 2, _lib.current_stream_ptr()), "hsefr_ragged_maxpool")
-        torch.cuda.synchronize()
+        _, y = ragged_pool(sel, c)
         assert torch.isnan(y).all() if not sel else not torch.isnan(y).any()
         at = 0
         for i in order:
@@ -125,17 +168,22 @@ def test_ragged_maxpool_equals_maxpool_item_by_item():
 
 
 # ---- the ragged pyramid against hsefr_mtcnn_pyramid_level per (frame, level) ---------------------------------------------------------
-def ragged_levels(frames, plan, buffer=None):
-    """hsefr_ragged_pyramid over the plan -> the packed level buffer.  ``buffer``: the packed frames on the device already."""
+def ragged_levels(frames, plan, buffer=None, **declared):
+    """hsefr_ragged_pyramid over the plan -> the packed level buffer.  ``buffer``: the packed frames on the device already.
+    ``declared``: n_frames, n_items, n_blocks, levels_elems, lds_bytes to tell the entry point instead of the plan's (the tables and
+    buffers are the whole plan's either way)."""
     import torch
     from hse_facerec_tf_amd import _lib
     from hse_facerec_tf_amd.mtcnn_ragged import DevicePlan
+    assert set(declared) <= {"n_frames", "n_items", "n_blocks", "levels_elems", "lds_bytes"}
     dplan = DevicePlan(plan, torch.device("cuda", torch.cuda.current_device()))
     packed = buffer if buffer is not None else torch.from_numpy(np.concatenate([f.reshape(-1) for f in frames])).cuda()
     levels = torch.full((plan.pixels[0] * 3,), float("nan"), dtype=torch.float32, device="cuda")
     _lib.ragged_check(_lib.ragged_lib().hsefr_ragged_pyramid(
-        packed.data_ptr(), plan.frames_bytes, dplan.frames, plan.n_frames, dplan.levels, plan.n_items, dplan.level_block_item,
-        len(plan.level_block_item), levels.data_ptr(), plan.pixels[0] * 3, plan.level_lds, _lib.current_stream_ptr()), "hsefr_ragged_pyramid")
+        packed.data_ptr(), plan.frames_bytes, dplan.frames, declared.get("n_frames", plan.n_frames), dplan.levels,
+        declared.get("n_items", plan.n_items), dplan.level_block_item, declared.get("n_blocks", len(plan.level_block_item)), levels.data_ptr(),
+        declared.get("levels_elems", plan.pixels[0] * 3), declared.get("lds_bytes", plan.level_lds), _lib.current_stream_ptr()),
+        "hsefr_ragged_pyramid")
     torch.cuda.synchronize()
     return levels
 
@@ -210,29 +258,33 @@ def stage1_maps(plan, rs, per_item):
     return prob, reg
 
 
-def run_ragged_stage1(plan, prob, reg, cap):
+def run_ragged_stage1(plan, prob, reg, cap, n_frames=None, n_items=None, n_cells=None):
+    """``n_frames``, ``n_items``, ``n_cells``: what to tell the entry point instead of the plan's counts (the tables and maps are the whole
+    plan's either way)."""
     import torch
     from hse_facerec_tf_amd import _lib
     from hse_facerec_tf_amd.mtcnn_ragged import DevicePlan
     dplan = DevicePlan(plan, torch.device("cuda", torch.cuda.current_device()))
-    n = plan.n_frames
+    n = plan.n_frames if n_frames is None else n_frames
     d_prob, d_reg = torch.from_numpy(prob).cuda(), torch.from_numpy(reg).cuda()
     found = torch.zeros((n, cap, 9), dtype=torch.float64, device="cuda")
     boxes = torch.zeros((n, cap, 5), dtype=torch.float64, device="cuda")
     tab = torch.zeros((n, cap, 8), dtype=torch.int32, device="cuda")
     counters = torch.zeros((n, 8), dtype=torch.int32, device="cuda")
     _lib.ragged_check(_lib.ragged_lib().hsefr_ragged_stage1(
-        d_prob.data_ptr(), d_reg.data_ptr(), plan.pixels[-1], dplan.frames, n, dplan.cells, plan.n_items, float(np.float32(0.6)), found.data_ptr(),
+        d_prob.data_ptr(), d_reg.data_ptr(), plan.pixels[-1] if n_cells is None else n_cells, dplan.frames, n, dplan.cells,
+        plan.n_items if n_items is None else n_items, float(np.float32(0.6)), found.data_ptr(),
         counters.data_ptr(), boxes.data_ptr(), tab.data_ptr(), _lib.current_stream_ptr()), "hsefr_ragged_stage1")
     return [t.cpu().numpy() for t in (counters, found, boxes, tab)]
 
 
-def run_single_frame_stage1(plan, prob, reg, cap):
-    """Per frame: hsefr_mtcnn_stage1_level on each of its levels, then hsefr_mtcnn_stage1_finish."""
+def run_single_frame_stage1(plan, prob, reg, cap, n_frames=None, skip=()):
+    """Per frame: hsefr_mtcnn_stage1_level on each of its levels, then hsefr_mtcnn_stage1_finish.  ``skip``: items to leave out;
+    ``n_frames``: the first frames of the plan only."""
     import torch
     from hse_facerec_tf_amd import _lib
     L = _lib.lib()
-    n = plan.n_frames
+    n = plan.n_frames if n_frames is None else n_frames
     d_prob, d_reg = torch.from_numpy(prob).cuda(), torch.from_numpy(reg).cuda()
     found = torch.zeros((n, cap, 9), dtype=torch.float64, device="cuda")
     boxes = torch.zeros((n, cap, 5), dtype=torch.float64, device="cuda")
@@ -242,6 +294,8 @@ def run_single_frame_stage1(plan, prob, reg, cap):
     for f in range(n):
         first, count = int(plan.frames["first_item"][f]), int(plan.frames["n_items"][f])
         for it in range(first, first + count):
+            if it in skip:
+                continue
             off, w, h = int(plan.cells["cell_off"][it]), int(plan.cells["w"][it]), int(plan.cells["h"][it])
             _lib.check(L.hsefr_mtcnn_stage1_level(d_prob[off:].data_ptr(), d_reg[off:].data_ptr(), w, h, float(plan.scales[it]), float(np.float32(0.6)),
                                                   found[f].data_ptr(), counters[f].data_ptr(), st), "hsefr_mtcnn_stage1_level")
