@@ -169,6 +169,17 @@ RAGGED_SIGNATURES = {
     "hsefr_ragged_stage_finish": (c_int, [c_int, _fp, _fp, c_int, _fp, _fp, _fp, ctypes.c_float, _fp, _fp, _fp, _fp, _fp, c_int, c_void_p]),
 }
 
+# libhsefr_mixed.so (include/hsefr_mixed.h): a mixed-size pass's frames turned, converted and cropped on the device, a sixth library.
+# HSEFR_MIXED_LIB selects another build.  The two tables are HOST pointers (c_void_p: a NumPy array's ctypes.data)
+MIXED_LIB_PATH = os.path.join(_HERE, os.environ.get("HSEFR_MIXED_LIB", "libhsefr_mixed.so"))
+_mixed_lib = None
+MIXED_SIGNATURES = {
+    "hsefr_mixed_version": (c_int, []),
+    "hsefr_mixed_last_error_string": (c_char_p, []),
+    "hsefr_mixed_frames_prepare": (c_int, [_fp, _fp, _i64, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "hsefr_mixed_face_crops": (c_int, [_fp, _i64, c_void_p, c_int, c_void_p, c_int, _fp, c_int, c_int, c_void_p]),
+}
+
 
 class HsefrError(RuntimeError):
     pass
@@ -308,6 +319,34 @@ def ragged_check(status: int, what: str = "") -> None:
     """check() for a status of libhsefr_ragged.so (its own error string)."""
     if status != OK:
         _raise(status, "%s%s (hsefr_ragged status %d)" % (what + ": " if what else "", ragged_last_error(), status))
+
+
+def mixed_lib() -> ctypes.CDLL:
+    """Load libhsefr_mixed.so once (torch first, as lib() does and for the same reason).  Missing is an error: there is no fallback."""
+    global _mixed_lib
+    if _mixed_lib is None:
+        import torch  # noqa: F401
+        if not os.path.exists(MIXED_LIB_PATH):
+            raise ImportError("%s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                              "(hipcc --offload-arch=gfx950). There is no CPU fallback." % MIXED_LIB_PATH)
+        L = ctypes.CDLL(MIXED_LIB_PATH)
+        for name, (res, args) in MIXED_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        _mixed_lib = L
+    return _mixed_lib
+
+
+def mixed_last_error() -> str:
+    s = mixed_lib().hsefr_mixed_last_error_string()
+    return s.decode("utf-8", "replace") if s else ""
+
+
+def mixed_check(status: int, what: str = "") -> None:
+    """check() for a status of libhsefr_mixed.so (its own error string)."""
+    if status != OK:
+        _raise(status, "%s%s (hsefr_mixed status %d)" % (what + ": " if what else "", mixed_last_error(), status))
 
 
 def last_error() -> str:

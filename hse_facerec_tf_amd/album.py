@@ -32,6 +32,14 @@ DEVICE_FRAMES_DEFAULT = True
 # than its spread; otherwise False.  Measured on an MI355X: 0.51 / 0.37 / 0.30 against 1.55 / 1.52 / 1.45 ms per frame (spreads 0.12 / 0.004 /
 # 0.013) and the album 86 against 150 ms -- so the frames whose size nothing shares go through mixed-size passes where the detector has them
 MIXED_SIZES_DEFAULT = True
+# process_images(mixed_device=...) of both loops when the caller does not say.  The rule, applied by tools/mixed_device_time.py in the last
+# line of profiles/mixed_device_time.txt: True if process_images(mixed_sizes=True, device_frames=True, mixed_device=True) is faster than the
+# same call without mixed_device by more than the spread between repetitions at 4, 8 and 16 frames of different sizes per call at BOTH
+# rotations 0 and 90 AND the 64-photo album of 64 sizes is not slower by more than its spread; otherwise False.  Measured on an MI355X:
+# 0.67 / 0.49 / 0.38 against 1.11 / 0.91 / 0.76 ms per frame at rotation 0 (spreads 0.009 / 0.008 / 0.004), 0.63 / 0.47 / 0.37 against 2.71 /
+# 2.60 / 2.48 at rotation 90 (spreads 0.28 / 0.36 / 0.13) and the album 43 against 82 ms (spread 18) -- so the frames and the faces of the
+# mixed-size passes stay on the device where those passes and the device crops or frames are in use
+MIXED_DEVICE_DEFAULT = True
 
 DECISION_TEMPLATES = ((0.875, 0.125), (0.353, 0.647))      # process_photos.py:209: rows = classes (male, female), columns = (p, 1 - p)
 
@@ -204,6 +212,16 @@ def _use_mixed_sizes(img_processing, mixed_sizes: Optional[bool]) -> bool:
     return bool(MIXED_SIZES_DEFAULT and getattr(detector, "detect_ragged", None) is not None and getattr(detector, "device_boxes", False))
 
 
+def _use_mixed_device(img_processing, mixed_device: Optional[bool], use_mixed_sizes: bool, use_device_crops: bool, use_device_frames: bool) -> bool:
+    """(Unasked, the device stages of the mixed-size passes follow those passes and the device crops or frames they extend, and need a
+    detector that detects from a packed buffer.)"""
+    if mixed_device is not None:
+        return bool(mixed_device)
+    detector = getattr(img_processing, "detector", None)
+    return bool(MIXED_DEVICE_DEFAULT and use_mixed_sizes and (use_device_crops or use_device_frames)
+                and getattr(detector, "detect_packed", None) is not None and getattr(detector, "device_boxes", False))
+
+
 def _normalized_on_device(features: Sequence[np.ndarray], device):
     """[n, d] raw features -> their L2-normalised rows as a CUDA tensor (ops.l2_normalize); they stay there for the clustering."""
     from . import ops
@@ -215,7 +233,7 @@ def _normalized_on_device(features: Sequence[np.ndarray], device):
 
 def process_video(img_processing, frames: Iterable[np.ndarray], mdate, rotation: int = 0, config: AlbumConfig = AlbumConfig(),
                   max_frames: int = 32, device_crops: Optional[bool] = None, device_frames: Optional[bool] = None,
-                  mixed_sizes: Optional[bool] = None) -> VideoResult:
+                  mixed_sizes: Optional[bool] = None, mixed_device: Optional[bool] = None) -> VideoResult:
     """process_photos.py:80-156 for the BGR uint8 frames of a video, in grab order.  Whether frame k is processed depends on the faces
     of earlier frames, but only counters divisible by 3 or 5 can ever be: those candidate frames run through
     ``process_images`` in windows of ``max_frames`` (batched detector passes), the rule is then replayed on the host over the face
@@ -223,12 +241,16 @@ def process_video(img_processing, frames: Iterable[np.ndarray], mdate, rotation:
     sequential loop.  Clusters need config.min_frames faces; no date rule.  ``rotation`` (0, 90 or 270: :102-107) is applied by
     process_images, on the device with ``device_frames`` (None: DEVICE_FRAMES_DEFAULT where the configuration allows it).
     ``mixed_sizes`` (None: MIXED_SIZES_DEFAULT where the detector has ragged passes): frames whose size no other frame of their
-    call shares are detected together (process_images(mixed_sizes=True)); the keyword is passed on only when it is in use."""
+    call shares are detected together (process_images(mixed_sizes=True)); the keyword is passed on only when it is in use.
+    ``mixed_device`` (None: MIXED_DEVICE_DEFAULT where those passes and the device crops or frames are in use): those passes' frames and
+    crops stay on the device (process_images(mixed_device=True)); passed on only when it is in use, too."""
     rotation = preprocess_device.check_rotation(rotation)
     video_year = _fractional_year(mdate)
     use_device = _use_device_crops(img_processing, device_crops)
     use_frames = _use_device_frames(img_processing, device_frames, use_device)
     mixed = dict(mixed_sizes=True) if _use_mixed_sizes(img_processing, mixed_sizes) else {}
+    if _use_mixed_device(img_processing, mixed_device, bool(mixed), use_device, use_frames):
+        mixed["mixed_device"] = True
     per_frame = {}                     # candidate frame index -> (ages, genders, features, crops)
     n_frames = 0
 
@@ -281,7 +303,8 @@ def _as_bgr(photo) -> np.ndarray:
 
 
 def process_album(img_processing, photos, mdates, videos=(), config: AlbumConfig = AlbumConfig(), max_frames: int = 32,
-                  device_crops: Optional[bool] = None, device_frames: Optional[bool] = None, mixed_sizes: Optional[bool] = None) -> AlbumResult:
+                  device_crops: Optional[bool] = None, device_frames: Optional[bool] = None, mixed_sizes: Optional[bool] = None,
+                  mixed_device: Optional[bool] = None) -> AlbumResult:
     """process_photos.py:219-358.  ``photos``: BGR uint8 arrays or paths, ``mdates`` their dates; ``videos``: (frames, mdate) or
     (frames, mdate, rotation) per video, frames as process_video takes them.  Pass 1 runs every photo, pass 2 the quarter turns
     clockwise of the photos without a face, pass 3 the quarter turns counter-clockwise of those still without one (:241-247) -- each pass
@@ -293,7 +316,9 @@ def process_album(img_processing, photos, mdates, videos=(), config: AlbumConfig
     DEVICE_FRAMES_DEFAULT where the configuration allows it).  ``mixed_sizes`` (None: MIXED_SIZES_DEFAULT where the detector has ragged
     passes): the photos of a call whose size no other shares -- most of a real album -- are detected together in mixed-size passes
     (process_images(mixed_sizes=True)) instead of one by one; it goes to the videos too, and the keyword is passed on only when it is
-    in use, so an ``img_processing`` written without it keeps working."""
+    in use, so an ``img_processing`` written without it keeps working.  ``mixed_device`` (None: MIXED_DEVICE_DEFAULT where those passes
+    and the device crops or frames are in use): the frames and the crops of those passes stay on the device
+    (process_images(mixed_device=True)); it goes to the videos too and is passed on only when it is in use."""
     photos = list(photos)
     mdates = list(mdates)
     videos = list(videos)
@@ -304,6 +329,8 @@ def process_album(img_processing, photos, mdates, videos=(), config: AlbumConfig
     use_device = _use_device_crops(img_processing, device_crops)
     use_frames = _use_device_frames(img_processing, device_frames, use_device)
     mixed = dict(mixed_sizes=True) if _use_mixed_sizes(img_processing, mixed_sizes) else {}
+    if _use_mixed_device(img_processing, mixed_device, bool(mixed), use_device, use_frames):
+        mixed["mixed_device"] = True
     n_photos = len(photos)
     found = [None] * n_photos          # per photo: (ages, genders, features, crops, has_center_face)
     call = 4 * max_frames              # frames per process_images call: bounds the frame stacks held on the device at one time
@@ -336,7 +363,7 @@ def process_album(img_processing, photos, mdates, videos=(), config: AlbumConfig
     for j, video in enumerate(videos):
         frames, vdate = video[0], video[1]
         v = process_video(img_processing, frames, vdate, video[2] if len(video) > 2 else 0, config, max_frames, use_device, use_frames,
-                          bool(mixed))
+                          "mixed_sizes" in mixed, "mixed_device" in mixed)
         if v.video_has_faces:
             private.append(n_photos + j)
         images.extend(v.cluster_images)

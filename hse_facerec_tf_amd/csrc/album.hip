@@ -12,7 +12,10 @@
 // the compiler does not fuse the product with the subtraction: contraction is off for this file (the pragma below, and the flag
 // csrc/build.sh adds for it).
 //
-// Shared with libhsefr.so: nothing (it is linked with -fvisibility=hidden; this library has its own error string).
+// The tap and the blend of one output byte live in cv_linear_px.h, which mixed_frames.hip (libhsefr_mixed.so: the same crops from a packed
+// buffer of frames of different sizes) compiles too.
+//
+// Shared with libhsefr.so: no symbol (it is linked with -fvisibility=hidden; this library has its own error string).
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -20,6 +23,10 @@
 #include "../../include/hsefr_album.h"
 
 #pragma clang fp contract(off)
+
+#include "cv_linear_px.h"
+
+using namespace hsefr;      // linear_tap, linear_blend (cv_linear_px.h, shared with mixed_frames.hip)
 
 namespace {
 
@@ -51,22 +58,6 @@ void set_error(const char* fmt, ...) {
 
 constexpr int UNITS_PER_BLOCK = 1024;      // 16-byte pieces (or single bytes) of one face's output per workgroup: four per thread
 constexpr int MAX_TAPS = 4096;             // oh + ow: the two tap tables of a workgroup, 12 bytes per entry, in LDS
-
-// one output coordinate of cv2.resize INTER_LINEAR, 8 bit (preprocess_device.cv_linear_taps): the two source indices and the 11-bit
-// weight of the second
-__device__ __forceinline__ void linear_tap(int o, int n_in, int n_out, int& i0, int& i1, int& w1) {
-    const double scale = (double)n_in / (double)n_out;
-    const double prod = ((double)o + 0.5) * scale;
-    const float pos = (float)(prod - 0.5);
-    const float fl = floorf(pos);
-    int base = (int)fl;
-    float frac = pos - fl;
-    if (base < 0 || base >= n_in - 1) frac = 0.f;
-    base = min(max(base, 0), n_in - 1);
-    i0 = base;
-    i1 = min(base + 1, n_in - 1);
-    w1 = (int)rintf(frac * 2048.f);
-}
 
 // VEC: a thread writes 16 consecutive bytes of its face's [oh, ow, 3] output with one store (the face's byte count is a multiple of
 // 16 and `out` is 16-byte aligned: 224 x 224 x 3 rows are 42 such stores); otherwise one byte per thread.  Every output byte is the
@@ -111,13 +102,7 @@ __global__ __launch_bounds__(256) void face_crops_kernel(const unsigned char* __
         unsigned word[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
         for (int k = 0; k < (VEC ? 16 : 1); ++k) {
-            const int a1 = xw1[x], a0 = 2048 - a1, b1 = yw1[y], b0 = 2048 - b1;
-            const unsigned char* r0 = src + yr0[y] * wrow + c;
-            const unsigned char* r1 = src + yr1[y] * wrow + c;
-            const int s0 = r0[xo0[x]] * a0 + r0[xo1[x]] * a1;
-            const int s1 = r1[xo0[x]] * a0 + r1[xo1[x]] * a1;
-            // at most 255: the weights of a pair sum to 2048
-            const unsigned v = (unsigned)((((b0 * (s0 >> 4)) >> 16) + ((b1 * (s1 >> 4)) >> 16) + 2) >> 2) & 255u;
+            const unsigned v = linear_blend(src + yr0[y] * wrow + c, src + yr1[y] * wrow + c, xo0[x], xo1[x], xw1[x], yw1[y]);
             if (VEC) {
                 word[k >> 2] |= v << (8 * (k & 3));
                 if (++c == 3) { c = 0; ++x; }

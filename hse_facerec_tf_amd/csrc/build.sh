@@ -3,7 +3,9 @@
 # the album organiser's device code, a library of its own because libhsefr.so is held below 4 MB by its tests) and libhsefr_frames.so
 # (include/hsefr_frames.h: the frame stack's channel swap and quarter turns, a library of its own for the same reason) and
 # libhsefr_forest.so (include/hsefr_forest.h: the random forest classifier, a fourth library for the same reason) and
-# libhsefr_ragged.so (include/hsefr_ragged.h: the detector pass over frames of different sizes, a fifth library for the same reason).
+# libhsefr_ragged.so (include/hsefr_ragged.h: the detector pass over frames of different sizes, a fifth library for the same reason) and
+# libhsefr_mixed.so (include/hsefr_mixed.h: the frames of such a pass turned, converted and cropped on the device, a sixth library for the
+# same reason).
 #   HSEFR_DEV=1 build.sh   builds libhsefr_dev.so instead: the same sources with -DHSEFR_DEV (tuning knobs as run-time
 #                          variables, hsefr_debug_*, the calibration kernels of devtools.hip) -- for tools/kbench.py only.
 set -euo pipefail
@@ -35,6 +37,11 @@ FOREST_FLAGS="$FLAGS $DEVICE_STRIP -ffp-contract=off"
 # area_resize_px.h) and must give their bits
 RAGGED_SRCS="mtcnn_ragged.hip"
 RAGGED_FLAGS="$FLAGS $DEVICE_STRIP"
+# libhsefr_mixed.so (include/hsefr_mixed.h: a mixed-size pass's frames turned and converted, and its faces cut, on the device): a sixth
+# library, built as the fifth.  It compiles the per-pixel bodies of album.hip and frames.hip (cv_linear_px.h, frames_px.h) and must give
+# their bits.  -ffp-contract=off: the crop taps are two separately rounded operations, as in album.hip
+MIXED_SRCS="mixed_frames.hip"
+MIXED_FLAGS="$FLAGS $DEVICE_STRIP -ffp-contract=off"
 LINT=1
 HOST_STRIP=0
 HOST_SIZE_FLAGS=""
@@ -105,7 +112,7 @@ if [ "$LINT" = "1" ]; then
   for s in $ALBUM_SRCS; do
     o="$BUILD/${s%.hip}.o"
     stale=0
-    for dep in "$s" ../../include/hsefr_album.h build.sh; do
+    for dep in "$s" cv_linear_px.h ../../include/hsefr_album.h build.sh; do
       if [ ! -f "$o" ] || [ "$dep" -nt "$o" ]; then stale=1; fi
     done
     if [ "$stale" = 1 ]; then
@@ -124,7 +131,7 @@ if [ "$LINT" = "1" ]; then
   for s in $FRAMES_SRCS; do
     o="$BUILD/${s%.hip}.o"
     stale=0
-    for dep in "$s" ../../include/hsefr_frames.h build.sh; do
+    for dep in "$s" frames_px.h ../../include/hsefr_frames.h build.sh; do
       if [ ! -f "$o" ] || [ "$dep" -nt "$o" ]; then stale=1; fi
     done
     if [ "$stale" = 1 ]; then
@@ -175,4 +182,23 @@ if [ "$LINT" = "1" ]; then
   /opt/rocm/lib/llvm/bin/llvm-strip --strip-all -w --keep-symbol='_ZN*_kernel*' --keep-symbol='!*__device_stub__*' "$RAGGED_OUT"
   python3 ../../tools/isa_lint.py "$RAGGED_OUT"
   echo "built $(realpath $RAGGED_OUT)"
+  # the sixth library: built, stripped and linted as the fifth; stale against the headers it shares with the second and the third too
+  MIXED_OUT=../libhsefr_mixed.so
+  MIXED_OBJS=""
+  for s in $MIXED_SRCS; do
+    o="$BUILD/${s%.hip}.o"
+    stale=0
+    for dep in "$s" cv_linear_px.h frames_px.h ../../include/hsefr_mixed.h build.sh; do
+      if [ ! -f "$o" ] || [ "$dep" -nt "$o" ]; then stale=1; fi
+    done
+    if [ "$stale" = 1 ]; then
+      rm -f "$o"
+      hipcc $MIXED_FLAGS -Xarch_host -Os ${HSEFR_EXTRA_FLAGS:-} -c "$s" -o "$o"
+    fi
+    MIXED_OBJS="$MIXED_OBJS $o"
+  done
+  hipcc $LINK -shared -fPIC -o "$MIXED_OUT" $MIXED_OBJS
+  /opt/rocm/lib/llvm/bin/llvm-strip --strip-all -w --keep-symbol='_ZN*_kernel*' --keep-symbol='!*__device_stub__*' "$MIXED_OUT"
+  python3 ../../tools/isa_lint.py "$MIXED_OUT"
+  echo "built $(realpath $MIXED_OUT)"
 fi

@@ -17,15 +17,18 @@
 // odd pointer) are read and written byte by byte, one pixel per lane, and edge tiles are cut by predicates: no byte outside the
 // destination stack is written.
 //
-// The byte permutes are shifts and masks of 24-bit values, nothing that saturates: hipcc has no reason to select v_ashr_pk_u8_i32 here
-// (tools/isa_lint.py refuses it, DESIGN.md lesson 36), and the 12-byte stores carry the gfx950 store-data guard (lesson 14).
+// The per-pixel bodies (a pixel as a dword, the 12-byte unit and its guarded store, the byte forms) live in frames_px.h, which
+// mixed_frames.hip (libhsefr_mixed.so: the same work over a packed buffer of frames of different sizes) compiles too.
 //
-// Shared with libhsefr.so and libhsefr_album.so: nothing (linked with -fvisibility=hidden; this library has its own error string).
+// Shared with libhsefr.so and libhsefr_album.so: no symbol (linked with -fvisibility=hidden; this library has its own error string).
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
 
 #include "../../include/hsefr_frames.h"
+#include "frames_px.h"
+
+using namespace hsefr;      // Px4, unpack4, pack4, store_px4, load_pixel, store_pixel, swap_02 (frames_px.h, shared with mixed_frames.hip)
 
 namespace {
 
@@ -51,49 +54,6 @@ constexpr int TILE_STRIDE = TILE + 4;      // dwords per LDS row (see the head o
 constexpr int THREADS = 256;
 constexpr int MAX_GRID_Y = 65535;
 constexpr int SWAP_BLOCKS = 4096;          // rotation 0: about this many workgroups over all frames, each lane striding through its frame
-
-// 12 bytes = 4 pixels, 4-byte aligned: one global_load_dwordx3 / global_store_dwordx3
-struct __attribute__((aligned(4))) Px4 {
-    unsigned a, b, c;
-};
-
-// a pixel as a dword: channel 0 in bits 0..7, channel 1 in 8..15, channel 2 in 16..23, bits 24..31 zero
-__device__ __forceinline__ unsigned swap_02(unsigned p) { return ((p & 0xffu) << 16) | (p & 0xff00u) | ((p >> 16) & 0xffu); }
-
-__device__ __forceinline__ void unpack4(const Px4& v, bool swap, unsigned p[4]) {
-    p[0] = v.a & 0xffffffu;
-    p[1] = ((v.a >> 24) | (v.b << 8)) & 0xffffffu;
-    p[2] = ((v.b >> 16) | (v.c << 16)) & 0xffffffu;
-    p[3] = v.c >> 8;
-    if (swap) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) p[k] = swap_02(p[k]);
-    }
-}
-
-__device__ __forceinline__ Px4 pack4(unsigned p0, unsigned p1, unsigned p2, unsigned p3) {
-    Px4 v;
-    v.a = p0 | (p1 << 24);
-    v.b = (p1 >> 8) | (p2 << 16);
-    v.c = (p2 >> 16) | (p3 << 8);
-    return v;
-}
-
-__device__ __forceinline__ void store_px4(unsigned char* at, const Px4& v) {
-    *reinterpret_cast<Px4*>(at) = v;
-    asm volatile("s_nop 1" ::: "memory");      // gfx950 store-data hazard: two wait states behind a wide store (tools/isa_lint.py)
-}
-
-__device__ __forceinline__ unsigned load_pixel(const unsigned char* at, bool swap) {
-    const unsigned c0 = at[0], c1 = at[1], c2 = at[2];
-    return swap ? (c2 | (c1 << 8) | (c0 << 16)) : (c0 | (c1 << 8) | (c2 << 16));
-}
-
-__device__ __forceinline__ void store_pixel(unsigned char* at, unsigned p) {
-    at[0] = (unsigned char)(p & 0xffu);
-    at[1] = (unsigned char)((p >> 8) & 0xffu);
-    at[2] = (unsigned char)((p >> 16) & 0xffu);
-}
 
 // rotation 0.  VEC: both stacks 4-byte aligned and h * w a multiple of 4, so every frame is a whole number of 12-byte units that start
 // on dword boundaries; otherwise one pixel per lane, byte by byte.  src and dst may be the same stack (no __restrict__): a lane reads

@@ -150,6 +150,11 @@ class FacialImageProcessing:
         """detect_batch's keyword, passed only when it is in use (a detector written without it keeps working)."""
         return dict(mixed_sizes=True) if mixed_sizes else {}
 
+    @staticmethod
+    def _packed_kw(mixed_device: bool) -> dict:
+        """detect_batch's keyword of mixed_device, passed only when it is in use, as _mixed_kw's."""
+        return dict(packed_sources=True) if mixed_device else {}
+
     # ---- facial_analysis.py:225-294 -----------------------------------------------------------------
     @staticmethod
     def face_boxes(bounding_boxes, img_w: int, img_h: int) -> List[List[int]]:
@@ -224,8 +229,11 @@ class FacialImageProcessing:
         """The resized faces of process_images on the device, CUDA uint8 [m, h, w, 3] RGB in list order.  The frames of a detector
         pass (``sources[i]`` = the pass's stack on the device and the frame's row in it) are cut from that stack by ONE launch per pass
         (preprocess_device.face_crops: one [m, 5] table uploaded, no frame and no crop uploaded again, no launch per crop size); the
-        frames that took the single-frame call are cut on the host and resized by preprocess_faces_cv, as without device_crops."""
+        frames that took the single-frame call are cut on the host and resized by preprocess_faces_cv, as without device_crops.
+        The frames of a mixed-size pass whose source is (PackedFrames, row) -- process_images(mixed_device=True) -- are cut the same
+        way from that pass's packed buffer (preprocess_device.face_crops_packed): the source's type decides."""
         from . import preprocess_device
+        from .mtcnn_ragged import PackedFrames
         torch = _lib.require_gpu()
         counts = [len(b) for b in all_bboxes]
         starts = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
@@ -241,10 +249,14 @@ class FacialImageProcessing:
         for stack, idx in passes.values():
             table = np.array([[sources[i][1]] + list(box) for i in idx for box in all_bboxes[i]], dtype=np.int32)
             where = np.concatenate([np.arange(starts[i], starts[i + 1]) for i in idx])
-            if where[-1] - where[0] + 1 == len(where):            # the pass's faces stand together in the batch: written in place
-                preprocess_device.face_crops(stack, table, (self.h, self.w), out=x8[int(where[0]):int(where[-1]) + 1])
+            if isinstance(stack, PackedFrames):
+                cut = lambda out=None, p=stack: preprocess_device.face_crops_packed(p.data, p.shapes, table, (self.h, self.w), out=out)  # noqa: E731
             else:
-                x8[torch.from_numpy(where).to(x8.device)] = preprocess_device.face_crops(stack, table, (self.h, self.w))
+                cut = lambda out=None, p=stack: preprocess_device.face_crops(p, table, (self.h, self.w), out=out)      # noqa: E731
+            if where[-1] - where[0] + 1 == len(where):            # the pass's faces stand together in the batch: written in place
+                cut(x8[int(where[0]):int(where[-1]) + 1])
+            else:
+                x8[torch.from_numpy(where).to(x8.device)] = cut()
         if alone:
             crops = [imgs[i][y1:y2, x1:x2, :] for i in alone for (x1, y1, x2, y2) in all_bboxes[i]]
             where = np.concatenate([np.arange(starts[i], starts[i + 1]) for i in alone])
@@ -259,7 +271,7 @@ class FacialImageProcessing:
         return bool(self.device_preprocess and self.sess.accepts_u8 and getattr(self.detector, "detect_stack", None) is not None
                     and getattr(self.detector, "device_boxes", False))
 
-    def _detect_device_frames(self, draws, rotation: int, max_frames: int, mixed_sizes: bool = False):
+    def _detect_device_frames(self, draws, rotation: int, max_frames: int, mixed_sizes: bool = False, mixed_device: bool = False):
         """process_images' detection with device_frames: the frames grouped by their TURNED size (mtcnn.plan_passes); a group of two or
         more is stacked as decoded (BGR, unrotated), uploaded, turned and converted by ONE launch (preprocess_device.prepare_frames; in
         place for rotation 0, and a quarter turn's raw stack is dropped as soon as the prepared one is written) and detected from that
@@ -268,9 +280,15 @@ class FacialImageProcessing:
         (converted on the host, as without device_frames) and a frame whose candidate list overflowed (read back from its row of the
         prepared stack) -- and None for the others, whose pixels the host never touches; ``shapes[i]`` the turned (h, w).
         ``mixed_sizes``: the frames alone in their size group are converted on the host as before and then detected TOGETHER, in the
-        detector's mixed-size passes (detect_batch(mixed_sizes=True)), instead of one by one."""
+        detector's mixed-size passes (detect_batch(mixed_sizes=True)), instead of one by one.
+        ``mixed_device`` (with ``mixed_sizes``): those frames get what the same-size groups get -- the passes are planned here
+        (mtcnn.plan_mixed_passes over the TURNED shapes, the plan detect_batch makes), a pass's frames are concatenated as decoded,
+        uploaded once, turned and converted by ONE launch (preprocess_device.prepare_packed; in place for rotation 0) and detected from
+        that buffer (MTCNNDetector.detect_packed); ``sources[i]`` is (PackedFrames, row), ``imgs[i]`` stays None, and a frame that
+        overflowed is read back from its range of the prepared buffer and redone alone."""
         from . import preprocess_device
-        from .mtcnn import empty_detection, plan_passes
+        from .mtcnn import empty_detection, plan_mixed_passes, plan_passes
+        from .mtcnn_ragged import PackedFrames
         torch = _lib.require_gpu()
         raw = []
         for d in draws:
@@ -293,7 +311,8 @@ class FacialImageProcessing:
             if len(idx) == 1:
                 if mixed_sizes:
                     lone.append(idx[0])
-                    imgs[idx[0]] = self._bgr_to_rgb(preprocess_device.turn_frame(raw[idx[0]], rotation))
+                    if not mixed_device:
+                        imgs[idx[0]] = self._bgr_to_rgb(preprocess_device.turn_frame(raw[idx[0]], rotation))
                 else:
                     alone(idx[0], self._bgr_to_rgb(preprocess_device.turn_frame(raw[idx[0]], rotation)))
                 continue
@@ -307,13 +326,35 @@ class FacialImageProcessing:
                     detections[i], sources[i] = res, (stack, row)
                 else:
                     alone(i, stack[row].cpu().numpy())
-        if lone:
+        if lone and mixed_device:
+            det = self.detector
+            for hw, part in plan_mixed_passes([shapes[i] for i in lone], max_frames, minsize=det.minsize, factor=det.FACTOR):
+                idx = [lone[k] for k in part]
+                if hw is not None:                                         # a pass of one: the single-frame call, converted on the host
+                    for i in idx:
+                        alone(i, self._bgr_to_rgb(preprocess_device.turn_frame(raw[i], rotation)))
+                    continue
+                det.ragged_passes += 1
+                det.ragged_frames += len(idx)
+                buf = torch.from_numpy(np.concatenate([np.ascontiguousarray(raw[i]).reshape(-1) for i in idx])).to(det.device)   # one upload per pass
+                raw_shapes = [raw[i].shape[:2] for i in idx]
+                if rotation == 0:
+                    preprocess_device.prepare_packed(buf, raw_shapes, 0, True, out=buf)                 # in place: never a second buffer
+                else:
+                    buf = preprocess_device.prepare_packed(buf, raw_shapes, rotation, True)             # (the raw buffer is released here)
+                packed = PackedFrames(buf, [shapes[i] for i in idx])
+                for row, (i, res) in enumerate(zip(idx, det.detect_packed(packed))):
+                    if res is not None:
+                        detections[i], sources[i] = res, (packed, row)
+                    else:
+                        alone(i, packed.frame(row).cpu().numpy())
+        elif lone:
             for i, res in zip(lone, self.detector.detect_batch([imgs[i] for i in lone], max_frames=max_frames, mixed_sizes=True)):
                 detections[i] = res
         return imgs, shapes, detections, sources
 
     def process_images(self, draws, max_frames: int = 32, device_crops: bool = False, return_crops: bool = False, rotation: int = 0,
-                       device_frames: bool = False, mixed_sizes: bool = False):
+                       device_frames: bool = False, mixed_sizes: bool = False, mixed_device: bool = False):
         """process_image for a list of BGR uint8 frames (the photos of an album, the frames of a video: process_photos.py:92-118,
         :238-247) -> a list of process_image's 5-tuples, in list order.  One detect_faces_batch call over all frames, then ONE
         age_gender_batch call over the crops of all frames on the bulk plan (it chunks by max_batch itself), split back per frame.
@@ -333,28 +374,42 @@ class FacialImageProcessing:
         ``detect_stack``.  Results are those of device_frames=False bit for bit.
         mixed_sizes: the frames whose (turned) size no other frame of the call shares -- today one single-frame detector call each --
         are detected together in mixed-size passes (MTCNNDetector.detect_batch(mixed_sizes=True)); with device_frames they are converted
-        on the host as before, and their faces are cut on the host, as for any frame without a source stack.  Same-size groups keep
+        on the host as before, and their faces are cut on the host, as for any frame without a source stack (mixed_device, below,
+        moves both onto the device).  Same-size groups keep
         the device frames and the device crops.  Results are those of mixed_sizes=False bit for bit.  Needs a detector whose
-        detect_batch takes the keyword."""
+        detect_batch takes the keyword.
+        mixed_device (with mixed_sizes and one of device_crops / device_frames; ValueError otherwise, before any device work): the
+        mixed-size passes get what the same-size passes get.  Under device_crops the faces of such a pass are cut by one launch from
+        the buffer the pass uploaded (preprocess_device.face_crops_packed) and no crop is uploaded; under device_frames, additionally,
+        the pass's frames are uploaded as decoded and turned and converted by one launch (preprocess_device.prepare_packed), and the
+        host never touches their pixels.  Results are those of mixed_device=False bit for bit.  Needs an MTCNNDetector with
+        device_boxes (``detect_packed``)."""
         from . import preprocess_device
         from .mtcnn import split_by_counts
         rotation = preprocess_device.check_rotation(rotation)
         byte_path = self.device_preprocess and self.sess.accepts_u8
+        if mixed_device and not mixed_sizes:
+            raise ValueError("mixed_device needs mixed_sizes=True (it moves the mixed-size passes' frames and crops onto the device)")
+        if mixed_device and not (device_crops or device_frames):
+            raise ValueError("mixed_device needs device_crops=True or device_frames=True")
         if device_frames and not self.device_frames_supported():
             raise ValueError("device_frames needs device_preprocess=True, an engine that accepts bytes and a detector with detect_stack "
                              "(an MTCNNDetector with device_boxes)")
         if device_crops and not byte_path:
             raise ValueError("device_crops needs device_preprocess=True and an engine that accepts bytes")
+        if mixed_device and not (getattr(self.detector, "detect_packed", None) is not None and getattr(self.detector, "device_boxes", False)):
+            raise ValueError("mixed_device needs a detector with detect_packed (an MTCNNDetector with device_boxes)")
         device_crops = bool(device_crops or device_frames)
         if not device_frames:
             imgs = [self._bgr_to_rgb(preprocess_device.turn_frame(np.asarray(d), rotation) if rotation else d) for d in draws]
             shapes = [img.shape[:2] for img in imgs]
         t = time.time()
         if device_frames:
-            imgs, shapes, detections, sources = self._detect_device_frames(draws, rotation, max_frames, mixed_sizes)
+            imgs, shapes, detections, sources = self._detect_device_frames(draws, rotation, max_frames, mixed_sizes, mixed_device)
         elif device_crops and getattr(self.detector, "detect_batch", None) is not None:
             # (a detector whose detect_batch cannot hand its stacks back raises here: device_crops was asked for)
-            detections, sources = self.detector.detect_batch(imgs, max_frames=max_frames, return_stacks=True, **self._mixed_kw(mixed_sizes))
+            detections, sources = self.detector.detect_batch(imgs, max_frames=max_frames, return_stacks=True, **self._mixed_kw(mixed_sizes),
+                                                                 **self._packed_kw(mixed_device))
         else:                                      # no batched detector: every frame takes the single-frame call and the host crops
             detections, sources = self.detect_faces_batch(imgs, max_frames=max_frames, mixed_sizes=mixed_sizes), [None] * len(imgs)
         if self.print_stat:

@@ -30,7 +30,7 @@ import numpy as np
 
 from . import _lib, ops, preprocess
 from .graphdef import Graph, GraphNode, read_graph
-from .mtcnn_ragged import DevicePlan, RaggedMaps, RaggedPlan, frame_workspace_bytes, ragged_plan  # noqa: F401  (ragged_plan: part of this module's face)
+from .mtcnn_ragged import DevicePlan, PackedFrames, RaggedMaps, RaggedPlan, frame_workspace_bytes, ragged_plan  # noqa: F401  (ragged_plan: part of this module's face)
 
 MTCNN_PB = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "models", "mtcnn.pb")
 
@@ -721,7 +721,7 @@ class MTCNNDetector:
         self._ragged_plans[key] = dplan
         return dplan
 
-    def detect_ragged(self, frames) -> List[Optional[Tuple[np.ndarray, np.ndarray]]]:
+    def detect_ragged(self, frames, packed_out: Optional[list] = None) -> List[Optional[Tuple[np.ndarray, np.ndarray]]]:
         """ONE pass over frames of any sizes (uint8 RGB [H, W, 3] each): per frame (boxes [n,5] float64, points [10,n] float32), bit
         for bit what ``self(frame)`` returns (a frame without faces gives shapes (0, 5) and (10, 0)), or None where that frame's
         candidate list overflowed (the caller redoes that frame alone).  Uploads: the frames' bytes packed back to back, the plan's
@@ -732,24 +732,53 @@ class MTCNNDetector:
         Bit identity with the single-frame call: the pyramid, the crops and the box logic run the one-frame bodies the single-frame
         entries run (csrc/area_resize_px.h, csrc/mtcnn_post_frame.h), with a frame's place and size read from the plan's tables; P-Net
         runs through the program _DeviceNet compiled, with the same weight tensors, each output's FMA chain in conv2d_direct's order
-        (tests/test_mtcnn_ragged_gpu.py checks every step and the whole)."""
+        (tests/test_mtcnn_ragged_gpu.py checks every step and the whole).
+        ``packed_out``: a list that receives the pass's uploaded frames as a PackedFrames, for a caller that cuts the faces from them
+        on the device (nothing is appended where no frame has a pyramid level: nothing is uploaded then)."""
         if not self.device_boxes:
             raise ValueError("detect_ragged needs a detector with device_boxes")
         imgs = [self._check_frame(f) for f in frames]
         if not imgs:
             return []
+        shapes = tuple((int(f.shape[0]), int(f.shape[1])) for f in imgs)
+        if self._ragged_device_plan(shapes).plan.n_items == 0:            # no frame has a pyramid level: no upload, no launch
+            return [empty_detection() for _ in imgs]
+        packed = self._torch.from_numpy(np.concatenate([np.ascontiguousarray(f).reshape(-1) for f in imgs])).to(self.device)      # one upload per pass
+        if packed_out is not None:
+            packed_out.append(PackedFrames(packed, shapes))
+        return self._detect_ragged_body(shapes, packed)
+
+    def detect_packed(self, packed: PackedFrames) -> List[Optional[Tuple[np.ndarray, np.ndarray]]]:
+        """detect_ragged for a pass whose frames are on the device already: ``packed`` a PackedFrames of RGB frames on the detector's
+        device (preprocess_device.prepare_packed writes one).  Nothing is uploaded but the plan's tables where the list of shapes is new;
+        the launches, the read-backs and the results are those of detect_ragged on the same frames.  Per frame (boxes, points), or None
+        where that frame's candidate list overflowed (the caller redoes that frame alone: ``self(packed.frame(row).cpu().numpy())``).
+        Needs ``device_boxes``."""
+        if not self.device_boxes:
+            raise ValueError("detect_packed needs a detector with device_boxes")
+        if not isinstance(packed, PackedFrames):
+            raise ValueError("detect_packed takes a PackedFrames, not %s" % type(packed).__name__)
+        if not getattr(packed.data, "is_cuda", False):
+            raise ValueError("detect_packed takes frames on the device (a CUDA buffer)")
+        if packed.data.device != self.device:
+            raise ValueError("the frames are on %s, the detector on %s" % (packed.data.device, self.device))
+        if not len(packed):
+            return []
+        if self._ragged_device_plan(packed.shapes).plan.n_items == 0:
+            return [empty_detection() for _ in packed.shapes]
+        return self._detect_ragged_body(packed.shapes, packed.data)
+
+    def _detect_ragged_body(self, shapes: tuple, packed) -> List[Optional[Tuple[np.ndarray, np.ndarray]]]:
+        """detect_ragged behind its upload: ``packed`` the CUDA uint8 buffer that holds the frames of ``shapes`` back to back."""
         torch, L, R = self._torch, _lib.lib(), _lib.ragged_lib()
-        dplan = self._ragged_device_plan(tuple((int(f.shape[0]), int(f.shape[1])) for f in imgs))
+        dplan = self._ragged_device_plan(shapes)
         plan = dplan.plan
         n_frames, dev = plan.n_frames, self.device
         results: List[Optional[Tuple[np.ndarray, np.ndarray]]] = [empty_detection() for _ in range(n_frames)]
-        if plan.n_items == 0:                                              # no frame has a pyramid level: no upload, no launch
-            return results
         cap = int(L.hsefr_mtcnn_post_capacity())
         if int(R.hsefr_ragged_capacity()) != cap:
             raise RuntimeError("libhsefr.so and libhsefr_ragged.so were built from different sources (list capacity %d / %d)"
                                % (cap, int(R.hsefr_ragged_capacity())))
-        packed = torch.from_numpy(np.concatenate([np.ascontiguousarray(f).reshape(-1) for f in imgs])).to(dev)      # one upload per pass
         with _lib.on_device(packed):
             st = _lib.current_stream_ptr()
             wk = self._batch_work_tensors(cap, n_frames)
@@ -787,7 +816,7 @@ class MTCNNDetector:
         boxes, points = self(img)
         return (boxes, points) if boxes.shape[0] else empty_detection()
 
-    def detect_batch(self, frames, max_frames: int = 32, return_stacks: bool = False, mixed_sizes: bool = False):
+    def detect_batch(self, frames, max_frames: int = 32, return_stacks: bool = False, mixed_sizes: bool = False, packed_sources: bool = False):
         """[(boxes [n,5] float64, points [10,n] float32)] in the order of ``frames`` (uint8 RGB [H, W, 3] each), every entry bit for bit
         what ``self(frame)`` returns; a frame without faces gives shapes (0, 5) and (10, 0).  Frames of one size run together, at most
         ``max_frames`` per pass: one upload, the launches of one frame and three read-backs per pass (a pass of ONE frame is the
@@ -799,7 +828,10 @@ class MTCNNDetector:
         redone after an overflow, any frame of a detector without ``device_boxes``) or had no pyramid level.
         ``mixed_sizes``: the frames that would take the single-frame call because nothing shares their size run together in ragged
         passes instead (plan_mixed_passes, detect_ragged), with the same results; ``ragged_passes`` and ``ragged_frames`` count them,
-        a frame that overflows there is redone alone as above, and ``sources`` stays None for the frames of a ragged pass."""
+        a frame that overflows there is redone alone as above, and ``sources`` stays None for the frames of a ragged pass.
+        ``packed_sources`` (with ``return_stacks`` and ``mixed_sizes``): sources[i] of a frame of a ragged pass is (PackedFrames, row)
+        instead -- the buffer that pass uploaded and the frame's place in it (preprocess_device.face_crops_packed cuts from it) -- and
+        None where the frame was redone alone."""
         imgs = [self._check_frame(f) for f in frames]
         shapes = [f.shape[:2] for f in imgs]
         passes = plan_mixed_passes(shapes, max_frames, minsize=self.minsize, factor=self.FACTOR) if mixed_sizes and self.device_boxes else \
@@ -813,8 +845,11 @@ class MTCNNDetector:
             if hw is None:                                                 # frames of different sizes: one ragged pass
                 self.ragged_passes += 1
                 self.ragged_frames += len(idx)
-                for i, res in zip(idx, self.detect_ragged([imgs[i] for i in idx])):
+                kept = [] if return_stacks and packed_sources else None
+                for row, (i, res) in enumerate(zip(idx, self.detect_ragged([imgs[i] for i in idx], kept))):
                     results[i] = res if res is not None else self._alone(imgs[i])
+                    if res is not None and kept:
+                        sources[i] = (kept[0], row)
                 continue
             h, w = hw
             if not self.pyramid_scales(h, w):                              # smaller than minsize: no level, no launch

@@ -186,6 +186,58 @@ def ragged_plan(shapes: Sequence[Tuple[int, int]], minsize: int, factor: float, 
     return p
 
 
+# the frame table of include/hsefr_mixed.h (libhsefr_mixed.so reads it from the host)
+MIXED_FRAME_DT = np.dtype([("offset", "<i8"), ("h", "<i4"), ("w", "<i4")])
+assert MIXED_FRAME_DT.itemsize == 16
+
+
+def packed_offsets(shapes: Sequence[Tuple[int, int]]) -> np.ndarray:
+    """The byte offsets of uint8 [h, w, 3] frames packed back to back in list order, int64: ragged_plan's ``frames["offset"]``."""
+    sizes = np.array([int(h) * int(w) * 3 for h, w in shapes], np.int64)
+    return np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64) if len(sizes) else np.zeros(0, np.int64)
+
+
+def frame_table(shapes: Sequence[Tuple[int, int]], offsets=None) -> np.ndarray:
+    """MIXED_FRAME_DT [n]: the host table libhsefr_mixed.so takes, for frames of the given (h, w) at ``offsets`` (default: back to back)."""
+    table = np.zeros(len(shapes), MIXED_FRAME_DT)
+    table["offset"] = packed_offsets(shapes) if offsets is None else np.asarray(offsets, np.int64)
+    if len(shapes):
+        table["h"], table["w"] = [int(h) for h, _ in shapes], [int(w) for _, w in shapes]
+    return table
+
+
+class PackedFrames:
+    """The frames of a mixed-size pass on the device: ``data`` a contiguous uint8 1-D buffer (CUDA for every consumer) that holds
+    frame i as [h, w, 3] at byte ``offsets[i]``; ``shapes`` the (h, w) of the frames AS THEY STAND in the buffer (after
+    preprocess_device.prepare_packed turned them: the turned sizes); ``offsets`` int64, the frames back to back in list order -- the
+    layout of ragged_plan, whose ``frames["offset"]`` they equal.  ``frame(i)`` is a [h, w, 3] view of frame i."""
+
+    def __init__(self, data, shapes: Sequence[Tuple[int, int]]):
+        self.shapes = tuple((int(h), int(w)) for h, w in shapes)
+        for f, (h, w) in enumerate(self.shapes):
+            if h < 1 or w < 1 or h * w * 3 >= 1 << 31:
+                raise ValueError("frame %d: bad size %d x %d" % (f, h, w))
+        self.offsets = packed_offsets(self.shapes)
+        self.nbytes = int(sum(h * w * 3 for h, w in self.shapes))
+        if not (hasattr(data, "dim") and data.dim() == 1 and str(data.dtype) == "torch.uint8" and data.is_contiguous()):
+            raise ValueError("data must be a contiguous uint8 1-D tensor")
+        if int(data.shape[0]) < self.nbytes:
+            raise ValueError("the frames take %d bytes, the buffer has %d" % (self.nbytes, int(data.shape[0])))
+        self.data = data
+
+    def __len__(self) -> int:
+        return len(self.shapes)
+
+    @property
+    def table(self) -> np.ndarray:
+        return frame_table(self.shapes, self.offsets)
+
+    def frame(self, i: int):
+        h, w = self.shapes[i]
+        at = int(self.offsets[i])
+        return self.data[at:at + h * w * 3].reshape(h, w, 3)
+
+
 class DevicePlan:
     """A RaggedPlan's tables on the device: ONE upload of all of them (sections aligned to 16 bytes), addressed by pointer."""
 

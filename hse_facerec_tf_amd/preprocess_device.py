@@ -248,3 +248,84 @@ def prepare_frames(stack, rotation: int = 0, swap_rb: bool = True, out=None):
         _lib.frames_check(_lib.frames_lib().hsefr_frames_prepare(stack.data_ptr(), out.data_ptr(), n, h, w, rotation, 1 if swap_rb else 0,
                                                                   _lib.current_stream_ptr()), "hsefr_frames_prepare")
     return out
+
+
+def _packed_args(packed, shapes, offsets, what: str):
+    """The checks prepare_packed and face_crops_packed share -> the host frame table (mtcnn_ragged.MIXED_FRAME_DT)."""
+    import torch
+    from .mtcnn_ragged import frame_table
+    if not isinstance(packed, torch.Tensor):
+        raise ValueError("%s must be a CUDA uint8 1-D tensor, not %s" % (what, type(packed).__name__))
+    if packed.dtype != torch.uint8 or packed.dim() != 1:
+        raise ValueError("%s must be a uint8 1-D tensor, got %s %r" % (what, packed.dtype, tuple(packed.shape)))
+    if not packed.is_contiguous():
+        raise ValueError("%s must be contiguous" % what)
+    if not packed.is_cuda:
+        raise ValueError("%s must be a CUDA tensor (the caller uploads the frames)" % what)
+    shapes = [(int(h), int(w)) for h, w in shapes]
+    for f, (h, w) in enumerate(shapes):
+        if h < 1 or w < 1 or h * w * 3 >= 1 << 31:
+            raise ValueError("frame %d: bad size %d x %d" % (f, h, w))
+    if offsets is not None and len(offsets) != len(shapes):
+        raise ValueError("%d offsets for %d frames" % (len(offsets), len(shapes)))
+    table = frame_table(shapes, offsets)
+    ends = table["offset"] + table["h"].astype(np.int64) * table["w"] * 3
+    if len(table) and (int(table["offset"].min()) < 0 or int(ends.max()) > int(packed.shape[0])):
+        raise ValueError("the frames do not fit %s of %d bytes (they end at byte %d)" % (what, int(packed.shape[0]), int(ends.max())))
+    return table
+
+
+def prepare_packed(packed, shapes, rotation: int = 0, swap_rb: bool = True, out=None, offsets=None):
+    """prepare_frames for frames of DIFFERENT sizes packed in one buffer, in ONE launch (libhsefr_mixed.so, csrc/mixed_frames.hip):
+    ``packed`` a contiguous CUDA uint8 1-D tensor that holds frame i as [h, w, 3] (``shapes[i]``, the SOURCE shapes) at byte
+    ``offsets[i]`` (default: back to back in list order, mtcnn.ragged_plan's layout) -> a CUDA uint8 tensor of the same length with
+    frame i at the same offset, as [h, w, 3] for rotation 0 and as [w, h, 3] for 90 (np.rot90(x, -1)) and 270 (np.rot90(x, 1)), with
+    channels 0 and 2 exchanged when ``swap_rb``, byte for byte.  Bytes outside the frames are not written (those of a fresh ``out`` are
+    undefined).  ``out``: a tensor like ``packed`` to write into; ``out=packed`` with rotation 0 runs in place.  ValueError before any
+    launch for a host tensor, a wrong dtype or shape, frames that do not fit or overlap, a bad rotation and an ``out`` that does not
+    fit."""
+    import torch
+    rotation = check_rotation(rotation)
+    table = _packed_args(packed, shapes, offsets, "packed")
+    if out is None:
+        out = torch.empty_like(packed)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == packed.device and out.dtype == torch.uint8
+              and tuple(out.shape) == tuple(packed.shape) and out.is_contiguous()):
+        raise ValueError("out must be a contiguous uint8 %r tensor on %s" % (tuple(packed.shape), packed.device))
+    if rotation != 0 and out.data_ptr() == packed.data_ptr() and len(table):
+        raise ValueError("a quarter turn cannot run in place")
+    if len(table) == 0:
+        return out
+    with _lib.on_device(packed):
+        _lib.mixed_check(_lib.mixed_lib().hsefr_mixed_frames_prepare(packed.data_ptr(), out.data_ptr(), int(packed.shape[0]), table.ctypes.data,
+                                                                      len(table), rotation, 1 if swap_rb else 0, _lib.current_stream_ptr()),
+                         "hsefr_mixed_frames_prepare")
+    return out
+
+
+def face_crops_packed(packed, shapes, boxes, out_hw: Tuple[int, int], out=None, offsets=None):
+    """face_crops for frames of DIFFERENT sizes packed in one buffer, in ONE launch (libhsefr_mixed.so): ``packed`` and ``offsets`` as
+    prepare_packed takes them, ``shapes`` the (h, w) of the frames as they stand in the buffer, ``boxes`` host int32 [m, 5] rows
+    (frame, x1, y1, x2, y2) with x2, y2 exclusive, checked against their own frame -> CUDA uint8 [m, oh, ow, 3] with
+    out[i] = cv2.resize(frame[y1:y2, x1:x2], (ow, oh)) byte for byte.  ``out``: a contiguous CUDA uint8 [m, oh, ow, 3] tensor to write
+    into (a slice of a larger batch).  ValueError before any launch for bad arguments."""
+    import torch
+    table = _packed_args(packed, shapes, offsets, "packed")
+    rows = np.ascontiguousarray(boxes, dtype=np.int32)
+    if rows.ndim != 2 or rows.shape[1] != 5:
+        raise ValueError("boxes must be [m, 5] rows of (frame, x1, y1, x2, y2), got shape %r" % (rows.shape,))
+    m, oh, ow = rows.shape[0], int(out_hw[0]), int(out_hw[1])
+    if oh < 1 or ow < 1:
+        raise ValueError("bad output size %d x %d" % (oh, ow))
+    if out is None:
+        out = torch.empty((m, oh, ow, 3), dtype=torch.uint8, device=packed.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == packed.device and out.dtype == torch.uint8
+              and tuple(out.shape) == (m, oh, ow, 3) and out.is_contiguous()):
+        raise ValueError("out must be a contiguous uint8 [%d, %d, %d, 3] tensor on %s" % (m, oh, ow, packed.device))
+    if m == 0:
+        return out
+    with _lib.on_device(packed):
+        _lib.mixed_check(_lib.mixed_lib().hsefr_mixed_face_crops(packed.data_ptr(), int(packed.shape[0]), table.ctypes.data, len(table),
+                                                                  rows.ctypes.data, m, out.data_ptr(), oh, ow, _lib.current_stream_ptr()),
+                         "hsefr_mixed_face_crops")
+    return out
