@@ -180,6 +180,17 @@ MIXED_SIGNATURES = {
     "hsefr_mixed_face_crops": (c_int, [_fp, _i64, c_void_p, c_int, c_void_p, c_int, _fp, c_int, c_int, c_void_p]),
 }
 
+# libhsefr_split.so (include/hsefr_split.h): the same-photo split of every cluster of a clustering in one pass, a seventh library.
+# HSEFR_SPLIT_LIB selects another build.  The offset table is a HOST pointer (c_void_p: a NumPy array's ctypes.data)
+SPLIT_LIB_PATH = os.path.join(_HERE, os.environ.get("HSEFR_SPLIT_LIB", "libhsefr_split.so"))
+_split_lib = None
+SPLIT_SIGNATURES = {
+    "hsefr_split_version": (c_int, []),
+    "hsefr_split_last_error": (c_char_p, []),
+    "hsefr_split_groups": (c_int, [_fp, c_int, c_int, _fp, _fp, _fp, _fp, c_void_p, c_int, _fp, ctypes.c_double, ctypes.c_double, _fp, _fp,
+                                   _fp, c_void_p]),
+}
+
 
 class HsefrError(RuntimeError):
     pass
@@ -347,6 +358,34 @@ def mixed_check(status: int, what: str = "") -> None:
     """check() for a status of libhsefr_mixed.so (its own error string)."""
     if status != OK:
         _raise(status, "%s%s (hsefr_mixed status %d)" % (what + ": " if what else "", mixed_last_error(), status))
+
+
+def split_lib() -> ctypes.CDLL:
+    """Load libhsefr_split.so once (torch first, as lib() does and for the same reason).  Missing is an error: there is no fallback."""
+    global _split_lib
+    if _split_lib is None:
+        import torch  # noqa: F401
+        if not os.path.exists(SPLIT_LIB_PATH):
+            raise ImportError("%s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                              "(hipcc --offload-arch=gfx950). There is no CPU fallback." % SPLIT_LIB_PATH)
+        L = ctypes.CDLL(SPLIT_LIB_PATH)
+        for name, (res, args) in SPLIT_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        _split_lib = L
+    return _split_lib
+
+
+def split_last_error() -> str:
+    s = split_lib().hsefr_split_last_error()
+    return s.decode("utf-8", "replace") if s else ""
+
+
+def split_check(status: int, what: str = "") -> None:
+    """check() for a status of libhsefr_split.so (its own error string)."""
+    if status != OK:
+        _raise(status, "%s%s (hsefr_split status %d)" % (what + ": " if what else "", split_last_error(), status))
 
 
 def last_error() -> str:

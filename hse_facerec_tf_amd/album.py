@@ -40,6 +40,13 @@ MIXED_SIZES_DEFAULT = True
 # 2.60 / 2.48 at rotation 90 (spreads 0.28 / 0.36 / 0.13) and the album 43 against 82 ms (spread 18) -- so the frames and the faces of the
 # mixed-size passes stay on the device where those passes and the device crops or frames are in use
 MIXED_DEVICE_DEFAULT = True
+# perform_clustering(split=...) of both loops when the caller does not say.  The rule, applied by tools/same_photo_split_time.py in the last
+# line of profiles/same_photo_split_time.txt: True if cluster_faces(all_indices=..., split="device") is faster than split="host" by more
+# than the spread between repetitions on 9164 faces of 1680 identities (the gallery-scale case) AND not slower by more than the spread on
+# a 129-face, 6-cluster album; otherwise False.  Measured on an MI355X: 52.5 against 201.9 ms on the gallery (spread 5.5; the split
+# alone 3.5 ms of device time against 158 ms of host time) and 1.12 against 2.05 ms on the album (spread 0.03) -- so the clusters of both
+# loops are split in one device pass
+SPLIT_DEVICE_DEFAULT = True
 
 DECISION_TEMPLATES = ((0.875, 0.125), (0.353, 0.647))      # process_photos.py:209: rows = classes (male, female), columns = (p, 1 - p)
 
@@ -119,13 +126,14 @@ def _fractional_year(mdate) -> float:
 
 # ---- perform_clustering (process_photos.py:45-77) -----------------------------------------------------------------------------------
 def perform_clustering(features, born_years, mdates, all_indices, min_size: int, check_dates: bool = True,
-                       config: AlbumConfig = AlbumConfig(), device=None) -> List[List[int]]:
+                       config: AlbumConfig = AlbumConfig(), device=None, split: Optional[str] = None) -> List[List[int]]:
     """Clusters of face indices: ``clustering.cluster_faces`` at config.distance_threshold with the age term (photo year = the integer
     tm_year of the face's file, as the reference uses) and the same-photo split, then is_good_cluster -- at least ``min_size`` faces
     and, with ``check_dates``, photos that span at least config.min_days_difference days.  ``features``: [n, d] L2-normalised, NumPy
     or a CUDA tensor (it stays on the device); ``mdates``: per FILE, struct_time or POSIX seconds; ``all_indices``: the file of every face.
     Fewer faces than ``min_size`` give [].  cluster_faces' ValueError for a face whose year minus birth year is not positive passes
-    through unchanged.
+    through unchanged.  ``split`` ('host' or 'device': cluster_faces' keyword, where the same-photo split runs) is passed on only when
+    given.
 
     The day span is floor((max - min) / 86400) of the files' POSIX times.  The reference takes both dates through local-time
     ``mktime`` and subtracts the datetimes; the two agree wherever no daylight-saving change lies between the two dates."""
@@ -136,7 +144,8 @@ def perform_clustering(features, born_years, mdates, all_indices, min_size: int,
     dates = [_struct(m) for m in mdates]
     photo_years = [dates[i].tm_year for i in all_indices]
     clusters = clustering.cluster_faces(features, config.distance_threshold, born_years=born_years, photo_years=photo_years,
-                                        all_indices=all_indices, min_cluster_size=min_size, device=device, method=config.method)
+                                        all_indices=all_indices, min_cluster_size=min_size, device=device, method=config.method,
+                                        **({} if split is None else dict(split=split)))
     posix = [calendar.timegm(d) for d in dates]
 
     def is_good_cluster(cluster):
@@ -212,6 +221,16 @@ def _use_mixed_sizes(img_processing, mixed_sizes: Optional[bool]) -> bool:
     return bool(MIXED_SIZES_DEFAULT and getattr(detector, "detect_ragged", None) is not None and getattr(detector, "device_boxes", False))
 
 
+def _use_device_split(device_split: Optional[bool]) -> bool:
+    """(Unasked, the same-photo split follows SPLIT_DEVICE_DEFAULT.)"""
+    return bool(SPLIT_DEVICE_DEFAULT if device_split is None else device_split)
+
+
+def _split_keyword(use_device_split: bool) -> dict:
+    """perform_clustering's ``split`` keyword, present only when the device split is in use."""
+    return dict(split="device") if use_device_split else {}
+
+
 def _use_mixed_device(img_processing, mixed_device: Optional[bool], use_mixed_sizes: bool, use_device_crops: bool, use_device_frames: bool) -> bool:
     """(Unasked, the device stages of the mixed-size passes follow those passes and the device crops or frames they extend, and need a
     detector that detects from a packed buffer.)"""
@@ -233,7 +252,8 @@ def _normalized_on_device(features: Sequence[np.ndarray], device):
 
 def process_video(img_processing, frames: Iterable[np.ndarray], mdate, rotation: int = 0, config: AlbumConfig = AlbumConfig(),
                   max_frames: int = 32, device_crops: Optional[bool] = None, device_frames: Optional[bool] = None,
-                  mixed_sizes: Optional[bool] = None, mixed_device: Optional[bool] = None) -> VideoResult:
+                  mixed_sizes: Optional[bool] = None, mixed_device: Optional[bool] = None,
+                  device_split: Optional[bool] = None) -> VideoResult:
     """process_photos.py:80-156 for the BGR uint8 frames of a video, in grab order.  Whether frame k is processed depends on the faces
     of earlier frames, but only counters divisible by 3 or 5 can ever be: those candidate frames run through
     ``process_images`` in windows of ``max_frames`` (batched detector passes), the rule is then replayed on the host over the face
@@ -243,7 +263,9 @@ def process_video(img_processing, frames: Iterable[np.ndarray], mdate, rotation:
     ``mixed_sizes`` (None: MIXED_SIZES_DEFAULT where the detector has ragged passes): frames whose size no other frame of their
     call shares are detected together (process_images(mixed_sizes=True)); the keyword is passed on only when it is in use.
     ``mixed_device`` (None: MIXED_DEVICE_DEFAULT where those passes and the device crops or frames are in use): those passes' frames and
-    crops stay on the device (process_images(mixed_device=True)); passed on only when it is in use, too."""
+    crops stay on the device (process_images(mixed_device=True)); passed on only when it is in use, too.
+    ``device_split`` (None: SPLIT_DEVICE_DEFAULT): the same-photo split of the clusters runs in one device pass
+    (perform_clustering(split="device")); passed on only when it is in use, too."""
     rotation = preprocess_device.check_rotation(rotation)
     video_year = _fractional_year(mdate)
     use_device = _use_device_crops(img_processing, device_crops)
@@ -284,7 +306,7 @@ def process_video(img_processing, frames: Iterable[np.ndarray], mdate, rotation:
     clusters = []
     if len(indices) >= max(config.min_frames, 1):
         clusters = perform_clustering(_normalized_on_device(features, img_processing.sess.device), born, [mdate] * len(processed), indices,
-                                      config.min_frames, False, config)
+                                      config.min_frames, False, config, **_split_keyword(_use_device_split(device_split)))
     summary = summarize_clusters(clusters, genders, born, features, year=video_year) if clusters else []
     return VideoResult([images[c[0]] for c in clusters], [s.age for s in summary], [s.gender for s in summary], [s.feature for s in summary],
                        len(clusters) > 0, processed, clusters)
@@ -304,7 +326,7 @@ def _as_bgr(photo) -> np.ndarray:
 
 def process_album(img_processing, photos, mdates, videos=(), config: AlbumConfig = AlbumConfig(), max_frames: int = 32,
                   device_crops: Optional[bool] = None, device_frames: Optional[bool] = None, mixed_sizes: Optional[bool] = None,
-                  mixed_device: Optional[bool] = None) -> AlbumResult:
+                  mixed_device: Optional[bool] = None, device_split: Optional[bool] = None) -> AlbumResult:
     """process_photos.py:219-358.  ``photos``: BGR uint8 arrays or paths, ``mdates`` their dates; ``videos``: (frames, mdate) or
     (frames, mdate, rotation) per video, frames as process_video takes them.  Pass 1 runs every photo, pass 2 the quarter turns
     clockwise of the photos without a face, pass 3 the quarter turns counter-clockwise of those still without one (:241-247) -- each pass
@@ -318,7 +340,9 @@ def process_album(img_processing, photos, mdates, videos=(), config: AlbumConfig
     (process_images(mixed_sizes=True)) instead of one by one; it goes to the videos too, and the keyword is passed on only when it is
     in use, so an ``img_processing`` written without it keeps working.  ``mixed_device`` (None: MIXED_DEVICE_DEFAULT where those passes
     and the device crops or frames are in use): the frames and the crops of those passes stay on the device
-    (process_images(mixed_device=True)); it goes to the videos too and is passed on only when it is in use."""
+    (process_images(mixed_device=True)); it goes to the videos too and is passed on only when it is in use.  ``device_split`` (None:
+    SPLIT_DEVICE_DEFAULT): the same-photo split of the clusters runs in one device pass (perform_clustering(split="device")); it goes to
+    the videos too and is passed on only when it is in use."""
     photos = list(photos)
     mdates = list(mdates)
     videos = list(videos)
@@ -331,6 +355,9 @@ def process_album(img_processing, photos, mdates, videos=(), config: AlbumConfig
     mixed = dict(mixed_sizes=True) if _use_mixed_sizes(img_processing, mixed_sizes) else {}
     if _use_mixed_device(img_processing, mixed_device, bool(mixed), use_device, use_frames):
         mixed["mixed_device"] = True
+    use_split = _use_device_split(device_split)       # decided once, for the album's clusters and for its videos'
+    # a video gets the decision itself; the keyword is left out only where it is off and off is what process_video would choose anyway
+    video_split = dict(device_split=use_split) if use_split or SPLIT_DEVICE_DEFAULT else {}
     n_photos = len(photos)
     found = [None] * n_photos          # per photo: (ages, genders, features, crops, has_center_face)
     call = 4 * max_frames              # frames per process_images call: bounds the frame stacks held on the device at one time
@@ -363,7 +390,7 @@ def process_album(img_processing, photos, mdates, videos=(), config: AlbumConfig
     for j, video in enumerate(videos):
         frames, vdate = video[0], video[1]
         v = process_video(img_processing, frames, vdate, video[2] if len(video) > 2 else 0, config, max_frames, use_device, use_frames,
-                          "mixed_sizes" in mixed, "mixed_device" in mixed)
+                          "mixed_sizes" in mixed, "mixed_device" in mixed, **video_split)
         if v.video_has_faces:
             private.append(n_photos + j)
         images.extend(v.cluster_images)
@@ -376,7 +403,7 @@ def process_album(img_processing, photos, mdates, videos=(), config: AlbumConfig
     clusters = []
     if len(all_indices) >= max(config.min_photos, 1):
         clusters = perform_clustering(_normalized_on_device(features, img_processing.sess.device), born, all_dates, all_indices,
-                                      config.min_photos, True, config)
+                                      config.min_photos, True, config, **_split_keyword(use_split))
     summary = summarize_clusters(clusters, genders, born, features) if clusters else []
     private_photos, public_photos = split_private_public(clusters, all_indices, private, len(all_dates))
     return AlbumResult(clusters, ['male' if s.ds_gender == 0 else 'female' for s in summary], [int(s.born_year) for s in summary],

@@ -5,7 +5,8 @@ The reference groups faces with ``hac.linkage(squareform(D), 'single')`` + ``fcl
 (facial_clustering.py:214-285, process_photos.py:45-77, facial_clustering_test.py:362-414).  Single linkage is the minimum spanning
 tree of the distance graph, which libhsefr builds by Boruvka rounds without an N x N matrix (ops.single_linkage_edges,
 csrc/linkage.hip).  Here the tree becomes scipy's linkage matrix Z, flat cuts of Z cost O(n) each (a threshold sweep pays for one
-tree), and the reference's same-photo split (complete linkage on small per-cluster matrices) runs on the host in NumPy.
+tree), and the reference's same-photo split (complete linkage on small per-cluster matrices) runs on the host in NumPy or, with
+``split="device"``, for all clusters in one device pass (split_same_photo, ops.split_groups, csrc/group_split.hip).
 The study's other methods (facial_clustering_test.py:513-514: 'average', 'complete', 'weighted') need the whole matrix: libhsefr
 merges reciprocal nearest neighbours round by round on an fp64 n x n device matrix (ops.hier_linkage_merges, csrc/hier_linkage.hip).
 The reference's third branch, scikit-learn's DBSCAN on the precomputed matrix (facial_clustering.py:260-265), runs on the device with
@@ -473,6 +474,77 @@ def _split_groups(groups, all_indices, n, sub_dist) -> List[np.ndarray]:
     return clusters
 
 
+# ---- the same-photo split of every cluster in one device pass ----------------------------------------------------------
+SPLIT_CHOICES = ("host", "device")
+
+
+def _check_split(split):
+    if split not in SPLIT_CHOICES:
+        raise ValueError("split %r is not supported; the choices are %s" % (split, ", ".join(SPLIT_CHOICES)))
+
+
+def group_table(labels):
+    """The clusters of a labelling as ops.split_groups takes them -> (members int32 [n], offsets int64 [groups + 1]): group g holds the
+    items members[offsets[g]:offsets[g + 1]], ascending, and the groups are ordered by their smallest member (_groups' order).  Labels
+    are compared for equality only; they need not be dense.  Pure NumPy."""
+    labels = np.asarray(labels).reshape(-1)
+    n = len(labels)
+    if n == 0:
+        return np.zeros(0, dtype=np.int32), np.zeros(1, dtype=np.int64)
+    _, first, inverse = np.unique(labels, return_index=True, return_inverse=True)
+    rank = np.empty(len(first), dtype=np.int64)
+    rank[np.argsort(first, kind="stable")] = np.arange(len(first))      # a group's place = the place of its smallest member
+    group = rank[inverse.reshape(-1)]
+    members = np.argsort(group, kind="stable").astype(np.int32)
+    offsets = np.zeros(len(first) + 1, dtype=np.int64)
+    np.cumsum(np.bincount(group, minlength=len(first)), out=offsets[1:])
+    return members, offsets
+
+
+def split_same_photo(labels, all_indices, features=None, dist_matrix=None, born_years=None, photo_years=None,
+                     device=None) -> List[np.ndarray]:
+    """The same-photo split (facial_clustering.py:250-261) of every cluster of ``labels`` in one device pass (ops.split_groups) ->
+    the clusters as _split_groups returns them: cluster by cluster in _groups' order, each one's parts in order of their first face.
+    ``all_indices`` is the photo of every face.  Exactly one source: ``features`` [n, d] with optional born / photo years -- the
+    distances are then w(i,j), the ones the linkage itself uses -- or ``dist_matrix`` [n, n].  SAME_PHOTO_PENALTY between two faces of
+    one photo, cut at half of it.  No faces give []."""
+    if (features is None) == (dist_matrix is None):
+        raise ValueError("split_same_photo: pass exactly one of features and dist_matrix")
+    if len(np.asarray(labels).reshape(-1)) == 0 and len(np.asarray(all_indices).reshape(-1)) == 0:
+        return []
+    if features is not None:
+        x, born, year = _features(features, born_years, photo_years, device, finite=False)
+        source = dict(x=x, born=born, year=year)
+    else:
+        if born_years is not None or photo_years is not None:
+            raise ValueError("split_same_photo: the age term belongs to the features path")
+        source = dict(dense=_dist_matrix(dist_matrix, device))
+    return _split_on_device(labels, all_indices, **source)
+
+
+def _split_on_device(labels, all_indices, **source) -> List[np.ndarray]:
+    """split_same_photo on ops' source arguments (x, born, year or dense), already checked and on the device."""
+    from . import ops
+    import torch
+    labels = np.asarray(labels).reshape(-1)
+    n = len(labels)
+    photo = np.asarray(all_indices).reshape(-1)
+    if len(photo) != n:
+        raise ValueError("%d faces, %d photo indices" % (n, len(photo)))
+    data = source["x"] if source.get("x") is not None else source["dense"]
+    if data.shape[0] != n:
+        raise ValueError("%d labels for %d faces" % (n, data.shape[0]))
+    dev = data.device
+    members, offsets = group_table(labels)
+    codes = np.unique(photo, return_inverse=True)[1].reshape(-1).astype(np.int32)      # photos are compared for equality only
+    sub, _ = ops.split_groups(torch.from_numpy(members).to(dev), offsets, torch.from_numpy(codes).to(dev),
+                              penalty=SAME_PHOTO_PENALTY, cut=SAME_PHOTO_PENALTY / 2, return_stats=True, **source)
+    sub = sub.cpu().numpy().astype(np.int64)
+    key = np.repeat(np.arange(len(offsets) - 1, dtype=np.int64), np.diff(offsets)) * (int(sub.max()) + 1) + sub
+    order = np.argsort(key, kind="stable")
+    return np.split(members[order].astype(np.int64), np.flatnonzero(np.diff(key[order])) + 1)
+
+
 def _finish(clusters: List[np.ndarray], min_size: int = 1) -> List[List[int]]:
     out = [sorted(int(i) for i in c) for c in clusters if len(c) >= min_size]
     out.sort(key=lambda c: (-len(c), c[0]))
@@ -480,7 +552,7 @@ def _finish(clusters: List[np.ndarray], min_size: int = 1) -> List[List[int]]:
 
 
 def get_facial_clusters(dist_matrix, distanceThreshold=1, all_indices=None, no_images_in_cluster=1, device=None,
-                        method="single") -> List[List[int]]:
+                        method="single", split="host") -> List[List[int]]:
     """The scipy branch of facial_clustering.get_facial_clusters (:243-261) with the linkage on the GPU (dense fp64 path) -- single
     linkage by default, or ``method`` 'average' / 'complete' / 'weighted' (the module global clusteringMethod the study sets):
     clusters of faces joined at distances <= distanceThreshold; with ``all_indices`` (the photo of every face) each cluster is split so
@@ -492,8 +564,12 @@ def get_facial_clusters(dist_matrix, distanceThreshold=1, all_indices=None, no_i
     no_images_in_cluster, noise dropped, ``all_indices`` accepted and ignored, the same order; one face gives scikit-learn's answer.
     ``method`` 'rankorder' is the rank-order branch (:229-239): rank_order_dense with distanceThreshold = the study's pair (norm, rank),
     or a scalar norm threshold with the reference's default rank threshold 14; clusters of at least two faces in the reference's order;
-    ``all_indices`` and ``no_images_in_cluster`` accepted and ignored, as that branch does; one face gives []."""
+    ``all_indices`` and ``no_images_in_cluster`` accepted and ignored, as that branch does; one face gives [].
+    ``split`` 'host' (the default) runs the same-photo split cluster by cluster in NumPy; 'device' runs it for all clusters in one
+    device pass (split_same_photo) on the same matrix, with the same clusters, ties included.  Any other value raises ValueError before
+    any device work; where ``all_indices`` is ignored ('dbscan', 'rankorder'), so is ``split``."""
     _check_method(method, CLUSTER_METHODS)
+    _check_split(split)
     if method == "dbscan":
         return _finish(_clusters(dbscan_dense(dist_matrix, distanceThreshold, no_images_in_cluster, device)[1]))
     if method == "rankorder":
@@ -502,6 +578,9 @@ def get_facial_clusters(dist_matrix, distanceThreshold=1, all_indices=None, no_i
     n = D.shape[0]
     if n == 1:
         return [[0]]
+    if split == "device" and all_indices is not None:
+        Dd = _dist_matrix(D, device)                 # one upload for the linkage and the split
+        return _finish(_split_on_device(fcluster_distance(_linkage(method, n, dense=Dd), distanceThreshold), all_indices, dense=Dd))
     groups = _groups(fcluster_distance(linkage_dense(D, method, device), distanceThreshold))
     if all_indices is None:
         return _finish(groups)
@@ -509,7 +588,7 @@ def get_facial_clusters(dist_matrix, distanceThreshold=1, all_indices=None, no_i
 
 
 def cluster_faces(features, distance_threshold: float, born_years=None, photo_years=None, all_indices=None,
-                  min_cluster_size: int = 1, device=None, method: str = "single") -> List[List[int]]:
+                  min_cluster_size: int = 1, device=None, method: str = "single", split: str = "host") -> List[List[int]]:
     """perform_clustering (process_photos.py:45-77) without the date rule, from the features: single linkage on the GPU with no N x N
     matrix (or ``method`` 'average' / 'complete' / 'weighted' on an fp64 device matrix; see linkage), the age term when born / photo
     years are given, the same-photo split on each cluster's own distances (its rows through
@@ -518,22 +597,31 @@ def cluster_faces(features, distance_threshold: float, born_years=None, photo_ye
     dbscan with eps = distance_threshold and min_samples = min_cluster_size, noise dropped, then the clusters shorter than
     min_cluster_size (a border point claimed by an earlier cluster can leave one short); ``all_indices`` is ignored.  ``method``
     'rankorder' is rank_order with distance_threshold = (norm, rank) or a scalar norm threshold (rank threshold 14): clusters of at least
-    two faces; ``all_indices`` and ``min_cluster_size`` are ignored, as the reference's branch ignores them."""
+    two faces; ``all_indices`` and ``min_cluster_size`` are ignored, as the reference's branch ignores them.
+    ``split`` 'host' (the default) is the same-photo split described above; 'device' runs it for all clusters in one device pass
+    (split_same_photo) and splits on w(i,j), the distance the clusters were formed by (csrc/linkage_scan.h's feat_tile, age term
+    included), where the host split recomputes its distances another way.  Both are fp32 distances of the same features: the two
+    choices can differ only where two candidate merges of a cluster are within rounding of each other.  Any other value raises
+    ValueError before any device work; where ``all_indices`` is ignored ('dbscan', 'rankorder'), so is ``split``."""
     from . import ops
     _check_method(method, CLUSTER_METHODS)
+    _check_split(split)
     if method == "dbscan":
         _, labels = dbscan(features, distance_threshold, min_cluster_size, born_years, photo_years, device)
         return _finish(_clusters(labels), min_cluster_size)
     if method == "rankorder":
         return rank_order(features, *_rank_order_threshold_pair(distance_threshold), born_years=born_years, photo_years=photo_years,
                           device=device)[0]
-    x = _features(features, born_years, photo_years, device, finite=False)[0]
+    x, born, year = _features(features, born_years, photo_years, device, finite=False)
     n = x.shape[0]
     by, yr = _age_arrays(born_years, photo_years, n)
     if n == 1:
         return _finish([np.zeros(1, dtype=np.int64)], min_cluster_size)
     Z = linkage_single(x, by, yr) if method == "single" else linkage(x, method, by, yr)
-    groups = _groups(fcluster_distance(Z, distance_threshold))
+    labels = fcluster_distance(Z, distance_threshold)
+    if split == "device" and all_indices is not None:
+        return _finish(_split_on_device(labels, all_indices, x=x, born=born, year=year), min_cluster_size)
+    groups = _groups(labels)
     if all_indices is None:
         return _finish(groups, min_cluster_size)
     import torch

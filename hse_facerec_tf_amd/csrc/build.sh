@@ -5,7 +5,8 @@
 # libhsefr_forest.so (include/hsefr_forest.h: the random forest classifier, a fourth library for the same reason) and
 # libhsefr_ragged.so (include/hsefr_ragged.h: the detector pass over frames of different sizes, a fifth library for the same reason) and
 # libhsefr_mixed.so (include/hsefr_mixed.h: the frames of such a pass turned, converted and cropped on the device, a sixth library for the
-# same reason).
+# same reason) and libhsefr_split.so (include/hsefr_split.h: the same-photo split of every cluster of a clustering in one pass, a seventh
+# library for the same reason).
 #   HSEFR_DEV=1 build.sh   builds libhsefr_dev.so instead: the same sources with -DHSEFR_DEV (tuning knobs as run-time
 #                          variables, hsefr_debug_*, the calibration kernels of devtools.hip) -- for tools/kbench.py only.
 set -euo pipefail
@@ -42,6 +43,11 @@ RAGGED_FLAGS="$FLAGS $DEVICE_STRIP"
 # their bits.  -ffp-contract=off: the crop taps are two separately rounded operations, as in album.hip
 MIXED_SRCS="mixed_frames.hip"
 MIXED_FLAGS="$FLAGS $DEVICE_STRIP -ffp-contract=off"
+# libhsefr_split.so (include/hsefr_split.h: the same-photo split of every cluster of a clustering in one pass): a seventh library, built
+# as the sixth.  The flags are libhsefr.so's own, as the fifth's: group_split.hip compiles the clustering distance that library compiles
+# (linkage_scan.h's feat_tile over mfma_dot.h) and must give its bits
+SPLIT_SRCS="group_split.hip"
+SPLIT_FLAGS="$FLAGS $DEVICE_STRIP"
 LINT=1
 HOST_STRIP=0
 HOST_SIZE_FLAGS=""
@@ -201,4 +207,23 @@ if [ "$LINT" = "1" ]; then
   /opt/rocm/lib/llvm/bin/llvm-strip --strip-all -w --keep-symbol='_ZN*_kernel*' --keep-symbol='!*__device_stub__*' "$MIXED_OUT"
   python3 ../../tools/isa_lint.py "$MIXED_OUT"
   echo "built $(realpath $MIXED_OUT)"
+  # the seventh library: built, stripped and linted as the sixth; stale against the headers it shares with libhsefr.so too
+  SPLIT_OUT=../libhsefr_split.so
+  SPLIT_OBJS=""
+  for s in $SPLIT_SRCS; do
+    o="$BUILD/${s%.hip}.o"
+    stale=0
+    for dep in "$s" linkage_scan.h mfma_dot.h common.h ../../include/hsefr.h ../../include/hsefr_split.h build.sh; do
+      if [ ! -f "$o" ] || [ "$dep" -nt "$o" ]; then stale=1; fi
+    done
+    if [ "$stale" = 1 ]; then
+      rm -f "$o"
+      hipcc $SPLIT_FLAGS -Xarch_host -Os ${HSEFR_EXTRA_FLAGS:-} -c "$s" -o "$o"
+    fi
+    SPLIT_OBJS="$SPLIT_OBJS $o"
+  done
+  hipcc $LINK -shared -fPIC -o "$SPLIT_OUT" $SPLIT_OBJS
+  /opt/rocm/lib/llvm/bin/llvm-strip --strip-all -w --keep-symbol='_ZN*_kernel*' --keep-symbol='!*__device_stub__*' "$SPLIT_OUT"
+  python3 ../../tools/isa_lint.py "$SPLIT_OUT"
+  echo "built $(realpath $SPLIT_OUT)"
 fi

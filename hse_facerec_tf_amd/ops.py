@@ -4,6 +4,7 @@ and by the identification stage; the engine calls the same launchers internally.
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import Optional, Tuple
 
 import numpy as np
@@ -1264,6 +1265,54 @@ def rank_order_labels(x=None, dense=None, born=None, year=None, norm_threshold=0
     _lib.check(_lib.lib().hsefr_rank_order_sweep(*src, thr, len(pairs), labels.data_ptr(), iters, _lib.current_stream_ptr()),
                "hsefr_rank_order")
     return (labels, list(iters)) if sweep else (labels[0], int(iters[0]))
+
+
+SPLIT_WAVE_MAX, SPLIT_LDS_MAX = 32, 128      # HSEFR_SPLIT_WAVE_MAX / _LDS_MAX: the largest group of the two LDS chain classes
+SPLIT_STATS = ("early", "lds", "global", "merges", "bad_members")      # HSEFR_SPLIT_STAT_*
+
+
+@_device_guarded
+def split_groups(members, offsets, photo, x=None, dense=None, born=None, year=None, penalty=100.0, cut=50.0, return_distances=False,
+                 return_stats=False):
+    """Complete linkage inside every group of points, cut at ``cut``, with ``penalty`` between two points of one photo
+    (hsefr_split_groups, libhsefr_split.so): the reference's same-photo split for all clusters of a clustering in one call ->
+    sublabel int32 CUDA tensor [len(members)]: sublabel[offsets[g] + a] is clustering.complete_linkage_labels(P_g, cut)[a] for the matrix
+    P_g[a][b] = w(m_a, m_b) + penalty * [photo[m_a] == photo[m_b]] of group g's members m = members[offsets[g]:offsets[g + 1]], in the
+    order given.  members int32 CUDA tensor; offsets a HOST int64 sequence [groups + 1] from 0, strictly increasing, to len(members)
+    (clustering.group_table makes both); photo int32 CUDA tensor [n].  The sources are hier_linkage_merges': x [n,d] float32 features
+    (zero columns pad d to a multiple of 8) with optional born / year float32 [n] -- w is then the distance the clusterings use, feat_tile's,
+    widened to fp64 -- or dense [n,n] float64 read as its upper triangle and left as it is.  With ``return_distances`` also the float64
+    CUDA tensor of every group's P as first built, row-major, group after group (diagonals unspecified); with ``return_stats`` also the
+    call's five counts as a host int64 array in SPLIT_STATS order, read back (the one synchronisation), and a member outside [0, n)
+    raises ValueError then.  Without it the call is asynchronous on the current stream and such a member's group comes back as -1."""
+    torch = _lib.require_gpu()
+    x, n, dev, src = _dist_source("split_groups", x, dense, born, year)
+    _typed(members, torch.int32, "members", "int32")
+    _typed(photo, torch.int32, "photo", "int32")
+    off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    if members.dim() != 1 or photo.dim() != 1 or photo.shape[0] != n:
+        raise ValueError("split_groups: members [m] and photo [n = %d] are vectors, got %r and %r" % (n, tuple(members.shape), tuple(photo.shape)))
+    if len(off) < 1 or int(off[-1]) != members.shape[0] or (members.shape[0] == 0 and len(off) != 1):
+        raise ValueError("split_groups: %d offsets ending at %s for %d members" % (len(off), off[-1] if len(off) else None, members.shape[0]))
+    if not (math.isfinite(penalty) and penalty >= 0 and math.isfinite(cut)):
+        raise ValueError("split_groups: penalty=%r must be finite and >= 0, cut=%r finite" % (penalty, cut))
+    m = members.shape[0]
+    sublabel = torch.empty((m,), dtype=torch.int32, device=dev)
+    counts = np.diff(off)
+    dist = torch.empty((int((counts * counts).sum()),), dtype=torch.float64, device=dev) if return_distances else None
+    stats = torch.empty((len(SPLIT_STATS),), dtype=torch.int64, device=dev) if return_stats else None
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    if m:                                             # (no members: no groups, nothing to do)
+        _lib.split_check(_lib.split_lib().hsefr_split_groups(*src, members.data_ptr(), off.ctypes.data, len(off) - 1, photo.data_ptr(),
+                                                             float(penalty), float(cut), sublabel.data_ptr(), ptr(dist), ptr(stats),
+                                                             _lib.current_stream_ptr()), "hsefr_split_groups")
+    out = (sublabel,) + ((dist,) if return_distances else ())
+    if return_stats:
+        host = stats.cpu().numpy() if m else np.zeros(len(SPLIT_STATS), dtype=np.int64)
+        if host[4]:
+            raise ValueError("split_groups: %d member(s) outside [0, %d)" % (int(host[4]), n))
+        out += (host,)
+    return out if len(out) > 1 else sublabel
 
 
 SCORES_MAX_N = 65536       # HSEFR_SCORES_MAX_N
