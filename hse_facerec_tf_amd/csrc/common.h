@@ -109,6 +109,7 @@ __device__ __forceinline__ void bstore16_welded(hsefr_f32x4 v, __amdgpu_buffer_r
 // The same with the non-temporal hint: for a layer's output that nothing re-reads before the next launch streams it in.  Measured per
 // kernel in the network (round 5): the epilogue GEMMs' split rows -2.5 us per layer; the fused blocks' and the pointwise GEMMs' outputs
 // must NOT have it (the depthwise layers behind them read more slowly: +7 / +3 us), nor the bf16 ResNet kernels' (-5 % on the forward).
+// Round 10 (lesson 76, the edges of the three fused launches): the stride-2 block's output WITH it, -4.5 us over the block and its reader.
 __device__ __forceinline__ void bstore16_welded_nt(hsefr_f32x4 v, __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
     asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen nt\n\ts_nop 1" ::"v"(v), "v"(voff), "s"(r), "s"(soff) : "memory");
 }
@@ -116,7 +117,6 @@ __device__ __forceinline__ void bstore16(hsefr_f32x4 v, __amdgpu_buffer_rsrc_t r
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(hsefr_u32x4, v), r, voff, soff, 0);
     hsefr_store_guard();
 }
-
 // fp32 -> bf16, round to nearest even, on gfx950's own instruction (v_cvt_pk_bf16_f32: two values per instruction).  Until round 5
 // every bf16 epilogue rounded with integer arithmetic on the bits -- (u + 0x7FFF + ((u >> 16) & 1)) >> 16: four vector
 // instructions per value, and the bf16 convolutions turned out to be EPILOGUE-bound where their K loop is short (the 1x1

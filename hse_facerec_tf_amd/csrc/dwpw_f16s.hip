@@ -326,6 +326,14 @@ __global__ __launch_bounds__(256 + 64 * (BN == 256 ? 8 : 4), BN == 256 ? 1 : 2) 
                      "s"(r), "s"(__builtin_amdgcn_readfirstlane(soff))
                      : "memory", "m0");   // issued from asm so that hipcc does not drain vmcnt before every LDS read
     };
+    // the same piece with the streaming hint: the 16 x 8 patch's halo pieces (the strip tiling).  This launch is the last reader of its
+    // input, and with `nt` the bytes it fetches leave the Infinity Cache to the tensor it writes: at 24 x 24 x 256, batch 256, the block
+    // itself + 4 us and the depthwise layer behind it - 9.5 us (lesson 76)
+    auto piece_nt = [&](const __amdgpu_buffer_rsrc_t& r, unsigned lds_addr, unsigned voff, unsigned soff) {
+        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen nt lds" ::"s"(__builtin_amdgcn_readfirstlane(lds_addr)), "v"(voff),
+                     "s"(r), "s"(__builtin_amdgcn_readfirstlane(soff))
+                     : "memory", "m0");
+    };
     // halo DMA duty: producers.  (Measured both ways with in-kernel stamps: the patch time does not change, the waiting moves to
     // whichever waves issue the vector-memory instructions.  Neither did keeping all the weight rows of the 128-channel block
     // resident in LDS (-29 % instructions) nor slicing the epilogue's stores over the next patch's steps: at 611 MB per
@@ -366,7 +374,10 @@ __global__ __launch_bounds__(256 + 64 * (BN == 256 ? 8 : 4), BN == 256 ? 1 : 2) 
         const unsigned base = lds0 + (pf_step % HS) * HALO_B;
         const unsigned so = (unsigned)pf_kc * 128u;
 #pragma unroll
-        for (int j = 0; j < HPW; ++j) piece(rx, base + (hw * HPW + j) * 1024, hv[j], so);
+        for (int j = 0; j < HPW; ++j) {
+            if (TW == 8) piece_nt(rx, base + (hw * HPW + j) * 1024, hv[j], so);
+            else piece(rx, base + (hw * HPW + j) * 1024, hv[j], so);
+        }
         ++pf_step;
         if (++pf_kc == KT) {
             pf_kc = 0;
@@ -830,8 +841,9 @@ __global__ __launch_bounds__(512, 1) void dwpws2_f16s_kernel(DwPwSParams p) {
                             f32x4 o;
 #pragma unroll
                             for (int e = 0; e < 4; ++e) o[e] = apply_act<ACT>(z[e]);
-                            // (no non-temporal hint: the depthwise layer behind this one reads faster with the tensor in the caches, lesson 60)
-                            bstore16_welded(o, ry, sv[mi][hb][i], __builtin_amdgcn_readfirstlane((unsigned)(ni * 32) * 4u));
+                            // (with the non-temporal hint: this launch 92 -> 87 us at 48 x 48 -> 24 x 24, batch 256, the block behind it
+                            // + 0.6, the depthwise layer behind that one - 3.5: lesson 76.  Lesson 60's "no hint" was the old two-launch plan's)
+                            bstore16_welded_nt(o, ry, sv[mi][hb][i], __builtin_amdgcn_readfirstlane((unsigned)(ni * 32) * 4u));
                         }
                     }
             }

@@ -149,9 +149,9 @@ __global__ __launch_bounds__(512, 1) void pwblk_stream_f16s_kernel(PwBlkParams p
         Cur cl;
         cl.i = 0;
         open(cl);
-        auto gload = [&]() {                  // the load cursor's row
+        auto gload = [&]() {                  // the load cursor's row; past the last item (the three drain steps) nothing is fetched
             const int q = cl.r0 - 1 + cl.s;
-            const bool ok = q >= 0 && q < H;
+            const bool ok = q >= 0 && q < H && cl.i < nitem;
             const unsigned so = __builtin_amdgcn_readfirstlane(ok ? (unsigned)((cl.n * H + q) * W) * (unsigned)(PB_CIN * 4) : 0u);
 #pragma unroll
             for (int j = 0; j < 3; ++j) xr[j] = bload16(rx, ok ? xv[j] : OOB, so);
