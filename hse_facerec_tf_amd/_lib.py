@@ -191,6 +191,15 @@ SPLIT_SIGNATURES = {
                                    _fp, c_void_p]),
 }
 
+# libhsefr_geom.so (include/hsefr_geom.h): centroid, median and Ward linkage, an eighth library.  HSEFR_GEOM_LIB selects another build
+GEOM_LIB_PATH = os.path.join(_HERE, os.environ.get("HSEFR_GEOM_LIB", "libhsefr_geom.so"))
+_geom_lib = None
+GEOM_SIGNATURES = {
+    "hsefr_geom_version": (c_int, []),
+    "hsefr_geom_last_error": (c_char_p, []),
+    "hsefr_geom_linkage": (c_int, [_fp, c_int, c_int, _fp, _fp, _fp, c_int, _fp, _fp, _fp, _fp, _fp, _fp, c_void_p]),
+}
+
 
 class HsefrError(RuntimeError):
     pass
@@ -386,6 +395,34 @@ def split_check(status: int, what: str = "") -> None:
     """check() for a status of libhsefr_split.so (its own error string)."""
     if status != OK:
         _raise(status, "%s%s (hsefr_split status %d)" % (what + ": " if what else "", split_last_error(), status))
+
+
+def geom_lib() -> ctypes.CDLL:
+    """Load libhsefr_geom.so once (torch first, as lib() does and for the same reason).  Missing is an error: there is no fallback."""
+    global _geom_lib
+    if _geom_lib is None:
+        import torch  # noqa: F401
+        if not os.path.exists(GEOM_LIB_PATH):
+            raise ImportError("%s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                              "(hipcc --offload-arch=gfx950). There is no CPU fallback." % GEOM_LIB_PATH)
+        L = ctypes.CDLL(GEOM_LIB_PATH)
+        for name, (res, args) in GEOM_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        _geom_lib = L
+    return _geom_lib
+
+
+def geom_last_error() -> str:
+    s = geom_lib().hsefr_geom_last_error()
+    return s.decode("utf-8", "replace") if s else ""
+
+
+def geom_check(status: int, what: str = "") -> None:
+    """check() for a status of libhsefr_geom.so (its own error string)."""
+    if status != OK:
+        _raise(status, "%s%s (hsefr_geom status %d)" % (what + ": " if what else "", geom_last_error(), status))
 
 
 def last_error() -> str:

@@ -17,6 +17,11 @@ The study's statistics and its threshold selection (get_clustering_statistics, t
 facial_clustering_test.py:416-499) score a whole sweep on the device: one clustering per album, every threshold's labels cut there
 (ops.flat_cuts), every row scored by one call and read back once (ops.partition_scores, csrc/partition_scores.hip): clustering_scores,
 threshold_sweep, select_threshold.
+The last three of the study's seven scipy methods ('centroid', 'median', 'ward', facial_clustering_test.py:514) have entry points of
+their own -- linkage_geometric, linkage_geometric_dense, cluster_faces_geometric, get_facial_clusters_geometric -- over
+ops.geom_linkage_merges (libhsefr_geom.so): Ward by the same rounds with its three-term update (csrc/hier_linkage.hip compiled a second
+time), centroid and median, whose trees have inversions, by a closest-pair engine that merges the least pair step by step
+(csrc/geom_linkage.hip).  threshold_sweep scores them as it scores the other linkages.
 No CPU fallback: the functions that compute distances raise without the library or a GPU.
 """
 from __future__ import annotations
@@ -29,11 +34,13 @@ from typing import List, NamedTuple, Optional, Sequence
 import numpy as np
 
 SAME_PHOTO_PENALTY = 100.0      # facial_clustering.py:254 (inf_dist)
-# scipy's reducible methods with a per-round Lance-Williams update; 'centroid' and 'median' are not reducible (their trees can have
-# inversions), and 'ward''s update of two clusters merged in the same round does not factor into two-way steps
+# scipy's reducible methods with a two-term per-round Lance-Williams update (csrc/hier_linkage.hip as libhsefr.so compiles it).
+# 'centroid' and 'median' are not reducible (their trees can have inversions) and 'ward''s update has a third term: GEOMETRIC_METHODS
 LINKAGE_METHODS = ("single", "average", "complete", "weighted")
 # get_facial_clusters and cluster_faces also take the reference's DBSCAN and rank-order branches
 CLUSTER_METHODS = LINKAGE_METHODS + ("dbscan", "rankorder")
+# the other three of scipy's seven: squared-Euclidean ("geometric") updates.  Entry points of their own: linkage_geometric and its kin
+GEOMETRIC_METHODS = ("centroid", "median", "ward")
 RANK_ORDER_NORM_THRESHOLD = 0.9     # find_clusters' defaults (facial_clustering_test.py:193)
 RANK_ORDER_RANK_THRESHOLD = 14
 
@@ -70,6 +77,19 @@ def linkage_from_merges(merge_a, merge_b, merge_h, merge_round, n: int) -> np.nd
         raise ValueError("a hierarchy of %d points has %d merges, got %d" % (n, n - 1, len(a)))
     lo, hi = np.minimum(a, b), np.maximum(a, b)
     return _join(lo, hi, h, np.lexsort((lo, r, h)), n, "linkage")
+
+
+def linkage_from_sequence(merge_a, merge_b, merge_h, n: int) -> np.ndarray:
+    """scipy-format Z from the n - 1 merge records of a sequential algorithm (ops.geom_linkage_merges, 'centroid' / 'median'): record k
+    joined the clusters of points merge_a[k] and merge_b[k] at merge_h[k], and the records are taken in the order given -- they are
+    not sorted, since the heights of these trees may fall (inversions).  Joined by union-find as in linkage_from_edges: row k =
+    [lower id, higher id, height, size]."""
+    a = np.asarray(merge_a, dtype=np.int64)
+    b = np.asarray(merge_b, dtype=np.int64)
+    h = np.asarray(merge_h, dtype=np.float64)
+    if not (len(a) == len(b) == len(h) == n - 1):
+        raise ValueError("a hierarchy of %d points has %d merges, got %d" % (n, n - 1, len(a)))
+    return _join(np.minimum(a, b), np.maximum(a, b), h, np.arange(n - 1), n, "linkage")
 
 
 def _join(lo, hi, h, order, n, what) -> np.ndarray:
@@ -175,6 +195,9 @@ def _linkage(method, n, **source):
     from . import ops
     if method == "single":
         return linkage_from_edges(*(t.cpu().numpy() for t in ops.single_linkage_edges(**source)), n)
+    if method in GEOMETRIC_METHODS:
+        records = [t.cpu().numpy() for t in ops.geom_linkage_merges(method=method, **source)]
+        return linkage_from_merges(*records, n) if method == "ward" else linkage_from_sequence(*records[:3], n)
     return linkage_from_merges(*(t.cpu().numpy() for t in ops.hier_linkage_merges(method=method, **source)), n)
 
 
@@ -206,6 +229,28 @@ def linkage_dense(dist_matrix, method, device=None) -> np.ndarray:
     linkage_single_dense, 'average' / 'complete' / 'weighted' run on an fp64 device copy with scipy's Lance-Williams updates (complete
     linkage's heights are scipy's bit for bit; the two means agree to rounding)."""
     _check_method(method)
+    D = _dist_matrix(dist_matrix, device)
+    return _linkage(method, D.shape[0], dense=D)
+
+
+def linkage_geometric(features, method, born_years=None, photo_years=None, device=None) -> np.ndarray:
+    """hac.linkage(squareform(D), method) for ``method`` 'centroid', 'median' or 'ward' and D = the feature distance of
+    perform_clustering (process_photos.py:45-56) from the features [n, d] on the GPU: D is built as an fp64 device matrix (fp32
+    distances widened, 8 n^2 bytes), the matrix linkage builds.  Ward merges reciprocal nearest neighbours round by round; centroid
+    and median merge the closest pair step by step, and their Z may have inversions (heights that fall).  scipy's update rules
+    operation by operation, except that a negative radicand -- rounding, or the age term, which is not Euclidean -- gives 0 where
+    scipy gives NaN.  Non-finite features raise ValueError; so does any other method, before any device work.  One point gives a
+    (0, 4) array."""
+    _check_method(method, GEOMETRIC_METHODS)
+    x, born, year = _features(features, born_years, photo_years, device, finite=True)
+    return _linkage(method, x.shape[0], x=x, born=born, year=year)
+
+
+def linkage_geometric_dense(dist_matrix, method, device=None) -> np.ndarray:
+    """hac.linkage(squareform(dist_matrix, checks=False), method) for ``method`` 'centroid', 'median' or 'ward', the matrix read as its
+    upper triangle, on an fp64 device copy: centroid's and median's Z are scipy's bit for bit where the distances have no ties, Ward's
+    has scipy's clusters and its heights to rounding.  A negative radicand gives 0 where scipy gives NaN (see linkage_geometric)."""
+    _check_method(method, GEOMETRIC_METHODS)
     D = _dist_matrix(dist_matrix, device)
     return _linkage(method, D.shape[0], dense=D)
 
@@ -574,17 +619,34 @@ def get_facial_clusters(dist_matrix, distanceThreshold=1, all_indices=None, no_i
         return _finish(_clusters(dbscan_dense(dist_matrix, distanceThreshold, no_images_in_cluster, device)[1]))
     if method == "rankorder":
         return rank_order_dense(dist_matrix, *_rank_order_threshold_pair(distanceThreshold), device=device)[0]
+    return _matrix_clusters(dist_matrix, distanceThreshold, all_indices, device, method, split)
+
+
+def _matrix_clusters(dist_matrix, distanceThreshold, all_indices, device, method, split) -> List[List[int]]:
+    """get_facial_clusters behind its argument checks for a linkage ``method``: the tree cut at distanceThreshold, the same-photo
+    split, the order.  get_facial_clusters_geometric ends here too."""
     D = _check_dist_matrix(np.asarray(dist_matrix, dtype=np.float64))
     n = D.shape[0]
     if n == 1:
         return [[0]]
+    Dd = _dist_matrix(D, device)                     # one upload for the linkage and the split
+    labels = fcluster_distance(_linkage(method, n, dense=Dd), distanceThreshold)
     if split == "device" and all_indices is not None:
-        Dd = _dist_matrix(D, device)                 # one upload for the linkage and the split
-        return _finish(_split_on_device(fcluster_distance(_linkage(method, n, dense=Dd), distanceThreshold), all_indices, dense=Dd))
-    groups = _groups(fcluster_distance(linkage_dense(D, method, device), distanceThreshold))
+        return _finish(_split_on_device(labels, all_indices, dense=Dd))
+    groups = _groups(labels)
     if all_indices is None:
         return _finish(groups)
     return _finish(_split_groups(groups, all_indices, n, lambda g: D[np.ix_(g, g)]))
+
+
+def get_facial_clusters_geometric(dist_matrix, distanceThreshold, method, all_indices=None, device=None, split="host") -> List[List[int]]:
+    """get_facial_clusters behind a 'centroid', 'median' or 'ward' tree (linkage_geometric_dense): the clusters of faces joined at
+    distances <= distanceThreshold -- fcluster(Z, t, 'distance'), which on a tree with inversions cuts by the largest height inside a
+    cluster -- then the same-photo split with ``all_indices`` and get_facial_clusters' order.  Any other method or split raises
+    ValueError before any device work.  One face gives [[0]]."""
+    _check_method(method, GEOMETRIC_METHODS)
+    _check_split(split)
+    return _matrix_clusters(dist_matrix, distanceThreshold, all_indices, device, method, split)
 
 
 def cluster_faces(features, distance_threshold: float, born_years=None, photo_years=None, all_indices=None,
@@ -612,12 +674,23 @@ def cluster_faces(features, distance_threshold: float, born_years=None, photo_ye
     if method == "rankorder":
         return rank_order(features, *_rank_order_threshold_pair(distance_threshold), born_years=born_years, photo_years=photo_years,
                           device=device)[0]
+    return _feature_clusters(features, distance_threshold, born_years, photo_years, all_indices, min_cluster_size, device, method, split)
+
+
+def _feature_clusters(features, distance_threshold, born_years, photo_years, all_indices, min_cluster_size, device, method,
+                      split) -> List[List[int]]:
+    """cluster_faces behind its argument checks for a linkage ``method``: the tree cut at distance_threshold, the same-photo split,
+    the minimum size, the order.  cluster_faces_geometric ends here too."""
+    from . import ops
     x, born, year = _features(features, born_years, photo_years, device, finite=False)
     n = x.shape[0]
     by, yr = _age_arrays(born_years, photo_years, n)
     if n == 1:
         return _finish([np.zeros(1, dtype=np.int64)], min_cluster_size)
-    Z = linkage_single(x, by, yr) if method == "single" else linkage(x, method, by, yr)
+    if method == "single":
+        Z = linkage_single(x, by, yr)
+    else:
+        Z = linkage_geometric(x, method, by, yr) if method in GEOMETRIC_METHODS else linkage(x, method, by, yr)
     labels = fcluster_distance(Z, distance_threshold)
     if split == "device" and all_indices is not None:
         return _finish(_split_on_device(labels, all_indices, x=x, born=born, year=year), min_cluster_size)
@@ -637,6 +710,16 @@ def cluster_faces(features, distance_threshold: float, born_years=None, photo_ye
             D = D + 0.1 * (ai - aj) ** 2 / (ai + aj)
         return np.clip(D, 0, None)
     return _finish(_split_groups(groups, all_indices, n, sub_dist), min_cluster_size)
+
+
+def cluster_faces_geometric(features, distance_threshold: float, method: str, born_years=None, photo_years=None, all_indices=None,
+                            min_cluster_size: int = 1, device=None, split: str = "host") -> List[List[int]]:
+    """cluster_faces behind a 'centroid', 'median' or 'ward' tree (linkage_geometric): the tree cut at distance_threshold, the age term
+    when born / photo years are given, the same-photo split, clusters shorter than ``min_cluster_size`` dropped, cluster_faces' order
+    and its two ``split`` choices.  Any other method or split raises ValueError before any device work."""
+    _check_method(method, GEOMETRIC_METHODS)
+    _check_split(split)
+    return _feature_clusters(features, distance_threshold, born_years, photo_years, all_indices, min_cluster_size, device, method, split)
 
 
 # ---- scoring --------------------------------------------------------------------------------------------------------
@@ -761,7 +844,7 @@ def _sweep_labels(source, method, thresholds, born_years, photo_years, dense, mi
         if method == "dbscan":
             for eps in ts:
                 _check_dbscan_args(float(eps), min_samples)
-    negative = None if method in LINKAGE_METHODS else "dist_matrix holds negative values"
+    negative = None if method in LINKAGE_METHODS + GEOMETRIC_METHODS else "dist_matrix holds negative values"
     if dense:
         src = dict(dense=_dist_matrix(source, device, negative))
         n, dev = src["dense"].shape[0], src["dense"].device
@@ -788,8 +871,9 @@ def threshold_sweep(source, y_true, method, thresholds, born_years=None, photo_y
     get_facial_clusters' no_images_in_cluster), 'rankorder' takes (norm, rank) pairs through one matrix build; every row is scored by
     one ops.partition_scores call and read back once.  Faces outside every cluster (DBSCAN's noise, rank-order's single faces) are
     clusters of their own, as the study's y_pred has them, and 'clusters' is the reference's len(clusters): every flat cluster of a
-    linkage cut, DBSCAN's non-noise clusters, rank-order's clusters of at least two faces."""
-    _check_method(method, CLUSTER_METHODS)
+    linkage cut, DBSCAN's non-noise clusters, rank-order's clusters of at least two faces.  ``method`` may also be one of
+    GEOMETRIC_METHODS ('centroid', 'median', 'ward': linkage_geometric's trees), cut and scored as the other linkages' are."""
+    _check_method(method, CLUSTER_METHODS + GEOMETRIC_METHODS)
     t = _dense_labels(y_true, "y_true")
     labels = _sweep_labels(source, method, thresholds, born_years, photo_years, dense, min_samples, device)
     return _score_rows(t, labels, _CLUSTERS_COLUMN.get(method, 1))
@@ -854,7 +938,8 @@ def select_threshold(albums, method, thresholds=None, drop=SWEEP_DROP, ceiling=S
     reference's answer.  Returns a Selection: the best threshold, its statistic, the (threshold, statistic) points the reference
     would have evaluated, and test_avg_clustering's mean and standard deviation of the ten statistics over the albums at the best
     threshold.  When no point scores above 0 the reference goes on with its initial threshold 0: a linkage method is cut there;
-    'dbscan' and 'rankorder', which accept no zero threshold, raise ValueError."""
+    'dbscan' and 'rankorder', which accept no zero threshold, raise ValueError.  For 'centroid', 'median' and 'ward' apply
+    select_from_curve to a threshold_sweep, which takes those names."""
     _check_method(method, CLUSTER_METHODS)
     albums = list(albums)
     if not albums:

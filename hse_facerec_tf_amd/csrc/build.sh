@@ -6,7 +6,8 @@
 # libhsefr_ragged.so (include/hsefr_ragged.h: the detector pass over frames of different sizes, a fifth library for the same reason) and
 # libhsefr_mixed.so (include/hsefr_mixed.h: the frames of such a pass turned, converted and cropped on the device, a sixth library for the
 # same reason) and libhsefr_split.so (include/hsefr_split.h: the same-photo split of every cluster of a clustering in one pass, a seventh
-# library for the same reason).
+# library for the same reason) and libhsefr_geom.so (include/hsefr_geom.h: centroid, median and Ward linkage, an eighth library for the
+# same reason).
 #   HSEFR_DEV=1 build.sh   builds libhsefr_dev.so instead: the same sources with -DHSEFR_DEV (tuning knobs as run-time
 #                          variables, hsefr_debug_*, the calibration kernels of devtools.hip) -- for tools/kbench.py only.
 set -euo pipefail
@@ -48,6 +49,12 @@ MIXED_FLAGS="$FLAGS $DEVICE_STRIP -ffp-contract=off"
 # (linkage_scan.h's feat_tile over mfma_dot.h) and must give its bits
 SPLIT_SRCS="group_split.hip"
 SPLIT_FLAGS="$FLAGS $DEVICE_STRIP"
+# libhsefr_geom.so (include/hsefr_geom.h: centroid, median and Ward linkage): an eighth library, built as the seventh.  The flags are
+# libhsefr.so's own plus -DHSEFR_GEOM_LIB: besides geom_linkage.hip it compiles hier_linkage.hip a second time (the working matrix over
+# linkage_scan.h's feat_tile, which must give libhsefr.so's bits, and the rounds with Ward's rule); its objects carry a geom_ prefix so
+# that they do not replace libhsefr.so's.  The three update rules switch contraction off themselves (geom_rules.h), as lw2 does
+GEOM_SRCS="geom_linkage.hip hier_linkage.hip"
+GEOM_FLAGS="$FLAGS $DEVICE_STRIP -DHSEFR_GEOM_LIB"
 LINT=1
 HOST_STRIP=0
 HOST_SIZE_FLAGS=""
@@ -226,4 +233,23 @@ if [ "$LINT" = "1" ]; then
   /opt/rocm/lib/llvm/bin/llvm-strip --strip-all -w --keep-symbol='_ZN*_kernel*' --keep-symbol='!*__device_stub__*' "$SPLIT_OUT"
   python3 ../../tools/isa_lint.py "$SPLIT_OUT"
   echo "built $(realpath $SPLIT_OUT)"
+  # the eighth library: built, stripped and linted as the seventh; stale against the headers it shares with libhsefr.so too
+  GEOM_OUT=../libhsefr_geom.so
+  GEOM_OBJS=""
+  for s in $GEOM_SRCS; do
+    o="$BUILD/geom_${s%.hip}.o"
+    stale=0
+    for dep in "$s" hier_build.h geom_rules.h linkage_scan.h mfma_dot.h common.h ../../include/hsefr.h ../../include/hsefr_geom.h build.sh; do
+      if [ ! -f "$o" ] || [ "$dep" -nt "$o" ]; then stale=1; fi
+    done
+    if [ "$stale" = 1 ]; then
+      rm -f "$o"
+      hipcc $GEOM_FLAGS -Xarch_host -Os ${HSEFR_EXTRA_FLAGS:-} -c "$s" -o "$o"
+    fi
+    GEOM_OBJS="$GEOM_OBJS $o"
+  done
+  hipcc $LINK -shared -fPIC -o "$GEOM_OUT" $GEOM_OBJS
+  /opt/rocm/lib/llvm/bin/llvm-strip --strip-all -w --keep-symbol='_ZN*_kernel*' --keep-symbol='!*__device_stub__*' "$GEOM_OUT"
+  python3 ../../tools/isa_lint.py "$GEOM_OUT"
+  echo "built $(realpath $GEOM_OUT)"
 fi

@@ -13,4 +13,16 @@ namespace hsefr {
 // Launches the build of W (n^2 doubles) from src on s; the caller's launch_status covers it.
 void build_working_matrix(const DistSource& src, double* W, hipStream_t s);
 
+#ifdef HSEFR_GEOM_LIB
+// libhsefr_geom.so (include/hsefr_geom.h) compiles hier_linkage.hip a second time under this macro and takes from it, besides the build:
+//   rescan_rows          hl_rescan_kernel on `blocks` workgroups: nn / nnd of the rows list[0 .. cnt[HL_CNT_LIST]) over the alive columns,
+//                        least (value, column); a no-op while cnt[HL_CNT_ALIVE] <= 1.  cnt: a block of HL_CNT_WORDS ints of the caller's;
+//   launch_ward_linkage  launch_hier_linkage with Ward's rule; w_out (optional) receives W as first built, counts (optional, device)
+//                        {records written, radicands clamped at zero}.
+constexpr int HL_CNT_ALIVE = 0, HL_CNT_LIST = 4, HL_CNT_WORDS = 8;
+void rescan_rows(const double* W, int n, const int* alive, const int* list, const int* cnt, int* nn, double* nnd, int blocks, hipStream_t s);
+int launch_ward_linkage(const DistSource& src, int* merge_a, int* merge_b, double* merge_h, int* merge_round, double* w_out, long long* counts,
+                        hipStream_t s);
+#endif
+
 }  // namespace hsefr

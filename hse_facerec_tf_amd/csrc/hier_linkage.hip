@@ -22,6 +22,12 @@
 // barriers, no persistent kernels.  Workspace: 8 n^2 + O(n) bytes, stream-ordered (hipMallocAsync), refused before any launch.
 #include "hier_build.h"
 #include "linkage_scan.h"
+#ifdef HSEFR_GEOM_LIB
+// Compiled a second time into libhsefr_geom.so (include/hsefr_geom.h) under this macro: the same rounds with Ward's three-term rule
+// (geom_rules.h) in the update, the working matrix as first built copied out on request, and the record and clamp counts handed back.
+// Without the macro this translation unit is what libhsefr.so has always compiled.
+#include "geom_rules.h"
+#endif
 
 namespace hsefr {
 
@@ -32,11 +38,20 @@ constexpr int UPD_Y = 128;         // merges walked in parallel by the update la
 constexpr int SCAN_BLOCKS = 1024;  // workgroups of the rescan launch
 
 // cnt[]: 0 alive clusters, 1 merges so far, 2 first merge of the current round, 3 round number, 4 rows on the rescan list
+#ifndef HSEFR_GEOM_LIB
 enum { C_ALIVE = 0, C_MERGES = 1, C_RSTART = 2, C_ROUND = 3, C_LIST = 4, C_N = 5 };
+#else
+// 5: radicands clamped at zero.  The closest-pair engine of geom_linkage.hip hands rescan_rows a block of these words of its own
+enum { C_ALIVE = 0, C_MERGES = 1, C_RSTART = 2, C_ROUND = 3, C_LIST = 4, C_CLAMPS = 5, C_N = 6 };
+static_assert(C_ALIVE == HL_CNT_ALIVE && C_LIST == HL_CNT_LIST && C_N <= HL_CNT_WORDS, "hier_build.h states the rescan's two words");
+#endif
 
 __device__ __forceinline__ bool better(double v, int i, double bv, int bi) { return v < bv || (v == bv && i < bi); }
 
 // Lance-Williams updates as scipy's _hierarchy_distance_update.pxi states them (no contraction, so the same roundings)
+#ifdef HSEFR_GEOM_LIB
+[[maybe_unused]]                                               // (this build's update takes geom::ward)
+#endif
 __device__ __forceinline__ double lw2(int method, double dx, double dy, int sx, int sy) {
 #pragma clang fp contract(off)
     if (method == HSEFR_LINK_AVERAGE) return ((double)sx * dx + (double)sy * dy) / (double)(sx + sy);
@@ -121,6 +136,9 @@ __global__ __launch_bounds__(256) void hl_init_kernel(int* __restrict__ alive, i
         cnt[C_RSTART] = 0;
         cnt[C_ROUND] = 0;
         cnt[C_LIST] = n;
+#ifdef HSEFR_GEOM_LIB
+        cnt[C_CLAMPS] = 0;
+#endif
     }
 }
 
@@ -216,6 +234,7 @@ __global__ __launch_bounds__(256) void hl_update_kernel(double* __restrict__ W, 
         const double* ra2 = W + (size_t)a2 * n;
         const int sa = size[a], sa2 = size[a2];
         double v;
+#ifndef HSEFR_GEOM_LIB
         if (pb < 0) {
             v = lw2(method, ra[b], ra2[b], sa, sa2);
             if (better(v, a, nnd[b], nn[b])) flag[b] = 1;
@@ -225,6 +244,22 @@ __global__ __launch_bounds__(256) void hl_update_kernel(double* __restrict__ W, 
             const double vpb = lw2(method, ra[pb], ra2[pb], sa, sa2);    // d(a u a', b')
             v = lw2(method, vb, vpb, size[b], size[pb]);
         }
+#else
+        // Ward's rule also reads the merged pair's own distance.  W[a,a'] and W[b,b'] are entries of columns that died in this round's
+        // pair launch: nobody writes them here.  Two pairs merged in one round compose as scipy's two steps, the lower survivor's first
+        unsigned clamps = 0;
+        const double daa = ra[a2];
+        if (pb < 0) {
+            v = geom::ward(ra[b], ra2[b], daa, sa, sa2, size[b], clamps);
+            if (better(v, a, nnd[b], nn[b])) flag[b] = 1;
+        } else {
+            if (b < a) continue;
+            const double vb = geom::ward(ra[b], ra2[b], daa, sa, sa2, size[b], clamps);       // d(a u a', b)
+            const double vpb = geom::ward(ra[pb], ra2[pb], daa, sa, sa2, size[pb], clamps);   // d(a u a', b')
+            v = geom::ward(vb, vpb, W[(size_t)b * n + pb], size[b], size[pb], sa + sa2, clamps);
+        }
+        if (clamps) atomicAdd(&cnt[C_CLAMPS], (int)clamps);
+#endif
         W[(size_t)a * n + b] = v;
         W[(size_t)b * n + a] = v;
     }
@@ -264,6 +299,13 @@ __global__ __launch_bounds__(256) void hl_finalize_kernel(int n, const int* __re
     if (want) list[base + __popcll(m & ((1ull << lane) - 1))] = i;
 }
 
+#ifdef HSEFR_GEOM_LIB
+// two threads, one count each (8-byte stores)
+__global__ void hl_counts_kernel(const int* __restrict__ cnt, long long* __restrict__ counts) {
+    if (threadIdx.x < 2) counts[threadIdx.x] = cnt[threadIdx.x == 0 ? C_MERGES : C_CLAMPS];
+}
+#endif
+
 }  // namespace
 
 void build_working_matrix(const DistSource& src, double* W, hipStream_t s) {
@@ -275,7 +317,17 @@ void build_working_matrix(const DistSource& src, double* W, hipStream_t s) {
         HSEFR_LAUNCH(hl_build_feat_kernel, gt, blk, 0, s, src.x, src.n, src.d, src.born, src.year, W);
 }
 
+#ifdef HSEFR_GEOM_LIB
+void rescan_rows(const double* W, int n, const int* alive, const int* list, const int* cnt, int* nn, double* nnd, int blocks, hipStream_t s) {
+    HSEFR_LAUNCH(hl_rescan_kernel, dim3(blocks), dim3(256), 0, s, W, n, alive, list, cnt, nn, nnd);
+}
+
+int launch_ward_linkage(const DistSource& src, int* merge_a, int* merge_b, double* merge_h, int* merge_round, double* w_out, long long* counts,
+                        hipStream_t s) {
+    const int method = 0;                                      // (the update of this build knows one rule)
+#else
 int launch_hier_linkage(const DistSource& src, int method, int* merge_a, int* merge_b, double* merge_h, int* merge_round, hipStream_t s) {
+#endif
     const int n = src.n;
     if (n == 1) return HSEFR_OK;
     // W first (n^2 doubles), then nnd (n doubles), then int arrays: nn, alive, partner, size, flag, list, cnt
@@ -299,6 +351,13 @@ int launch_hier_linkage(const DistSource& src, int method, int* merge_a, int* me
     const dim3 blk(256), g1((n + 255) / 256);
     HSEFR_LAUNCH(hl_init_kernel, g1, blk, 0, s, alive, partner, size, flag, list, cnt, n);
     build_working_matrix(src, W, s);
+#ifdef HSEFR_GEOM_LIB
+    if (w_out && hipMemcpyAsync(w_out, W, (size_t)n * n * 8, hipMemcpyDeviceToDevice, s) != hipSuccess) {
+        set_error("ward linkage: copying the working matrix out failed: %s", hipGetErrorString(hipGetLastError()));
+        (void)hipFreeAsync(ws, s);
+        return HSEFR_ERR_HIP;
+    }
+#endif
     const dim3 gs(n < SCAN_BLOCKS ? n : SCAN_BLOCKS), gu((n + 255) / 256, UPD_Y);
     HSEFR_LAUNCH(hl_rescan_kernel, gs, blk, 0, s, W, n, alive, list, cnt, nn, nnd);
     int rc = launch_status("hier_linkage");
@@ -324,6 +383,12 @@ int launch_hier_linkage(const DistSource& src, int method, int* merge_a, int* me
         set_error("hier_linkage: %d clusters and %d merges left after the rounds (n=%d)", host_cnt[0], host_cnt[1], n);
         rc = HSEFR_ERR_HIP;
     }
+#ifdef HSEFR_GEOM_LIB
+    if (rc == HSEFR_OK && counts) {
+        HSEFR_LAUNCH(hl_counts_kernel, dim3(1), dim3(64), 0, s, cnt, counts);
+        rc = launch_status("ward linkage");
+    }
+#endif
     (void)hipFreeAsync(ws, s);
     return rc;
 }

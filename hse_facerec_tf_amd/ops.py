@@ -1229,6 +1229,42 @@ def hier_linkage_merges(x=None, dense=None, born=None, year=None, method="averag
     return ma[:n - 1], mb[:n - 1], mh[:n - 1], mr[:n - 1]
 
 
+GEOM_METHODS = {"centroid": 0, "median": 1, "ward": 2}     # HSEFR_GEOM_CENTROID / _MEDIAN / _WARD
+GEOM_LDS_MAX = 128      # HSEFR_GEOM_LDS_MAX: the largest n centroid / median run as one launch of one workgroup
+
+
+@_device_guarded
+def geom_linkage_merges(x=None, dense=None, born=None, year=None, method="ward", return_matrix=False, return_counts=False):
+    """Centroid, median or Ward linkage (hsefr_geom_linkage, libhsefr_geom.so) -> (merge_a int32, merge_b int32, merge_h float64,
+    merge_round int32), n - 1 CUDA tensors each, merge_a < merge_b the points whose clusters merged at height merge_h.  'ward' runs
+    hier_linkage_merges' rounds: the cluster lives on in merge_a's slot and merge_round is the round (clustering.linkage_from_merges
+    makes Z).  'centroid' and 'median' merge the least pair step by step: the cluster lives on in merge_b's slot, the records are in
+    merge order with heights that may fall, and merge_round is the step (clustering.linkage_from_sequence makes Z).  The sources are
+    hier_linkage_merges'.  With ``return_matrix`` also the float64 CUDA tensor [n, n] of the working matrix as first built (diagonal
+    +inf); with ``return_counts`` also a host int64 [2] = (records written, radicands clamped at zero), read back.  Needs 8 n^2 bytes of
+    device workspace.  'ward' returns with the current stream synchronised; the other two are asynchronous unless the counts are read."""
+    torch = _lib.require_gpu()
+    if method not in GEOM_METHODS:
+        raise ValueError("geom_linkage_merges: method %r is not one of %s" % (method, ", ".join(sorted(GEOM_METHODS))))
+    x, n, dev, src = _dist_source("geom_linkage_merges", x, dense, born, year)
+    m = max(n - 1, 1)
+    ma = torch.full((m,), -1, dtype=torch.int32, device=dev)
+    mb = torch.full((m,), -1, dtype=torch.int32, device=dev)
+    mh = torch.empty((m,), dtype=torch.float64, device=dev)
+    mr = torch.full((m,), -1, dtype=torch.int32, device=dev)
+    W = torch.full((n, n), float("inf"), dtype=torch.float64, device=dev) if return_matrix else None
+    counts = torch.zeros((2,), dtype=torch.int64, device=dev) if return_counts else None
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    _lib.geom_check(_lib.geom_lib().hsefr_geom_linkage(*src, GEOM_METHODS[method], ma.data_ptr(), mb.data_ptr(), mh.data_ptr(), mr.data_ptr(),
+                                                       ptr(W), ptr(counts), _lib.current_stream_ptr()), "hsefr_geom_linkage")
+    out = (ma[:n - 1], mb[:n - 1], mh[:n - 1], mr[:n - 1])
+    if return_matrix:
+        out += (W,)
+    if return_counts:
+        out += (counts.cpu().numpy(),)
+    return out
+
+
 @_device_guarded
 def dbscan_labels(x=None, dense=None, born=None, year=None, eps=0.5, min_samples=5):
     """DBSCAN with scikit-learn's labels (hsefr_dbscan) -> (labels int32 [n], core uint8 [n]) CUDA tensors: clusters 0, 1, ... in

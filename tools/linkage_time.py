@@ -10,9 +10,15 @@ DBSCAN on it (up to n = 9164).
 With --method rankorder: hsefr_rank_order (csrc/rank_order.hip: the fp64 n x n matrix, top-20 lists, pair tests and an in-place cluster
 reduce per iteration) for n in {2048, 9164} at --norm / --rank, with the iterations, clusters and faces left single, and a three-pair
 threshold sequence next to three single calls, against the host matrix + the NumPy restatement of tests/rank_order_ref.py.
+With --method centroid / median / ward: hsefr_geom_linkage (libhsefr_geom.so; csrc/geom_linkage.hip's closest-pair engine, or
+csrc/hier_linkage.hip's rounds with Ward's rule) for n in {128, 129, 2048, 9164} at d = 1024 -- 128 is the one-workgroup class of
+centroid / median, 129 the smallest n of their two-launches-per-step class -- against the host matrix + scipy's linkage of the same
+method, with hsefr_hier_linkage 'average' on the same features alternated in the same run.  Every size runs in a child process under
+its own time limit.
 usage: python tools/linkage_time.py [--method M] [--eps E] [--min-samples K] [--norm T] [--rank R] [--out FILE]"""
 import argparse
 import os
+import subprocess
 import sys
 import time
 
@@ -128,6 +134,134 @@ def main_hier(method, out):
     print(text)
 
 
+GEOM_SIZES = (128, 129, 2048, 9164)
+GEOM_SECTION_TIMEOUT_S = 240
+
+
+def replay_rescans(W, method, a, b, h):
+    """The closest-pair engine replayed on the host from the device's own working matrix, with the cached row minima: checks the
+    device's records bit for bit and counts the rows whose minimum had to be rescanned (row y of every step included)."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import geom_linkage_ref as gref
+    n = W.shape[0]
+    alive = np.ones(n, dtype=bool)
+    size = np.ones(n, dtype=np.int64)
+    nn = np.argmin(W, axis=1)
+    nnd = W[np.arange(n), nn]
+    rescans = 0
+    for step in range(n - 1):
+        d = nnd.min()
+        cand = np.flatnonzero(nnd == d)
+        lo, hi = np.minimum(cand, nn[cand]), np.maximum(cand, nn[cand])
+        k = np.lexsort((hi, lo))[0]
+        x, y = int(lo[k]), int(hi[k])
+        assert (x, y, d) == (int(a[step]), int(b[step]), h[step]), (step, x, y, d, a[step], b[step], h[step])
+        alive[x] = False
+        idx = np.flatnonzero(alive)
+        idx = idx[idx != y]
+        if method == "centroid":
+            v = gref.centroid(W[x, idx], W[y, idx], d, int(size[x]), int(size[y]))[0]
+        else:
+            v = gref.median(W[x, idx], W[y, idx], d)[0]
+        W[y, idx] = v
+        W[idx, y] = v
+        W[x, :] = np.inf
+        W[:, x] = np.inf
+        nnd[x] = np.inf
+        size[y] += size[x]
+        gone = (nn[idx] == x) | (nn[idx] == y)
+        take = ~gone & ((v < nnd[idx]) | ((v == nnd[idx]) & (y < nn[idx])))
+        nn[idx[take]] = y
+        nnd[idx[take]] = v[take]
+        rows = np.append(idx[gone], y)
+        for r in rows:
+            nn[r] = int(np.argmin(W[r]))
+            nnd[r] = W[r, nn[r]]
+        rescans += len(rows)
+    return rescans
+
+
+def geom_ms(x, method, reps):
+    """Device-event ms per call of ops.geom_linkage_merges and, alternated with it in the same loop, of hsefr_hier_linkage 'average'"""
+    ops.geom_linkage_merges(x=x, method=method)
+    ops.hier_linkage_merges(x=x, method="average")
+    torch.cuda.synchronize()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2 * reps + 1)]
+    ev[0].record()
+    for k in range(reps):
+        out = ops.geom_linkage_merges(x=x, method=method)
+        ev[2 * k + 1].record()
+        ops.hier_linkage_merges(x=x, method="average")
+        ev[2 * k + 2].record()
+    torch.cuda.synchronize()
+    ms = sum(ev[2 * k].elapsed_time(ev[2 * k + 1]) for k in range(reps)) / reps
+    avg = sum(ev[2 * k + 1].elapsed_time(ev[2 * k + 2]) for k in range(reps)) / reps
+    return ms, avg, out
+
+
+def geom_section(method, n):
+    """One size, in a process of its own: prints the table's row"""
+    d = 1024
+    x = unit_rows(n, d, n + d)
+    ms, avg_ms, (a, b, h, r) = geom_ms(x, method, 3)
+    hd, hl = host_s(x.cpu().numpy(), method)
+    if method == "ward":
+        rounds = int(r.max().item()) + 1
+        detail = "%9d %13.3f" % (rounds, ms / rounds)
+    else:
+        W, counts = ops.geom_linkage_merges(x=x, method=method, return_matrix=True, return_counts=True)[4:]
+        assert counts.tolist() == [n - 1, 0], counts
+        rescans = replay_rescans(W.cpu().numpy(), method, a.cpu().numpy(), b.cpu().numpy(), h.cpu().numpy())
+        detail = "%9.2f %13.2f" % (ms * 1e3 / (n - 1), rescans / (n - 1))
+    print("ROW %7d %5d %11.2f %s %14.2f %12.3f %12.3f %10.1f  # %s" % (n, d, ms, detail, avg_ms, hd, hl, (hd + hl) * 1e3 / ms,
+                                                                     torch.cuda.get_device_name(0)), flush=True)
+
+
+def main_geom(method, out):
+    if method == "ward":
+        what = ["# GPU: hsefr_geom_linkage, device-event time per call (mean of 3 after one warm-up): matrix build + reciprocal-NN rounds with",
+                "# Ward's three-term rule; rounds = rounds the tree needed (launched in batches of 32); ms_per_round = gpu_ms / rounds"]
+        cols = ("rounds", "ms_per_round")
+    else:
+        what = ["# GPU: hsefr_geom_linkage, device-event time per call (mean of 3 after one warm-up): matrix build + n - 1 closest-pair steps",
+                "# (n <= 128: one launch of one workgroup, the matrix in LDS; above: two launches per step, no host synchronisation)",
+                "# us_per_step = gpu_ms / (n - 1), the matrix build included; rescans_per_step = rows whose cached minimum was rescanned per",
+                "# step (row y included), from a host replay of the engine on the device's matrix that also checks every record's bits"]
+        cols = ("us_per_step", "rescans_per_step")
+    lines = ["# %s-linkage clustering from unit-norm features, fp32 distances in an fp64 matrix (tools/linkage_time.py --method %s)"
+             % (method, method)] + what + [
+             "# average_ms = hsefr_hier_linkage 'average' on the same features, alternated with it in the same loop",
+             "# host: identification.feature_distance_matrix (GPU distances + copy to a host float64 matrix) + scipy linkage '%s'" % method,
+             "# every row ran in a child process of its own under a %d s limit" % GEOM_SECTION_TIMEOUT_S,
+             "%7s %5s %11s %9s %13s %14s %12s %12s %10s" % (("n", "d", "gpu_ms") + cols + ("average_ms", "host_D_s", "host_link_s", "speedup"))]
+    device, failed = None, False
+    for n in GEOM_SIZES:
+        try:
+            res = subprocess.run([sys.executable, os.path.abspath(__file__), "--method", method, "--section", str(n)], capture_output=True,
+                                 text=True, timeout=GEOM_SECTION_TIMEOUT_S)
+        except subprocess.TimeoutExpired:
+            lines.append("%7d  -- no result within %d s; the sizes after it were not run" % (n, GEOM_SECTION_TIMEOUT_S))
+            failed = True
+            break
+        rows = [l for l in res.stdout.splitlines() if l.startswith("ROW ")]
+        if res.returncode != 0 or not rows:
+            lines.append("%7d  -- the section ended with status %d; the sizes after it were not run" % (n, res.returncode))
+            sys.stderr.write(res.stderr[-2000:])
+            failed = True
+            break
+        row, _, device = rows[0][4:].partition("  # ")
+        lines.append(row)
+        print(lines[-1], flush=True)
+    lines[0] += "; %s" % device
+    text = "\n".join(lines) + "\n"
+    if out:
+        with open(out, "w") as f:
+            f.write(text)
+    print(text)
+    if failed:
+        sys.exit(1)                                  # nothing more is started on a GPU that a section may have left in a bad state
+
+
 def dbscan_ms(x, eps, min_samples, reps):
     ops.dbscan_labels(x=x, eps=eps, min_samples=min_samples)
     torch.cuda.synchronize()
@@ -239,12 +373,15 @@ def main_rankorder(norm, rank, out):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
-    ap.add_argument("--method", default="single", choices=["single", "average", "complete", "weighted", "dbscan", "rankorder"])
+    ap.add_argument("--method", default="single", choices=["single", "average", "complete", "weighted", "dbscan", "rankorder", "centroid", "median", "ward"])
+    ap.add_argument("--section", type=int, default=None, help="--method centroid / median / ward: run this one size (the tool's own child)")
     ap.add_argument("--eps", type=float, default=0.9, help="--method dbscan: the neighbourhood radius")
     ap.add_argument("--min-samples", type=int, default=4, help="--method dbscan: points within eps (itself included) that make a core")
     ap.add_argument("--norm", type=float, default=1.06, help="--method rankorder: the normalised-distance threshold")
     ap.add_argument("--rank", type=float, default=16, help="--method rankorder: the rank-order threshold")
     args = ap.parse_args()
+    if args.method in ("centroid", "median", "ward"):
+        return geom_section(args.method, args.section) if args.section else main_geom(args.method, args.out)
     if args.method == "rankorder":
         return main_rankorder(args.norm, args.rank, args.out)
     if args.method == "dbscan":
