@@ -1,7 +1,7 @@
-"""ctypes binding of libhsefr.so (include/hsefr.h).  No fallback: if the library is missing the
-import of anything that needs it raises, and every non-zero status becomes a Python exception
-in the reference's error style (ValueError for shape errors, NotImplementedError for unsupported
-graphs, RuntimeError otherwise)."""
+"""ctypes binding of libhsefr.so (include/hsefr.h) and of the libraries built beside it (include/hsefr_<name>.h), each described by
+one Library record in LIBRARIES.  No fallback: if a library is missing the import of anything that needs it raises, and every
+non-zero status becomes a Python exception in the reference's error style (ValueError for shape errors, NotImplementedError for
+unsupported graphs, RuntimeError otherwise)."""
 from __future__ import annotations
 
 import ctypes
@@ -9,13 +9,68 @@ import os
 from ctypes import POINTER, c_char_p, c_float, c_int, c_longlong, c_size_t, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# HSEFR_LIB selects another build of the library (e.g. libhsefr_dev.so for tools/kbench.py); the product is libhsefr.so
-LIB_PATH = os.path.join(_HERE, os.environ.get("HSEFR_LIB", "libhsefr.so"))
 
 OK, ERR_INVALID, ERR_UNSUPPORTED, ERR_HIP, ERR_NOMEM, ERR_SHAPE = 0, -1, -2, -3, -4, -5
 
-_lib = None
 
+class HsefrError(RuntimeError):
+    pass
+
+
+class Library:
+    """One shared library of the package: where it lies, what it exports and how it reports an error.
+
+    ``tag`` stands in messages ("... (hsefr_album status -1)"), ``env`` names the variable that selects another build of the file,
+    ``signatures`` is name -> (restype, argtypes) with one row per declaration in the public header, ``optional`` the same for names
+    bound only when the loaded file has them, ``error_fn`` and ``version_fn`` name the error-string and version functions, and
+    ``version`` is what the latter must return."""
+
+    def __init__(self, tag, file, env, signatures, error_fn, version_fn, version, optional=None):
+        self.tag, self.file, self.env, self.signatures, self.optional = tag, file, env, signatures, optional or {}
+        self.error_fn, self.version_fn, self.version = error_fn, version_fn, version
+        self.path = os.path.join(_HERE, os.environ.get(env, file))
+        self._handle = None
+
+    def load(self) -> ctypes.CDLL:
+        """Load the library once.  torch is imported first on purpose: the library's DT_NEEDED libamdhip64.so.7 must resolve to the
+        HIP runtime PyTorch already mapped, so that torch streams and ``data_ptr()`` addresses belong to the same runtime instance.
+        Missing is an error: there is no fallback."""
+        if self._handle is None:
+            import torch  # noqa: F401  (side effect: maps torch's libamdhip64)
+            if not os.path.exists(self.path):
+                raise ImportError("%s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                                  "(hipcc --offload-arch=gfx950). There is no CPU fallback." % self.path)
+            L = ctypes.CDLL(self.path)
+            for table, required in ((self.signatures, True), (self.optional, False)):
+                for name, (res, args) in table.items():
+                    if required or hasattr(L, name):
+                        fn = getattr(L, name)
+                        fn.restype = res
+                        fn.argtypes = args
+            self._handle = L
+        return self._handle
+
+    def last_error(self) -> str:
+        s = getattr(self.load(), self.error_fn)()
+        return s.decode("utf-8", "replace") if s else ""
+
+    def check(self, status: int, what: str = "") -> None:
+        """Raise for a non-zero status of this library, with its own error string."""
+        if status != OK:
+            _raise(status, "%s%s (%s status %d)" % (what + ": " if what else "", self.last_error(), self.tag, status))
+
+
+def _raise(status: int, msg: str) -> None:
+    if status == ERR_SHAPE or status == ERR_INVALID:
+        raise ValueError(msg)
+    if status == ERR_UNSUPPORTED:
+        raise NotImplementedError(msg)
+    if status == ERR_NOMEM:
+        raise MemoryError(msg)
+    raise HsefrError(msg)
+
+
+# ---- libhsefr.so.  HSEFR_LIB selects another build of it (e.g. libhsefr_dev.so for tools/kbench.py)
 # name -> (restype, argtypes); one row per declaration in include/hsefr.h
 _fp = c_void_p   # device pointers travel as integers (tensor.data_ptr())
 SIGNATURES = {
@@ -121,29 +176,22 @@ DEV_SIGNATURES = {
     "hsefr_stem_fused": (c_int, [_fp] * 6 + [c_void_p, _fp, _fp, _fp] + [c_int] * 9 + [c_void_p]),     # round 1's stem: dev builds only since round 6
 }
 
-
-# libhsefr_album.so (include/hsefr_album.h): the album organiser's device code, a library of its own.  HSEFR_ALBUM_LIB selects another build
-ALBUM_LIB_PATH = os.path.join(_HERE, os.environ.get("HSEFR_ALBUM_LIB", "libhsefr_album.so"))
-_album_lib = None
+# ---- the later libraries, each with its own header, version and error string; HSEFR_<NAME>_LIB selects another build of one
+# libhsefr_album.so (include/hsefr_album.h): the album organiser's device code
 ALBUM_SIGNATURES = {
     "hsefr_album_version": (c_int, []),
     "hsefr_album_last_error_string": (c_char_p, []),
     "hsefr_album_face_crops": (c_int, [_fp, c_int, c_int, c_int, c_void_p, c_int, _fp, c_int, c_int, c_void_p]),
 }
 
-# libhsefr_frames.so (include/hsefr_frames.h): the frame stack's channel swap and quarter turns, a third library.  HSEFR_FRAMES_LIB selects
-# another build
-FRAMES_LIB_PATH = os.path.join(_HERE, os.environ.get("HSEFR_FRAMES_LIB", "libhsefr_frames.so"))
-_frames_lib = None
+# libhsefr_frames.so (include/hsefr_frames.h): the frame stack's channel swap and quarter turns
 FRAMES_SIGNATURES = {
     "hsefr_frames_version": (c_int, []),
     "hsefr_frames_last_error_string": (c_char_p, []),
     "hsefr_frames_prepare": (c_int, [_fp, _fp, c_int, c_int, c_int, c_int, c_int, c_void_p]),
 }
 
-# libhsefr_forest.so (include/hsefr_forest.h): the random forest classifier, a fourth library.  HSEFR_FOREST_LIB selects another build
-FOREST_LIB_PATH = os.path.join(_HERE, os.environ.get("HSEFR_FOREST_LIB", "libhsefr_forest.so"))
-_forest_lib = None
+# libhsefr_forest.so (include/hsefr_forest.h): the random forest classifier
 FOREST_SIGNATURES = {
     "hsefr_forest_version": (c_int, []),
     "hsefr_forest_last_error_string": (c_char_p, []),
@@ -152,10 +200,7 @@ FOREST_SIGNATURES = {
     "hsefr_forest_predict": (c_int, [_fp] + [c_int] * 6 + [_fp] * 11 + [c_void_p]),
 }
 
-# libhsefr_ragged.so (include/hsefr_ragged.h): one detector pass over frames of different sizes, a fifth library.  HSEFR_RAGGED_LIB selects
-# another build
-RAGGED_LIB_PATH = os.path.join(_HERE, os.environ.get("HSEFR_RAGGED_LIB", "libhsefr_ragged.so"))
-_ragged_lib = None
+# libhsefr_ragged.so (include/hsefr_ragged.h): one detector pass over frames of different sizes
 _i64 = ctypes.c_int64
 RAGGED_SIGNATURES = {
     "hsefr_ragged_version": (c_int, []),
@@ -169,10 +214,8 @@ RAGGED_SIGNATURES = {
     "hsefr_ragged_stage_finish": (c_int, [c_int, _fp, _fp, c_int, _fp, _fp, _fp, ctypes.c_float, _fp, _fp, _fp, _fp, _fp, c_int, c_void_p]),
 }
 
-# libhsefr_mixed.so (include/hsefr_mixed.h): a mixed-size pass's frames turned, converted and cropped on the device, a sixth library.
-# HSEFR_MIXED_LIB selects another build.  The two tables are HOST pointers (c_void_p: a NumPy array's ctypes.data)
-MIXED_LIB_PATH = os.path.join(_HERE, os.environ.get("HSEFR_MIXED_LIB", "libhsefr_mixed.so"))
-_mixed_lib = None
+# libhsefr_mixed.so (include/hsefr_mixed.h): a mixed-size pass's frames turned, converted and cropped on the device.  The two tables
+# are HOST pointers (c_void_p: a NumPy array's ctypes.data)
 MIXED_SIGNATURES = {
     "hsefr_mixed_version": (c_int, []),
     "hsefr_mixed_last_error_string": (c_char_p, []),
@@ -180,10 +223,8 @@ MIXED_SIGNATURES = {
     "hsefr_mixed_face_crops": (c_int, [_fp, _i64, c_void_p, c_int, c_void_p, c_int, _fp, c_int, c_int, c_void_p]),
 }
 
-# libhsefr_split.so (include/hsefr_split.h): the same-photo split of every cluster of a clustering in one pass, a seventh library.
-# HSEFR_SPLIT_LIB selects another build.  The offset table is a HOST pointer (c_void_p: a NumPy array's ctypes.data)
-SPLIT_LIB_PATH = os.path.join(_HERE, os.environ.get("HSEFR_SPLIT_LIB", "libhsefr_split.so"))
-_split_lib = None
+# libhsefr_split.so (include/hsefr_split.h): the same-photo split of every cluster of a clustering in one pass.  The offset table is
+# a HOST pointer (c_void_p: a NumPy array's ctypes.data)
 SPLIT_SIGNATURES = {
     "hsefr_split_version": (c_int, []),
     "hsefr_split_last_error": (c_char_p, []),
@@ -191,9 +232,7 @@ SPLIT_SIGNATURES = {
                                    _fp, c_void_p]),
 }
 
-# libhsefr_geom.so (include/hsefr_geom.h): centroid, median and Ward linkage, an eighth library.  HSEFR_GEOM_LIB selects another build
-GEOM_LIB_PATH = os.path.join(_HERE, os.environ.get("HSEFR_GEOM_LIB", "libhsefr_geom.so"))
-_geom_lib = None
+# libhsefr_geom.so (include/hsefr_geom.h): centroid, median and Ward linkage
 GEOM_SIGNATURES = {
     "hsefr_geom_version": (c_int, []),
     "hsefr_geom_last_error": (c_char_p, []),
@@ -201,249 +240,33 @@ GEOM_SIGNATURES = {
 }
 
 
-class HsefrError(RuntimeError):
-    pass
+def _later(name, signatures, error_fn):
+    return Library("hsefr_" + name, "libhsefr_%s.so" % name, "HSEFR_%s_LIB" % name.upper(), signatures, error_fn, "hsefr_%s_version" % name, 100)
 
 
-def lib() -> ctypes.CDLL:
-    """Load libhsefr.so once.  torch is imported first on purpose: the library's DT_NEEDED
-    libamdhip64.so.7 must resolve to the HIP runtime PyTorch already mapped, so that torch
-    streams and ``data_ptr()`` addresses belong to the same runtime instance."""
-    global _lib
-    if _lib is None:
-        import torch  # noqa: F401  (side effect: maps torch's libamdhip64)
-        if not os.path.exists(LIB_PATH):
-            raise ImportError("%s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                              "(hipcc --offload-arch=gfx950). There is no CPU fallback." % LIB_PATH)
-        L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        for name, (res, args) in DEV_SIGNATURES.items():
-            if hasattr(L, name):
-                fn = getattr(L, name)
-                fn.restype = res
-                fn.argtypes = args
-        _lib = L
-    return _lib
+# every library, in build order (csrc/build.sh's table has the same rows; tests/test_libraries_cpu.py holds the two together)
+LIBRARIES = (
+    Library("hsefr", "libhsefr.so", "HSEFR_LIB", SIGNATURES, "hsefr_last_error_string", "hsefr_version", 141, optional=DEV_SIGNATURES),
+    _later("album", ALBUM_SIGNATURES, "hsefr_album_last_error_string"),
+    _later("frames", FRAMES_SIGNATURES, "hsefr_frames_last_error_string"),
+    _later("forest", FOREST_SIGNATURES, "hsefr_forest_last_error_string"),
+    _later("ragged", RAGGED_SIGNATURES, "hsefr_ragged_last_error_string"),
+    _later("mixed", MIXED_SIGNATURES, "hsefr_mixed_last_error_string"),
+    _later("split", SPLIT_SIGNATURES, "hsefr_split_last_error"),
+    _later("geom", GEOM_SIGNATURES, "hsefr_geom_last_error"),
+)
+_MAIN, _ALBUM, _FRAMES, _FOREST, _RAGGED, _MIXED, _SPLIT, _GEOM = LIBRARIES
 
-
-def album_lib() -> ctypes.CDLL:
-    """Load libhsefr_album.so once (torch first, as lib() does and for the same reason).  Missing is an error: there is no fallback."""
-    global _album_lib
-    if _album_lib is None:
-        import torch  # noqa: F401
-        if not os.path.exists(ALBUM_LIB_PATH):
-            raise ImportError("%s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                              "(hipcc --offload-arch=gfx950). There is no CPU fallback." % ALBUM_LIB_PATH)
-        L = ctypes.CDLL(ALBUM_LIB_PATH)
-        for name, (res, args) in ALBUM_SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _album_lib = L
-    return _album_lib
-
-
-def album_last_error() -> str:
-    s = album_lib().hsefr_album_last_error_string()
-    return s.decode("utf-8", "replace") if s else ""
-
-
-def album_check(status: int, what: str = "") -> None:
-    """check() for a status of libhsefr_album.so (its own error string)."""
-    if status != OK:
-        _raise(status, "%s%s (hsefr_album status %d)" % (what + ": " if what else "", album_last_error(), status))
-
-
-def frames_lib() -> ctypes.CDLL:
-    """Load libhsefr_frames.so once (torch first, as lib() does and for the same reason).  Missing is an error: there is no fallback."""
-    global _frames_lib
-    if _frames_lib is None:
-        import torch  # noqa: F401
-        if not os.path.exists(FRAMES_LIB_PATH):
-            raise ImportError("%s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                              "(hipcc --offload-arch=gfx950). There is no CPU fallback." % FRAMES_LIB_PATH)
-        L = ctypes.CDLL(FRAMES_LIB_PATH)
-        for name, (res, args) in FRAMES_SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _frames_lib = L
-    return _frames_lib
-
-
-def frames_last_error() -> str:
-    s = frames_lib().hsefr_frames_last_error_string()
-    return s.decode("utf-8", "replace") if s else ""
-
-
-def frames_check(status: int, what: str = "") -> None:
-    """check() for a status of libhsefr_frames.so (its own error string)."""
-    if status != OK:
-        _raise(status, "%s%s (hsefr_frames status %d)" % (what + ": " if what else "", frames_last_error(), status))
-
-
-def forest_lib() -> ctypes.CDLL:
-    """Load libhsefr_forest.so once (torch first, as lib() does and for the same reason).  Missing is an error: there is no fallback."""
-    global _forest_lib
-    if _forest_lib is None:
-        import torch  # noqa: F401
-        if not os.path.exists(FOREST_LIB_PATH):
-            raise ImportError("%s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                              "(hipcc --offload-arch=gfx950). There is no CPU fallback." % FOREST_LIB_PATH)
-        L = ctypes.CDLL(FOREST_LIB_PATH)
-        for name, (res, args) in FOREST_SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _forest_lib = L
-    return _forest_lib
-
-
-def forest_last_error() -> str:
-    s = forest_lib().hsefr_forest_last_error_string()
-    return s.decode("utf-8", "replace") if s else ""
-
-
-def forest_check(status: int, what: str = "") -> None:
-    """check() for a status of libhsefr_forest.so (its own error string)."""
-    if status != OK:
-        _raise(status, "%s%s (hsefr_forest status %d)" % (what + ": " if what else "", forest_last_error(), status))
-
-
-def ragged_lib() -> ctypes.CDLL:
-    """Load libhsefr_ragged.so once (torch first, as lib() does and for the same reason).  Missing is an error: there is no fallback."""
-    global _ragged_lib
-    if _ragged_lib is None:
-        import torch  # noqa: F401
-        if not os.path.exists(RAGGED_LIB_PATH):
-            raise ImportError("%s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                              "(hipcc --offload-arch=gfx950). There is no CPU fallback." % RAGGED_LIB_PATH)
-        L = ctypes.CDLL(RAGGED_LIB_PATH)
-        for name, (res, args) in RAGGED_SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _ragged_lib = L
-    return _ragged_lib
-
-
-def ragged_last_error() -> str:
-    s = ragged_lib().hsefr_ragged_last_error_string()
-    return s.decode("utf-8", "replace") if s else ""
-
-
-def ragged_check(status: int, what: str = "") -> None:
-    """check() for a status of libhsefr_ragged.so (its own error string)."""
-    if status != OK:
-        _raise(status, "%s%s (hsefr_ragged status %d)" % (what + ": " if what else "", ragged_last_error(), status))
-
-
-def mixed_lib() -> ctypes.CDLL:
-    """Load libhsefr_mixed.so once (torch first, as lib() does and for the same reason).  Missing is an error: there is no fallback."""
-    global _mixed_lib
-    if _mixed_lib is None:
-        import torch  # noqa: F401
-        if not os.path.exists(MIXED_LIB_PATH):
-            raise ImportError("%s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                              "(hipcc --offload-arch=gfx950). There is no CPU fallback." % MIXED_LIB_PATH)
-        L = ctypes.CDLL(MIXED_LIB_PATH)
-        for name, (res, args) in MIXED_SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _mixed_lib = L
-    return _mixed_lib
-
-
-def mixed_last_error() -> str:
-    s = mixed_lib().hsefr_mixed_last_error_string()
-    return s.decode("utf-8", "replace") if s else ""
-
-
-def mixed_check(status: int, what: str = "") -> None:
-    """check() for a status of libhsefr_mixed.so (its own error string)."""
-    if status != OK:
-        _raise(status, "%s%s (hsefr_mixed status %d)" % (what + ": " if what else "", mixed_last_error(), status))
-
-
-def split_lib() -> ctypes.CDLL:
-    """Load libhsefr_split.so once (torch first, as lib() does and for the same reason).  Missing is an error: there is no fallback."""
-    global _split_lib
-    if _split_lib is None:
-        import torch  # noqa: F401
-        if not os.path.exists(SPLIT_LIB_PATH):
-            raise ImportError("%s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                              "(hipcc --offload-arch=gfx950). There is no CPU fallback." % SPLIT_LIB_PATH)
-        L = ctypes.CDLL(SPLIT_LIB_PATH)
-        for name, (res, args) in SPLIT_SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _split_lib = L
-    return _split_lib
-
-
-def split_last_error() -> str:
-    s = split_lib().hsefr_split_last_error()
-    return s.decode("utf-8", "replace") if s else ""
-
-
-def split_check(status: int, what: str = "") -> None:
-    """check() for a status of libhsefr_split.so (its own error string)."""
-    if status != OK:
-        _raise(status, "%s%s (hsefr_split status %d)" % (what + ": " if what else "", split_last_error(), status))
-
-
-def geom_lib() -> ctypes.CDLL:
-    """Load libhsefr_geom.so once (torch first, as lib() does and for the same reason).  Missing is an error: there is no fallback."""
-    global _geom_lib
-    if _geom_lib is None:
-        import torch  # noqa: F401
-        if not os.path.exists(GEOM_LIB_PATH):
-            raise ImportError("%s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                              "(hipcc --offload-arch=gfx950). There is no CPU fallback." % GEOM_LIB_PATH)
-        L = ctypes.CDLL(GEOM_LIB_PATH)
-        for name, (res, args) in GEOM_SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _geom_lib = L
-    return _geom_lib
-
-
-def geom_last_error() -> str:
-    s = geom_lib().hsefr_geom_last_error()
-    return s.decode("utf-8", "replace") if s else ""
-
-
-def geom_check(status: int, what: str = "") -> None:
-    """check() for a status of libhsefr_geom.so (its own error string)."""
-    if status != OK:
-        _raise(status, "%s%s (hsefr_geom status %d)" % (what + ": " if what else "", geom_last_error(), status))
-
-
-def last_error() -> str:
-    s = lib().hsefr_last_error_string()
-    return s.decode("utf-8", "replace") if s else ""
-
-
-def check(status: int, what: str = "") -> None:
-    if status == OK:
-        return
-    _raise(status, "%s%s (hsefr status %d)" % (what + ": " if what else "", last_error(), status))
-
-
-def _raise(status: int, msg: str) -> None:
-    if status == ERR_SHAPE or status == ERR_INVALID:
-        raise ValueError(msg)
-    if status == ERR_UNSUPPORTED:
-        raise NotImplementedError(msg)
-    if status == ERR_NOMEM:
-        raise MemoryError(msg)
-    raise HsefrError(msg)
+# the module-level names of each library.  Callers go through the module attribute at call time (_lib.frames_lib()), so a test can put
+# another function in its place
+LIB_PATH, lib, last_error, check = _MAIN.path, _MAIN.load, _MAIN.last_error, _MAIN.check
+ALBUM_LIB_PATH, album_lib, album_last_error, album_check = _ALBUM.path, _ALBUM.load, _ALBUM.last_error, _ALBUM.check
+FRAMES_LIB_PATH, frames_lib, frames_last_error, frames_check = _FRAMES.path, _FRAMES.load, _FRAMES.last_error, _FRAMES.check
+FOREST_LIB_PATH, forest_lib, forest_last_error, forest_check = _FOREST.path, _FOREST.load, _FOREST.last_error, _FOREST.check
+RAGGED_LIB_PATH, ragged_lib, ragged_last_error, ragged_check = _RAGGED.path, _RAGGED.load, _RAGGED.last_error, _RAGGED.check
+MIXED_LIB_PATH, mixed_lib, mixed_last_error, mixed_check = _MIXED.path, _MIXED.load, _MIXED.last_error, _MIXED.check
+SPLIT_LIB_PATH, split_lib, split_last_error, split_check = _SPLIT.path, _SPLIT.load, _SPLIT.last_error, _SPLIT.check
+GEOM_LIB_PATH, geom_lib, geom_last_error, geom_check = _GEOM.path, _GEOM.load, _GEOM.last_error, _GEOM.check
 
 
 _torch_gpu = None      # torch, once a GPU has been seen (torch.cuda.is_available() re-reads the environment on every call: the

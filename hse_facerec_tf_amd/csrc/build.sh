@@ -1,15 +1,11 @@
 #!/bin/bash
-# Builds libhsefr.so for gfx950 in-tree (hipcc cross-compiles without a GPU), and right after it libhsefr_album.so (include/hsefr_album.h:
-# the album organiser's device code, a library of its own because libhsefr.so is held below 4 MB by its tests) and libhsefr_frames.so
-# (include/hsefr_frames.h: the frame stack's channel swap and quarter turns, a library of its own for the same reason) and
-# libhsefr_forest.so (include/hsefr_forest.h: the random forest classifier, a fourth library for the same reason) and
-# libhsefr_ragged.so (include/hsefr_ragged.h: the detector pass over frames of different sizes, a fifth library for the same reason) and
-# libhsefr_mixed.so (include/hsefr_mixed.h: the frames of such a pass turned, converted and cropped on the device, a sixth library for the
-# same reason) and libhsefr_split.so (include/hsefr_split.h: the same-photo split of every cluster of a clustering in one pass, a seventh
-# library for the same reason) and libhsefr_geom.so (include/hsefr_geom.h: centroid, median and Ward linkage, an eighth library for the
-# same reason).
-#   HSEFR_DEV=1 build.sh   builds libhsefr_dev.so instead: the same sources with -DHSEFR_DEV (tuning knobs as run-time
+# Builds the project's shared libraries for gfx950 in-tree (hipcc cross-compiles without a GPU).  There are several because libhsefr.so
+# is held below 4 MB and at its version by its tests: device code that came later lives in a library of its own, with its own public
+# header, version and error string.  The table LIBS below declares them, one row each, and build_lib builds a row.
+#   HSEFR_DEV=1 build.sh   builds libhsefr_dev.so in place of libhsefr.so: the same sources with -DHSEFR_DEV (tuning knobs as run-time
 #                          variables, hsefr_debug_*, the calibration kernels of devtools.hip) -- for tools/kbench.py only.
+#   build.sh --list        prints the resolved table and compiles nothing: per library its name, output, sources, the complete compile
+#                          flags of the current mode and the files its objects are stale against (tests/test_libraries_cpu.py reads it)
 set -euo pipefail
 cd "$(dirname "$0")"
 # product sources.  Development builds add round 1's stem (reachable only through lower_graph(stem_fusion="stem")) and the first window 3x3
@@ -22,234 +18,113 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -Wall -Wno
 # tests/test_abi_cpu.py): the runtime, the profilers and tools/isa_lint.py need only the kernel symbols, which stay
 DEVICE_STRIP="-Xoffload-linker --discard-all"
 LINK="--offload-arch=gfx950"
-# libhsefr_album.so: its own source list, the same flags in every mode (no -DHSEFR_DEV code in it).  -ffp-contract=off: album.hip computes
-# OpenCV's resize taps in the kernel, where a product fused with the subtraction behind it would round once instead of twice
-ALBUM_SRCS="album.hip"
-ALBUM_FLAGS="$FLAGS $DEVICE_STRIP -ffp-contract=off"
-# libhsefr_frames.so (include/hsefr_frames.h: the frames of a pass turned upright and converted to RGB on the device): a third library for
-# the same reason, built as the second -- its own source list, the same flags in every mode
-FRAMES_SRCS="frames.hip"
-FRAMES_FLAGS="$FLAGS $DEVICE_STRIP"
-# libhsefr_forest.so (include/hsefr_forest.h: the random forest fitted and applied on the device): a fourth library, built as the third.
-# -ffp-contract=off: a candidate's score and a threshold are the restatement's fp64 operations one by one (tests/random_forest_ref.py)
-FOREST_SRCS="forest.hip"
-FOREST_FLAGS="$FLAGS $DEVICE_STRIP -ffp-contract=off"
-# libhsefr_ragged.so (include/hsefr_ragged.h: one detector pass over frames of different sizes): a fifth library, built as the fourth.
-# The flags are libhsefr.so's own: mtcnn_ragged.hip compiles the one-frame bodies that library compiles (mtcnn_post_frame.h,
-# area_resize_px.h) and must give their bits
-RAGGED_SRCS="mtcnn_ragged.hip"
-RAGGED_FLAGS="$FLAGS $DEVICE_STRIP"
-# libhsefr_mixed.so (include/hsefr_mixed.h: a mixed-size pass's frames turned and converted, and its faces cut, on the device): a sixth
-# library, built as the fifth.  It compiles the per-pixel bodies of album.hip and frames.hip (cv_linear_px.h, frames_px.h) and must give
-# their bits.  -ffp-contract=off: the crop taps are two separately rounded operations, as in album.hip
-MIXED_SRCS="mixed_frames.hip"
-MIXED_FLAGS="$FLAGS $DEVICE_STRIP -ffp-contract=off"
-# libhsefr_split.so (include/hsefr_split.h: the same-photo split of every cluster of a clustering in one pass): a seventh library, built
-# as the sixth.  The flags are libhsefr.so's own, as the fifth's: group_split.hip compiles the clustering distance that library compiles
-# (linkage_scan.h's feat_tile over mfma_dot.h) and must give its bits
-SPLIT_SRCS="group_split.hip"
-SPLIT_FLAGS="$FLAGS $DEVICE_STRIP"
-# libhsefr_geom.so (include/hsefr_geom.h: centroid, median and Ward linkage): an eighth library, built as the seventh.  The flags are
-# libhsefr.so's own plus -DHSEFR_GEOM_LIB: besides geom_linkage.hip it compiles hier_linkage.hip a second time (the working matrix over
-# linkage_scan.h's feat_tile, which must give libhsefr.so's bits, and the rounds with Ward's rule); its objects carry a geom_ prefix so
-# that they do not replace libhsefr.so's.  The three update rules switch contraction off themselves (geom_rules.h), as lw2 does
-GEOM_SRCS="geom_linkage.hip hier_linkage.hip"
-GEOM_FLAGS="$FLAGS $DEVICE_STRIP -DHSEFR_GEOM_LIB"
-LINT=1
-HOST_STRIP=0
-HOST_SIZE_FLAGS=""
+# what the seven later libraries are compiled with in every mode (no -DHSEFR_DEV code in them): libhsefr.so's own product flags
+COMMON="$FLAGS $DEVICE_STRIP"
+# the three modes of the main library: its output, its build directory (the other libraries' objects go there too) and its flags
 if [ "${HSEFR_ASAN:-0}" = "1" ]; then
   # HSEFR_ASAN=1 build.sh   the HOST half of the same sources under the address + undefined-behaviour sanitizers (no device code is
   #                         compiled and none runs: GPU sanitizers are not available on this pool) -> build_asan/libhsefr_asan.so +
   #                         build_asan/fuzz_plan, the driver tests/test_plan_blob_fuzz_cpu.py runs.  The compiler flags of that mode live
   #                         in build_asan_flags.sh, which .gpurunignore keeps off the GPU boxes (their launcher refuses any tree whose
   #                         build scripts mention a sanitizer): a CPU-only recipe.
-  OUT=build_asan/libhsefr_asan.so; BUILD=build_asan; LINT=0
+  MODE=hostonly; OUT=build_asan/libhsefr_asan.so; BUILD=build_asan
   . ./build_asan_flags.sh
 elif [ "${HSEFR_DEV:-0}" = "1" ]; then
-  OUT=../libhsefr_dev.so; BUILD=build_dev; SRCS="$SRCS stem_fused.hip conv3x3_win_bf16.hip devtools.hip"; FLAGS="$FLAGS -DHSEFR_DEV $DEVICE_STRIP"
+  MODE=dev; OUT=../libhsefr_dev.so; BUILD=build_dev; SRCS="$SRCS stem_fused.hip conv3x3_win_bf16.hip devtools.hip"; FLAGS="$FLAGS -DHSEFR_DEV $DEVICE_STRIP"
 else
-  # the product also ships without most of its host symbol table (.symtab / .strtab, about 70 KB of 100): the exported functions are in
-  # .dynsym and the device kernels' symbols in .hip_fatbin, both untouched; of .symtab only the kernels' host-side handles stay, the data
-  # symbols from which hsefr_plan_describe reads a launched kernel's name and template arguments (engine.hip, stub_names)
-  # and the HOST half of every source but engine.hip (the forward call itself) is optimised for size: launchers and argument checks,
-  # 28 KB less of them.  -Xarch_host reaches the host compilation only: the device side keeps -O3 and its code objects hold the same
-  # instructions as without the flag
-  OUT=../libhsefr.so; BUILD=build; FLAGS="$FLAGS $DEVICE_STRIP"; HOST_STRIP=1; HOST_SIZE_FLAGS="-Xarch_host -Os"
+  MODE=product; OUT=../libhsefr.so; BUILD=build; FLAGS="$COMMON"
 fi
-OBJS=""
-PIDS=""
+# ---- the libraries, in build order:  name | output | public headers (its own first) | sources | compile flags | symbols llvm-strip keeps
+# The name is the prefix of a later library's objects (<name>_<source>.o: hier_linkage.hip is compiled twice); libhsefr.so's keep their
+# plain names, which tools/build_ko.sh and tools/build_ps_ko.sh link.  Every object is stale against its source, EVERY header here (by
+# glob: a new header needs no edit of this file), the row's public headers and this script.
+#   album, mixed  -ffp-contract=off: OpenCV's resize taps are computed in the kernel, where a product fused with the subtraction behind it
+#                 would round once instead of twice.  mixed compiles the per-pixel bodies of album.hip and frames.hip (cv_linear_px.h,
+#                 frames_px.h) and must give their bits
+#   forest        -ffp-contract=off: a candidate's score and a threshold are the restatement's fp64 operations one by one
+#                 (tests/random_forest_ref.py)
+#   ragged, split libhsefr.so's own flags: they compile bodies that library compiles (mtcnn_post_frame.h and area_resize_px.h;
+#                 linkage_scan.h's feat_tile over mfma_dot.h) and must give their bits
+#   geom          the same plus -DHSEFR_GEOM_LIB: besides geom_linkage.hip it compiles hier_linkage.hip a second time (the working matrix
+#                 over feat_tile, and the rounds with Ward's rule).  The three update rules switch contraction off themselves (geom_rules.h)
+LIBS=(
+  "hsefr|$OUT|hsefr.h|$SRCS|$FLAGS|_ZN5hsefr*_kernel*"
+  "album|../libhsefr_album.so|hsefr_album.h|album.hip|$COMMON -ffp-contract=off|_ZN*_kernel*"
+  "frames|../libhsefr_frames.so|hsefr_frames.h|frames.hip|$COMMON|_ZN*_kernel*"
+  "forest|../libhsefr_forest.so|hsefr_forest.h|forest.hip|$COMMON -ffp-contract=off|_ZN*_kernel*"
+  "ragged|../libhsefr_ragged.so|hsefr_ragged.h|mtcnn_ragged.hip|$COMMON|_ZN*_kernel*"
+  "mixed|../libhsefr_mixed.so|hsefr_mixed.h|mixed_frames.hip|$COMMON -ffp-contract=off|_ZN*_kernel*"
+  "split|../libhsefr_split.so|hsefr_split.h hsefr.h|group_split.hip|$COMMON|_ZN*_kernel*"
+  "geom|../libhsefr_geom.so|hsefr_geom.h hsefr.h|geom_linkage.hip hier_linkage.hip|$COMMON -DHSEFR_GEOM_LIB|_ZN*_kernel*"
+)
+if [ "$MODE" = hostonly ]; then LIBS=("${LIBS[0]}"); fi      # the host-only recipe has nothing of the other libraries
+
+row() { IFS='|' read -r name out headers srcs flags keep <<< "$1"; }
+object() { if [ "$name" = hsefr ]; then echo "$BUILD/${1%.hip}.o"; else echo "$BUILD/${name}_${1%.hip}.o"; fi; }
+deps() { echo *.h $(printf '../../include/%s ' $headers) build.sh; }
+# the HOST half of every source is optimised for size (launchers and argument checks, 28 KB less of them in libhsefr.so): -Xarch_host
+# reaches the host compilation only, the device side keeps -O3 and its code objects hold the same instructions as without the flag.
+# Not in the main library's other two modes, and not for engine.hip (the forward call itself)
+compile_flags() {
+  if [ "$name" = hsefr ] && { [ "$MODE" != product ] || [ "$1" = engine.hip ]; }; then echo "$flags${HSEFR_EXTRA_FLAGS:+ $HSEFR_EXTRA_FLAGS}"
+  else echo "$flags -Xarch_host -Os${HSEFR_EXTRA_FLAGS:+ $HSEFR_EXTRA_FLAGS}"; fi
+}
+
+if [ "${1:-}" = "--list" ]; then
+  for r in "${LIBS[@]}"; do
+    row "$r"
+    printf 'name=%s\tout=%s\tsrcs=%s\tflags=%s\tdeps=%s\tkeep=%s\tlint=%s' "$name" "$out" "$srcs" "$(compile_flags "")" "$(deps)" "$keep" \
+      "$([ "$MODE" = hostonly ] && echo 0 || echo 1)"
+    if [ "$name" = hsefr ]; then printf '\tflags[engine.hip]=%s' "$(compile_flags engine.hip)"; fi
+    printf '\n'
+  done
+  exit 0
+fi
+
+# every stale compile of every library goes into one pool of at most 16 hipcc at a time; a failed compile fails the build (xargs
+# exits 123, set -e)
 mkdir -p "$BUILD"
-for s in $SRCS; do
-  o="$BUILD/${s%.hip}.o"
-  # an object is stale against its source, EVERY header here (by glob: a new header needs no edit of this line), the public header and this script
-  stale=0
-  for dep in "$s" *.h ../../include/hsefr.h build.sh; do
-    if [ ! -f "$o" ] || [ "$dep" -nt "$o" ]; then stale=1; fi
+: > "$BUILD/compile.list"
+for r in "${LIBS[@]}"; do
+  row "$r"
+  for s in $srcs; do
+    o="$(object "$s")"
+    for dep in "$s" $(deps); do
+      if [ ! -f "$o" ] || [ "$dep" -nt "$o" ]; then rm -f "$o"; fi
+    done
+    if [ ! -f "$o" ]; then echo "$(compile_flags "$s") -c $s -o $o" >> "$BUILD/compile.list"; fi
   done
-  if [ "$stale" = 1 ]; then
-    rm -f "$o"
-    host_flags="$HOST_SIZE_FLAGS"
-    if [ "$s" = engine.hip ]; then host_flags=""; fi
-    hipcc $FLAGS $host_flags ${HSEFR_EXTRA_FLAGS:-} -c "$s" -o "$o" &
-    PIDS="$PIDS $!"
-  fi
-  OBJS="$OBJS $o"
 done
-for pid in $PIDS; do wait "$pid"; done     # a failed compile fails the build (set -e)
-if [ "$LINT" = "0" ]; then
-  # host-only objects still reference their translation unit's device image (__hip_fatbin_<id>, registered with the HIP runtime when the
-  # library is loaded and parsed lazily at a first launch, which never happens here): empty images stand in for the device code that was
-  # not compiled
-  nm -u $OBJS | grep -o "__hip_fatbin_[0-9a-f]*" | sort -u |
-    awk '{print "__attribute__((visibility(\"default\"), aligned(4096))) const char " $1 "[4096] = {0};"}' > "$BUILD/fatbin_stubs.c"
-  /opt/rocm/lib/llvm/bin/clang -fPIC -c "$BUILD/fatbin_stubs.c" -o "$BUILD/fatbin_stubs.o"
-  OBJS="$OBJS $BUILD/fatbin_stubs.o"
-fi
-hipcc $LINK -shared -fPIC -o "$OUT" $OBJS
-if [ "$HOST_STRIP" = "1" ]; then
-  /opt/rocm/lib/llvm/bin/llvm-strip --strip-all -w --keep-symbol='_ZN5hsefr*_kernel*' --keep-symbol='!*__device_stub__*' "$OUT"
-fi
-if [ "$LINT" = "1" ]; then
-  # refuse a library with an unguarded gfx950 store-data hazard (see tools/isa_lint.py)
-  python3 ../../tools/isa_lint.py "$OUT"
-else
-  hipcc $SAN_EXE_FLAGS -x c++ fuzz_plan.cc -o "$BUILD/fuzz_plan" -L"$BUILD" -lhsefr_asan -Wl,-rpath,"$(realpath $BUILD)"
-fi
-echo "built $(realpath $OUT)"
-if [ "$LINT" = "1" ]; then
-  # the second library (product and development builds alike; the host-only sanitizer recipe above has nothing of it): built, stripped
-  # and linted as the first
-  ALBUM_OUT=../libhsefr_album.so
-  ALBUM_OBJS=""
-  for s in $ALBUM_SRCS; do
-    o="$BUILD/${s%.hip}.o"
-    stale=0
-    for dep in "$s" cv_linear_px.h ../../include/hsefr_album.h build.sh; do
-      if [ ! -f "$o" ] || [ "$dep" -nt "$o" ]; then stale=1; fi
-    done
-    if [ "$stale" = 1 ]; then
-      rm -f "$o"
-      hipcc $ALBUM_FLAGS -Xarch_host -Os ${HSEFR_EXTRA_FLAGS:-} -c "$s" -o "$o"
-    fi
-    ALBUM_OBJS="$ALBUM_OBJS $o"
-  done
-  hipcc $LINK -shared -fPIC -o "$ALBUM_OUT" $ALBUM_OBJS
-  /opt/rocm/lib/llvm/bin/llvm-strip --strip-all -w --keep-symbol='_ZN*_kernel*' --keep-symbol='!*__device_stub__*' "$ALBUM_OUT"
-  python3 ../../tools/isa_lint.py "$ALBUM_OUT"
-  echo "built $(realpath $ALBUM_OUT)"
-  # the third library: built, stripped and linted as the second
-  FRAMES_OUT=../libhsefr_frames.so
-  FRAMES_OBJS=""
-  for s in $FRAMES_SRCS; do
-    o="$BUILD/${s%.hip}.o"
-    stale=0
-    for dep in "$s" frames_px.h ../../include/hsefr_frames.h build.sh; do
-      if [ ! -f "$o" ] || [ "$dep" -nt "$o" ]; then stale=1; fi
-    done
-    if [ "$stale" = 1 ]; then
-      rm -f "$o"
-      hipcc $FRAMES_FLAGS -Xarch_host -Os ${HSEFR_EXTRA_FLAGS:-} -c "$s" -o "$o"
-    fi
-    FRAMES_OBJS="$FRAMES_OBJS $o"
-  done
-  hipcc $LINK -shared -fPIC -o "$FRAMES_OUT" $FRAMES_OBJS
-  /opt/rocm/lib/llvm/bin/llvm-strip --strip-all -w --keep-symbol='_ZN*_kernel*' --keep-symbol='!*__device_stub__*' "$FRAMES_OUT"
-  python3 ../../tools/isa_lint.py "$FRAMES_OUT"
-  echo "built $(realpath $FRAMES_OUT)"
-  # the fourth library: built, stripped and linted as the third
-  FOREST_OUT=../libhsefr_forest.so
-  FOREST_OBJS=""
-  for s in $FOREST_SRCS; do
-    o="$BUILD/${s%.hip}.o"
-    stale=0
-    for dep in "$s" ../../include/hsefr_forest.h build.sh; do
-      if [ ! -f "$o" ] || [ "$dep" -nt "$o" ]; then stale=1; fi
-    done
-    if [ "$stale" = 1 ]; then
-      rm -f "$o"
-      hipcc $FOREST_FLAGS -Xarch_host -Os ${HSEFR_EXTRA_FLAGS:-} -c "$s" -o "$o"
-    fi
-    FOREST_OBJS="$FOREST_OBJS $o"
-  done
-  hipcc $LINK -shared -fPIC -o "$FOREST_OUT" $FOREST_OBJS
-  /opt/rocm/lib/llvm/bin/llvm-strip --strip-all -w --keep-symbol='_ZN*_kernel*' --keep-symbol='!*__device_stub__*' "$FOREST_OUT"
-  python3 ../../tools/isa_lint.py "$FOREST_OUT"
-  echo "built $(realpath $FOREST_OUT)"
-  # the fifth library: built, stripped and linted as the fourth; stale against the headers it shares with libhsefr.so too
-  RAGGED_OUT=../libhsefr_ragged.so
-  RAGGED_OBJS=""
-  for s in $RAGGED_SRCS; do
-    o="$BUILD/${s%.hip}.o"
-    stale=0
-    for dep in "$s" mtcnn_post_frame.h area_resize_px.h ../../include/hsefr_ragged.h build.sh; do
-      if [ ! -f "$o" ] || [ "$dep" -nt "$o" ]; then stale=1; fi
-    done
-    if [ "$stale" = 1 ]; then
-      rm -f "$o"
-      hipcc $RAGGED_FLAGS -Xarch_host -Os ${HSEFR_EXTRA_FLAGS:-} -c "$s" -o "$o"
-    fi
-    RAGGED_OBJS="$RAGGED_OBJS $o"
-  done
-  hipcc $LINK -shared -fPIC -o "$RAGGED_OUT" $RAGGED_OBJS
-  /opt/rocm/lib/llvm/bin/llvm-strip --strip-all -w --keep-symbol='_ZN*_kernel*' --keep-symbol='!*__device_stub__*' "$RAGGED_OUT"
-  python3 ../../tools/isa_lint.py "$RAGGED_OUT"
-  echo "built $(realpath $RAGGED_OUT)"
-  # the sixth library: built, stripped and linted as the fifth; stale against the headers it shares with the second and the third too
-  MIXED_OUT=../libhsefr_mixed.so
-  MIXED_OBJS=""
-  for s in $MIXED_SRCS; do
-    o="$BUILD/${s%.hip}.o"
-    stale=0
-    for dep in "$s" cv_linear_px.h frames_px.h ../../include/hsefr_mixed.h build.sh; do
-      if [ ! -f "$o" ] || [ "$dep" -nt "$o" ]; then stale=1; fi
-    done
-    if [ "$stale" = 1 ]; then
-      rm -f "$o"
-      hipcc $MIXED_FLAGS -Xarch_host -Os ${HSEFR_EXTRA_FLAGS:-} -c "$s" -o "$o"
-    fi
-    MIXED_OBJS="$MIXED_OBJS $o"
-  done
-  hipcc $LINK -shared -fPIC -o "$MIXED_OUT" $MIXED_OBJS
-  /opt/rocm/lib/llvm/bin/llvm-strip --strip-all -w --keep-symbol='_ZN*_kernel*' --keep-symbol='!*__device_stub__*' "$MIXED_OUT"
-  python3 ../../tools/isa_lint.py "$MIXED_OUT"
-  echo "built $(realpath $MIXED_OUT)"
-  # the seventh library: built, stripped and linted as the sixth; stale against the headers it shares with libhsefr.so too
-  SPLIT_OUT=../libhsefr_split.so
-  SPLIT_OBJS=""
-  for s in $SPLIT_SRCS; do
-    o="$BUILD/${s%.hip}.o"
-    stale=0
-    for dep in "$s" linkage_scan.h mfma_dot.h common.h ../../include/hsefr.h ../../include/hsefr_split.h build.sh; do
-      if [ ! -f "$o" ] || [ "$dep" -nt "$o" ]; then stale=1; fi
-    done
-    if [ "$stale" = 1 ]; then
-      rm -f "$o"
-      hipcc $SPLIT_FLAGS -Xarch_host -Os ${HSEFR_EXTRA_FLAGS:-} -c "$s" -o "$o"
-    fi
-    SPLIT_OBJS="$SPLIT_OBJS $o"
-  done
-  hipcc $LINK -shared -fPIC -o "$SPLIT_OUT" $SPLIT_OBJS
-  /opt/rocm/lib/llvm/bin/llvm-strip --strip-all -w --keep-symbol='_ZN*_kernel*' --keep-symbol='!*__device_stub__*' "$SPLIT_OUT"
-  python3 ../../tools/isa_lint.py "$SPLIT_OUT"
-  echo "built $(realpath $SPLIT_OUT)"
-  # the eighth library: built, stripped and linted as the seventh; stale against the headers it shares with libhsefr.so too
-  GEOM_OUT=../libhsefr_geom.so
-  GEOM_OBJS=""
-  for s in $GEOM_SRCS; do
-    o="$BUILD/geom_${s%.hip}.o"
-    stale=0
-    for dep in "$s" hier_build.h geom_rules.h linkage_scan.h mfma_dot.h common.h ../../include/hsefr.h ../../include/hsefr_geom.h build.sh; do
-      if [ ! -f "$o" ] || [ "$dep" -nt "$o" ]; then stale=1; fi
-    done
-    if [ "$stale" = 1 ]; then
-      rm -f "$o"
-      hipcc $GEOM_FLAGS -Xarch_host -Os ${HSEFR_EXTRA_FLAGS:-} -c "$s" -o "$o"
-    fi
-    GEOM_OBJS="$GEOM_OBJS $o"
-  done
-  hipcc $LINK -shared -fPIC -o "$GEOM_OUT" $GEOM_OBJS
-  /opt/rocm/lib/llvm/bin/llvm-strip --strip-all -w --keep-symbol='_ZN*_kernel*' --keep-symbol='!*__device_stub__*' "$GEOM_OUT"
-  python3 ../../tools/isa_lint.py "$GEOM_OUT"
-  echo "built $(realpath $GEOM_OUT)"
-fi
+xargs -r -P 16 -L 1 hipcc < "$BUILD/compile.list"
+
+# link, strip, lint and report one row
+build_lib() {
+  row "$1"
+  objs=""
+  for s in $srcs; do objs="$objs $(object "$s")"; done
+  if [ "$MODE" = hostonly ]; then
+    # host-only objects still reference their translation unit's device image (__hip_fatbin_<id>, registered with the HIP runtime when the
+    # library is loaded and parsed lazily at a first launch, which never happens here): empty images stand in for the device code that was
+    # not compiled
+    nm -u $objs | grep -o "__hip_fatbin_[0-9a-f]*" | sort -u |
+      awk '{print "__attribute__((visibility(\"default\"), aligned(4096))) const char " $1 "[4096] = {0};"}' > "$BUILD/fatbin_stubs.c"
+    /opt/rocm/lib/llvm/bin/clang -fPIC -c "$BUILD/fatbin_stubs.c" -o "$BUILD/fatbin_stubs.o"
+    objs="$objs $BUILD/fatbin_stubs.o"
+  fi
+  hipcc $LINK -shared -fPIC -o "$out" $objs
+  if [ "$name" != hsefr ] || [ "$MODE" = product ]; then
+    # a shipped library goes without most of its host symbol table (.symtab / .strtab, about 70 KB of 100 in libhsefr.so): the exported
+    # functions are in .dynsym and the device kernels' symbols in .hip_fatbin, both untouched; of .symtab only the kernels' host-side
+    # handles stay, the data symbols from which hsefr_plan_describe reads a launched kernel's name and template arguments (engine.hip,
+    # stub_names)
+    /opt/rocm/lib/llvm/bin/llvm-strip --strip-all -w --keep-symbol="$keep" --keep-symbol='!*__device_stub__*' "$out"
+  fi
+  if [ "$MODE" = hostonly ]; then
+    hipcc $SAN_EXE_FLAGS -x c++ fuzz_plan.cc -o "$BUILD/fuzz_plan" -L"$BUILD" -lhsefr_asan -Wl,-rpath,"$(realpath $BUILD)"
+  else
+    # refuse a library with an unguarded gfx950 store-data hazard (see tools/isa_lint.py)
+    python3 ../../tools/isa_lint.py "$out"
+  fi
+  echo "built $(realpath $out)"
+}
+for r in "${LIBS[@]}"; do build_lib "$r"; done

@@ -1,74 +1,21 @@
-"""CPU suite: the frame front end without a GPU -- the ABI of libhsefr_frames.so (include/hsefr_frames.h, the library's dynamic symbols and
-_lib.FRAMES_SIGNATURES agree; gfx950 only; the ISA lint; every refused argument combination returns a status and a message before
-any device work), the input rules of preprocess_device.prepare_frames, the rotation rule of process_images and of both album
-functions, and the two other libraries' headers untouched."""
+"""CPU suite: the frame front end without a GPU -- the names libhsefr_frames.so exports (what holds for every library is in
+tests/test_libraries_cpu.py), every refused argument combination returns a status and a message before any device work, the input
+rules of preprocess_device.prepare_frames, and the rotation rule of process_images and of both album functions."""
 import ctypes
-import importlib.util
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "hsefr_frames.h")
 NAMES = ["hsefr_frames_last_error_string", "hsefr_frames_prepare", "hsefr_frames_version"]
-
-
-def declared(header, prefix):
-    src = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(%s[a-z0-9_]+)\s*\(" % prefix, src)))
 
 
 # ---- the library -----------------------------------------------------------------------------------------------------------------
 def test_header_library_and_binding_agree():
     from hse_facerec_tf_amd import _lib
-    assert declared(HEADER, "hsefr_frames_") == NAMES
-    assert os.path.exists(_lib.FRAMES_LIB_PATH), "run __graft_entry__.build() first"
-    assert os.path.basename(_lib.FRAMES_LIB_PATH) == os.environ.get("HSEFR_FRAMES_LIB", "libhsefr_frames.so")
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.FRAMES_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = sorted(l.split()[-1] for l in out.splitlines() if " T " in l and not l.split()[-1].startswith(("_init", "_fini")))
-    assert exported == NAMES
     assert sorted(_lib.FRAMES_SIGNATURES) == NAMES
-    L = _lib.frames_lib()
-    assert L.hsefr_frames_version() == 100
-    assert int(re.search(r"#define HSEFR_FRAMES_VERSION (\d+)", open(HEADER).read()).group(1)) == 100
-    assert _lib.frames_lib() is L                                                       # loaded once
-
-
-def test_the_other_two_libraries_are_untouched():
-    from hse_facerec_tf_amd import _lib
-    for header in ("hsefr.h", "hsefr_album.h"):
-        assert "hsefr_frames_" not in open(os.path.join(ROOT, "include", header)).read(), header
-    assert not [n for n in list(_lib.SIGNATURES) + list(_lib.ALBUM_SIGNATURES) if n.startswith("hsefr_frames")]
-    assert sorted(_lib.ALBUM_SIGNATURES) == declared(os.path.join(ROOT, "include", "hsefr_album.h"), "hsefr_album_")
-    assert os.path.getsize(_lib.LIB_PATH) < 4_000_000
     assert "HSEFR_KNOB" not in open(os.path.join(ROOT, "hse_facerec_tf_amd", "csrc", "frames.hip")).read()
-    for lib in (_lib.LIB_PATH, _lib.ALBUM_LIB_PATH):                                    # neither exports a name of the third
-        out = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True, check=True).stdout
-        assert "hsefr_frames_" not in out, lib
-
-
-def test_frames_code_object_targets_gfx950_only():
-    from hse_facerec_tf_amd import _lib
-    blob = open(_lib.FRAMES_LIB_PATH, "rb").read()
-    assert b"gfx950" in blob
-    for other in (b"gfx942", b"gfx90a", b"sm_90", b"gfx1100"):
-        assert other not in blob
-
-
-def test_frames_device_code_passes_the_isa_lint():
-    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump"):
-        pytest.skip("no llvm-objdump on this machine")
-    spec = importlib.util.spec_from_file_location("isa_lint", os.path.join(ROOT, "tools", "isa_lint.py"))
-    lint = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(lint)
-    from hse_facerec_tf_amd import _lib
-    findings, n_symbols, n_stores = lint.lint(_lib.FRAMES_LIB_PATH)
-    # the vector forms of both kernels: swap_kernel<true>, and the three turn_kernel instances with a 12-byte side
-    assert n_symbols >= 6 and n_stores >= 3, "the lint did not see the kernels and their 12-byte stores"
-    assert findings == []
 
 
 def test_prepare_checks_its_arguments_without_a_gpu():

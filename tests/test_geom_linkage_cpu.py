@@ -1,19 +1,18 @@
 """CPU suite: centroid, median and Ward linkage without a GPU -- the NumPy restatements the GPU suite compares with are scipy's trees on
 every dense input that suite uses (so the GPU suite stands on inputs the reference alone passes), clustering.linkage_from_sequence,
-flat cuts of a tree with inversions, the names the entry points take and refuse, the ABI of libhsefr_geom.so (include/hsefr_geom.h, the
-library's dynamic symbols and _lib.GEOM_SIGNATURES agree; the other seven libraries untouched) and every refused argument of
-hsefr_geom_linkage before any device work."""
+flat cuts of a tree with inversions, the names the entry points take and refuse, the names libhsefr_geom.so exports with its header's
+limit and enum (what holds for every library is in tests/test_libraries_cpu.py) and every refused argument of hsefr_geom_linkage
+before any device work."""
 import ctypes
-import importlib.util
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 from scipy.cluster import hierarchy as hac
 from scipy.spatial.distance import squareform
 
+import build_table
 import geom_linkage_ref as gref
 import linkage_ref as ref
 
@@ -21,12 +20,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "hse_facerec_tf_amd", "csrc")
 HEADER = os.path.join(ROOT, "include", "hsefr_geom.h")
 NAMES = ["hsefr_geom_last_error", "hsefr_geom_linkage", "hsefr_geom_version"]
-OTHER_HEADERS = ("hsefr.h", "hsefr_album.h", "hsefr_frames.h", "hsefr_forest.h", "hsefr_ragged.h", "hsefr_mixed.h", "hsefr_split.h")
-
-
-def exported(path, kind=" T "):
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    return sorted(l.split()[-1] for l in out.splitlines() if kind in l and not l.split()[-1].startswith(("_init", "_fini")))
 
 
 # ---- the restatement is scipy ------------------------------------------------------------------------------------------------------
@@ -189,48 +182,25 @@ def test_header_library_and_binding_agree():
     from hse_facerec_tf_amd import _lib, ops
     header = open(HEADER).read()
     code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    assert sorted(set(re.findall(r"\b(hsefr_geom_[a-z0-9_]+)\s*\(", code))) == NAMES
-    assert os.path.exists(_lib.GEOM_LIB_PATH), "run __graft_entry__.build() first"
-    assert os.path.basename(_lib.GEOM_LIB_PATH) == os.environ.get("HSEFR_GEOM_LIB", "libhsefr_geom.so")
-    assert exported(_lib.GEOM_LIB_PATH) == NAMES
     assert sorted(_lib.GEOM_SIGNATURES) == NAMES
-    L = _lib.geom_lib()
-    assert L.hsefr_geom_version() == 100 and int(re.search(r"#define HSEFR_GEOM_VERSION (\d+)", header).group(1)) == 100
-    assert _lib.geom_lib() is L                                                         # loaded once
-    assert isinstance(_lib.geom_last_error(), str)
     args = re.search(r"int hsefr_geom_linkage\((.*?)\);", code, flags=re.S).group(1)
     assert len(args.split(",")) == len(_lib.GEOM_SIGNATURES["hsefr_geom_linkage"][1]) == 14
     assert int(re.search(r"#define HSEFR_GEOM_LDS_MAX (\d+)", header).group(1)) == ops.GEOM_LDS_MAX == 128
     assert {ops.GEOM_LDS_MAX - 1, ops.GEOM_LDS_MAX, ops.GEOM_LDS_MAX + 1} <= set(gref.DENSE_NS)      # the GPU suite stands on both sides
     enum = re.search(r"enum \{ HSEFR_GEOM_CENTROID = (\d), HSEFR_GEOM_MEDIAN = (\d), HSEFR_GEOM_WARD = (\d) \};", header).groups()
     assert [int(v) for v in enum] == [ops.GEOM_METHODS[m] for m in ("centroid", "median", "ward")]
-    assert exported(_lib.GEOM_LIB_PATH, " W ") == []                                    # nothing of the C++ runtime's templates
-    blob = open(_lib.GEOM_LIB_PATH, "rb").read()
-    assert b"gfx950" in blob
-    for other in (b"gfx942", b"gfx90a", b"sm_90", b"gfx1100"):
-        assert other not in blob
-
-
-def test_the_other_libraries_are_untouched():
-    from hse_facerec_tf_amd import _lib
-    for header in OTHER_HEADERS:
-        assert "hsefr_geom_" not in open(os.path.join(ROOT, "include", header)).read(), header
-    others = list(_lib.SIGNATURES) + list(_lib.ALBUM_SIGNATURES) + list(_lib.FRAMES_SIGNATURES) + list(_lib.FOREST_SIGNATURES) + \
-        list(_lib.RAGGED_SIGNATURES) + list(_lib.MIXED_SIGNATURES) + list(_lib.SPLIT_SIGNATURES)
-    assert not [n for n in others if n.startswith("hsefr_geom_")]
-    for lib in (_lib.LIB_PATH, _lib.ALBUM_LIB_PATH, _lib.FRAMES_LIB_PATH, _lib.FOREST_LIB_PATH, _lib.RAGGED_LIB_PATH, _lib.MIXED_LIB_PATH,
-                _lib.SPLIT_LIB_PATH):
-        assert not [n for n in exported(lib) if n.startswith("hsefr_geom_")], lib
-    assert os.path.getsize(_lib.LIB_PATH) < 4_000_000
-    assert _lib.lib().hsefr_version() == 141
 
 
 def test_the_rounds_and_the_matrix_are_compiled_twice_not_written_twice():
     """Ward's rounds, the matrix build and the row rescan are hier_linkage.hip's, compiled into this library under one macro; without the
     macro that file is what libhsefr.so has always compiled."""
-    build = open(os.path.join(CSRC, "build.sh")).read()
-    assert 'GEOM_SRCS="geom_linkage.hip hier_linkage.hip"' in build and 'GEOM_FLAGS="$FLAGS $DEVICE_STRIP -DHSEFR_GEOM_LIB"' in build
-    assert 'python3 ../../tools/isa_lint.py "$GEOM_OUT"' in build
+    table = build_table.rows()
+    assert table["geom"]["srcs"] == ["geom_linkage.hip", "hier_linkage.hip"] and "hier_linkage.hip" in table["hsefr"]["srcs"]
+    assert "-DHSEFR_GEOM_LIB" in table["geom"]["flags"] and "-DHSEFR_GEOM_LIB" not in table["hsefr"]["flags"]
+    assert [f for f in table["geom"]["flags"] if f != "-DHSEFR_GEOM_LIB"] == table["hsefr"]["flags"]
+    assert build_table.stale_against("geom", "linkage_scan.h", "mfma_dot.h", "common.h", "hier_build.h", "geom_rules.h", "include/hsefr.h",
+                                     "include/hsefr_geom.h")
+    assert table["geom"]["lint"] == "1"
     geom = open(os.path.join(CSRC, "geom_linkage.hip")).read()
     assert '#include "hier_build.h"' in geom and "build_working_matrix(" in geom and "rescan_rows(" in geom and "launch_ward_linkage(" in geom
     assert "feat_tile" not in geom and "hl_rescan_kernel" not in geom and "HSEFR_KNOB" not in geom
@@ -243,18 +213,6 @@ def test_the_rounds_and_the_matrix_are_compiled_twice_not_written_twice():
         r"#ifndef HSEFR_GEOM_LIB(.*?)#else.*?#endif", r"\1", src, flags=re.S), flags=re.S)
     rules = open(os.path.join(CSRC, "geom_rules.h")).read()
     assert rules.count("#pragma clang fp contract(off)") == 3
-
-
-def test_geom_device_code_passes_the_isa_lint():
-    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump"):
-        pytest.skip("no llvm-objdump on this machine")
-    spec = importlib.util.spec_from_file_location("isa_lint", os.path.join(ROOT, "tools", "isa_lint.py"))
-    lint = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(lint)
-    from hse_facerec_tf_amd import _lib
-    findings, n_symbols, n_stores = lint.lint(_lib.GEOM_LIB_PATH)
-    assert n_symbols >= 10, "the lint did not see the kernels"            # the rounds' seven, the engine's four
-    assert findings == []
 
 
 def test_geom_linkage_checks_its_arguments_without_a_gpu():

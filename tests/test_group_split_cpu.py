@@ -1,49 +1,28 @@
-"""CPU suite: the same-photo split's library without a GPU -- the ABI of libhsefr_split.so (include/hsefr_split.h, the library's dynamic
-symbols and _lib.SPLIT_SIGNATURES agree; gfx950 only; the ISA lint; the other six libraries untouched; compiled with libhsefr.so's flags
-against the shared distance headers), every refused argument of hsefr_split_groups before any device work, clustering.group_table, the
-``split`` keyword of the two entry points and of the album, and the host restatement the GPU suite compares with against scipy."""
+"""CPU suite: the same-photo split's library without a GPU -- the names libhsefr_split.so exports and the limits of its header (what
+holds for every library is in tests/test_libraries_cpu.py), compiled with libhsefr.so's flags against the shared distance headers,
+every refused argument of hsefr_split_groups before any device work, clustering.group_table, the ``split`` keyword of the two entry points and of the album, and the host restatement the GPU suite compares with against scipy."""
 import ctypes
-import importlib.util
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import build_table
 import group_split_cases as cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "hse_facerec_tf_amd", "csrc")
 HEADER = os.path.join(ROOT, "include", "hsefr_split.h")
 NAMES = ["hsefr_split_groups", "hsefr_split_last_error", "hsefr_split_version"]
-OTHER_HEADERS = ("hsefr.h", "hsefr_album.h", "hsefr_frames.h", "hsefr_forest.h", "hsefr_ragged.h", "hsefr_mixed.h")
-
-
-def declared(header, prefix):
-    src = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(%s[a-z0-9_]+)\s*\(" % prefix, src)))
-
-
-def exported(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    return sorted(l.split()[-1] for l in out.splitlines() if " T " in l and not l.split()[-1].startswith(("_init", "_fini")))
 
 
 # ---- the library -----------------------------------------------------------------------------------------------------------------
 def test_header_library_and_binding_agree():
     from hse_facerec_tf_amd import _lib, ops
-    assert declared(HEADER, "hsefr_split_") == NAMES
-    assert os.path.exists(_lib.SPLIT_LIB_PATH), "run __graft_entry__.build() first"
-    assert os.path.basename(_lib.SPLIT_LIB_PATH) == os.environ.get("HSEFR_SPLIT_LIB", "libhsefr_split.so")
-    assert exported(_lib.SPLIT_LIB_PATH) == NAMES
     assert sorted(_lib.SPLIT_SIGNATURES) == NAMES
-    L = _lib.split_lib()
-    assert L.hsefr_split_version() == 100
+    assert "HSEFR_KNOB" not in open(os.path.join(CSRC, "group_split.hip")).read()
     header = open(HEADER).read()
-    assert int(re.search(r"#define HSEFR_SPLIT_VERSION (\d+)", header).group(1)) == 100
-    assert _lib.split_lib() is L                                                        # loaded once
-    assert _lib.split_last_error() == "" or isinstance(_lib.split_last_error(), str)
     # the argument count of the one call is the header's
     args = re.search(r"int hsefr_split_groups\((.*?)\);", re.sub(r"/\*.*?\*/", "", header, flags=re.S), flags=re.S).group(1)
     assert len(args.split(",")) == len(_lib.SPLIT_SIGNATURES["hsefr_split_groups"][1]) == 16
@@ -53,23 +32,6 @@ def test_header_library_and_binding_agree():
     assert limits["STATS"] == len(ops.SPLIT_STATS) == 5
     for limit in (cases.WAVE_MAX, cases.LDS_MAX):                                      # the GPU suite stands on both sides of each
         assert {limit - 1, limit, limit + 1} <= set(cases.SIZES)
-    # nothing of the C++ runtime's templates is exported either
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.SPLIT_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert [l.split()[-1] for l in out.splitlines() if " W " in l] == []
-
-
-def test_the_other_libraries_are_untouched():
-    from hse_facerec_tf_amd import _lib
-    for header in OTHER_HEADERS:
-        assert "hsefr_split_" not in open(os.path.join(ROOT, "include", header)).read(), header
-    others = list(_lib.SIGNATURES) + list(_lib.ALBUM_SIGNATURES) + list(_lib.FRAMES_SIGNATURES) + list(_lib.FOREST_SIGNATURES) + \
-        list(_lib.RAGGED_SIGNATURES) + list(_lib.MIXED_SIGNATURES)
-    assert not [n for n in others if n.startswith("hsefr_split_")]
-    for lib in (_lib.LIB_PATH, _lib.ALBUM_LIB_PATH, _lib.FRAMES_LIB_PATH, _lib.FOREST_LIB_PATH, _lib.RAGGED_LIB_PATH, _lib.MIXED_LIB_PATH):
-        assert not [n for n in exported(lib) if n.startswith("hsefr_split_")], lib
-    assert os.path.getsize(_lib.LIB_PATH) < 4_000_000
-    assert _lib.lib().hsefr_version() == 141
-    assert "HSEFR_KNOB" not in open(os.path.join(CSRC, "group_split.hip")).read()
 
 
 def test_the_library_compiles_the_shared_distance_with_the_main_librarys_flags():
@@ -78,31 +40,10 @@ def test_the_library_compiles_the_shared_distance_with_the_main_librarys_flags()
     src = open(os.path.join(CSRC, "group_split.hip")).read()
     assert '#include "linkage_scan.h"' in src and "link::feat_tile(" in src and "link::better(" in src
     assert not re.search(r"__device__[^;{]*\bfeat_tile\(", src) and "mfma_f32_32x32x2f32" not in src      # called, not written again
-    build = open(os.path.join(CSRC, "build.sh")).read()
-    assert 'SPLIT_SRCS="group_split.hip"' in build and 'SPLIT_FLAGS="$FLAGS $DEVICE_STRIP"' in build
-    assert 'for dep in "$s" linkage_scan.h mfma_dot.h common.h ../../include/hsefr.h ../../include/hsefr_split.h build.sh' in build
-    assert 'python3 ../../tools/isa_lint.py "$SPLIT_OUT"' in build
-
-
-def test_split_code_object_targets_gfx950_only():
-    from hse_facerec_tf_amd import _lib
-    blob = open(_lib.SPLIT_LIB_PATH, "rb").read()
-    assert b"gfx950" in blob
-    for other in (b"gfx942", b"gfx90a", b"sm_90", b"gfx1100"):
-        assert other not in blob
-
-
-def test_split_device_code_passes_the_isa_lint():
-    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump"):
-        pytest.skip("no llvm-objdump on this machine")
-    spec = importlib.util.spec_from_file_location("isa_lint", os.path.join(ROOT, "tools", "isa_lint.py"))
-    lint = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(lint)
-    from hse_facerec_tf_amd import _lib
-    findings, n_symbols, n_stores = lint.lint(_lib.SPLIT_LIB_PATH)
-    assert n_symbols >= 4, "the lint did not see the kernels"            # the build and the three chain instances
-    assert n_stores >= 1, "the lint did not see the wide stores"         # the build's pair of matrix entries
-    assert findings == []
+    table = build_table.rows()
+    assert table["split"]["srcs"] == ["group_split.hip"] and table["split"]["flags"] == table["hsefr"]["flags"]
+    assert build_table.stale_against("split", "linkage_scan.h", "mfma_dot.h", "common.h", "include/hsefr.h", "include/hsefr_split.h")
+    assert table["split"]["lint"] == "1"
 
 
 # ---- argument checks before any device work ------------------------------------------------------------------------------------------

@@ -1,15 +1,14 @@
-"""CPU suite: the device stages of a mixed-size pass without a GPU -- the ABI of libhsefr_mixed.so (include/hsefr_mixed.h, the library's
-dynamic symbols and _lib.MIXED_SIGNATURES agree; gfx950 only; the ISA lint; the other five libraries untouched), the per-pixel bodies it
-shares with album.hip and frames.hip, every refused argument of its two entry points and of their Python wrappers before any device
+"""CPU suite: the device stages of a mixed-size pass without a GPU -- the names libhsefr_mixed.so exports and its table's layout (what
+holds for every library is in tests/test_libraries_cpu.py), the per-pixel bodies it shares with album.hip and frames.hip, every refused argument of its two entry points and of their Python wrappers before any device
 work, PackedFrames' layout, which side of a quarter turn takes which path for the shapes the GPU suite uses, and the album's keyword."""
 import ctypes
-import importlib.util
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
+
+import build_table
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "hse_facerec_tf_amd", "csrc")
@@ -19,31 +18,11 @@ NAMES = ["hsefr_mixed_face_crops", "hsefr_mixed_frames_prepare", "hsefr_mixed_la
 SHAPES = [(72, 132), (64, 48), (66, 40), (40, 70), (37, 53), (68, 36), (5, 7), (1, 9), (9, 1), (66, 129), (12, 12)]
 
 
-def declared(header, prefix):
-    src = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(%s[a-z0-9_]+)\s*\(" % prefix, src)))
-
-
-def exported(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    return sorted(l.split()[-1] for l in out.splitlines() if " T " in l and not l.split()[-1].startswith(("_init", "_fini")))
-
-
 # ---- the library -----------------------------------------------------------------------------------------------------------------
 def test_header_library_and_binding_agree():
     from hse_facerec_tf_amd import _lib
-    assert declared(HEADER, "hsefr_mixed_") == NAMES
-    assert os.path.exists(_lib.MIXED_LIB_PATH), "run __graft_entry__.build() first"
-    assert os.path.basename(_lib.MIXED_LIB_PATH) == os.environ.get("HSEFR_MIXED_LIB", "libhsefr_mixed.so")
-    assert exported(_lib.MIXED_LIB_PATH) == NAMES
     assert sorted(_lib.MIXED_SIGNATURES) == NAMES
-    L = _lib.mixed_lib()
-    assert L.hsefr_mixed_version() == 100
-    assert int(re.search(r"#define HSEFR_MIXED_VERSION (\d+)", open(HEADER).read()).group(1)) == 100
-    assert _lib.mixed_lib() is L                                                        # loaded once
-    # nothing of the C++ runtime's templates is exported either: the four entries and the HIP module's id
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.MIXED_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert [l.split()[-1] for l in out.splitlines() if " W " in l] == []
+    assert "HSEFR_KNOB" not in open(os.path.join(CSRC, "mixed_frames.hip")).read()
 
 
 def test_the_table_has_the_headers_layout():
@@ -53,21 +32,6 @@ def test_the_table_has_the_headers_layout():
     assert fields == list(mr.MIXED_FRAME_DT.names) == ["offset", "h", "w"]
     assert mr.MIXED_FRAME_DT.itemsize == int(size) == 16
     assert [mr.MIXED_FRAME_DT.fields[f][1] for f in fields] == [0, 8, 12]
-
-
-def test_the_other_libraries_are_untouched():
-    from hse_facerec_tf_amd import _lib
-    for header in ("hsefr.h", "hsefr_album.h", "hsefr_frames.h", "hsefr_forest.h", "hsefr_ragged.h"):
-        assert "hsefr_mixed_" not in open(os.path.join(ROOT, "include", header)).read(), header
-    others = list(_lib.SIGNATURES) + list(_lib.ALBUM_SIGNATURES) + list(_lib.FRAMES_SIGNATURES) + list(_lib.FOREST_SIGNATURES) + \
-        list(_lib.RAGGED_SIGNATURES)
-    assert not [n for n in others if n.startswith("hsefr_mixed_")]
-    for lib in (_lib.LIB_PATH, _lib.ALBUM_LIB_PATH, _lib.FRAMES_LIB_PATH, _lib.FOREST_LIB_PATH, _lib.RAGGED_LIB_PATH):
-        assert not [n for n in exported(lib) if n.startswith("hsefr_mixed_")], lib
-    assert os.path.getsize(_lib.LIB_PATH) < 4_000_000
-    assert _lib.lib().hsefr_version() == 141
-    assert (_lib.album_lib().hsefr_album_version(), _lib.frames_lib().hsefr_frames_version()) == (100, 100)
-    assert "HSEFR_KNOB" not in open(os.path.join(CSRC, "mixed_frames.hip")).read()
 
 
 def test_the_libraries_compile_the_shared_per_pixel_bodies():
@@ -89,32 +53,15 @@ def test_the_libraries_compile_the_shared_per_pixel_bodies():
         for body in cv_bodies + px_bodies:
             assert not re.search(r"__device__[^;{]*\b%s\(" % body, src), (source, body)       # called, not defined again
         assert not re.search(r"struct[^;{]*\bPx4\s*\{", src), source
-    build = open(os.path.join(CSRC, "build.sh")).read()
-    assert 'for dep in "$s" cv_linear_px.h ../../include/hsefr_album.h build.sh' in build
-    assert 'for dep in "$s" frames_px.h ../../include/hsefr_frames.h build.sh' in build
-    assert 'for dep in "$s" cv_linear_px.h frames_px.h ../../include/hsefr_mixed.h build.sh' in build
-    assert 'MIXED_FLAGS="$FLAGS $DEVICE_STRIP -ffp-contract=off"' in build
-
-
-def test_mixed_code_object_targets_gfx950_only():
-    from hse_facerec_tf_amd import _lib
-    blob = open(_lib.MIXED_LIB_PATH, "rb").read()
-    assert b"gfx950" in blob
-    for other in (b"gfx942", b"gfx90a", b"sm_90", b"gfx1100"):
-        assert other not in blob
-
-
-def test_mixed_device_code_passes_the_isa_lint():
-    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump"):
-        pytest.skip("no llvm-objdump on this machine")
-    spec = importlib.util.spec_from_file_location("isa_lint", os.path.join(ROOT, "tools", "isa_lint.py"))
-    lint = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(lint)
-    from hse_facerec_tf_amd import _lib
-    findings, n_symbols, n_stores = lint.lint(_lib.MIXED_LIB_PATH)
-    assert n_symbols >= 4, "the lint did not see the kernels"            # the swap, the turn, two crop instances
-    assert n_stores >= 4, "the lint did not see the wide stores"         # the swap's unit, the turn's two directions, the crops' 16 bytes
-    assert findings == []
+    # each is rebuilt when a header it includes changes, and the crops' taps round twice in both libraries
+    assert build_table.stale_against("album", "cv_linear_px.h", "include/hsefr_album.h")
+    assert build_table.stale_against("frames", "frames_px.h", "include/hsefr_frames.h")
+    assert build_table.stale_against("mixed", "cv_linear_px.h", "frames_px.h", "include/hsefr_mixed.h")
+    table = build_table.rows()
+    assert "-ffp-contract=off" in table["mixed"]["flags"] and "-ffp-contract=off" in table["album"]["flags"]
+    assert "-ffp-contract=off" not in table["hsefr"]["flags"] and "-ffp-contract=off" not in table["frames"]["flags"]
+    assert [f for f in table["mixed"]["flags"] if f != "-ffp-contract=off"] == table["hsefr"]["flags"] == table["frames"]["flags"]
+    assert table["mixed"]["flags"] == table["album"]["flags"] and table["mixed"]["srcs"] == ["mixed_frames.hip"]
 
 
 # ---- argument checks before any device work ------------------------------------------------------------------------------------------

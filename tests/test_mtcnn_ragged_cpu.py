@@ -1,15 +1,14 @@
-"""CPU suite: the mixed-size detector pass without a GPU -- the ABI of libhsefr_ragged.so (include/hsefr_ragged.h, the library's dynamic
-symbols and _lib.RAGGED_SIGNATURES agree; gfx950 only; the ISA lint; libhsefr.so and the other headers untouched), every entry point's
-argument checks before any device work, and the two pure planning functions: mtcnn.ragged_plan (the tables the kernels read) and
+"""CPU suite: the mixed-size detector pass without a GPU -- the names libhsefr_ragged.so exports, its tables' layout and the bodies it
+shares with libhsefr.so (what holds for every library is in tests/test_libraries_cpu.py), every entry point's argument checks before any device work, and the two pure planning functions: mtcnn.ragged_plan (the tables the kernels read) and
 mtcnn.plan_mixed_passes (which frames share which pass)."""
 import ctypes
-import importlib.util
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
+
+import build_table
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "hsefr_ragged.h")
@@ -19,28 +18,12 @@ SHAPES = [(588, 784), (784, 588), (480, 600), (294, 392), (90, 200), (20, 500), 
 MINSIZE, FACTOR = 32, 0.709
 
 
-def declared(header, prefix):
-    src = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(%s[a-z0-9_]+)\s*\(" % prefix, src)))
-
-
-def exported(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    return sorted(l.split()[-1] for l in out.splitlines() if " T " in l and not l.split()[-1].startswith(("_init", "_fini")))
-
-
 # ---- the library -----------------------------------------------------------------------------------------------------------------
 def test_header_library_and_binding_agree():
     from hse_facerec_tf_amd import _lib
-    assert declared(HEADER, "hsefr_ragged_") == NAMES
-    assert os.path.exists(_lib.RAGGED_LIB_PATH), "run __graft_entry__.build() first"
-    assert os.path.basename(_lib.RAGGED_LIB_PATH) == os.environ.get("HSEFR_RAGGED_LIB", "libhsefr_ragged.so")
-    assert exported(_lib.RAGGED_LIB_PATH) == NAMES
     assert sorted(_lib.RAGGED_SIGNATURES) == NAMES
+    assert "HSEFR_KNOB" not in open(os.path.join(ROOT, "hse_facerec_tf_amd", "csrc", "mtcnn_ragged.hip")).read()
     L = _lib.ragged_lib()
-    assert L.hsefr_ragged_version() == 100
-    assert int(re.search(r"#define HSEFR_RAGGED_VERSION (\d+)", open(HEADER).read()).group(1)) == 100
-    assert _lib.ragged_lib() is L                                                       # loaded once
     # the list capacity is the shared header's constant in both libraries
     assert L.hsefr_ragged_capacity() == _lib.lib().hsefr_mtcnn_post_capacity()
 
@@ -62,19 +45,6 @@ def test_the_tables_have_the_headers_layout():
                 at += widths[ctype]
 
 
-def test_the_other_libraries_are_untouched():
-    from hse_facerec_tf_amd import _lib
-    for header in ("hsefr.h", "hsefr_album.h", "hsefr_frames.h", "hsefr_forest.h"):
-        assert "hsefr_ragged" not in open(os.path.join(ROOT, "include", header)).read(), header
-    others = list(_lib.SIGNATURES) + list(_lib.ALBUM_SIGNATURES) + list(_lib.FRAMES_SIGNATURES) + list(_lib.FOREST_SIGNATURES)
-    assert not [n for n in others if n.startswith("hsefr_ragged")]
-    assert os.path.getsize(_lib.LIB_PATH) < 4_000_000
-    assert _lib.lib().hsefr_version() == 141
-    for lib in (_lib.LIB_PATH, _lib.ALBUM_LIB_PATH, _lib.FRAMES_LIB_PATH, _lib.FOREST_LIB_PATH):
-        assert not [n for n in exported(lib) if n.startswith("hsefr_ragged")], lib
-    assert "HSEFR_KNOB" not in open(os.path.join(ROOT, "hse_facerec_tf_amd", "csrc", "mtcnn_ragged.hip")).read()
-
-
 def test_both_libraries_compile_the_shared_one_frame_bodies():
     """The bit identity rests on it: the bodies live in the two headers, and both sources include them instead of holding a copy."""
     csrc = os.path.join(ROOT, "hse_facerec_tf_amd", "csrc")
@@ -90,29 +60,10 @@ def test_both_libraries_compile_the_shared_one_frame_bodies():
             assert '#include "%s"' % h in src, (source, h)
         for body in ("stage1_level_frame", "stage1_finish_frame", "stage23_finish_frame", "area_level_pixel", "area_level_row", "area_crop_pixel"):
             assert not re.search(r"__device__[^;{]*\b%s\(" % body, src), (source, body)      # called, not defined again
-    build = open(os.path.join(csrc, "build.sh")).read()
-    assert "for dep in \"$s\" mtcnn_post_frame.h area_resize_px.h ../../include/hsefr_ragged.h build.sh" in build
-
-
-def test_ragged_code_object_targets_gfx950_only():
-    from hse_facerec_tf_amd import _lib
-    blob = open(_lib.RAGGED_LIB_PATH, "rb").read()
-    assert b"gfx950" in blob
-    for other in (b"gfx942", b"gfx90a", b"sm_90", b"gfx1100"):
-        assert other not in blob
-
-
-def test_ragged_device_code_passes_the_isa_lint():
-    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump"):
-        pytest.skip("no llvm-objdump on this machine")
-    spec = importlib.util.spec_from_file_location("isa_lint", os.path.join(ROOT, "tools", "isa_lint.py"))
-    lint = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(lint)
-    from hse_facerec_tf_amd import _lib
-    findings, n_symbols, n_stores = lint.lint(_lib.RAGGED_LIB_PATH)
-    # the pyramid, three convolution instances, the pooling, stage 1, the crops, two stage-finish instances
-    assert n_symbols >= 9, "the lint did not see the kernels"
-    assert findings == []
+    # and with the same flags, rebuilt when either header changes
+    table = build_table.rows()
+    assert table["ragged"]["flags"] == table["hsefr"]["flags"] and table["ragged"]["srcs"] == ["mtcnn_ragged.hip"]
+    assert build_table.stale_against("ragged", "mtcnn_post_frame.h", "area_resize_px.h", "include/hsefr_ragged.h")
 
 
 # ---- argument checks before any device work ------------------------------------------------------------------------------------------
