@@ -52,6 +52,16 @@ inline int launch_status(const char* what) {
     return HSEFR_OK;
 }
 
+// The three activations a kernel is instantiated for: M(A) launches instance A.  Like HSEFR_REQUIRE, any other `act` RETURNS
+// HSEFR_ERR_UNSUPPORTED from the calling launcher, with the message "<who>: act <n>"
+#define HSEFR_ACT_SWITCH(act, who, M)                                                       \
+    do {                                                                                    \
+        if ((act) == HSEFR_ACT_RELU6) M(HSEFR_ACT_RELU6);                                   \
+        else if ((act) == HSEFR_ACT_RELU) M(HSEFR_ACT_RELU);                                \
+        else if ((act) == HSEFR_ACT_NONE) M(HSEFR_ACT_NONE);                                \
+        else { ::hsefr::set_error(who ": act %d", act); return HSEFR_ERR_UNSUPPORTED; }     \
+    } while (0)
+
 // Epilogue activation.  RELU6 restates the graph's Relu -> Minimum(.,6) -> Maximum(.,0)
 // chain (nodes #32-34): max(min(max(x,0),6),0) == min(max(x,0),6).
 template <int ACT>

@@ -15,7 +15,7 @@
 //   * vertically adjacent strips (which share 2 halo rows) get workgroup ids on the same
 //     XCD (xcd_remap) so the halo re-read hits that XCD's L2.
 // Algorithmic bytes per image: 4*C*(H*W + OH*OW) + 36*C + 8*C   (SURVEY 8d).
-#include "common.h"
+#include "f16s.h"
 
 namespace hsefr {
 
@@ -27,7 +27,8 @@ HSEFR_KNOB(g_dw_variant, "dw_variant", 0);    // load-policy / grid variants
 HSEFR_KNOB(g_dw_look, "dw_look", 4, [](int v) { return v >= 2 && v <= 5 ? v : 2; });       // 2..5 rows of load lookahead, stride-1 kernel (measured in situ: 4 is best)
 HSEFR_KNOB(g_dw_look2, "dw_look2", 2, [](int v) { return v == 4 ? 4 : 2; });      // 2 | 4 = one | two iterations of lookahead, stride-2 kernel
 
-typedef float f4 __attribute__((ext_vector_type(4)));
+using f16s::f32x4;
+using f16s::f16x4;
 
 struct DwParams {
     const float4* x;
@@ -42,18 +43,17 @@ struct DwParams {
     float a_scale;  // SPLIT kernels: 2^a_log2
 };
 
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float4 ntload(const float4* p) {
-    const f4 v = __builtin_nontemporal_load((const f4*)p);
+    const f32x4 v = __builtin_nontemporal_load((const f32x4*)p);
     return make_float4(v.x, v.y, v.z, v.w);
 }
 __device__ __forceinline__ void ntstore(float4 v, float4* p) {
-    f4 t;
+    f32x4 t;
     t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w;
-    __builtin_nontemporal_store(t, (f4*)p);
+    __builtin_nontemporal_store(t, (f32x4*)p);
 }
 
 __device__ __forceinline__ float4 fma4(float4 a, float4 b, float4 c) {
@@ -64,7 +64,7 @@ __device__ __forceinline__ float4 fma4(float4 a, float4 b, float4 c) {
 // in flight per CU: the waves of this kernel spend two thirds of their life waiting on memory).
 // SPLIT = 1: the result is stored PRE-SPLIT for the split-f16 GEMM that consumes it (pwconv_ps.hip): per pixel and
 // 32-channel group one 128-byte "split row" [hi(32 x f16) | lo(32 x f16)], hi = f16(v * 2^a_log2), lo = f16(v * 2^a_log2 - hi)
-// -- the very operations pwconv_f16s.hip applies on its way into LDS, so the GEMM sees the same bits either way.  The
+// -- f16s.h's split, the very one pwconv_f16s.hip applies on its way into LDS, so the GEMM sees the same bits either way.  The
 // tensor keeps its size (4 B per element).  A thread owns 4 channels = 8 B of the hi half and 8 B of the lo half; lane
 // pairs (the quads 2j, 2j+1 of a group) swap one 8-byte half by DPP, so that every lane still issues ONE 16-byte store
 // and a wave still writes whole 128-byte lines: even quad -> [hi(2j) | hi(2j+1)], odd quad -> [lo(2j) | lo(2j+1)].
@@ -142,9 +142,8 @@ __global__ __launch_bounds__(256, LOOK == 2 ? 4 : (LOOK <= 4 ? 3 : 2)) void dwco
         o.z = apply_act<ACT>(o.z);
         o.w = apply_act<ACT>(o.w);
         if (SPLIT) {
-            const f4 v = f4{o.x, o.y, o.z, o.w} * p.a_scale;
-            const f16x4 hi = __builtin_convertvector(v, f16x4);
-            const f16x4 lo = __builtin_convertvector(v - __builtin_convertvector(hi, f4), f16x4);
+            f16x4 hi, lo;
+            f16s::split(f32x4{o.x, o.y, o.z, o.w} * p.a_scale, hi, lo);
             const u32x2 hb = __builtin_bit_cast(u32x2, hi), lb = __builtin_bit_cast(u32x2, lo);
             const bool odd = qg & 1;
             const u32x2 send = odd ? hb : lb;          // the even quad gives away its lo half, the odd quad its hi half
@@ -152,7 +151,7 @@ __global__ __launch_bounds__(256, LOOK == 2 ? 4 : (LOOK <= 4 ? 3 : 2)) void dwco
             recv.x = (unsigned)__builtin_amdgcn_mov_dpp((int)send.x, 0xB1, 0xF, 0xF, true);
             recv.y = (unsigned)__builtin_amdgcn_mov_dpp((int)send.y, 0xB1, 0xF, 0xF, true);
             const u32x4 out = odd ? u32x4{recv.x, recv.y, lb.x, lb.y} : u32x4{hb.x, hb.y, recv.x, recv.y};
-            const f4 ov = __builtin_bit_cast(f4, out);
+            const f32x4 ov = __builtin_bit_cast(f32x4, out);
             if (NT & 2) ntstore(make_float4(ov.x, ov.y, ov.z, ov.w), yout + (size_t)oh * p.OW * p.C4);
             else yout[(size_t)oh * p.OW * p.C4] = make_float4(ov.x, ov.y, ov.z, ov.w);
             return;

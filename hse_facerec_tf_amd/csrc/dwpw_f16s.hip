@@ -1,5 +1,5 @@
 // Fused depthwise 3x3 (+scale+shift+ReLU6) -> pointwise 1x1 (+shift+act) for ANY channel count, the pointwise products
-// on the f16 MFMA from two-term f16 splits (fp32-grade; arithmetic and weight image: pwconv_f16s.hip), NHWC fp32, gfx950.
+// on the f16 MFMA from two-term f16 splits (fp32-grade; row layout, split and product: f16s.h), NHWC fp32, gfx950.
 //
 // Replaces one whole MobileNet block of the frozen graph (nodes DepthwiseConv2dNative, Mul, Add, Relu, Minimum, Maximum,
 // Conv2D 1x1, Add, Relu, Minimum, Maximum -- e.g. #35-#49 -- run by tf_sess.run at facerec_test.py:120 /
@@ -24,16 +24,13 @@
 // neighbouring patches and the N-tiles of one patch share an L2) + 128 x Cout out.
 #include <type_traits>
 
-#include "common.h"
+#include "f16s.h"
 
 namespace hsefr {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+using namespace f16s;
 
 struct DwPwSParams {
     const float4* x;       // [N,H,W,C]
@@ -57,12 +54,9 @@ struct DwPwSParams {
     unsigned long long* stamps;   // diagnostic builds (-DHSEFR_STEM_STAMPS) only
 };
 
-constexpr int ROWB = 128;
-__device__ __forceinline__ int swzb(int row, int chunk) { return row * ROWB + 16 * (chunk ^ ((row >> 1) & 7) ^ ((row & 1) << 2)); }
 __device__ __forceinline__ float4 fma4(float4 a, float4 b, float4 c) {
     return make_float4(fmaf(a.x, b.x, c.x), fmaf(a.y, b.y, c.y), fmaf(a.z, b.z, c.z), fmaf(a.w, b.w, c.w));
 }
-__device__ __forceinline__ float relu6(float v) { return fminf(fmaxf(v, 0.f), 6.f); }
 // x / d by multiplication with m = ceil(2^32 / d) (m = 0 stands for d = 1): exact while x * d < 2^32
 __device__ __forceinline__ unsigned fastdiv(unsigned x, unsigned m) { return m ? __umulhi(x, m) : x; }
 
@@ -150,9 +144,7 @@ __global__ __launch_bounds__(256, OCC) void dwpw_f16s_kernel(DwPwSParams p) {
                 const float4 o = fma4(s, dsc, dsh);
                 f32x4 v;
                 v[0] = relu6(o.x); v[1] = relu6(o.y); v[2] = relu6(o.z); v[3] = relu6(o.w);
-                v = v * p.a_scale;
-                ohi[j] = __builtin_convertvector(v, f16x4);
-                olo[j] = __builtin_convertvector(v - __builtin_convertvector(ohi[j], f32x4), f16x4);
+                split(v * p.a_scale, ohi[j], olo[j]);
             };
             if (STRIDE == 1) {
                 Row r0 = load_row(ih0), r1 = load_row(ih0 + 1), r2 = load_row(ih0 + 2), r3 = load_row(ih0 + 3);
@@ -174,11 +166,7 @@ __global__ __launch_bounds__(256, OCC) void dwpw_f16s_kernel(DwPwSParams p) {
             // ---- publish ----
             __syncthreads();   // every wave is done reading the previous chunk's tiles
 #pragma unroll
-            for (int j = 0; j < RPT; ++j) {
-                const int R = (row0 + j) * TW + tw;
-                *(f16x4*)(&As[swzb(R, c4l >> 1) + 8 * (c4l & 1)]) = ohi[j];
-                *(f16x4*)(&As[swzb(R, 4 + (c4l >> 1)) + 8 * (c4l & 1)]) = olo[j];
-            }
+            for (int j = 0; j < RPT; ++j) put_quad(As, (row0 + j) * TW + tw, c4l, ohi[j], olo[j]);
 #pragma unroll
             for (int q = 0; q < BP; ++q) *(f32x4*)(&Bs[swzb(srow + 32 * q, skq)]) = rb[q];
             __syncthreads();
@@ -188,25 +176,22 @@ __global__ __launch_bounds__(256, OCC) void dwpw_f16s_kernel(DwPwSParams p) {
                 f16x8 ah[2], al[2], bh[NI], bl[NI];
 #pragma unroll
                 for (int mi = 0; mi < 2; ++mi) {
-                    ah[mi] = *(const f16x8*)(&As[swzb(arow + mi * 32, 2 * s + lh)]);
-                    al[mi] = *(const f16x8*)(&As[swzb(arow + mi * 32, 4 + 2 * s + lh)]);
+                    ah[mi] = frag(As, arow + mi * 32, 2 * s + lh);
+                    al[mi] = frag(As, arow + mi * 32, 4 + 2 * s + lh);
                 }
 #pragma unroll
                 for (int ni = 0; ni < NI; ++ni) {
-                    bh[ni] = *(const f16x8*)(&Bs[swzb(brow + ni * 32, 2 * s + lh)]);
-                    bl[ni] = *(const f16x8*)(&Bs[swzb(brow + ni * 32, 4 + 2 * s + lh)]);
+                    bh[ni] = frag(Bs, brow + ni * 32, 2 * s + lh);
+                    bl[ni] = frag(Bs, brow + ni * 32, 4 + 2 * s + lh);
                 }
 #pragma unroll
                 for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-                    for (int ni = 0; ni < NI; ++ni) {
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[mi], bh[ni], acc[mi][ni], 0, 0, 0);
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mi], bl[ni], acc[mi][ni], 0, 0, 0);
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mi], bh[ni], acc[mi][ni], 0, 0, 0);
-                    }
+                    for (int ni = 0; ni < NI; ++ni) mac3_t(ah[mi], al[mi], bh[ni], bl[ni], acc[mi][ni]);
             }
         }
-        // ---- epilogue: tile row R = th*TW + tw; accumulator register r of lane-half lh -> R = base + (r&3) + 8*(r>>2) + 4*lh
+        // ---- epilogue: tile row R = th*TW + tw; accumulator register r of lane-half lh -> R = base + acc_row(r, lh) (activations first;
+        // the lane half's 4 * lh is in Rb)
         // (full patches store unconditionally: a per-store bounds branch costs an s_waitcnt vmcnt(0) per store)
         const bool full = oh0 + TH <= p.OH && ow0 + TW <= p.OW;
         float* ybase = p.y + ((size_t)n * p.OH * p.OW) * p.Cout;
@@ -220,13 +205,13 @@ __global__ __launch_bounds__(256, OCC) void dwpw_f16s_kernel(DwPwSParams p) {
                 if (full) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int R = Rb + (r & 3) + 8 * (r >> 2);
+                        const int R = Rb + acc_row(r, 0);
                         ybase[((size_t)(oh0 + R / TW) * p.OW + ow0 + (R % TW)) * p.Cout + col] = apply_act<ACT>(fmaf(acc[mi][ni][r], ds, sh));
                     }
                 } else {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int R = Rb + (r & 3) + 8 * (r >> 2);
+                        const int R = Rb + acc_row(r, 0);
                         const int oh = oh0 + R / TW, owc = ow0 + (R % TW);
                         if (oh < p.OH && owc < p.OW)
                             ybase[((size_t)oh * p.OW + owc) * p.Cout + col] = apply_act<ACT>(fmaf(acc[mi][ni][r], ds, sh));
@@ -435,12 +420,9 @@ __global__ __launch_bounds__(256 + 64 * (BN == 256 ? 8 : 4), BN == 256 ? 1 : 2) 
                     f32x4 v;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = relu6(o[e]);
-                    v = v * p.a_scale;
-                    const f16x4 hi = __builtin_convertvector(v, f16x4);
-                    const f16x4 lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x4), f16x4);
-                    const int R = (r0 + j) * TW + col;
-                    *(f16x4*)(At + swzb(R, quad >> 1) + 8 * (quad & 1)) = hi;
-                    *(f16x4*)(At + swzb(R, 4 + (quad >> 1)) + 8 * (quad & 1)) = lo;
+                    f16x4 hi, lo;
+                    split(v * p.a_scale, hi, lo);
+                    put_quad(At, (r0 + j) * TW + col, quad, hi, lo);
                 }
                 if (++dkc == KT) { dkc = 0; hx = seam_shift(++di); STEM_STAMP_COUNT; }
             }
@@ -492,7 +474,7 @@ __global__ __launch_bounds__(256 + 64 * (BN == 256 ? 8 : 4), BN == 256 ? 1 : 2) 
                     for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
         };
         auto epilogue = [&](const Item& cur, int stage) {
-            // lane (li, lh) holds row m = li, columns 4*lh + 8*(r >> 2) + (r & 3) of each 32 x 32 block (operands swapped)
+            // lane (li, lh) holds row m = li, columns acc_row(r, lh) of each 32 x 32 block (weights first)
             unsigned char* scr = smem + B_OFF + stage * B_ST + cw * (BPW * 1024);
             const float* el = (const float*)(smem + E_OFF);
             unsigned sv[2][4];
@@ -575,22 +557,18 @@ __global__ __launch_bounds__(256 + 64 * (BN == 256 ? 8 : 4), BN == 256 ? 1 : 2) 
                     f16x8 ah[2], al[2], bh[NI], bl[NI];
 #pragma unroll
                     for (int mi = 0; mi < 2; ++mi) {
-                        ah[mi] = *(const f16x8*)(As + swzb(arow + mi * 32, 2 * s + lh));
-                        al[mi] = *(const f16x8*)(As + swzb(arow + mi * 32, 4 + 2 * s + lh));
+                        ah[mi] = frag(As, arow + mi * 32, 2 * s + lh);
+                        al[mi] = frag(As, arow + mi * 32, 4 + 2 * s + lh);
                     }
 #pragma unroll
                     for (int ni = 0; ni < NI; ++ni) {
-                        bh[ni] = *(const f16x8*)(Bs + swzb(brow + ni * 32, 2 * s + lh));
-                        bl[ni] = *(const f16x8*)(Bs + swzb(brow + ni * 32, 4 + 2 * s + lh));
+                        bh[ni] = frag(Bs, brow + ni * 32, 2 * s + lh);
+                        bl[ni] = frag(Bs, brow + ni * 32, 4 + 2 * s + lh);
                     }
 #pragma unroll
                     for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-                        for (int ni = 0; ni < NI; ++ni) {
-                            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[ni], al[mi], acc[mi][ni], 0, 0, 0);
-                            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[ni], ah[mi], acc[mi][ni], 0, 0, 0);
-                            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[ni], ah[mi], acc[mi][ni], 0, 0, 0);
-                        }
+                        for (int ni = 0; ni < NI; ++ni) mac3(bh[ni], bl[ni], ah[mi], al[mi], acc[mi][ni]);
                 }
                 if (++ckc == KT) { ckc = 0; pending = true; }
             }
@@ -756,10 +734,9 @@ __global__ __launch_bounds__(512, 1) void dwpws2_f16s_kernel(DwPwSParams p) {
                 f32x4 v;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = relu6(o[e]);
-                v = v * p.a_scale;
-                const f16x4 hi = __builtin_convertvector(v, f16x4);
-                const f16x4 lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x4), f16x4);
-                const int R = (row0 + j) * S2_T + col;
+                f16x4 hi, lo;
+                split(v * p.a_scale, hi, lo);
+                const int R = (row0 + j) * S2_T + col;      // (put_quad's two stores, spelt out: through the helper hipcc compiles this kernel differently)
                 *(f16x4*)(At + swzb(R, quad >> 1) + 8 * (quad & 1)) = hi;
                 *(f16x4*)(At + swzb(R, 4 + (quad >> 1)) + 8 * (quad & 1)) = lo;
             }
@@ -795,7 +772,7 @@ __global__ __launch_bounds__(512, 1) void dwpws2_f16s_kernel(DwPwSParams p) {
                     for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
         };
         auto epilogue = [&](const Item& cur) {
-            // lane (li, lh) holds row m = li, columns 4*lh + 8*(r >> 2) + (r & 3) of each 32 x 32 block (operands swapped); rows 0-15 and
+            // lane (li, lh) holds row m = li, columns acc_row(r, lh) of each 32 x 32 block (weights first); rows 0-15 and
             // 16-31 of a block take turns in the scratch: 8 lanes read a row back, a store writes 8 rows x 128 B
             unsigned char* scr = smem + S2_S_OFF + cw * S2_SCR;
             const float* el = (const float*)(smem + S2_E_OFF);
@@ -868,22 +845,18 @@ __global__ __launch_bounds__(512, 1) void dwpws2_f16s_kernel(DwPwSParams p) {
                 f16x8 ah[2], al[2], bh[2], bl[2];
 #pragma unroll
                 for (int mi = 0; mi < 2; ++mi) {
-                    ah[mi] = *(const f16x8*)(As + swzb(li + mi * 32, 2 * s + lh));
-                    al[mi] = *(const f16x8*)(As + swzb(li + mi * 32, 4 + 2 * s + lh));
+                    ah[mi] = frag(As, li + mi * 32, 2 * s + lh);
+                    al[mi] = frag(As, li + mi * 32, 4 + 2 * s + lh);
                 }
 #pragma unroll
                 for (int ni = 0; ni < 2; ++ni) {
-                    bh[ni] = *(const f16x8*)(Bs + swzb(brow + ni * 32, 2 * s + lh));
-                    bl[ni] = *(const f16x8*)(Bs + swzb(brow + ni * 32, 4 + 2 * s + lh));
+                    bh[ni] = frag(Bs, brow + ni * 32, 2 * s + lh);
+                    bl[ni] = frag(Bs, brow + ni * 32, 4 + 2 * s + lh);
                 }
 #pragma unroll
                 for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-                    for (int ni = 0; ni < 2; ++ni) {
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[ni], al[mi], acc[mi][ni], 0, 0, 0);
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[ni], ah[mi], acc[mi][ni], 0, 0, 0);
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[ni], ah[mi], acc[mi][ni], 0, 0, 0);
-                    }
+                    for (int ni = 0; ni < 2; ++ni) mac3(bh[ni], bl[ni], ah[mi], al[mi], acc[mi][ni]);
             }
             if (++ckc == S2_KT) { ckc = 0; pending = true; }
         }
@@ -907,10 +880,7 @@ int launch_t(DwPwSParams& p, int n, int act, hipStream_t s) {
     const unsigned cap = 256u * OCC;
     const unsigned g = p.total < cap ? p.total : cap;
 #define HSEFR_DWPWS(A) HSEFR_LAUNCH((dwpw_f16s_kernel<STRIDE, TW, BN, OCC, A>), dim3(g), dim3(256), 0, s, p)
-    if (act == HSEFR_ACT_RELU6) HSEFR_DWPWS(HSEFR_ACT_RELU6);
-    else if (act == HSEFR_ACT_RELU) HSEFR_DWPWS(HSEFR_ACT_RELU);
-    else if (act == HSEFR_ACT_NONE) HSEFR_DWPWS(HSEFR_ACT_NONE);
-    else { set_error("dwpw_f16split: act %d", act); return HSEFR_ERR_UNSUPPORTED; }
+    HSEFR_ACT_SWITCH(act, "dwpw_f16split", HSEFR_DWPWS);
 #undef HSEFR_DWPWS
     return launch_status("dwpw_f16split");
 }
@@ -945,10 +915,7 @@ int launch_v3(DwPwSParams& p, int n, int act, bool strip, hipStream_t s) {
                   HSEFR_ERR_UNSUPPORTED, "dwpw_f16split: grid too large for the quotient multipliers");
     const unsigned g = p.total < 256u ? p.total : 256u;
 #define HSEFR_DWPW3(A) HSEFR_LAUNCH((dwpw3_f16s_kernel<TW, BN, HS, A>), dim3(g), dim3(256 + 64 * (BN == 256 ? 8 : 4)), 0, s, p)
-    if (act == HSEFR_ACT_RELU6) HSEFR_DWPW3(HSEFR_ACT_RELU6);
-    else if (act == HSEFR_ACT_RELU) HSEFR_DWPW3(HSEFR_ACT_RELU);
-    else if (act == HSEFR_ACT_NONE) HSEFR_DWPW3(HSEFR_ACT_NONE);
-    else { set_error("dwpw_f16split: act %d", act); return HSEFR_ERR_UNSUPPORTED; }
+    HSEFR_ACT_SWITCH(act, "dwpw_f16split", HSEFR_DWPW3);
 #undef HSEFR_DWPW3
     return launch_status("dwpw_f16split");
 }
@@ -966,10 +933,7 @@ int launch_s2(DwPwSParams& p, int n, int act, hipStream_t s) {
                   "dwpw_f16split: grid too large for the quotient multipliers");
     const unsigned g = p.total < S2_GRID ? p.total : S2_GRID;
 #define HSEFR_DWPWS2(A) HSEFR_LAUNCH((dwpws2_f16s_kernel<A>), dim3(g), dim3(512), 0, s, p)
-    if (act == HSEFR_ACT_RELU6) HSEFR_DWPWS2(HSEFR_ACT_RELU6);
-    else if (act == HSEFR_ACT_RELU) HSEFR_DWPWS2(HSEFR_ACT_RELU);
-    else if (act == HSEFR_ACT_NONE) HSEFR_DWPWS2(HSEFR_ACT_NONE);
-    else { set_error("dwpw_f16split: act %d", act); return HSEFR_ERR_UNSUPPORTED; }
+    HSEFR_ACT_SWITCH(act, "dwpw_f16split", HSEFR_DWPWS2);
 #undef HSEFR_DWPWS2
     return launch_status("dwpw_f16split");
 }

@@ -30,7 +30,8 @@
 // t = x0*w0, fma(x1,w1,t), fma(x2,w2,t) per input row, (row0 + row1) + row2, fma(sum, scale, shift), ReLU6, x 2^a_log2, hi = f16(v),
 // lo = f16(v - hi) (dwpw3_f16s_kernel's producer).  A row's arithmetic does not depend on the segment it is in, nor on the batch.
 // LDS: ring 2 x 25.6 KB + A2 2 x 12 KB + A3 2 x 24 KB + scratch 4 x 8 KB + 1 KB constants + 1 KB item table = 156 KB.
-#include "common.h"
+// Row layout, split and product: f16s.h.
+#include "f16s.h"
 
 #ifndef PB_ABLATE
 #define PB_ABLATE 0     // knock-out builds (tools/build_ko.sh; timing only, wrong results): 1 no products, 2 no depthwise, 4 no input loads / split, 8 no stores
@@ -39,18 +40,14 @@ namespace hsefr {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+using namespace f16s;
 
 constexpr int PB_CIN = 64, PB_C = 128, PB_COUT = 128;   // the one shape: conv_pw_2 64 -> 128, block 128 -> 128
 constexpr int PB_WMAX = 48;                             // widest map row the LDS budget takes
 constexpr unsigned PB_GRID = 256;                       // persistent workgroups: one per CU of the MI355X
-constexpr int PB_ROWB = 128;
 constexpr int PB_CELLB = PB_C * 4;                      // a ring cell: one pixel's 128 fp32 channels
 constexpr int PB_RING = (PB_WMAX + 2) * PB_CELLB;       // one ring row
-constexpr int PB_KT = PB_WMAX * PB_ROWB;                // one K-tile (32 channels) of a stage: 48 pixel rows of 128 B
+constexpr int PB_KT = PB_WMAX * ROWB;                // one K-tile (32 channels) of a stage: 48 pixel rows of 128 B
 constexpr int PB_A2 = (PB_CIN / 32) * PB_KT, PB_A3 = (PB_C / 32) * PB_KT;
 // (the second 32-pixel column block reads pixel rows 32..63 of a K-tile: rows 48..63 are the next K-tile's, the next stage's or -- behind
 // the last A3 stage -- the scratch's first bytes: finite or not, a column of the product depends on its own pixel row alone and columns
@@ -80,8 +77,6 @@ struct PwBlkParams {
     hsefr_udiv kS;          // exact division by S (S >= 2)
 };
 
-__device__ __forceinline__ int swzb(int row, int chunk) { return row * PB_ROWB + 16 * (chunk ^ ((row >> 1) & 7) ^ ((row & 1) << 2)); }
-__device__ __forceinline__ float relu6(float v) { return fminf(fmaxf(v, 0.f), 6.f); }
 // ring cell `cell` (pixel + 1), 16-byte chunk `chunk` (channel quad): eight neighbouring cells spread one chunk over 128 contiguous bytes
 __device__ __forceinline__ int ringb(int cell, int chunk) { return cell * PB_CELLB + 16 * (chunk ^ (cell & 7)); }
 
@@ -160,9 +155,8 @@ __global__ __launch_bounds__(512, 1) void pwblk_stream_f16s_kernel(PwBlkParams p
         auto split = [&](unsigned char* At) {      // pwconv_f16s.hip's staging arithmetic
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
-                const f32x4 v = xr[j] * p.a_scale2;
-                const f16x4 hi = __builtin_convertvector(v, f16x4);
-                const f16x4 lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x4), f16x4);
+                f16x4 hi, lo;
+                f16s::split(xr[j] * p.a_scale2, hi, lo);
                 *(f16x4*)(At + a2o[j]) = hi;
                 *(f16x4*)(At + (a2o[j] ^ 64)) = lo;
             }
@@ -199,10 +193,9 @@ __global__ __launch_bounds__(512, 1) void pwblk_stream_f16s_kernel(PwBlkParams p
                 f32x4 v;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = relu6(o[e]);
-                v = v * p.a_scale3;
-                const f16x4 hi = __builtin_convertvector(v, f16x4);
-                const f16x4 lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x4), f16x4);
-                const int ao = (a3e ^ (64 * (j & 1))) + j * 8 * PB_ROWB;
+                f16x4 hi, lo;
+                f16s::split(v * p.a_scale3, hi, lo);
+                const int ao = (a3e ^ (64 * (j & 1))) + j * 8 * ROWB;
                 *(f16x4*)(At + ao) = hi;
                 *(f16x4*)(At + (ao ^ 64)) = lo;
             }
@@ -257,7 +250,7 @@ __global__ __launch_bounds__(512, 1) void pwblk_stream_f16s_kernel(PwBlkParams p
         c1.i = 0;
         open(c1);
         c3 = c1;
-        // pixels x weights: lane (li, lh) holds pixel li of column block b, channels 8 (r >> 2) + 4 lh + (r & 3) of the wave's 32
+        // weights first: lane (li, lh) holds pixel li of column block b, channels acc_row(r, lh) of the wave's 32
         f32x16 acc2[NB], acc3[NB];             // conv_pw_2's and conv_pw_3's accumulators (both live: see the step below)
         f16x8 fh[2][NB], fl[2][NB];            // activation fragments, two K-steps
         auto zero = [&](f32x16* acc) {
@@ -270,13 +263,13 @@ __global__ __launch_bounds__(512, 1) void pwblk_stream_f16s_kernel(PwBlkParams p
             const unsigned char* row = St + (s >> 1) * PB_KT;
 #pragma unroll
             for (int b = 0; b < NB; ++b) {
-                fh[buf][b] = *(const f16x8*)(row + swzb(b * 32 + li, 2 * (s & 1) + lh));
-                fl[buf][b] = *(const f16x8*)(row + swzb(b * 32 + li, 4 + 2 * (s & 1) + lh));
+                fh[buf][b] = frag(row, b * 32 + li, 2 * (s & 1) + lh);
+                fl[buf][b] = frag(row, b * 32 + li, 4 + 2 * (s & 1) + lh);
             }
         };
         auto mfmas = [&](f32x16* acc, const f16x8& wh, const f16x8& wl, int buf) {      // one K-step: wh*al, wl*ah, wh*ah into one accumulator
 #pragma unroll
-            for (int b = 0; b < NB; ++b) {
+            for (int b = 0; b < NB; ++b) {      // (f16s.h's mac3, spelt out: through the helper hipcc numbers this kernel's registers differently)
                 acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, fl[buf][b], acc[b], 0, 0, 0);
                 acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, fh[buf][b], acc[b], 0, 0, 0);
                 acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, fh[buf][b], acc[b], 0, 0, 0);

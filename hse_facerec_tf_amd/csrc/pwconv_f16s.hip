@@ -26,11 +26,11 @@
 //   [ wh(k = 32kt .. 32kt+31) : 32 x f16 | wl(same k) : 32 x f16 ]      -> [Cout][K/32][64] f16, byte-compatible with a
 // [Cout][K] fp32 matrix, so it is staged with the same full-line 16-B copies and lands in LDS in MFMA-ready form.  The
 // activation tile is split by the staging threads (4 values each: scale, 2 x cvt, subtract) on its way into the same
-// row format.  LDS rows are 128 B with the 16-B chunk swizzle c ^ ((row >> 1) & 7) of pwconv_f32.hip: conflict-free
-// ds_read_b128 fragments (8 f16 of one row = K-slice [16s + 8*(lane>>5), +8) of MFMA step s) and ds_write_b64 staging.
+// row format.  The row layout, its LDS swizzle, the split and the three-MFMA product are f16s.h's, shared with every other
+// split-f16 kernel.
 #include <type_traits>
 
-#include "common.h"
+#include "f16s.h"
 
 #ifndef PWS_AAUX
 #define PWS_AAUX 0     // cache policy of the activation loads (buffer aux bits: 1 glc, 2 slc)
@@ -39,10 +39,7 @@ namespace hsefr {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+using namespace f16s;
 
 #ifdef HSEFR_PWS_STAMPS
 // Diagnostic build only (build.sh HSEFR_EXTRA_FLAGS=-DHSEFR_PWS_STAMPS): per-wave s_memtime sums of the step phases.
@@ -51,12 +48,6 @@ __device__ unsigned long long g_pws_stamps[1024 * 8 * 8];
 #else
 #define PWS_STAMP(i) do { } while (0)
 #endif
-
-constexpr int BK = 32;          // input channels per K-tile
-constexpr int ROWB = 128;       // LDS bytes per tile row: 32 hi halves | 32 lo halves
-
-// byte offset of 16-B chunk `chunk` of tile row `row`
-__device__ __forceinline__ int swzb(int row, int chunk) { return row * ROWB + 16 * (chunk ^ ((row >> 1) & 7) ^ ((row & 1) << 2)); }
 
 // sched_group_barrier masks
 #define SG_VALU 0x002
@@ -141,12 +132,9 @@ __global__ __launch_bounds__(128 * WAVES_N, OCC) void pwconv_f16s_kernel(const f
         constexpr int S = decltype(SET)::value;
 #pragma unroll
         for (int p = 0; p < AP; ++p) {
-            const f32x4 v = ra[S][p] * a_scale;
-            const f16x4 hi = __builtin_convertvector(v, f16x4);
-            const f16x4 lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x4), f16x4);
-            const int row = srow + SR * p;
-            *(f16x4*)(As(buf) + swzb(row, skq >> 1) + 8 * (skq & 1)) = hi;
-            *(f16x4*)(As(buf) + swzb(row, 4 + (skq >> 1)) + 8 * (skq & 1)) = lo;
+            f16x4 hi, lo;
+            split(ra[S][p] * a_scale, hi, lo);
+            put_quad(As(buf), srow + SR * p, skq, hi, lo);
         }
 #pragma unroll
         for (int p = 0; p < BP; ++p) *(f32x4*)(Bs(buf) + swzb(srow + SR * p, skq)) = rb[S][p];
@@ -178,11 +166,11 @@ __global__ __launch_bounds__(128 * WAVES_N, OCC) void pwconv_f16s_kernel(const f
     swrite(S0(), 0);
     __syncthreads();
     const int arow = wm * WM + li, brow = wn * WN + li;
-    // Epilogue geometry.  The MFMAs run with the operands SWAPPED (weights first): lane (li, lh) then owns output row
-    // m = li of a 32 x 32 block and, in accumulator register r, column n = 4*lh + 8*(r >> 2) + (r & 3): four runs of 4
-    // consecutive channels = four ds_write_b128 into a wave-private 32 x 128 B scratch (the LDS stage the tile's last
-    // step has just finished with).  Read back 8 lanes per row, a block leaves as 4 stores of 8 rows x 128 B: whole
-    // lines, a quarter of the store instructions of the register-per-row layout.
+    // Epilogue geometry.  The MFMAs run with the weights first: lane (li, lh) then owns output row m = li of a 32 x 32
+    // block and, in accumulator register r, column n = acc_row(r, lh): four runs of 4 consecutive channels = four
+    // ds_write_b128 into a wave-private 32 x 128 B scratch (the LDS stage the tile's last step has just finished with).
+    // Read back 8 lanes per row, a block leaves as 4 stores of 8 rows x 128 B: whole lines, a quarter of the store
+    // instructions of the register-per-row layout.
     const int erow = lane >> 3, ech = lane & 7;
     const unsigned yvoff = ((unsigned)(wm * WM + erow) * (unsigned)Cout + (unsigned)(wn * WN + 4 * ech)) * 4u;
 
@@ -208,13 +196,13 @@ __global__ __launch_bounds__(128 * WAVES_N, OCC) void pwconv_f16s_kernel(const f
         for (int s = 0; s < 2; ++s) {
 #pragma unroll
             for (int mi = 0; mi < MI; ++mi) {
-                ah[s][mi] = *(const f16x8*)(As(P) + swzb(arow + mi * 32, 2 * s + lh));
-                al[s][mi] = *(const f16x8*)(As(P) + swzb(arow + mi * 32, 4 + 2 * s + lh));
+                ah[s][mi] = frag(As(P), arow + mi * 32, 2 * s + lh);
+                al[s][mi] = frag(As(P), arow + mi * 32, 4 + 2 * s + lh);
             }
 #pragma unroll
             for (int ni = 0; ni < NI; ++ni) {
-                bh[s][ni] = *(const f16x8*)(Bs(P) + swzb(brow + ni * 32, 2 * s + lh));
-                bl[s][ni] = *(const f16x8*)(Bs(P) + swzb(brow + ni * 32, 4 + 2 * s + lh));
+                bh[s][ni] = frag(Bs(P), brow + ni * 32, 2 * s + lh);
+                bl[s][ni] = frag(Bs(P), brow + ni * 32, 4 + 2 * s + lh);
             }
         }
         gload(PAR);
@@ -223,11 +211,7 @@ __global__ __launch_bounds__(128 * WAVES_N, OCC) void pwconv_f16s_kernel(const f
 #pragma unroll
             for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-                for (int ni = 0; ni < NI; ++ni) {
-                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[s][ni], al[s][mi], acc[mi][ni], 0, 0, 0);
-                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[s][ni], ah[s][mi], acc[mi][ni], 0, 0, 0);
-                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[s][ni], ah[s][mi], acc[mi][ni], 0, 0, 0);
-                }
+                for (int ni = 0; ni < NI; ++ni) mac3(bh[s][ni], bl[s][ni], ah[s][mi], al[s][mi], acc[mi][ni]);
         swrite(std::integral_constant<int, 1 - P>(), 1 - P);
         // desired order: fragments, then one prefetch load per MFMA, then the conversion VALU + LDS writes of the
         // next stage spread under the remaining MFMAs (the wave never queues up 12 loads at once, and the ~60 VALU
@@ -347,10 +331,7 @@ int launch_cfg(const float* x, const void* wsplit, const float* descale, const f
 #define HSEFR_PWS_LAUNCH(A)                                                                                         \
     HSEFR_LAUNCH((pwconv_f16s_kernel<BM, BN, WAVES_N, OCC, A>), grid, block, 0, s, x, (const float*)wsplit, descale, shift, \
                        y, m, k, cout, a_scale, tiles_n, (unsigned)total, sweep_reverse())
-    if (act == HSEFR_ACT_RELU6) HSEFR_PWS_LAUNCH(HSEFR_ACT_RELU6);
-    else if (act == HSEFR_ACT_RELU) HSEFR_PWS_LAUNCH(HSEFR_ACT_RELU);
-    else if (act == HSEFR_ACT_NONE) HSEFR_PWS_LAUNCH(HSEFR_ACT_NONE);
-    else { set_error("pwconv_f16split: act %d", act); return HSEFR_ERR_UNSUPPORTED; }
+    HSEFR_ACT_SWITCH(act, "pwconv_f16split", HSEFR_PWS_LAUNCH);
 #undef HSEFR_PWS_LAUNCH
     return launch_status("pwconv_f16split");
 }

@@ -43,14 +43,14 @@
 // Every output element is accumulated over K in ONE fixed order by ONE wave: results are bit-identical run to run and
 // independent of the grid.  (They are NOT bit-identical to pwconv_f16s.hip: a 16x16x32 MFMA sums its 32 products in a
 // different internal order than two 32x32x16 steps -- same error bound, same 2e-6 test bar.)
-#include "common.h"
+// Row layout, swizzle key, split and product: f16s.h.
+#include "f16s.h"
 
 namespace hsefr {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+using namespace f16s;
 
 #ifdef HSEFR_PS_STAMPS
 // Diagnostic build only (HSEFR_DEV=1 HSEFR_EXTRA_FLAGS=-DHSEFR_PS_STAMPS=1 build.sh): per-wave s_memtime sums of the step phases.
@@ -76,11 +76,7 @@ __device__ unsigned long long g_ps_stamps[256 * 12 * 8];
 #else
 #define PS_EPI_STORE(v, r, off) bstore16_welded_nt(v, r, off, 0u)
 #endif
-constexpr int ROWB = 128;       // bytes per split row: 32 hi halves | 32 lo halves
 constexpr int BN = 128;
-
-// swizzle key of a tile row: the 16-B chunk c of row r lives at chunk position c ^ key(r) (pwconv_f16s.hip's swizzle)
-__device__ __forceinline__ int swz_key(int row) { return ((row >> 1) & 7) ^ ((row & 1) << 2); }
 
 // the depthwise layer fused behind the GEMM (DW kernels): dwc = [11][Cout] floats (taps 0..8 row-major, then scale and shift, the
 // latter two already multiplied by out_scale), W = H = map edge, ys = its split-row output
@@ -93,7 +89,6 @@ struct PsDwParams {
                           // computed but belong to the next tile: 14 x 14 maps ride in 224-row tiles, five 7 x 7 maps in 256-row ones)
 };
 
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
@@ -275,8 +270,8 @@ __global__ __launch_bounds__(768, 1) void pwconv_ps_kernel(const void* __restric
                 f32x4 o;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) o[e] = fminf(fmaxf(fmaf(acc3[j][e], sc[e], sh[e]), 0.f), dw.clamp_hi);
-                const f16x4 hi = __builtin_convertvector(o, f16x4);
-                const f16x4 lo = __builtin_convertvector(o - __builtin_convertvector(hi, f32x4), f16x4);
+                f16x4 hi, lo;
+                split(o, hi, lo);
                 const u32x2 hb = __builtin_bit_cast(u32x2, hi), lb = __builtin_bit_cast(u32x2, lo);
                 const u32x2 send = odd ? hb : lb;
                 u32x2 recv;
@@ -319,8 +314,8 @@ __global__ __launch_bounds__(768, 1) void pwconv_ps_kernel(const void* __restric
             f32x4 o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = fminf(fmaxf(fmaf(a[k3][e], sc[e], sh[e]), 0.f), dw.clamp_hi);
-            const f16x4 hi = __builtin_convertvector(o, f16x4);
-            const f16x4 lo = __builtin_convertvector(o - __builtin_convertvector(hi, f32x4), f16x4);
+            f16x4 hi, lo;
+            split(o, hi, lo);
             const u32x2 hb = __builtin_bit_cast(u32x2, hi), lb = __builtin_bit_cast(u32x2, lo);
             const u32x2 send = odd ? hb : lb;
             u32x2 recv;
@@ -504,7 +499,8 @@ __global__ __launch_bounds__(768, 1) void pwconv_ps_kernel(const void* __restric
 #pragma unroll
     for (int i = 0; i < HB; ++i) h_ah[i] = h_al[i] = fzero;
     auto mfma_block = [&](int mb, const f16x8& xh, const f16x8& xl, const f16x8& wh0, const f16x8& wl0, const f16x8& wh1, const f16x8& wl1) {
-        // per accumulator the products keep the order (wh*al, wl*ah, wh*ah) of pwconv_f16s.hip
+        // per accumulator the products keep the order (wh*al, wl*ah, wh*ah) of f16s.h's mac3_16; the two accumulators' MFMAs alternate, so
+        // the six stay spelt out (two calls of the helper in a row make hipcc schedule every instance of this kernel differently)
         if constexpr (SWAP) {      // lane (l16, lq) -> channel l16 of the block, pixels 4 lq .. 4 lq + 3
             acc[mb][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xl, wh0, acc[mb][0], 0, 0, 0);
             acc[mb][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xl, wh1, acc[mb][1], 0, 0, 0);
@@ -715,10 +711,7 @@ int launch_mb(const void* xs, const void* wsplit, const float* descale, const fl
 #define HSEFR_PS_LAUNCH(A)                                                                                                 \
     HSEFR_LAUNCH((pwconv_ps_kernel<MB, A, 0>), dim3(g), dim3(768), 0, s, xs, wsplit, descale, shift, y, m, k, cout, tiles_n, \
                        (unsigned)total, sweep_reverse(), nodw)
-    if (act == HSEFR_ACT_RELU6) HSEFR_PS_LAUNCH(HSEFR_ACT_RELU6);
-    else if (act == HSEFR_ACT_RELU) HSEFR_PS_LAUNCH(HSEFR_ACT_RELU);
-    else if (act == HSEFR_ACT_NONE) HSEFR_PS_LAUNCH(HSEFR_ACT_NONE);
-    else { set_error("pwconv_presplit: act %d", act); return HSEFR_ERR_UNSUPPORTED; }
+    HSEFR_ACT_SWITCH(act, "pwconv_presplit", HSEFR_PS_LAUNCH);
 #undef HSEFR_PS_LAUNCH
     return launch_status("pwconv_presplit");
 }
@@ -824,10 +817,7 @@ static int launch_psgap(const void* xs, const void* wsplit, const float* descale
 #define HSEFR_PSGAP_LAUNCH(A)                                                                                                    \
     HSEFR_LAUNCH((pwconv_ps_kernel<MB, A, 4>), dim3(g), dim3(768), 0, s, xs, wsplit, descale, shift, (float*)nullptr, m, k, cout, \
                        tiles_n, (unsigned)total, sweep_reverse(), dw)
-    if (act == HSEFR_ACT_RELU6) HSEFR_PSGAP_LAUNCH(HSEFR_ACT_RELU6);
-    else if (act == HSEFR_ACT_RELU) HSEFR_PSGAP_LAUNCH(HSEFR_ACT_RELU);
-    else if (act == HSEFR_ACT_NONE) HSEFR_PSGAP_LAUNCH(HSEFR_ACT_NONE);
-    else { set_error("pwconv_presplit_gap: act %d", act); return HSEFR_ERR_UNSUPPORTED; }
+    HSEFR_ACT_SWITCH(act, "pwconv_presplit_gap", HSEFR_PSGAP_LAUNCH);
 #undef HSEFR_PSGAP_LAUNCH
     return launch_status("pwconv_presplit_gap");
 }

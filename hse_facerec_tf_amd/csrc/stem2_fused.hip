@@ -206,9 +206,8 @@ __global__ __launch_bounds__(256, 2) void stem2_fused_kernel(Stem2Params p) {
                 const f32x4 o = vfma(s, as_v(d1sc), as_v(d1sh));
                 f32x4 v;
                 v[0] = relu6(o[0]); v[1] = relu6(o[1]); v[2] = relu6(o[2]); v[3] = relu6(o[3]);
-                v = v * p.a_scale;
-                const f16x4 hi = __builtin_convertvector(v, f16x4);
-                const f16x4 lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x4), f16x4);
+                f16x4 hi, lo;
+                split(v * p.a_scale, hi, lo);
                 *(f16x4*)(&As[swzb(q, c4l >> 1) + 8 * (c4l & 1)]) = hi;
                 *(f16x4*)(&As[swzb(q, 4 + (c4l >> 1)) + 8 * (c4l & 1)]) = lo;
             }
@@ -225,9 +224,7 @@ __global__ __launch_bounds__(256, 2) void stem2_fused_kernel(Stem2Params p) {
             const f16x8 ah = *(const f16x8*)(&As[swzb(mb * 16 + l16, q4)]);
             const f16x8 al = *(const f16x8*)(&As[swzb(mb * 16 + l16, 4 + q4)]);
             f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh, al, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(bl, ah, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh, ah, acc, 0, 0, 0);
+            f16s::mac3_16(bh, bl, ah, al, acc);
             // lane: block-1 pixel m = 16*mb + l16, channels 16*wave + 4*q4 + (0..3)
             const int m = mb * 16 + l16;
             if (m < R1PIX) {

@@ -174,9 +174,8 @@ __global__ __launch_bounds__(256, 2) void stem4_fused_kernel(Stem4Params p) {
                     v[0] = (float)(b & 255u); v[1] = (float)((b >> 8) & 255u); v[2] = (float)((b >> 16) & 255u); v[3] = (float)(b >> 24);
                     *(f16x4*)dst = __builtin_convertvector(v, f16x4);               // exact
                 } else {
-                    const f32x4 v = rawv[k] * p.in_scale;                            // a power of two: exact
-                    const f16x4 hi = __builtin_convertvector(v, f16x4);
-                    const f16x4 lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x4), f16x4);
+                    f16x4 hi, lo;
+                    split(rawv[k] * p.in_scale, hi, lo);                             // (the scale is a power of two: exact)
                     *(f16x4*)dst = hi;
                     *(f16x4*)(dst + WPLANE) = lo;
                     // bound check on the hi halves: |v| < 2^15 <=> (bits & 0x7fff) < 0x7800; an Inf / NaN has all exponent bits set

@@ -286,9 +286,8 @@ __global__ __launch_bounds__(64 * WAVES, S5_WGS) void stem5_stream_kernel(Stem5P
                         v[0] = (float)(b & 255u); v[1] = (float)((b >> 8) & 255u); v[2] = (float)((b >> 16) & 255u); v[3] = (float)(b >> 24);
                         *(f16x4*)dst = __builtin_convertvector(v, f16x4);               // exact
                     } else {
-                        const f32x4 v = rawv[k] * p.in_scale;                            // a power of two: exact
-                        const f16x4 hi = __builtin_convertvector(v, f16x4);
-                        const f16x4 lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x4), f16x4);
+                        f16x4 hi, lo;
+                        split(rawv[k] * p.in_scale, hi, lo);                             // (the scale is a power of two: exact)
                         *(f16x4*)dst = hi;
                         *(f16x4*)(dst + WPLANE) = lo;
                         const u32x2 hb = __builtin_bit_cast(u32x2, hi);
@@ -379,8 +378,8 @@ __global__ __launch_bounds__(64 * WAVES, S5_WGS) void stem5_stream_kernel(Stem5P
                         f32x4 v = vfma(sP, d1sc, d1sh);
 #pragma unroll
                         for (int e = 0; e < 4; ++e) v[e] = __builtin_amdgcn_fmed3f(v[e], 0.f, cap6);
-                        const f16x4 hi = __builtin_convertvector(v, f16x4);
-                        const f16x4 lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x4), f16x4);
+                        f16x4 hi, lo;
+                        split(v, hi, lo);
                         const int q = cr * PXW + x;
                         if (8 * rd + 8 <= PXW || x < PXW) {
                             *(f16x4*)(L + OFF_AS + swzb(q, d1_q >> 1) + 8 * (d1_q & 1)) = hi;

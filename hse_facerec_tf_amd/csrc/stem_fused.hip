@@ -20,16 +20,14 @@
 //   E  epilogue  acc * descale + shift, activation, transposed through LDS into whole 128-B lines, buffer stores.
 // The next patch's gather is in flight during B-E.  Halo recomputation: 180 conv1 pixels per 128 outputs (1.4x of a
 // 4 GFLOP layer); HBM reads of the halo hit L2 (patch ids are XCD-remapped).
-#include "common.h"
+// Row layout, split and product: f16s.h.
+#include "f16s.h"
 
 namespace hsefr {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+using namespace f16s;
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 struct __attribute__((packed, aligned(4))) F3 { float a, b, c; };
 
@@ -57,8 +55,6 @@ constexpr int TW = 16, TH = 8, RW = TW + 2, RH = TH + 2, RPIX = RW * RH;   // co
 constexpr int RROWS = 192;                                                   // padded to 12 MFMA row blocks of 16
 
 __device__ __forceinline__ int swz32(int row, int chunk) { return row * 32 + 4 * (chunk ^ ((row >> 1) & 7) ^ ((row & 1) << 2)); }       // floats
-__device__ __forceinline__ int swzb(int row, int chunk) { return row * 128 + 16 * (chunk ^ ((row >> 1) & 7) ^ ((row & 1) << 2)); }      // bytes; b64 writes of adjacent rows land in different halves of the 128-B bank window
-__device__ __forceinline__ float relu6(float v) { return fminf(fmaxf(v, 0.f), 6.f); }
 __device__ __forceinline__ float4 fma4(float4 a, float4 b, float4 c) {
     return make_float4(fmaf(a.x, b.x, c.x), fmaf(a.y, b.y, c.y), fmaf(a.z, b.z, c.z), fmaf(a.w, b.w, c.w));
 }
@@ -252,12 +248,9 @@ __global__ __launch_bounds__(256, 2) void stem_fused_kernel(StemParams p) {
                 const float4 o = fma4(s, dsc, dsh);
                 f32x4 v;
                 v[0] = relu6(o.x); v[1] = relu6(o.y); v[2] = relu6(o.z); v[3] = relu6(o.w);
-                v = v * p.a_scale;
-                const f16x4 hi = __builtin_convertvector(v, f16x4);
-                const f16x4 lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x4), f16x4);
-                const int R = (drow0 + j) * TW + dtw;
-                *(f16x4*)(&As[swzb(R, c4l >> 1) + 8 * (c4l & 1)]) = hi;
-                *(f16x4*)(&As[swzb(R, 4 + (c4l >> 1)) + 8 * (c4l & 1)]) = lo;
+                f16x4 hi, lo;
+                split(v * p.a_scale, hi, lo);
+                put_quad(As, (drow0 + j) * TW + dtw, c4l, hi, lo);
                 r0 = r1; r1 = r2;
             }
         }
@@ -276,17 +269,12 @@ __global__ __launch_bounds__(256, 2) void stem_fused_kernel(StemParams p) {
             f16x8 ah[2], al[2];
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi) {
-                ah[mi] = *(const f16x8*)(&As[swzb(wm * 64 + mi * 32 + li, 2 * s + lh)]);
-                al[mi] = *(const f16x8*)(&As[swzb(wm * 64 + mi * 32 + li, 4 + 2 * s + lh)]);
+                ah[mi] = frag(As, wm * 64 + mi * 32 + li, 2 * s + lh);
+                al[mi] = frag(As, wm * 64 + mi * 32 + li, 4 + 2 * s + lh);
             }
-            const f16x8 bh = *(const f16x8*)(&Bw[swzb(wn * 32 + li, 2 * s + lh)]);
-            const f16x8 bl = *(const f16x8*)(&Bw[swzb(wn * 32 + li, 4 + 2 * s + lh)]);
+            const f16x8 bh = frag(Bw, wn * 32 + li, 2 * s + lh), bl = frag(Bw, wn * 32 + li, 4 + 2 * s + lh);
 #pragma unroll
-            for (int mi = 0; mi < 2; ++mi) {
-                pacc[mi] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh, al[mi], pacc[mi], 0, 0, 0);
-                pacc[mi] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl, ah[mi], pacc[mi], 0, 0, 0);
-                pacc[mi] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh, ah[mi], pacc[mi], 0, 0, 0);
-            }
+            for (int mi = 0; mi < 2; ++mi) mac3(bh, bl, ah[mi], al[mi], pacc[mi]);
         }
 
         STEM_STAMP(4);

@@ -3,23 +3,25 @@
 // stem4_fused.hip) -- their geometry, the persistent loop's patch cursor, the stages behind conv1 and the launchers' common part.
 // A generation is its front end (gather / window, conv1) and its history; stages C-E of stem3 and stem4 are these functions, so
 // "same operation order, same bits for equal conv1 results" holds by construction (tests/test_stem_bits_gpu.py pins the bits).
+// The split-f16 vocabulary -- vector types, the split rows' swzb, relu6, split -- is f16s.h's.
 #pragma once
-#include "common.h"
+#include "f16s.h"
 
 namespace hsefr {
 namespace stem {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+using f16s::f32x4;
+using f16s::f16x4;
+using f16s::f16x8;
+using f16s::swzb;
+using f16s::relu6;
+using f16s::split;
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 struct __attribute__((packed, aligned(4))) F3 { float a, b, c; };
 struct __attribute__((packed, aligned(4))) Frag4 { f16x8 v; };      // a 16-byte MFMA fragment at a 4-byte-aligned LDS address
 
 __device__ __forceinline__ int swz32(int row, int chunk) { return row * 32 + 4 * (chunk ^ ((row >> 1) & 7) ^ ((row & 1) << 2)); }       // floats
-__device__ __forceinline__ int swzb(int row, int chunk) { return row * 128 + 16 * (chunk ^ ((row >> 1) & 7) ^ ((row & 1) << 2)); }      // bytes; b64 writes of adjacent rows land in different halves of the 128-B bank window
-__device__ __forceinline__ float relu6(float v) { return fminf(fmaxf(v, 0.f), 6.f); }
 // 4-wide fused multiply-add on vector types: lowers to two v_pk_fma_f32 (same rounding as fmaf, half the instructions);
 // used where no MFMA shares the issue slots (the depthwise stages).
 __device__ __forceinline__ f32x4 vfma(f32x4 a, f32x4 b, f32x4 c) { return __builtin_elementwise_fma(a, b, c); }
@@ -127,8 +129,8 @@ __device__ __forceinline__ void stage_dw1(const float* Co, const float4* W1, uns
                 f32x4 v;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = fminf(fmaxf(o[e], 0.f), cap6);
-                const f16x4 hi = __builtin_convertvector(v, f16x4);
-                const f16x4 lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x4), f16x4);
+                f16x4 hi, lo;
+                split(v, hi, lo);
                 const int q = ry * R1W + c0 + j;
                 *(f16x4*)(&As[swzb(q, c4l >> 1) + 8 * (c4l & 1)]) = hi;
                 *(f16x4*)(&As[swzb(q, 4 + (c4l >> 1)) + 8 * (c4l & 1)]) = lo;
@@ -229,15 +231,8 @@ inline int fill_params(PatchParams& p, const char* kernel, const float* wd1, con
     return HSEFR_OK;
 }
 
-// the three activations a stem kernel is instantiated for: LAUNCH(A) launches instance A.  Like HSEFR_REQUIRE, any other `act`
-// RETURNS HSEFR_ERR_UNSUPPORTED from the calling launcher (a macro: it has no namespace)
-#define HSEFR_STEM_ACT_DISPATCH(kernel, act, LAUNCH)                                     \
-    do {                                                                                 \
-        if ((act) == HSEFR_ACT_RELU6) LAUNCH(HSEFR_ACT_RELU6);                           \
-        else if ((act) == HSEFR_ACT_RELU) LAUNCH(HSEFR_ACT_RELU);                        \
-        else if ((act) == HSEFR_ACT_NONE) LAUNCH(HSEFR_ACT_NONE);                        \
-        else { set_error(kernel ": act %d", act); return HSEFR_ERR_UNSUPPORTED; }        \
-    } while (0)
+// the three activations a stem kernel is instantiated for: common.h's switch (`kernel` names the generation in the error message)
+#define HSEFR_STEM_ACT_DISPATCH(kernel, act, LAUNCH) HSEFR_ACT_SWITCH(act, kernel, LAUNCH)
 
 }  // namespace patch
 }  // namespace stem
