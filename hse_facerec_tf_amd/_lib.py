@@ -1,5 +1,5 @@
 """ctypes binding of libhsefr.so (include/hsefr.h) and of the libraries built beside it (include/hsefr_<name>.h), each described by
-one Library record in LIBRARIES.  No fallback: if a library is missing the import of anything that needs it raises, and every
+one Library record in LIBRARIES, or in EXTENSIONS for a library that is not yet a member of that registry.  No fallback: if a library is missing the import of anything that needs it raises, and every
 non-zero status becomes a Python exception in the reference's error style (ValueError for shape errors, NotImplementedError for
 unsupported graphs, RuntimeError otherwise)."""
 from __future__ import annotations
@@ -239,6 +239,16 @@ GEOM_SIGNATURES = {
     "hsefr_geom_linkage": (c_int, [_fp, c_int, c_int, _fp, _fp, _fp, c_int, _fp, _fp, _fp, _fp, _fp, _fp, c_void_p]),
 }
 
+# libhsefr_shift.so (include/hsefr_shift.h): mean-shift clustering, the first extension (EXTENSIONS below)
+_i32p = _fp
+SHIFT_SIGNATURES = {
+    "hsefr_shift_version": (c_int, []),
+    "hsefr_shift_last_error": (c_char_p, []),
+    "hsefr_shift_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "hsefr_shift_fit": (c_int, [_fp, c_int, c_int, ctypes.c_double, c_int, _fp, _i32p, _i32p, _fp, _i32p, _fp, c_size_t, c_void_p]),
+    "hsefr_shift_assign": (c_int, [_fp, c_int, c_int, _fp, c_int, _i32p, _fp, c_void_p]),
+}
+
 
 def _later(name, signatures, error_fn):
     return Library("hsefr_" + name, "libhsefr_%s.so" % name, "HSEFR_%s_LIB" % name.upper(), signatures, error_fn, "hsefr_%s_version" % name, 100)
@@ -257,6 +267,12 @@ LIBRARIES = (
 )
 _MAIN, _ALBUM, _FRAMES, _FOREST, _RAGGED, _MIXED, _SPLIT, _GEOM = LIBRARIES
 
+# the extensions (csrc/build.sh: EXT_LIBS): libraries built, loaded and checked like the eight above that are not members of LIBRARIES
+EXTENSIONS = (
+    Library("hsefr_shift", "libhsefr_shift.so", "HSEFR_SHIFT_LIB", SHIFT_SIGNATURES, "hsefr_shift_last_error", "hsefr_shift_version", 100),
+)
+_SHIFT, = EXTENSIONS
+
 # the module-level names of each library.  Callers go through the module attribute at call time (_lib.frames_lib()), so a test can put
 # another function in its place
 LIB_PATH, lib, last_error, check = _MAIN.path, _MAIN.load, _MAIN.last_error, _MAIN.check
@@ -267,6 +283,7 @@ RAGGED_LIB_PATH, ragged_lib, ragged_last_error, ragged_check = _RAGGED.path, _RA
 MIXED_LIB_PATH, mixed_lib, mixed_last_error, mixed_check = _MIXED.path, _MIXED.load, _MIXED.last_error, _MIXED.check
 SPLIT_LIB_PATH, split_lib, split_last_error, split_check = _SPLIT.path, _SPLIT.load, _SPLIT.last_error, _SPLIT.check
 GEOM_LIB_PATH, geom_lib, geom_last_error, geom_check = _GEOM.path, _GEOM.load, _GEOM.last_error, _GEOM.check
+SHIFT_LIB_PATH, shift_lib, shift_last_error, shift_check = _SHIFT.path, _SHIFT.load, _SHIFT.last_error, _SHIFT.check
 
 
 _torch_gpu = None      # torch, once a GPU has been seen (torch.cuda.is_available() re-reads the environment on every call: the

@@ -722,6 +722,88 @@ def cluster_faces_geometric(features, distance_threshold: float, method: str, bo
     return _feature_clusters(features, distance_threshold, born_years, photo_years, all_indices, min_cluster_size, device, method, split)
 
 
+# ---- mean shift -----------------------------------------------------------------------------------------------------
+MEAN_SHIFT_BANDWIDTH = 0.7      # facial_clustering_test.py:264: MeanShift(bandwidth=0.7).fit(all_features)
+
+
+def _check_mean_shift_args(bandwidth, max_iter):
+    if isinstance(bandwidth, bool) or not isinstance(bandwidth, numbers.Real) or not math.isfinite(bandwidth) or not bandwidth > 0:
+        raise ValueError("mean_shift: bandwidth must be a finite real > 0, got %r" % (bandwidth,))
+    if isinstance(max_iter, bool) or not isinstance(max_iter, numbers.Integral) or max_iter < 0:
+        raise ValueError("mean_shift: max_iter must be an int >= 0, got %r" % (max_iter,))
+
+
+def _mean_shift(x, bandwidth, max_iter, cluster_all):
+    """mean_shift on the checked device tensor x -> (centres, labels, n_iter), host arrays"""
+    from . import ops
+    centers, _, labels, dist, info = ops.mean_shift_fit(x, bandwidth, max_iter)
+    labels = labels.cpu().numpy().astype(np.int64)
+    if not cluster_all:
+        labels[dist.cpu().numpy() > bandwidth] = -1
+    return centers.cpu().numpy(), labels, info["n_iter"]
+
+
+def mean_shift(features, bandwidth=MEAN_SHIFT_BANDWIDTH, max_iter=300, cluster_all=True, device=None):
+    """sklearn.cluster.MeanShift(bandwidth=bandwidth, max_iter=max_iter, cluster_all=cluster_all).fit(features) on the GPU -- every face a
+    seed, all seeds advanced together in fp64, no N x N matrix but one of bits -> (cluster_centers float64 [k, d], labels int64 [n],
+    n_iter), scikit-learn's cluster_centers_ (to rounding), labels_ and n_iter_.  The default bandwidth is the clustering study's
+    (facial_clustering_test.py:264).  With ``cluster_all=False`` a face farther than the bandwidth from its nearest centre gets -1.
+    Bad bandwidth, max_iter or features raise ValueError before any device work (for host inputs)."""
+    _check_mean_shift_args(bandwidth, max_iter)
+    x, _, _ = _features(features, None, None, device, finite=True)
+    return _mean_shift(x, float(bandwidth), int(max_iter), cluster_all)
+
+
+def mean_shift_predict(features, cluster_centers, device=None) -> np.ndarray:
+    """MeanShift.predict: the index of the nearest of ``cluster_centers`` [k, d] for every row of ``features`` [n, d], the lowest index
+    among equal distances -> int64 [n]."""
+    from . import _lib, ops
+    centers = cluster_centers if hasattr(cluster_centers, "is_cuda") else np.asarray(cluster_centers, dtype=np.float64)
+    if centers.ndim != 2 or centers.shape[0] < 1:
+        raise ValueError("cluster_centers must be [k, d] with k >= 1")
+    if isinstance(centers, np.ndarray) and not np.isfinite(centers).all():
+        raise ValueError("cluster_centers hold non-finite values")
+    if not hasattr(features, "is_cuda"):
+        features = np.asarray(features, dtype=np.float32)
+    if features.ndim != 2 or features.shape[1] != centers.shape[1]:
+        raise ValueError("features must be [n, %d] as the centres" % centers.shape[1])
+    x, _, _ = _features(features, None, None, device, finite=True)
+    c = _device_tensor(centers, _lib.require_gpu().float64, x.device)
+    return ops.mean_shift_assign(x, c)[0].cpu().numpy().astype(np.int64)
+
+
+def cluster_faces_mean_shift(features, bandwidth=MEAN_SHIFT_BANDWIDTH, all_indices=None, min_cluster_size: int = 1, split: str = "host",
+                             device=None) -> List[List[int]]:
+    """The scikit-learn branch of the reference's get_facial_clusters with its mean-shift row (facial_clustering_test.py:264-266, 285):
+    the members of every label >= 0 of mean_shift(features, bandwidth), the largest cluster first (a stable sort of the clusters in
+    label order), as lists of ints.  With ``all_indices`` (the photo of every face) every cluster goes through the same-photo split
+    (facial_clustering.py:250-261) -- ``split`` 'host': cluster by cluster on the host, 'device': split_same_photo's one pass -- its
+    parts in order of their first face; clusters shorter than ``min_cluster_size`` are dropped."""
+    from . import ops
+    _check_mean_shift_args(bandwidth, 300)
+    _check_split(split)
+    x, _, _ = _features(features, None, None, device, finite=True)
+    n = x.shape[0]
+    labels = _mean_shift(x, float(bandwidth), 300, True)[1]
+    groups = [np.flatnonzero(labels == c) for c in range(int(labels.max()) + 1)]
+    groups = [g for g in groups if len(g)]
+    if all_indices is not None:
+        if split == "device":
+            groups = [np.sort(g) for g in split_same_photo(labels, all_indices, features=x)]      # clusters in order of their first face:
+            groups.sort(key=lambda g: int(labels[g[0]]))                   # back to label order (stable: a cluster's parts stay in theirs)
+        else:
+            import torch
+            xp = x if x.shape[1] % 8 == 0 else torch.nn.functional.pad(x, (0, 8 - x.shape[1] % 8)).contiguous()
+
+            def sub_dist(g):
+                rows = xp[torch.from_numpy(g).to(x.device)].contiguous()
+                return np.clip(ops.pairwise_distances(rows).cpu().numpy().astype(np.float64), 0, None)
+            groups = _split_groups(groups, all_indices, n, sub_dist)
+    out = [[int(i) for i in g] for g in groups if len(g) >= min_cluster_size]
+    out.sort(key=len, reverse=True)
+    return out
+
+
 # ---- scoring --------------------------------------------------------------------------------------------------------
 def bcubed(y_true: Sequence, y_pred: Sequence):
     """Extended B-cubed of the clustering study (facial_clustering_test.py:321-359, one label per item) -> (precision, recall, f).
@@ -829,6 +911,22 @@ def clustering_scores(y_true, y_pred, device=None) -> np.ndarray:
     if len(t) != len(p):
         raise ValueError("%d true labels, %d predicted" % (len(t), len(p)))
     return _score_rows(t, torch.from_numpy(p).to(_lib.cuda_device(device))[None])[0]
+
+
+def mean_shift_scores(features, y_true, bandwidths, device=None) -> np.ndarray:
+    """get_clustering_statistics' ten numbers (STATS_NAMES) of mean_shift(features, bandwidth) for every bandwidth -> float64
+    [len(bandwidths), 10]: the row of a bandwidth is clustering_scores(y_true, its labels)."""
+    bandwidths = list(bandwidths) if isinstance(bandwidths, (list, tuple)) else list(np.asarray(bandwidths).reshape(-1))
+    for b in bandwidths:
+        _check_mean_shift_args(b, 300)
+    bandwidths = [float(b) for b in bandwidths]
+    x, _, _ = _features(features, None, None, device, finite=True)
+    if len(np.asarray(y_true).reshape(-1)) != x.shape[0]:
+        raise ValueError("%d true labels for %d faces" % (len(np.asarray(y_true).reshape(-1)), x.shape[0]))
+    out = np.empty((len(bandwidths), len(STATS_NAMES)), dtype=np.float64)
+    for r, b in enumerate(bandwidths):
+        out[r] = clustering_scores(y_true, _mean_shift(x, b, 300, True)[1], device=x.device)
+    return out
 
 
 def _sweep_labels(source, method, thresholds, born_years, photo_years, dense, min_samples, device):

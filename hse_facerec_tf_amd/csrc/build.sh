@@ -6,6 +6,8 @@
 #                          variables, hsefr_debug_*, the calibration kernels of devtools.hip) -- for tools/kbench.py only.
 #   build.sh --list        prints the resolved table and compiles nothing: per library its name, output, sources, the complete compile
 #                          flags of the current mode and the files its objects are stale against (tests/test_libraries_cpu.py reads it)
+#   build.sh --list-extensions   the same for the table EXT_LIBS: the extensions, libraries built like the others that are not (yet) among
+#                          the package's registry of eight (hse_facerec_tf_amd/_lib.py: EXTENSIONS beside LIBRARIES)
 set -euo pipefail
 cd "$(dirname "$0")"
 # product sources.  Development builds add round 1's stem (reachable only through lower_graph(stem_fusion="stem")) and the first window 3x3
@@ -57,7 +59,12 @@ LIBS=(
   "split|../libhsefr_split.so|hsefr_split.h hsefr.h|group_split.hip|$COMMON|_ZN*_kernel*"
   "geom|../libhsefr_geom.so|hsefr_geom.h hsefr.h|geom_linkage.hip hier_linkage.hip|$COMMON -DHSEFR_GEOM_LIB|_ZN*_kernel*"
 )
-if [ "$MODE" = hostonly ]; then LIBS=("${LIBS[0]}"); fi      # the host-only recipe has nothing of the other libraries
+# ---- the extensions, same row format: compiled in the same pool and linked, stripped and linted by the same build_lib
+#   shift         libhsefr.so's own flags: mean-shift clustering (mean_shift.hip), fp64 on the MFMA
+EXT_LIBS=(
+  "shift|../libhsefr_shift.so|hsefr_shift.h hsefr.h|mean_shift.hip|$COMMON|_ZN*_kernel*"
+)
+if [ "$MODE" = hostonly ]; then LIBS=("${LIBS[0]}"); EXT_LIBS=(); fi      # the host-only recipe has nothing of the other libraries
 
 row() { IFS='|' read -r name out headers srcs flags keep <<< "$1"; }
 object() { if [ "$name" = hsefr ]; then echo "$BUILD/${1%.hip}.o"; else echo "$BUILD/${name}_${1%.hip}.o"; fi; }
@@ -70,8 +77,9 @@ compile_flags() {
   else echo "$flags -Xarch_host -Os${HSEFR_EXTRA_FLAGS:+ $HSEFR_EXTRA_FLAGS}"; fi
 }
 
-if [ "${1:-}" = "--list" ]; then
-  for r in "${LIBS[@]}"; do
+if [ "${1:-}" = "--list" ] || [ "${1:-}" = "--list-extensions" ]; then
+  if [ "$1" = "--list" ]; then LISTED=("${LIBS[@]}"); else LISTED=(${EXT_LIBS[@]+"${EXT_LIBS[@]}"}); fi
+  for r in ${LISTED[@]+"${LISTED[@]}"}; do
     row "$r"
     printf 'name=%s\tout=%s\tsrcs=%s\tflags=%s\tdeps=%s\tkeep=%s\tlint=%s' "$name" "$out" "$srcs" "$(compile_flags "")" "$(deps)" "$keep" \
       "$([ "$MODE" = hostonly ] && echo 0 || echo 1)"
@@ -83,9 +91,10 @@ fi
 
 # every stale compile of every library goes into one pool of at most 16 hipcc at a time; a failed compile fails the build (xargs
 # exits 123, set -e)
+ALL_LIBS=("${LIBS[@]}" ${EXT_LIBS[@]+"${EXT_LIBS[@]}"})
 mkdir -p "$BUILD"
 : > "$BUILD/compile.list"
-for r in "${LIBS[@]}"; do
+for r in "${ALL_LIBS[@]}"; do
   row "$r"
   for s in $srcs; do
     o="$(object "$s")"
@@ -127,4 +136,4 @@ build_lib() {
   fi
   echo "built $(realpath $out)"
 }
-for r in "${LIBS[@]}"; do build_lib "$r"; done
+for r in "${ALL_LIBS[@]}"; do build_lib "$r"; done

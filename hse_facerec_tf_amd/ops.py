@@ -1265,6 +1265,84 @@ def geom_linkage_merges(x=None, dense=None, born=None, year=None, method="ward",
     return out
 
 
+# include/hsefr_shift.h: HSEFR_SHIFT_MAX_N, _MAX_D, _D_MULTIPLE, _MAX_ITER, HSEFR_SHIFT_DIST2_ULPS(d) = d + SHIFT_DIST2_ULPS_PLUS and the
+# words of info
+SHIFT_MAX_N, SHIFT_MAX_D, SHIFT_D_MULTIPLE, SHIFT_MAX_ITER, SHIFT_DIST2_ULPS_PLUS = 65535, 4096, 4, 10000, 8
+SHIFT_INFO = ("centers", "n_iter", "distinct", "max_iter", "nonfinite", "internal", "work", "reserved")
+
+
+def mean_shift_distance_bound(d, bandwidth, norm_a=1.0, norm_b=1.0):
+    """The header's bound of the membership decision (include/hsefr_shift.h): with rows of norms <= norm_a and norm_b in d dimensions,
+    hsefr_shift_fit decides |a - b| <= bandwidth exactly wherever | |a - b| - bandwidth | exceeds this."""
+    return (d + SHIFT_DIST2_ULPS_PLUS) * 2.0 ** -53 * ((norm_a + norm_b) ** 2 + bandwidth ** 2) / bandwidth
+
+
+def _shift_rows(t, name):
+    """[n, d] float32 CUDA -> the same with zero columns padding d to a multiple of 4 (they change no distance and no mean)"""
+    torch = _lib.require_gpu()
+    _f32c(t, name)
+    if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError("%s must be [n, d] with n, d >= 1" % name)
+    if t.shape[1] % SHIFT_D_MULTIPLE:
+        t = torch.nn.functional.pad(t, (0, SHIFT_D_MULTIPLE - t.shape[1] % SHIFT_D_MULTIPLE)).contiguous()
+    return t
+
+
+@_device_guarded
+def mean_shift_fit(x, bandwidth, max_iter=300, info=None, workspace=None):
+    """sklearn.cluster.MeanShift(bandwidth=bandwidth, max_iter=max_iter).fit(x) (hsefr_shift_fit, libhsefr_shift.so) for x [n, d] float32
+    CUDA -> (cluster_centers float64 [k, d], intensity int32 [k], labels int32 [n], label_dist float64 [n], info), CUDA tensors but
+    info, a host dict of SHIFT_INFO's names read back.  fp64 on the device; zero columns pad d to a multiple of 4.  ``info``: an int32 CUDA
+    tensor [8] to receive the words (it holds them also when the call raises: info[4] = 1 with the ValueError of a non-finite feature);
+    ``workspace``: a uint8 CUDA tensor to use instead of a fresh one (ValueError if it is too small).  Returns with the current stream
+    synchronised."""
+    torch = _lib.require_gpu()
+    xp = _shift_rows(x, "x")
+    n, d = xp.shape
+    dev = xp.device
+    L = _lib.shift_lib()
+    need = L.hsefr_shift_workspace_bytes(n, d)
+    if workspace is None:
+        workspace = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
+    elif not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == dev):
+        raise ValueError("workspace must be a contiguous uint8 CUDA tensor on x's device")
+    if info is None:
+        info = torch.zeros((8,), dtype=torch.int32, device=dev)
+    elif not (info.is_cuda and info.dtype == torch.int32 and info.is_contiguous() and info.numel() == 8 and info.device == dev):
+        raise ValueError("info must be a contiguous int32 CUDA tensor of 8 words on x's device")
+    centers = torch.empty((n, d), dtype=torch.float64, device=dev)
+    intensity = torch.empty((n,), dtype=torch.int32, device=dev)
+    labels = torch.empty((n,), dtype=torch.int32, device=dev)
+    dist = torch.empty((n,), dtype=torch.float64, device=dev)
+    _lib.shift_check(L.hsefr_shift_fit(xp.data_ptr(), n, d, float(bandwidth), int(max_iter), centers.data_ptr(), intensity.data_ptr(),
+                                       labels.data_ptr(), dist.data_ptr(), info.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                       _lib.current_stream_ptr()), "hsefr_shift_fit")
+    words = dict(zip(SHIFT_INFO, (int(v) for v in info.cpu().numpy())))
+    k = words["centers"]
+    return centers[:k, :x.shape[1]], intensity[:k], labels, dist, words
+
+
+@_device_guarded
+def mean_shift_assign(q, centers):
+    """MeanShift.predict (hsefr_shift_assign): q [nq, d] float32 CUDA, centers [k, d] float64 CUDA -> (labels int32 [nq]: the nearest centre,
+    the lowest index among equal distances; dist float64 [nq]).  Asynchronous on the current stream."""
+    torch = _lib.require_gpu()
+    if not (centers.is_cuda and centers.dtype == torch.float64 and centers.dim() == 2 and centers.shape[0] >= 1):
+        raise ValueError("centers must be a float64 CUDA tensor [k, d] with k >= 1")
+    if q.dim() != 2 or q.shape[1] != centers.shape[1]:
+        raise ValueError("q must be [nq, %d] as the centres" % centers.shape[1])
+    qp = _shift_rows(q, "q")
+    nq, d = qp.shape
+    cp = centers.contiguous()
+    if cp.shape[1] != d:
+        cp = torch.nn.functional.pad(cp, (0, d - cp.shape[1])).contiguous()
+    labels = torch.empty((nq,), dtype=torch.int32, device=qp.device)
+    dist = torch.empty((nq,), dtype=torch.float64, device=qp.device)
+    _lib.shift_check(_lib.shift_lib().hsefr_shift_assign(qp.data_ptr(), nq, d, cp.data_ptr(), cp.shape[0], labels.data_ptr(), dist.data_ptr(),
+                                                         _lib.current_stream_ptr()), "hsefr_shift_assign")
+    return labels, dist
+
+
 @_device_guarded
 def dbscan_labels(x=None, dense=None, born=None, year=None, eps=0.5, min_samples=5):
     """DBSCAN with scikit-learn's labels (hsefr_dbscan) -> (labels int32 [n], core uint8 [n]) CUDA tensors: clusters 0, 1, ... in
