@@ -1,5 +1,6 @@
 """ctypes binding of libhsefr.so (include/hsefr.h) and of the libraries built beside it (include/hsefr_<name>.h), each described by
-one Library record in LIBRARIES, or in EXTENSIONS for a library that is not yet a member of that registry.  No fallback: if a library is missing the import of anything that needs it raises, and every
+one Library record in LIBRARIES, in EXTENSIONS for a library that is not yet a member of that registry, or in ADDONS, the open-ended
+dict by name that later libraries join.  No fallback: if a library is missing the import of anything that needs it raises, and every
 non-zero status becomes a Python exception in the reference's error style (ValueError for shape errors, NotImplementedError for
 unsupported graphs, RuntimeError otherwise)."""
 from __future__ import annotations
@@ -249,6 +250,17 @@ SHIFT_SIGNATURES = {
     "hsefr_shift_assign": (c_int, [_fp, c_int, c_int, _fp, c_int, _i32p, _fp, c_void_p]),
 }
 
+# libhsefr_affinity.so (include/hsefr_affinity.h): affinity-propagation clustering, the first add-on (ADDONS below)
+_f64, _ll = ctypes.c_double, c_longlong
+_AFFINITY_TAIL = [_f64, c_int, c_int, _f64, _ll, _i32p, _i32p, _fp, _fp, _i32p, _fp, c_size_t, c_void_p]
+AFFINITY_SIGNATURES = {
+    "hsefr_affinity_version": (c_int, []),
+    "hsefr_affinity_last_error": (c_char_p, []),
+    "hsefr_affinity_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "hsefr_affinity_fit": (c_int, [_fp, c_int, c_int] + _AFFINITY_TAIL),
+    "hsefr_affinity_fit_dense": (c_int, [_fp, c_int] + _AFFINITY_TAIL),
+}
+
 
 def _later(name, signatures, error_fn):
     return Library("hsefr_" + name, "libhsefr_%s.so" % name, "HSEFR_%s_LIB" % name.upper(), signatures, error_fn, "hsefr_%s_version" % name, 100)
@@ -273,6 +285,13 @@ EXTENSIONS = (
 )
 _SHIFT, = EXTENSIONS
 
+# the add-ons (csrc/build.sh: ADDON_LIBS), by name: libraries built, loaded and checked like those above.  The table is open-ended -- a
+# later library is one more entry here and one more row there, found by its name; nothing counts the entries
+ADDONS = {
+    "affinity": _later("affinity", AFFINITY_SIGNATURES, "hsefr_affinity_last_error"),
+}
+_AFFINITY = ADDONS["affinity"]
+
 # the module-level names of each library.  Callers go through the module attribute at call time (_lib.frames_lib()), so a test can put
 # another function in its place
 LIB_PATH, lib, last_error, check = _MAIN.path, _MAIN.load, _MAIN.last_error, _MAIN.check
@@ -284,6 +303,7 @@ MIXED_LIB_PATH, mixed_lib, mixed_last_error, mixed_check = _MIXED.path, _MIXED.l
 SPLIT_LIB_PATH, split_lib, split_last_error, split_check = _SPLIT.path, _SPLIT.load, _SPLIT.last_error, _SPLIT.check
 GEOM_LIB_PATH, geom_lib, geom_last_error, geom_check = _GEOM.path, _GEOM.load, _GEOM.last_error, _GEOM.check
 SHIFT_LIB_PATH, shift_lib, shift_last_error, shift_check = _SHIFT.path, _SHIFT.load, _SHIFT.last_error, _SHIFT.check
+AFFINITY_LIB_PATH, affinity_lib, affinity_last_error, affinity_check = _AFFINITY.path, _AFFINITY.load, _AFFINITY.last_error, _AFFINITY.check
 
 
 _torch_gpu = None      # torch, once a GPU has been seen (torch.cuda.is_available() re-reads the environment on every call: the

@@ -779,12 +779,17 @@ def cluster_faces_mean_shift(features, bandwidth=MEAN_SHIFT_BANDWIDTH, all_indic
     label order), as lists of ints.  With ``all_indices`` (the photo of every face) every cluster goes through the same-photo split
     (facial_clustering.py:250-261) -- ``split`` 'host': cluster by cluster on the host, 'device': split_same_photo's one pass -- its
     parts in order of their first face; clusters shorter than ``min_cluster_size`` are dropped."""
-    from . import ops
     _check_mean_shift_args(bandwidth, 300)
     _check_split(split)
     x, _, _ = _features(features, None, None, device, finite=True)
-    n = x.shape[0]
     labels = _mean_shift(x, float(bandwidth), 300, True)[1]
+    return _label_clusters(x, labels, all_indices, min_cluster_size, split)
+
+
+def _label_clusters(x, labels, all_indices, min_cluster_size, split) -> List[List[int]]:
+    """the list form of a labelling of the device features x: every label >= 0, the same-photo split, the largest first"""
+    from . import ops
+    n = x.shape[0]
     groups = [np.flatnonzero(labels == c) for c in range(int(labels.max()) + 1)]
     groups = [g for g in groups if len(g)]
     if all_indices is not None:
@@ -802,6 +807,96 @@ def cluster_faces_mean_shift(features, bandwidth=MEAN_SHIFT_BANDWIDTH, all_indic
     out = [[int(i) for i in g] for g in groups if len(g) >= min_cluster_size]
     out.sort(key=len, reverse=True)
     return out
+
+
+# ---- affinity propagation --------------------------------------------------------------------------------------------
+# facial_clustering_test.py:263: AffinityPropagation().fit(all_features) -- scikit-learn's defaults
+AFFINITY_DAMPING = 0.5
+AFFINITY_MAX_ITER = 200
+AFFINITY_CONVERGENCE_ITER = 15
+
+
+class ConvergenceWarning(UserWarning):
+    """affinity propagation ran max_iter iterations without its stop test holding (scikit-learn's warning of the same name)"""
+
+
+def _check_affinity_args(damping, max_iter, convergence_iter, preference, seed):
+    if isinstance(damping, bool) or not isinstance(damping, numbers.Real) or not 0.5 <= damping < 1:
+        raise ValueError("affinity_propagation: damping must be a real in [0.5, 1), got %r" % (damping,))
+    if isinstance(max_iter, bool) or not isinstance(max_iter, numbers.Integral) or max_iter < 1:
+        raise ValueError("affinity_propagation: max_iter must be an int >= 1, got %r" % (max_iter,))
+    if isinstance(convergence_iter, bool) or not isinstance(convergence_iter, numbers.Integral) or not 1 <= convergence_iter <= 64:
+        raise ValueError("affinity_propagation: convergence_iter must be an int in 1 .. 64, got %r" % (convergence_iter,))
+    if preference is not None and (isinstance(preference, bool) or not isinstance(preference, numbers.Real) or not math.isfinite(preference)):
+        raise ValueError("affinity_propagation: preference must be None (the median) or a finite real, got %r" % (preference,))
+    if seed is not None and (isinstance(seed, bool) or not isinstance(seed, numbers.Integral) or seed < 0):
+        raise ValueError("affinity_propagation: seed must be None (no noise) or an int >= 0, got %r" % (seed,))
+
+
+def _affinity(source, damping, max_iter, convergence_iter, preference, seed):
+    """affinity propagation on a checked device tensor, source = dict(x=...) or dict(S=...) -> (exemplars, labels, n_iter), host arrays"""
+    import warnings
+    from . import ops
+    exemplars, labels, _, _, info = ops.affinity_propagation_fit(damping=float(damping), max_iter=int(max_iter),
+                                                                 convergence_iter=int(convergence_iter), preference=preference, seed=seed,
+                                                                 **source)
+    if not info["converged"]:
+        warnings.warn("Affinity propagation did not converge%s." % (", this model may return degenerate cluster centers and labels"
+                                                                    if info["clusters"] else " and this model will not have any cluster centers"),
+                      ConvergenceWarning, stacklevel=3)
+    return exemplars.cpu().numpy().astype(np.int64), labels.cpu().numpy().astype(np.int64), info["n_iter"]
+
+
+def affinity_propagation(features, damping=AFFINITY_DAMPING, max_iter=AFFINITY_MAX_ITER, convergence_iter=AFFINITY_CONVERGENCE_ITER,
+                         preference=None, seed=0, device=None):
+    """sklearn.cluster.AffinityPropagation(damping=, max_iter=, convergence_iter=, preference=).fit(features.astype(float64)) on the GPU
+    -> (cluster_centers_indices int64 [K] ascending, labels int64 [n], n_iter).  The float32 features are widened exactly and everything
+    is fp64 (scikit-learn keeps float32 input's similarities in float32 and perturbs them at float32's eps).  ``preference`` None: the
+    median of the similarities.  ``seed``: the seed of the tie-breaking noise (scikit-learn's is unseeded; which member of a two-point
+    cluster is its exemplar depends on it), None for none.  A fit that does not converge raises a ConvergenceWarning and, without an
+    exemplar, labels every face -1.  Bad arguments or features raise ValueError before any device work (for host inputs)."""
+    _check_affinity_args(damping, max_iter, convergence_iter, preference, seed)
+    x, _, _ = _features(features, None, None, device, finite=True)
+    return _affinity(dict(x=x), damping, max_iter, convergence_iter, preference, seed)
+
+
+def affinity_propagation_dense(S, damping=AFFINITY_DAMPING, max_iter=AFFINITY_MAX_ITER, convergence_iter=AFFINITY_CONVERGENCE_ITER,
+                               preference=None, seed=0, device=None):
+    """AffinityPropagation(affinity="precomputed", ...).fit(S): ``S`` [n, n] similarities (larger is more alike; they may be asymmetric),
+    host or CUDA, read as float64 -> as affinity_propagation."""
+    from . import _lib
+    _check_affinity_args(damping, max_iter, convergence_iter, preference, seed)
+    M = S if hasattr(S, "is_cuda") else np.asarray(S, dtype=np.float64)
+    if M.ndim != 2 or M.shape[0] != M.shape[1] or M.shape[0] < 1:
+        raise ValueError("S must be a non-empty square matrix, got shape %r" % (tuple(M.shape),))
+    if not bool(np.isfinite(M).all() if isinstance(M, np.ndarray) else M.isfinite().all()):
+        raise ValueError("S holds non-finite values")
+    return _affinity(dict(S=_device_tensor(M, _lib.require_gpu().float64, device)), damping, max_iter, convergence_iter, preference, seed)
+
+
+def affinity_propagation_predict(features, centers, device=None) -> np.ndarray:
+    """AffinityPropagation.predict: the index of the nearest of ``centers`` [K, d] (the exemplars' rows, cluster_centers_) for every row of
+    ``features`` [n, d], the lowest index among equal distances -> int64 [n]; all -1 when the fit had no centre (K = 0)."""
+    centers = centers if hasattr(centers, "is_cuda") else np.asarray(centers, dtype=np.float64)
+    if centers.ndim != 2:
+        raise ValueError("centers must be [K, d]")
+    if centers.shape[0] == 0:
+        n = features.shape[0] if hasattr(features, "shape") else len(features)
+        return np.full(n, -1, dtype=np.int64)
+    return mean_shift_predict(features, centers, device=device)
+
+
+def cluster_faces_affinity_propagation(features, all_indices=None, min_cluster_size: int = 1, split: str = "host",
+                                       damping=AFFINITY_DAMPING, max_iter=AFFINITY_MAX_ITER, convergence_iter=AFFINITY_CONVERGENCE_ITER,
+                                       preference=None, seed=0, device=None) -> List[List[int]]:
+    """The scikit-learn branch of the reference's get_facial_clusters with its affinity-propagation row (facial_clustering_test.py:263,
+    265-266, 285): the members of every label >= 0 of affinity_propagation(features, ...), the largest cluster first (a stable sort of
+    the clusters in label order), as lists of ints.  ``all_indices``, ``split`` and ``min_cluster_size`` as in cluster_faces_mean_shift."""
+    _check_affinity_args(damping, max_iter, convergence_iter, preference, seed)
+    _check_split(split)
+    x, _, _ = _features(features, None, None, device, finite=True)
+    labels = _affinity(dict(x=x), damping, max_iter, convergence_iter, preference, seed)[1]
+    return _label_clusters(x, labels, all_indices, min_cluster_size, split)
 
 
 # ---- scoring --------------------------------------------------------------------------------------------------------
@@ -926,6 +1021,23 @@ def mean_shift_scores(features, y_true, bandwidths, device=None) -> np.ndarray:
     out = np.empty((len(bandwidths), len(STATS_NAMES)), dtype=np.float64)
     for r, b in enumerate(bandwidths):
         out[r] = clustering_scores(y_true, _mean_shift(x, b, 300, True)[1], device=x.device)
+    return out
+
+
+def affinity_propagation_scores(features, y_true, preferences, damping=AFFINITY_DAMPING, max_iter=AFFINITY_MAX_ITER,
+                                convergence_iter=AFFINITY_CONVERGENCE_ITER, seed=0, device=None) -> np.ndarray:
+    """get_clustering_statistics' ten numbers (STATS_NAMES) of affinity_propagation(features, preference=p) for every preference (None: the
+    median) -> float64 [len(preferences), 10]: the row of a preference is clustering_scores(y_true, its labels)."""
+    preferences = list(preferences) if isinstance(preferences, (list, tuple)) else list(np.asarray(preferences).reshape(-1))
+    for p in preferences:
+        _check_affinity_args(damping, max_iter, convergence_iter, p, seed)
+    x, _, _ = _features(features, None, None, device, finite=True)
+    if len(np.asarray(y_true).reshape(-1)) != x.shape[0]:
+        raise ValueError("%d true labels for %d faces" % (len(np.asarray(y_true).reshape(-1)), x.shape[0]))
+    out = np.empty((len(preferences), len(STATS_NAMES)), dtype=np.float64)
+    for r, p in enumerate(preferences):
+        labels = _affinity(dict(x=x), damping, max_iter, convergence_iter, None if p is None else float(p), seed)[1]
+        out[r] = clustering_scores(y_true, labels, device=x.device)
     return out
 
 

@@ -8,6 +8,8 @@
 #                          flags of the current mode and the files its objects are stale against (tests/test_libraries_cpu.py reads it)
 #   build.sh --list-extensions   the same for the table EXT_LIBS: the extensions, libraries built like the others that are not (yet) among
 #                          the package's registry of eight (hse_facerec_tf_amd/_lib.py: EXTENSIONS beside LIBRARIES)
+#   build.sh --list-addons the same for the table ADDON_LIBS: the add-ons, the open-ended third table (hse_facerec_tf_amd/_lib.py: ADDONS, a
+#                          dict by name) -- a later library is one more row there, found by its name, and nothing counts the rows
 set -euo pipefail
 cd "$(dirname "$0")"
 # product sources.  Development builds add round 1's stem (reachable only through lower_graph(stem_fusion="stem")) and the first window 3x3
@@ -64,7 +66,12 @@ LIBS=(
 EXT_LIBS=(
   "shift|../libhsefr_shift.so|hsefr_shift.h hsefr.h|mean_shift.hip|$COMMON|_ZN*_kernel*"
 )
-if [ "$MODE" = hostonly ]; then LIBS=("${LIBS[0]}"); EXT_LIBS=(); fi      # the host-only recipe has nothing of the other libraries
+# ---- the add-ons, same row format, same pool, same build_lib; rows are found by name and may be added freely
+#   affinity      libhsefr.so's own flags: affinity-propagation clustering (affinity.hip), fp64; the source switches contraction off itself
+ADDON_LIBS=(
+  "affinity|../libhsefr_affinity.so|hsefr_affinity.h hsefr.h|affinity.hip|$COMMON|_ZN*_kernel*"
+)
+if [ "$MODE" = hostonly ]; then LIBS=("${LIBS[0]}"); EXT_LIBS=(); ADDON_LIBS=(); fi      # the host-only recipe has nothing of the other libraries
 
 row() { IFS='|' read -r name out headers srcs flags keep <<< "$1"; }
 object() { if [ "$name" = hsefr ]; then echo "$BUILD/${1%.hip}.o"; else echo "$BUILD/${name}_${1%.hip}.o"; fi; }
@@ -77,8 +84,9 @@ compile_flags() {
   else echo "$flags -Xarch_host -Os${HSEFR_EXTRA_FLAGS:+ $HSEFR_EXTRA_FLAGS}"; fi
 }
 
-if [ "${1:-}" = "--list" ] || [ "${1:-}" = "--list-extensions" ]; then
-  if [ "$1" = "--list" ]; then LISTED=("${LIBS[@]}"); else LISTED=(${EXT_LIBS[@]+"${EXT_LIBS[@]}"}); fi
+if [ "${1:-}" = "--list" ] || [ "${1:-}" = "--list-extensions" ] || [ "${1:-}" = "--list-addons" ]; then
+  if [ "$1" = "--list" ]; then LISTED=("${LIBS[@]}"); elif [ "$1" = "--list-extensions" ]; then LISTED=(${EXT_LIBS[@]+"${EXT_LIBS[@]}"})
+  else LISTED=(${ADDON_LIBS[@]+"${ADDON_LIBS[@]}"}); fi
   for r in ${LISTED[@]+"${LISTED[@]}"}; do
     row "$r"
     printf 'name=%s\tout=%s\tsrcs=%s\tflags=%s\tdeps=%s\tkeep=%s\tlint=%s' "$name" "$out" "$srcs" "$(compile_flags "")" "$(deps)" "$keep" \
@@ -91,7 +99,7 @@ fi
 
 # every stale compile of every library goes into one pool of at most 16 hipcc at a time; a failed compile fails the build (xargs
 # exits 123, set -e)
-ALL_LIBS=("${LIBS[@]}" ${EXT_LIBS[@]+"${EXT_LIBS[@]}"})
+ALL_LIBS=("${LIBS[@]}" ${EXT_LIBS[@]+"${EXT_LIBS[@]}"} ${ADDON_LIBS[@]+"${ADDON_LIBS[@]}"})
 mkdir -p "$BUILD"
 : > "$BUILD/compile.list"
 for r in "${ALL_LIBS[@]}"; do

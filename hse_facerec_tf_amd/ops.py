@@ -1343,6 +1343,67 @@ def mean_shift_assign(q, centers):
     return labels, dist
 
 
+# include/hsefr_affinity.h: HSEFR_AFFINITY_MAX_N, _MAX_D, _D_MULTIPLE, _MAX_ITER, _MAX_CONVERGENCE_ITER, HSEFR_AFFINITY_SIM_ULPS(d) = d +
+# AFFINITY_SIM_ULPS_PLUS, HSEFR_AFFINITY_MSG_ULPS(n, d) = n (d + AFFINITY_MSG_ULPS_PLUS) and the words of info
+AFFINITY_MAX_N, AFFINITY_MAX_D, AFFINITY_D_MULTIPLE, AFFINITY_MAX_ITER, AFFINITY_MAX_CONVERGENCE_ITER = 16384, 4096, 4, 10000, 64
+AFFINITY_SIM_ULPS_PLUS, AFFINITY_MSG_ULPS_PLUS = 8, 24
+AFFINITY_INFO = ("clusters", "n_iter", "converged", "equal", "nonfinite", "internal", "reserved6", "reserved7")
+
+
+def affinity_message_bound(n, d, s_max):
+    """The header's first-order bound (include/hsefr_affinity.h) of how far A_kk + R_kk, a member sum or an assignment's similarity of
+    hsefr_affinity_fit can lie from scikit-learn's on fp64 input: n points of d features, similarities and preference within s_max."""
+    return n * (d + AFFINITY_MSG_ULPS_PLUS) * 2.0 ** -53 * s_max
+
+
+@_device_guarded
+def affinity_propagation_fit(x=None, S=None, damping=0.5, max_iter=200, convergence_iter=15, preference=None, seed=0, info=None,
+                             workspace=None):
+    """sklearn.cluster.AffinityPropagation(damping=, max_iter=, convergence_iter=, preference=).fit on fp64 input (libhsefr_affinity.so):
+    exactly one of ``x`` [n, d] float32 CUDA features (hsefr_affinity_fit: S = -|x_i - x_j|^2 in fp64, zero columns pad d to a multiple
+    of 4) and ``S`` [n, n] float64 CUDA similarities, which may be asymmetric (hsefr_affinity_fit_dense: affinity="precomputed") ->
+    (exemplars int32 [K] ascending, labels int32 [n], diag float64 [n]: the final A_kk + R_kk, preference: a float, info), CUDA tensors
+    but the last two; info is a host dict of AFFINITY_INFO's names.  ``preference`` None: the median of the similarities, exact.
+    ``seed`` >= 0: the header's hash noise (what decides exact ties; scikit-learn's is unseeded); None: no noise.  ``info``: an int32 CUDA
+    tensor [8] to receive the words (it holds them also when the call raises); ``workspace``: a uint8 CUDA tensor to use instead of a
+    fresh one.  Neither input is written.  Returns with the current stream synchronised."""
+    torch = _lib.require_gpu()
+    if (x is None) == (S is None):
+        raise ValueError("affinity_propagation_fit takes exactly one of x and S")
+    L = _lib.affinity_lib()
+    if x is not None:
+        src = _shift_rows(x, "x")
+        n, d = src.shape
+    else:
+        if not (S.is_cuda and S.dtype == torch.float64 and S.dim() == 2 and S.shape[0] == S.shape[1] and S.shape[0] >= 1):
+            raise ValueError("S must be a square float64 CUDA tensor [n, n] with n >= 1")
+        src = S.contiguous()
+        n, d = src.shape[0], AFFINITY_D_MULTIPLE
+    dev = src.device
+    need = L.hsefr_affinity_workspace_bytes(n, d)
+    if workspace is None:
+        workspace = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
+    elif not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == dev):
+        raise ValueError("workspace must be a contiguous uint8 CUDA tensor on the input's device")
+    if info is None:
+        info = torch.zeros((8,), dtype=torch.int32, device=dev)
+    elif not (info.is_cuda and info.dtype == torch.int32 and info.is_contiguous() and info.numel() == 8 and info.device == dev):
+        raise ValueError("info must be a contiguous int32 CUDA tensor of 8 words on the input's device")
+    exemplars = torch.empty((n,), dtype=torch.int32, device=dev)
+    labels = torch.empty((n,), dtype=torch.int32, device=dev)
+    diag = torch.empty((n,), dtype=torch.float64, device=dev)
+    pref = torch.empty((1,), dtype=torch.float64, device=dev)
+    tail = (float(damping), int(max_iter), int(convergence_iter), float("nan") if preference is None else float(preference),
+            -1 if seed is None else int(seed), exemplars.data_ptr(), labels.data_ptr(), diag.data_ptr(), pref.data_ptr(), info.data_ptr(),
+            workspace.data_ptr(), workspace.numel(), _lib.current_stream_ptr())
+    if x is not None:
+        _lib.affinity_check(L.hsefr_affinity_fit(src.data_ptr(), n, d, *tail), "hsefr_affinity_fit")
+    else:
+        _lib.affinity_check(L.hsefr_affinity_fit_dense(src.data_ptr(), n, *tail), "hsefr_affinity_fit_dense")
+    words = dict(zip(AFFINITY_INFO, (int(v) for v in info.cpu().numpy())))
+    return exemplars[:words["clusters"]], labels, diag, float(pref.item()), words
+
+
 @_device_guarded
 def dbscan_labels(x=None, dense=None, born=None, year=None, eps=0.5, min_samples=5):
     """DBSCAN with scikit-learn's labels (hsefr_dbscan) -> (labels int32 [n], core uint8 [n]) CUDA tensors: clusters 0, 1, ... in
