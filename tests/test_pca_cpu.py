@@ -146,6 +146,18 @@ def test_designed_spectra_keep_their_gaps(n, d, k):
     assert pca_cases.relative_gap(pca_cases.designed_spectrum(n, d, k), k) >= 1e-3
 
 
+@pytest.mark.parametrize("case", range(len(pca_cases.BLOCK_SHAPES) + 1))
+def test_stepped_spectra_keep_their_gaps(case):
+    """The same precondition at the block sizes of the protocol's own k, where 0.95^i leaves no gap: by construction 1 / 2k of lambda_1,
+    measured 5.56e-2, 7.14e-3, 6.25e-3, 3.91e-3, 1.95e-3, 3.91e-3, and 3.90e-3 for the large-mean case, which has no negative entry."""
+    name, x, k = pca_cases.block_cases()[case]
+    gap = pca_cases.relative_gap(x, k)
+    print("%s k=%d b=%d: gap %.2e" % (name, k, pca_cases.block_size(x.shape[0], x.shape[1], k), gap))
+    assert gap >= 1e-3
+    if case == len(pca_cases.BLOCK_SHAPES):
+        assert x.min() > 0 and x.mean() >= 100 * (x - x.mean(axis=0)).std()
+
+
 def test_protocol_gallery_keeps_its_gap():
     z, Xraw, _ = pca_cases.protocol_fixture()
     assert pca_cases.relative_gap(Xraw[z["gallery"]], 16) >= 1e-3
@@ -185,3 +197,38 @@ def test_golden_split_neighbour_margin():
     margin = pca_ref.neighbour_margin(pca_ref.transform(Xn[test], mean, comp), pca_ref.transform(Xn[train], mean, comp), first=2)
     print("golden split: margin %.2e" % margin)
     assert margin >= 4e-5
+
+
+def test_raw_gallery_at_the_reference_k():
+    """k = 128 (facerec_test.py:417) on the raw gallery, 170 x 256, so the block is capped at b = 169, an odd size: the restatement
+    agrees with PCA(svd_solver="full") on the float64 copy (measured 3.2e-15 lambda_1, 7.0e-14, 1.2e-13 max|Z|), the neighbour margin
+    is over the 4e-5 floor (measured 6.19e-5) and scikit-learn's pipeline finds the same neighbours.  The normalised gallery is left out:
+    its margin at k = 128 is 2.49e-5."""
+    from sklearn.decomposition import PCA
+    from sklearn.neighbors import KNeighborsClassifier
+    from sklearn.pipeline import Pipeline
+    k = 128
+    z, Xraw, _ = pca_cases.protocol_fixture()
+    g, p = z["gallery"], z["probe"]
+    yg = z["y"][g]
+    assert Xraw[g].shape == (170, 256) and pca_cases.block_size(170, 256, k) == 169
+    A = Xraw.astype(np.float64)
+    want = PCA(n_components=k, svd_solver="full").fit(A[g])
+    mean, comp, var = pca_ref.fit(A[g], k)
+    assert np.abs(var - want.explained_variance_).max() <= 1e-12 * var[0]
+    assert np.abs(np.abs(comp) - np.abs(want.components_)).max() <= 1e-9
+    assert np.array_equal(np.sign(comp), np.sign(want.components_))
+    for rows in (g, p):
+        Z, Zw = pca_ref.transform64(A[rows], mean, comp), want.transform(A[rows])
+        assert np.abs(Z - Zw).max() <= 1e-12 * np.abs(Zw).max()
+    zg, zp = pca_ref.transform(Xraw[g], mean, comp), pca_ref.transform(Xraw[p], mean, comp)
+    margin = pca_ref.neighbour_margin(zp, zg)
+    print("raw gallery k=%d: eigenvalues %.1e lambda_1, components %.1e, margin %.2e"
+          % (k, np.abs(var - want.explained_variance_).max() / var[0], np.abs(np.abs(comp) - np.abs(want.components_)).max(), margin))
+    assert margin >= 4e-5
+    for nn in (1, 3):
+        pipe = Pipeline(steps=[("pca", PCA(n_components=k)), ("classifier", KNeighborsClassifier(n_neighbors=nn, p=2))]).fit(Xraw[g], yg)
+        idx, _, pred = knn_ref.knn(zp, zg, nn, yg)
+        _, want_idx = pipe.named_steps["classifier"].kneighbors(pipe.named_steps["pca"].transform(Xraw[p]))
+        assert np.array_equal(idx, want_idx)
+        assert np.array_equal(pred, pipe.predict(Xraw[p]))
