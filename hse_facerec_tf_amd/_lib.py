@@ -1,8 +1,10 @@
 """ctypes binding of libhsefr.so (include/hsefr.h) and of the libraries built beside it (include/hsefr_<name>.h), each described by
-one Library record in LIBRARIES, in EXTENSIONS for a library that is not yet a member of that registry, or in ADDONS, the open-ended
-dict by name that later libraries join.  No fallback: if a library is missing the import of anything that needs it raises, and every
-non-zero status becomes a Python exception in the reference's error style (ValueError for shape errors, NotImplementedError for
-unsupported graphs, RuntimeError otherwise)."""
+one Library record in LIBRARIES.  No fallback: if a library is missing the import of anything that needs it raises, and every non-zero
+status becomes a Python exception in the reference's error style (ValueError for shape errors, NotImplementedError for unsupported
+graphs, RuntimeError otherwise).
+
+A new library is a record in LIBRARIES with its line of module-level names, a row of csrc/build.sh's table at the same place, a header
+under include/ and a row of FLOORS in tests/test_libraries_cpu.py."""
 from __future__ import annotations
 
 import ctypes
@@ -240,7 +242,7 @@ GEOM_SIGNATURES = {
     "hsefr_geom_linkage": (c_int, [_fp, c_int, c_int, _fp, _fp, _fp, c_int, _fp, _fp, _fp, _fp, _fp, _fp, c_void_p]),
 }
 
-# libhsefr_shift.so (include/hsefr_shift.h): mean-shift clustering, the first extension (EXTENSIONS below)
+# libhsefr_shift.so (include/hsefr_shift.h): mean-shift clustering
 _i32p = _fp
 SHIFT_SIGNATURES = {
     "hsefr_shift_version": (c_int, []),
@@ -250,7 +252,7 @@ SHIFT_SIGNATURES = {
     "hsefr_shift_assign": (c_int, [_fp, c_int, c_int, _fp, c_int, _i32p, _fp, c_void_p]),
 }
 
-# libhsefr_affinity.so (include/hsefr_affinity.h): affinity-propagation clustering, the first add-on (ADDONS below)
+# libhsefr_affinity.so (include/hsefr_affinity.h): affinity-propagation clustering
 _f64, _ll = ctypes.c_double, c_longlong
 _AFFINITY_TAIL = [_f64, c_int, c_int, _f64, _ll, _i32p, _i32p, _fp, _fp, _i32p, _fp, c_size_t, c_void_p]
 AFFINITY_SIGNATURES = {
@@ -276,21 +278,10 @@ LIBRARIES = (
     _later("mixed", MIXED_SIGNATURES, "hsefr_mixed_last_error_string"),
     _later("split", SPLIT_SIGNATURES, "hsefr_split_last_error"),
     _later("geom", GEOM_SIGNATURES, "hsefr_geom_last_error"),
+    _later("shift", SHIFT_SIGNATURES, "hsefr_shift_last_error"),
+    _later("affinity", AFFINITY_SIGNATURES, "hsefr_affinity_last_error"),
 )
-_MAIN, _ALBUM, _FRAMES, _FOREST, _RAGGED, _MIXED, _SPLIT, _GEOM = LIBRARIES
-
-# the extensions (csrc/build.sh: EXT_LIBS): libraries built, loaded and checked like the eight above that are not members of LIBRARIES
-EXTENSIONS = (
-    Library("hsefr_shift", "libhsefr_shift.so", "HSEFR_SHIFT_LIB", SHIFT_SIGNATURES, "hsefr_shift_last_error", "hsefr_shift_version", 100),
-)
-_SHIFT, = EXTENSIONS
-
-# the add-ons (csrc/build.sh: ADDON_LIBS), by name: libraries built, loaded and checked like those above.  The table is open-ended -- a
-# later library is one more entry here and one more row there, found by its name; nothing counts the entries
-ADDONS = {
-    "affinity": _later("affinity", AFFINITY_SIGNATURES, "hsefr_affinity_last_error"),
-}
-_AFFINITY = ADDONS["affinity"]
+_MAIN, _ALBUM, _FRAMES, _FOREST, _RAGGED, _MIXED, _SPLIT, _GEOM, _SHIFT, _AFFINITY = LIBRARIES
 
 # the module-level names of each library.  Callers go through the module attribute at call time (_lib.frames_lib()), so a test can put
 # another function in its place

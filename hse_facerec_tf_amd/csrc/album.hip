@@ -17,44 +17,20 @@
 //
 // Shared with libhsefr.so: no symbol (it is linked with -fvisibility=hidden; this library has its own error string).
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include "../../include/hsefr_album.h"
+#include "lib_error.h"
 
 #pragma clang fp contract(off)
 
 #include "cv_linear_px.h"
 
-using namespace hsefr;      // linear_tap, linear_blend (cv_linear_px.h, shared with mixed_frames.hip)
+using namespace hsefr;      // linear_tap, linear_blend (cv_linear_px.h, shared with mixed_frames.hip); g_error, set_error (lib_error.h)
+
+#define ALBUM_REQUIRE HSEFR_LIB_REQUIRE
+#define ALBUM_HIP_CHECK(expr) HSEFR_LIB_HIP_CHECK(expr, HSEFR_ALBUM_ERR_NOMEM, HSEFR_ALBUM_ERR_HIP)
 
 namespace {
-
-thread_local char g_error[512] = "";
-
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_error, sizeof g_error, fmt, ap);
-    va_end(ap);
-}
-
-#define ALBUM_REQUIRE(cond, code, ...) \
-    do {                               \
-        if (!(cond)) {                 \
-            set_error(__VA_ARGS__);    \
-            return (code);             \
-        }                              \
-    } while (0)
-
-#define ALBUM_HIP_CHECK(expr)                                                                              \
-    do {                                                                                                   \
-        hipError_t _e = (expr);                                                                            \
-        if (_e != hipSuccess) {                                                                            \
-            set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);          \
-            return _e == hipErrorOutOfMemory ? HSEFR_ALBUM_ERR_NOMEM : HSEFR_ALBUM_ERR_HIP;                \
-        }                                                                                                  \
-    } while (0)
 
 constexpr int UNITS_PER_BLOCK = 1024;      // 16-byte pieces (or single bytes) of one face's output per workgroup: four per thread
 constexpr int MAX_TAPS = 4096;             // oh + ow: the two tap tables of a workgroup, 12 bytes per entry, in LDS

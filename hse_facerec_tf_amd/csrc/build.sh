@@ -6,10 +6,8 @@
 #                          variables, hsefr_debug_*, the calibration kernels of devtools.hip) -- for tools/kbench.py only.
 #   build.sh --list        prints the resolved table and compiles nothing: per library its name, output, sources, the complete compile
 #                          flags of the current mode and the files its objects are stale against (tests/test_libraries_cpu.py reads it)
-#   build.sh --list-extensions   the same for the table EXT_LIBS: the extensions, libraries built like the others that are not (yet) among
-#                          the package's registry of eight (hse_facerec_tf_amd/_lib.py: EXTENSIONS beside LIBRARIES)
-#   build.sh --list-addons the same for the table ADDON_LIBS: the add-ons, the open-ended third table (hse_facerec_tf_amd/_lib.py: ADDONS, a
-#                          dict by name) -- a later library is one more row there, found by its name, and nothing counts the rows
+# A new library is a row of LIBS, a record in hse_facerec_tf_amd/_lib.py's LIBRARIES at the same place, a header under include/ and a row
+# of FLOORS in tests/test_libraries_cpu.py.
 set -euo pipefail
 cd "$(dirname "$0")"
 # product sources.  Development builds add round 1's stem (reachable only through lower_graph(stem_fusion="stem")) and the first window 3x3
@@ -22,7 +20,7 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -Wall -Wno
 # tests/test_abi_cpu.py): the runtime, the profilers and tools/isa_lint.py need only the kernel symbols, which stay
 DEVICE_STRIP="-Xoffload-linker --discard-all"
 LINK="--offload-arch=gfx950"
-# what the seven later libraries are compiled with in every mode (no -DHSEFR_DEV code in them): libhsefr.so's own product flags
+# what the nine later libraries are compiled with in every mode (no -DHSEFR_DEV code in them): libhsefr.so's own product flags
 COMMON="$FLAGS $DEVICE_STRIP"
 # the three modes of the main library: its output, its build directory (the other libraries' objects go there too) and its flags
 if [ "${HSEFR_ASAN:-0}" = "1" ]; then
@@ -51,6 +49,8 @@ fi
 #                 linkage_scan.h's feat_tile over mfma_dot.h) and must give their bits
 #   geom          the same plus -DHSEFR_GEOM_LIB: besides geom_linkage.hip it compiles hier_linkage.hip a second time (the working matrix
 #                 over feat_tile, and the rounds with Ward's rule).  The three update rules switch contraction off themselves (geom_rules.h)
+#   shift         libhsefr.so's own flags: mean-shift clustering (mean_shift.hip), fp64 on the MFMA
+#   affinity      libhsefr.so's own flags: affinity-propagation clustering (affinity.hip), fp64; the source switches contraction off itself
 LIBS=(
   "hsefr|$OUT|hsefr.h|$SRCS|$FLAGS|_ZN5hsefr*_kernel*"
   "album|../libhsefr_album.so|hsefr_album.h|album.hip|$COMMON -ffp-contract=off|_ZN*_kernel*"
@@ -60,18 +60,10 @@ LIBS=(
   "mixed|../libhsefr_mixed.so|hsefr_mixed.h|mixed_frames.hip|$COMMON -ffp-contract=off|_ZN*_kernel*"
   "split|../libhsefr_split.so|hsefr_split.h hsefr.h|group_split.hip|$COMMON|_ZN*_kernel*"
   "geom|../libhsefr_geom.so|hsefr_geom.h hsefr.h|geom_linkage.hip hier_linkage.hip|$COMMON -DHSEFR_GEOM_LIB|_ZN*_kernel*"
-)
-# ---- the extensions, same row format: compiled in the same pool and linked, stripped and linted by the same build_lib
-#   shift         libhsefr.so's own flags: mean-shift clustering (mean_shift.hip), fp64 on the MFMA
-EXT_LIBS=(
   "shift|../libhsefr_shift.so|hsefr_shift.h hsefr.h|mean_shift.hip|$COMMON|_ZN*_kernel*"
-)
-# ---- the add-ons, same row format, same pool, same build_lib; rows are found by name and may be added freely
-#   affinity      libhsefr.so's own flags: affinity-propagation clustering (affinity.hip), fp64; the source switches contraction off itself
-ADDON_LIBS=(
   "affinity|../libhsefr_affinity.so|hsefr_affinity.h hsefr.h|affinity.hip|$COMMON|_ZN*_kernel*"
 )
-if [ "$MODE" = hostonly ]; then LIBS=("${LIBS[0]}"); EXT_LIBS=(); ADDON_LIBS=(); fi      # the host-only recipe has nothing of the other libraries
+if [ "$MODE" = hostonly ]; then LIBS=("${LIBS[0]}"); fi      # the host-only recipe has nothing of the other libraries
 
 row() { IFS='|' read -r name out headers srcs flags keep <<< "$1"; }
 object() { if [ "$name" = hsefr ]; then echo "$BUILD/${1%.hip}.o"; else echo "$BUILD/${name}_${1%.hip}.o"; fi; }
@@ -84,10 +76,8 @@ compile_flags() {
   else echo "$flags -Xarch_host -Os${HSEFR_EXTRA_FLAGS:+ $HSEFR_EXTRA_FLAGS}"; fi
 }
 
-if [ "${1:-}" = "--list" ] || [ "${1:-}" = "--list-extensions" ] || [ "${1:-}" = "--list-addons" ]; then
-  if [ "$1" = "--list" ]; then LISTED=("${LIBS[@]}"); elif [ "$1" = "--list-extensions" ]; then LISTED=(${EXT_LIBS[@]+"${EXT_LIBS[@]}"})
-  else LISTED=(${ADDON_LIBS[@]+"${ADDON_LIBS[@]}"}); fi
-  for r in ${LISTED[@]+"${LISTED[@]}"}; do
+if [ "${1:-}" = "--list" ]; then
+  for r in "${LIBS[@]}"; do
     row "$r"
     printf 'name=%s\tout=%s\tsrcs=%s\tflags=%s\tdeps=%s\tkeep=%s\tlint=%s' "$name" "$out" "$srcs" "$(compile_flags "")" "$(deps)" "$keep" \
       "$([ "$MODE" = hostonly ] && echo 0 || echo 1)"
@@ -99,10 +89,9 @@ fi
 
 # every stale compile of every library goes into one pool of at most 16 hipcc at a time; a failed compile fails the build (xargs
 # exits 123, set -e)
-ALL_LIBS=("${LIBS[@]}" ${EXT_LIBS[@]+"${EXT_LIBS[@]}"} ${ADDON_LIBS[@]+"${ADDON_LIBS[@]}"})
 mkdir -p "$BUILD"
 : > "$BUILD/compile.list"
-for r in "${ALL_LIBS[@]}"; do
+for r in "${LIBS[@]}"; do
   row "$r"
   for s in $srcs; do
     o="$(object "$s")"
@@ -144,4 +133,4 @@ build_lib() {
   fi
   echo "built $(realpath $out)"
 }
-for r in "${ALL_LIBS[@]}"; do build_lib "$r"; done
+for r in "${LIBS[@]}"; do build_lib "$r"; done

@@ -30,29 +30,16 @@
 //
 // Shared with the other three libraries: nothing (linked with -fvisibility=hidden; this library has its own error string).
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include "../../include/hsefr_forest.h"
+#include "lib_error.h"
+
+using hsefr::g_error;
+using hsefr::set_error;
+
+#define FOREST_REQUIRE HSEFR_LIB_REQUIRE
 
 namespace {
-
-thread_local char g_error[512] = "";
-
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_error, sizeof g_error, fmt, ap);
-    va_end(ap);
-}
-
-#define FOREST_REQUIRE(cond, code, ...) \
-    do {                                \
-        if (!(cond)) {                  \
-            set_error(__VA_ARGS__);     \
-            return (code);              \
-        }                               \
-    } while (0)
 
 typedef unsigned long long u64;
 

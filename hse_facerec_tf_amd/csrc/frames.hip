@@ -22,32 +22,17 @@
 //
 // Shared with libhsefr.so and libhsefr_album.so: no symbol (linked with -fvisibility=hidden; this library has its own error string).
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include "../../include/hsefr_frames.h"
 #include "frames_px.h"
+#include "lib_error.h"
 
-using namespace hsefr;      // Px4, unpack4, pack4, store_px4, load_pixel, store_pixel, swap_02 (frames_px.h, shared with mixed_frames.hip)
+// Px4, unpack4, pack4, store_px4, load_pixel, store_pixel, swap_02 (frames_px.h, shared with mixed_frames.hip); g_error, set_error (lib_error.h)
+using namespace hsefr;
+
+#define FRAMES_REQUIRE HSEFR_LIB_REQUIRE
 
 namespace {
-
-thread_local char g_error[512] = "";
-
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_error, sizeof g_error, fmt, ap);
-    va_end(ap);
-}
-
-#define FRAMES_REQUIRE(cond, code, ...) \
-    do {                                \
-        if (!(cond)) {                  \
-            set_error(__VA_ARGS__);     \
-            return (code);              \
-        }                               \
-    } while (0)
 
 constexpr int TILE = 64;                   // pixels per tile side
 constexpr int TILE_STRIDE = TILE + 4;      // dwords per LDS row (see the head of the file)

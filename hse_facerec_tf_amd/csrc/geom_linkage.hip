@@ -30,28 +30,16 @@
 // No grid-wide barriers, no cooperative launches, no spin-waits, no persistent kernels.  Every store is a vector store from plain C++.
 //
 // Shared with the other seven libraries: no symbol (linked with -fvisibility=hidden).  What common.h declares of libhsefr.so and this
-// library uses -- the error string, the route probe behind launch_status -- is defined here for this library alone.
+// library uses -- the error string, the route probe behind launch_status -- is defined by lib_error.h, in this source of the two.
 #include <math.h>
 #include <string.h>
 
 #include "hier_build.h"
 #include "geom_rules.h"
+#include "lib_error.h"
 #include "../../include/hsefr_geom.h"
 
 namespace hsefr {
-
-namespace {
-thread_local char g_error[512] = "";
-}
-
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_error, sizeof g_error, fmt, ap);
-    va_end(ap);
-}
-bool route_probe() { return false; }                 // this library has no plan and no probe: every launch launches
-void route_record(const void*, const char*) {}
 
 namespace {
 

@@ -29,28 +29,16 @@
 // Every store is a vector store from plain C++.
 //
 // Shared with the other six libraries: no symbol (linked with -fvisibility=hidden).  What common.h declares of libhsefr.so and this file
-// uses -- the error string, the route probe behind launch_status -- is defined here for this library alone.
+// uses -- the error string, the route probe behind launch_status -- is defined by lib_error.h for this library alone.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include "linkage_scan.h"
+#include "lib_error.h"
 #include "../../include/hsefr_split.h"
 
 namespace hsefr {
-
-namespace {
-thread_local char g_error[512] = "";
-}
-
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_error, sizeof g_error, fmt, ap);
-    va_end(ap);
-}
-bool route_probe() { return false; }                 // this library has no plan and no probe: every launch launches
-void route_record(const void*, const char*) {}
 
 namespace {
 

@@ -26,22 +26,10 @@
 #include <string.h>
 
 #include "common.h"
+#include "lib_error.h"
 #include "../../include/hsefr_shift.h"
 
 namespace hsefr {
-
-namespace {
-thread_local char g_error[512] = "";
-}
-
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_error, sizeof g_error, fmt, ap);
-    va_end(ap);
-}
-bool route_probe() { return false; }                 // this library has no plan and no probe: every launch launches
-void route_record(const void*, const char*) {}
 
 namespace {
 

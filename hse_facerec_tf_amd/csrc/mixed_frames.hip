@@ -23,8 +23,6 @@
 //
 // Shared with the other five libraries: no symbol (linked with -fvisibility=hidden; this library has its own error string).
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -32,38 +30,16 @@
 
 #include "../../include/hsefr_mixed.h"
 
+#include "lib_error.h"
 #include "frames_px.h"
 #include "cv_linear_px.h"      // (turns contraction off from here on; csrc/build.sh adds the flag too)
 
 using namespace hsefr;
 
+#define MIXED_REQUIRE HSEFR_LIB_REQUIRE
+#define MIXED_HIP_CHECK(expr) HSEFR_LIB_HIP_CHECK(expr, HSEFR_MIXED_ERR_NOMEM, HSEFR_MIXED_ERR_HIP)
+
 namespace {
-
-thread_local char g_error[512] = "";
-
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_error, sizeof g_error, fmt, ap);
-    va_end(ap);
-}
-
-#define MIXED_REQUIRE(cond, code, ...) \
-    do {                               \
-        if (!(cond)) {                 \
-            set_error(__VA_ARGS__);    \
-            return (code);             \
-        }                              \
-    } while (0)
-
-#define MIXED_HIP_CHECK(expr)                                                                              \
-    do {                                                                                                   \
-        hipError_t _e = (expr);                                                                            \
-        if (_e != hipSuccess) {                                                                            \
-            set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);          \
-            return _e == hipErrorOutOfMemory ? HSEFR_MIXED_ERR_NOMEM : HSEFR_MIXED_ERR_HIP;                \
-        }                                                                                                  \
-    } while (0)
 
 // host scratch of a call (malloc, not std::vector: the library exports its four entries and nothing of the C++ runtime's templates)
 template <typename T>

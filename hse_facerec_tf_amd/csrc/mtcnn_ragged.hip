@@ -18,33 +18,17 @@
 //
 // Shared with the other four libraries: nothing at link time (-fvisibility=hidden; this library has its own error string).
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include "../../include/hsefr_ragged.h"
 #include "area_resize_px.h"
+#include "lib_error.h"
 #include "mtcnn_post_frame.h"
+
+#define RAGGED_REQUIRE HSEFR_LIB_REQUIRE
 
 namespace hsefr {
 
 namespace {
-
-thread_local char g_error[512] = "";
-
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_error, sizeof g_error, fmt, ap);
-    va_end(ap);
-}
-
-#define RAGGED_REQUIRE(cond, code, ...) \
-    do {                                \
-        if (!(cond)) {                  \
-            set_error(__VA_ARGS__);     \
-            return (code);              \
-        }                               \
-    } while (0)
 
 int launch_status(const char* what) {
     const hipError_t e = hipGetLastError();

@@ -11,9 +11,8 @@
  * are doubles.  scikit-learn itself keeps an fp32 input's similarities in fp32 and perturbs them at fp32's eps; what this library
  * answers is AffinityPropagation(...).fit(X.astype(np.float64)).
  *
- * The first ADD-ON of the package (hse_facerec_tf_amd/_lib.py: ADDONS, a dict by name; csrc/build.sh: ADDON_LIBS): a library of its own
- * as the nine before it -- nothing is shared but the status values of hsefr.h, its own version and per-thread error string -- in a table
- * that is open-ended: a later library is one more row and one more entry, and nothing counts them.
+ * The tenth library of the package (hse_facerec_tf_amd/_lib.py: LIBRARIES; csrc/build.sh: LIBS): a library of its own as the nine
+ * before it -- nothing is shared but the status values of hsefr.h, its own version and per-thread error string.
  *
  * Conventions: those of hsefr.h, whose status values this header uses -- extern "C", plain C types, 0 on success or a negative
  * hsefr_status, never throws, data pointers are DEVICE pointers owned by the caller, `stream` is a hipStream_t.  Built for gfx950 only.

@@ -9,9 +9,9 @@
  * all seeds advanced together: every row of X is a seed, an iteration of all active seeds is two fp64 matrix products, and the only
  * N x N object is a BIT matrix (one bit per pair: 10.5 MB at 9164 faces).
  *
- * The first EXTENSION of the package (hse_facerec_tf_amd/_lib.py: EXTENSIONS; csrc/build.sh: EXT_LIBS): a library of its own as the
- * seven before it -- libhsefr.so stays as it is, nothing is shared but the status values below, its own version and per-thread error
- * string -- that is not yet a member of the package's registry of eight.
+ * The ninth library of the package (hse_facerec_tf_amd/_lib.py: LIBRARIES; csrc/build.sh: LIBS): a library of its own as the seven
+ * later ones before it -- libhsefr.so stays as it is, nothing is shared but the status values below, its own version and per-thread
+ * error string.
  *
  * Conventions: those of hsefr.h, whose status values this header uses -- extern "C", plain C types, 0 on success or a negative
  * hsefr_status, never throws, data pointers are DEVICE pointers owned by the caller, `stream` is a hipStream_t.  Built for gfx950 only.

@@ -1,13 +1,12 @@
 """CPU suite: affinity-propagation clustering without a GPU -- the NumPy restatement the GPU suite compares with is scikit-learn (on fp64
 input) on every recorded case (tests/golden/affinity.npz, recorded by tools/record_affinity_golden.py), without noise and with the
-header's hash noise; the hash restated in NumPy is the header's; and libhsefr_affinity.so, the package's first add-on: header, exports
-and binding agree, version, loaded once, gfx950 only, the ISA lint, its row of csrc/build.sh found by name, every refused argument
-before any device work."""
+header's hash noise; the hash restated in NumPy is the header's; and what is libhsefr_affinity.so's own: its functions' argument counts,
+the header's limits, bounds and info words against ops, its row of csrc/build.sh, what its source promises, every refused argument before
+any device work.  What holds for every library of the package -- header, exports and binding agree, version, loaded once, gfx950 only,
+the ISA lint, no other library's names -- tests/test_libraries_cpu.py asserts for this one too."""
 import ctypes
-import importlib.util
 import os
 import re
-import subprocess
 import warnings
 
 import numpy as np
@@ -221,33 +220,15 @@ def test_the_older_entry_points_still_refuse_the_name(monkeypatch, name):
             call()
 
 
-# ---- the library -------------------------------------------------------------------------------------------------------------------------
-def code(path):
-    return re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-
-
-def test_header_library_and_binding_agree():
+# ---- the library: what is libhsefr_affinity.so's own (what every library shares is asserted for it in tests/test_libraries_cpu.py) ------
+def test_the_arguments_limits_bounds_and_info_words_are_the_headers():
     from hse_facerec_tf_amd import _lib, ops
-    library = _lib.ADDONS["affinity"]
-    assert isinstance(_lib.ADDONS, dict) and isinstance(library, _lib.Library)
-    assert (library.tag, library.file, library.env, library.version) == ("hsefr_affinity", "libhsefr_affinity.so", "HSEFR_AFFINITY_LIB", 100)
-    assert library not in _lib.LIBRARIES and library not in _lib.EXTENSIONS
-    assert sorted(set(re.findall(r"\b(hsefr_affinity_[a-z0-9_]+)\s*\(", code(HEADER)))) == NAMES
-    assert sorted(_lib.AFFINITY_SIGNATURES) == NAMES and library.signatures is _lib.AFFINITY_SIGNATURES
-    out = subprocess.run(["nm", "-D", "--defined-only", library.path], capture_output=True, text=True, check=True).stdout
-    symbols = [l.split() for l in out.splitlines()]
-    assert sorted(s[-1] for s in symbols if s[-2] == "T" and not s[-1].startswith(("_init", "_fini"))) == NAMES
-    assert not [s[-1] for s in symbols if s[-2] == "W"]
-    for name, count in (("hsefr_affinity_fit", 16), ("hsefr_affinity_fit_dense", 15), ("hsefr_affinity_workspace_bytes", 2)):
-        args = re.search(r"\b%s\((.*?)\);" % name, code(HEADER), flags=re.S).group(1)
-        assert len(args.split(",")) == len(_lib.AFFINITY_SIGNATURES[name][1]) == count
-    L = library.load()
+    assert sorted(_lib.AFFINITY_SIGNATURES) == NAMES
     header = open(HEADER).read()
-    assert L.hsefr_affinity_version() == int(re.search(r"#define HSEFR_AFFINITY_VERSION (\d+)", header).group(1)) == 100
-    assert library.load() is L and _lib.affinity_lib() is L                              # loaded once
-    assert (_lib.AFFINITY_LIB_PATH, _lib.affinity_lib, _lib.affinity_last_error, _lib.affinity_check) == \
-        (library.path, library.load, library.last_error, library.check)
-    assert isinstance(_lib.affinity_last_error(), str)
+    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    for name, count in (("hsefr_affinity_fit", 16), ("hsefr_affinity_fit_dense", 15), ("hsefr_affinity_workspace_bytes", 2)):
+        args = re.search(r"\b%s\((.*?)\);" % name, code, flags=re.S).group(1)
+        assert len(args.split(",")) == len(_lib.AFFINITY_SIGNATURES[name][1]) == count
     for macro, value in (("MAX_N", ops.AFFINITY_MAX_N), ("MAX_D", ops.AFFINITY_MAX_D), ("D_MULTIPLE", ops.AFFINITY_D_MULTIPLE),
                          ("MAX_ITER", ops.AFFINITY_MAX_ITER), ("MAX_CONVERGENCE_ITER", ops.AFFINITY_MAX_CONVERGENCE_ITER)):
         assert int(re.search(r"#define HSEFR_AFFINITY_%s (\d+)" % macro, header).group(1)) == value
@@ -257,54 +238,15 @@ def test_header_library_and_binding_agree():
     plus = int(re.search(r"#define HSEFR_AFFINITY_MSG_ULPS\(n, d\) \(\(n\) \* \(\(d\) \+ (\d+)\)\)", header).group(1))
     assert plus == ops.AFFINITY_MSG_ULPS_PLUS
     assert ops.affinity_message_bound(1926, 64, 4.0) == 1926 * (64 + plus) * 2.0 ** -53 * 4.0 < 8e-11
-    words = re.search(r"enum \{(.*?)\};", code(HEADER), flags=re.S).group(1)
+    words = re.search(r"enum \{(.*?)\};", code, flags=re.S).group(1)
     assert [int(v) for v in re.findall(r"HSEFR_AFFINITY_INFO_[A-Z_]+ = (\d+)", words)] == [0, 1, 2, 3, 4, 5, 8] and len(ops.AFFINITY_INFO) == 8
 
 
-def test_the_build_after_check_covers_every_table():
-    from hse_facerec_tf_amd import _lib
-    entry = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert "_lib.LIBRARIES" in entry and "_lib.EXTENSIONS" in entry and "_lib.ADDONS" in entry
-    for library in tuple(_lib.EXTENSIONS) + tuple(_lib.ADDONS.values()):
-        assert getattr(library.load(), library.version_fn)() == library.version
-
-
-def test_code_object_targets_gfx950_only():
-    from hse_facerec_tf_amd import _lib
-    blob = open(_lib.AFFINITY_LIB_PATH, "rb").read()
-    assert b"gfx950" in blob
-    for other in (b"gfx942", b"gfx90a", b"sm_90", b"gfx1100"):
-        assert other not in blob
-
-
-def test_device_code_passes_the_isa_lint():
-    from hse_facerec_tf_amd import _lib
-    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump"):
-        pytest.skip("no llvm-objdump on this machine")
-    spec = importlib.util.spec_from_file_location("isa_lint", os.path.join(ROOT, "tools", "isa_lint.py"))
-    lint = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(lint)
-    findings, n_symbols, n_stores = lint.lint(_lib.AFFINITY_LIB_PATH)
-    assert n_symbols >= KERNELS, "the lint did not see the kernels"
-    assert findings == []
-
-
-def listed(flag):
-    out = subprocess.run(["bash", build_table.BUILD_SH, flag], capture_output=True, text=True, check=True,
-                         env={k: v for k, v in os.environ.items() if k not in ("HSEFR_DEV", "HSEFR_ASAN", "HSEFR_EXTRA_FLAGS")}).stdout
-    return [dict(field.split("=", 1) for field in line.split("\t")) for line in out.splitlines()]
-
-
-def test_the_build_script_lists_the_addon_by_name():
-    rows = {row["name"]: row for row in listed("--list-addons")}
-    row = rows["affinity"]
-    assert (row["out"], row["srcs"], row["keep"], row["lint"]) == ("../libhsefr_affinity.so", "affinity.hip", "_ZN*_kernel*", "1")
-    deps = row["deps"].split()
-    assert "../../include/hsefr_affinity.h" in deps and "../../include/hsefr.h" in deps and "build.sh" in deps and "common.h" in deps
-    assert row["flags"].split() == build_table.rows()["frames"]["flags"]               # $COMMON, the flags of the other later libraries
-    assert "affinity" not in build_table.rows() and "affinity" not in [r["name"] for r in listed("--list-extensions")]
-    script = open(build_table.BUILD_SH).read()
-    assert script.count("isa_lint.py \"") == 1 and script.count("\nADDON_LIBS=(\n") == 1      # one build_lib, one lint, one table
+def test_the_librarys_row_of_the_build_table():
+    row = build_table.rows()["affinity"]
+    assert (row["out"], row["srcs"]) == ("../libhsefr_affinity.so", ["affinity.hip"])
+    assert build_table.stale_against("affinity", "common.h", "include/hsefr.h", "include/hsefr_affinity.h")
+    assert row["flags"] == build_table.rows()["frames"]["flags"]                       # $COMMON, the flags of the other later libraries
 
 
 def test_the_source_keeps_its_promises():

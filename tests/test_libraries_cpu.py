@@ -29,6 +29,10 @@ FLOORS = {
     "hsefr_mixed": (4, 4),            # the swap, the turn, two crop instances; the swap's unit, the turn's two directions, the crops' 16 bytes
     "hsefr_split": (4, 1),            # the build and the three chain instances; the build's pair of matrix entries
     "hsefr_geom": (10, 0),            # the rounds' seven, the engine's four
+    "hsefr_shift": (14, 3),           # prep, norms x 2, member x 2, means, step, compact, rank, gather, suppress, centers, assign, info; the
+                                      # 16-byte stores of the three row copies
+    "hsefr_affinity": (19, 0),        # norms, sim, copy, minmax, hist, digit, prepare, sweep x 2, colsum, stop, select, assign, member_sum,
+                                      # winner, relist, labels, trivial, info
 }
 # libhsefr.so alone exports weak symbols: instances of the C++ runtime's own templates (std::vector, std::map), which no flag of its
 # build hides.  Nothing of the project is among them, and no other library has any
@@ -78,8 +82,9 @@ def test_header_library_and_binding_agree(library):
 
 
 def test_the_module_names_are_the_registrys():
-    assert IDS == ["hsefr", "hsefr_album", "hsefr_frames", "hsefr_forest", "hsefr_ragged", "hsefr_mixed", "hsefr_split", "hsefr_geom"]
-    assert [library.version for library in LIBRARIES] == [141] + [100] * 7
+    assert IDS == ["hsefr", "hsefr_album", "hsefr_frames", "hsefr_forest", "hsefr_ragged", "hsefr_mixed", "hsefr_split", "hsefr_geom",
+                   "hsefr_shift", "hsefr_affinity"]
+    assert [library.version for library in LIBRARIES] == [141] + [100] * 9
     assert (_lib.LIB_PATH, _lib.SIGNATURES, _lib.DEV_SIGNATURES) == (LIBRARIES[0].path, LIBRARIES[0].signatures, LIBRARIES[0].optional)
     assert (_lib.lib, _lib.last_error, _lib.check) == (LIBRARIES[0].load, LIBRARIES[0].last_error, LIBRARIES[0].check)
     for library in LIBRARIES[1:]:
@@ -89,6 +94,8 @@ def test_the_module_names_are_the_registrys():
             (library.load, library.last_error, library.check)
         assert library.env == "HSEFR_%s_LIB" % x.upper() and library.file == "lib%s.so" % library.tag
         assert getattr(_lib, x + "_lib")() is library.load()
+    # the check behind a build walks this registry and no other table
+    assert "for library in _lib.LIBRARIES:" in open(os.path.join(ROOT, "__graft_entry__.py")).read()
 
 
 @pytest.mark.parametrize("library", LIBRARIES, ids=IDS)

@@ -1,12 +1,12 @@
 """CPU suite: mean-shift clustering without a GPU -- the NumPy restatement the GPU suite compares with is scikit-learn on every recorded
 case (tests/golden/mean_shift.npz, recorded by tools/record_mean_shift_golden.py) and on a live fit of the small ones, the margins in
-the file are the restatement's, and libhsefr_shift.so, the package's first extension: header, exports and binding agree, version, loaded
-once, gfx950 only, the ISA lint, its row of csrc/build.sh beside the eight, every refused argument before any device work."""
+the file are the restatement's, and what is libhsefr_shift.so's own: its functions' argument counts, the header's limits, bound and info
+words against ops, its row of csrc/build.sh, what its source promises, every refused argument before any device work.  What holds for
+every library of the package -- header, exports and binding agree, version, loaded once, gfx950 only, the ISA lint, no other library's
+names -- tests/test_libraries_cpu.py asserts for this one too."""
 import ctypes
-import importlib.util
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -141,31 +141,15 @@ def test_the_older_entry_points_still_refuse_the_name(monkeypatch, name):
             call()
 
 
-# ---- the library -------------------------------------------------------------------------------------------------------------------------
-def code(path):
-    return re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-
-
-def test_header_library_and_binding_agree():
+# ---- the library: what is libhsefr_shift.so's own (what every library shares is asserted for it in tests/test_libraries_cpu.py) ---------
+def test_the_arguments_limits_bound_and_info_words_are_the_headers():
     from hse_facerec_tf_amd import _lib, ops
-    library, = _lib.EXTENSIONS
-    assert (library.tag, library.file, library.env, library.version) == ("hsefr_shift", "libhsefr_shift.so", "HSEFR_SHIFT_LIB", 100)
-    assert sorted(set(re.findall(r"\b(hsefr_shift_[a-z0-9_]+)\s*\(", code(HEADER)))) == NAMES
-    assert sorted(_lib.SHIFT_SIGNATURES) == NAMES and library.signatures is _lib.SHIFT_SIGNATURES
-    out = subprocess.run(["nm", "-D", "--defined-only", library.path], capture_output=True, text=True, check=True).stdout
-    symbols = [l.split() for l in out.splitlines()]
-    assert sorted(s[-1] for s in symbols if s[-2] == "T" and not s[-1].startswith(("_init", "_fini"))) == NAMES
-    assert not [s[-1] for s in symbols if s[-2] == "W"]
-    for name in ("hsefr_shift_fit", "hsefr_shift_assign", "hsefr_shift_workspace_bytes"):
-        args = re.search(r"\b%s\((.*?)\);" % name, code(HEADER), flags=re.S).group(1)
-        assert len(args.split(",")) == len(_lib.SHIFT_SIGNATURES[name][1]) == {"hsefr_shift_fit": 13, "hsefr_shift_assign": 8}.get(name, 2)
-    L = library.load()
+    assert sorted(_lib.SHIFT_SIGNATURES) == NAMES
     header = open(HEADER).read()
-    assert L.hsefr_shift_version() == int(re.search(r"#define HSEFR_SHIFT_VERSION (\d+)", header).group(1)) == 100
-    assert library.load() is L and _lib.shift_lib() is L                               # loaded once
-    assert (_lib.SHIFT_LIB_PATH, _lib.shift_lib, _lib.shift_last_error, _lib.shift_check) == \
-        (library.path, library.load, library.last_error, library.check)
-    assert isinstance(_lib.shift_last_error(), str)
+    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    for name in ("hsefr_shift_fit", "hsefr_shift_assign", "hsefr_shift_workspace_bytes"):
+        args = re.search(r"\b%s\((.*?)\);" % name, code, flags=re.S).group(1)
+        assert len(args.split(",")) == len(_lib.SHIFT_SIGNATURES[name][1]) == {"hsefr_shift_fit": 13, "hsefr_shift_assign": 8}.get(name, 2)
     for macro, value in (("MAX_N", ops.SHIFT_MAX_N), ("MAX_D", ops.SHIFT_MAX_D), ("D_MULTIPLE", ops.SHIFT_D_MULTIPLE),
                          ("MAX_ITER", ops.SHIFT_MAX_ITER)):
         assert int(re.search(r"#define HSEFR_SHIFT_%s (\d+)" % macro, header).group(1)) == value
@@ -173,56 +157,15 @@ def test_header_library_and_binding_agree():
     plus = int(re.search(r"#define HSEFR_SHIFT_DIST2_ULPS\(d\) \(\(d\) \+ (\d+)\)", header).group(1))
     assert plus == ops.SHIFT_DIST2_ULPS_PLUS
     assert ops.mean_shift_distance_bound(256, 0.7) == (256 + plus) * 2.0 ** -53 * (4 + 0.49) / 0.7 < 2e-13
-    words = re.search(r"enum \{(.*?)\};", code(HEADER), flags=re.S).group(1)
+    words = re.search(r"enum \{(.*?)\};", code, flags=re.S).group(1)
     assert [int(v) for v in re.findall(r"HSEFR_SHIFT_INFO_[A-Z_]+ = (\d+)", words)] == [0, 1, 2, 3, 4, 5, 6, 8] and len(ops.SHIFT_INFO) == 8
 
 
-def test_the_registry_of_eight_does_not_know_the_extension():
-    from hse_facerec_tf_amd import _lib
-    assert len(_lib.LIBRARIES) == 8 and len(_lib.EXTENSIONS) == 1 and _lib.EXTENSIONS[0] not in _lib.LIBRARIES
-    for library in _lib.LIBRARIES:
-        assert "hsefr_shift" not in open(os.path.join(ROOT, "include", library.tag + ".h")).read()
-        assert not [n for n in list(library.signatures) + list(library.optional) if n.startswith("hsefr_shift")]
-    with pytest.raises(ValueError, match=r"why \(hsefr_shift status -1\)"):
-        _lib.Library.check(type("L", (), {"last_error": lambda self: "why", "tag": "hsefr_shift"})(), -1)
-
-
-def test_code_object_targets_gfx950_only():
-    from hse_facerec_tf_amd import _lib
-    blob = open(_lib.SHIFT_LIB_PATH, "rb").read()
-    assert b"gfx950" in blob
-    for other in (b"gfx942", b"gfx90a", b"sm_90", b"gfx1100"):
-        assert other not in blob
-
-
-def test_device_code_passes_the_isa_lint():
-    from hse_facerec_tf_amd import _lib
-    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump"):
-        pytest.skip("no llvm-objdump on this machine")
-    spec = importlib.util.spec_from_file_location("isa_lint", os.path.join(ROOT, "tools", "isa_lint.py"))
-    lint = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(lint)
-    findings, n_symbols, n_stores = lint.lint(_lib.SHIFT_LIB_PATH)
-    assert n_symbols >= KERNELS, "the lint did not see the kernels"
-    assert n_stores >= 3, "the lint did not see the 16-byte stores of the three row copies"
-    assert findings == []
-
-
-def listed(flag):
-    out = subprocess.run(["bash", build_table.BUILD_SH, flag], capture_output=True, text=True, check=True,
-                         env={k: v for k, v in os.environ.items() if k not in ("HSEFR_DEV", "HSEFR_ASAN", "HSEFR_EXTRA_FLAGS")}).stdout
-    return [dict(field.split("=", 1) for field in line.split("\t")) for line in out.splitlines()]
-
-
-def test_the_build_script_lists_the_extension_beside_the_eight():
-    assert len(listed("--list")) == 8 == len(build_table.rows()) and "shift" not in build_table.rows()
-    row, = listed("--list-extensions")
-    assert (row["name"], row["out"], row["srcs"], row["keep"], row["lint"]) == ("shift", "../libhsefr_shift.so", "mean_shift.hip", "_ZN*_kernel*", "1")
-    deps = row["deps"].split()
-    assert "../../include/hsefr_shift.h" in deps and "../../include/hsefr.h" in deps and "build.sh" in deps and "common.h" in deps
-    assert row["flags"].split() == build_table.rows()["frames"]["flags"]               # $COMMON, the flags of the other later libraries
-    script = open(build_table.BUILD_SH).read()
-    assert script.count("isa_lint.py \"") == 1 and script.count("\nEXT_LIBS=(\n") == 1
+def test_the_librarys_row_of_the_build_table():
+    row = build_table.rows()["shift"]
+    assert (row["out"], row["srcs"]) == ("../libhsefr_shift.so", ["mean_shift.hip"])
+    assert build_table.stale_against("shift", "common.h", "include/hsefr.h", "include/hsefr_shift.h")
+    assert row["flags"] == build_table.rows()["frames"]["flags"]                       # $COMMON, the flags of the other later libraries
 
 
 def test_the_source_keeps_its_promises():

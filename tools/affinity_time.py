@@ -13,8 +13,8 @@ the synthetic unit-norm features of tools/mean_shift_time.py at 328 x 256, 2048 
 
 With --alternative LIB every size is also run on another build of the library (HSEFR_AFFINITY_LIB), for the schedule that lost: the
 same kernel with the row's similarities read again in sweep 2 instead of kept in LDS, built beside the product with
-    hipcc $(bash hse_facerec_tf_amd/csrc/build.sh --list-addons | tr '\t' '\n' | sed -n 's/^flags=//p') -DHSEFR_AFFINITY_ROW_IN_LDS=0 \
-          -shared hse_facerec_tf_amd/csrc/affinity.hip -o LIB
+    hipcc $(bash hse_facerec_tf_amd/csrc/build.sh --list | grep '^name=affinity' | tr '\t' '\n' | sed -n 's/^flags=//p') \
+          -DHSEFR_AFFINITY_ROW_IN_LDS=0 -shared hse_facerec_tf_amd/csrc/affinity.hip -o LIB
 
 Each size runs in a child process of its own under `timeout -k 10`; a section that fails or runs out of time ends the run.
 usage: python tools/affinity_time.py [--out FILE] [--limit SECONDS_PER_SECTION] [--host-limit SECONDS] [--alternative LIB]"""
