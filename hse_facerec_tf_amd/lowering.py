@@ -7,6 +7,8 @@ per image, the graph is pattern-matched ONCE into fused layers
     Conv2D(3x3x3)  + Add                 + Relu/Minimum/Maximum  -> CONV_C3   (+shift +ReLU6)
     DepthwiseConv  + Mul + Add           + Relu/Minimum/Maximum  -> DWCONV3X3 (+scale +shift +ReLU6)
     Conv2D(1x1)    + Add                 + Relu/Minimum/Maximum  -> PWCONV    (+shift +ReLU6)
+    Conv2D(1x1)    + FusedBatchNorm      + Add(shortcut)          -> CONV_F32  (+scale +shift +residual: MobileNetV2's projection)
+    Pad            + VALID 3x3 Conv2D / DepthwiseConv             -> the convolution's own pads (Keras's ZeroPadding2D)
     Mean[1,2] (+Reshape)                                           -> GAP
     MatMul + BiasAdd (+Relu | Sigmoid)                             -> DENSE
     Softmax                                                        -> SOFTMAX
@@ -453,6 +455,8 @@ class _Lowerer:
         self.where: Dict[str, int] = {}      # node name -> layer index whose (possibly open) output it is
         self.ver: Dict[str, int] = {}        # node name -> layer version at which it was that output
         self.in_c = 3
+        self.pending_pad: Dict[str, Tuple[int, int, int, int]] = {}   # Pad node -> (top, bottom, left, right), for its consumer to fold
+        self.pad_taken = set()               # (consumer node, Pad node) pairs that did
 
     # ---- constant folding ---------------------------------------------------------------
     def const_of(self, node: GraphNode) -> Optional[np.ndarray]:
@@ -593,13 +597,37 @@ class _Lowerer:
     def shape_of(self, idx: int) -> Tuple[int, int, int]:
         return (self.in_hw[0], self.in_hw[1], self.in_c) if idx < 0 else self.layers[idx].out_shape
 
+    def take_pad(self, node: GraphNode, src_node: GraphNode) -> Optional[Tuple[int, int, int, int]]:
+        """(top, bottom, left, right) of the Pad `src_node` in front of `node`, which folds it into its own geometry; None when
+        `src_node` is no Pad.  lower_node() refuses every Pad whose consumer did not come here for it."""
+        epad = self.pending_pad.get(src_node.name)
+        if epad is not None:
+            self.pad_taken.add((node.name, src_node.name))
+        return epad
+
     def lower_node(self, node: GraphNode) -> int:
         """Returns the layer index whose output equals this node's output (-1 = graph input)."""
         if node.name in self.where:
             return self.where[node.name]
         idx = self._lower_node(node)
         self.ver[node.name] = self.layers[idx].version if idx >= 0 else 0
+        if node.op != "Merge":
+            for m, _ in self.g.data_inputs(node):      # a Pad is honoured or refused, never dropped
+                if m.name in self.pending_pad and (node.name, m.name) not in self.pad_taken:
+                    raise LoweringError("%s: Pad %s in front of a %s, which cannot take it" % (node.name, m.name, node.op))
         return idx
+
+    @staticmethod
+    def padded_geometry(name: str, epad, h: int, wd: int, kh: int, kw: int, stride: int, padding: str, max_pad: int) -> Tuple[int, int, int, int]:
+        """(oh, ow, pad_t, pad_l) of a VALID convolution behind an explicit Pad: the kernels read rows and columns beyond the map as
+        zero, so the top / left pads and the output size say it all.  max_pad: the largest top / left pad the consumer's kernels take."""
+        if padding != "VALID":
+            raise LoweringError("%s: Pad followed by a %s convolution" % (name, padding))
+        pt, pb, pl, pr = epad
+        oh, ow = (h + pt + pb - kh) // stride + 1, (wd + pl + pr - kw) // stride + 1
+        if pt > max_pad or pl > max_pad or oh < 1 or ow < 1 or (oh - 1) * stride - pt >= h or (ow - 1) * stride - pl >= wd:
+            raise LoweringError("%s: pads %r on a %dx%d map are more than its %dx%d / %d kernel takes" % (name, epad, h, wd, kh, kw, stride))
+        return oh, ow, pt, pl
 
     def _lower_node(self, node: GraphNode) -> int:
         g = self.g
@@ -624,8 +652,7 @@ class _Lowerer:
             if pads.shape[0] != 4 or pads[0].any() or pads[3].any():
                 raise LoweringError("%s: padding of batch/channel axes" % node.name)
             r = self.lower_node(acts[0][0])
-            self.where[node.name] = r
-            self.pending_pad = getattr(self, "pending_pad", {})
+            self.where[node.name] = r      # (listed under its producer, as Plan.tensor_layer always had it; lower_graph refuses it as an OUTPUT)
             self.pending_pad[node.name] = (int(pads[1][0]), int(pads[1][1]), int(pads[2][0]), int(pads[2][1]))
             return r
         if op in ("MaxPool", "AvgPool") and self.general:
@@ -633,7 +660,7 @@ class _Lowerer:
             src = self.finished(self.lower_node(src_node))
             h, wd, c = self.shape_of(src)
             k, st = node.attr_ints("ksize"), node.attr_ints("strides")
-            epad = getattr(self, "pending_pad", {}).get(src_node.name)
+            epad = self.take_pad(node, src_node)
             if op == "AvgPool":
                 if (k[1], k[2]) != (h, wd) or node.attr_s("padding") != "VALID" or epad:
                     raise LoweringError("%s: only a global VALID AvgPool is supported" % node.name)
@@ -663,7 +690,7 @@ class _Lowerer:
             kh, kw, cout = int(w.shape[0]), int(w.shape[1]), int(w.shape[3])
             if s[1] != s[2] or w.shape[2] != c:
                 raise LoweringError("%s: strides %r / kernel %r on %d channels" % (node.name, s, w.shape, c))
-            epad = getattr(self, "pending_pad", {}).get(src_node.name)
+            epad = self.take_pad(node, src_node)
             if epad:
                 if node.attr_s("padding") != "VALID":
                     raise LoweringError("%s: Pad followed by a %s convolution" % (node.name, node.attr_s("padding")))
@@ -686,16 +713,20 @@ class _Lowerer:
                 raise LoweringError("%s: no bf16 kernel for Conv2D k=%r stride %d pads (%d,%d)" % (node.name, w.shape, s[1], pt, pl))
             return self.new_layer(Layer(kind, node.name, src, (h, wd, c), (oh, ow, cout), w=w, kh=kh, kw=kw, stride=s[1],
                                         pad_t=pt, pad_l=pl), node)
-        if op in ("Add", "AddV2") and self.general and len(acts) == 2:
-            # residual sum: folded into the epilogue of whichever branch ends in an open conv layer
+        if op in ("Add", "AddV2") and len(acts) == 2:
+            # residual sum: folded into the epilogue of whichever branch ends in an open conv layer.  In the MobileNet mode that is the
+            # linear 1x1 projection of an inverted residual block: it becomes a general fp32 convolution, whose epilogue has the residual
+            takes_res = (OP_CONV_BF16, OP_CONV_F32) if self.general else (OP_PWCONV_F32, OP_CONV_F32)
             ia, ib = self.lower_node(acts[0][0]), self.lower_node(acts[1][0])
             for (i_main, n_main, i_res) in ((ia, acts[0][0], ib), (ib, acts[1][0], ia)):
                 L = self.layers[i_main] if i_main >= 0 else None
-                if (L is not None and L.kind in (OP_CONV_BF16, OP_CONV_F32) and not L.sealed and L.act == ACT_NONE and L.res < 0 and
-                        self.live_consumers(n_main.name) == 1 and i_res >= 0 and i_res != i_main):
+                if (L is not None and L.kind in takes_res and not L.sealed and L.act == ACT_NONE and L.res < 0 and
+                        self.live_consumers(n_main.name) == 1 and i_res >= 0 and i_res != i_main and
+                        tuple(self.layers[i_res].out_shape) == tuple(L.out_shape)):
                     self.finished(i_res)
                     if i_res > i_main:      # the shortcut branch was lowered after this conv: run the conv last
                         i_main, i_res = self._move_to_end(i_main), i_res - 1
+                    L.kind = OP_CONV_F32 if L.kind == OP_PWCONV_F32 else L.kind
                     L.res = i_res
                     L.version += 1
                     self.where[node.name] = i_main
@@ -704,7 +735,8 @@ class _Lowerer:
         if op in ("Conv2D", "DepthwiseConv2dNative"):
             if node.attr_s("data_format", "NHWC") != "NHWC":
                 raise LoweringError("%s: only NHWC graphs are supported" % node.name)
-            src = self.finished(self.lower_node(acts[0][0]))
+            src_node = acts[0][0]
+            src = self.finished(self.lower_node(src_node))
             w = consts[0].astype(np.float32)
             h, wd, c = self.shape_of(src)
             s = node.attr_ints("strides")
@@ -714,7 +746,15 @@ class _Lowerer:
                 raise LoweringError("%s: dilated convolution" % node.name)
             kh, kw = int(w.shape[0]), int(w.shape[1])
             pad = node.attr_s("padding")
-            if pad == "SAME":
+            epad = self.take_pad(node, src_node)
+            if epad:
+                # Keras writes its stride-2 3x3 layers as ZeroPadding2D + VALID.  csrc/dwconv.hip and csrc/conv_first.hip clamp every
+                # address and mask taps above, below and right of the map; their LEFT mask assumes the window's third column is not
+                # left of the map: top / left pads of at most 2
+                if (kh, kw) != (3, 3):
+                    raise LoweringError("%s: Pad in front of a %dx%d convolution of the MobileNet mode" % (node.name, kh, kw))
+                oh, ow, pt, pl = self.padded_geometry(node.name, epad, h, wd, 3, 3, s[1], pad, 2)
+            elif pad == "SAME":
                 oh, pt = tf_same_padding(h, kh, s[1])
                 ow, pl = tf_same_padding(wd, kw, s[1])
             elif pad == "VALID":
@@ -732,6 +772,8 @@ class _Lowerer:
                     raise LoweringError("%s: kernel %r does not match %d input channels" % (node.name, w.shape, c))
                 if (kh, kw) == (1, 1) and s[1] == 1 and c % 32 == 0 and cout % 64 == 0:
                     kind = OP_PWCONV_F32
+                elif (kh, kw) == (1, 1) and s[1] == 1 and c % 8 == 0 and cout % 8 == 0:
+                    kind = OP_CONV_F32        # a width the pointwise GEMMs do not take: the general kernel, unless pad_channels() widens it
                 elif c == 3 and (kh, kw) == (3, 3) and cout % 4 == 0:
                     kind = OP_CONV_C3
                 else:
@@ -917,10 +959,18 @@ def rebuild(layers: List[Layer], drop, put: Dict[int, Layer]) -> Tuple[List[Laye
     return new_layers, remap
 
 
+def same_geometry(L: Layer) -> bool:
+    """The layer's pads and output size are TensorFlow SAME's.  The fused kernels a 3x3 layer can be merged into were written for
+    SAME graphs and tile their maps by that geometry, so every pass that merges one asks first; an explicit Pad + VALID layer
+    with other pads stays a layer of its own (Keras's correct_pad IS this geometry, on even and on odd maps)."""
+    return (tf_same_padding(L.in_shape[0], L.kh, L.stride) == (L.out_shape[0], L.pad_t) and
+            tf_same_padding(L.in_shape[1], L.kw, L.stride) == (L.out_shape[1], L.pad_l))
+
+
 def dwpw_fusable(dw: Layer, pw: Layer) -> bool:
     """Shapes libhsefr's fused depthwise->pointwise kernel covers (csrc/dwpw_fused.hip)."""
     return (dw.kind == OP_DWCONV3X3 and pw.kind == OP_PWCONV_F32 and dw.act == ACT_RELU6 and pw.act == ACT_RELU6 and
-            dw.in_shape[2] in (32, 64) and pw.out_shape[2] in (64, 128) and dw.stride in (1, 2))
+            dw.in_shape[2] in (32, 64) and pw.out_shape[2] in (64, 128) and dw.stride in (1, 2) and same_geometry(dw))
 
 
 def fuse_dwpw(layers: List[Layer], keep: Sequence[int]) -> Tuple[List[Layer], Dict[int, int]]:
@@ -1124,7 +1174,7 @@ def fuse_stem(layers: List[Layer], keep: Sequence[int]) -> Tuple[List[Layer], Di
                 L.out_shape[2] == 32 and L.stride == 2 and L.kh == 3 and L.kw == 3 and L.act == ACT_RELU6):
             continue
         B = layers[b]
-        if not (B.kind == OP_DWPW_F32 and B.stride == 1 and B.in_shape[2] == 32 and B.out_shape[2] == 64):
+        if not (B.kind == OP_DWPW_F32 and B.stride == 1 and B.in_shape[2] == 32 and B.out_shape[2] == 64 and same_geometry(L) and same_geometry(B)):
             continue
         S = Layer(OP_STEM_F16S, B.name, -1, L.in_shape, B.out_shape, w=B.w, scale=B.scale, shift=B.shift, act=B.act, kh=3, kw=3,
                   stride=2, pad_t=L.pad_t, pad_l=L.pad_l, sealed=True, w2=B.w2, shift2=B.shift2, a_log2=F16S_ACT_LOG2_RELU6,
@@ -1154,6 +1204,8 @@ def fuse_stem2(layers: List[Layer], keep: Sequence[int]) -> Tuple[List[Layer], D
                           layers[i3].act in (ACT_NONE, ACT_RELU, ACT_RELU6)):
             continue
         L1, L2, L3 = layers[i1], layers[i2], layers[i3]
+        if not (same_geometry(L0) and same_geometry(L1) and same_geometry(L3)):
+            continue
         S = Layer(OP_STEM2_F16S, L3.name, -1, L0.in_shape, L3.out_shape, w=L1.w, scale=L1.scale, shift=L1.shift, act=L3.act, kh=3, kw=3,
                   stride=2, pad_t=L0.pad_t, pad_l=L0.pad_l, sealed=True, w2=L2.w, shift2=L2.shift, a_log2=F16S_ACT_LOG2_RELU6,
                   w0=L0.w, shift0=L0.shift, w3=L3.w, scale3=L3.scale, shift3=L3.shift, pad3=(L3.pad_t, L3.pad_l))
@@ -1173,7 +1225,7 @@ def block_f16s_fusable(dw: Layer, pw: Layer, which: str) -> bool:
     """Blocks csrc/dwpw_f16s.hip covers: depthwise 3x3 + ReLU6 feeding ONLY a split-f16 pointwise layer."""
     c, cout = dw.in_shape[2], pw.out_shape[2]
     if not (dw.kind == OP_DWCONV3X3 and pw.kind == OP_PWCONV_F32 and pw.a_log2 > 0 and dw.act == ACT_RELU6 and
-            pw.act in (ACT_NONE, ACT_RELU, ACT_RELU6) and dw.stride in (1, 2) and c % 32 == 0 and cout % 64 == 0):
+            pw.act in (ACT_NONE, ACT_RELU, ACT_RELU6) and dw.stride in (1, 2) and c % 32 == 0 and cout % 64 == 0 and same_geometry(dw)):
         return False
     return which == "all" or (dw.stride == 1 and (c, cout) in BLOCK_F16S_AUTO)
 
@@ -1213,7 +1265,7 @@ def mark_dwpw_pairs(layers: List[Layer], keep: Sequence[int]) -> int:
             continue
         pw = layers[j]
         if (pw.kind == OP_PWCONV_F32 and 0 < pw.a_log2 <= 12 and not pw.in_split and pw.flags == 0 and pw.res < 0 and
-                tuple(pw.in_shape) == tuple(dw.out_shape) and dwpw_pair_covered(dw, pw)):
+                tuple(pw.in_shape) == tuple(dw.out_shape) and dwpw_pair_covered(dw, pw) and same_geometry(dw)):
             dw.flags |= OPF_DWPW_NEXT
             n += 1
     return n
@@ -1245,6 +1297,91 @@ def mark_pw_blocks(layers: List[Layer], keep: Sequence[int]) -> int:
             pw.flags |= OPF_PWBLK_NEXT
             n += 1
     return n
+
+
+# THE rule of pad_channels(): a tensor whose width the pointwise GEMMs do not take is widened with zero channels when the padded
+# width is at most this many times the real one; above it, the 1x1 layers around it stay on the general kernel (OP_CONV_F32).
+# Measured on MI355X at batch 256 (profiles/mobilenetv2_time.txt; DESIGN.md, "MobileNetV2"): MobileNetV2 alpha 1.0 at 192 takes 3.75 / 4.05 /
+# 5.75 / 6.14 / 7.74 ms with a bound of 4 / 3 / 2 / 1.5 / no padding -- every class sent to the general kernel costs more than its padding,
+# the 16 -> 64 one included -- so the bound is the widest ratio those graphs have (a width of 8 would be padded 8 x: not measured, it stays on the general kernel).
+CHANNEL_PAD_MAX_RATIO = 4.0
+
+
+def _is_1x1(L: Layer) -> bool:
+    return L.kind in (OP_PWCONV_F32, OP_CONV_F32) and (L.kh, L.kw, L.stride, L.pad_t, L.pad_l) == (1, 1, 1, 0, 0)
+
+
+def pad_channels(layers: List[Layer], keep: Sequence[int], max_ratio: float = CHANNEL_PAD_MAX_RATIO) -> Dict[int, int]:
+    """MobileNet mode, on the layer list as lowered (before the post-conditions): widen tensors to the multiples the pointwise
+    GEMMs take -- 64 output channels (csrc/pwconv_f32.hip, pwconv_f16s.hip, conv_f32_mfma.hip), 32 input channels -- with channels
+    that are exactly zero.  Tensors that must agree on a width form one class: a depthwise layer's input and output, a residual sum's
+    operands and result.  A class is widened from C to P channels by zero columns in its producers' kernels, scales and shifts
+    (act(0 * x + 0) = 0; a residual adds 0 + 0), zero depthwise kernels, scales and shifts, and zero rows in its 1x1 consumers'
+    kernels: every sum keeps its value.  A class stays as it is when a requested output, the network input or a layer of another
+    kind (pool, dense) belongs to it -- a requested output is never a padded tensor -- when it needs nothing, or when
+    P > max_ratio * C (CHANNEL_PAD_MAX_RATIO); its 1x1 layers then stay OP_CONV_F32.  Afterwards every 1x1 OP_CONV_F32 layer without
+    a residual whose widths the GEMMs take becomes OP_PWCONV_F32, so choose_pointwise_math() can give it split-f16 products.
+    Returns {layer index: real output width} of the widened tensors."""
+    parent = list(range(len(layers)))
+
+    def find(i: int) -> int:
+        while parent[i] != i:
+            parent[i] = parent[parent[i]]
+            i = parent[i]
+        return i
+
+    fixed = set(keep)                   # tensors that keep their width
+    for i, L in enumerate(layers):
+        if L.kind == OP_DWCONV3X3:
+            if L.src < 0:
+                fixed.add(i)
+            else:
+                parent[find(i)] = find(L.src)
+        elif not (_is_1x1(L) or L.kind == OP_CONV_C3):
+            fixed.add(i)                # another kind produces it ...
+            if L.src >= 0:
+                fixed.add(L.src)        # ... or reads it
+        if L.res >= 0:
+            parent[find(i)] = find(L.res)
+    need: Dict[int, int] = {}
+    for i, L in enumerate(layers):
+        if _is_1x1(L):
+            need[find(i)] = 64
+    for L in layers:
+        if _is_1x1(L) and L.src >= 0:
+            need.setdefault(find(L.src), 32)
+    blocked = {find(i) for i in fixed}
+    real: Dict[int, int] = {}
+    width: Dict[int, int] = {}
+    for i, L in enumerate(layers):
+        r = find(i)
+        c = L.out_shape[2]
+        p = -(-c // need.get(r, 1)) * need.get(r, 1)
+        if r not in blocked and c < p <= max_ratio * c:
+            real[i], width[i] = c, p
+
+    def widen(a: Optional[np.ndarray], axis: int, p: int) -> Optional[np.ndarray]:
+        if a is None:
+            return None
+        pads = [(0, 0)] * a.ndim
+        pads[axis] = (0, p - a.shape[axis])
+        return np.pad(a, pads)
+
+    for i, L in enumerate(layers):
+        if L.src in width:              # reads a widened tensor
+            p = width[L.src]
+            if L.kind != OP_DWCONV3X3:
+                L.w = widen(L.w, 2, p)
+            L.in_shape = (L.in_shape[0], L.in_shape[1], p)
+        if i in width:                  # produces one
+            p = width[i]
+            L.w = widen(L.w, 2 if L.kind == OP_DWCONV3X3 else 3, p)
+            L.scale, L.shift = widen(L.scale, 0, p), widen(L.shift, 0, p)
+            L.out_shape = (L.out_shape[0], L.out_shape[1], p)
+    for L in layers:
+        if L.kind == OP_CONV_F32 and _is_1x1(L) and L.res < 0 and L.in_shape[2] % 32 == 0 and L.out_shape[2] % 64 == 0:
+            L.kind = OP_PWCONV_F32
+    return real
 
 
 def choose_pointwise_math(layers: List[Layer], pw_math: str) -> None:
@@ -1345,7 +1482,7 @@ def lower_graph(g: Graph, input_tensor: str, outputs: Dict[int, str], input_hw: 
                 pw_math: Optional[str] = None, fuse_stem_block: Optional[bool] = None, stem_fusion: Optional[str] = None,
                 block_fusion: Optional[str] = None, presplit: Optional[str] = None, input_bound: Optional[float] = None,
                 pwdw_fusion: Optional[str] = None, u8_mean_bgr: Optional[Sequence[float]] = None, launch_fusion: bool = True,
-                s2_fusion: Optional[str] = None, pw_block_fusion: Optional[str] = None) -> Plan:
+                s2_fusion: Optional[str] = None, pw_block_fusion: Optional[str] = None, channel_padding: Optional[object] = None) -> Plan:
     """outputs: {slot: 'tensor:0'}.  feeds: constant feeds such as the Keras learning phase.
     fuse: merge depthwise -> pointwise pairs into one kernel where a fused kernel covers the shape.  stem_fusion:
     'stem2' (default) = conv1 + block 1 + the depthwise of block 2 in one
@@ -1376,6 +1513,10 @@ def lower_graph(g: Graph, input_tensor: str, outputs: Dict[int, str], input_hw: 
     pw_block_fusion: 'auto' (default) = a split-f16 pointwise layer whose only reader is a stride-1 fused block of a covered shape
     (64 -> 128 -> 128 channels on rows of at most 48 pixels: conv_pw_2 -> conv_dw_3 + conv_pw_3 at 192 x 192) runs with it as one
     row-streaming launch (mark_pw_blocks; the layer list does not change); 'none' = two launches.
+    channel_padding (dtype 'f32'): 'auto' (default) = tensors whose width the pointwise GEMMs do not take (MobileNetV2's 16, 24, 96,
+    144 ...) are widened with zero channels where CHANNEL_PAD_MAX_RATIO allows (pad_channels); 'none' = every 1x1 layer of such a
+    width runs on the general fp32 kernel (OP_CONV_F32) at its own width; a number >= 1 = 'auto' with that bound in place of
+    CHANNEL_PAD_MAX_RATIO (what tools/bench_configs.py mobilenetv2 sweeps to set the constant).
     dtype 'f32': the MobileNet kernels (exact fp32); 'bf16': ResNet-style graphs on the bf16-MFMA kernels
     (general KxK Conv2D, Pad, FusedBatchNorm / Mul+Add, residual Add, MaxPool 3x3/2, global AvgPool / Mean); 'f32g': the
     same ResNet-style graph patterns on exact-fp32 kernels (OP_CONV_F32 / OP_MAXPOOL_F32 / OP_GAP) -- the fp32-grade mode
@@ -1401,8 +1542,21 @@ def lower_graph(g: Graph, input_tensor: str, outputs: Dict[int, str], input_hw: 
         li = low.lower_node(node)
         if li < 0:
             raise LoweringError("output %s is the graph input" % tname)
+        if node.name in low.pending_pad:      # (the plan holds the tensor in front of the Pad: handing that out would drop the Pad)
+            raise LoweringError("output %s is a Pad's own tensor, which no layer materialises; fetch its input or its consumer" % tname)
         out_layers[slot] = (li, int(np.prod(low.layers[li].out_shape)))
     layers = low.layers
+    for name in low.pending_pad:
+        if name not in {p for _, p in low.pad_taken}:
+            raise LoweringError("%s: a Pad that no convolution or pool consumes" % name)
+    channel_padding = "auto" if channel_padding is None else channel_padding
+    pad_bound = CHANNEL_PAD_MAX_RATIO
+    if isinstance(channel_padding, (int, float)) and not isinstance(channel_padding, bool) and channel_padding >= 1:
+        channel_padding, pad_bound = "auto", float(channel_padding)
+    if channel_padding not in ("auto", "none"):
+        raise ValueError("channel_padding must be 'auto', 'none' or a bound >= 1, not %r" % (channel_padding,))
+    if dtype == "f32" and channel_padding == "auto":
+        pad_channels(layers, [li for li, _ in out_layers.values()], pad_bound)
 
     # post-conditions every kernel relies on
     for L in layers:

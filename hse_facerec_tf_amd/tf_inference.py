@@ -431,6 +431,13 @@ def get_tf_face_recognizer(model: str = "age_gender", models_dir: Optional[str] 
         kw.setdefault("input_size", (192, 192))
         return TensorFlowInference(os.path.join(d, 'vgg2_mobilenet.h5'), input_tensor='input_1:0', output_tensor='reshape_1/Reshape:0',
                                    convert2BGR=True, imageNetUtilsMean=True, **kw)
+    # MobileNetV2 (keras_applications, include_top=False, pooling='avg'): x / 127.5 - 1 on RGB, no learning-phase feed
+    if model == "mobilenet2":            # facerec_test.py:216 (alpha 1.0 at 192 x 192)
+        return TensorFlowInference(os.path.join(d, 'mobilenet2_alpha=1_192_augm_ft_sgd.pb'), input_tensor='input_1:0',
+                                   output_tensor='global_average_pooling2d_1/Mean:0', convert2BGR=False, **kw)
+    if model == "vgg2_mobilenet2":       # facerec_test.py:217 (224 x 224)
+        return TensorFlowInference(os.path.join(d, 'vgg2_mobilenet2_224-08-0.87.pb'), input_tensor='input_1:0',
+                                   output_tensor='reshape_1/Mean:0', convert2BGR=False, **kw)
     if model == "vgg2_resnet":           # facerec_test.py:213
         return TensorFlowInference(os.path.join(d, 'vgg2_resnet.pb'), input_tensor='input:0',
                                    output_tensor='pool5_7x7_s1:0', convert2BGR=True, imageNetUtilsMean=False, **kw)
