@@ -241,6 +241,17 @@ def _use_mixed_device(img_processing, mixed_device: Optional[bool], use_mixed_si
                 and getattr(detector, "detect_packed", None) is not None and getattr(detector, "device_boxes", False))
 
 
+def _device_switches(img_processing, device_crops, device_frames, mixed_sizes, mixed_device):
+    """The device switches of both loops, each decided by its _use_* rule -> (device_crops, device_frames, mixed): ``mixed`` holds
+    process_images' ``mixed_sizes`` and ``mixed_device`` keywords, each present only when it is in use."""
+    use_device = _use_device_crops(img_processing, device_crops)
+    use_frames = _use_device_frames(img_processing, device_frames, use_device)
+    mixed = dict(mixed_sizes=True) if _use_mixed_sizes(img_processing, mixed_sizes) else {}
+    if _use_mixed_device(img_processing, mixed_device, bool(mixed), use_device, use_frames):
+        mixed["mixed_device"] = True
+    return use_device, use_frames, mixed
+
+
 def _normalized_on_device(features: Sequence[np.ndarray], device):
     """[n, d] raw features -> their L2-normalised rows as a CUDA tensor (ops.l2_normalize); they stay there for the clustering."""
     from . import ops
@@ -268,11 +279,7 @@ def process_video(img_processing, frames: Iterable[np.ndarray], mdate, rotation:
     (perform_clustering(split="device")); passed on only when it is in use, too."""
     rotation = preprocess_device.check_rotation(rotation)
     video_year = _fractional_year(mdate)
-    use_device = _use_device_crops(img_processing, device_crops)
-    use_frames = _use_device_frames(img_processing, device_frames, use_device)
-    mixed = dict(mixed_sizes=True) if _use_mixed_sizes(img_processing, mixed_sizes) else {}
-    if _use_mixed_device(img_processing, mixed_device, bool(mixed), use_device, use_frames):
-        mixed["mixed_device"] = True
+    use_device, use_frames, mixed = _device_switches(img_processing, device_crops, device_frames, mixed_sizes, mixed_device)
     per_frame = {}                     # candidate frame index -> (ages, genders, features, crops)
     n_frames = 0
 
@@ -350,11 +357,7 @@ def process_album(img_processing, photos, mdates, videos=(), config: AlbumConfig
         raise ValueError("%d photos, %d dates" % (len(photos), len(mdates)))
     for video in videos:
         preprocess_device.check_rotation(video[2] if len(video) > 2 else 0)
-    use_device = _use_device_crops(img_processing, device_crops)
-    use_frames = _use_device_frames(img_processing, device_frames, use_device)
-    mixed = dict(mixed_sizes=True) if _use_mixed_sizes(img_processing, mixed_sizes) else {}
-    if _use_mixed_device(img_processing, mixed_device, bool(mixed), use_device, use_frames):
-        mixed["mixed_device"] = True
+    use_device, use_frames, mixed = _device_switches(img_processing, device_crops, device_frames, mixed_sizes, mixed_device)
     use_split = _use_device_split(device_split)       # decided once, for the album's clusters and for its videos'
     # a video gets the decision itself; the keyword is left out only where it is off and off is what process_video would choose anyway
     video_split = dict(device_split=use_split) if use_split or SPLIT_DEVICE_DEFAULT else {}

@@ -110,7 +110,7 @@ class FacialImageProcessing:
             if self.device_preprocess and self.sess.accepts_u8:      # cv2.resize on the GPU (integer: same bits), bytes into the net
                 from . import preprocess_device
                 x8 = preprocess_device.preprocess_faces_cv(chunk, (self.h, self.w), device=self.sess.device, raw_u8=True)
-                r = self.sess.forward_u8(x8, (OUT_FEATURES, OUT_AGE, OUT_GENDER), latency=latency)
+                a, g, fea = self._forward_u8_batch(x8, latency)
             else:
                 if self.device_preprocess:  # cv2.resize + BGR + mean on the GPU
                     from . import preprocess_device
@@ -118,16 +118,21 @@ class FacialImageProcessing:
                 else:
                     x = np.stack([self.preprocess_face(f) for f in chunk])
                     xd = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(self.sess.device)
-                r = self.sess.forward(xd, (OUT_FEATURES, OUT_AGE, OUT_GENDER), latency=latency)
-            # one read-back (three small device-to-host copies are three synchronisations)
-            packed = torch.cat([r["age_probs"], r["gender"], r["features"]], dim=1).cpu().numpy()
-            na, ng = r["age_probs"].shape[1], r["gender"].shape[1]
-            age_p, gen, fea = packed[:, :na], packed[:, na:na + ng].copy(), packed[:, na + ng:].copy()
-            for j in range(len(chunk)):
-                ages.append(decode_age(age_p[j])[0])
-                genders.append(gen[j])
-                feats.append(fea[j])
+                a, g, fea = self._read_back(self.sess.forward(xd, (OUT_FEATURES, OUT_AGE, OUT_GENDER), latency=latency))
+            ages.extend(a)
+            genders.extend(g)
+            feats.extend(fea)
         return ages, genders, feats
+
+    @staticmethod
+    def _read_back(r):
+        """A forward's three outputs -> (ages, genders, features), a list entry per image: one read-back (three small device-to-host
+        copies are three synchronisations), the ages decoded."""
+        torch = _lib.require_gpu()
+        packed = torch.cat([r["age_probs"], r["gender"], r["features"]], dim=1).cpu().numpy()
+        na, ng = r["age_probs"].shape[1], r["gender"].shape[1]
+        age_p, gen, fea = packed[:, :na], packed[:, na:na + ng].copy(), packed[:, na + ng:].copy()
+        return [decode_age(p)[0] for p in age_p], list(gen), list(fea)
 
     # ---- facial_analysis.py:210-223 ---------------------------------------------------------------
     def detect_faces(self, img):
@@ -208,21 +213,16 @@ class FacialImageProcessing:
             print('age gender elapsed', time.time() - t)
         return bboxes, points if points is not None else [], ages, genders, facial_features
 
-    def _forward_u8_batch(self, x8):
+    def _forward_u8_batch(self, x8, latency: bool = False):
         """age_gender_batch's forward and read-back for resized faces that are already on the device: ``x8`` CUDA uint8 [m, h, w, 3]
-        RGB, in chunks of max_batch on the bulk plan -> (ages, genders, features)."""
-        torch = _lib.require_gpu()
+        RGB, in chunks of max_batch (on the bulk plan unless ``latency``) -> (ages, genders, features)."""
         ages, genders, feats = [], [], []
         mb = self.sess.max_batch
         for i in range(0, int(x8.shape[0]), mb):
-            r = self.sess.forward_u8(x8[i:i + mb], (OUT_FEATURES, OUT_AGE, OUT_GENDER), latency=False)
-            packed = torch.cat([r["age_probs"], r["gender"], r["features"]], dim=1).cpu().numpy()
-            na, ng = r["age_probs"].shape[1], r["gender"].shape[1]
-            age_p, gen, fea = packed[:, :na], packed[:, na:na + ng].copy(), packed[:, na + ng:].copy()
-            for j in range(packed.shape[0]):
-                ages.append(decode_age(age_p[j])[0])
-                genders.append(gen[j])
-                feats.append(fea[j])
+            a, g, fea = self._read_back(self.sess.forward_u8(x8[i:i + mb], (OUT_FEATURES, OUT_AGE, OUT_GENDER), latency=latency))
+            ages.extend(a)
+            genders.extend(g)
+            feats.extend(fea)
         return ages, genders, feats
 
     def _resized_faces(self, imgs, all_bboxes, sources):
@@ -231,9 +231,8 @@ class FacialImageProcessing:
         (preprocess_device.face_crops: one [m, 5] table uploaded, no frame and no crop uploaded again, no launch per crop size); the
         frames that took the single-frame call are cut on the host and resized by preprocess_faces_cv, as without device_crops.
         The frames of a mixed-size pass whose source is (PackedFrames, row) -- process_images(mixed_device=True) -- are cut the same
-        way from that pass's packed buffer (preprocess_device.face_crops_packed): the source's type decides."""
+        way from that pass's packed buffer: preprocess_device.face_crops_from takes either kind of source."""
         from . import preprocess_device
-        from .mtcnn_ragged import PackedFrames
         torch = _lib.require_gpu()
         counts = [len(b) for b in all_bboxes]
         starts = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
@@ -246,17 +245,13 @@ class FacialImageProcessing:
                 alone.append(i)
             else:
                 passes.setdefault(id(src[0]), (src[0], []))[1].append(i)
-        for stack, idx in passes.values():
+        for source, idx in passes.values():
             table = np.array([[sources[i][1]] + list(box) for i in idx for box in all_bboxes[i]], dtype=np.int32)
             where = np.concatenate([np.arange(starts[i], starts[i + 1]) for i in idx])
-            if isinstance(stack, PackedFrames):
-                cut = lambda out=None, p=stack: preprocess_device.face_crops_packed(p.data, p.shapes, table, (self.h, self.w), out=out)  # noqa: E731
-            else:
-                cut = lambda out=None, p=stack: preprocess_device.face_crops(p, table, (self.h, self.w), out=out)      # noqa: E731
             if where[-1] - where[0] + 1 == len(where):            # the pass's faces stand together in the batch: written in place
-                cut(x8[int(where[0]):int(where[-1]) + 1])
+                preprocess_device.face_crops_from(source, table, (self.h, self.w), out=x8[int(where[0]):int(where[-1]) + 1])
             else:
-                x8[torch.from_numpy(where).to(x8.device)] = cut()
+                x8[torch.from_numpy(where).to(x8.device)] = preprocess_device.face_crops_from(source, table, (self.h, self.w))
         if alone:
             crops = [imgs[i][y1:y2, x1:x2, :] for i in alone for (x1, y1, x2, y2) in all_bboxes[i]]
             where = np.concatenate([np.arange(starts[i], starts[i + 1]) for i in alone])
@@ -298,58 +293,56 @@ class FacialImageProcessing:
             raw.append(d)
         shapes = [(d.shape[1], d.shape[0]) if rotation else (d.shape[0], d.shape[1]) for d in raw]
         imgs, detections, sources = [None] * len(raw), [None] * len(raw), [None] * len(raw)
+        det = self.detector
 
         def alone(i, img):                         # the single-frame call, through the path a lone frame takes without device_frames
             imgs[i] = img
-            detections[i] = self.detector.detect_batch([img], max_frames=max_frames)[0]
+            detections[i] = det.detect_batch([img], max_frames=max_frames)[0]
+
+        def host_rgb(i):                           # frame i turned and converted on the host, as without device_frames
+            return self._bgr_to_rgb(preprocess_device.turn_frame(raw[i], rotation))
+
+        def run_pass(idx, host, prepare, detect, frame_of):
+            """One pass on the device.  ``host``: its frames as ONE array, as decoded; ``prepare(buf, out)``: that array on the device
+            turned and converted by one launch into ``out`` -> the pass's source; ``detect(source)``: the detector's entry for such a
+            source; ``frame_of(source, row)``: one frame of it."""
+            buf = torch.from_numpy(host).to(det.device)                    # one upload per pass, as decoded
+            source = prepare(buf, buf if rotation == 0 else None)          # in place for rotation 0: never a second buffer
+            del buf                                                        # (a quarter turn's raw buffer is released here)
+            for row, (i, res) in enumerate(zip(idx, detect(source))):
+                if res is not None:
+                    detections[i], sources[i] = res, (source, row)
+                else:                                                      # overflowed: read back from the prepared buffer and redone alone
+                    alone(i, frame_of(source, row).cpu().numpy())
         lone: list = []                            # mixed_sizes: the frames alone in their size group, in list order
         for (h, w), idx in plan_passes(shapes, max_frames):
-            if not self.detector.pyramid_scales(h, w):                     # smaller than minsize: no level, no launch, no upload
+            if not det.pyramid_scales(h, w):                               # smaller than minsize: no level, no launch, no upload
                 for i in idx:
                     detections[i] = empty_detection()
-                continue
-            if len(idx) == 1:
-                if mixed_sizes:
-                    lone.append(idx[0])
-                    if not mixed_device:
-                        imgs[idx[0]] = self._bgr_to_rgb(preprocess_device.turn_frame(raw[idx[0]], rotation))
-                else:
-                    alone(idx[0], self._bgr_to_rgb(preprocess_device.turn_frame(raw[idx[0]], rotation)))
-                continue
-            stack = torch.from_numpy(np.stack([raw[i] for i in idx])).to(self.detector.device)      # one upload per pass, as decoded
-            if rotation == 0:
-                preprocess_device.prepare_frames(stack, 0, True, out=stack)                         # in place: never a second stack
+            elif len(idx) > 1:
+                run_pass(idx, np.stack([raw[i] for i in idx]), lambda buf, out: preprocess_device.prepare_frames(buf, rotation, True, out=out),
+                         det.detect_stack, lambda stack, row: stack[row])
+            elif not mixed_sizes:
+                alone(idx[0], host_rgb(idx[0]))
             else:
-                stack = preprocess_device.prepare_frames(stack, rotation, True)                     # (the raw stack is released here)
-            for row, (i, res) in enumerate(zip(idx, self.detector.detect_stack(stack))):
-                if res is not None:
-                    detections[i], sources[i] = res, (stack, row)
-                else:
-                    alone(i, stack[row].cpu().numpy())
+                lone.append(idx[0])
+                if not mixed_device:
+                    imgs[idx[0]] = host_rgb(idx[0])
         if lone and mixed_device:
-            det = self.detector
             for hw, part in plan_mixed_passes([shapes[i] for i in lone], max_frames, minsize=det.minsize, factor=det.FACTOR):
                 idx = [lone[k] for k in part]
                 if hw is not None:                                         # a pass of one: the single-frame call, converted on the host
                     for i in idx:
-                        alone(i, self._bgr_to_rgb(preprocess_device.turn_frame(raw[i], rotation)))
+                        alone(i, host_rgb(i))
                     continue
                 det.ragged_passes += 1
                 det.ragged_frames += len(idx)
-                buf = torch.from_numpy(np.concatenate([np.ascontiguousarray(raw[i]).reshape(-1) for i in idx])).to(det.device)   # one upload per pass
-                raw_shapes = [raw[i].shape[:2] for i in idx]
-                if rotation == 0:
-                    preprocess_device.prepare_packed(buf, raw_shapes, 0, True, out=buf)                 # in place: never a second buffer
-                else:
-                    buf = preprocess_device.prepare_packed(buf, raw_shapes, rotation, True)             # (the raw buffer is released here)
-                packed = PackedFrames(buf, [shapes[i] for i in idx])
-                for row, (i, res) in enumerate(zip(idx, det.detect_packed(packed))):
-                    if res is not None:
-                        detections[i], sources[i] = res, (packed, row)
-                    else:
-                        alone(i, packed.frame(row).cpu().numpy())
+                raw_shapes, turned = [raw[i].shape[:2] for i in idx], [shapes[i] for i in idx]
+                run_pass(idx, np.concatenate([np.ascontiguousarray(raw[i]).reshape(-1) for i in idx]),
+                         lambda buf, out: PackedFrames(preprocess_device.prepare_packed(buf, raw_shapes, rotation, True, out=out), turned),
+                         det.detect_packed, PackedFrames.frame)
         elif lone:
-            for i, res in zip(lone, self.detector.detect_batch([imgs[i] for i in lone], max_frames=max_frames, mixed_sizes=True)):
+            for i, res in zip(lone, det.detect_batch([imgs[i] for i in lone], max_frames=max_frames, mixed_sizes=True)):
                 detections[i] = res
         return imgs, shapes, detections, sources
 

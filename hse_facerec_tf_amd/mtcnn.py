@@ -17,7 +17,8 @@ from ONE upload of the frame (csrc/area_resize.hip: hsefr_mtcnn_pyramid_level / 
 reference's numbers including its conventions: boxes are 1-based inclusive, ``np.fix`` truncation.
 ``device_resize=False`` keeps the round-1 path (host resizes through preprocess.resize_area).
 ``MTCNNDetector.detect_batch`` runs same-size frames through that launch sequence together (the ``*_batch`` entry points of
-include/hsefr.h), each frame's result bit for bit its single-frame result.  ``MTCNNDetector.detect_ragged`` runs frames of ANY sizes
+include/hsefr.h; the single-frame call with the box logic on the device is such a pass of ONE frame), each frame's result bit for bit
+its single-frame result.  ``MTCNNDetector.detect_ragged`` runs frames of ANY sizes
 through one pass (include/hsefr_ragged.h, mtcnn_ragged.py: one list of (frame, level) items, one launch per P-Net layer), with the same
 bits; ``detect_batch(mixed_sizes=True)`` sends the frames that are alone in their size group through such passes.
 """
@@ -28,7 +29,7 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from . import _lib, ops, preprocess
+from . import _lib, mtcnn_ragged, ops, preprocess
 from .graphdef import Graph, GraphNode, read_graph
 from .mtcnn_ragged import DevicePlan, PackedFrames, RaggedMaps, RaggedPlan, frame_workspace_bytes, ragged_plan  # noqa: F401  (ragged_plan: part of this module's face)
 
@@ -429,7 +430,7 @@ class MTCNNDetector:
         self.ragged_passes = 0             # mixed-size passes detect_batch(mixed_sizes=True) ran, and the frames in them
         self.ragged_frames = 0
         self._ragged_plans: Dict[tuple, DevicePlan] = {}      # (shapes, minsize) -> the plan and its tables on the device
-        self._work = None                  # cap-sized work tensors of the device box logic, allocated once (_detect_device)
+        self._work = None                  # cap-sized work tensors of the device box logic, allocated once (_work_tensors)
         self.device = _lib.cuda_device(device)
         self.net = _DeviceNet(read_graph(mtcnn_pb or MTCNN_PB), self.device)
 
@@ -444,14 +445,7 @@ class MTCNNDetector:
         return self.net.run(['onet/conv6-2/conv6-2:0', 'onet/conv6-3/conv6-3:0', 'onet/prob1:0'], 'onet/input:0', img)
 
     def pyramid_scales(self, h: int, w: int) -> List[float]:
-        m = 12.0 / self.minsize
-        side = min(h, w) * m
-        scales, k = [], 0
-        while side >= 12:
-            scales.append(m * np.power(self.FACTOR, k))
-            side *= self.FACTOR
-            k += 1
-        return scales
+        return mtcnn_ragged.pyramid_scales(h, w, self.minsize, self.FACTOR)
 
     def _to_device(self, a: np.ndarray):
         return self._torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self.device)
@@ -469,17 +463,16 @@ class MTCNNDetector:
     def _stage1(self, img: np.ndarray, frame=None) -> np.ndarray:
         h, w = img.shape[:2]
         found = [np.empty((0, 9))]
-        scales = self.pyramid_scales(h, w)
+        sizes = mtcnn_ragged.level_sizes(h, w, self.minsize, self.FACTOR)
         maps = []
-        for scale in scales:                                         # launch every level first ...
-            hs, ws = int(np.ceil(h * scale)), int(np.ceil(w * scale))
+        for _, hs, ws in sizes:                                      # launch every level first ...
             if self.device_resize:
                 x = self._level_device(frame, h, w, hs, ws)
             else:
                 level = (preprocess.resize_area(img, ws, hs) - 127.5) * 0.0078125
                 x = self._to_device(np.transpose(level, (1, 0, 2))[None])           # nets see (W, H)
             maps.append(self.pnet(x))
-        for scale, (reg_t, prob_t) in zip(scales, maps):             # ... then read the maps back
+        for (scale, _, _), (reg_t, prob_t) in zip(sizes, maps):      # ... then read the maps back
             prob = prob_t[0, :, :, 1].cpu().numpy()                  # [W', H']
             reg = reg_t[0].cpu().numpy()                             # [W', H', 4]
             found.append(stage1_level(prob, reg, scale, self.THRESHOLDS[0]))
@@ -506,96 +499,34 @@ class MTCNNDetector:
         out = (out - 127.5) * 0.0078125
         return self._to_device(np.transpose(out, (0, 2, 1, 3)))      # [n, W, H, 3]
 
-    # ---- the cascade with its box logic on the device (csrc/mtcnn_post.hip) ------------------------------------------------
-    def _work_tensors(self, cap: int):
-        """The cap-sized lists of the device box logic, allocated once per detector and thread (work on one stream is ordered,
-        so a frame may overwrite what the previous frame of the same thread left)."""
+    # ---- the cascade with its box logic on the device, one frame or many per pass (csrc/mtcnn_post.hip, the *_batch entries) -------------
+    def _work_tensors(self, cap: int, n_frames: int):
+        """The [frames, cap, .] lists of the device box logic, allocated once per detector and thread and grown to the largest pass
+        seen (work on one stream is ordered, so a pass may overwrite what the previous pass of the same thread left; a pass takes the
+        first n_frames frames' rows, which are contiguous)."""
         import threading
         torch, dev = self._torch, self.device
         if self._work is None:
             self._work = threading.local()
         wk = self._work
-        if getattr(wk, "cap", None) != cap:
-            wk.cap = cap
-            wk.found = torch.empty((cap, 9), dtype=torch.float64, device=dev)
-            wk.boxes = [torch.empty((cap, 5), dtype=torch.float64, device=dev) for _ in range(3)]
-            wk.tab = torch.empty((cap, 8), dtype=torch.int32, device=dev)
-            wk.points = torch.empty((cap, 10), dtype=torch.float32, device=dev)
-        return wk
-
-    def _detect_device(self, img: np.ndarray, frame):
-        """Returns (boxes, points), or None when a candidate list overflowed the device capacity (caller falls back)."""
-        torch, L = self._torch, _lib.lib()
-        h, w = img.shape[:2]
-        cap = int(L.hsefr_mtcnn_post_capacity())
-        dev = self.device
-        with _lib.on_device(frame):
-            st = _lib.current_stream_ptr()
-            wk = self._work_tensors(cap)
-            counters = torch.zeros(8, dtype=torch.int32, device=dev)
-            found, (boxes1, boxes2, boxes3), tab, points3 = wk.found, wk.boxes, wk.tab, wk.points
-            thr = [float(np.float32(t)) for t in self.THRESHOLDS]
-            for scale in self.pyramid_scales(h, w):
-                hs, ws = int(np.ceil(h * scale)), int(np.ceil(w * scale))
-                reg_t, prob_t = self.pnet(self._level_device(frame, h, w, hs, ws))
-                reg_t, prob_t = reg_t.contiguous(), prob_t.contiguous()
-                _lib.check(L.hsefr_mtcnn_stage1_level(prob_t.data_ptr(), reg_t.data_ptr(), int(prob_t.shape[1]), int(prob_t.shape[2]),
-                                                      float(scale), thr[0], found.data_ptr(), counters.data_ptr(), st), "hsefr_mtcnn_stage1_level")
-            _lib.check(L.hsefr_mtcnn_stage1_finish(found.data_ptr(), counters.data_ptr(), boxes1.data_ptr(), tab.data_ptr(), w, h, st),
-                       "hsefr_mtcnn_stage1_finish")
-            c = counters.cpu().numpy()
-            if c[4]:
-                return None
-            n1 = int(c[1])
-            if n1 == 0:
-                return np.empty((0, 9)), np.array([])
-            crops = torch.empty((n1, 24, 24, 3), dtype=torch.float32, device=dev)
-            _lib.check(L.hsefr_mtcnn_crops(frame.data_ptr(), tab.data_ptr(), crops.data_ptr(), h, w, n1, 24, st), "hsefr_mtcnn_crops")
-            reg_t, prob_t = self.rnet(crops)
-            reg_t, prob_t = reg_t.contiguous(), prob_t.contiguous()
-            _lib.check(L.hsefr_mtcnn_stage_finish(2, boxes1.data_ptr(), n1, prob_t.data_ptr(), reg_t.data_ptr(), None, thr[1], boxes2.data_ptr(),
-                                                  tab.data_ptr(), None, counters.data_ptr(), w, h, st), "hsefr_mtcnn_stage_finish")
-            n2 = int(counters.cpu().numpy()[2])
-            if n2 == 0:
-                return np.empty((0, 5)), np.array([])
-            crops = torch.empty((n2, 48, 48, 3), dtype=torch.float32, device=dev)
-            _lib.check(L.hsefr_mtcnn_crops(frame.data_ptr(), tab.data_ptr(), crops.data_ptr(), h, w, n2, 48, st), "hsefr_mtcnn_crops")
-            reg_t, pts_t, prob_t = self.onet(crops)
-            reg_t, pts_t, prob_t = reg_t.contiguous(), pts_t.contiguous(), prob_t.contiguous()
-            _lib.check(L.hsefr_mtcnn_stage_finish(3, boxes2.data_ptr(), n2, prob_t.data_ptr(), reg_t.data_ptr(), pts_t.data_ptr(), thr[2],
-                                                  boxes3.data_ptr(), None, points3.data_ptr(), counters.data_ptr(), w, h, st), "hsefr_mtcnn_stage_finish")
-            n3 = int(counters.cpu().numpy()[3])
-            if n3 == 0:
-                return np.empty((0, 5)), np.empty((10, 0), np.float32)
-            return boxes3[:n3].cpu().numpy(), np.ascontiguousarray(points3[:n3].cpu().numpy().T)
-
-    # ---- many frames per pass (csrc/mtcnn_post.hip, the *_batch entries) -----------------------------------------------------------
-    def _batch_work_tensors(self, cap: int, n_frames: int):
-        """_work_tensors for a pass of n_frames frames: [frames, cap, .] lists per detector and thread, grown to the largest pass seen
-        (a pass takes the first n_frames frames' rows, which are contiguous)."""
-        import threading
-        torch, dev = self._torch, self.device
-        if self._work is None:
-            self._work = threading.local()
-        wk = self._work
-        if getattr(wk, "bcap", None) != cap or wk.bframes < n_frames:
-            wk.bcap, wk.bframes = cap, n_frames
-            wk.bfound = torch.empty((n_frames, cap, 9), dtype=torch.float64, device=dev)
-            wk.bboxes = [torch.empty((n_frames, cap, 5), dtype=torch.float64, device=dev) for _ in range(3)]
-            wk.btab = torch.empty((n_frames, cap, 8), dtype=torch.int32, device=dev)
-            wk.bpoints = torch.empty((n_frames, cap, 10), dtype=torch.float32, device=dev)
+        if getattr(wk, "cap", None) != cap or wk.frames < n_frames:
+            wk.cap, wk.frames = cap, n_frames
+            wk.found = torch.empty((n_frames, cap, 9), dtype=torch.float64, device=dev)
+            wk.boxes = [torch.empty((n_frames, cap, 5), dtype=torch.float64, device=dev) for _ in range(3)]
+            wk.tab = torch.empty((n_frames, cap, 8), dtype=torch.int32, device=dev)
+            wk.points = torch.empty((n_frames, cap, 10), dtype=torch.float32, device=dev)
         return wk
 
     def _detect_pass(self, imgs: List[np.ndarray], stack_out: Optional[list] = None) -> List[Optional[Tuple[np.ndarray, np.ndarray]]]:
-        """One pass over same-size frames: the launches of _detect_device, each covering every frame, and three read-backs.  Per
+        """One pass over same-size frames: the launches of the cascade, each covering every frame, and three read-backs.  Per
         frame (boxes, points), or None where that frame's candidate list overflowed (the caller redoes that frame alone).
         ``stack_out``: a list that receives the pass's uploaded frame stack (CUDA uint8 [frames, h, w, 3]), for a caller that cuts
-        the faces from it on the device.
+        the faces from it on the device.  The single-frame call is a pass of one (__call__).
 
-        Bit identity with _detect_device frame by frame: the pyramid, the crops and the box logic compute a frame's values from that
-        frame's data by the same operations (the kernels take the frame as a grid index); the nets run on the stacked levels and on
-        the concatenated crop lists, and conv2d_direct, maxpool_f32 and softmax (csrc/smallnet.hip) compute each output element from
-        its own image alone in a fixed FMA order, so a row's values do not depend on the batch it stands in
+        A frame's result does not depend on the pass it stands in: the pyramid, the crops and the box logic compute a frame's values
+        from that frame's data by the same operations (the kernels take the frame as a grid index); the nets run on the stacked levels
+        and on the concatenated crop lists, and conv2d_direct, maxpool_f32 and softmax (csrc/smallnet.hip) compute each output element
+        from its own image alone in a fixed FMA order, so a row's values do not depend on the batch it stands in
         (tests/test_mtcnn_batch_gpu.py checks both)."""
         stack = self._torch.from_numpy(np.stack(imgs)).to(self.device)     # one upload per pass
         if stack_out is not None:
@@ -620,8 +551,8 @@ class MTCNNDetector:
             return [empty_detection() for _ in range(int(stack.shape[0]))]
         return self._detect_stack_body(stack)
 
-    def _detect_stack_body(self, stack) -> List[Optional[Tuple[np.ndarray, np.ndarray]]]:
-        """_detect_pass behind its upload."""
+    def _detect_stack_body(self, stack, counts: Optional[list] = None) -> List[Optional[Tuple[np.ndarray, np.ndarray]]]:
+        """_detect_pass behind its upload (``counts``: see _finish_pass)."""
         torch, L = self._torch, _lib.lib()
         n_frames, h, w = int(stack.shape[0]), int(stack.shape[1]), int(stack.shape[2])
         cap = int(L.hsefr_mtcnn_post_capacity())
@@ -629,12 +560,11 @@ class MTCNNDetector:
         results: List[Optional[Tuple[np.ndarray, np.ndarray]]] = [empty_detection() for _ in range(n_frames)]
         with _lib.on_device(stack):
             st = _lib.current_stream_ptr()
-            wk = self._batch_work_tensors(cap, n_frames)
+            wk = self._work_tensors(cap, n_frames)
             counters = torch.zeros((n_frames, 8), dtype=torch.int32, device=dev)
-            found, boxes1, tab = wk.bfound, wk.bboxes[0], wk.btab
+            found, boxes1, tab = wk.found, wk.boxes[0], wk.tab
             thr = [float(np.float32(t)) for t in self.THRESHOLDS]
-            for scale in self.pyramid_scales(h, w):
-                hs, ws = int(np.ceil(h * scale)), int(np.ceil(w * scale))
+            for scale, hs, ws in mtcnn_ragged.level_sizes(h, w, self.minsize, self.FACTOR):
                 level = torch.empty((n_frames, ws, hs, 3), dtype=torch.float32, device=dev)
                 _lib.check(L.hsefr_mtcnn_pyramid_level_batch(stack.data_ptr(), level.data_ptr(), n_frames, h, w, hs, ws, st),
                            "hsefr_mtcnn_pyramid_level_batch")
@@ -653,17 +583,22 @@ class MTCNNDetector:
                                                  None if pts is None else pts.data_ptr(), t, b_out.data_ptr(), None if tab is None else tab.data_ptr(),
                                                  None if points is None else points.data_ptr(), counters.data_ptr(), n_frames, w, h, st),
                 "hsefr_mtcnn_stage_finish_batch")
-            return self._finish_pass(n_frames, counters, wk, results, crops_of, finish)
+            return self._finish_pass(n_frames, counters, wk, results, crops_of, finish, counts)
 
-    def _finish_pass(self, n_frames: int, counters, wk, results, crops_of, finish) -> List[Optional[Tuple[np.ndarray, np.ndarray]]]:
+    def _finish_pass(self, n_frames: int, counters, wk, results, crops_of, finish,
+                     counts: Optional[list] = None) -> List[Optional[Tuple[np.ndarray, np.ndarray]]]:
         """A pass behind its stage 1 (run under on_device): the three read-backs, R-Net and O-Net on the concatenated crop lists, the
         results per frame.  ``crops_of(tab, d_off, total, size, out)`` cuts the crops of all frames and ``finish(stage, boxes_in, d_off,
         total, prob, reg, pts, thr, boxes_out, tab, points)`` runs stage 2 / 3 of all frames: the same-size pass and the ragged pass
-        differ only in where those two read a frame's place and size."""
+        differ only in where those two read a frame's place and size.  ``counts``: a list that receives every read-back of the
+        counters, int32 [frames, 8] each (columns 1, 2, 3: the boxes stages 1, 2, 3 kept; a stage not reached has 0), for a caller
+        that has to know WHERE a frame's cascade emptied (__call__)."""
         torch, dev = self._torch, self.device
-        (boxes1, boxes2, boxes3), tab, points3 = wk.bboxes, wk.btab, wk.bpoints
+        (boxes1, boxes2, boxes3), tab, points3 = wk.boxes, wk.tab, wk.points
         thr = [float(np.float32(t)) for t in self.THRESHOLDS]
+        seen = [] if counts is None else counts
         c = counters.cpu().numpy()                                     # read-back 1
+        seen.append(c)
         over = c[:, 4] != 0                                            # (only a pyramid level can overflow: later lists are no longer)
         for b in np.nonzero(over)[0]:
             results[int(b)] = None
@@ -682,6 +617,7 @@ class MTCNNDetector:
         reg_t, prob_t = reg_t.contiguous(), prob_t.contiguous()
         finish(2, boxes1, d_off, total, prob_t, reg_t, None, thr[1], boxes2, tab, None)
         c = counters.cpu().numpy()                                     # read-back 2
+        seen.append(c)
         n2 = np.where(over, 0, c[:, 2])
         total, d_off = offsets_of(c[:, 2])
         if total == 0:
@@ -698,6 +634,7 @@ class MTCNNDetector:
         at_boxes = n_frames * 32
         at_points = at_boxes + n_frames * m * 40
         c = np.frombuffer(packed, np.int32, n_frames * 8, 0).reshape(n_frames, 8)
+        seen.append(c)
         boxes = np.frombuffer(packed, np.float64, n_frames * m * 5, at_boxes).reshape(n_frames, m, 5)
         points = np.frombuffer(packed, np.float32, n_frames * m * 10, at_points).reshape(n_frames, m, 10)
         for b in range(n_frames):
@@ -781,7 +718,7 @@ class MTCNNDetector:
                                % (cap, int(R.hsefr_ragged_capacity())))
         with _lib.on_device(packed):
             st = _lib.current_stream_ptr()
-            wk = self._batch_work_tensors(cap, n_frames)
+            wk = self._work_tensors(cap, n_frames)
             counters = torch.zeros((n_frames, 8), dtype=torch.int32, device=dev)
             levels = torch.empty(plan.pixels[0] * 3, dtype=torch.float32, device=dev)
             _lib.ragged_check(R.hsefr_ragged_pyramid(packed.data_ptr(), plan.frames_bytes, dplan.frames, n_frames, dplan.levels, plan.n_items,
@@ -789,8 +726,8 @@ class MTCNNDetector:
                                                      plan.level_lds, st), "hsefr_ragged_pyramid")
             reg_m, prob_m = self.pnet(RaggedMaps(dplan, 0, 3, levels))
             _lib.ragged_check(R.hsefr_ragged_stage1(prob_m.data.data_ptr(), reg_m.data.data_ptr(), plan.pixels[-1], dplan.frames, n_frames, dplan.cells,
-                                                    plan.n_items, float(np.float32(self.THRESHOLDS[0])), wk.bfound.data_ptr(), counters.data_ptr(),
-                                                    wk.bboxes[0].data_ptr(), wk.btab.data_ptr(), st), "hsefr_ragged_stage1")
+                                                    plan.n_items, float(np.float32(self.THRESHOLDS[0])), wk.found.data_ptr(), counters.data_ptr(),
+                                                    wk.boxes[0].data_ptr(), wk.tab.data_ptr(), st), "hsefr_ragged_stage1")
             crops_of = lambda tab, d_off, total, size, out: _lib.ragged_check(      # noqa: E731
                 R.hsefr_ragged_crops(packed.data_ptr(), plan.frames_bytes, dplan.frames, n_frames, tab.data_ptr(), d_off.data_ptr(), out.data_ptr(),
                                      cap, total, size, st), "hsefr_ragged_crops")
@@ -842,47 +779,36 @@ class MTCNNDetector:
             return (alone, sources) if return_stacks else alone
         results: List[Optional[Tuple[np.ndarray, np.ndarray]]] = [None] * len(imgs)
         for hw, idx in passes:
+            group = [imgs[i] for i in idx]
+            kept: list = []                                                # receives the pass's frames on the device where the caller asked for them
             if hw is None:                                                 # frames of different sizes: one ragged pass
                 self.ragged_passes += 1
                 self.ragged_frames += len(idx)
-                kept = [] if return_stacks and packed_sources else None
-                for row, (i, res) in enumerate(zip(idx, self.detect_ragged([imgs[i] for i in idx], kept))):
-                    results[i] = res if res is not None else self._alone(imgs[i])
-                    if res is not None and kept:
-                        sources[i] = (kept[0], row)
-                continue
-            h, w = hw
-            if not self.pyramid_scales(h, w):                              # smaller than minsize: no level, no launch
-                for i in idx:
-                    results[i] = empty_detection()
-                continue
-            if len(idx) == 1:                                              # nothing to share: the single-frame call, without the stacking
-                results[idx[0]] = self._alone(imgs[idx[0]])
-                continue
-            kept: list = []
-            group = [imgs[i] for i in idx]
-            for row, (i, res) in enumerate(zip(idx, self._detect_pass(group, kept) if return_stacks else self._detect_pass(group))):
-                if res is not None:
-                    results[i] = res
-                    if return_stacks:
-                        sources[i] = (kept[0], row)
-                else:
-                    results[i] = self._alone(imgs[i])
+                got = self.detect_ragged(group, kept if return_stacks and packed_sources else None)
+            elif not self.pyramid_scales(*hw):                             # smaller than minsize: no level, no launch
+                got = [empty_detection() for _ in idx]
+            elif len(idx) == 1:                                            # nothing to share: the single-frame call, without the stacking
+                got = [self._alone(group[0])]
+            else:
+                got = self._detect_pass(group, kept) if return_stacks else self._detect_pass(group)
+            for row, (i, res) in enumerate(zip(idx, got)):
+                results[i] = res if res is not None else self._alone(imgs[i])       # an overflowed frame is redone alone
+                if res is not None and kept:
+                    sources[i] = (kept[0], row)
         return (results, sources) if return_stacks else results
 
     def __call__(self, img: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
-        img = np.asarray(img)
-        if img.ndim != 3 or img.shape[2] != 3:
-            raise ValueError("the detector takes an RGB frame [H, W, 3]")
+        img = self._check_frame(img)   # (the device resampler is OpenCV's 8-bit path; float frames: MTCNNDetector(device_resize=False))
         frame = None
         if self.device_resize:
-            if img.dtype != np.uint8:      # the device resampler is OpenCV's 8-bit path; float frames: MTCNNDetector(device_resize=False)
-                raise ValueError("device_resize takes a uint8 RGB frame [H, W, 3]; construct the detector with device_resize=False "
-                                 "for %s frames" % img.dtype)
             frame = self._torch.from_numpy(np.ascontiguousarray(img)).to(self.device)     # local: no per-frame detector state
-        if self.device_boxes:
-            res = self._detect_device(img, frame)
+        if self.device_boxes:              # a pass of one frame (frame[None]: a contiguous view)
+            counts: list = []
+            res = self._detect_stack_body(frame[None], counts)[0]
             if res is not None:
+                n1, n2 = (int(n) for n in counts[-1][0, 1:3])
+                if n1 == 0 or n2 == 0:     # this call's own empty results where stage 1 or 2 kept nothing (stage 3: empty_detection())
+                    return np.empty((0, 9) if n1 == 0 else (0, 5)), np.array([])
                 return res
             self.host_fallbacks += 1
         points = np.array([])

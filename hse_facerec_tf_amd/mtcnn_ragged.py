@@ -40,7 +40,8 @@ def conv_co(cout: int) -> int:
 
 
 def pyramid_scales(h: int, w: int, minsize: int, factor: float) -> List[float]:
-    """MTCNNDetector.pyramid_scales as a function of the detector's two constants (the same operations: the scales are its floats)."""
+    """The scales of a frame's image pyramid (facial_analysis.py:489-499) as a function of the detector's two constants:
+    MTCNNDetector.pyramid_scales is this."""
     m = 12.0 / minsize
     side = min(h, w) * m
     scales, k = [], 0
@@ -52,7 +53,7 @@ def pyramid_scales(h: int, w: int, minsize: int, factor: float) -> List[float]:
 
 
 def level_sizes(h: int, w: int, minsize: int, factor: float) -> List[Tuple[float, int, int]]:
-    """[(scale, hs, ws)] of a frame's pyramid: the level sizes of MTCNNDetector._detect_device."""
+    """[(scale, hs, ws)] of a frame's pyramid: the level sizes every MTCNNDetector path resamples to."""
     return [(s, int(np.ceil(h * s)), int(np.ceil(w * s))) for s in pyramid_scales(h, w, minsize, factor)]
 
 

@@ -329,3 +329,13 @@ def face_crops_packed(packed, shapes, boxes, out_hw: Tuple[int, int], out=None, 
                                                                   rows.ctypes.data, m, out.data_ptr(), oh, ow, _lib.current_stream_ptr()),
                          "hsefr_mixed_face_crops")
     return out
+
+
+def face_crops_from(source, boxes, out_hw: Tuple[int, int], out=None):
+    """The faces of one detector pass cut from whatever that pass left on the device: face_crops for a CUDA uint8 [n, h, w, 3] stack
+    (a same-size pass), face_crops_packed for a mtcnn_ragged.PackedFrames (a mixed-size pass).  ``boxes``, ``out_hw`` and ``out`` as both
+    take them."""
+    from .mtcnn_ragged import PackedFrames
+    if isinstance(source, PackedFrames):
+        return face_crops_packed(source.data, source.shapes, boxes, out_hw, out=out)
+    return face_crops(source, boxes, out_hw, out=out)

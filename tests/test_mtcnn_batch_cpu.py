@@ -119,3 +119,33 @@ def test_argument_errors_come_before_any_pass():
             det.detect_batch(bad, **kw)
     assert det.passes == [] and det.alone == []
     assert det.detect_batch([]) == []
+
+
+def test_an_overflowed_pass_of_one_falls_back_to_the_host_cascade():
+    """The single-frame call is a pass of one frame: where that pass reports an overflow (None), __call__ counts a host fallback and
+    runs the host cascade on the same upload.  Faked one level below FakeDetector: the pass body and the host stage 1."""
+    import torch
+
+    class Overflowing(MTCNNDetector):
+        def __init__(self):
+            self.minsize, self.device_resize, self.device_boxes, self.host_fallbacks = 32, True, True, 0
+            self._torch, self.device = torch, torch.device("cpu")
+            self.passes, self.host = [], []
+
+        def _detect_stack_body(self, stack, counts=None):
+            self.passes.append(tuple(stack.shape))
+            return [None]
+
+        def _stage1(self, img, frame=None):
+            self.host.append((img.shape, tuple(frame.shape)))
+            return np.empty((0, 9))                                        # the host cascade ends here: no candidates
+
+    det = Overflowing()
+    boxes, points = det(frame(7))
+    assert det.passes == [(1, 64, 48, 3)] and det.host == [((64, 48, 3), (64, 48, 3))] and det.host_fallbacks == 1
+    assert boxes.shape == (0, 9) and points.shape == (0,)
+    det(frame(8, 40, 90))
+    assert det.passes[1:] == [(1, 40, 90, 3)] and len(det.host) == 2 and det.host_fallbacks == 2
+    with pytest.raises(ValueError):                                        # the frame check comes before the pass
+        det(frame(1).astype(np.float32))
+    assert len(det.passes) == 2

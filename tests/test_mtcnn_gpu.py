@@ -218,3 +218,39 @@ def test_device_box_logic_is_the_host_box_logic():
     assert total >= 8 and dev.host_fallbacks == 0
     with pytest.raises(ValueError):
         MTCNNDetector(minsize=32, device_resize=False, device_boxes=True)
+
+
+def keep_nothing(net):
+    """``net`` with the face probability of its last output set to 0 (channel 1; channel 0 is 1): its stage keeps no box."""
+    def wrapped(x):
+        outs = list(net(x))
+        prob = outs[-1].clone()
+        prob[..., 1] = 0.0
+        prob[..., 0] = 1.0
+        outs[-1] = prob
+        return outs
+    return wrapped
+
+
+def test_the_single_frame_call_keeps_its_empty_results_stage_by_stage():
+    """What ``det(frame)`` returns when the cascade empties at stage 1, 2 or 3: the shapes and dtypes callers of the single-frame call
+    have always seen (they differ from detect_batch's empty_detection()), from the device cascade itself, not the host fallback."""
+    from hse_facerec_tf_amd import preprocess
+    from hse_facerec_tf_amd.mtcnn import MTCNNDetector
+    img = preprocess.imread_rgb(TEST_IMAGE)
+    det = MTCNNDetector(minsize=32)
+    assert det(img)[0].shape == (4, 5)                                     # unwrapped, every stage keeps boxes on this photo
+    want = {"pnet": ((0, 9), np.float64, (0,), np.float64),
+            "rnet": ((0, 5), np.float64, (0,), np.float64),
+            "onet": ((0, 5), np.float64, (10, 0), np.float32)}
+    for name, (bshape, bdtype, pshape, pdtype) in want.items():
+        setattr(det, name, keep_nothing(getattr(det, name)))               # an instance attribute over the class's method
+        try:
+            boxes, points = det(img)
+        finally:
+            delattr(det, name)
+        assert isinstance(boxes, np.ndarray) and isinstance(points, np.ndarray), name
+        assert (boxes.shape, boxes.dtype, points.shape, points.dtype) == (bshape, bdtype, pshape, pdtype), name
+    boxes, points = det(np.zeros((20, 500, 3), np.uint8))                  # no pyramid level: the stage-1 row
+    assert (boxes.shape, boxes.dtype, points.shape, points.dtype) == want["pnet"]
+    assert det(img)[0].shape == (4, 5) and det.host_fallbacks == 0

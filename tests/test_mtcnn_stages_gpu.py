@@ -1,5 +1,5 @@
 """GPU suite: the four kernels of csrc/mtcnn_post.hip the detector runs (stage1_level, stage1_finish, stage23_finish<2>,
-stage23_finish<3>), called through _lib exactly as MTCNNDetector._detect_device calls them, one stage at a time, against the
+stage23_finish<3>), called through _lib's single-frame entries (the detector's pass launches the same kernels per frame), one stage at a time, against the
 oracle's stage functions (oracle.mtcnn) on every case of tests/mtcnn_stage_cases.py at the library's own capacity.
 
 Exact: counts, float64 boxes, int32 crop rows, float32 landmark bits.  Every call runs twice on fresh buffers (candidates are
